@@ -8,11 +8,15 @@ Workload (BASELINE.json metric / configs[1]): the reference's scenes/test_scene_
 N > 1 is STRONG scaling of that same run: the image rows are dealt to the ranks in interleaved 16-row strips, every
 rank traces its 1/N of the 268.4 M camera samples with a full scene replica and DMAs its rows straight into one
 shared-memory film (no data-path collective).  `value` = 268.4 M samples x steps / max-over-ranks wall time.
-Secondary entries of the same line (their own short timed regions, outside `value`): the weak-scaling figure
-(spp = 256 N, the same work per GPU as at N = 1) and BASELINE configs[2] (4096x4096 @ 1024 spp over N ranks); at
-N = 1 also `other_configs` (configs[3] and one GPU's share of configs[4]) and `parity` against the CPU oracle.
 
-Launch: `python bench.py --gpus N --steps K --warmup W`.  For N > 1 the parent process only spawns
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds what takes runs of its own, all
+outside `value`: per-kernel HIP-event times and the `roofline` block (from untimed steps after the timed region), the
+secondary entries (the weak-scaling figure - spp = 256 N, the same work per GPU as at N = 1 - and BASELINE configs[2],
+4096x4096 @ 1024 spp over N ranks) and, at N = 1, `cpu_baseline` and `parity` against the CPU oracle and
+`other_configs` (configs[3] and one GPU's share of configs[4]).  `--dump-outputs DIR` writes the film of the last timed
+step as DIR/film.npy (float32; a seeded sample of its pixels when the image is larger than 64 MB).
+
+Launch: `python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]`.  For N > 1 the parent process only spawns
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...`
 BEFORE anything touches the GPU and relays its output; launching it under torch.distributed.run directly (RANK /
 WORLD_SIZE set) works too.  PyTorch is only the barrier / synchronize / max-reduce plumbing.
@@ -156,6 +160,26 @@ def film_parity(spt, got, ref):
             "u8_pixels_differ_gt1": int((np.abs(u8g - u8r) > 1).any(axis=2).sum())}
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_PIXELS = 1 << 20
+
+
+def dump_outputs(out_dir, film):
+    """--dump-outputs: the (height, width, 3) f32 film the timed path delivered in its last step, as DIR/film.npy.  An image
+    over DUMP_MAX_BYTES is written as a sample instead: DUMP_SAMPLE_PIXELS pixels drawn with a fixed seed (the same pixels
+    for the same --width / --height), their values as film_sample.npy (n, 3) f32 and their row-major indices as
+    film_sample_pixels.npy (n,) f64."""
+    os.makedirs(out_dir, exist_ok=True)
+    film = np.ascontiguousarray(film, dtype=np.float32)
+    if film.nbytes <= DUMP_MAX_BYTES:
+        np.save(os.path.join(out_dir, "film.npy"), film)
+        return
+    pixels = film.reshape(-1, 3)
+    idx = np.sort(np.random.default_rng(0).choice(len(pixels), DUMP_SAMPLE_PIXELS, replace=False))
+    np.save(os.path.join(out_dir, "film_sample.npy"), pixels[idx])
+    np.save(os.path.join(out_dir, "film_sample_pixels.npy"), idx.astype(np.float64))
+
+
 def free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -186,9 +210,14 @@ def main():
     ap.add_argument("--renderer", default=os.path.join(ROOT, "scenes_amd", "pt.json"))
     ap.add_argument("--samples-per-pass", type=int, default=0)
     ap.add_argument("--sync-steps", action="store_true", help="timed steps wait for their film one by one (no copy / compute overlap between steps)")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the oracle legs (cpu_baseline and parity)")
-    ap.add_argument("--no-profile", action="store_true", help="do not time kernel classes with HIP events")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary entries (weak scaling, configs[2], other_configs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: per-kernel HIP-event times and the roofline, "
+                         "the secondary entries (weak scaling, configs[2]), cpu_baseline / parity against the CPU oracle, other_configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the film of the last timed step to DIR/film.npy (float32; a seeded sample of its pixels above 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the oracle legs (cpu_baseline and parity)")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: do not time kernel classes with HIP events")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary entries (weak scaling, configs[2], other_configs)")
     ap.add_argument("--profile-steps", type=int, default=3)
     ap.add_argument("--backend", default="gloo",
                     help="torch.distributed backend of the control plane (N > 1): two barriers and one max-reduce of a double per "
@@ -265,20 +294,22 @@ def main():
             films[(h, w)] = f
         return films[(h, w)]
 
-    def timed(renderer, sc, cfg, steps, warmup, profile_steps=0):
+    def timed(renderer, sc, cfg, steps, warmup, profile_steps=0, keep_film=False):
         """`steps` renders of this rank's shard of `cfg`, bracketed by barrier + synchronize on both sides, max over ranks.
-        Returns (seconds, last stats, per-class kernel ms, per-class launches) - the kernel times come from separate,
-        untimed steps right after the timed region (an event pair around every launch costs ~7 % of a step)."""
+        Returns (seconds, last stats, per-class kernel ms, per-class launches, film) - the kernel times come from separate,
+        untimed steps right after the timed region (an event pair around every launch costs ~7 % of a step); `film` is a
+        copy of the whole image the last timed step delivered (keep_film, rank 0; else None)."""
         film = shared_film(cfg.height, cfg.width)
         kernel_ms = np.zeros(spt.N_KERNELS)
         kernel_launches = np.zeros(spt.N_KERNELS, dtype=np.int64)
+        last = [None]
 
         def step(profiled, wait=True):
             # N > 1: this rank's strips are DMA-ed straight into the node's shared-memory film (no collective, no host-side
             # scatter); N = 1: the pinned shard buffer is the image
-            renderer.render_shard(sc, cfg, device=local_rank, shard_index=rank, shard_count=world, strip_rows=strip_rows,
-                                  samples_per_pass=args.samples_per_pass, profile=profiled, reuse_output=True,
-                                  film=film.film if film is not None else None, wait=wait)
+            last[0] = renderer.render_shard(sc, cfg, device=local_rank, shard_index=rank, shard_count=world, strip_rows=strip_rows,
+                                            samples_per_pass=args.samples_per_pass, profile=profiled, reuse_output=True,
+                                            film=film.film if film is not None else None, wait=wait)
             st = renderer.last_stats
             if profiled:
                 for k in range(spt.N_KERNELS):
@@ -298,6 +329,8 @@ def main():
         renderer.wait(sc, device=local_rank)
         barrier()
         dt = time.perf_counter() - t0
+        # (every rank's rows have arrived: the pinned buffer at N = 1, the shared film at N > 1; later steps overwrite it)
+        kept = np.array(last[0]) if keep_film and rank == 0 else None
         if st is None:
             st = step(False)      # --warmup 0: the counters from one untimed step
         for _ in range(profile_steps):
@@ -308,23 +341,26 @@ def main():
             tt = torch.tensor([dt], dtype=torch.float64)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
-        return dt, st, kernel_ms, kernel_launches
+        return dt, st, kernel_ms, kernel_launches, kept
 
     # ---- the metric's run: 1024 x 1024 @ 256 spp over `world` ranks (strong scaling) ----------------------------------
     renderer = spt.load_renderer(args.renderer, seed=1)
     renderer.spp = args.spp
     cfg = spt.OutputConfig(args.width, args.height)
-    n_prof = 0 if args.no_profile else max(args.profile_steps, 1)
-    dt, stats_last, kernel_ms, kernel_launches = timed(renderer, scene, cfg, args.steps, args.warmup, n_prof)
+    n_prof = max(args.profile_steps, 1) if args.full and not args.no_profile else 0
+    dt, stats_last, kernel_ms, kernel_launches, last_film = timed(renderer, scene, cfg, args.steps, args.warmup, n_prof,
+                                                                  keep_film=args.dump_outputs is not None)
+    if last_film is not None:
+        dump_outputs(args.dump_outputs, last_film)
 
-    # ---- secondary entries: their own timed regions, never part of `value` -------------------------------------------
+    # ---- secondary entries (--full): their own timed regions, never part of `value` ----------------------------------
     secondary = {}
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         if world > 1:
             weak = spt.load_renderer(args.renderer, seed=1)
             weak.spp = args.spp * world
             k = max(3, min(args.steps, 40))
-            wdt, _, _, _ = timed(weak, scene, cfg, k, 1)
+            wdt, _, _, _, _ = timed(weak, scene, cfg, k, 1)
             secondary["weak_scaling"] = {
                 "workload": "%dx%d @ %d spp (= %d spp per GPU-share: the N = 1 work on every GPU)" % (args.width, args.height, weak.spp, args.spp),
                 "value": round(args.width * args.height * weak.spp * k / wdt / 1e6, 2), "unit": "Msamples/s", "steps": k,
@@ -333,7 +369,7 @@ def main():
         big.spp = 1024
         bcfg = spt.OutputConfig(4096, 4096)
         k = 3 if world > 1 else 2
-        bdt, _, _, _ = timed(big, scene, bcfg, k, 1)
+        bdt, _, _, _, _ = timed(big, scene, bcfg, k, 1)
         secondary["configs2_cube_4096x4096_1024spp"] = {
             "workload": "BASELINE configs[2]: the same scene at 4096x4096 @ 1024 spp, rows dealt to %d rank(s)" % world,
             "value": round(4096 * 4096 * 1024 * k / bdt / 1e6, 2), "unit": "Msamples/s", "steps": k, "ms_per_step": round(bdt / k * 1e3, 2)}
@@ -343,82 +379,84 @@ def main():
         ms_per_step = dt / args.steps * 1e3
         value = samples_per_step * args.steps / dt / 1e6
         st = stats_last                                              # rank 0's shard, one step
-        n_launch = np.maximum(kernel_launches, 1)
         smp, seg_c, seg_s = st.samples, st.segments_closest, st.segments_shadow
         ext, hits0, verts = seg_c - smp, st.primary_hits, st.path_vertices
-        n_pix = len(spt.shard_rows(args.height, 0, world, strip_rows)) * args.width
-        passes = max(int(kernel_launches[0]) // max(n_prof, 1), 1)
-        RNAME = {"shade_first": "k_shade"}                           # kernel symbol behind a class name
-        # ALGORITHMIC bytes each kernel class moves per step (DESIGN.md "Kernels and rooflines"):
-        # queue records written/read once + radiance-slot / film read-modify-writes; scene geometry of
-        # this workload (< 2 KB) is LDS-resident and counted as 0 ("count it once").
-        # fused bounces (LDS-resident scenes): shade traces its own shadow / extension rays, so the shadow and
-        # path-to-extend records do not exist; it reads the vertices, writes the next bounce's vertices and
-        # read-modify-writes one radiance slot per (unoccluded) shadow ray
-        fused = int(kernel_launches[2]) == 0 and int(kernel_launches[3]) == 0
-        seg_s0, verts1 = st.shadow_first, st.vertices_second        # bounce 0: shadow rays issued, vertices kept for bounce 1
-        later = verts - hits0                                        # path vertices of bounces >= 1
-        live = st.live_samples
-        alg = {
-            # chunked (sample chunks per tile): a hit writes its compact record, a black sample writes nothing; one mask byte per 8
-            # samples of a live pixel says which samples own a radiance slot.  un-chunked: hit records + film read / write
-            "primary": (hits0 * (S_PATH0 + S_HIT) + live // 8) if live else
-                       hits0 * (S_PATH0 + S_HIT) + passes * n_pix * 2 * S_RAD,
-            # bounce-0 shade launches (one per pass): read the compact hit records, WRITE the sample's radiance slot once (the first
-            # contributions are summed in registers), (fused) write the kept bounce-1 vertices, (un-fused) shadow + path records
-            "shade_first": (hits0 * (S_PATH0 + S_HIT + S_RAD) + verts1 * (S_PATH + S_HIT)) if fused else
-                           hits0 * (S_PATH0 + S_HIT + S_RAD) + seg_s0 * S_SHADOW + min(ext, hits0) * S_PATH,
-            "shade": (later * (S_PATH + S_HIT) + (later - verts1) * (S_PATH + S_HIT) + (seg_s - seg_s0) * 2 * S_RAD) if fused else
-                     later * (S_PATH + S_HIT) + (seg_s - seg_s0) * S_SHADOW + max(ext - hits0, 0) * S_PATH,
-            "shadow": seg_s * (S_SHADOW + 2 * S_RAD),
-            # the extend stage reads the ray of a path record and leaves a hit + the record's index (no copy of the record)
-            "extend": ext * S_RAY + (verts - hits0) * S_HIT,
-            # chunked passes (k_resolve_bits): every slot of a live pixel is read (marked or not), its mask byte per 8 samples, the 4-byte
-            # first_slot word of every pixel and the film read + write of the live pixels; plus k_finish's film read + image write
-            "resolve": (live * S_RAD + live // 8 + passes * (n_pix * 4 + (live // max(renderer.spp, 1)) * 2 * S_RAD) + n_pix * 2 * S_RAD) if live else
-                       hits0 * S_RAD + passes * n_pix * 2 * S_RAD,
-        }
-        kern = {}
-        for k in (0, 6, 1, 2, 3, 4):
-            name = spt.KERNEL_NAMES[k]
-            if kernel_launches[k] == 0:
-                continue
-            total_ms = float(kernel_ms[k]) / n_prof                 # per step
-            launches = int(kernel_launches[k]) // n_prof
-            gbs = alg[name] / (total_ms * 1e-3) / 1e9 if total_ms > 0 else 0.0
-            kern[name] = {"launches_per_step": launches, "avg_launch_ms": round(total_ms / launches, 4),
-                          "ms_per_step": round(total_ms, 3), "alg_MB_per_launch": round(alg[name] / launches / 1e6, 3),
-                          "GBps": round(gbs, 1), "frac": round(gbs / HBM_PEAK_GBS, 4)}
-        dom_name = max(kern, key=lambda n: kern[n]["ms_per_step"]) if kern else "primary"
-        dom = kern.get(dom_name, {"GBps": 0.0, "frac": 0.0, "avg_launch_ms": None, "alg_MB_per_launch": None})
-        pipeline_bytes = sum(alg[n] for n in kern)                     # only the kernel classes that ran (fused: no shadow / extend)
-        # HBM bytes per launch from the PMC counters (FETCH_SIZE x2 on gfx950 + WRITE_SIZE), collected in a
-        # separate rocprofv3 --pmc run of this same command and committed under profiles/ (tools/pmc_traffic.py)
-        traffic, traffic_file = None, None
-        for cand in ("r03_traffic_bench.json", "r02_traffic_bench.json", "r01_traffic_bench.json"):
-            if os.path.exists(os.path.join(ROOT, "profiles", cand)):
-                traffic_file = cand
-                break
-        if traffic_file and world == 1 and args.samples_per_pass == 0 and args.spp == 256:
-            tk = json.load(open(os.path.join(ROOT, "profiles", traffic_file)))["kernels"].get("k_" + dom_name)   # "k_shade_first": bounce-0 instances
-            # (the PMC run renders the step a few times: its launch count is a multiple of the step's when the pass layout is the same)
-            if tk and dom.get("launches_per_step") and tk["launches"] % dom["launches_per_step"] == 0:
-                traffic = round(tk["hbm_bytes_per_launch"] / 1e6, 3)
-        roofline = {
-            "bound": "hbm", "kernel": RNAME.get(dom_name, "k_" + dom_name) + (" (bounce 0)" if dom_name == "shade_first" else ""), "achieved": dom["GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": dom["frac"], "traffic": traffic, "traffic_unit": "MB per launch (PMC, profiles/%s)" % traffic_file,
-            "avg_launch_ms": dom["avg_launch_ms"], "alg_MB_per_launch": dom["alg_MB_per_launch"],
-            # `bound` keeps the vocabulary of the bench contract (hbm | mfma: achieved / peak / frac above are the HBM figures of the
-            # dominant kernel); what actually limits the kernel is named here and priced in `valu`
-            "limited_by": "valu-issue",
-            "limiter": "VALU instruction issue, not HBM: the scene is LDS-resident and a missing ray touches no memory at all (DESIGN.md section 6)",
-            "valu": valu_block(dom_name, {"primary": r"k_primary<true, true, false, true>", "shade_first": r"k_shade<0, true, true"}.get(dom_name, "k_" + dom_name),
-                               dom.get("avg_launch_ms"), dom.get("launches_per_step"), world, args.samples_per_pass == 0 and args.spp == 256),
-            "kernels": kern,
-            "pipeline": {"alg_bytes_per_sample": round(pipeline_bytes / max(smp, 1), 2),
-                         "GBps_at_value": round(pipeline_bytes / max(smp, 1) * value * 1e6 / world / 1e9, 1)},
-            "note": "HIP-event kernel times from %d untimed steps after the timed region (rank 0's shard)" % n_prof,
-        }
+        roofline = None
+        if args.full:   # per-kernel figures: HIP-event times of the untimed profiled steps
+            n_launch = np.maximum(kernel_launches, 1)
+            n_pix = len(spt.shard_rows(args.height, 0, world, strip_rows)) * args.width
+            passes = max(int(kernel_launches[0]) // max(n_prof, 1), 1)
+            RNAME = {"shade_first": "k_shade"}                           # kernel symbol behind a class name
+            # ALGORITHMIC bytes each kernel class moves per step (DESIGN.md "Kernels and rooflines"):
+            # queue records written/read once + radiance-slot / film read-modify-writes; scene geometry of
+            # this workload (< 2 KB) is LDS-resident and counted as 0 ("count it once").
+            # fused bounces (LDS-resident scenes): shade traces its own shadow / extension rays, so the shadow and
+            # path-to-extend records do not exist; it reads the vertices, writes the next bounce's vertices and
+            # read-modify-writes one radiance slot per (unoccluded) shadow ray
+            fused = int(kernel_launches[2]) == 0 and int(kernel_launches[3]) == 0
+            seg_s0, verts1 = st.shadow_first, st.vertices_second        # bounce 0: shadow rays issued, vertices kept for bounce 1
+            later = verts - hits0                                        # path vertices of bounces >= 1
+            live = st.live_samples
+            alg = {
+                # chunked (sample chunks per tile): a hit writes its compact record, a black sample writes nothing; one mask byte per 8
+                # samples of a live pixel says which samples own a radiance slot.  un-chunked: hit records + film read / write
+                "primary": (hits0 * (S_PATH0 + S_HIT) + live // 8) if live else
+                           hits0 * (S_PATH0 + S_HIT) + passes * n_pix * 2 * S_RAD,
+                # bounce-0 shade launches (one per pass): read the compact hit records, WRITE the sample's radiance slot once (the first
+                # contributions are summed in registers), (fused) write the kept bounce-1 vertices, (un-fused) shadow + path records
+                "shade_first": (hits0 * (S_PATH0 + S_HIT + S_RAD) + verts1 * (S_PATH + S_HIT)) if fused else
+                               hits0 * (S_PATH0 + S_HIT + S_RAD) + seg_s0 * S_SHADOW + min(ext, hits0) * S_PATH,
+                "shade": (later * (S_PATH + S_HIT) + (later - verts1) * (S_PATH + S_HIT) + (seg_s - seg_s0) * 2 * S_RAD) if fused else
+                         later * (S_PATH + S_HIT) + (seg_s - seg_s0) * S_SHADOW + max(ext - hits0, 0) * S_PATH,
+                "shadow": seg_s * (S_SHADOW + 2 * S_RAD),
+                # the extend stage reads the ray of a path record and leaves a hit + the record's index (no copy of the record)
+                "extend": ext * S_RAY + (verts - hits0) * S_HIT,
+                # chunked passes (k_resolve_bits): every slot of a live pixel is read (marked or not), its mask byte per 8 samples, the 4-byte
+                # first_slot word of every pixel and the film read + write of the live pixels; plus k_finish's film read + image write
+                "resolve": (live * S_RAD + live // 8 + passes * (n_pix * 4 + (live // max(renderer.spp, 1)) * 2 * S_RAD) + n_pix * 2 * S_RAD) if live else
+                           hits0 * S_RAD + passes * n_pix * 2 * S_RAD,
+            }
+            kern = {}
+            for k in (0, 6, 1, 2, 3, 4):
+                name = spt.KERNEL_NAMES[k]
+                if kernel_launches[k] == 0:
+                    continue
+                total_ms = float(kernel_ms[k]) / n_prof                 # per step
+                launches = int(kernel_launches[k]) // n_prof
+                gbs = alg[name] / (total_ms * 1e-3) / 1e9 if total_ms > 0 else 0.0
+                kern[name] = {"launches_per_step": launches, "avg_launch_ms": round(total_ms / launches, 4),
+                              "ms_per_step": round(total_ms, 3), "alg_MB_per_launch": round(alg[name] / launches / 1e6, 3),
+                              "GBps": round(gbs, 1), "frac": round(gbs / HBM_PEAK_GBS, 4)}
+            dom_name = max(kern, key=lambda n: kern[n]["ms_per_step"]) if kern else "primary"
+            dom = kern.get(dom_name, {"GBps": 0.0, "frac": 0.0, "avg_launch_ms": None, "alg_MB_per_launch": None})
+            pipeline_bytes = sum(alg[n] for n in kern)                     # only the kernel classes that ran (fused: no shadow / extend)
+            # HBM bytes per launch from the PMC counters (FETCH_SIZE x2 on gfx950 + WRITE_SIZE), collected in a
+            # separate rocprofv3 --pmc run of this same command and committed under profiles/ (tools/pmc_traffic.py)
+            traffic, traffic_file = None, None
+            for cand in ("r03_traffic_bench.json", "r02_traffic_bench.json", "r01_traffic_bench.json"):
+                if os.path.exists(os.path.join(ROOT, "profiles", cand)):
+                    traffic_file = cand
+                    break
+            if traffic_file and world == 1 and args.samples_per_pass == 0 and args.spp == 256:
+                tk = json.load(open(os.path.join(ROOT, "profiles", traffic_file)))["kernels"].get("k_" + dom_name)   # "k_shade_first": bounce-0 instances
+                # (the PMC run renders the step a few times: its launch count is a multiple of the step's when the pass layout is the same)
+                if tk and dom.get("launches_per_step") and tk["launches"] % dom["launches_per_step"] == 0:
+                    traffic = round(tk["hbm_bytes_per_launch"] / 1e6, 3)
+            roofline = {
+                "bound": "hbm", "kernel": RNAME.get(dom_name, "k_" + dom_name) + (" (bounce 0)" if dom_name == "shade_first" else ""), "achieved": dom["GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": dom["frac"], "traffic": traffic, "traffic_unit": "MB per launch (PMC, profiles/%s)" % traffic_file,
+                "avg_launch_ms": dom["avg_launch_ms"], "alg_MB_per_launch": dom["alg_MB_per_launch"],
+                # `bound` keeps the vocabulary of the bench contract (hbm | mfma: achieved / peak / frac above are the HBM figures of the
+                # dominant kernel); what actually limits the kernel is named here and priced in `valu`
+                "limited_by": "valu-issue",
+                "limiter": "VALU instruction issue, not HBM: the scene is LDS-resident and a missing ray touches no memory at all (DESIGN.md section 6)",
+                "valu": valu_block(dom_name, {"primary": r"k_primary<true, true, false, true>", "shade_first": r"k_shade<0, true, true"}.get(dom_name, "k_" + dom_name),
+                                   dom.get("avg_launch_ms"), dom.get("launches_per_step"), world, args.samples_per_pass == 0 and args.spp == 256),
+                "kernels": kern,
+                "pipeline": {"alg_bytes_per_sample": round(pipeline_bytes / max(smp, 1), 2),
+                             "GBps_at_value": round(pipeline_bytes / max(smp, 1) * value * 1e6 / world / 1e9, 1)},
+                "note": "HIP-event kernel times from %d untimed steps after the timed region (rank 0's shard)" % n_prof,
+            }
         out = {
             "metric": "Msamples/sec (whole node) at 1024x1024/256spp; per-pixel mean L1 vs CPU ref",
             "value": round(value, 2), "unit": "Msamples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -439,11 +477,12 @@ def main():
                        "primary_hit_fraction": round(hits0 / max(smp, 1), 4),
                        "what_bounds_large_N": "a rank's share is 1/N of ~4.1 ms of kernels; the per-step fixed cost (counter memset, ~10 "
                                               "launches of ~5 us, strided D2H of the rank's rows, one stream sync) does not shrink with N"},
-            "roofline": roofline,
         }
+        if roofline is not None:
+            out["roofline"] = roofline
         if secondary:
             out["secondary"] = secondary
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             ref_renderer = spt.load_renderer(args.renderer, seed=1)
             ref_renderer.spp = args.spp
             base, ref_film, ran = cpu_baseline(spt, scene, ref_renderer, args.width, args.height)
@@ -460,7 +499,7 @@ def main():
                              "vs_exhaustive_oracle": film_parity(spt, gpu_film, exhaustive),
                              "note": "reference_walk = the oracle as bvh.rs / bbox.rs are written (the timed cpu_baseline); exhaustive = "
                                      "every triangle tested, (t, instance, prim) tie rule - the answer the library's padded trees reproduce"}
-        if world == 1 and not args.no_secondary:
+        if args.full and world == 1 and not args.no_secondary:
             try:
                 out["other_configs"] = other_configs(spt, local_rank)
             except Exception as e:   # the headline line must survive a failure of the extras

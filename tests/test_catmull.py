@@ -195,14 +195,13 @@ def test_scene_loader_turns_patches_into_instances(tmp_path):
         assert e.value.status == status and word in str(e.value)
 
 
-REF_MODELS = "/root/reference/scenes/models"
+REF_MODELS = os.path.join(_util.GOLDEN, "reference_scenes", "models")   # the reference's scenes/models/*.ply (data fixtures)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_MODELS), reason="the reference's model files are only present in the build container")
 @pytest.mark.parametrize("model,fas", [("cube.ply", 3), ("letter-p.ply", 2), ("letter-p.ply", 3)])
 def test_reference_models_subdivide_onto_their_limit_surface(model, fas):
     """The control meshes the reference's scenes 19 / 20 use (scenes/common_primitives.json: `letter-p.ply`, `cube_crease.ply`;
-    `cube.ply` next to them), read in place as data: the patches pass through the limit surface the independent numpy
+    `cube.ply` next to them), kept as data fixtures under tests/golden: the patches pass through the limit surface the independent numpy
     subdivision finds.  (Blender's `vertex_indices` spelling of the face list is accepted like `vertex_index`.)"""
     v, faces = read_ply(os.path.join(REF_MODELS, model))
     size = np.abs(v).max()
@@ -217,7 +216,6 @@ def test_reference_models_subdivide_onto_their_limit_surface(model, fas):
     assert nearest(mids, cloud).max() < 0.03 * size
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_MODELS), reason="the reference's model files are only present in the build container")
 def test_reference_crease_cube():
     """scenes/models/cube_crease.ply: eight edges (bottom ring + verticals) of sharpness 2 in the `element edge` block."""
     crease = spt.catmull_clark_patches(os.path.join(REF_MODELS, "cube_crease.ply"), 4)

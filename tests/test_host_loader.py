@@ -9,7 +9,8 @@ import pytest
 import _util
 
 spt = _util.load_pkg()
-REF = "/root/reference/scenes"
+# the reference's scenes/test_scene_0{0,1}.json and the model they name, stored as data fixtures
+REF = os.path.join(_util.GOLDEN, "reference_scenes")
 
 BASE = {
     "cameras": {"type": "perspective", "name": "c", "eye": [0.0, 0.0, 5.0], "forward": [0.0, 0.0, -1.0], "up": [0.0, 1.0, 0.0], "fov": 45.0},
@@ -241,7 +242,6 @@ def test_exr_roundtrip_and_png_and_u8_truncation(tmp_path):
     assert np.array_equal(np.asarray(Image.open(tmp_path / "a.png")), spt.film_to_rgb8(np.tile(film, (4, 3, 1))))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree only exists in the build container")
 @pytest.mark.parametrize("mine,theirs", [("cfg1_sphere.json", "test_scene_00.json"), ("cfg2_cube.json", "test_scene_01.json")])
 def test_authored_scenes_equal_the_reference_scenes(mine, theirs):
     a = spt.load_scene(os.path.join(_util.SCENES, mine))

@@ -84,12 +84,15 @@ def test_shard_rows_partition_every_layout():
 
 def test_bench_launches_its_own_ranks_when_typed_plainly():
     """`python bench.py --gpus 2` (no torch.distributed.run around it) must start the two ranks itself: here, without a
-    GPU, each rank gets as far as the device check and says so - the parent did not exit with a launch-me-differently error."""
+    GPU, each rank gets as far as the device check and says so - the parent did not exit with a launch-me-differently error.
+    With one GPU the two ranks share it (--single-device), so the line comes from rank 0 as on a box with two."""
     import subprocess
     import sys
+    spt = _util.load_pkg()
+    n_gpus = spt.device_count() if os.path.exists(os.path.join(spt.LIB_DIR, "libspt_hip.so")) else 0
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    p = subprocess.run([sys.executable, os.path.join(_util.ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"],
-                       capture_output=True, text=True, timeout=300, env=env)
+    p = subprocess.run([sys.executable, os.path.join(_util.ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"]
+                       + (["--single-device"] if n_gpus == 1 else []), capture_output=True, text=True, timeout=300, env=env)
     if p.returncode == 0:      # a box with GPUs: rank 0 printed the line
         assert '"n_gpus": 2' in p.stdout and '"scaling": "strong"' in p.stdout
     else:

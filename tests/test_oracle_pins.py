@@ -240,7 +240,7 @@ def test_tie_rule_is_order_independent(tmp_path):
 
 
 # ---------------------------------------------------------------- the headline workload's mesh
-REF_CUBE = "/root/reference/scenes/models/cube.obj"
+REF_CUBE = os.path.join(_util.GOLDEN, "reference_scenes", "models", "cube.obj")   # the reference's scenes/models/cube.obj (data fixture)
 
 
 def _obj_triangles(path):
@@ -265,10 +265,9 @@ def _obj_triangles(path):
     return tris
 
 
-@pytest.mark.skipif(not os.path.exists(REF_CUBE), reason="the reference's model files are only present in the build container")
 def test_generated_cube_is_the_reference_cube(tmp_path):
-    """scenes_amd/models/cube.obj is generated (24 vertices, another face / uv order) because reference files are not copied
-    into the repo; the headline workload claims to be the reference's scenes/test_scene_01.json.  Read in place as data:
+    """scenes_amd/models/cube.obj is generated (24 vertices, another face / uv order); the headline workload claims to be the
+    reference's scenes/test_scene_01.json.  With the reference's own cube.obj kept as a data fixture under tests/golden:
     the two files describe the same 12 triangles with the same normals, and the scene rendered from the reference's own
     file has the same closed-form film (interior pixels to 1e-5; the two visible face radiances 0.3363 / 1.2552)."""
     ours = _obj_triangles(os.path.join(_util.SCENES, "models", "cube.obj"))

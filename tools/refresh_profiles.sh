@@ -7,7 +7,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
 O=gpurun_out/refresh
 mkdir -p $O
-timeout -k 10 900 python bench.py > $O/bench.json 2> $O/bench.err || { echo bench failed; tail -5 $O/bench.err; exit 1; }
+timeout -k 10 900 python bench.py --full > $O/bench.json 2> $O/bench.err || { echo bench failed; tail -5 $O/bench.err; exit 1; }
 echo "bench: $(python -c "import json;d=json.loads(open('$O/bench.json').read().strip().splitlines()[-1]);print(d['value'],d['ms_per_step'],d['roofline']['frac'],d['cpu_baseline']['value'])")"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py --steps 5 --warmup 1 --profile-steps 0 --no-cpu-baseline --no-secondary > $O/stats.log 2>&1 || { echo stats failed; tail -5 $O/stats.log; exit 1; }
 for c in FETCH_SIZE WRITE_SIZE; do

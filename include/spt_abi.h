@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SPT_ABI_VERSION 13
+#define SPT_ABI_VERSION 14
 
 typedef int32_t spt_status;
 enum {
@@ -426,6 +426,34 @@ spt_status spt_render(const spt_scene* scene, const spt_camera* cam, const spt_r
 spt_status spt_render_wait(const spt_scene* scene);
 /* Number of image rows spt_render writes for these params. */
 spt_status spt_shard_rows(const spt_render_params* params, uint32_t* rows);
+
+/* ---- progressive rendering (ABI v14) ----------------------------------------------------------
+ * A film owns one shard's running sums on the device.  `params` is the PLAN: spp stays its total and still drives the
+ * jittered grid, the R2 index k = pixel * spp + s + 1 and the auxiliary-ray spread 1/sqrt(spp); each spt_film_render adds the
+ * next samples of that plan in sample order, so increments summing to spp (first_sample 0) give the bits of one spt_render.
+ * The film covers the samples [first_sample, first_sample + done).  Plans with SPT_RENDER_ASYNC / PROFILE / COUNT_VISITS or a
+ * non-packed out_strip_stride are refused by spt_film_render (SPT_ERR_INVALID_ARG); a box filter that reaches neighbouring
+ * pixels (ceil(radius - 0.5) >= 1) by spt_film_create (SPT_ERR_UNSUPPORTED).  Film calls take the scene's lock and never
+ * touch the buffers of spt_render (an asynchronous copy-out may be reading them); a film is destroyed before its scene. */
+typedef struct spt_film spt_film;
+enum { SPT_FILM_MOMENTS = 1u };   /* also keep the per-channel sum of squared sample radiance (SUM_SQ, VAR_OF_MEAN) */
+enum {
+    SPT_FILM_MEAN = 0,            /* what spt_render returns for the covered samples: S * (1 / done), or S * (1 / wsum) for a box
+                                     radius other than 0.5 (wsum = covered samples whose offset lies in the box); done > 0 */
+    SPT_FILM_SUM = 1,             /* S: the running sum of the covered samples, in sample order                             */
+    SPT_FILM_SUM_SQ = 2,          /* Q = Q + x * x per channel, in sample order (SPT_FILM_MOMENTS)                          */
+    SPT_FILM_VAR_OF_MEAN = 3      /* m = S * (1/n); v = (Q * (1/n) - m * m) * (1/(n - 1)); max(v, 0); +inf at n == 1
+                                     (SPT_FILM_MOMENTS, radius 0.5, n = done > 0)                                           */
+};
+spt_status spt_film_create(const spt_scene* scene, const spt_camera* cam, const spt_render_params* params,
+                           uint32_t first_sample, uint32_t film_flags, spt_film** out);
+/* Adds the next n_samples samples of the plan (0: nothing).  Synchronous.  A call that would pass the plan's spp is refused
+ * (SPT_ERR_INVALID_ARG) and the film is left as it was. */
+spt_status spt_film_render(spt_film* film, uint32_t n_samples);
+spt_status spt_film_samples(const spt_film* film, uint32_t* done);
+/* One of SPT_FILM_*: the shard's rows packed, rows * width * 3 f32 (spt_shard_rows of the plan). */
+spt_status spt_film_read(spt_film* film, uint32_t what, float* out);
+void spt_film_destroy(spt_film* film);   /* before spt_scene_destroy of its scene */
 
 /* Seams below the renderer, for parity tests of rows a4/a6/a8/a9/a10:
  * Primitive::intersect / intersect_test of the scene aggregate on caller rays. */

@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import weakref
 from dataclasses import dataclass
 from typing import Optional
 
@@ -24,7 +25,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.environ.get("SPT_LIB_DIR") or os.path.join(_HERE, "lib")   # (SPT_LIB_DIR: A/B runs against another build, tools/ only)
 REPO_ROOT = os.path.dirname(_HERE)
 
-SPT_ABI_VERSION = 13
+SPT_ABI_VERSION = 14
 SPT_LEAF_FLAG = 0x80000000
 
 STATUS_NAMES = {
@@ -181,6 +182,8 @@ RENDER_BOX_RADIUS = 2
 RENDER_COUNT_VISITS = 4
 RENDER_ASYNC = 8
 RENDER_DEBUG_NORMAL = 16   # the reference's cargo feature `debug_normal` (Cargo.toml:34-36, pt.rs:113-118)
+FILM_MOMENTS = 1          # spt_film_create: also keep the per-channel sum of squared sample radiance (ABI v14)
+FILM_MEAN, FILM_SUM, FILM_SUM_SQ, FILM_VAR_OF_MEAN = 0, 1, 2, 3   # spt_film_read
 N_KERNELS = 7
 KERNEL_NAMES = ("primary", "shade", "shadow", "extend", "resolve", "other", "shade_first")
 
@@ -280,6 +283,12 @@ def hip_lib() -> C.CDLL:
         lib.spt_pin_host.argtypes = [C.c_void_p, C.c_uint64]
         lib.spt_unpin_host.argtypes = [C.c_void_p]
         lib.spt_unpin_host.restype = None
+        lib.spt_film_create.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+        lib.spt_film_render.argtypes = [C.c_void_p, C.c_uint32]
+        lib.spt_film_samples.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        lib.spt_film_read.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        lib.spt_film_destroy.argtypes = [C.c_void_p]
+        lib.spt_film_destroy.restype = None
         lib.spt_debug_detmath.argtypes = [C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.spt_debug_bxdf.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Material), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -383,6 +392,7 @@ class DeviceScene:
         self.scene = scene
         self.device = device
         self._pinned = {}
+        self._films = weakref.WeakSet()   # ProgressiveFilm objects on this scene: destroyed before it
         desc = scene.desc
         _check_hip(hip_lib().spt_scene_create(C.byref(desc), device, C.byref(self._h)))
 
@@ -412,6 +422,8 @@ class DeviceScene:
     def close(self) -> None:
         # an asynchronous frame may still be copying into one of the pinned film buffers: the scene goes first (its destroy
         # drains the render and the copy stream), the buffers after it
+        for film in list(self._films):
+            film.close()
         if self._h:
             hip_lib().spt_render_wait(self._h)
             hip_lib().spt_scene_destroy(self._h)
@@ -516,6 +528,16 @@ class PathTracer:
             self.last_stats = stats
         return out
 
+    def progressive(self, scene: Scene, config: OutputConfig, device: int = 0, first_sample: int = 0, moments: bool = False,
+                    shard_index: int = 0, shard_count: int = 1, strip_rows: int = 16, samples_per_pass: int = 0,
+                    flags: int = 0) -> "ProgressiveFilm":
+        """A film that takes this renderer's samples in increments (spt_film_*): `spp` is the plan's total, each
+        ProgressiveFilm.render(n) adds the next n samples, and after increments summing to spp (first_sample 0) mean() has the
+        bits of render_shard with the same arguments.  moments=True also keeps the sums of squares (sum_sq, variance_of_mean).
+        `flags` are extra SPT_RENDER_* bits of the plan."""
+        return ProgressiveFilm(self, scene, config, device, first_sample, moments, shard_index, shard_count, strip_rows,
+                               samples_per_pass, flags)
+
     def wait(self, scene: Scene, device: int = 0) -> None:
         """spt_render_wait: every render_shard(..., wait=False) queued on the scene has delivered its film."""
         _check_hip(hip_lib().spt_render_wait(scene.device_scene(device)._h))
@@ -527,6 +549,80 @@ class PathTracer:
         if config.output_filename:
             write_image(config.output_filename, film)
         return film
+
+
+class ProgressiveFilm:
+    """One shard's running sums of a fixed render plan on the device (spt_film_create); see PathTracer.progressive.
+    Keeps its DeviceScene alive; closing the scene closes the film first."""
+
+    def __init__(self, renderer: PathTracer, scene: Scene, config: OutputConfig, device: int = 0, first_sample: int = 0,
+                 moments: bool = False, shard_index: int = 0, shard_count: int = 1, strip_rows: int = 16,
+                 samples_per_pass: int = 0, flags: int = 0):
+        self._h = C.c_void_p()
+        self._ds = scene.device_scene(device)
+        self.scene = scene
+        self.first_sample = first_sample
+        self.width = config.width
+        self._cam = scene.get_camera(config.used_camera_name)
+        self._params = renderer.params(config.width, config.height, shard_index, shard_count, strip_rows, samples_per_pass, flags)
+        rows = C.c_uint32()
+        _check_hip(hip_lib().spt_shard_rows(C.byref(self._params), C.byref(rows)))
+        self.rows = rows.value
+        _check_hip(hip_lib().spt_film_create(self._ds._h, C.byref(self._cam), C.byref(self._params), first_sample,
+                                             FILM_MOMENTS if moments else 0, C.byref(self._h)))
+        self._ds._films.add(self)
+
+    def render(self, n: int) -> "ProgressiveFilm":
+        """Adds the next n samples of the plan (synchronous)."""
+        _check_hip(hip_lib().spt_film_render(self._handle(), n))
+        return self
+
+    @property
+    def samples(self) -> int:
+        """Samples covered so far: the plan's [first_sample, first_sample + samples)."""
+        done = C.c_uint32()
+        _check_hip(hip_lib().spt_film_samples(self._handle(), C.byref(done)))
+        return done.value
+
+    def read(self, what: int) -> np.ndarray:
+        """(rows, width, 3) f32 of one FILM_* quantity."""
+        out = np.zeros((self.rows, self.width, 3), dtype=np.float32)
+        _check_hip(hip_lib().spt_film_read(self._handle(), what, out.ctypes.data))
+        return out
+
+    def mean(self) -> np.ndarray:
+        return self.read(FILM_MEAN)
+
+    def sum(self) -> np.ndarray:
+        return self.read(FILM_SUM)
+
+    def sum_sq(self) -> np.ndarray:
+        return self.read(FILM_SUM_SQ)
+
+    def variance_of_mean(self) -> np.ndarray:
+        return self.read(FILM_VAR_OF_MEAN)
+
+    def _handle(self):
+        if not self._h:
+            raise SptError(1, "the progressive film is closed")
+        return self._h
+
+    def close(self) -> None:
+        if self._h:
+            hip_lib().spt_film_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self) -> "ProgressiveFilm":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class DeviceApi(C.Structure):

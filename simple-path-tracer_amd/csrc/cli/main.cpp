@@ -2,7 +2,10 @@
 //   spt -s scene.json -r renderer.json [-w 512] [-h 512] -o out.png [-c camera]
 // plus --seed, --spp, --device D | --gpus N (one image over N devices: one worker thread and one scene replica per device,
 // interleaved row strips, one film - spt_host_multi_*, the counterpart of the thread fan-out of pt.rs:243-287),
-// --strip-rows R, --debug-normal and --bezier-ni (the reference's two cargo features, Cargo.toml:34-36: pt.rs:113-118, bezier.rs:58-103).  It loads the scene
+// --strip-rows R, --debug-normal and --bezier-ni (the reference's two cargo features, Cargo.toml:34-36: pt.rs:113-118, bezier.rs:58-103),
+// and progressive rendering on one device through a film object (spt_film_*): --preview-every K rewrites the image after every
+// K samples, --time-limit SEC stops after the increment during which SEC seconds have passed, --variance-out PATH.exr writes the
+// per-pixel variance of the mean.  It loads the scene
 // with libspt_host, renders with libspt_hip (HIP kernels only) and writes the image; like the reference it reports the
 // time spent inside `render`.
 #include <algorithm>
@@ -18,7 +21,8 @@
 static void usage() {
     std::fprintf(stderr,
                  "usage: spt -s <scene.json> -r <renderer.json> -o <out.png> [-w 512] [-h 512] [-c camera]\n"
-                 "           [--seed N] [--spp N] [--device D | --gpus N | --devices a,b,..] [--strip-rows R] [--debug-normal] [--bezier-ni]\n");
+                 "           [--seed N] [--spp N] [--device D | --gpus N | --devices a,b,..] [--strip-rows R] [--debug-normal] [--bezier-ni]\n"
+                 "           [--preview-every K] [--time-limit SEC] [--variance-out var.exr]\n");
 }
 
 int main(int argc, char** argv) {
@@ -28,6 +32,9 @@ int main(int argc, char** argv) {
     int device = 0, gpus = 0;
     uint32_t strip_rows = 0;
     bool debug_normal = false, bezier_ni = false;
+    uint32_t preview_every = 0;
+    double time_limit = 0.0;
+    std::string variance_out;
     std::vector<int32_t> device_list;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -57,9 +64,21 @@ int main(int argc, char** argv) {
         else if (a == "--strip-rows") strip_rows = (uint32_t)std::atoi(next());
         else if (a == "--debug-normal") debug_normal = true;
         else if (a == "--bezier-ni") bezier_ni = true;
+        else if (a == "--preview-every") preview_every = (uint32_t)std::atoi(next());
+        else if (a == "--time-limit") time_limit = std::atof(next());
+        else if (a == "--variance-out") variance_out = next();
         else { usage(); return 2; }
     }
     if (scene_path.empty() || renderer_path.empty() || out_path.empty()) { usage(); return 2; }
+    const bool progressive = preview_every > 0 || time_limit > 0.0 || !variance_out.empty();
+    if (progressive && gpus > 1) {
+        std::fprintf(stderr, "Error: --preview-every, --time-limit and --variance-out render on one device (a film object), not on the %d of --gpus / --devices\n", gpus);
+        return 2;
+    }
+    if (progressive && gpus == 1) {   // one device named through --gpus 1 / --devices d: the film lives there
+        device = device_list.empty() ? 0 : device_list[0];
+        gpus = 0;
+    }
 
     // this binary and the library it found at run time must agree on the struct layouts of include/spt_abi.h
     if (spt_abi_version() != SPT_ABI_VERSION) {
@@ -128,16 +147,70 @@ int main(int argc, char** argv) {
         }
         std::fprintf(stderr, "Scene JSON is loaded successfully. Rendering...\n");
         t0 = std::chrono::steady_clock::now();
-        if (spt_render(ds, &cam, &params, film.data(), st.data()) != SPT_OK) {
+        if (!progressive && spt_render(ds, &cam, &params, film.data(), st.data()) != SPT_OK) {
             std::fprintf(stderr, "Error: %s\n", spt_last_error());
             return 1;
         }
     }
-    std::vector<uint8_t> rgb8(film.size());
-    spt_host_film_to_rgb8(film.data(), (uint64_t)width * height, rgb8.data());
-    if (spt_host_write_image(out_path.c_str(), rgb8.data(), width, height) != SPT_OK)
-        std::printf("Failed to save image, err: %s\n", spt_host_last_error());  // printed and ignored, like pt.rs:292-294
+    auto write_film = [&]() {
+        std::vector<uint8_t> rgb8(film.size());
+        spt_host_film_to_rgb8(film.data(), (uint64_t)width * height, rgb8.data());
+        if (spt_host_write_image(out_path.c_str(), rgb8.data(), width, height) != SPT_OK)
+            std::printf("Failed to save image, err: %s\n", spt_host_last_error());  // printed and ignored, like pt.rs:292-294
+    };
+    uint32_t done = 0;
+    if (progressive) {
+        // the film takes the plan's samples in increments; the mean after all of them has the bits of one spt_render
+        spt_film* pf = nullptr;
+        auto film_fail = [&]() {
+            std::fprintf(stderr, "Error: %s\n", spt_last_error());
+            if (pf) spt_film_destroy(pf);
+            spt_scene_destroy(ds);
+            spt_host_scene_free(hs);
+            return 1;
+        };
+        if (spt_film_create(ds, &cam, &params, 0, variance_out.empty() ? 0u : (uint32_t)SPT_FILM_MOMENTS, &pf) != SPT_OK) return film_fail();
+        const uint32_t inc = preview_every ? preview_every : (time_limit > 0.0 ? std::max(1u, params.spp / 16u) : params.spp);
+        while (done < params.spp) {
+            const uint32_t n = std::min(inc, params.spp - done);
+            if (spt_film_render(pf, n) != SPT_OK) return film_fail();
+            done += n;
+            const bool out_of_time = time_limit > 0.0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() >= time_limit;
+            if (done == params.spp || out_of_time) break;
+            if (preview_every) {
+                if (spt_film_read(pf, SPT_FILM_MEAN, film.data()) != SPT_OK) return film_fail();
+                write_film();
+            }
+        }
+        if (spt_film_read(pf, SPT_FILM_MEAN, film.data()) != SPT_OK) return film_fail();
+        if (time_limit > 0.0) {
+            std::fprintf(stderr, "Rendered %u of %u samples per pixel\n", done, params.spp);
+            if (done < params.spp && params.sampler == SPT_SAMPLER_JITTERED)
+                std::fprintf(stderr, "Warning: the jittered sampler's %ux%u grid is walked row by row: these %u samples cover only its first rows\n",
+                             params.division_x, params.division_y, done);
+        }
+        if (!variance_out.empty()) {
+            std::vector<float> var(film.size());
+            if (spt_film_read(pf, SPT_FILM_VAR_OF_MEAN, var.data()) != SPT_OK) return film_fail();
+            if (spt_host_write_exr(variance_out.c_str(), var.data(), width, height) != SPT_OK) {
+                std::fprintf(stderr, "Error: %s\n", spt_host_last_error());
+                spt_film_destroy(pf);
+                spt_scene_destroy(ds);
+                spt_host_scene_free(hs);
+                return 1;
+            }
+        }
+        spt_film_destroy(pf);
+    }
+    write_film();
     double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (progressive) {   // (a film returns no kernel times: the host clock of the whole loop)
+        std::fprintf(stderr, "Finished, time used: %.3fs (%.1f Msamples/s, %u samples per pixel)\n", sec,
+                     (double)width * height * done / (sec * 1e6), done);
+        spt_scene_destroy(ds);
+        spt_host_scene_free(hs);
+        return 0;
+    }
     uint64_t samples = 0;
     double gpu_ms = 0.0;      // the slowest device's time on its stream
     for (const spt_render_stats& d : st) { samples += d.samples; gpu_ms = std::max(gpu_ms, d.gpu_ms); }

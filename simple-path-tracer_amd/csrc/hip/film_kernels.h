@@ -11,8 +11,14 @@
 // unmarked slot is read (whatever it holds) and not added.  With the per-row spans nearly every live sample is marked, so the
 // extra reads are few.  (Round 2's form - mask first, then the marked slots of one byte at a time - took one round trip per 8
 // samples: 0.07 ms per launch whatever the shard size, 0.17 of the 0.6 ms step of an 8-GPU rank.)
-template <uint32_t kResolveBatch>
-__global__ void __launch_bounds__(256, 3) k_resolve_bits(RenderCtx rc) {
+//
+// kMoments (a film object with SPT_FILM_MOMENTS, spt_film_*): the one extra argument is the film's Q, and every added sample x also
+// gives Q = Q + x * x per channel in the same pass over the slots.  Without kMoments there is no extra argument: the signature, and
+// with it the kernel's code, stay those of the plain resolve (the Q pointer does not go into RenderCtx, which every hot kernel
+// takes by value).
+template <uint32_t kResolveBatch, bool kMoments = false, class... Sq>
+__global__ void __launch_bounds__(256, 3) k_resolve_bits(RenderCtx rc, Sq... sq_arg) {
+    static_assert(sizeof...(Sq) == (kMoments ? 1u : 0u), "k_resolve_bits<., true> takes the film's Q pointer, <., false> nothing more");
     const uint32_t lp = blockIdx.x * blockDim.x + threadIdx.x;
     if (lp >= rc.n_pixels) return;
     if (rc.first_slot[lp] >= rc.pass_samples) return;
@@ -20,6 +26,12 @@ __global__ void __launch_bounds__(256, 3) k_resolve_bits(RenderCtx rc) {
     const float* rp = rc.rad + lp;
     const uint8_t* bp = rc.slot_bits + lp;
     f3 sum = mk3(rc.film[3 * lp], rc.film[3 * lp + 1], rc.film[3 * lp + 2]);
+    float* sq = nullptr;
+    f3 sum_sq = mk3(0, 0, 0);
+    if constexpr (kMoments) {
+        sq = (sq_arg, ...);
+        sum_sq = mk3(sq[3 * lp], sq[3 * lp + 1], sq[3 * lp + 2]);
+    }
     for (uint32_t s0 = 0; s0 < rc.pass_samples; s0 += kResolveBatch) {
         uint32_t m = 0u;
         float r[kResolveBatch], g[kResolveBatch], b[kResolveBatch];
@@ -36,18 +48,33 @@ __global__ void __launch_bounds__(256, 3) k_resolve_bits(RenderCtx rc) {
         if (m == 0u) continue;
 #pragma unroll
         for (uint32_t k = 0; k < kResolveBatch; ++k)
-            if ((m >> k) & 1u) sum = sum + mk3(r[k], g[k], b[k]);
+            if ((m >> k) & 1u) {
+                const f3 x = mk3(r[k], g[k], b[k]);
+                sum = sum + x;
+                if (kMoments) sum_sq = sum_sq + x * x;
+            }
     }
     rc.film[3 * lp] = sum.x; rc.film[3 * lp + 1] = sum.y; rc.film[3 * lp + 2] = sum.z;
+    if constexpr (kMoments) { sq[3 * lp] = sum_sq.x; sq[3 * lp + 1] = sum_sq.y; sq[3 * lp + 2] = sum_sq.z; }
 }
 
-__global__ void __launch_bounds__(256) k_resolve(RenderCtx rc) {
+// kMoments: as in k_resolve_bits.  The samples before `first` went into the film in k_primary: misses, black unless the scene has an
+// environment, and a film with moments of such a scene takes the chunked path (k_resolve_bits), so Q misses nothing here.
+template <bool kMoments = false, class... Sq>
+__global__ void __launch_bounds__(256) k_resolve(RenderCtx rc, Sq... sq_arg) {
+    static_assert(sizeof...(Sq) == (kMoments ? 1u : 0u), "k_resolve<true> takes the film's Q pointer, <false> nothing more");
     const uint32_t lp = blockIdx.x * blockDim.x + threadIdx.x;
     if (lp >= rc.n_pixels) return;
     const uint32_t first = rc.first_slot[lp];
     if (first >= rc.pass_samples) return;
     const size_t plane = rc.rad_plane;
     f3 sum = mk3(rc.film[3 * lp], rc.film[3 * lp + 1], rc.film[3 * lp + 2]);
+    float* sq = nullptr;
+    f3 sum_sq = mk3(0, 0, 0);
+    if constexpr (kMoments) {
+        sq = (sq_arg, ...);
+        sum_sq = mk3(sq[3 * lp], sq[3 * lp + 1], sq[3 * lp + 2]);
+    }
     // the additions are sequential (sample order = the reference's, film.rs:87), the loads are not: 8 samples
     // (24 loads) in flight per lane, which matters when a narrow shard leaves few pixels to hide latency with
     uint32_t s = first;
@@ -59,13 +86,20 @@ __global__ void __launch_bounds__(256) k_resolve(RenderCtx rc) {
             r[k] = rc.rad[ri]; g[k] = rc.rad[plane + ri]; b[k] = rc.rad[2 * plane + ri];
         }
 #pragma unroll
-        for (uint32_t k = 0; k < 8u; ++k) sum = sum + mk3(r[k], g[k], b[k]);
+        for (uint32_t k = 0; k < 8u; ++k) {
+            const f3 x = mk3(r[k], g[k], b[k]);
+            sum = sum + x;
+            if (kMoments) sum_sq = sum_sq + x * x;
+        }
     }
     for (; s < rc.pass_samples; ++s) {
         const size_t ri = (size_t)s * rc.n_pixels + lp;
-        sum = sum + mk3(rc.rad[ri], rc.rad[plane + ri], rc.rad[2 * plane + ri]);  // film.rs:87
+        const f3 x = mk3(rc.rad[ri], rc.rad[plane + ri], rc.rad[2 * plane + ri]);
+        sum = sum + x;  // film.rs:87
+        if (kMoments) sum_sq = sum_sq + x * x;
     }
     rc.film[3 * lp] = sum.x; rc.film[3 * lp + 1] = sum.y; rc.film[3 * lp + 2] = sum.z;
+    if constexpr (kMoments) { sq[3 * lp] = sum_sq.x; sq[3 * lp + 1] = sum_sq.y; sq[3 * lp + 2] = sum_sq.z; }
 }
 
 // film.rs:91: color / weight_sum  (Color / f32 = Color * (1/f32))
@@ -92,7 +126,8 @@ SPT_DEV float box_weight(const RenderCtx& rc, uint32_t pixel, uint32_t s, int32_
 // radius_int <= 0 (radius <= 0.5): the colour is the pixel's own in-order sum (rc.film), the weight sum counts the
 // samples whose offset lies inside the box (all of them at radius 0.5, which is k_finish).  radius_int < 0
 // (radius <= -0.5) leaves both loops of filter_pixel empty: 0 * (1 / 0).
-__global__ void __launch_bounds__(256) k_finish_box(RenderCtx rc, float* out, float radius, int32_t R) {
+// The film holds the samples [s_first, s_first + s_count) of the plan: spt_render passes [0, spp), a film object what it covers.
+__global__ void __launch_bounds__(256) k_finish_box(RenderCtx rc, float* out, float radius, int32_t R, uint32_t s_first, uint32_t s_count) {
     const uint32_t lp = blockIdx.x * blockDim.x + threadIdx.x;
     if (lp >= rc.n_pixels) return;
     f3 sum = mk3(0, 0, 0);
@@ -101,10 +136,24 @@ __global__ void __launch_bounds__(256) k_finish_box(RenderCtx rc, float* out, fl
         const uint32_t row_local = lp / rc.width, col = lp - row_local * rc.width;
         const uint32_t pixel = global_row(rc, row_local) * rc.width + col;
         sum = mk3(rc.film[3 * lp], rc.film[3 * lp + 1], rc.film[3 * lp + 2]);
-        for (uint32_t s = 0; s < rc.spp; ++s) wsum += box_weight(rc, pixel, s, 0, 0, radius);
+        for (uint32_t s = s_first; s < s_first + s_count; ++s) wsum += box_weight(rc, pixel, s, 0, 0, radius);
     }
     const f3 c = sum * (1.0f / wsum);   // film.rs:91, Color / f32 = Color * (1 / f32) (color.rs:125-131)
     out[3 * lp] = c.x; out[3 * lp + 1] = c.y; out[3 * lp + 2] = c.z;
+}
+
+// Read-out of a film object (spt_film_read) for radius 0.5, one lane per float: SPT_FILM_MEAN is S * (1 / n), the operation of
+// k_finish; SPT_FILM_VAR_OF_MEAN is the variance of that mean from the moments, m = S * (1/n), v = (Q * (1/n) - m * m) * (1/(n - 1)),
+// clamped at 0 (a NaN stays one) and +inf for one sample.  The reciprocals come from the host, as rc.spp_inv does for k_finish.
+__global__ void __launch_bounds__(256) k_film_read(uint32_t what, uint32_t n_floats, const float* sum, const float* sum_sq, uint32_t n,
+                                                   float inv_n, float inv_n1, float* out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_floats) return;
+    const float m = sum[i] * inv_n;
+    if (what == SPT_FILM_MEAN) { out[i] = m; return; }
+    if (n == 1u) { out[i] = __builtin_huge_valf(); return; }
+    const float v = (sum_sq[i] * inv_n - m * m) * inv_n1;
+    out[i] = v < 0.0f ? 0.0f : v;
 }
 
 // radius_int >= 1: Film::filter_pixel (film.rs:71-92) over the kept samples of a band of whole rows.  Rows j, then

@@ -500,6 +500,11 @@ struct BezierLib {
     void (*destroy)(spt_scene*) = nullptr;
     spt_status (*render)(const spt_scene*, const spt_camera*, const spt_render_params*, float*, spt_render_stats*) = nullptr;
     spt_status (*render_wait)(const spt_scene*) = nullptr;
+    spt_status (*film_create)(const spt_scene*, const spt_camera*, const spt_render_params*, uint32_t, uint32_t, spt_film**) = nullptr;
+    spt_status (*film_render)(spt_film*, uint32_t) = nullptr;
+    spt_status (*film_samples)(const spt_film*, uint32_t*) = nullptr;
+    spt_status (*film_read)(spt_film*, uint32_t, float*) = nullptr;
+    void (*film_destroy)(spt_film*) = nullptr;
     spt_status (*trace_closest)(const spt_scene*, uint32_t, const spt_ray*, spt_hit*) = nullptr;
     spt_status (*trace_any)(const spt_scene*, uint32_t, const spt_ray*, uint8_t*) = nullptr;
     spt_status (*debug_bxdf)(const spt_scene*, int32_t, const spt_material*, uint32_t, uint32_t, const float*, const float*, const uint64_t*, float*, float*,
@@ -573,6 +578,23 @@ struct spt_scene {
         if (stream2) (void)hipStreamDestroy(stream2);
         if (stream) (void)hipStreamDestroy(stream);
     }
+};
+
+// A film object (spt_film_*, ABI v14): one shard's running sums of a fixed plan on the scene's device, which every
+// spt_film_render extends by the next samples.  Its buffers are its own: spt_render's film / out (which an asynchronous
+// copy-out may still be reading) are never touched, the render workspace is shared under the scene's lock.
+struct spt_film {
+    const BezierLib* fwd = nullptr;   // set: `inner` is a film of libspt_hip_bez.so and nothing below is used
+    spt_film* inner = nullptr;
+    spt_scene* sc = nullptr;
+    spt_camera cam{};
+    spt_render_params plan{};
+    uint32_t first = 0, done = 0;     // covers the plan's samples [first, first + done)
+    uint32_t flags = 0;               // SPT_FILM_*
+    uint32_t rows = 0;                // image rows of the shard
+    float radius = 0.5f;
+    int32_t R = 0;                    // ceil(radius - 0.5) <= 0
+    DeviceBuffer sum, sq, out;        // S, Q (SPT_FILM_MOMENTS) and the read-out staging buffer, rows * width * 3 f32 each
 };
 
 namespace {
@@ -794,12 +816,17 @@ const BezierLib* bezier_lib() {
         lib.destroy = reinterpret_cast<decltype(lib.destroy)>(dlsym(h, "spt_scene_destroy"));
         lib.render = reinterpret_cast<decltype(lib.render)>(dlsym(h, "spt_render"));
         lib.render_wait = reinterpret_cast<decltype(lib.render_wait)>(dlsym(h, "spt_render_wait"));
+        lib.film_create = reinterpret_cast<decltype(lib.film_create)>(dlsym(h, "spt_film_create"));
+        lib.film_render = reinterpret_cast<decltype(lib.film_render)>(dlsym(h, "spt_film_render"));
+        lib.film_samples = reinterpret_cast<decltype(lib.film_samples)>(dlsym(h, "spt_film_samples"));
+        lib.film_read = reinterpret_cast<decltype(lib.film_read)>(dlsym(h, "spt_film_read"));
+        lib.film_destroy = reinterpret_cast<decltype(lib.film_destroy)>(dlsym(h, "spt_film_destroy"));
         lib.trace_closest = reinterpret_cast<decltype(lib.trace_closest)>(dlsym(h, "spt_trace_closest"));
         lib.trace_any = reinterpret_cast<decltype(lib.trace_any)>(dlsym(h, "spt_trace_any"));
         lib.debug_bxdf = reinterpret_cast<decltype(lib.debug_bxdf)>(dlsym(h, "spt_debug_bxdf"));
         lib.last_error = reinterpret_cast<decltype(lib.last_error)>(dlsym(h, "spt_last_error"));
         auto version = reinterpret_cast<uint32_t (*)(void)>(dlsym(h, "spt_abi_version"));
-        if (!lib.create || !lib.destroy || !lib.render || !lib.render_wait || !lib.trace_closest || !lib.trace_any || !lib.debug_bxdf || !lib.last_error || !version || version() != SPT_ABI_VERSION) {
+        if (!lib.create || !lib.destroy || !lib.render || !lib.render_wait || !lib.film_create || !lib.film_render || !lib.film_samples || !lib.film_read || !lib.film_destroy || !lib.trace_closest || !lib.trace_any || !lib.debug_bxdf || !lib.last_error || !version || version() != SPT_ABI_VERSION) {
             err = path + " does not export ABI version " + std::to_string(SPT_ABI_VERSION);
             return;
         }
@@ -1425,6 +1452,556 @@ static void make_eye_blob(spt_scene* sc, const float eye[3]) {
     sc->eye_valid = true;
 }
 
+namespace {
+
+uint32_t env_u32(const char* name, uint32_t dflt) { const char* v = std::getenv(name); return v ? (uint32_t)std::atoi(v) : dflt; }
+
+// The samples one run of the pass loop adds, and where it adds them: spt_render sums [0, spp) of its plan into the scene's
+// workspace film, zeroed first; a film object (spt_film_render) adds its next increment to its own sums as they stand.
+struct SampleTarget {
+    uint32_t first, count;   // the plan's samples [first, first + count)
+    float* sum;              // window pixels * 3 running sums on the device; null: the scene's workspace film (sc->film)
+    float* sq;               // SPT_FILM_MOMENTS: the running sums of the squares (k_resolve*<., true>); null: none
+    bool zero;               // zero the sums before the first pass
+};
+
+// One call of the render loop: its plan, the kernel choices made once per call, the profiling spans and the counters that
+// become spt_render_stats (spt_render with stats only).
+struct RenderRun {
+    spt_scene* sc = nullptr;
+    const spt_camera* cam = nullptr;
+    const spt_render_params* params = nullptr;
+    spt_render_stats* stats = nullptr;
+    hipStream_t st = nullptr;
+    bool profile = false, count = false, overlap = false, L = false, use_eye = false, dyn_shadow = false, dyn_extend = false;
+    size_t lds = 0;
+    uint32_t kDynBlocks = 0, dyn_refill_below = 0, dyn_steps = 0;
+    const int2* row_span_dev = nullptr;
+    struct Span { int cls; size_t e0; };
+    std::vector<Span> spans;
+    size_t ev_used = 0;
+    std::vector<uint32_t> h_counts;
+    uint64_t seg_closest = 0, seg_shadow = 0, primary_hits = 0, path_vertices = 0, shadow_first = 0, vertices_second = 0;
+    uint64_t samples_traced = 0, live_samples = 0;
+    hipEvent_t get_event() {
+        if (ev_used == sc->events.size()) {
+            hipEvent_t e;
+            HIP_CHECK(hipEventCreate(&e));
+            sc->events.push_back(e);
+        }
+        return sc->events[ev_used++];
+    }
+    void begin(int cls) {
+        if (!profile) return;
+        spans.push_back(Span{cls, ev_used});
+        HIP_CHECK(hipEventRecord(get_event(), st));
+    }
+    void end() {
+        if (!profile) return;
+        HIP_CHECK(hipEventRecord(get_event(), st));
+    }
+};
+
+// The kernel choices of one call (the scene's lock is held and its device selected).
+void run_setup(RenderRun& run) {
+    spt_scene* const sc = run.sc;
+    const spt_render_params& p = *run.params;
+    const spt_camera* const cam = run.cam;
+    run.st = sc->stream;
+    run.profile = (p.flags & SPT_RENDER_PROFILE) != 0;
+    // visit counters: only the kernels that fetch their geometry from memory count (an LDS-resident scene is read once
+    // per workgroup whatever the rays do)
+    run.count = (p.flags & SPT_RENDER_COUNT_VISITS) != 0 && !sc->lds_geo;
+    sc->visits.ensure(12 * sizeof(unsigned long long));
+    if (run.count) HIP_CHECK(hipMemsetAsync(sc->visits.p, 0, 12 * sizeof(unsigned long long), sc->stream));
+    // per-kernel event timing needs one stream; so does a scene with an environment (see the bounce loop)
+    run.overlap = !run.profile && sc->d.env_w == 0u && std::getenv("SPT_NO_OVERLAP") == nullptr;
+    run.lds = sc->lds_bytes;
+    run.L = sc->lds_geo;
+    // primary rays of an LDS-resident scene through the eye-relative copy of its geometry (eye.h), remade when the eye has moved
+    run.use_eye = run.L && !run.count && sc->eye_ok && std::getenv("SPT_NO_EYE_BLOB") == nullptr;
+    if (run.use_eye && (!sc->eye_valid || std::memcmp(sc->eye_key, cam->eye, sizeof(sc->eye_key)) != 0)) make_eye_blob(sc, cam->eye);
+    // refilling persistent waves for large scenes: on for shadow rays (any-hit walks end at very
+    // different times: 10.9 -> 8.8 ms on the 1 M-triangle scene), off for extension rays (28 vs 20 ms)
+    run.dyn_shadow = !run.L && std::getenv("SPT_NO_DYN_SHADOW") == nullptr;
+    // (with the 2-wide nodes the refilling extension kernel was slower, 28 vs 20 ms; with the 4-wide nodes it is
+    //  faster, 16.0 vs 17.7 ms on cfg5 - measured - and on by default)
+    run.dyn_extend = !run.L && std::getenv("SPT_NO_DYN_EXTEND") == nullptr;
+    run.kDynBlocks = env_u32("SPT_DYN_BLOCKS", 2048);   // persistent blocks that pull work
+    run.dyn_refill_below = env_u32("SPT_DYN_REFILL", kRefillBelow);
+    run.dyn_steps = env_u32("SPT_DYN_STEPS", kStepsPerCheck);
+}
+
+void run_spans(RenderRun& run) {
+    spt_scene* const sc = run.sc;
+    const spt_render_params& p = *run.params;
+    const spt_camera* const cam = run.cam;
+    const int2*& row_span_dev = run.row_span_dev;
+
+    // Per-row screen-space spans: every instance's object-space box (8 world-space corners, spt_scene_create) is
+    // projected, the convex hull of the 8 image points is the exact silhouette of the box, and row j keeps the pixels
+    // from the leftmost to the rightmost hull point within one row of slack above and below, plus one pixel each side.
+    // A pixel outside its row's span cannot see any instance with any sample (k_primary's `in_bounds`): the rotated
+    // cube of the headline scene fills 19 % of the image, its world-space AABB's rectangle 25 %.
+    if (!sc->hull_corners.empty() && sc->d.env_w == 0u && std::getenv("SPT_NO_PIXEL_CULL") == nullptr && std::getenv("SPT_NO_ROW_SPANS") == nullptr) {
+        std::vector<double> key = {(double)p.width, (double)p.height, (double)cam->half_cot_half_fov};
+        for (int k = 0; k < 3; ++k) { key.push_back(cam->eye[k]); key.push_back(cam->forward[k]); key.push_back(cam->up[k]); key.push_back(cam->right[k]); }
+        if (key != sc->span_key) {
+            sc->span_key.clear();
+            std::vector<int32_t>& sp = sc->span_host;
+            sp.assign((size_t)p.height * 2, 0);
+            for (uint32_t j = 0; j < p.height; ++j) { sp[2 * j] = (int32_t)p.width; sp[2 * j + 1] = -1; }
+            const double W = (double)p.width, H = (double)p.height, aspect = W / H;
+            bool ok = true;
+            for (const auto& cn : sc->hull_corners) {
+                double px[8], py[8];
+                for (int c = 0; c < 8 && ok; ++c) {
+                    double z = 0, xr = 0, yu = 0, n2 = 0;
+                    for (int k = 0; k < 3; ++k) {
+                        const double v = cn[3 * c + k] - (double)cam->eye[k];
+                        z += v * (double)cam->forward[k]; xr += v * (double)cam->right[k]; yu += v * (double)cam->up[k]; n2 += v * v;
+                    }
+                    if (!(z > 1e-6 * std::sqrt(n2)) || !(z > 0)) { ok = false; break; }   // beside / behind the eye: no finite silhouette
+                    const double x = (double)cam->half_cot_half_fov * xr / z, y = (double)cam->half_cot_half_fov * yu / z;
+                    px[c] = (x / aspect + 0.5) * W;                 // pixel i covers [i, i + 1)
+                    py[c] = H - (y + 0.5) * H;                     // row j covers (j, j + 1]  (k_primary: y = ((H - j - 1) + oy) / H - 0.5)
+                    ok = std::isfinite(px[c]) && std::isfinite(py[c]) && std::fabs(px[c]) < 1e9 && std::fabs(py[c]) < 1e9;
+                }
+                if (!ok) break;
+                // convex hull (monotone chain)
+                int idx[8];
+                for (int c = 0; c < 8; ++c) idx[c] = c;
+                std::sort(idx, idx + 8, [&](int a, int b) { return px[a] < px[b] || (px[a] == px[b] && py[a] < py[b]); });
+                int hull[17], hn = 0;
+                auto crs = [&](int o, int a, int b) { return (px[a] - px[o]) * (py[b] - py[o]) - (py[a] - py[o]) * (px[b] - px[o]); };
+                for (int c = 0; c < 8; ++c) { while (hn >= 2 && crs(hull[hn - 2], hull[hn - 1], idx[c]) <= 0) --hn; hull[hn++] = idx[c]; }
+                for (int c = 6, lower = hn + 1; c >= 0; --c) { while (hn >= lower && crs(hull[hn - 2], hull[hn - 1], idx[c]) <= 0) --hn; hull[hn++] = idx[c]; }
+                if (hn > 1) --hn;      // the last point repeats the first
+                double ymin = 1e300, ymax = -1e300;
+                for (int c = 0; c < hn; ++c) { ymin = std::min(ymin, py[hull[c]]); ymax = std::max(ymax, py[hull[c]]); }
+                const int64_t j0 = std::max<int64_t>(0, (int64_t)std::floor(ymin) - 2), j1 = std::min<int64_t>((int64_t)p.height - 1, (int64_t)std::floor(ymax) + 2);
+                for (int64_t j = j0; j <= j1; ++j) {
+                    const double ya = (double)j - 1.0, yb = (double)j + 2.0;    // the row's own band (j, j + 1] and one row of slack each way
+                    double xmin = 1e300, xmax = -1e300;
+                    for (int c = 0; c < hn; ++c) {
+                        const int a = hull[c], b = hull[(c + 1) % hn];
+                        double xa = px[a], yA = py[a], xb = px[b], yB = py[b];
+                        if (yA > yB) { std::swap(xa, xb); std::swap(yA, yB); }
+                        if (yB < ya || yA > yb) continue;
+                        double x0 = xa, x1 = xb;
+                        if (yB > yA) {      // clip the edge to the band
+                            const double t0 = std::max(0.0, (ya - yA) / (yB - yA)), t1 = std::min(1.0, (yb - yA) / (yB - yA));
+                            x0 = xa + (xb - xa) * t0; x1 = xa + (xb - xa) * t1;
+                        }
+                        xmin = std::min({xmin, x0, x1}); xmax = std::max({xmax, x0, x1});
+                    }
+                    if (xmin > xmax) continue;
+                    const int32_t lo = (int32_t)std::max(-1.0, std::min(W, std::floor(xmin) - 1.0)), hi = (int32_t)std::max(-1.0, std::min(W, std::floor(xmax) + 1.0));
+                    sp[2 * j] = std::min(sp[2 * j], lo);
+                    sp[2 * j + 1] = std::max(sp[2 * j + 1], hi);
+                }
+            }
+            if (ok) {
+                sc->row_span.ensure((size_t)p.height * 2 * sizeof(int32_t));
+                HIP_CHECK(hipMemcpyAsync(sc->row_span.p, sp.data(), (size_t)p.height * 2 * sizeof(int32_t), hipMemcpyHostToDevice, sc->stream));
+                HIP_CHECK(hipStreamSynchronize(sc->stream));   // `sp` is pageable; once per camera
+                sc->span_key = key;
+            } else {
+                sp.clear();
+            }
+        }
+        if (!sc->span_key.empty()) row_span_dev = sc->row_span.as<int2>();
+    }
+}
+
+// What spt_render and spt_film_create both check of a plan; `who` prefixes the messages.
+void check_plan(const spt_render_params& p, const char* who) {
+    const std::string w(who);
+    if (p.width == 0 || p.height == 0 || p.spp == 0) fail(SPT_ERR_INVALID_ARG, w + ": width, height and spp must be > 0");
+    if (p.max_depth > 255) fail(SPT_ERR_UNSUPPORTED, w + ": max_depth > 255");
+    if (p.sampler > SPT_SAMPLER_RECURRENCE) fail(SPT_ERR_INVALID_ARG, w + ": unknown sampler");
+    if (p.sampler == SPT_SAMPLER_JITTERED && (p.division_x == 0 || p.division_y == 0 || p.division_x * p.division_y != p.spp))
+        fail(SPT_ERR_INVALID_ARG, w + ": jittered sampler needs spp == division_x * division_y");
+    const uint32_t shard_count = p.shard_count ? p.shard_count : 1u;
+    if (p.shard_index >= shard_count) fail(SPT_ERR_INVALID_ARG, w + ": shard_index >= shard_count");
+    if ((uint64_t)p.width * p.height > 0xffffffffull) fail(SPT_ERR_UNSUPPORTED, w + ": more than 2^32 pixels");
+}
+
+// BoxFilter (src/filter/boxf.rs:11-14): radius_int = ceil(radius - 0.5) neighbour pixels each way
+float plan_radius(const spt_render_params& p, const char* who) {
+    const float radius = (p.flags & SPT_RENDER_BOX_RADIUS) ? p.filter_radius : 0.5f;
+    if (!(radius == radius) || std::fabs(radius) > 64.0f) fail(SPT_ERR_UNSUPPORTED, std::string(who) + ": box filter radius must be finite and at most 64");
+    return radius;
+}
+
+// One window of whole image rows through the wavefront pipeline.  A shard is one window (row_base 0, the
+// strip formula of the ABI); a wide box filter renders bands of consecutive rows (w_count = w_strip = 1).
+// collect: keep every sample's radiance (3 planes [c][sample][pixel] in sc->rad) instead of summing it into
+// the film.  tgt: the samples of the plan this call adds and the sums they go to (see SampleTarget).  Returns the
+// context the resolve kernels of the caller need.
+RenderCtx trace_window(RenderRun& run, uint32_t row_base, uint32_t rows, uint32_t w_index, uint32_t w_count, uint32_t w_strip, bool collect,
+                       const SampleTarget& tgt) {
+    spt_scene* const sc = run.sc;
+    const spt_render_params& p = *run.params;
+    const spt_camera* const cam = run.cam;
+    spt_render_stats* const stats = run.stats;
+    const hipStream_t st = run.st;
+    const bool count = run.count, overlap = run.overlap, L = run.L, use_eye = run.use_eye, dyn_shadow = run.dyn_shadow, dyn_extend = run.dyn_extend;
+    const size_t lds = run.lds;
+    const uint32_t kDynBlocks = run.kDynBlocks, dyn_refill_below = run.dyn_refill_below, dyn_steps = run.dyn_steps;
+    const int2* const row_span_dev = run.row_span_dev;
+    auto begin = [&](int cls) { run.begin(cls); };
+    auto end = [&]() { run.end(); };
+    std::vector<uint32_t>& h_counts = run.h_counts;
+    uint64_t &seg_closest = run.seg_closest, &seg_shadow = run.seg_shadow, &primary_hits = run.primary_hits, &path_vertices = run.path_vertices;
+    uint64_t &shadow_first = run.shadow_first, &vertices_second = run.vertices_second;
+    const uint32_t s_end = tgt.first + tgt.count;
+    const uint64_t n_pix64 = (uint64_t)rows * p.width;
+    if (n_pix64 > 0x7fffffffull) fail(SPT_ERR_UNSUPPORTED, "render: window larger than 2^31 pixels");
+    const uint32_t n_pix = (uint32_t)n_pix64;
+    // samples per pass: keep the queues around a few million entries
+    uint32_t spp_pass = p.samples_per_pass;
+    if (spp_pass == 0) {
+        const uint64_t target = 128ull << 20;
+        spp_pass = (uint32_t)std::max<uint64_t>(1, target / n_pix);
+    }
+    spp_pass = std::min(spp_pass, tgt.count);   // (a film's increment: what is left of it)
+    // queue shards: shard s holds what the primary tiles mapped to it can emit, which also bounds
+    // every later generation of that shard
+    const uint32_t tiles_x = (p.width + kTile - 1) / kTile, tiles_y = (rows + kTile - 1) / kTile;
+    const uint32_t pix_blocks = tiles_x * tiles_y;
+    uint32_t max_tiles = 0;
+    {
+        std::vector<uint32_t> per(kShards, 0u);
+        for (uint32_t ty = 0; ty < tiles_y; ++ty)
+            for (uint32_t tx = 0; tx < tiles_x; ++tx) max_tiles = std::max(max_tiles, ++per[(tx + 9u * ty) % kShards]);
+    }
+    const uint64_t shard_cap64 = (uint64_t)max_tiles * kBlock * spp_pass;
+    const uint64_t cap64 = shard_cap64 * kShards;
+    if (cap64 > 0x7fffffffull) fail(SPT_ERR_UNSUPPORTED, "render: pass too large (lower samples_per_pass)");
+    const size_t cap = (size_t)cap64;
+    // collect: every sample of the window is kept (wide box filter), else only the samples of one pass
+    const uint64_t rad64 = (uint64_t)n_pix * (collect ? p.spp : spp_pass);
+
+    // the hit queue is binned by BxDF class for the general shade kernels (kernels.h, kClasses): class c lives c * cap
+    // entries further.  Memory is what MI355X has (24 B x cap x 8 classes = 26 GB for a 128 M-sample pass)
+    const bool fused_here = sc->fused && sc->simple && std::getenv("SPT_NO_FUSED") == nullptr;
+    const uint32_t n_classes = (!fused_here && p.max_depth > 1 && cap * (uint64_t)kClasses <= 0xffffffffull && std::getenv("SPT_NO_CLASS_QUEUES") == nullptr) ? kClasses : 1u;
+    for (int k = 0; k < 4; ++k) { sc->qa[k].ensure(cap * 16 * (k == 1 ? n_classes : 1u)); sc->qb[k].ensure(cap * 16); }   // (qa[1]: the compact bounce-0 records sit at their hit's index, in every class)
+    sc->qa[4].ensure(cap * 8);
+    sc->qb[4].ensure(cap * 8);
+    sc->hit_f4.ensure(cap * 16 * n_classes);
+    sc->hit_inst.ensure(cap * 8 * n_classes);
+    // see k_shade<.., kFused>.  Only the lean k_shade<0> variant gains: with the general kernel's 220+ VGPRs
+    // the two traversals run at 2 waves / SIMD and cfg4 is faster un-fused (4.30 vs 4.00 Gsamples/s, measured)
+    const bool fused = sc->fused && sc->simple && std::getenv("SPT_NO_FUSED") == nullptr;
+    if (fused) {
+        sc->hit_f4_next.ensure(cap * 16);
+        sc->hit_inst_next.ensure(cap * 8);
+    }
+    for (int k = 0; k < 3; ++k) sc->sh[k].ensure(cap * 16);
+    const size_t counts_words = (size_t)(p.max_depth + 1) * Q_KINDS * kShards * 32;
+    const size_t counts_bytes = counts_words * sizeof(uint32_t);
+    sc->counts.ensure(counts_bytes);
+    sc->rad.ensure((size_t)rad64 * 3 * sizeof(float));
+    float* const film_sum = tgt.sum ? tgt.sum : (sc->film.ensure((size_t)n_pix * 3 * sizeof(float)), sc->film.as<float>());
+    sc->first_slot.ensure((size_t)n_pix * sizeof(uint32_t));
+    sc->slot_bits.ensure((size_t)n_pix * ((spp_pass + 7u) / 8u));
+
+    RenderCtx rc{};
+    rc.cam.eye = f3{cam->eye[0], cam->eye[1], cam->eye[2]};
+    rc.cam.forward = f3{cam->forward[0], cam->forward[1], cam->forward[2]};
+    rc.cam.up = f3{cam->up[0], cam->up[1], cam->up[2]};
+    rc.cam.right = f3{cam->right[0], cam->right[1], cam->right[2]};
+    rc.cam.half_cot = cam->half_cot_half_fov;
+    rc.width = p.width; rc.height = p.height; rc.spp = p.spp; rc.max_depth = p.max_depth;
+    rc.sampler = p.sampler; rc.division_x = p.division_x; rc.division_y = p.division_y;
+    rc.seed = p.seed;
+    rc.shard_index = w_index; rc.shard_count = w_count; rc.strip_rows = w_strip;
+    rc.row_base = row_base;
+    rc.n_pixels = n_pix;
+    rc.rows = rows;
+    rc.tiles_x = tiles_x;
+    rc.qa = PathQueue{sc->qa[0].as<float4>(), sc->qa[1].as<float4>(), sc->qa[2].as<float4>(), sc->qa[3].as<float4>(), sc->qa[4].as<uint2>()};
+    rc.qb = PathQueue{sc->qb[0].as<float4>(), sc->qb[1].as<float4>(), sc->qb[2].as<float4>(), sc->qb[3].as<float4>(), sc->qb[4].as<uint2>()};
+    rc.hits = HitQueue{sc->hit_f4.as<float4>(), sc->hit_inst.as<uint2>()};
+    rc.hits_next = HitQueue{sc->hit_f4_next.as<float4>(), sc->hit_inst_next.as<uint2>()};
+    rc.shadow = ShadowQueue{sc->sh[0].as<float4>(), sc->sh[1].as<float4>(), sc->sh[2].as<float4>()};
+    rc.counts = sc->counts.as<uint32_t>();
+    rc.shard_cap = (uint32_t)shard_cap64;
+    rc.n_classes = n_classes;
+    rc.class_cap = (uint32_t)cap;
+    rc.rad = sc->rad.as<float>();
+    rc.film = film_sum;
+    rc.first_slot = sc->first_slot.as<uint32_t>();
+    rc.aspect = (float)p.width / (float)p.height;   // pt.rs:239
+    rc.width_inv = 1.0f / (float)p.width;           // pt.rs:250-251
+    rc.height_inv = 1.0f / (float)p.height;
+    rc.spp_inv = 1.0f / (float)p.spp;
+    {   // pt.rs:253-254, 272-275
+        const float spp_sqrt_inv = 1.0f / std::sqrt((float)p.spp);
+        rc.aux_dx = rc.aspect * rc.width_inv * spp_sqrt_inv;
+        rc.aux_dy = rc.height_inv * spp_sqrt_inv;
+    }
+    {
+        double oc[3], d2 = 0;
+        for (int k = 0; k < 3; ++k) { oc[k] = sc->bs_center[k] - (double)cam->eye[k]; d2 += oc[k] * oc[k]; }
+        rc.bs_oc = f3{(float)oc[0], (float)oc[1], (float)oc[2]};
+        // a little extra slack for the f32 rounding of oc and of the test itself
+        rc.bs_c = (float)((d2 - sc->bs_radius * sc->bs_radius) * (1.0 - 1e-5));
+        rc.bs_valid = sc->bs_valid ? 1u : 0u;
+        // screen-space bound: project the 8 corners of the union of the instance boxes (double precision).
+        // A point P is seen through image coordinates (u, v) = ((x / aspect + 0.5) W, (y + 0.5) H) with
+        // x = half_cot * (P - eye).right / (P - eye).forward, y likewise with up (k_primary: pt.rs:269-271).
+        rc.cull_i0 = 0; rc.cull_i1 = (int32_t)p.width - 1; rc.cull_j0 = 0; rc.cull_j1 = (int32_t)p.height - 1;
+        if (sc->bs_valid && std::getenv("SPT_NO_PIXEL_CULL") == nullptr) {
+            double umin = 1e300, umax = -1e300, vmin = 1e300, vmax = -1e300;
+            bool ok = true;
+            const double ext = std::max({sc->world_hi[0] - sc->world_lo[0], sc->world_hi[1] - sc->world_lo[1], sc->world_hi[2] - sc->world_lo[2], 1e-30});
+            for (int c = 0; c < 8 && ok; ++c) {
+                double v[3], z = 0, xr = 0, yu = 0;
+                for (int k = 0; k < 3; ++k) {
+                    const double pad = 1e-4 * ext;   // covers the (tiny) padding of the device-side boxes
+                    v[k] = (((c >> k) & 1) ? sc->world_hi[k] + pad : sc->world_lo[k] - pad) - (double)cam->eye[k];
+                    z += v[k] * (double)cam->forward[k];
+                    xr += v[k] * (double)cam->right[k];
+                    yu += v[k] * (double)cam->up[k];
+                }
+                if (!(z > 1e-6 * ext)) { ok = false; break; }   // a corner beside / behind the eye: no finite bound
+                const double x = (double)cam->half_cot_half_fov * xr / z, y = (double)cam->half_cot_half_fov * yu / z;
+                const double u = (x / ((double)p.width / (double)p.height) + 0.5) * (double)p.width, w = (y + 0.5) * (double)p.height;
+                umin = std::min(umin, u); umax = std::max(umax, u);
+                vmin = std::min(vmin, w); vmax = std::max(vmax, w);
+            }
+            if (ok && std::isfinite(umin) && std::isfinite(umax) && std::isfinite(vmin) && std::isfinite(vmax)) {
+                // pixel i covers u in [i, i + 1); row j covers v in [H - 1 - j, H - j); one pixel of slack each side
+                const double H = (double)p.height;
+                auto clampi = [](double x, double lo, double hi) { return (int32_t)std::max(lo, std::min(hi, x)); };
+                rc.cull_i0 = clampi(std::floor(umin) - 1.0, -1.0, (double)p.width);
+                rc.cull_i1 = clampi(std::floor(umax) + 1.0, -1.0, (double)p.width);
+                rc.cull_j0 = clampi(std::floor(H - 1.0 - vmax) - 1.0, -1.0, H);
+                rc.cull_j1 = clampi(std::floor(H - 1.0 - vmin) + 2.0, -1.0, H);
+            }
+        }
+    }
+
+    rc.dyn_refill_below = dyn_refill_below;
+    rc.dyn_steps = dyn_steps;
+    // rays of a path tracer are short (cfg5: ~4 node + ~2 triangle + ~1 instance records per segment = 2 - 3 rounds):
+    // a finished lane that waits several rounds for its wave costs more than the refill check
+    // if-if with 4 rounds per check: 87.4 ms; 8 rounds 95.2; while-while (SPT_STREAM_IFIF=0) 100 - 121 ms
+    rc.stream_rounds = std::max(1u, std::min(255u, env_u32("SPT_STREAM_ROUNDS", 4u))) | (env_u32("SPT_STREAM_IFIF", 1u) ? 0x100u : 0u);
+    rc.stream_refill_below = std::max(1u, std::min(64u, env_u32("SPT_STREAM_REFILL", 40u)));
+    rc.visits = sc->visits.as<unsigned long long>();
+    rc.debug_normal = (p.flags & SPT_RENDER_DEBUG_NORMAL) ? 1u : 0u;
+    rc.row_span = row_span_dev;
+    // tiles of this shard that intersect the screen-space bound (all of them with an environment)
+    uint32_t active_tiles = pix_blocks;
+    uint64_t live_pixels = n_pix;
+    if (sc->d.env_w == 0u) {
+        active_tiles = 0;
+        live_pixels = 0;
+        for (uint32_t r = 0; r < rows; ++r) {
+            const uint32_t strip = r / w_strip;
+            const int32_t j = (int32_t)(row_base + (strip * w_count + w_index) * w_strip + (r - strip * w_strip));
+            if (j >= rc.cull_j0 && j <= rc.cull_j1) {
+                int32_t i0 = std::max(rc.cull_i0, 0), i1 = std::min(rc.cull_i1, (int32_t)p.width - 1);
+                if (row_span_dev) { i0 = std::max(i0, sc->span_host[2 * (size_t)j]); i1 = std::min(i1, sc->span_host[2 * (size_t)j + 1]); }
+                live_pixels += (uint64_t)std::max(0, i1 - i0 + 1);
+            }
+        }
+        for (uint32_t ty = 0; ty < tiles_y; ++ty)
+            for (uint32_t tx = 0; tx < tiles_x; ++tx) {
+                const int32_t i_lo = (int32_t)(tx * kTile), i_hi = (int32_t)std::min(p.width, (tx + 1) * kTile) - 1;
+                bool rows_in = false;
+                for (uint32_t r = ty * kTile; r < std::min(rows, (ty + 1) * kTile) && !rows_in; ++r) {
+                    const uint32_t strip = r / w_strip;
+                    const int32_t j = (int32_t)(row_base + (strip * w_count + w_index) * w_strip + (r - strip * w_strip));
+                    rows_in = j >= rc.cull_j0 && j <= rc.cull_j1 && i_hi >= rc.cull_i0 && i_lo <= rc.cull_i1;
+                    if (rows_in && row_span_dev) rows_in = i_hi >= sc->span_host[2 * (size_t)j] && i_lo <= sc->span_host[2 * (size_t)j + 1];
+                }
+                if (rows_in) ++active_tiles;
+            }
+    }
+    if (tgt.zero) {
+        HIP_CHECK(hipMemsetAsync(rc.film, 0, (size_t)n_pix * 3 * sizeof(float), st));
+        if (tgt.sq) HIP_CHECK(hipMemsetAsync(tgt.sq, 0, (size_t)n_pix * 3 * sizeof(float), st));
+    }
+    if (collect) HIP_CHECK(hipMemsetAsync(sc->rad.p, 0, (size_t)rad64 * 3 * sizeof(float), st));   // pixels outside the screen bound write no slots
+    bool chunked_any = false;
+    // max_depth 0: `while curr_depth < self.max_depth` (pt.rs:48) never runs, every sample is black - environment included.
+    // Nothing is traced: the film (and, for a wide box filter, the kept samples) stay at the zeros written above.  (The
+    // passes below would mark the hits' radiance slots as owned and no shade launch would ever write them.)
+    // Passes start anywhere in the plan (a film's increment at its first uncovered sample): the slot bits, the chunks and the
+    // packed sample index of k_primary count from the pass's first sample, only the sampler sees the plan's index pass_first + s.
+    for (uint32_t s0 = tgt.first; s0 < (p.max_depth == 0u ? tgt.first : s_end); s0 += spp_pass) {
+        rc.pass_first = s0;
+        rc.pass_samples = std::min(spp_pass, s_end - s0);
+        rc.rad_plane = collect ? (size_t)p.spp * n_pix : (size_t)rc.pass_samples * n_pix;
+        rc.pack_first = (sc->d.n_instances < (1u << 20) && rc.pass_samples <= 4096u && std::getenv("SPT_NO_PACK_FIRST") == nullptr) ? 1u : 0u;
+        rc.rad = sc->rad.as<float>() + (collect ? (size_t)(s0 - tgt.first) * n_pix : 0);
+        begin(SPT_K_OTHER);
+        HIP_CHECK(hipMemsetAsync(rc.counts, 0, counts_bytes, st));
+        end();
+        begin(SPT_K_PRIMARY);
+        // sample chunks per tile: aim at ~6144 busy workgroups (24 per CU; 4096 .. 8192 measured within 2 %) given the tiles inside the screen bound
+        rc.n_tiles = pix_blocks;
+        rc.primary_chunks = 1;
+        {
+            uint32_t want = std::min<uint32_t>(64u, (6144u + active_tiles - 1u) / std::max(active_tiles, 1u));
+            if (const char* v = std::getenv("SPT_PRIMARY_CHUNKS")) want = (uint32_t)std::max(1, std::atoi(v));
+            want = std::max(1u, std::min(want, rc.pass_samples));
+            rc.chunk_samples = (rc.pass_samples + want - 1u) / want;
+            rc.chunk_samples = (rc.chunk_samples + 7u) / 8u * 8u;   // slot_bits: a group of 8 samples belongs to one chunk
+            rc.primary_chunks = (rc.pass_samples + rc.chunk_samples - 1u) / rc.chunk_samples;
+        }
+        const bool stream = sc->swalk && !L;
+        // which kernel classes the streaming walker serves (1 primary, 2 shadow, 4 extend).  Measured on cfg5, one box
+        // (gpurun_out r2j): extension rays 93.5 ms refilling state machine -> 87.4 ms streaming if-if; primary rays
+        // 8.8 -> 12.4 ms and shadow rays 9.8 -> 11.3 ms (coherent / short walks: the state machine's tighter loop wins)
+        const uint32_t stream_mask = env_u32("SPT_STREAM_MASK", SPT_WITH_BEZIER ? 6u : 4u);   // (patch scenes: shadow rays too, 214 -> 197 ms on t_catmull.json)
+        const bool stream_p = stream && (stream_mask & 1u), stream_s = stream && (stream_mask & 2u), stream_e = stream && (stream_mask & 4u);
+        rc.slot_bits = nullptr;
+        // collect: every sample owns a slot, which is what the chunked kernel does.  Moments of a scene with an environment: the
+        // un-chunked kernel adds the misses before a pixel's first hit straight into its sum, past k_resolve<true>'s Q
+        const bool all_slots = collect || (tgt.sq != nullptr && sc->d.env_w != 0u);
+        if (rc.primary_chunks > 1u || all_slots) {
+            chunked_any = true;
+            rc.slot_bits = sc->slot_bits.as<uint8_t>();
+            if (stream_p && count) hipLaunchKernelGGL((k_primary_stream<true, true>), dim3(pix_blocks * rc.primary_chunks), dim3(kBlock), lds, st, sc->d, rc);
+            else if (stream_p) hipLaunchKernelGGL((k_primary_stream<true, false>), dim3(pix_blocks * rc.primary_chunks), dim3(kBlock), lds, st, sc->d, rc);
+            else if (L && use_eye) hipLaunchKernelGGL((k_primary<true, true, false, true>), dim3(pix_blocks * rc.primary_chunks), dim3(kBlock), sc->eye_lds_bytes, st, sc->eye_d, rc);
+            else if (L) hipLaunchKernelGGL((k_primary<true, true, false>), dim3(pix_blocks * rc.primary_chunks), dim3(kBlock), lds, st, sc->d, rc);
+            else if (count) hipLaunchKernelGGL((k_primary<false, true, true>), dim3(pix_blocks * rc.primary_chunks), dim3(kBlock), lds, st, sc->d, rc);
+            else hipLaunchKernelGGL((k_primary<false, true, false>), dim3(pix_blocks * rc.primary_chunks), dim3(kBlock), lds, st, sc->d, rc);
+        } else {
+            if (stream_p && count) hipLaunchKernelGGL((k_primary_stream<false, true>), dim3(pix_blocks), dim3(kBlock), lds, st, sc->d, rc);
+            else if (stream_p) hipLaunchKernelGGL((k_primary_stream<false, false>), dim3(pix_blocks), dim3(kBlock), lds, st, sc->d, rc);
+            else if (L && use_eye) hipLaunchKernelGGL((k_primary<true, false, false, true>), dim3(pix_blocks), dim3(kBlock), sc->eye_lds_bytes, st, sc->eye_d, rc);
+            else if (L) hipLaunchKernelGGL((k_primary<true, false, false>), dim3(pix_blocks), dim3(kBlock), lds, st, sc->d, rc);
+            else if (count) hipLaunchKernelGGL((k_primary<false, false, true>), dim3(pix_blocks), dim3(kBlock), lds, st, sc->d, rc);
+            else hipLaunchKernelGGL((k_primary<false, false, false>), dim3(pix_blocks), dim3(kBlock), lds, st, sc->d, rc);
+        }
+        end();
+        for (uint32_t b = 0; b < p.max_depth; ++b) {
+            begin(b == 0 ? SPT_K_SHADE_FIRST : SPT_K_SHADE);
+            if (fused) {
+                // shade + shadow + extend of this bounce in one kernel; vertices of bounce b live in
+                // (qa, hits) for even b and in (qb, hits_next) for odd b
+                RenderCtx rb = rc;
+                if (b & 1u) { std::swap(rb.qa, rb.qb); std::swap(rb.hits, rb.hits_next); }
+                // few vertices left after bounce 0 (seen by the previous pass with a counter readback): bounce 1 and
+                // everything after it in ONE launch, each lane following its path to the end (k_shade's kLoop)
+                const bool tail_loop = b == 1 && sc->tail_vertices <= kTailLoopBelow && std::getenv("SPT_NO_TAIL_LOOP") == nullptr;
+                if (b == 0) hipLaunchKernelGGL((k_shade<0, true, true, true, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, rb, b);
+                else if (tail_loop) hipLaunchKernelGGL((k_shade<0, false, true, true, true, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, rb, b);
+                else hipLaunchKernelGGL((k_shade<0, false, true, true, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, rb, b);
+                end();
+                if (tail_loop) break;
+                continue;
+            }
+            // un-fused: the shade stage of bounce b reads the path records its predecessor wrote (ru.qa) through the
+            // hits' source indices and writes the next ones to ru.qb, which the extend stage traces: the two path
+            // queues swap roles every bounce, the hit queue is one buffer
+            RenderCtx ru = rc;
+            if (b & 1u) std::swap(ru.qa, ru.qb);
+            const bool tab = sc->lds_tables && std::getenv("SPT_NO_LDS_TABLES") == nullptr;   // shading tables from LDS (tab_ld)
+            const size_t shade_lds = sc->has_probe ? lds : 0;   // the BSSRDF probe walks the BVH inside k_shade<3 | 5>: traversal stack
+#define SPT_LAUNCH_SHADE(FEAT)                                                                                                                 \
+if (tab) {                                                                                                                                 \
+    if (b == 0) hipLaunchKernelGGL((k_shade<FEAT, true, false, true, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, ru, b);  \
+    else hipLaunchKernelGGL((k_shade<FEAT, false, false, true, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, ru, b);        \
+} else {                                                                                                                                   \
+    if (b == 0) hipLaunchKernelGGL((k_shade<FEAT, true, false, false, false>), dim3(kPersistentBlocks), dim3(kBlock), shade_lds, st, sc->d, ru, b); \
+    else hipLaunchKernelGGL((k_shade<FEAT, false, false, false, false>), dim3(kPersistentBlocks), dim3(kBlock), shade_lds, st, sc->d, ru, b);       \
+}
+            if (sc->simple) { SPT_LAUNCH_SHADE(0) } else if (!sc->textured) { SPT_LAUNCH_SHADE(1) } else if (!sc->subsurface) { SPT_LAUNCH_SHADE(2) }
+            else if (!sc->has_probe) { SPT_LAUNCH_SHADE(4) }          // glints only: no probe, so the geometry's place does not matter
+            else if (tab || !L) { if (sc->has_pndf) { SPT_LAUNCH_SHADE(5) } else { SPT_LAUNCH_SHADE(3) } }
+            else if (sc->has_pndf) {   // geometry in LDS, tables not: the probe still walks the LDS copy (k_shade's kGeoLds)
+                if (b == 0) hipLaunchKernelGGL((k_shade<5, true, false, false, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, ru, b);
+                else hipLaunchKernelGGL((k_shade<5, false, false, false, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, ru, b);
+            } else {
+                if (b == 0) hipLaunchKernelGGL((k_shade<3, true, false, false, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, ru, b);
+                else hipLaunchKernelGGL((k_shade<3, false, false, false, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, ru, b);
+            }
+#undef SPT_LAUNCH_SHADE
+            end();
+            // k_shadow(b) and k_extend(b) are independent unless the scene has an environment (then a missing
+            // extension ray adds its term to the same radiance slot the shadow ray of that vertex adds to, and
+            // the reference's order of the two additions has to be kept): without one, the shadow kernel runs on
+            // a side stream next to the extension kernel and is joined before the next stage reads the slots.
+            const bool side = overlap && b + 1 < p.max_depth;
+            hipStream_t ss = side ? sc->stream2 : st;
+            if (side) {
+                HIP_CHECK(hipEventRecord(sc->ev_fork, st));
+                HIP_CHECK(hipStreamWaitEvent(ss, sc->ev_fork, 0));
+            }
+            begin(SPT_K_SHADOW);
+            if (stream_s && count) hipLaunchKernelGGL(k_shadow_stream<true>, dim3(kDynBlocks), dim3(kBlock), lds, ss, sc->d, ru, b);
+            else if (stream_s) hipLaunchKernelGGL(k_shadow_stream<false>, dim3(kDynBlocks), dim3(kBlock), lds, ss, sc->d, ru, b);
+            else if (L && sc->d.flat) hipLaunchKernelGGL((k_shadow<true, false, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, ss, sc->d, ru, b);
+            else if (L) hipLaunchKernelGGL((k_shadow<true, false>), dim3(kPersistentBlocks), dim3(kBlock), lds, ss, sc->d, ru, b);
+            else if (dyn_shadow && count) hipLaunchKernelGGL(k_shadow_dyn<true>, dim3(kDynBlocks), dim3(kBlock), lds, ss, sc->d, ru, b);
+            else if (dyn_shadow) hipLaunchKernelGGL(k_shadow_dyn<false>, dim3(kDynBlocks), dim3(kBlock), lds, ss, sc->d, ru, b);
+            else if (count) hipLaunchKernelGGL((k_shadow<false, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, ss, sc->d, ru, b);
+            else hipLaunchKernelGGL((k_shadow<false, false>), dim3(kPersistentBlocks), dim3(kBlock), lds, ss, sc->d, ru, b);
+            end();
+            if (side) HIP_CHECK(hipEventRecord(sc->ev_join, ss));
+            if (b + 1 < p.max_depth) {
+                begin(SPT_K_EXTEND);
+                if (stream_e && count) hipLaunchKernelGGL(k_extend_stream<true>, dim3(kDynBlocks), dim3(kBlock), lds, st, sc->d, ru, b);
+                else if (stream_e) hipLaunchKernelGGL(k_extend_stream<false>, dim3(kDynBlocks), dim3(kBlock), lds, st, sc->d, ru, b);
+                else if (L && sc->d.flat) hipLaunchKernelGGL((k_extend<true, false, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, ru, b);
+                else if (L) hipLaunchKernelGGL((k_extend<true, false>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, ru, b);
+                else if (dyn_extend && count) hipLaunchKernelGGL(k_extend_dyn<true>, dim3(kDynBlocks), dim3(kBlock), lds, st, sc->d, ru, b);
+                else if (dyn_extend) hipLaunchKernelGGL(k_extend_dyn<false>, dim3(kDynBlocks), dim3(kBlock), lds, st, sc->d, ru, b);
+                else if (count) hipLaunchKernelGGL((k_extend<false, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, ru, b);
+                else hipLaunchKernelGGL((k_extend<false, false>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, ru, b);
+                end();
+            }
+            if (side) HIP_CHECK(hipStreamWaitEvent(st, sc->ev_join, 0));
+        }
+        if (!collect) {
+            begin(SPT_K_RESOLVE);
+            if (tgt.sq != nullptr && rc.slot_bits != nullptr) hipLaunchKernelGGL((k_resolve_bits<16u, true, float*>), dim3(pix_blocks), dim3(kBlock), 0, st, rc, tgt.sq);
+            else if (tgt.sq != nullptr) hipLaunchKernelGGL((k_resolve<true, float*>), dim3(pix_blocks), dim3(kBlock), 0, st, rc, tgt.sq);
+            else if (rc.slot_bits != nullptr && env_u32("SPT_RESOLVE_BATCH", 16u) == 32u) hipLaunchKernelGGL(k_resolve_bits<32u>, dim3(pix_blocks), dim3(kBlock), 0, st, rc);
+            else if (rc.slot_bits != nullptr) hipLaunchKernelGGL(k_resolve_bits<16u>, dim3(pix_blocks), dim3(kBlock), 0, st, rc);
+            else hipLaunchKernelGGL(k_resolve<>, dim3(pix_blocks), dim3(kBlock), 0, st, rc);
+            end();
+        }
+        if (stats) {
+            h_counts.resize(counts_words);
+            HIP_CHECK(hipMemcpyAsync(h_counts.data(), rc.counts, counts_bytes, hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipStreamSynchronize(st));
+            seg_closest += (uint64_t)n_pix * rc.pass_samples;
+            auto qsum = [&](uint32_t b, uint32_t q) {
+                uint64_t t = 0;
+                for (uint32_t s = 0; s < kShards; ++s) t += h_counts[((size_t)(b * Q_KINDS + q) * kShards + s) * 32];
+                if (q == Q_HIT)     // the hit queue's other classes (bounce >= 1 of the general pipeline)
+                    for (uint32_t c = 1; c < kClasses; ++c)
+                        for (uint32_t s = 0; s < kShards; ++s) t += h_counts[((size_t)(b * Q_KINDS + Q_HIT_CLASS1 + c - 1u) * kShards + s) * 32];
+                return t;
+            };
+            if (p.max_depth > 1) sc->tail_vertices = qsum(1, Q_HIT);
+            primary_hits += qsum(0, Q_HIT);
+            shadow_first += qsum(0, Q_SHADOW);
+            if (p.max_depth > 1) vertices_second += qsum(1, Q_HIT);
+            for (uint32_t b = 0; b < p.max_depth; ++b) {
+                path_vertices += qsum(b, Q_HIT);
+                seg_shadow += qsum(b, Q_SHADOW);
+                if (b + 1 < p.max_depth) seg_closest += qsum(b, Q_EXT);
+            }
+        }
+    }
+    run.samples_traced += (uint64_t)n_pix * tgt.count;
+    if (chunked_any) run.live_samples += live_pixels * tgt.count;
+    return rc;
+}
+
+}  // namespace
+
 spt_status spt_render(const spt_scene* scene_c, const spt_camera* cam, const spt_render_params* params,
                       float* rgb_mean_out, spt_render_stats* stats) {
     if (!scene_c || !cam || !params || !rgb_mean_out) { g_error = "render: null argument"; return SPT_ERR_INVALID_ARG; }
@@ -1437,14 +2014,8 @@ spt_status spt_render(const spt_scene* scene_c, const spt_camera* cam, const spt
     std::lock_guard<std::mutex> lock(sc->mu);
     try {
         const spt_render_params& p = *params;
-        if (p.width == 0 || p.height == 0 || p.spp == 0) fail(SPT_ERR_INVALID_ARG, "render: width, height and spp must be > 0");
-        if (p.max_depth > 255) fail(SPT_ERR_UNSUPPORTED, "render: max_depth > 255");
-        if (p.sampler > SPT_SAMPLER_RECURRENCE) fail(SPT_ERR_INVALID_ARG, "render: unknown sampler");
-        if (p.sampler == SPT_SAMPLER_JITTERED && (p.division_x == 0 || p.division_y == 0 || p.division_x * p.division_y != p.spp))
-            fail(SPT_ERR_INVALID_ARG, "render: jittered sampler needs spp == division_x * division_y");
+        check_plan(p, "render");
         const uint32_t shard_count = p.shard_count ? p.shard_count : 1u, strip_rows = p.strip_rows ? p.strip_rows : 1u;
-        if (p.shard_index >= shard_count) fail(SPT_ERR_INVALID_ARG, "render: shard_index >= shard_count");
-        if ((uint64_t)p.width * p.height > 0xffffffffull) fail(SPT_ERR_UNSUPPORTED, "render: more than 2^32 pixels");
         const uint32_t own_rows = shard_row_count(p);
         const uint64_t own_pix64 = (uint64_t)own_rows * p.width;
         const bool async_out = (p.flags & SPT_RENDER_ASYNC) != 0;
@@ -1469,481 +2040,32 @@ spt_status spt_render(const spt_scene* scene_c, const spt_camera* cam, const spt
         if (own_pix64 == 0) return SPT_OK;
         if (own_pix64 > 0x7fffffffull) fail(SPT_ERR_UNSUPPORTED, "render: shard larger than 2^31 pixels");
         const uint32_t own_pix = (uint32_t)own_pix64;
-        // BoxFilter (src/filter/boxf.rs:11-14): radius_int = ceil(radius - 0.5) neighbour pixels each way
-        const float radius = (p.flags & SPT_RENDER_BOX_RADIUS) ? p.filter_radius : 0.5f;
-        if (!(radius == radius) || std::fabs(radius) > 64.0f) fail(SPT_ERR_UNSUPPORTED, "render: box filter radius must be finite and at most 64");
+        const float radius = plan_radius(p, "render");
         const int32_t R = (int32_t)std::ceil(radius - 0.5f);
         HIP_CHECK(hipSetDevice(sc->device));
         sc->out.ensure((size_t)own_pix * 3 * sizeof(float));
 
-        hipStream_t st = sc->stream;
-        const bool profile = (p.flags & SPT_RENDER_PROFILE) != 0;
-        // visit counters: only the kernels that fetch their geometry from memory count (an LDS-resident scene is read once
-        // per workgroup whatever the rays do)
-        const bool count = (p.flags & SPT_RENDER_COUNT_VISITS) != 0 && !sc->lds_geo;
-        sc->visits.ensure(12 * sizeof(unsigned long long));
-        if (count) HIP_CHECK(hipMemsetAsync(sc->visits.p, 0, 12 * sizeof(unsigned long long), sc->stream));
-        // per-kernel event timing needs one stream; so does a scene with an environment (see the bounce loop)
-        const bool overlap = !profile && sc->d.env_w == 0u && std::getenv("SPT_NO_OVERLAP") == nullptr;
-        const size_t lds = sc->lds_bytes;
-        const bool L = sc->lds_geo;
-        // primary rays of an LDS-resident scene through the eye-relative copy of its geometry (eye.h), remade when the eye has moved
-        const bool use_eye = L && !count && sc->eye_ok && std::getenv("SPT_NO_EYE_BLOB") == nullptr;
-        if (use_eye && (!sc->eye_valid || std::memcmp(sc->eye_key, cam->eye, sizeof(sc->eye_key)) != 0)) make_eye_blob(sc, cam->eye);
-        // refilling persistent waves for large scenes: on for shadow rays (any-hit walks end at very
-        // different times: 10.9 -> 8.8 ms on the 1 M-triangle scene), off for extension rays (28 vs 20 ms)
-        const bool dyn_shadow = !L && std::getenv("SPT_NO_DYN_SHADOW") == nullptr;
-        // (with the 2-wide nodes the refilling extension kernel was slower, 28 vs 20 ms; with the 4-wide nodes it is
-        //  faster, 16.0 vs 17.7 ms on cfg5 - measured - and on by default)
-        const bool dyn_extend = !L && std::getenv("SPT_NO_DYN_EXTEND") == nullptr;
-        auto env_u32 = [](const char* name, uint32_t dflt) { const char* v = std::getenv(name); return v ? (uint32_t)std::atoi(v) : dflt; };
-        const uint32_t kDynBlocks = env_u32("SPT_DYN_BLOCKS", 2048);   // persistent blocks that pull work
-        const uint32_t dyn_refill_below = env_u32("SPT_DYN_REFILL", kRefillBelow), dyn_steps = env_u32("SPT_DYN_STEPS", kStepsPerCheck);
-        struct Span { int cls; size_t e0; };
-        std::vector<Span> spans;
-        size_t ev_used = 0;
-        auto get_event = [&]() -> hipEvent_t {
-            if (ev_used == sc->events.size()) {
-                hipEvent_t e;
-                HIP_CHECK(hipEventCreate(&e));
-                sc->events.push_back(e);
-            }
-            return sc->events[ev_used++];
-        };
-        auto begin = [&](int cls) {
-            if (!profile) return;
-            spans.push_back(Span{cls, ev_used});
-            HIP_CHECK(hipEventRecord(get_event(), st));
-        };
-        auto end = [&]() {
-            if (!profile) return;
-            HIP_CHECK(hipEventRecord(get_event(), st));
-        };
-        hipEvent_t ev_total0 = get_event(), ev_total1 = get_event();
+        RenderRun run;
+        run.sc = sc;
+        run.cam = cam;
+        run.params = &p;
+        run.stats = stats;
+        run_setup(run);
+        const hipStream_t st = run.st;
+        const bool count = run.count;
+        hipEvent_t ev_total0 = run.get_event(), ev_total1 = run.get_event();
         HIP_CHECK(hipEventRecord(ev_total0, st));
-        std::vector<uint32_t> h_counts;
-        uint64_t seg_closest = 0, seg_shadow = 0, primary_hits = 0, path_vertices = 0, shadow_first = 0, vertices_second = 0;
-        uint64_t samples_traced = 0, live_samples = 0;
-        // Per-row screen-space spans: every instance's object-space box (8 world-space corners, spt_scene_create) is
-        // projected, the convex hull of the 8 image points is the exact silhouette of the box, and row j keeps the pixels
-        // from the leftmost to the rightmost hull point within one row of slack above and below, plus one pixel each side.
-        // A pixel outside its row's span cannot see any instance with any sample (k_primary's `in_bounds`): the rotated
-        // cube of the headline scene fills 19 % of the image, its world-space AABB's rectangle 25 %.
-        const int2* row_span_dev = nullptr;
-        if (!sc->hull_corners.empty() && sc->d.env_w == 0u && std::getenv("SPT_NO_PIXEL_CULL") == nullptr && std::getenv("SPT_NO_ROW_SPANS") == nullptr) {
-            std::vector<double> key = {(double)p.width, (double)p.height, (double)cam->half_cot_half_fov};
-            for (int k = 0; k < 3; ++k) { key.push_back(cam->eye[k]); key.push_back(cam->forward[k]); key.push_back(cam->up[k]); key.push_back(cam->right[k]); }
-            if (key != sc->span_key) {
-                sc->span_key.clear();
-                std::vector<int32_t>& sp = sc->span_host;
-                sp.assign((size_t)p.height * 2, 0);
-                for (uint32_t j = 0; j < p.height; ++j) { sp[2 * j] = (int32_t)p.width; sp[2 * j + 1] = -1; }
-                const double W = (double)p.width, H = (double)p.height, aspect = W / H;
-                bool ok = true;
-                for (const auto& cn : sc->hull_corners) {
-                    double px[8], py[8];
-                    for (int c = 0; c < 8 && ok; ++c) {
-                        double z = 0, xr = 0, yu = 0, n2 = 0;
-                        for (int k = 0; k < 3; ++k) {
-                            const double v = cn[3 * c + k] - (double)cam->eye[k];
-                            z += v * (double)cam->forward[k]; xr += v * (double)cam->right[k]; yu += v * (double)cam->up[k]; n2 += v * v;
-                        }
-                        if (!(z > 1e-6 * std::sqrt(n2)) || !(z > 0)) { ok = false; break; }   // beside / behind the eye: no finite silhouette
-                        const double x = (double)cam->half_cot_half_fov * xr / z, y = (double)cam->half_cot_half_fov * yu / z;
-                        px[c] = (x / aspect + 0.5) * W;                 // pixel i covers [i, i + 1)
-                        py[c] = H - (y + 0.5) * H;                     // row j covers (j, j + 1]  (k_primary: y = ((H - j - 1) + oy) / H - 0.5)
-                        ok = std::isfinite(px[c]) && std::isfinite(py[c]) && std::fabs(px[c]) < 1e9 && std::fabs(py[c]) < 1e9;
-                    }
-                    if (!ok) break;
-                    // convex hull (monotone chain)
-                    int idx[8];
-                    for (int c = 0; c < 8; ++c) idx[c] = c;
-                    std::sort(idx, idx + 8, [&](int a, int b) { return px[a] < px[b] || (px[a] == px[b] && py[a] < py[b]); });
-                    int hull[17], hn = 0;
-                    auto crs = [&](int o, int a, int b) { return (px[a] - px[o]) * (py[b] - py[o]) - (py[a] - py[o]) * (px[b] - px[o]); };
-                    for (int c = 0; c < 8; ++c) { while (hn >= 2 && crs(hull[hn - 2], hull[hn - 1], idx[c]) <= 0) --hn; hull[hn++] = idx[c]; }
-                    for (int c = 6, lower = hn + 1; c >= 0; --c) { while (hn >= lower && crs(hull[hn - 2], hull[hn - 1], idx[c]) <= 0) --hn; hull[hn++] = idx[c]; }
-                    if (hn > 1) --hn;      // the last point repeats the first
-                    double ymin = 1e300, ymax = -1e300;
-                    for (int c = 0; c < hn; ++c) { ymin = std::min(ymin, py[hull[c]]); ymax = std::max(ymax, py[hull[c]]); }
-                    const int64_t j0 = std::max<int64_t>(0, (int64_t)std::floor(ymin) - 2), j1 = std::min<int64_t>((int64_t)p.height - 1, (int64_t)std::floor(ymax) + 2);
-                    for (int64_t j = j0; j <= j1; ++j) {
-                        const double ya = (double)j - 1.0, yb = (double)j + 2.0;    // the row's own band (j, j + 1] and one row of slack each way
-                        double xmin = 1e300, xmax = -1e300;
-                        for (int c = 0; c < hn; ++c) {
-                            const int a = hull[c], b = hull[(c + 1) % hn];
-                            double xa = px[a], yA = py[a], xb = px[b], yB = py[b];
-                            if (yA > yB) { std::swap(xa, xb); std::swap(yA, yB); }
-                            if (yB < ya || yA > yb) continue;
-                            double x0 = xa, x1 = xb;
-                            if (yB > yA) {      // clip the edge to the band
-                                const double t0 = std::max(0.0, (ya - yA) / (yB - yA)), t1 = std::min(1.0, (yb - yA) / (yB - yA));
-                                x0 = xa + (xb - xa) * t0; x1 = xa + (xb - xa) * t1;
-                            }
-                            xmin = std::min({xmin, x0, x1}); xmax = std::max({xmax, x0, x1});
-                        }
-                        if (xmin > xmax) continue;
-                        const int32_t lo = (int32_t)std::max(-1.0, std::min(W, std::floor(xmin) - 1.0)), hi = (int32_t)std::max(-1.0, std::min(W, std::floor(xmax) + 1.0));
-                        sp[2 * j] = std::min(sp[2 * j], lo);
-                        sp[2 * j + 1] = std::max(sp[2 * j + 1], hi);
-                    }
-                }
-                if (ok) {
-                    sc->row_span.ensure((size_t)p.height * 2 * sizeof(int32_t));
-                    HIP_CHECK(hipMemcpyAsync(sc->row_span.p, sp.data(), (size_t)p.height * 2 * sizeof(int32_t), hipMemcpyHostToDevice, sc->stream));
-                    HIP_CHECK(hipStreamSynchronize(sc->stream));   // `sp` is pageable; once per camera
-                    sc->span_key = key;
-                } else {
-                    sp.clear();
-                }
-            }
-            if (!sc->span_key.empty()) row_span_dev = sc->row_span.as<int2>();
-        }
-        // One window of whole image rows through the wavefront pipeline.  A shard is one window (row_base 0, the
-        // strip formula of the ABI); a wide box filter renders bands of consecutive rows (w_count = w_strip = 1).
-        // collect: keep every sample's radiance (3 planes [c][sample][pixel] in sc->rad) instead of summing it into
-        // the film.  Returns the context the resolve kernels of the caller need.
-        auto trace_window = [&](uint32_t row_base, uint32_t rows, uint32_t w_index, uint32_t w_count, uint32_t w_strip, bool collect) -> RenderCtx {
-            const uint64_t n_pix64 = (uint64_t)rows * p.width;
-            if (n_pix64 > 0x7fffffffull) fail(SPT_ERR_UNSUPPORTED, "render: window larger than 2^31 pixels");
-            const uint32_t n_pix = (uint32_t)n_pix64;
-            // samples per pass: keep the queues around a few million entries
-            uint32_t spp_pass = p.samples_per_pass;
-            if (spp_pass == 0) {
-                const uint64_t target = 128ull << 20;
-                spp_pass = (uint32_t)std::max<uint64_t>(1, target / n_pix);
-            }
-            spp_pass = std::min(spp_pass, p.spp);
-            // queue shards: shard s holds what the primary tiles mapped to it can emit, which also bounds
-            // every later generation of that shard
-            const uint32_t tiles_x = (p.width + kTile - 1) / kTile, tiles_y = (rows + kTile - 1) / kTile;
-            const uint32_t pix_blocks = tiles_x * tiles_y;
-            uint32_t max_tiles = 0;
-            {
-                std::vector<uint32_t> per(kShards, 0u);
-                for (uint32_t ty = 0; ty < tiles_y; ++ty)
-                    for (uint32_t tx = 0; tx < tiles_x; ++tx) max_tiles = std::max(max_tiles, ++per[(tx + 9u * ty) % kShards]);
-            }
-            const uint64_t shard_cap64 = (uint64_t)max_tiles * kBlock * spp_pass;
-            const uint64_t cap64 = shard_cap64 * kShards;
-            if (cap64 > 0x7fffffffull) fail(SPT_ERR_UNSUPPORTED, "render: pass too large (lower samples_per_pass)");
-            const size_t cap = (size_t)cap64;
-            // collect: every sample of the window is kept (wide box filter), else only the samples of one pass
-            const uint64_t rad64 = (uint64_t)n_pix * (collect ? p.spp : spp_pass);
-
-            // the hit queue is binned by BxDF class for the general shade kernels (kernels.h, kClasses): class c lives c * cap
-            // entries further.  Memory is what MI355X has (24 B x cap x 8 classes = 26 GB for a 128 M-sample pass)
-            const bool fused_here = sc->fused && sc->simple && std::getenv("SPT_NO_FUSED") == nullptr;
-            const uint32_t n_classes = (!fused_here && p.max_depth > 1 && cap * (uint64_t)kClasses <= 0xffffffffull && std::getenv("SPT_NO_CLASS_QUEUES") == nullptr) ? kClasses : 1u;
-            for (int k = 0; k < 4; ++k) { sc->qa[k].ensure(cap * 16 * (k == 1 ? n_classes : 1u)); sc->qb[k].ensure(cap * 16); }   // (qa[1]: the compact bounce-0 records sit at their hit's index, in every class)
-            sc->qa[4].ensure(cap * 8);
-            sc->qb[4].ensure(cap * 8);
-            sc->hit_f4.ensure(cap * 16 * n_classes);
-            sc->hit_inst.ensure(cap * 8 * n_classes);
-            // see k_shade<.., kFused>.  Only the lean k_shade<0> variant gains: with the general kernel's 220+ VGPRs
-            // the two traversals run at 2 waves / SIMD and cfg4 is faster un-fused (4.30 vs 4.00 Gsamples/s, measured)
-            const bool fused = sc->fused && sc->simple && std::getenv("SPT_NO_FUSED") == nullptr;
-            if (fused) {
-                sc->hit_f4_next.ensure(cap * 16);
-                sc->hit_inst_next.ensure(cap * 8);
-            }
-            for (int k = 0; k < 3; ++k) sc->sh[k].ensure(cap * 16);
-            const size_t counts_words = (size_t)(p.max_depth + 1) * Q_KINDS * kShards * 32;
-            const size_t counts_bytes = counts_words * sizeof(uint32_t);
-            sc->counts.ensure(counts_bytes);
-            sc->rad.ensure((size_t)rad64 * 3 * sizeof(float));
-            sc->film.ensure((size_t)n_pix * 3 * sizeof(float));
-            sc->first_slot.ensure((size_t)n_pix * sizeof(uint32_t));
-            sc->slot_bits.ensure((size_t)n_pix * ((spp_pass + 7u) / 8u));
-
-            RenderCtx rc{};
-            rc.cam.eye = f3{cam->eye[0], cam->eye[1], cam->eye[2]};
-            rc.cam.forward = f3{cam->forward[0], cam->forward[1], cam->forward[2]};
-            rc.cam.up = f3{cam->up[0], cam->up[1], cam->up[2]};
-            rc.cam.right = f3{cam->right[0], cam->right[1], cam->right[2]};
-            rc.cam.half_cot = cam->half_cot_half_fov;
-            rc.width = p.width; rc.height = p.height; rc.spp = p.spp; rc.max_depth = p.max_depth;
-            rc.sampler = p.sampler; rc.division_x = p.division_x; rc.division_y = p.division_y;
-            rc.seed = p.seed;
-            rc.shard_index = w_index; rc.shard_count = w_count; rc.strip_rows = w_strip;
-            rc.row_base = row_base;
-            rc.n_pixels = n_pix;
-            rc.rows = rows;
-            rc.tiles_x = tiles_x;
-            rc.qa = PathQueue{sc->qa[0].as<float4>(), sc->qa[1].as<float4>(), sc->qa[2].as<float4>(), sc->qa[3].as<float4>(), sc->qa[4].as<uint2>()};
-            rc.qb = PathQueue{sc->qb[0].as<float4>(), sc->qb[1].as<float4>(), sc->qb[2].as<float4>(), sc->qb[3].as<float4>(), sc->qb[4].as<uint2>()};
-            rc.hits = HitQueue{sc->hit_f4.as<float4>(), sc->hit_inst.as<uint2>()};
-            rc.hits_next = HitQueue{sc->hit_f4_next.as<float4>(), sc->hit_inst_next.as<uint2>()};
-            rc.shadow = ShadowQueue{sc->sh[0].as<float4>(), sc->sh[1].as<float4>(), sc->sh[2].as<float4>()};
-            rc.counts = sc->counts.as<uint32_t>();
-            rc.shard_cap = (uint32_t)shard_cap64;
-            rc.n_classes = n_classes;
-            rc.class_cap = (uint32_t)cap;
-            rc.rad = sc->rad.as<float>();
-            rc.film = sc->film.as<float>();
-            rc.first_slot = sc->first_slot.as<uint32_t>();
-            rc.aspect = (float)p.width / (float)p.height;   // pt.rs:239
-            rc.width_inv = 1.0f / (float)p.width;           // pt.rs:250-251
-            rc.height_inv = 1.0f / (float)p.height;
-            rc.spp_inv = 1.0f / (float)p.spp;
-            {   // pt.rs:253-254, 272-275
-                const float spp_sqrt_inv = 1.0f / std::sqrt((float)p.spp);
-                rc.aux_dx = rc.aspect * rc.width_inv * spp_sqrt_inv;
-                rc.aux_dy = rc.height_inv * spp_sqrt_inv;
-            }
-            {
-                double oc[3], d2 = 0;
-                for (int k = 0; k < 3; ++k) { oc[k] = sc->bs_center[k] - (double)cam->eye[k]; d2 += oc[k] * oc[k]; }
-                rc.bs_oc = f3{(float)oc[0], (float)oc[1], (float)oc[2]};
-                // a little extra slack for the f32 rounding of oc and of the test itself
-                rc.bs_c = (float)((d2 - sc->bs_radius * sc->bs_radius) * (1.0 - 1e-5));
-                rc.bs_valid = sc->bs_valid ? 1u : 0u;
-                // screen-space bound: project the 8 corners of the union of the instance boxes (double precision).
-                // A point P is seen through image coordinates (u, v) = ((x / aspect + 0.5) W, (y + 0.5) H) with
-                // x = half_cot * (P - eye).right / (P - eye).forward, y likewise with up (k_primary: pt.rs:269-271).
-                rc.cull_i0 = 0; rc.cull_i1 = (int32_t)p.width - 1; rc.cull_j0 = 0; rc.cull_j1 = (int32_t)p.height - 1;
-                if (sc->bs_valid && std::getenv("SPT_NO_PIXEL_CULL") == nullptr) {
-                    double umin = 1e300, umax = -1e300, vmin = 1e300, vmax = -1e300;
-                    bool ok = true;
-                    const double ext = std::max({sc->world_hi[0] - sc->world_lo[0], sc->world_hi[1] - sc->world_lo[1], sc->world_hi[2] - sc->world_lo[2], 1e-30});
-                    for (int c = 0; c < 8 && ok; ++c) {
-                        double v[3], z = 0, xr = 0, yu = 0;
-                        for (int k = 0; k < 3; ++k) {
-                            const double pad = 1e-4 * ext;   // covers the (tiny) padding of the device-side boxes
-                            v[k] = (((c >> k) & 1) ? sc->world_hi[k] + pad : sc->world_lo[k] - pad) - (double)cam->eye[k];
-                            z += v[k] * (double)cam->forward[k];
-                            xr += v[k] * (double)cam->right[k];
-                            yu += v[k] * (double)cam->up[k];
-                        }
-                        if (!(z > 1e-6 * ext)) { ok = false; break; }   // a corner beside / behind the eye: no finite bound
-                        const double x = (double)cam->half_cot_half_fov * xr / z, y = (double)cam->half_cot_half_fov * yu / z;
-                        const double u = (x / ((double)p.width / (double)p.height) + 0.5) * (double)p.width, w = (y + 0.5) * (double)p.height;
-                        umin = std::min(umin, u); umax = std::max(umax, u);
-                        vmin = std::min(vmin, w); vmax = std::max(vmax, w);
-                    }
-                    if (ok && std::isfinite(umin) && std::isfinite(umax) && std::isfinite(vmin) && std::isfinite(vmax)) {
-                        // pixel i covers u in [i, i + 1); row j covers v in [H - 1 - j, H - j); one pixel of slack each side
-                        const double H = (double)p.height;
-                        auto clampi = [](double x, double lo, double hi) { return (int32_t)std::max(lo, std::min(hi, x)); };
-                        rc.cull_i0 = clampi(std::floor(umin) - 1.0, -1.0, (double)p.width);
-                        rc.cull_i1 = clampi(std::floor(umax) + 1.0, -1.0, (double)p.width);
-                        rc.cull_j0 = clampi(std::floor(H - 1.0 - vmax) - 1.0, -1.0, H);
-                        rc.cull_j1 = clampi(std::floor(H - 1.0 - vmin) + 2.0, -1.0, H);
-                    }
-                }
-            }
-
-            rc.dyn_refill_below = dyn_refill_below;
-            rc.dyn_steps = dyn_steps;
-            // rays of a path tracer are short (cfg5: ~4 node + ~2 triangle + ~1 instance records per segment = 2 - 3 rounds):
-            // a finished lane that waits several rounds for its wave costs more than the refill check
-            // if-if with 4 rounds per check: 87.4 ms; 8 rounds 95.2; while-while (SPT_STREAM_IFIF=0) 100 - 121 ms
-            rc.stream_rounds = std::max(1u, std::min(255u, env_u32("SPT_STREAM_ROUNDS", 4u))) | (env_u32("SPT_STREAM_IFIF", 1u) ? 0x100u : 0u);
-            rc.stream_refill_below = std::max(1u, std::min(64u, env_u32("SPT_STREAM_REFILL", 40u)));
-            rc.visits = sc->visits.as<unsigned long long>();
-            rc.debug_normal = (p.flags & SPT_RENDER_DEBUG_NORMAL) ? 1u : 0u;
-            rc.row_span = row_span_dev;
-            // tiles of this shard that intersect the screen-space bound (all of them with an environment)
-            uint32_t active_tiles = pix_blocks;
-            uint64_t live_pixels = n_pix;
-            if (sc->d.env_w == 0u) {
-                active_tiles = 0;
-                live_pixels = 0;
-                for (uint32_t r = 0; r < rows; ++r) {
-                    const uint32_t strip = r / w_strip;
-                    const int32_t j = (int32_t)(row_base + (strip * w_count + w_index) * w_strip + (r - strip * w_strip));
-                    if (j >= rc.cull_j0 && j <= rc.cull_j1) {
-                        int32_t i0 = std::max(rc.cull_i0, 0), i1 = std::min(rc.cull_i1, (int32_t)p.width - 1);
-                        if (row_span_dev) { i0 = std::max(i0, sc->span_host[2 * (size_t)j]); i1 = std::min(i1, sc->span_host[2 * (size_t)j + 1]); }
-                        live_pixels += (uint64_t)std::max(0, i1 - i0 + 1);
-                    }
-                }
-                for (uint32_t ty = 0; ty < tiles_y; ++ty)
-                    for (uint32_t tx = 0; tx < tiles_x; ++tx) {
-                        const int32_t i_lo = (int32_t)(tx * kTile), i_hi = (int32_t)std::min(p.width, (tx + 1) * kTile) - 1;
-                        bool rows_in = false;
-                        for (uint32_t r = ty * kTile; r < std::min(rows, (ty + 1) * kTile) && !rows_in; ++r) {
-                            const uint32_t strip = r / w_strip;
-                            const int32_t j = (int32_t)(row_base + (strip * w_count + w_index) * w_strip + (r - strip * w_strip));
-                            rows_in = j >= rc.cull_j0 && j <= rc.cull_j1 && i_hi >= rc.cull_i0 && i_lo <= rc.cull_i1;
-                            if (rows_in && row_span_dev) rows_in = i_hi >= sc->span_host[2 * (size_t)j] && i_lo <= sc->span_host[2 * (size_t)j + 1];
-                        }
-                        if (rows_in) ++active_tiles;
-                    }
-            }
-            HIP_CHECK(hipMemsetAsync(rc.film, 0, (size_t)n_pix * 3 * sizeof(float), st));
-            if (collect) HIP_CHECK(hipMemsetAsync(sc->rad.p, 0, (size_t)rad64 * 3 * sizeof(float), st));   // pixels outside the screen bound write no slots
-            bool chunked_any = false;
-            // max_depth 0: `while curr_depth < self.max_depth` (pt.rs:48) never runs, every sample is black - environment included.
-            // Nothing is traced: the film (and, for a wide box filter, the kept samples) stay at the zeros written above.  (The
-            // passes below would mark the hits' radiance slots as owned and no shade launch would ever write them.)
-            for (uint32_t s0 = 0; s0 < (p.max_depth == 0u ? 0u : p.spp); s0 += spp_pass) {
-                rc.pass_first = s0;
-                rc.pass_samples = std::min(spp_pass, p.spp - s0);
-                rc.rad_plane = collect ? (size_t)p.spp * n_pix : (size_t)rc.pass_samples * n_pix;
-                rc.pack_first = (sc->d.n_instances < (1u << 20) && rc.pass_samples <= 4096u && std::getenv("SPT_NO_PACK_FIRST") == nullptr) ? 1u : 0u;
-                rc.rad = sc->rad.as<float>() + (collect ? (size_t)s0 * n_pix : 0);
-                begin(SPT_K_OTHER);
-                HIP_CHECK(hipMemsetAsync(rc.counts, 0, counts_bytes, st));
-                end();
-                begin(SPT_K_PRIMARY);
-                // sample chunks per tile: aim at ~6144 busy workgroups (24 per CU; 4096 .. 8192 measured within 2 %) given the tiles inside the screen bound
-                rc.n_tiles = pix_blocks;
-                rc.primary_chunks = 1;
-                {
-                    uint32_t want = std::min<uint32_t>(64u, (6144u + active_tiles - 1u) / std::max(active_tiles, 1u));
-                    if (const char* v = std::getenv("SPT_PRIMARY_CHUNKS")) want = (uint32_t)std::max(1, std::atoi(v));
-                    want = std::max(1u, std::min(want, rc.pass_samples));
-                    rc.chunk_samples = (rc.pass_samples + want - 1u) / want;
-                    rc.chunk_samples = (rc.chunk_samples + 7u) / 8u * 8u;   // slot_bits: a group of 8 samples belongs to one chunk
-                    rc.primary_chunks = (rc.pass_samples + rc.chunk_samples - 1u) / rc.chunk_samples;
-                }
-                const bool stream = sc->swalk && !L;
-                // which kernel classes the streaming walker serves (1 primary, 2 shadow, 4 extend).  Measured on cfg5, one box
-                // (gpurun_out r2j): extension rays 93.5 ms refilling state machine -> 87.4 ms streaming if-if; primary rays
-                // 8.8 -> 12.4 ms and shadow rays 9.8 -> 11.3 ms (coherent / short walks: the state machine's tighter loop wins)
-                const uint32_t stream_mask = env_u32("SPT_STREAM_MASK", SPT_WITH_BEZIER ? 6u : 4u);   // (patch scenes: shadow rays too, 214 -> 197 ms on t_catmull.json)
-                const bool stream_p = stream && (stream_mask & 1u), stream_s = stream && (stream_mask & 2u), stream_e = stream && (stream_mask & 4u);
-                rc.slot_bits = nullptr;
-                if (rc.primary_chunks > 1u || collect) {   // collect: every sample owns a slot, which is what the chunked kernel does
-                    chunked_any = true;
-                    rc.slot_bits = sc->slot_bits.as<uint8_t>();
-                    if (stream_p && count) hipLaunchKernelGGL((k_primary_stream<true, true>), dim3(pix_blocks * rc.primary_chunks), dim3(kBlock), lds, st, sc->d, rc);
-                    else if (stream_p) hipLaunchKernelGGL((k_primary_stream<true, false>), dim3(pix_blocks * rc.primary_chunks), dim3(kBlock), lds, st, sc->d, rc);
-                    else if (L && use_eye) hipLaunchKernelGGL((k_primary<true, true, false, true>), dim3(pix_blocks * rc.primary_chunks), dim3(kBlock), sc->eye_lds_bytes, st, sc->eye_d, rc);
-                    else if (L) hipLaunchKernelGGL((k_primary<true, true, false>), dim3(pix_blocks * rc.primary_chunks), dim3(kBlock), lds, st, sc->d, rc);
-                    else if (count) hipLaunchKernelGGL((k_primary<false, true, true>), dim3(pix_blocks * rc.primary_chunks), dim3(kBlock), lds, st, sc->d, rc);
-                    else hipLaunchKernelGGL((k_primary<false, true, false>), dim3(pix_blocks * rc.primary_chunks), dim3(kBlock), lds, st, sc->d, rc);
-                } else {
-                    if (stream_p && count) hipLaunchKernelGGL((k_primary_stream<false, true>), dim3(pix_blocks), dim3(kBlock), lds, st, sc->d, rc);
-                    else if (stream_p) hipLaunchKernelGGL((k_primary_stream<false, false>), dim3(pix_blocks), dim3(kBlock), lds, st, sc->d, rc);
-                    else if (L && use_eye) hipLaunchKernelGGL((k_primary<true, false, false, true>), dim3(pix_blocks), dim3(kBlock), sc->eye_lds_bytes, st, sc->eye_d, rc);
-                    else if (L) hipLaunchKernelGGL((k_primary<true, false, false>), dim3(pix_blocks), dim3(kBlock), lds, st, sc->d, rc);
-                    else if (count) hipLaunchKernelGGL((k_primary<false, false, true>), dim3(pix_blocks), dim3(kBlock), lds, st, sc->d, rc);
-                    else hipLaunchKernelGGL((k_primary<false, false, false>), dim3(pix_blocks), dim3(kBlock), lds, st, sc->d, rc);
-                }
-                end();
-                for (uint32_t b = 0; b < p.max_depth; ++b) {
-                    begin(b == 0 ? SPT_K_SHADE_FIRST : SPT_K_SHADE);
-                    if (fused) {
-                        // shade + shadow + extend of this bounce in one kernel; vertices of bounce b live in
-                        // (qa, hits) for even b and in (qb, hits_next) for odd b
-                        RenderCtx rb = rc;
-                        if (b & 1u) { std::swap(rb.qa, rb.qb); std::swap(rb.hits, rb.hits_next); }
-                        // few vertices left after bounce 0 (seen by the previous pass with a counter readback): bounce 1 and
-                        // everything after it in ONE launch, each lane following its path to the end (k_shade's kLoop)
-                        const bool tail_loop = b == 1 && sc->tail_vertices <= kTailLoopBelow && std::getenv("SPT_NO_TAIL_LOOP") == nullptr;
-                        if (b == 0) hipLaunchKernelGGL((k_shade<0, true, true, true, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, rb, b);
-                        else if (tail_loop) hipLaunchKernelGGL((k_shade<0, false, true, true, true, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, rb, b);
-                        else hipLaunchKernelGGL((k_shade<0, false, true, true, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, rb, b);
-                        end();
-                        if (tail_loop) break;
-                        continue;
-                    }
-                    // un-fused: the shade stage of bounce b reads the path records its predecessor wrote (ru.qa) through the
-                    // hits' source indices and writes the next ones to ru.qb, which the extend stage traces: the two path
-                    // queues swap roles every bounce, the hit queue is one buffer
-                    RenderCtx ru = rc;
-                    if (b & 1u) std::swap(ru.qa, ru.qb);
-                    const bool tab = sc->lds_tables && std::getenv("SPT_NO_LDS_TABLES") == nullptr;   // shading tables from LDS (tab_ld)
-                    const size_t shade_lds = sc->has_probe ? lds : 0;   // the BSSRDF probe walks the BVH inside k_shade<3 | 5>: traversal stack
-#define SPT_LAUNCH_SHADE(FEAT)                                                                                                                 \
-        if (tab) {                                                                                                                                 \
-            if (b == 0) hipLaunchKernelGGL((k_shade<FEAT, true, false, true, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, ru, b);  \
-            else hipLaunchKernelGGL((k_shade<FEAT, false, false, true, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, ru, b);        \
-        } else {                                                                                                                                   \
-            if (b == 0) hipLaunchKernelGGL((k_shade<FEAT, true, false, false, false>), dim3(kPersistentBlocks), dim3(kBlock), shade_lds, st, sc->d, ru, b); \
-            else hipLaunchKernelGGL((k_shade<FEAT, false, false, false, false>), dim3(kPersistentBlocks), dim3(kBlock), shade_lds, st, sc->d, ru, b);       \
-        }
-                    if (sc->simple) { SPT_LAUNCH_SHADE(0) } else if (!sc->textured) { SPT_LAUNCH_SHADE(1) } else if (!sc->subsurface) { SPT_LAUNCH_SHADE(2) }
-                    else if (!sc->has_probe) { SPT_LAUNCH_SHADE(4) }          // glints only: no probe, so the geometry's place does not matter
-                    else if (tab || !L) { if (sc->has_pndf) { SPT_LAUNCH_SHADE(5) } else { SPT_LAUNCH_SHADE(3) } }
-                    else if (sc->has_pndf) {   // geometry in LDS, tables not: the probe still walks the LDS copy (k_shade's kGeoLds)
-                        if (b == 0) hipLaunchKernelGGL((k_shade<5, true, false, false, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, ru, b);
-                        else hipLaunchKernelGGL((k_shade<5, false, false, false, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, ru, b);
-                    } else {
-                        if (b == 0) hipLaunchKernelGGL((k_shade<3, true, false, false, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, ru, b);
-                        else hipLaunchKernelGGL((k_shade<3, false, false, false, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, ru, b);
-                    }
-#undef SPT_LAUNCH_SHADE
-                    end();
-                    // k_shadow(b) and k_extend(b) are independent unless the scene has an environment (then a missing
-                    // extension ray adds its term to the same radiance slot the shadow ray of that vertex adds to, and
-                    // the reference's order of the two additions has to be kept): without one, the shadow kernel runs on
-                    // a side stream next to the extension kernel and is joined before the next stage reads the slots.
-                    const bool side = overlap && b + 1 < p.max_depth;
-                    hipStream_t ss = side ? sc->stream2 : st;
-                    if (side) {
-                        HIP_CHECK(hipEventRecord(sc->ev_fork, st));
-                        HIP_CHECK(hipStreamWaitEvent(ss, sc->ev_fork, 0));
-                    }
-                    begin(SPT_K_SHADOW);
-                    if (stream_s && count) hipLaunchKernelGGL(k_shadow_stream<true>, dim3(kDynBlocks), dim3(kBlock), lds, ss, sc->d, ru, b);
-                    else if (stream_s) hipLaunchKernelGGL(k_shadow_stream<false>, dim3(kDynBlocks), dim3(kBlock), lds, ss, sc->d, ru, b);
-                    else if (L && sc->d.flat) hipLaunchKernelGGL((k_shadow<true, false, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, ss, sc->d, ru, b);
-                    else if (L) hipLaunchKernelGGL((k_shadow<true, false>), dim3(kPersistentBlocks), dim3(kBlock), lds, ss, sc->d, ru, b);
-                    else if (dyn_shadow && count) hipLaunchKernelGGL(k_shadow_dyn<true>, dim3(kDynBlocks), dim3(kBlock), lds, ss, sc->d, ru, b);
-                    else if (dyn_shadow) hipLaunchKernelGGL(k_shadow_dyn<false>, dim3(kDynBlocks), dim3(kBlock), lds, ss, sc->d, ru, b);
-                    else if (count) hipLaunchKernelGGL((k_shadow<false, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, ss, sc->d, ru, b);
-                    else hipLaunchKernelGGL((k_shadow<false, false>), dim3(kPersistentBlocks), dim3(kBlock), lds, ss, sc->d, ru, b);
-                    end();
-                    if (side) HIP_CHECK(hipEventRecord(sc->ev_join, ss));
-                    if (b + 1 < p.max_depth) {
-                        begin(SPT_K_EXTEND);
-                        if (stream_e && count) hipLaunchKernelGGL(k_extend_stream<true>, dim3(kDynBlocks), dim3(kBlock), lds, st, sc->d, ru, b);
-                        else if (stream_e) hipLaunchKernelGGL(k_extend_stream<false>, dim3(kDynBlocks), dim3(kBlock), lds, st, sc->d, ru, b);
-                        else if (L && sc->d.flat) hipLaunchKernelGGL((k_extend<true, false, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, ru, b);
-                        else if (L) hipLaunchKernelGGL((k_extend<true, false>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, ru, b);
-                        else if (dyn_extend && count) hipLaunchKernelGGL(k_extend_dyn<true>, dim3(kDynBlocks), dim3(kBlock), lds, st, sc->d, ru, b);
-                        else if (dyn_extend) hipLaunchKernelGGL(k_extend_dyn<false>, dim3(kDynBlocks), dim3(kBlock), lds, st, sc->d, ru, b);
-                        else if (count) hipLaunchKernelGGL((k_extend<false, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, ru, b);
-                        else hipLaunchKernelGGL((k_extend<false, false>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, ru, b);
-                        end();
-                    }
-                    if (side) HIP_CHECK(hipStreamWaitEvent(st, sc->ev_join, 0));
-                }
-                if (!collect) {
-                    begin(SPT_K_RESOLVE);
-                    if (rc.slot_bits != nullptr && env_u32("SPT_RESOLVE_BATCH", 16u) == 32u) hipLaunchKernelGGL(k_resolve_bits<32u>, dim3(pix_blocks), dim3(kBlock), 0, st, rc);
-                    else if (rc.slot_bits != nullptr) hipLaunchKernelGGL(k_resolve_bits<16u>, dim3(pix_blocks), dim3(kBlock), 0, st, rc);
-                    else hipLaunchKernelGGL(k_resolve, dim3(pix_blocks), dim3(kBlock), 0, st, rc);
-                    end();
-                }
-                if (stats) {
-                    h_counts.resize(counts_words);
-                    HIP_CHECK(hipMemcpyAsync(h_counts.data(), rc.counts, counts_bytes, hipMemcpyDeviceToHost, st));
-                    HIP_CHECK(hipStreamSynchronize(st));
-                    seg_closest += (uint64_t)n_pix * rc.pass_samples;
-                    auto qsum = [&](uint32_t b, uint32_t q) {
-                        uint64_t t = 0;
-                        for (uint32_t s = 0; s < kShards; ++s) t += h_counts[((size_t)(b * Q_KINDS + q) * kShards + s) * 32];
-                        if (q == Q_HIT)     // the hit queue's other classes (bounce >= 1 of the general pipeline)
-                            for (uint32_t c = 1; c < kClasses; ++c)
-                                for (uint32_t s = 0; s < kShards; ++s) t += h_counts[((size_t)(b * Q_KINDS + Q_HIT_CLASS1 + c - 1u) * kShards + s) * 32];
-                        return t;
-                    };
-                    if (p.max_depth > 1) sc->tail_vertices = qsum(1, Q_HIT);
-                    primary_hits += qsum(0, Q_HIT);
-                    shadow_first += qsum(0, Q_SHADOW);
-                    if (p.max_depth > 1) vertices_second += qsum(1, Q_HIT);
-                    for (uint32_t b = 0; b < p.max_depth; ++b) {
-                        path_vertices += qsum(b, Q_HIT);
-                        seg_shadow += qsum(b, Q_SHADOW);
-                        if (b + 1 < p.max_depth) seg_closest += qsum(b, Q_EXT);
-                    }
-                }
-            }
-            samples_traced += (uint64_t)n_pix * p.spp;
-            if (chunked_any) live_samples += live_pixels * p.spp;
-            return rc;
-        };
+        run_spans(run);
+        auto begin = [&](int cls) { run.begin(cls); };
+        auto end = [&]() { run.end(); };
+        const SampleTarget whole{0u, p.spp, nullptr, nullptr, true};   // every sample of the plan, into the scene's film from zero
         if (R <= 0) {
-            const RenderCtx rc = trace_window(0, own_rows, p.shard_index, shard_count, strip_rows, false);
+            const RenderCtx rc = trace_window(run, 0, own_rows, p.shard_index, shard_count, strip_rows, false, whole);
             begin(SPT_K_RESOLVE);
             const dim3 grid((own_pix + kBlock - 1) / kBlock);
             if (sc->copy_pending) HIP_CHECK(hipStreamWaitEvent(st, sc->ev_copy_done, 0));   // the previous frame's copy-out reads `out`
             if (radius == 0.5f) hipLaunchKernelGGL(k_finish, dim3((own_pix * 3 + kBlock - 1) / kBlock), dim3(kBlock), 0, st, rc, sc->out.as<float>());
-            else hipLaunchKernelGGL(k_finish_box, grid, dim3(kBlock), 0, st, rc, sc->out.as<float>(), radius, R);
+            else hipLaunchKernelGGL(k_finish_box, grid, dim3(kBlock), 0, st, rc, sc->out.as<float>(), radius, R, 0u, p.spp);
             end();
         } else {
             // Film::filter_pixel (film.rs:71-92) reads the samples of (2R+1)^2 pixels: each run of consecutive rows of
@@ -1963,7 +2085,7 @@ spt_status spt_render(const spt_scene* scene_c, const spt_camera* cam, const spt
                 while (e < own.size() && own[e] == own[e - 1] + 1u && e - k < run_max) ++e;
                 const uint32_t j0 = own[k], j1 = own[e - 1] + 1u;
                 const uint32_t b0 = j0 >= (uint32_t)R ? j0 - (uint32_t)R : 0u, b1 = (uint32_t)std::min<uint64_t>(p.height, (uint64_t)j1 + (uint64_t)R);
-                const RenderCtx rc = trace_window(b0, b1 - b0, 0u, 1u, 1u, true);
+                const RenderCtx rc = trace_window(run, b0, b1 - b0, 0u, 1u, 1u, true, whole);
                 begin(SPT_K_RESOLVE);
                 BoxJob job{sc->rad.as<float>(), b0, b1 - b0, j0, j1 - j0, sc->out.as<float>() + k * (size_t)p.width * 3, R, radius};
                 if (sc->copy_pending) HIP_CHECK(hipStreamWaitEvent(st, sc->ev_copy_done, 0));
@@ -2012,19 +2134,19 @@ spt_status spt_render(const spt_scene* scene_c, const spt_camera* cam, const spt
             stats->tri_tests = h_visits[1] + h_visits[4] + h_visits[7];
             stats->instance_visits = h_visits[2] + h_visits[5] + h_visits[8];
             stats->node_bytes = stats->node_visits * 64ull;   // wide 2-ary and compressed 4-ary nodes are both 64-byte records
-            stats->samples = samples_traced;
-            stats->segments_closest = seg_closest;
-            stats->segments_shadow = seg_shadow;
-            stats->primary_hits = primary_hits;
-            stats->path_vertices = path_vertices;
-            stats->shadow_first = shadow_first;
-            stats->vertices_second = vertices_second;
-            stats->live_samples = live_samples;
+            stats->samples = run.samples_traced;
+            stats->segments_closest = run.seg_closest;
+            stats->segments_shadow = run.seg_shadow;
+            stats->primary_hits = run.primary_hits;
+            stats->path_vertices = run.path_vertices;
+            stats->shadow_first = run.shadow_first;
+            stats->vertices_second = run.vertices_second;
+            stats->live_samples = run.live_samples;
             float ms = 0.0f;
             HIP_CHECK(hipEventElapsedTime(&ms, ev_total0, ev_total1));
             stats->gpu_ms = ms;
             const bool debug_spans = std::getenv("SPT_DEBUG_SPANS") != nullptr;   // per-launch HIP-event times (profile mode)
-            for (auto& sp : spans) {
+            for (auto& sp : run.spans) {
                 float k = 0.0f;
                 HIP_CHECK(hipEventElapsedTime(&k, sc->events[sp.e0], sc->events[sp.e0 + 1]));
                 stats->kernel_ms[sp.cls] += k;
@@ -2061,6 +2183,194 @@ spt_status spt_render_wait(const spt_scene* scene_c) {
         g_error = e.msg;
         return e.code;
     }
+}
+
+spt_status spt_film_create(const spt_scene* scene_c, const spt_camera* cam, const spt_render_params* params, uint32_t first_sample,
+                           uint32_t film_flags, spt_film** out) {
+    if (!scene_c || !cam || !params || !out) { g_error = "film_create: null argument"; return SPT_ERR_INVALID_ARG; }
+    *out = nullptr;
+    spt_scene* sc = const_cast<spt_scene*>(scene_c);
+    if (sc->fwd) {
+        spt_film* inner = nullptr;
+        const spt_status st = sc->fwd->film_create(sc->inner, cam, params, first_sample, film_flags, &inner);
+        if (st != SPT_OK) { g_error = sc->fwd->last_error(); return st; }
+        spt_film* f = new (std::nothrow) spt_film;
+        if (!f) { sc->fwd->film_destroy(inner); g_error = "film_create: out of host memory"; return SPT_ERR_OUT_OF_MEMORY; }
+        f->fwd = sc->fwd;
+        f->inner = inner;
+        *out = f;
+        return SPT_OK;
+    }
+    std::lock_guard<std::mutex> lock(sc->mu);
+    spt_film* f = nullptr;
+    try {
+        const spt_render_params& p = *params;
+        check_plan(p, "film_create");
+        if (film_flags & ~(uint32_t)SPT_FILM_MOMENTS) fail(SPT_ERR_INVALID_ARG, "film_create: unknown film flags");
+        if (first_sample > p.spp) fail(SPT_ERR_INVALID_ARG, "film_create: first_sample past the plan's spp");
+        const float radius = plan_radius(p, "film_create");
+        const int32_t R = (int32_t)std::ceil(radius - 0.5f);
+        // Film::filter_pixel of a wider box adds the samples of the neighbouring pixels into ONE running sum, pixel after pixel:
+        // the sum after n samples is not a prefix of the sum after n + k, so it cannot be extended bit-exactly
+        if (R >= 1) fail(SPT_ERR_UNSUPPORTED, "film_create: a box filter reaching neighbouring pixels (ceil(radius - 0.5) >= 1) cannot be rendered in increments");
+        const uint64_t own_pix64 = (uint64_t)shard_row_count(p) * p.width;
+        if (own_pix64 > 0x7fffffffull) fail(SPT_ERR_UNSUPPORTED, "film_create: shard larger than 2^31 pixels");
+        HIP_CHECK(hipSetDevice(sc->device));
+        f = new spt_film;
+        f->sc = sc;
+        f->cam = *cam;
+        f->plan = p;
+        f->first = first_sample;
+        f->flags = film_flags;
+        f->rows = shard_row_count(p);
+        f->radius = radius;
+        f->R = R;
+        const size_t bytes = (size_t)own_pix64 * 3 * sizeof(float);
+        f->sum.alloc(bytes);
+        HIP_CHECK(hipMemsetAsync(f->sum.p, 0, f->sum.bytes, sc->stream));
+        if (film_flags & SPT_FILM_MOMENTS) {
+            f->sq.alloc(bytes);
+            HIP_CHECK(hipMemsetAsync(f->sq.p, 0, f->sq.bytes, sc->stream));
+        }
+        HIP_CHECK(hipStreamSynchronize(sc->stream));
+        *out = f;
+        return SPT_OK;
+    } catch (const AbiError& e) {
+        delete f;
+        g_error = e.msg;
+        return e.code;
+    } catch (const std::exception& e) {
+        delete f;
+        g_error = std::string("film_create: ") + e.what();
+        return SPT_ERR_OUT_OF_MEMORY;
+    }
+}
+
+spt_status spt_film_render(spt_film* f, uint32_t n_samples) {
+    if (!f) { g_error = "film_render: null argument"; return SPT_ERR_INVALID_ARG; }
+    if (f->fwd) {
+        const spt_status st = f->fwd->film_render(f->inner, n_samples);
+        if (st != SPT_OK) g_error = f->fwd->last_error();
+        return st;
+    }
+    if (n_samples == 0) return SPT_OK;
+    spt_scene* sc = f->sc;
+    std::lock_guard<std::mutex> lock(sc->mu);
+    try {
+        const spt_render_params& p = f->plan;
+        // every check comes before the first change: a refused call leaves the film as it was
+        if (p.flags & (SPT_RENDER_ASYNC | SPT_RENDER_PROFILE | SPT_RENDER_COUNT_VISITS))
+            fail(SPT_ERR_INVALID_ARG, "film_render: the plan asks for SPT_RENDER_ASYNC / PROFILE / COUNT_VISITS (increments are synchronous and return no stats)");
+        const uint32_t shard_count = p.shard_count ? p.shard_count : 1u, strip_rows = p.strip_rows ? p.strip_rows : 1u;
+        const size_t strip_bytes = (size_t)strip_rows * p.width * 3 * sizeof(float);
+        if (p.out_strip_stride != 0 && p.out_strip_stride != strip_bytes) fail(SPT_ERR_INVALID_ARG, "film_render: the plan's out_strip_stride is not packed (films read out packed rows)");
+        if ((uint64_t)f->first + f->done + n_samples > p.spp)
+            fail(SPT_ERR_INVALID_ARG, "film_render: " + std::to_string(n_samples) + " more samples would pass the plan's spp (" + std::to_string(p.spp) + ", " +
+                                          std::to_string(f->first + f->done) + " covered)");
+        if (f->rows != 0) {
+            HIP_CHECK(hipSetDevice(sc->device));
+            RenderRun run;
+            run.sc = sc;
+            run.cam = &f->cam;
+            run.params = &p;
+            run_setup(run);
+            run_spans(run);
+            const SampleTarget inc{f->first + f->done, n_samples, f->sum.as<float>(), (f->flags & SPT_FILM_MOMENTS) ? f->sq.as<float>() : nullptr, false};
+            (void)trace_window(run, 0, f->rows, p.shard_index, shard_count, strip_rows, false, inc);
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipStreamSynchronize(run.st));
+        }
+        f->done += n_samples;
+        return SPT_OK;
+    } catch (const AbiError& e) {
+        g_error = e.msg;
+        return e.code;
+    } catch (const std::exception& e) {
+        g_error = std::string("film_render: ") + e.what();
+        return SPT_ERR_OUT_OF_MEMORY;
+    }
+}
+
+spt_status spt_film_samples(const spt_film* f, uint32_t* done) {
+    if (!f || !done) { g_error = "film_samples: null argument"; return SPT_ERR_INVALID_ARG; }
+    if (f->fwd) {
+        const spt_status st = f->fwd->film_samples(f->inner, done);
+        if (st != SPT_OK) g_error = f->fwd->last_error();
+        return st;
+    }
+    *done = f->done;
+    return SPT_OK;
+}
+
+spt_status spt_film_read(spt_film* f, uint32_t what, float* out) {
+    if (!f || !out) { g_error = "film_read: null argument"; return SPT_ERR_INVALID_ARG; }
+    if (f->fwd) {
+        const spt_status st = f->fwd->film_read(f->inner, what, out);
+        if (st != SPT_OK) g_error = f->fwd->last_error();
+        return st;
+    }
+    spt_scene* sc = f->sc;
+    std::lock_guard<std::mutex> lock(sc->mu);
+    try {
+        const spt_render_params& p = f->plan;
+        if (what > SPT_FILM_VAR_OF_MEAN) fail(SPT_ERR_INVALID_ARG, "film_read: unknown SPT_FILM_* value");
+        const bool moments = (f->flags & SPT_FILM_MOMENTS) != 0;
+        if ((what == SPT_FILM_SUM_SQ || what == SPT_FILM_VAR_OF_MEAN) && !moments)
+            fail(SPT_ERR_INVALID_ARG, "film_read: SUM_SQ / VAR_OF_MEAN need a film created with SPT_FILM_MOMENTS");
+        if (what == SPT_FILM_VAR_OF_MEAN && f->radius != 0.5f)
+            fail(SPT_ERR_UNSUPPORTED, "film_read: VAR_OF_MEAN needs the box radius 0.5 (every sample of the pixel weighs 1)");
+        if ((what == SPT_FILM_MEAN || what == SPT_FILM_VAR_OF_MEAN) && f->done == 0) fail(SPT_ERR_INVALID_ARG, "film_read: the film covers no samples yet");
+        if (f->rows == 0) return SPT_OK;
+        const uint32_t n_pix = f->rows * p.width;
+        const size_t bytes = (size_t)n_pix * 3 * sizeof(float);
+        HIP_CHECK(hipSetDevice(sc->device));
+        const hipStream_t st = sc->stream;
+        const void* src = f->sum.p;
+        if (what == SPT_FILM_SUM_SQ) src = f->sq.p;
+        if (what == SPT_FILM_MEAN || what == SPT_FILM_VAR_OF_MEAN) {
+            f->out.ensure(bytes);
+            if (what == SPT_FILM_MEAN && f->radius != 0.5f) {
+                // k_finish_box over the covered samples: the context it reads is the plan's sampler and shard
+                RenderCtx rc{};
+                rc.width = p.width; rc.height = p.height; rc.spp = p.spp; rc.max_depth = p.max_depth;
+                rc.sampler = p.sampler; rc.division_x = p.division_x; rc.division_y = p.division_y;
+                rc.seed = p.seed;
+                rc.shard_index = p.shard_index; rc.shard_count = p.shard_count ? p.shard_count : 1u; rc.strip_rows = p.strip_rows ? p.strip_rows : 1u;
+                rc.n_pixels = n_pix;
+                rc.rows = f->rows;
+                rc.film = f->sum.as<float>();
+                hipLaunchKernelGGL(k_finish_box, dim3((n_pix + kBlock - 1) / kBlock), dim3(kBlock), 0, st, rc, f->out.as<float>(), f->radius, f->R, f->first, f->done);
+            } else {
+                const float inv_n = 1.0f / (float)f->done, inv_n1 = f->done > 1u ? 1.0f / (float)(f->done - 1u) : 0.0f;
+                hipLaunchKernelGGL(k_film_read, dim3((n_pix * 3 + kBlock - 1) / kBlock), dim3(kBlock), 0, st, what, n_pix * 3u, f->sum.as<float>(),
+                                   moments ? f->sq.as<float>() : nullptr, f->done, inv_n, inv_n1, f->out.as<float>());
+            }
+            HIP_CHECK(hipGetLastError());
+            src = f->out.p;
+        }
+        HIP_CHECK(hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        return SPT_OK;
+    } catch (const AbiError& e) {
+        g_error = e.msg;
+        return e.code;
+    } catch (const std::exception& e) {
+        g_error = std::string("film_read: ") + e.what();
+        return SPT_ERR_OUT_OF_MEMORY;
+    }
+}
+
+void spt_film_destroy(spt_film* f) {
+    if (!f) return;
+    if (f->fwd) {
+        f->fwd->film_destroy(f->inner);
+        delete f;
+        return;
+    }
+    std::lock_guard<std::mutex> lock(f->sc->mu);
+    (void)hipSetDevice(f->sc->device);
+    (void)hipStreamSynchronize(f->sc->stream);   // (every film call is synchronous; nothing of this film is queued)
+    delete f;
 }
 
 static spt_status trace_common(const spt_scene* scene_c, uint32_t n, const spt_ray* rays, void* out, size_t out_elem, bool closest) {

@@ -455,6 +455,28 @@ spt_status spt_film_samples(const spt_film* film, uint32_t* done);
 spt_status spt_film_read(spt_film* film, uint32_t what, float* out);
 void spt_film_destroy(spt_film* film);   /* before spt_scene_destroy of its scene */
 
+/* ---- adaptive sampling of a film (additive to ABI v14: detect it by symbol) -------------------------------------------------
+ * spt_film_adapt, called between increments, RETIRES every still-active pixel whose error estimate meets the tolerance; a
+ * retired pixel stays retired.  Later spt_film_render calls trace only the active pixels; a retired pixel keeps its S, its Q and
+ * its sample count n_p.  All active pixels cover the same samples [first_sample, first_sample + done) (pixels only leave the
+ * set), so n_p = done for them; spt_film_samples keeps returning done, the plan position, which advances on every
+ * spt_film_render even when no pixel is active (that call traces nothing).  Because a sample depends only on (seed, pixel, plan
+ * index) and the sums run in sample order, a retired pixel's sums are the bits of a plain film stopped at n_p samples.
+ * Criterion, exact f32 (no contraction), per channel c, for an active pixel when n = done >= max(min_samples, 2), with
+ * r(k) = 1.0f / (float)k:
+ *     m_c = S_c * r(n);  v_c = max((Q_c * r(n) - m_c * m_c) * r(n - 1), 0)   (= SPT_FILM_VAR_OF_MEAN)
+ *     tol_c = rel_error * |m_c| + abs_floor;   retire <=> v_c <= tol_c * tol_c for all three channels
+ * No sqrt; a NaN never retires; rel_error = abs_floor = 0 retires exactly the zero-variance pixels.  After the first adapt,
+ * SPT_FILM_MEAN is S * r(n_p) and SPT_FILM_VAR_OF_MEAN the formula above at n_p (+inf at n_p == 1), per pixel; SUM and SUM_SQ
+ * are unchanged.  A film that never calls spt_film_adapt is a plain film.
+ * Refusals leave the film unchanged: a null film or a film without SPT_FILM_MOMENTS (SPT_ERR_INVALID_ARG), a box radius other
+ * than 0.5 (SPT_ERR_UNSUPPORTED), rel_error / abs_floor negative or not finite (SPT_ERR_INVALID_ARG).  min_samples < 2 counts
+ * as 2; while done < max(min_samples, 2) the call retires nothing.  Synchronous. */
+/* Retires the film's converged pixels (see above); *active_out (may be NULL) = pixels still active. */
+spt_status spt_film_adapt(spt_film* film, float rel_error, float abs_floor, uint32_t min_samples, uint32_t* active_out);
+/* rows * width u32: the samples each pixel covers (done for active pixels). */
+spt_status spt_film_read_counts(spt_film* film, uint32_t* out);
+
 /* Seams below the renderer, for parity tests of rows a4/a6/a8/a9/a10:
  * Primitive::intersect / intersect_test of the scene aggregate on caller rays. */
 spt_status spt_trace_closest(const spt_scene* scene, uint32_t n, const spt_ray* rays, spt_hit* hits);

@@ -289,6 +289,8 @@ def hip_lib() -> C.CDLL:
         lib.spt_film_read.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         lib.spt_film_destroy.argtypes = [C.c_void_p]
         lib.spt_film_destroy.restype = None
+        lib.spt_film_adapt.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_uint32, C.POINTER(C.c_uint32)]
+        lib.spt_film_read_counts.argtypes = [C.c_void_p, C.c_void_p]
         lib.spt_debug_detmath.argtypes = [C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.spt_debug_bxdf.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Material), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -601,6 +603,21 @@ class ProgressiveFilm:
 
     def variance_of_mean(self) -> np.ndarray:
         return self.read(FILM_VAR_OF_MEAN)
+
+    def adapt(self, rel_error: float, abs_floor: float = 0.0, min_samples: int = 16) -> int:
+        """spt_film_adapt: retires every active pixel whose variance of the mean v meets v <= (rel_error * |mean| + abs_floor)^2
+        in all three channels, once the film covers max(min_samples, 2) samples; later render() calls trace only the active
+        pixels.  Needs moments=True.  Returns the pixels still active."""
+        active = C.c_uint32()
+        _check_hip(hip_lib().spt_film_adapt(self._handle(), rel_error, abs_floor, min_samples, C.byref(active)))
+        return active.value
+
+    def sample_counts(self) -> np.ndarray:
+        """(rows, width) u32: the samples each pixel covers (`samples` while it is active; mean() and variance_of_mean()
+        follow these counts)."""
+        out = np.zeros((self.rows, self.width), dtype=np.uint32)
+        _check_hip(hip_lib().spt_film_read_counts(self._handle(), out.ctypes.data))
+        return out
 
     def _handle(self):
         if not self._h:

@@ -5,7 +5,8 @@
 // --strip-rows R, --debug-normal and --bezier-ni (the reference's two cargo features, Cargo.toml:34-36: pt.rs:113-118, bezier.rs:58-103),
 // and progressive rendering on one device through a film object (spt_film_*): --preview-every K rewrites the image after every
 // K samples, --time-limit SEC stops after the increment during which SEC seconds have passed, --variance-out PATH.exr writes the
-// per-pixel variance of the mean.  It loads the scene
+// per-pixel variance of the mean, --adaptive REL [--adaptive-floor A] [--adaptive-min-samples N] retires converged pixels after
+// every increment (spt_film_adapt) and stops once none is active, --samples-out PATH.exr writes each pixel's sample count.  It loads the scene
 // with libspt_host, renders with libspt_hip (HIP kernels only) and writes the image; like the reference it reports the
 // time spent inside `render`.
 #include <algorithm>
@@ -22,7 +23,8 @@ static void usage() {
     std::fprintf(stderr,
                  "usage: spt -s <scene.json> -r <renderer.json> -o <out.png> [-w 512] [-h 512] [-c camera]\n"
                  "           [--seed N] [--spp N] [--device D | --gpus N | --devices a,b,..] [--strip-rows R] [--debug-normal] [--bezier-ni]\n"
-                 "           [--preview-every K] [--time-limit SEC] [--variance-out var.exr]\n");
+                 "           [--preview-every K] [--time-limit SEC] [--variance-out var.exr]\n"
+                 "           [--adaptive REL [--adaptive-floor A] [--adaptive-min-samples N]] [--samples-out counts.exr]\n");
 }
 
 int main(int argc, char** argv) {
@@ -34,7 +36,9 @@ int main(int argc, char** argv) {
     bool debug_normal = false, bezier_ni = false;
     uint32_t preview_every = 0;
     double time_limit = 0.0;
-    std::string variance_out;
+    std::string variance_out, samples_out;
+    double adaptive = -1.0, adaptive_floor = 0.0;   // adaptive < 0: off
+    uint32_t adaptive_min = 16;
     std::vector<int32_t> device_list;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -67,12 +71,18 @@ int main(int argc, char** argv) {
         else if (a == "--preview-every") preview_every = (uint32_t)std::atoi(next());
         else if (a == "--time-limit") time_limit = std::atof(next());
         else if (a == "--variance-out") variance_out = next();
+        else if (a == "--adaptive") adaptive = std::atof(next());
+        else if (a == "--adaptive-floor") adaptive_floor = std::atof(next());
+        else if (a == "--adaptive-min-samples") adaptive_min = (uint32_t)std::atoi(next());
+        else if (a == "--samples-out") samples_out = next();
         else { usage(); return 2; }
     }
     if (scene_path.empty() || renderer_path.empty() || out_path.empty()) { usage(); return 2; }
-    const bool progressive = preview_every > 0 || time_limit > 0.0 || !variance_out.empty();
+    const bool adaptive_on = adaptive >= 0.0;
+    const bool progressive = preview_every > 0 || time_limit > 0.0 || !variance_out.empty() || adaptive_on || !samples_out.empty();
     if (progressive && gpus > 1) {
-        std::fprintf(stderr, "Error: --preview-every, --time-limit and --variance-out render on one device (a film object), not on the %d of --gpus / --devices\n", gpus);
+        std::fprintf(stderr, "Error: --preview-every, --time-limit, --variance-out, --adaptive and --samples-out render on one device (a film object), "
+                             "not on the %d of --gpus / --devices\n", gpus);
         return 2;
     }
     if (progressive && gpus == 1) {   // one device named through --gpus 1 / --devices d: the film lives there
@@ -169,22 +179,30 @@ int main(int argc, char** argv) {
             spt_host_scene_free(hs);
             return 1;
         };
-        if (spt_film_create(ds, &cam, &params, 0, variance_out.empty() ? 0u : (uint32_t)SPT_FILM_MOMENTS, &pf) != SPT_OK) return film_fail();
-        const uint32_t inc = preview_every ? preview_every : (time_limit > 0.0 ? std::max(1u, params.spp / 16u) : params.spp);
+        const bool moments = !variance_out.empty() || adaptive_on;
+        if (spt_film_create(ds, &cam, &params, 0, moments ? (uint32_t)SPT_FILM_MOMENTS : 0u, &pf) != SPT_OK) return film_fail();
+        const uint32_t inc = preview_every ? preview_every : ((time_limit > 0.0 || adaptive_on) ? std::max(1u, params.spp / 16u) : params.spp);
+        uint32_t active = width * height;
         while (done < params.spp) {
             const uint32_t n = std::min(inc, params.spp - done);
             if (spt_film_render(pf, n) != SPT_OK) return film_fail();
             done += n;
+            // adaptive: retire the converged pixels after every increment; the render ends once none is left
+            if (adaptive_on && spt_film_adapt(pf, (float)adaptive, (float)adaptive_floor, adaptive_min, &active) != SPT_OK) return film_fail();
             const bool out_of_time = time_limit > 0.0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() >= time_limit;
-            if (done == params.spp || out_of_time) break;
+            if (done == params.spp || out_of_time || active == 0) break;
             if (preview_every) {
                 if (spt_film_read(pf, SPT_FILM_MEAN, film.data()) != SPT_OK) return film_fail();
                 write_film();
             }
         }
         if (spt_film_read(pf, SPT_FILM_MEAN, film.data()) != SPT_OK) return film_fail();
-        if (time_limit > 0.0) {
+        if (adaptive_on) {
+            std::fprintf(stderr, "Rendered %u of %u samples per pixel, %u of %u pixels active\n", done, params.spp, active, width * height);
+        } else if (time_limit > 0.0) {
             std::fprintf(stderr, "Rendered %u of %u samples per pixel\n", done, params.spp);
+        }
+        if (time_limit > 0.0) {
             if (done < params.spp && params.sampler == SPT_SAMPLER_JITTERED)
                 std::fprintf(stderr, "Warning: the jittered sampler's %ux%u grid is walked row by row: these %u samples cover only its first rows\n",
                              params.division_x, params.division_y, done);
@@ -193,6 +211,19 @@ int main(int argc, char** argv) {
             std::vector<float> var(film.size());
             if (spt_film_read(pf, SPT_FILM_VAR_OF_MEAN, var.data()) != SPT_OK) return film_fail();
             if (spt_host_write_exr(variance_out.c_str(), var.data(), width, height) != SPT_OK) {
+                std::fprintf(stderr, "Error: %s\n", spt_host_last_error());
+                spt_film_destroy(pf);
+                spt_scene_destroy(ds);
+                spt_host_scene_free(hs);
+                return 1;
+            }
+        }
+        if (!samples_out.empty()) {   // the samples each pixel covers, as f32 in all three channels
+            std::vector<uint32_t> counts((size_t)width * height);
+            if (spt_film_read_counts(pf, counts.data()) != SPT_OK) return film_fail();
+            std::vector<float> rgb(film.size());
+            for (size_t k = 0; k < counts.size(); ++k) rgb[3 * k] = rgb[3 * k + 1] = rgb[3 * k + 2] = (float)counts[k];
+            if (spt_host_write_exr(samples_out.c_str(), rgb.data(), width, height) != SPT_OK) {
                 std::fprintf(stderr, "Error: %s\n", spt_host_last_error());
                 spt_film_destroy(pf);
                 spt_scene_destroy(ds);

@@ -145,6 +145,13 @@ __global__ void __launch_bounds__(256) k_finish_box(RenderCtx rc, float* out, fl
 // Read-out of a film object (spt_film_read) for radius 0.5, one lane per float: SPT_FILM_MEAN is S * (1 / n), the operation of
 // k_finish; SPT_FILM_VAR_OF_MEAN is the variance of that mean from the moments, m = S * (1/n), v = (Q * (1/n) - m * m) * (1/(n - 1)),
 // clamped at 0 (a NaN stays one) and +inf for one sample.  The reciprocals come from the host, as rc.spp_inv does for k_finish.
+// The variance of the mean of one channel from its mean m = S * (1/n), n >= 2 samples: the one formula of SPT_FILM_VAR_OF_MEAN and of
+// spt_film_adapt's criterion.
+SPT_DEV float film_var_of_mean(float m, float q, float inv_n, float inv_n1) {
+    const float v = (q * inv_n - m * m) * inv_n1;
+    return v < 0.0f ? 0.0f : v;
+}
+
 __global__ void __launch_bounds__(256) k_film_read(uint32_t what, uint32_t n_floats, const float* sum, const float* sum_sq, uint32_t n,
                                                    float inv_n, float inv_n1, float* out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -152,8 +159,68 @@ __global__ void __launch_bounds__(256) k_film_read(uint32_t what, uint32_t n_flo
     const float m = sum[i] * inv_n;
     if (what == SPT_FILM_MEAN) { out[i] = m; return; }
     if (n == 1u) { out[i] = __builtin_huge_valf(); return; }
-    const float v = (sum_sq[i] * inv_n - m * m) * inv_n1;
-    out[i] = v < 0.0f ? 0.0f : v;
+    out[i] = film_var_of_mean(m, sum_sq[i], inv_n, inv_n1);
+}
+
+// k_film_read of an adaptive film: pixel p covers n_p samples, `done` while it is active (mask 1), counts[p] once retired.  The
+// reciprocals come from the host's table inv[k] = 1.0f / (float)k, k = 0 .. spp (no device division), so MEAN and VAR_OF_MEAN
+// are those of a plain film read at n_p samples, bit for bit.
+__global__ void __launch_bounds__(256) k_film_read_counts(uint32_t what, uint32_t n_floats, const float* sum, const float* sum_sq,
+                                                          const uint8_t* mask, const uint32_t* counts, uint32_t done, const float* inv,
+                                                          float* out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_floats) return;
+    const uint32_t px = i / 3u;
+    const uint32_t n = mask[px] ? done : counts[px];
+    const float inv_n = inv[n];
+    const float m = sum[i] * inv_n;
+    if (what == SPT_FILM_MEAN) { out[i] = m; return; }
+    if (n == 1u) { out[i] = __builtin_huge_valf(); return; }
+    out[i] = film_var_of_mean(m, sum_sq[i], inv_n, inv[n - 1u]);
+}
+
+// spt_film_adapt: one 256-lane block per 16x16 tile of the shard, k_primary's numbering (tile = tx + tiles_x * ty over the packed
+// rows).  An active pixel whose variance of the mean meets v_c <= (rel * |m_c| + floor)^2 in all three channels (n = done samples,
+// exact f32, no sqrt: a NaN never retires) is retired: mask 0, counts = n.  The block's active count goes to tile_active[tile]
+// (plain store); totals[0] += active pixels, totals[1] += 1 if the tile keeps any (the host zeroes both first).
+__global__ void __launch_bounds__(256) k_film_adapt(uint32_t width, uint32_t rows, uint32_t tiles_x, const float* sum, const float* sum_sq,
+                                                    uint8_t* mask, uint32_t* counts, uint32_t* tile_active, uint32_t* totals, uint32_t n,
+                                                    float inv_n, float inv_n1, float rel_error, float abs_floor) {
+    __shared__ uint32_t wave_active[256 / 64];
+    const uint32_t tile = blockIdx.x, tx = tile % tiles_x, ty = tile / tiles_x;
+    const uint32_t i = tx * 16u + (threadIdx.x % 16u), row_local = ty * 16u + (threadIdx.x / 16u);
+    bool active = false;
+    if (i < width && row_local < rows) {
+        const uint32_t lp = row_local * width + i;
+        active = mask[lp] != 0u;
+        if (active) {
+            bool retire = true;
+#pragma unroll
+            for (uint32_t c = 0; c < 3u; ++c) {
+                const float m = sum[3 * lp + c] * inv_n;
+                const float v = film_var_of_mean(m, sum_sq[3 * lp + c], inv_n, inv_n1);
+                const float tol = rel_error * fabsf(m) + abs_floor;
+                retire = retire && (v <= tol * tol);
+            }
+            if (retire) {
+                mask[lp] = 0u;
+                counts[lp] = n;
+                active = false;
+            }
+        }
+    }
+    const unsigned long long b = __ballot(active);
+    if ((threadIdx.x & 63u) == 0u) wave_active[threadIdx.x / 64u] = (uint32_t)__popcll(b);
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        uint32_t t = 0u;
+        for (uint32_t w = 0; w < 256u / 64u; ++w) t += wave_active[w];
+        tile_active[tile] = t;
+        if (t != 0u) {
+            atomicAdd(&totals[0], t);
+            atomicAdd(&totals[1], 1u);
+        }
+    }
 }
 
 // radius_int >= 1: Film::filter_pixel (film.rs:71-92) over the kept samples of a band of whole rows.  Rows j, then

@@ -11,8 +11,9 @@
 
 #define SPT_ARGS_PRIMARY (DScene, RenderCtx)
 #define SPT_ARGS_BOUNCE (DScene, RenderCtx, uint32_t)
+#define SPT_ARGS_PRIMARY_MASK (DScene, RenderCtx, FilmMask)
 
-// k_primary<kLds, kChunked, kCount, kEye>
+// k_primary<kLds, kChunked, kCount, kEye, kMask>  (kMask: adaptive films, chunked only)
 #define SPT_KERNELS_PRIMARY(X)                          \
     X((k_primary<true, false, false>), SPT_ARGS_PRIMARY)  \
     X((k_primary<true, true, false>), SPT_ARGS_PRIMARY)   \
@@ -21,7 +22,10 @@
     X((k_primary<false, false, false>), SPT_ARGS_PRIMARY) \
     X((k_primary<false, true, false>), SPT_ARGS_PRIMARY)  \
     X((k_primary<false, false, true>), SPT_ARGS_PRIMARY)  \
-    X((k_primary<false, true, true>), SPT_ARGS_PRIMARY)
+    X((k_primary<false, true, true>), SPT_ARGS_PRIMARY)   \
+    X((k_primary<true, true, false, true, true, FilmMask>), SPT_ARGS_PRIMARY_MASK)  \
+    X((k_primary<true, true, false, false, true, FilmMask>), SPT_ARGS_PRIMARY_MASK) \
+    X((k_primary<false, true, false, false, true, FilmMask>), SPT_ARGS_PRIMARY_MASK)
 
 // k_shadow / k_extend <kLds, kCount, kFlat>, refilling variants <kCount>
 #define SPT_KERNELS_RAYS(X)                          \
@@ -38,7 +42,7 @@
     X((k_extend_dyn<false>), SPT_ARGS_BOUNCE)        \
     X((k_extend_dyn<true>), SPT_ARGS_BOUNCE)
 
-// streaming kernels (stream.h): k_shadow_stream / k_extend_stream <kCount>, k_primary_stream<kChunked, kCount>
+// streaming kernels (stream.h): k_shadow_stream / k_extend_stream <kCount>, k_primary_stream<kChunked, kCount, kMask>
 #define SPT_KERNELS_STREAM(X)                             \
     X((k_shadow_stream<false>), SPT_ARGS_BOUNCE)          \
     X((k_shadow_stream<true>), SPT_ARGS_BOUNCE)           \
@@ -47,7 +51,8 @@
     X((k_primary_stream<false, false>), SPT_ARGS_PRIMARY) \
     X((k_primary_stream<true, false>), SPT_ARGS_PRIMARY)  \
     X((k_primary_stream<false, true>), SPT_ARGS_PRIMARY)  \
-    X((k_primary_stream<true, true>), SPT_ARGS_PRIMARY)
+    X((k_primary_stream<true, true>), SPT_ARGS_PRIMARY)   \
+    X((k_primary_stream<true, false, true, FilmMask>), SPT_ARGS_PRIMARY_MASK)
 
 // k_shade<kFeat, kFirst, kFused, kTab, kGeoLds>
 #define SPT_KERNELS_SHADE0(X)                                        \

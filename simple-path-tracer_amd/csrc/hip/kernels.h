@@ -129,6 +129,13 @@ struct RenderCtx {
     uint32_t debug_normal;                  // SPT_RENDER_DEBUG_NORMAL: the reference's `debug_normal` feature (pt.rs:113-118)
 };
 
+// The active set of an adaptive film (spt_film_adapt): the extra argument of k_primary<..., kMask = true> and
+// k_primary_stream<..., kMask = true>, kept out of RenderCtx (which every hot kernel takes by value)
+struct FilmMask {
+    const uint8_t* pixel;     // per shard pixel: 1 = still active, 0 = retired
+    const uint32_t* tile;     // per 16x16 tile (k_primary's numbering): active pixels after the last adapt
+};
+
 SPT_DEV uint32_t lane_id() { return threadIdx.x & 63u; }
 // image row of a local row of this shard (row strips dealt round-robin, spt_abi.h)
 SPT_DEV uint32_t global_row(const RenderCtx& rc, uint32_t row_local) {
@@ -286,8 +293,28 @@ SPT_DEV uint32_t tile_shard(uint32_t tx, uint32_t ty) { return (tx + 9u * ty) % 
 // which adds the slots in sample order: the same additions in the same order as the register sum of the
 // un-chunked kernel (a miss adds exactly +0 or its environment term), so the film is bit-identical.
 // kEye (with kLds, no counting): `sc` describes the eye-relative copy of the geometry (eye.h) and the trace reads what trace.h computes per ray
-template <bool kLds, bool kChunked = false, bool kCount = false, bool kEye = false>
-__global__ void __launch_bounds__(256, SPT_WITH_BEZIER ? 1 : (kLds ? SPT_W_PRI_L : SPT_W_PRI)) k_primary(DScene sc, RenderCtx rc) {
+// kMask (chunked only, an adaptive film): the one extra argument is the film's FilmMask.  A tile without active pixels returns
+// before it stages the geometry (block-uniform), after chunk 0 has marked its pixels empty (first_slot = pass_samples, which
+// both resolve kernels skip); a retired pixel of a partly active tile is not live, so its sample loop is empty.  Without
+// kMask there is no extra argument and the kernel's code stays that of the plain instance.
+SPT_DEV bool mask_tile_idle(const RenderCtx& rc, const FilmMask& fm) {
+    const uint32_t tile = blockIdx.x % rc.n_tiles, chunk = blockIdx.x / rc.n_tiles;
+    if (fm.tile[tile] != 0u) return false;
+    const uint32_t tx = tile % rc.tiles_x, ty = tile / rc.tiles_x;
+    const uint32_t i = tx * kTile + (threadIdx.x % kTile), row_local = ty * kTile + (threadIdx.x / kTile);
+    if (chunk == 0u && i < rc.width && row_local < rc.rows) rc.first_slot[row_local * rc.width + i] = rc.pass_samples;
+    return true;
+}
+
+template <bool kLds, bool kChunked = false, bool kCount = false, bool kEye = false, bool kMask = false, class... M>
+__global__ void __launch_bounds__(256, SPT_WITH_BEZIER ? 1 : (kLds ? SPT_W_PRI_L : SPT_W_PRI)) k_primary(DScene sc, RenderCtx rc, M... mask_arg) {
+    static_assert(sizeof...(M) == (kMask ? 1u : 0u), "k_primary<..., true> takes the film's FilmMask, <..., false> nothing more");
+    static_assert(!kMask || (kChunked && !kCount), "masked primary instances are chunked and do not count");
+    FilmMask fm{nullptr, nullptr};
+    if constexpr (kMask) {
+        fm = (mask_arg, ...);
+        if (mask_tile_idle(rc, fm)) return;   // the whole block: fm.tile[tile] is one value per block
+    }
     stage_geometry<kLds>(sc);
     LaneVisits vc{0u, 0u, 0u};
     const uint32_t tile = kChunked ? blockIdx.x % rc.n_tiles : blockIdx.x, chunk = kChunked ? blockIdx.x / rc.n_tiles : 0u;
@@ -314,7 +341,8 @@ __global__ void __launch_bounds__(256, SPT_WITH_BEZIER ? 1 : (kLds ? SPT_W_PRI_L
         const int2 span = rc.row_span[j];
         in_bounds = (int32_t)i >= span.x && (int32_t)i <= span.y;
     }
-    const bool live = in_bounds || has_env;
+    bool live = in_bounds || has_env;
+    if constexpr (kMask) live = live && valid && fm.pixel[lp] != 0u;   // a retired pixel traces nothing, environment or not
     const uint32_t s_begin = kChunked ? chunk * rc.chunk_samples : 0u;
     const uint32_t s_end = live ? (kChunked ? min(s_begin + rc.chunk_samples, rc.pass_samples) : rc.pass_samples) : s_begin;
     uint32_t slot_mask = 0u;     // chunked: the slot bits of the current group of 8 samples (chunk_samples is a multiple of 8)
@@ -1202,9 +1230,16 @@ __global__ void __launch_bounds__(256, SPT_WITH_BEZIER ? 2 : SPT_W_EXT) k_extend
 
 // k_primary for large scenes: a lane owns a pixel and walks its samples one after the other; a lane whose walk is done
 // retires the sample (hit record / environment term / zero slot, exactly as k_primary) and starts its next one while the
-// rest of the wave keeps walking.  Same tiles, chunks, slots and film semantics as k_primary<false, kChunked>.
-template <bool kChunked, bool kCount>
-__global__ void __launch_bounds__(256, 2) k_primary_stream(DScene sc, RenderCtx rc) {
+// rest of the wave keeps walking.  Same tiles, chunks, slots and film semantics as k_primary<false, kChunked>, kMask included.
+template <bool kChunked, bool kCount, bool kMask = false, class... M>
+__global__ void __launch_bounds__(256, 2) k_primary_stream(DScene sc, RenderCtx rc, M... mask_arg) {
+    static_assert(sizeof...(M) == (kMask ? 1u : 0u), "k_primary_stream<., ., true> takes the film's FilmMask, <., ., false> nothing more");
+    static_assert(!kMask || (kChunked && !kCount), "masked primary instances are chunked and do not count");
+    FilmMask fm{nullptr, nullptr};
+    if constexpr (kMask) {
+        fm = (mask_arg, ...);
+        if (mask_tile_idle(rc, fm)) return;
+    }
     const uint32_t tile = kChunked ? blockIdx.x % rc.n_tiles : blockIdx.x, chunk = kChunked ? blockIdx.x / rc.n_tiles : 0u;
     const uint32_t tx = tile % rc.tiles_x, ty = tile / rc.tiles_x;
     const uint32_t i = tx * kTile + (threadIdx.x % kTile);
@@ -1226,7 +1261,8 @@ __global__ void __launch_bounds__(256, 2) k_primary_stream(DScene sc, RenderCtx 
         const int2 span = rc.row_span[j];
         in_bounds = (int32_t)i >= span.x && (int32_t)i <= span.y;
     }
-    const bool live = valid && (in_bounds || has_env);
+    bool live = valid && (in_bounds || has_env);
+    if constexpr (kMask) live = live && fm.pixel[lp] != 0u;
     const uint32_t s_begin = kChunked ? chunk * rc.chunk_samples : 0u;
     const uint32_t s_end = live ? (kChunked ? min(s_begin + rc.chunk_samples, rc.pass_samples) : rc.pass_samples) : s_begin;
     uint2 spill_mem[kSpillStack];
@@ -1309,7 +1345,7 @@ __global__ void __launch_bounds__(256, 2) k_primary_stream(DScene sc, RenderCtx 
     }
     if (kCount) flush_visits(rc, wk.vc, 0u);
     if (kChunked) {
-        if (valid && chunk == 0u) rc.first_slot[lp] = (in_bounds || has_env) ? 0u : rc.pass_samples;
+        if (valid && chunk == 0u) rc.first_slot[lp] = (kMask ? live : (in_bounds || has_env)) ? 0u : rc.pass_samples;
     } else if (valid) {
         rc.film[3 * lp] = sum.x; rc.film[3 * lp + 1] = sum.y; rc.film[3 * lp + 2] = sum.z;
         rc.first_slot[lp] = first;

@@ -505,6 +505,8 @@ struct BezierLib {
     spt_status (*film_samples)(const spt_film*, uint32_t*) = nullptr;
     spt_status (*film_read)(spt_film*, uint32_t, float*) = nullptr;
     void (*film_destroy)(spt_film*) = nullptr;
+    spt_status (*film_adapt)(spt_film*, float, float, uint32_t, uint32_t*) = nullptr;
+    spt_status (*film_read_counts)(spt_film*, uint32_t*) = nullptr;
     spt_status (*trace_closest)(const spt_scene*, uint32_t, const spt_ray*, spt_hit*) = nullptr;
     spt_status (*trace_any)(const spt_scene*, uint32_t, const spt_ray*, uint8_t*) = nullptr;
     spt_status (*debug_bxdf)(const spt_scene*, int32_t, const spt_material*, uint32_t, uint32_t, const float*, const float*, const uint64_t*, float*, float*,
@@ -595,6 +597,14 @@ struct spt_film {
     float radius = 0.5f;
     int32_t R = 0;                    // ceil(radius - 0.5) <= 0
     DeviceBuffer sum, sq, out;        // S, Q (SPT_FILM_MOMENTS) and the read-out staging buffer, rows * width * 3 f32 each
+    // adaptive sampling (spt_film_adapt), made by its first call that can retire pixels; until then the film is a plain one
+    bool adaptive = false;
+    DeviceBuffer mask;                // per pixel u8: 1 active, 0 retired
+    DeviceBuffer counts;              // per pixel u32: the samples a retired pixel covers (n_p; an active pixel covers `done`)
+    DeviceBuffer tile_active;         // per 16x16 tile of the shard (k_primary's numbering) u32: active pixels after the last adapt
+    DeviceBuffer totals;              // 2 u32 of k_film_adapt: active pixels, tiles with any
+    DeviceBuffer inv;                 // (spp + 1) f32: inv[k] = 1.0f / (float)k as the host rounds it (inv[0] = 0, never read)
+    uint32_t active = 0, active_tiles = 0;
 };
 
 namespace {
@@ -821,12 +831,14 @@ const BezierLib* bezier_lib() {
         lib.film_samples = reinterpret_cast<decltype(lib.film_samples)>(dlsym(h, "spt_film_samples"));
         lib.film_read = reinterpret_cast<decltype(lib.film_read)>(dlsym(h, "spt_film_read"));
         lib.film_destroy = reinterpret_cast<decltype(lib.film_destroy)>(dlsym(h, "spt_film_destroy"));
+        lib.film_adapt = reinterpret_cast<decltype(lib.film_adapt)>(dlsym(h, "spt_film_adapt"));
+        lib.film_read_counts = reinterpret_cast<decltype(lib.film_read_counts)>(dlsym(h, "spt_film_read_counts"));
         lib.trace_closest = reinterpret_cast<decltype(lib.trace_closest)>(dlsym(h, "spt_trace_closest"));
         lib.trace_any = reinterpret_cast<decltype(lib.trace_any)>(dlsym(h, "spt_trace_any"));
         lib.debug_bxdf = reinterpret_cast<decltype(lib.debug_bxdf)>(dlsym(h, "spt_debug_bxdf"));
         lib.last_error = reinterpret_cast<decltype(lib.last_error)>(dlsym(h, "spt_last_error"));
         auto version = reinterpret_cast<uint32_t (*)(void)>(dlsym(h, "spt_abi_version"));
-        if (!lib.create || !lib.destroy || !lib.render || !lib.render_wait || !lib.film_create || !lib.film_render || !lib.film_samples || !lib.film_read || !lib.film_destroy || !lib.trace_closest || !lib.trace_any || !lib.debug_bxdf || !lib.last_error || !version || version() != SPT_ABI_VERSION) {
+        if (!lib.create || !lib.destroy || !lib.render || !lib.render_wait || !lib.film_create || !lib.film_render || !lib.film_samples || !lib.film_read || !lib.film_destroy || !lib.film_adapt || !lib.film_read_counts || !lib.trace_closest || !lib.trace_any || !lib.debug_bxdf || !lib.last_error || !version || version() != SPT_ABI_VERSION) {
             err = path + " does not export ABI version " + std::to_string(SPT_ABI_VERSION);
             return;
         }
@@ -1463,6 +1475,9 @@ struct SampleTarget {
     float* sum;              // window pixels * 3 running sums on the device; null: the scene's workspace film (sc->film)
     float* sq;               // SPT_FILM_MOMENTS: the running sums of the squares (k_resolve*<., true>); null: none
     bool zero;               // zero the sums before the first pass
+    // an adaptive film (spt_film_adapt): only its active pixels are traced (k_primary*<..., kMask>); null: every pixel
+    FilmMask mask{nullptr, nullptr};
+    uint32_t mask_tiles = 0;  // tiles with an active pixel after the last adapt: what the primary chunk count is sized for
 };
 
 // One call of the render loop: its plan, the kernel choices made once per call, the profiling spans and the counters that
@@ -1848,7 +1863,9 @@ RenderCtx trace_window(RenderRun& run, uint32_t row_base, uint32_t rows, uint32_
         rc.n_tiles = pix_blocks;
         rc.primary_chunks = 1;
         {
-            uint32_t want = std::min<uint32_t>(64u, (6144u + active_tiles - 1u) / std::max(active_tiles, 1u));
+            // (an adaptive film: the tiles its last adapt left active; chunking does not change bits)
+        const uint32_t busy_tiles = tgt.mask.pixel ? std::min(active_tiles, tgt.mask_tiles) : active_tiles;
+        uint32_t want = std::min<uint32_t>(64u, (6144u + busy_tiles - 1u) / std::max(busy_tiles, 1u));
             if (const char* v = std::getenv("SPT_PRIMARY_CHUNKS")) want = (uint32_t)std::max(1, std::atoi(v));
             want = std::max(1u, std::min(want, rc.pass_samples));
             rc.chunk_samples = (rc.pass_samples + want - 1u) / want;
@@ -1864,8 +1881,18 @@ RenderCtx trace_window(RenderRun& run, uint32_t row_base, uint32_t rows, uint32_
         rc.slot_bits = nullptr;
         // collect: every sample owns a slot, which is what the chunked kernel does.  Moments of a scene with an environment: the
         // un-chunked kernel adds the misses before a pixel's first hit straight into its sum, past k_resolve<true>'s Q
-        const bool all_slots = collect || (tgt.sq != nullptr && sc->d.env_w != 0u);
-        if (rc.primary_chunks > 1u || all_slots) {
+        // An adaptive film takes the chunked path only (its masked instances), whatever the chunk count.
+        const bool all_slots = collect || (tgt.sq != nullptr && sc->d.env_w != 0u) || tgt.mask.pixel != nullptr;
+        if (tgt.mask.pixel != nullptr) {
+            if (count) fail(SPT_ERR_INVALID_ARG, "render: an adaptive film does not count visits");
+            chunked_any = true;
+            rc.slot_bits = sc->slot_bits.as<uint8_t>();
+            const dim3 grid(pix_blocks * rc.primary_chunks);
+            if (stream_p) hipLaunchKernelGGL((k_primary_stream<true, false, true, FilmMask>), grid, dim3(kBlock), lds, st, sc->d, rc, tgt.mask);
+            else if (L && use_eye) hipLaunchKernelGGL((k_primary<true, true, false, true, true, FilmMask>), grid, dim3(kBlock), sc->eye_lds_bytes, st, sc->eye_d, rc, tgt.mask);
+            else if (L) hipLaunchKernelGGL((k_primary<true, true, false, false, true, FilmMask>), grid, dim3(kBlock), lds, st, sc->d, rc, tgt.mask);
+            else hipLaunchKernelGGL((k_primary<false, true, false, false, true, FilmMask>), grid, dim3(kBlock), lds, st, sc->d, rc, tgt.mask);
+        } else if (rc.primary_chunks > 1u || all_slots) {
             chunked_any = true;
             rc.slot_bits = sc->slot_bits.as<uint8_t>();
             if (stream_p && count) hipLaunchKernelGGL((k_primary_stream<true, true>), dim3(pix_blocks * rc.primary_chunks), dim3(kBlock), lds, st, sc->d, rc);
@@ -2267,7 +2294,8 @@ spt_status spt_film_render(spt_film* f, uint32_t n_samples) {
         if ((uint64_t)f->first + f->done + n_samples > p.spp)
             fail(SPT_ERR_INVALID_ARG, "film_render: " + std::to_string(n_samples) + " more samples would pass the plan's spp (" + std::to_string(p.spp) + ", " +
                                           std::to_string(f->first + f->done) + " covered)");
-        if (f->rows != 0) {
+        // (an adaptive film without active pixels traces nothing: `done` still advances, every pixel keeps its n_p)
+        if (f->rows != 0 && !(f->adaptive && f->active == 0)) {
             HIP_CHECK(hipSetDevice(sc->device));
             RenderRun run;
             run.sc = sc;
@@ -2275,7 +2303,11 @@ spt_status spt_film_render(spt_film* f, uint32_t n_samples) {
             run.params = &p;
             run_setup(run);
             run_spans(run);
-            const SampleTarget inc{f->first + f->done, n_samples, f->sum.as<float>(), (f->flags & SPT_FILM_MOMENTS) ? f->sq.as<float>() : nullptr, false};
+            SampleTarget inc{f->first + f->done, n_samples, f->sum.as<float>(), (f->flags & SPT_FILM_MOMENTS) ? f->sq.as<float>() : nullptr, false};
+            if (f->adaptive) {
+                inc.mask = FilmMask{f->mask.as<uint8_t>(), f->tile_active.as<uint32_t>()};
+                inc.mask_tiles = f->active_tiles;
+            }
             (void)trace_window(run, 0, f->rows, p.shard_index, shard_count, strip_rows, false, inc);
             HIP_CHECK(hipGetLastError());
             HIP_CHECK(hipStreamSynchronize(run.st));
@@ -2340,6 +2372,9 @@ spt_status spt_film_read(spt_film* f, uint32_t what, float* out) {
                 rc.rows = f->rows;
                 rc.film = f->sum.as<float>();
                 hipLaunchKernelGGL(k_finish_box, dim3((n_pix + kBlock - 1) / kBlock), dim3(kBlock), 0, st, rc, f->out.as<float>(), f->radius, f->R, f->first, f->done);
+            } else if (f->adaptive) {   // radius 0.5 (spt_film_adapt refuses others): per-pixel sample counts
+                hipLaunchKernelGGL(k_film_read_counts, dim3((n_pix * 3 + kBlock - 1) / kBlock), dim3(kBlock), 0, st, what, n_pix * 3u, f->sum.as<float>(),
+                                   f->sq.as<float>(), f->mask.as<uint8_t>(), f->counts.as<uint32_t>(), f->done, f->inv.as<float>(), f->out.as<float>());
             } else {
                 const float inv_n = 1.0f / (float)f->done, inv_n1 = f->done > 1u ? 1.0f / (float)(f->done - 1u) : 0.0f;
                 hipLaunchKernelGGL(k_film_read, dim3((n_pix * 3 + kBlock - 1) / kBlock), dim3(kBlock), 0, st, what, n_pix * 3u, f->sum.as<float>(),
@@ -2356,6 +2391,101 @@ spt_status spt_film_read(spt_film* f, uint32_t what, float* out) {
         return e.code;
     } catch (const std::exception& e) {
         g_error = std::string("film_read: ") + e.what();
+        return SPT_ERR_OUT_OF_MEMORY;
+    }
+}
+
+spt_status spt_film_adapt(spt_film* f, float rel_error, float abs_floor, uint32_t min_samples, uint32_t* active_out) {
+    if (!f) { g_error = "film_adapt: null argument"; return SPT_ERR_INVALID_ARG; }
+    if (f->fwd) {
+        const spt_status st = f->fwd->film_adapt(f->inner, rel_error, abs_floor, min_samples, active_out);
+        if (st != SPT_OK) g_error = f->fwd->last_error();
+        return st;
+    }
+    spt_scene* sc = f->sc;
+    std::lock_guard<std::mutex> lock(sc->mu);
+    try {
+        const spt_render_params& p = f->plan;
+        // every check comes before the first change: a refused call leaves the film as it was
+        if (!(f->flags & SPT_FILM_MOMENTS)) fail(SPT_ERR_INVALID_ARG, "film_adapt: the film was created without SPT_FILM_MOMENTS (the criterion needs the sums of squares)");
+        if (f->radius != 0.5f) fail(SPT_ERR_UNSUPPORTED, "film_adapt: needs the box radius 0.5 (every sample of the pixel weighs 1)");
+        if (!std::isfinite(rel_error) || !std::isfinite(abs_floor) || rel_error < 0.0f || abs_floor < 0.0f)
+            fail(SPT_ERR_INVALID_ARG, "film_adapt: rel_error and abs_floor must be finite and >= 0");
+        const uint32_t n_pix = f->rows * p.width;
+        const uint32_t need = std::max(min_samples, 2u);
+        if (f->done < need || n_pix == 0 || (f->adaptive && f->active == 0)) {   // nothing to retire: the active set as it stands
+            if (active_out) *active_out = f->adaptive ? f->active : n_pix;
+            return SPT_OK;
+        }
+        HIP_CHECK(hipSetDevice(sc->device));
+        const hipStream_t st = sc->stream;
+        const uint32_t tiles_x = (p.width + kTile - 1) / kTile, n_tiles = tiles_x * ((f->rows + kTile - 1) / kTile);
+        if (!f->adaptive) {   // every pixel active, every tile busy; the reciprocal table of the plan's sample counts
+            f->mask.alloc(n_pix);
+            f->counts.alloc((size_t)n_pix * sizeof(uint32_t));
+            f->tile_active.alloc((size_t)n_tiles * sizeof(uint32_t));
+            f->totals.alloc(2 * sizeof(uint32_t));
+            f->inv.alloc(((size_t)p.spp + 1) * sizeof(float));
+            std::vector<float> inv((size_t)p.spp + 1, 0.0f);
+            for (uint32_t k = 1; k <= p.spp; ++k) inv[k] = 1.0f / (float)k;
+            HIP_CHECK(hipMemsetAsync(f->mask.p, 1, n_pix, st));
+            HIP_CHECK(hipMemsetAsync(f->counts.p, 0, f->counts.bytes, st));
+            HIP_CHECK(hipMemcpyAsync(f->inv.p, inv.data(), f->inv.bytes, hipMemcpyHostToDevice, st));
+            HIP_CHECK(hipStreamSynchronize(st));   // `inv` is pageable
+            f->adaptive = true;
+            f->active = n_pix;
+            f->active_tiles = n_tiles;
+        }
+        uint32_t totals[2] = {0u, 0u};
+        HIP_CHECK(hipMemsetAsync(f->totals.p, 0, 2 * sizeof(uint32_t), st));
+        const float inv_n = 1.0f / (float)f->done, inv_n1 = 1.0f / (float)(f->done - 1u);
+        hipLaunchKernelGGL(k_film_adapt, dim3(n_tiles), dim3(kBlock), 0, st, p.width, f->rows, tiles_x, f->sum.as<float>(), f->sq.as<float>(),
+                           f->mask.as<uint8_t>(), f->counts.as<uint32_t>(), f->tile_active.as<uint32_t>(), f->totals.as<uint32_t>(), f->done, inv_n,
+                           inv_n1, rel_error, abs_floor);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(totals, f->totals.p, sizeof totals, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        f->active = totals[0];
+        f->active_tiles = totals[1];
+        if (active_out) *active_out = f->active;
+        return SPT_OK;
+    } catch (const AbiError& e) {
+        g_error = e.msg;
+        return e.code;
+    } catch (const std::exception& e) {
+        g_error = std::string("film_adapt: ") + e.what();
+        return SPT_ERR_OUT_OF_MEMORY;
+    }
+}
+
+spt_status spt_film_read_counts(spt_film* f, uint32_t* out) {
+    if (!f || !out) { g_error = "film_read_counts: null argument"; return SPT_ERR_INVALID_ARG; }
+    if (f->fwd) {
+        const spt_status st = f->fwd->film_read_counts(f->inner, out);
+        if (st != SPT_OK) g_error = f->fwd->last_error();
+        return st;
+    }
+    spt_scene* sc = f->sc;
+    std::lock_guard<std::mutex> lock(sc->mu);
+    try {
+        const uint32_t n_pix = f->rows * f->plan.width;
+        if (!f->adaptive) {
+            std::fill(out, out + n_pix, f->done);
+            return SPT_OK;
+        }
+        std::vector<uint8_t> mask(n_pix);
+        HIP_CHECK(hipSetDevice(sc->device));
+        HIP_CHECK(hipMemcpyAsync(mask.data(), f->mask.p, n_pix, hipMemcpyDeviceToHost, sc->stream));
+        HIP_CHECK(hipMemcpyAsync(out, f->counts.p, (size_t)n_pix * sizeof(uint32_t), hipMemcpyDeviceToHost, sc->stream));
+        HIP_CHECK(hipStreamSynchronize(sc->stream));
+        for (uint32_t i = 0; i < n_pix; ++i)
+            if (mask[i]) out[i] = f->done;
+        return SPT_OK;
+    } catch (const AbiError& e) {
+        g_error = e.msg;
+        return e.code;
+    } catch (const std::exception& e) {
+        g_error = std::string("film_read_counts: ") + e.what();
         return SPT_ERR_OUT_OF_MEMORY;
     }
 }

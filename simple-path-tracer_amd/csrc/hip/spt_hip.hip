@@ -12,8 +12,10 @@
 #include <cstring>
 #include <functional>
 #include <limits>
+#include <memory>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "kernel_list.h"   // the heavy kernel templates: declared here, compiled in inst_*.hip
@@ -496,22 +498,21 @@ uint32_t build_n4(const spt_bvh_node* nodes, uint32_t root, std::vector<float4>&
 // opens the other one next to itself and every later call on that scene is passed through.
 struct BezierLib {
     void* handle = nullptr;
-    spt_status (*create)(const spt_scene_desc*, int32_t, spt_scene**) = nullptr;
-    void (*destroy)(spt_scene*) = nullptr;
-    spt_status (*render)(const spt_scene*, const spt_camera*, const spt_render_params*, float*, spt_render_stats*) = nullptr;
-    spt_status (*render_wait)(const spt_scene*) = nullptr;
-    spt_status (*film_create)(const spt_scene*, const spt_camera*, const spt_render_params*, uint32_t, uint32_t, spt_film**) = nullptr;
-    spt_status (*film_render)(spt_film*, uint32_t) = nullptr;
-    spt_status (*film_samples)(const spt_film*, uint32_t*) = nullptr;
-    spt_status (*film_read)(spt_film*, uint32_t, float*) = nullptr;
-    void (*film_destroy)(spt_film*) = nullptr;
-    spt_status (*film_adapt)(spt_film*, float, float, uint32_t, uint32_t*) = nullptr;
-    spt_status (*film_read_counts)(spt_film*, uint32_t*) = nullptr;
-    spt_status (*trace_closest)(const spt_scene*, uint32_t, const spt_ray*, spt_hit*) = nullptr;
-    spt_status (*trace_any)(const spt_scene*, uint32_t, const spt_ray*, uint8_t*) = nullptr;
-    spt_status (*debug_bxdf)(const spt_scene*, int32_t, const spt_material*, uint32_t, uint32_t, const float*, const float*, const uint64_t*, float*, float*,
-                             float*, int32_t*) = nullptr;
-    const char* (*last_error)(void) = nullptr;
+    decltype(&spt_scene_create) create = nullptr;
+    decltype(&spt_scene_destroy) destroy = nullptr;
+    decltype(&spt_render) render = nullptr;
+    decltype(&spt_render_wait) render_wait = nullptr;
+    decltype(&spt_film_create) film_create = nullptr;
+    decltype(&spt_film_render) film_render = nullptr;
+    decltype(&spt_film_samples) film_samples = nullptr;
+    decltype(&spt_film_read) film_read = nullptr;
+    decltype(&spt_film_destroy) film_destroy = nullptr;
+    decltype(&spt_film_adapt) film_adapt = nullptr;
+    decltype(&spt_film_read_counts) film_read_counts = nullptr;
+    decltype(&spt_trace_closest) trace_closest = nullptr;
+    decltype(&spt_trace_any) trace_any = nullptr;
+    decltype(&spt_debug_bxdf) debug_bxdf = nullptr;
+    decltype(&spt_last_error) last_error = nullptr;
 };
 
 struct spt_scene {
@@ -519,7 +520,7 @@ struct spt_scene {
     spt_scene* inner = nullptr;
     int device = 0;
     hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr;            // side stream: k_shadow(b) next to k_extend(b) (see spt_render)
+    hipStream_t stream2 = nullptr;            // side stream: k_shadow(b) next to k_extend(b) (see bounce)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     hipStream_t stream_copy = nullptr;        // SPT_RENDER_ASYNC: the film's D2H copy, next to the following render's kernels
     hipEvent_t ev_out_ready = nullptr, ev_copy_done = nullptr;
@@ -822,23 +823,18 @@ const BezierLib* bezier_lib() {
         path = (slash == std::string::npos ? std::string() : path.substr(0, slash + 1)) + "libspt_hip_bez.so";
         void* h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
         if (!h) { const char* e = dlerror(); err = e ? e : "dlopen failed"; return; }
-        lib.create = reinterpret_cast<decltype(lib.create)>(dlsym(h, "spt_scene_create"));
-        lib.destroy = reinterpret_cast<decltype(lib.destroy)>(dlsym(h, "spt_scene_destroy"));
-        lib.render = reinterpret_cast<decltype(lib.render)>(dlsym(h, "spt_render"));
-        lib.render_wait = reinterpret_cast<decltype(lib.render_wait)>(dlsym(h, "spt_render_wait"));
-        lib.film_create = reinterpret_cast<decltype(lib.film_create)>(dlsym(h, "spt_film_create"));
-        lib.film_render = reinterpret_cast<decltype(lib.film_render)>(dlsym(h, "spt_film_render"));
-        lib.film_samples = reinterpret_cast<decltype(lib.film_samples)>(dlsym(h, "spt_film_samples"));
-        lib.film_read = reinterpret_cast<decltype(lib.film_read)>(dlsym(h, "spt_film_read"));
-        lib.film_destroy = reinterpret_cast<decltype(lib.film_destroy)>(dlsym(h, "spt_film_destroy"));
-        lib.film_adapt = reinterpret_cast<decltype(lib.film_adapt)>(dlsym(h, "spt_film_adapt"));
-        lib.film_read_counts = reinterpret_cast<decltype(lib.film_read_counts)>(dlsym(h, "spt_film_read_counts"));
-        lib.trace_closest = reinterpret_cast<decltype(lib.trace_closest)>(dlsym(h, "spt_trace_closest"));
-        lib.trace_any = reinterpret_cast<decltype(lib.trace_any)>(dlsym(h, "spt_trace_any"));
-        lib.debug_bxdf = reinterpret_cast<decltype(lib.debug_bxdf)>(dlsym(h, "spt_debug_bxdf"));
-        lib.last_error = reinterpret_cast<decltype(lib.last_error)>(dlsym(h, "spt_last_error"));
-        auto version = reinterpret_cast<uint32_t (*)(void)>(dlsym(h, "spt_abi_version"));
-        if (!lib.create || !lib.destroy || !lib.render || !lib.render_wait || !lib.film_create || !lib.film_render || !lib.film_samples || !lib.film_read || !lib.film_destroy || !lib.film_adapt || !lib.film_read_counts || !lib.trace_closest || !lib.trace_any || !lib.debug_bxdf || !lib.last_error || !version || version() != SPT_ABI_VERSION) {
+        auto sym = [h](auto& fn, const char* name) {   // true: the library exports `name`
+            fn = reinterpret_cast<std::remove_reference_t<decltype(fn)>>(dlsym(h, name));
+            return fn != nullptr;
+        };
+        decltype(&spt_abi_version) version = nullptr;
+        const bool all = sym(lib.create, "spt_scene_create") && sym(lib.destroy, "spt_scene_destroy") && sym(lib.render, "spt_render") &&
+                         sym(lib.render_wait, "spt_render_wait") && sym(lib.film_create, "spt_film_create") && sym(lib.film_render, "spt_film_render") &&
+                         sym(lib.film_samples, "spt_film_samples") && sym(lib.film_read, "spt_film_read") && sym(lib.film_destroy, "spt_film_destroy") &&
+                         sym(lib.film_adapt, "spt_film_adapt") && sym(lib.film_read_counts, "spt_film_read_counts") &&
+                         sym(lib.trace_closest, "spt_trace_closest") && sym(lib.trace_any, "spt_trace_any") && sym(lib.debug_bxdf, "spt_debug_bxdf") &&
+                         sym(lib.last_error, "spt_last_error") && sym(version, "spt_abi_version");
+        if (!all || version() != SPT_ABI_VERSION) {
             err = path + " does not export ABI version " + std::to_string(SPT_ABI_VERSION);
             return;
         }
@@ -849,6 +845,29 @@ const BezierLib* bezier_lib() {
 }
 }  // namespace
 #endif
+
+namespace {
+// The body of a C entry point: an AbiError becomes its status and message, any other exception (std::bad_alloc of a host
+// buffer, ...) SPT_ERR_OUT_OF_MEMORY with "<who>: what()".  Nothing leaves through the C ABI.
+template <class Body>
+spt_status guarded(const char* who, Body&& body) {
+    try {
+        return body();
+    } catch (const AbiError& e) {
+        g_error = e.msg;
+        return e.code;
+    } catch (const std::exception& e) {
+        g_error = std::string(who) + ": " + e.what();
+        return SPT_ERR_OUT_OF_MEMORY;
+    }
+}
+
+// The status of a call passed through to libspt_hip_bez.so (see BezierLib), whose message becomes this library's on failure
+spt_status forwarded(const BezierLib* lib, spt_status st) {
+    if (st != SPT_OK) g_error = lib->last_error();
+    return st;
+}
+}  // namespace
 
 extern "C" {
 
@@ -870,8 +889,7 @@ spt_status spt_shard_rows(const spt_render_params* params, uint32_t* rows) {
 spt_status spt_scene_create(const spt_scene_desc* desc, int32_t device, spt_scene** out) {
     if (!desc || !out) { g_error = "scene_create: null argument"; return SPT_ERR_INVALID_ARG; }
     *out = nullptr;
-    spt_scene* sc = nullptr;
-    try {
+    return guarded("scene_create", [&] {
 #if !SPT_WITH_BEZIER
         bool has_patch_instance = false;   // a patch that no instance uses (a primitives library) does not count
         if (desc->n_bezier_patches > 0 && desc->instances)
@@ -881,10 +899,10 @@ spt_status spt_scene_create(const spt_scene_desc* desc, int32_t device, spt_scen
             spt_scene* inner = nullptr;
             const spt_status st = lib->create(desc, device, &inner);
             if (st != SPT_OK) fail(st, lib->last_error());
-            sc = new spt_scene();
+            auto sc = std::make_unique<spt_scene>();
             sc->fwd = lib;
             sc->inner = inner;
-            *out = sc;
+            *out = sc.release();
             return SPT_OK;
         }
 #endif
@@ -897,7 +915,7 @@ spt_status spt_scene_create(const spt_scene_desc* desc, int32_t device, spt_scen
         if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
             fail(SPT_ERR_NO_DEVICE, std::string("device is '") + prop.gcnArchName + "', the kernels are built for gfx950 only");
         HIP_CHECK(hipSetDevice(device));
-        sc = new spt_scene();
+        auto sc = std::make_unique<spt_scene>();
         sc->device = device;
         HIP_CHECK(hipStreamCreateWithFlags(&sc->stream, hipStreamNonBlocking));
         HIP_CHECK(hipStreamCreateWithFlags(&sc->stream2, hipStreamNonBlocking));
@@ -1386,17 +1404,9 @@ spt_status spt_scene_create(const spt_scene_desc* desc, int32_t device, spt_scen
                 }
             }
         }
-        *out = sc;
+        *out = sc.release();
         return SPT_OK;
-    } catch (const AbiError& e) {
-        g_error = e.msg;
-        delete sc;
-        return e.code;
-    } catch (const std::exception& e) {
-        g_error = std::string("scene_create: ") + e.what();
-        delete sc;
-        return SPT_ERR_OUT_OF_MEMORY;
-    }
+    });
 }
 
 void spt_scene_destroy(spt_scene* scene) {
@@ -1407,6 +1417,8 @@ void spt_scene_destroy(spt_scene* scene) {
     // every DeviceBuffer member frees itself (a list here used to miss the buffers added later)
     delete scene;
 }
+
+}  // extern "C"
 
 // eye.h: the copy of the LDS-resident geometry relative to the camera position `eye` (every value by the f32 operations, in the
 // order, in which the walkers of trace.h compute it per ray - this file is compiled with FP contraction off like the kernels),
@@ -1480,8 +1492,8 @@ struct SampleTarget {
     uint32_t mask_tiles = 0;  // tiles with an active pixel after the last adapt: what the primary chunk count is sized for
 };
 
-// One call of the render loop: its plan, the kernel choices made once per call, the profiling spans and the counters that
-// become spt_render_stats (spt_render with stats only).
+// One call of the render loop: its plan, the kernel choices made once per call (run_setup), the profiling spans and the
+// counters that become spt_render_stats (spt_render with stats only).
 struct RenderRun {
     spt_scene* sc = nullptr;
     const spt_camera* cam = nullptr;
@@ -1489,8 +1501,19 @@ struct RenderRun {
     spt_render_stats* stats = nullptr;
     hipStream_t st = nullptr;
     bool profile = false, count = false, overlap = false, L = false, use_eye = false, dyn_shadow = false, dyn_extend = false;
+    bool fused = false;          // k_shade<0, ., kFused>: shade, shadow and extend of a bounce in one kernel, one hit queue class
+    bool class_queues = false;   // the general shade kernels' hit queue may be binned by BxDF class (kClasses)
+    bool tab = false;            // the general shade kernels read the shading tables from LDS (k_shade<.., kTab>)
+    bool tail_loop = false;      // the fused pipeline may take bounce 1 and every later one in one launch (kTailLoopBelow)
+    bool pack_first = false;     // RenderCtx::pack_first for the passes of at most 4096 samples
+    bool pixel_cull = false, row_spans = false;   // k_primary's screen-space rectangle, and the per-row spans inside it
+    bool stream_p = false, stream_s = false, stream_e = false;   // the streaming walker serves primary / shadow / extension rays
+    bool resolve32 = false;      // k_resolve_bits<32u> instead of <16u>
+    bool debug_spans = false;    // per-launch HIP-event times on stderr (profile mode)
+    uint32_t primary_chunks = 0;   // sample chunks per primary tile; 0: sized to the busy tiles
+    uint64_t box_band_bytes = 0;   // kept radiance per band of a wide box filter
     size_t lds = 0;
-    uint32_t kDynBlocks = 0, dyn_refill_below = 0, dyn_steps = 0;
+    uint32_t kDynBlocks = 0, dyn_refill_below = 0, dyn_steps = 0, stream_rounds = 0, stream_refill_below = 0;
     const int2* row_span_dev = nullptr;
     struct Span { int cls; size_t e0; };
     std::vector<Span> spans;
@@ -1517,7 +1540,8 @@ struct RenderRun {
     }
 };
 
-// The kernel choices of one call (the scene's lock is held and its device selected).
+// The kernel choices of one call (the scene's lock is held and its device selected): every environment switch of the render
+// loop is read here, once.
 void run_setup(RenderRun& run) {
     spt_scene* const sc = run.sc;
     const spt_render_params& p = *run.params;
@@ -1529,7 +1553,7 @@ void run_setup(RenderRun& run) {
     run.count = (p.flags & SPT_RENDER_COUNT_VISITS) != 0 && !sc->lds_geo;
     sc->visits.ensure(12 * sizeof(unsigned long long));
     if (run.count) HIP_CHECK(hipMemsetAsync(sc->visits.p, 0, 12 * sizeof(unsigned long long), sc->stream));
-    // per-kernel event timing needs one stream; so does a scene with an environment (see the bounce loop)
+    // per-kernel event timing needs one stream; so does a scene with an environment (see bounce)
     run.overlap = !run.profile && sc->d.env_w == 0u && std::getenv("SPT_NO_OVERLAP") == nullptr;
     run.lds = sc->lds_bytes;
     run.L = sc->lds_geo;
@@ -1545,6 +1569,33 @@ void run_setup(RenderRun& run) {
     run.kDynBlocks = env_u32("SPT_DYN_BLOCKS", 2048);   // persistent blocks that pull work
     run.dyn_refill_below = env_u32("SPT_DYN_REFILL", kRefillBelow);
     run.dyn_steps = env_u32("SPT_DYN_STEPS", kStepsPerCheck);
+    // which kernel classes the streaming walker serves (1 primary, 2 shadow, 4 extend).  Measured on cfg5, one box
+    // (gpurun_out r2j): extension rays 93.5 ms refilling state machine -> 87.4 ms streaming if-if; primary rays
+    // 8.8 -> 12.4 ms and shadow rays 9.8 -> 11.3 ms (coherent / short walks: the state machine's tighter loop wins)
+    const bool stream = sc->swalk && !run.L;
+    const uint32_t stream_mask = env_u32("SPT_STREAM_MASK", SPT_WITH_BEZIER ? 6u : 4u);   // (patch scenes: shadow rays too, 214 -> 197 ms on t_catmull.json)
+    run.stream_p = stream && (stream_mask & 1u);
+    run.stream_s = stream && (stream_mask & 2u);
+    run.stream_e = stream && (stream_mask & 4u);
+    // rays of a path tracer are short (cfg5: ~4 node + ~2 triangle + ~1 instance records per segment = 2 - 3 rounds):
+    // a finished lane that waits several rounds for its wave costs more than the refill check
+    // if-if with 4 rounds per check: 87.4 ms; 8 rounds 95.2; while-while (SPT_STREAM_IFIF=0) 100 - 121 ms
+    run.stream_rounds = std::max(1u, std::min(255u, env_u32("SPT_STREAM_ROUNDS", 4u))) | (env_u32("SPT_STREAM_IFIF", 1u) ? 0x100u : 0u);
+    run.stream_refill_below = std::max(1u, std::min(64u, env_u32("SPT_STREAM_REFILL", 40u)));
+    // see k_shade<.., kFused>.  Only the lean k_shade<0> variant gains: with the general kernel's 220+ VGPRs
+    // the two traversals run at 2 waves / SIMD and cfg4 is faster un-fused (4.30 vs 4.00 Gsamples/s, measured)
+    run.fused = sc->fused && sc->simple && std::getenv("SPT_NO_FUSED") == nullptr;
+    run.class_queues = std::getenv("SPT_NO_CLASS_QUEUES") == nullptr;
+    run.tab = sc->lds_tables && std::getenv("SPT_NO_LDS_TABLES") == nullptr;   // shading tables from LDS (tab_ld)
+    run.tail_loop = std::getenv("SPT_NO_TAIL_LOOP") == nullptr;
+    run.pack_first = sc->d.n_instances < (1u << 20) && std::getenv("SPT_NO_PACK_FIRST") == nullptr;
+    run.pixel_cull = std::getenv("SPT_NO_PIXEL_CULL") == nullptr;
+    run.row_spans = run.pixel_cull && std::getenv("SPT_NO_ROW_SPANS") == nullptr;
+    if (const char* v = std::getenv("SPT_PRIMARY_CHUNKS")) run.primary_chunks = (uint32_t)std::max(1, std::atoi(v));
+    run.resolve32 = env_u32("SPT_RESOLVE_BATCH", 16u) == 32u;
+    run.box_band_bytes = 8ull << 30;
+    if (const char* v = std::getenv("SPT_BOX_BAND_BYTES")) run.box_band_bytes = std::max<uint64_t>(1, std::strtoull(v, nullptr, 10));
+    run.debug_spans = std::getenv("SPT_DEBUG_SPANS") != nullptr;
 }
 
 void run_spans(RenderRun& run) {
@@ -1558,7 +1609,7 @@ void run_spans(RenderRun& run) {
     // from the leftmost to the rightmost hull point within one row of slack above and below, plus one pixel each side.
     // A pixel outside its row's span cannot see any instance with any sample (k_primary's `in_bounds`): the rotated
     // cube of the headline scene fills 19 % of the image, its world-space AABB's rectangle 25 %.
-    if (!sc->hull_corners.empty() && sc->d.env_w == 0u && std::getenv("SPT_NO_PIXEL_CULL") == nullptr && std::getenv("SPT_NO_ROW_SPANS") == nullptr) {
+    if (!sc->hull_corners.empty() && sc->d.env_w == 0u && run.row_spans) {
         std::vector<double> key = {(double)p.width, (double)p.height, (double)cam->half_cot_half_fov};
         for (int k = 0; k < 3; ++k) { key.push_back(cam->eye[k]); key.push_back(cam->forward[k]); key.push_back(cam->up[k]); key.push_back(cam->right[k]); }
         if (key != sc->span_key) {
@@ -1649,94 +1700,94 @@ float plan_radius(const spt_render_params& p, const char* who) {
     return radius;
 }
 
-// One window of whole image rows through the wavefront pipeline.  A shard is one window (row_base 0, the
-// strip formula of the ABI); a wide box filter renders bands of consecutive rows (w_count = w_strip = 1).
-// collect: keep every sample's radiance (3 planes [c][sample][pixel] in sc->rad) instead of summing it into
-// the film.  tgt: the samples of the plan this call adds and the sums they go to (see SampleTarget).  Returns the
-// context the resolve kernels of the caller need.
-RenderCtx trace_window(RenderRun& run, uint32_t row_base, uint32_t rows, uint32_t w_index, uint32_t w_count, uint32_t w_strip, bool collect,
-                       const SampleTarget& tgt) {
-    spt_scene* const sc = run.sc;
-    const spt_render_params& p = *run.params;
-    const spt_camera* const cam = run.cam;
-    spt_render_stats* const stats = run.stats;
-    const hipStream_t st = run.st;
-    const bool count = run.count, overlap = run.overlap, L = run.L, use_eye = run.use_eye, dyn_shadow = run.dyn_shadow, dyn_extend = run.dyn_extend;
-    const size_t lds = run.lds;
-    const uint32_t kDynBlocks = run.kDynBlocks, dyn_refill_below = run.dyn_refill_below, dyn_steps = run.dyn_steps;
-    const int2* const row_span_dev = run.row_span_dev;
-    auto begin = [&](int cls) { run.begin(cls); };
-    auto end = [&]() { run.end(); };
-    std::vector<uint32_t>& h_counts = run.h_counts;
-    uint64_t &seg_closest = run.seg_closest, &seg_shadow = run.seg_shadow, &primary_hits = run.primary_hits, &path_vertices = run.path_vertices;
-    uint64_t &shadow_first = run.shadow_first, &vertices_second = run.vertices_second;
-    const uint32_t s_end = tgt.first + tgt.count;
-    const uint64_t n_pix64 = (uint64_t)rows * p.width;
-    if (n_pix64 > 0x7fffffffull) fail(SPT_ERR_UNSUPPORTED, "render: window larger than 2^31 pixels");
-    const uint32_t n_pix = (uint32_t)n_pix64;
-    // samples per pass: keep the queues around a few million entries
-    uint32_t spp_pass = p.samples_per_pass;
-    if (spp_pass == 0) {
-        const uint64_t target = 128ull << 20;
-        spp_pass = (uint32_t)std::max<uint64_t>(1, target / n_pix);
-    }
-    spp_pass = std::min(spp_pass, tgt.count);   // (a film's increment: what is left of it)
-    // queue shards: shard s holds what the primary tiles mapped to it can emit, which also bounds
-    // every later generation of that shard
-    const uint32_t tiles_x = (p.width + kTile - 1) / kTile, tiles_y = (rows + kTile - 1) / kTile;
-    const uint32_t pix_blocks = tiles_x * tiles_y;
-    uint32_t max_tiles = 0;
-    {
-        std::vector<uint32_t> per(kShards, 0u);
-        for (uint32_t ty = 0; ty < tiles_y; ++ty)
-            for (uint32_t tx = 0; tx < tiles_x; ++tx) max_tiles = std::max(max_tiles, ++per[(tx + 9u * ty) % kShards]);
-    }
-    const uint64_t shard_cap64 = (uint64_t)max_tiles * kBlock * spp_pass;
-    const uint64_t cap64 = shard_cap64 * kShards;
-    if (cap64 > 0x7fffffffull) fail(SPT_ERR_UNSUPPORTED, "render: pass too large (lower samples_per_pass)");
-    const size_t cap = (size_t)cap64;
-    // collect: every sample of the window is kept (wide box filter), else only the samples of one pass
-    const uint64_t rad64 = (uint64_t)n_pix * (collect ? p.spp : spp_pass);
-
-    // the hit queue is binned by BxDF class for the general shade kernels (kernels.h, kClasses): class c lives c * cap
-    // entries further.  Memory is what MI355X has (24 B x cap x 8 classes = 26 GB for a 128 M-sample pass)
-    const bool fused_here = sc->fused && sc->simple && std::getenv("SPT_NO_FUSED") == nullptr;
-    const uint32_t n_classes = (!fused_here && p.max_depth > 1 && cap * (uint64_t)kClasses <= 0xffffffffull && std::getenv("SPT_NO_CLASS_QUEUES") == nullptr) ? kClasses : 1u;
-    for (int k = 0; k < 4; ++k) { sc->qa[k].ensure(cap * 16 * (k == 1 ? n_classes : 1u)); sc->qb[k].ensure(cap * 16); }   // (qa[1]: the compact bounce-0 records sit at their hit's index, in every class)
-    sc->qa[4].ensure(cap * 8);
-    sc->qb[4].ensure(cap * 8);
-    sc->hit_f4.ensure(cap * 16 * n_classes);
-    sc->hit_inst.ensure(cap * 8 * n_classes);
-    // see k_shade<.., kFused>.  Only the lean k_shade<0> variant gains: with the general kernel's 220+ VGPRs
-    // the two traversals run at 2 waves / SIMD and cfg4 is faster un-fused (4.30 vs 4.00 Gsamples/s, measured)
-    const bool fused = sc->fused && sc->simple && std::getenv("SPT_NO_FUSED") == nullptr;
-    if (fused) {
-        sc->hit_f4_next.ensure(cap * 16);
-        sc->hit_inst_next.ensure(cap * 8);
-    }
-    for (int k = 0; k < 3; ++k) sc->sh[k].ensure(cap * 16);
-    const size_t counts_words = (size_t)(p.max_depth + 1) * Q_KINDS * kShards * 32;
-    const size_t counts_bytes = counts_words * sizeof(uint32_t);
-    sc->counts.ensure(counts_bytes);
-    sc->rad.ensure((size_t)rad64 * 3 * sizeof(float));
-    float* const film_sum = tgt.sum ? tgt.sum : (sc->film.ensure((size_t)n_pix * 3 * sizeof(float)), sc->film.as<float>());
-    sc->first_slot.ensure((size_t)n_pix * sizeof(uint32_t));
-    sc->slot_bits.ensure((size_t)n_pix * ((spp_pass + 7u) / 8u));
-
+// The plan and camera part of the RenderCtx of `rows` image rows: the strip formula of the ABI (w_index, w_count, w_strip)
+// from image row row_base.  A film read's k_finish_box gets its context from here too.
+RenderCtx plan_ctx(const spt_render_params& p, const spt_camera& cam, uint32_t row_base, uint32_t rows, uint32_t w_index, uint32_t w_count,
+                   uint32_t w_strip) {
     RenderCtx rc{};
-    rc.cam.eye = f3{cam->eye[0], cam->eye[1], cam->eye[2]};
-    rc.cam.forward = f3{cam->forward[0], cam->forward[1], cam->forward[2]};
-    rc.cam.up = f3{cam->up[0], cam->up[1], cam->up[2]};
-    rc.cam.right = f3{cam->right[0], cam->right[1], cam->right[2]};
-    rc.cam.half_cot = cam->half_cot_half_fov;
+    rc.cam.eye = f3{cam.eye[0], cam.eye[1], cam.eye[2]};
+    rc.cam.forward = f3{cam.forward[0], cam.forward[1], cam.forward[2]};
+    rc.cam.up = f3{cam.up[0], cam.up[1], cam.up[2]};
+    rc.cam.right = f3{cam.right[0], cam.right[1], cam.right[2]};
+    rc.cam.half_cot = cam.half_cot_half_fov;
     rc.width = p.width; rc.height = p.height; rc.spp = p.spp; rc.max_depth = p.max_depth;
     rc.sampler = p.sampler; rc.division_x = p.division_x; rc.division_y = p.division_y;
     rc.seed = p.seed;
     rc.shard_index = w_index; rc.shard_count = w_count; rc.strip_rows = w_strip;
     rc.row_base = row_base;
-    rc.n_pixels = n_pix;
+    rc.n_pixels = rows * p.width;
     rc.rows = rows;
-    rc.tiles_x = tiles_x;
+    rc.aspect = (float)p.width / (float)p.height;   // pt.rs:239
+    rc.width_inv = 1.0f / (float)p.width;           // pt.rs:250-251
+    rc.height_inv = 1.0f / (float)p.height;
+    rc.spp_inv = 1.0f / (float)p.spp;
+    {   // pt.rs:253-254, 272-275
+        const float spp_sqrt_inv = 1.0f / std::sqrt((float)p.spp);
+        rc.aux_dx = rc.aspect * rc.width_inv * spp_sqrt_inv;
+        rc.aux_dy = rc.height_inv * spp_sqrt_inv;
+    }
+    rc.debug_normal = (p.flags & SPT_RENDER_DEBUG_NORMAL) ? 1u : 0u;
+    return rc;
+}
+
+// The passes of one window: their size, and the queues and counters they use.
+struct PassShape {
+    uint32_t spp_pass;       // samples per pass
+    size_t counts_words;     // the pass counters, [bounce][Q_KINDS][kShards] 128-B lines
+    uint64_t rad_slots;      // per-sample radiance slots per colour plane
+};
+
+// Sizes the passes of the window of rc (plan_ctx) that add `n_samples` samples, grows the scene's workspace to them and binds
+// it and the window's tiles into rc.  sum: the running sums the passes add to (null: the scene's workspace film).
+// collect: every sample of the window is kept (wide box filter), else only the samples of one pass.
+PassShape grow_workspace(spt_scene* sc, const spt_render_params& p, uint32_t n_samples, bool collect, bool fused, bool class_queues, float* sum,
+                         RenderCtx& rc) {
+    const uint32_t n_pix = rc.n_pixels;
+    PassShape ps{};
+    // samples per pass: keep the queues around a few million entries
+    ps.spp_pass = p.samples_per_pass;
+    if (ps.spp_pass == 0) {
+        const uint64_t target = 128ull << 20;
+        ps.spp_pass = (uint32_t)std::max<uint64_t>(1, target / n_pix);
+    }
+    ps.spp_pass = std::min(ps.spp_pass, n_samples);   // (a film's increment: what is left of it)
+    // queue shards: shard s holds what the primary tiles mapped to it can emit, which also bounds
+    // every later generation of that shard
+    const uint32_t tiles_y = (rc.rows + kTile - 1) / kTile;
+    rc.tiles_x = (p.width + kTile - 1) / kTile;
+    rc.n_tiles = rc.tiles_x * tiles_y;
+    uint32_t max_tiles = 0;
+    {
+        std::vector<uint32_t> per(kShards, 0u);
+        for (uint32_t ty = 0; ty < tiles_y; ++ty)
+            for (uint32_t tx = 0; tx < rc.tiles_x; ++tx) max_tiles = std::max(max_tiles, ++per[(tx + 9u * ty) % kShards]);
+    }
+    const uint64_t shard_cap64 = (uint64_t)max_tiles * kBlock * ps.spp_pass;
+    const uint64_t cap64 = shard_cap64 * kShards;
+    if (cap64 > 0x7fffffffull) fail(SPT_ERR_UNSUPPORTED, "render: pass too large (lower samples_per_pass)");
+    const size_t cap = (size_t)cap64;
+    ps.rad_slots = (uint64_t)n_pix * (collect ? p.spp : ps.spp_pass);
+
+    // the hit queue is binned by BxDF class for the general shade kernels (kernels.h, kClasses): class c lives c * cap
+    // entries further.  Memory is what MI355X has (24 B x cap x 8 classes = 26 GB for a 128 M-sample pass)
+    const uint32_t n_classes = (!fused && p.max_depth > 1 && cap * (uint64_t)kClasses <= 0xffffffffull && class_queues) ? kClasses : 1u;
+    for (int k = 0; k < 4; ++k) { sc->qa[k].ensure(cap * 16 * (k == 1 ? n_classes : 1u)); sc->qb[k].ensure(cap * 16); }   // (qa[1]: the compact bounce-0 records sit at their hit's index, in every class)
+    sc->qa[4].ensure(cap * 8);
+    sc->qb[4].ensure(cap * 8);
+    sc->hit_f4.ensure(cap * 16 * n_classes);
+    sc->hit_inst.ensure(cap * 8 * n_classes);
+    if (fused) {
+        sc->hit_f4_next.ensure(cap * 16);
+        sc->hit_inst_next.ensure(cap * 8);
+    }
+    for (int k = 0; k < 3; ++k) sc->sh[k].ensure(cap * 16);
+    ps.counts_words = (size_t)(p.max_depth + 1) * Q_KINDS * kShards * 32;
+    sc->counts.ensure(ps.counts_words * sizeof(uint32_t));
+    sc->rad.ensure((size_t)ps.rad_slots * 3 * sizeof(float));
+    float* const film_sum = sum ? sum : (sc->film.ensure((size_t)n_pix * 3 * sizeof(float)), sc->film.as<float>());
+    sc->first_slot.ensure((size_t)n_pix * sizeof(uint32_t));
+    sc->slot_bits.ensure((size_t)n_pix * ((ps.spp_pass + 7u) / 8u));
+
     rc.qa = PathQueue{sc->qa[0].as<float4>(), sc->qa[1].as<float4>(), sc->qa[2].as<float4>(), sc->qa[3].as<float4>(), sc->qa[4].as<uint2>()};
     rc.qb = PathQueue{sc->qb[0].as<float4>(), sc->qb[1].as<float4>(), sc->qb[2].as<float4>(), sc->qb[3].as<float4>(), sc->qb[4].as<uint2>()};
     rc.hits = HitQueue{sc->hit_f4.as<float4>(), sc->hit_inst.as<uint2>()};
@@ -1749,297 +1800,336 @@ RenderCtx trace_window(RenderRun& run, uint32_t row_base, uint32_t rows, uint32_
     rc.rad = sc->rad.as<float>();
     rc.film = film_sum;
     rc.first_slot = sc->first_slot.as<uint32_t>();
-    rc.aspect = (float)p.width / (float)p.height;   // pt.rs:239
-    rc.width_inv = 1.0f / (float)p.width;           // pt.rs:250-251
-    rc.height_inv = 1.0f / (float)p.height;
-    rc.spp_inv = 1.0f / (float)p.spp;
-    {   // pt.rs:253-254, 272-275
-        const float spp_sqrt_inv = 1.0f / std::sqrt((float)p.spp);
-        rc.aux_dx = rc.aspect * rc.width_inv * spp_sqrt_inv;
-        rc.aux_dy = rc.height_inv * spp_sqrt_inv;
-    }
-    {
-        double oc[3], d2 = 0;
-        for (int k = 0; k < 3; ++k) { oc[k] = sc->bs_center[k] - (double)cam->eye[k]; d2 += oc[k] * oc[k]; }
-        rc.bs_oc = f3{(float)oc[0], (float)oc[1], (float)oc[2]};
-        // a little extra slack for the f32 rounding of oc and of the test itself
-        rc.bs_c = (float)((d2 - sc->bs_radius * sc->bs_radius) * (1.0 - 1e-5));
-        rc.bs_valid = sc->bs_valid ? 1u : 0u;
-        // screen-space bound: project the 8 corners of the union of the instance boxes (double precision).
-        // A point P is seen through image coordinates (u, v) = ((x / aspect + 0.5) W, (y + 0.5) H) with
-        // x = half_cot * (P - eye).right / (P - eye).forward, y likewise with up (k_primary: pt.rs:269-271).
-        rc.cull_i0 = 0; rc.cull_i1 = (int32_t)p.width - 1; rc.cull_j0 = 0; rc.cull_j1 = (int32_t)p.height - 1;
-        if (sc->bs_valid && std::getenv("SPT_NO_PIXEL_CULL") == nullptr) {
-            double umin = 1e300, umax = -1e300, vmin = 1e300, vmax = -1e300;
-            bool ok = true;
-            const double ext = std::max({sc->world_hi[0] - sc->world_lo[0], sc->world_hi[1] - sc->world_lo[1], sc->world_hi[2] - sc->world_lo[2], 1e-30});
-            for (int c = 0; c < 8 && ok; ++c) {
-                double v[3], z = 0, xr = 0, yu = 0;
-                for (int k = 0; k < 3; ++k) {
-                    const double pad = 1e-4 * ext;   // covers the (tiny) padding of the device-side boxes
-                    v[k] = (((c >> k) & 1) ? sc->world_hi[k] + pad : sc->world_lo[k] - pad) - (double)cam->eye[k];
-                    z += v[k] * (double)cam->forward[k];
-                    xr += v[k] * (double)cam->right[k];
-                    yu += v[k] * (double)cam->up[k];
-                }
-                if (!(z > 1e-6 * ext)) { ok = false; break; }   // a corner beside / behind the eye: no finite bound
-                const double x = (double)cam->half_cot_half_fov * xr / z, y = (double)cam->half_cot_half_fov * yu / z;
-                const double u = (x / ((double)p.width / (double)p.height) + 0.5) * (double)p.width, w = (y + 0.5) * (double)p.height;
-                umin = std::min(umin, u); umax = std::max(umax, u);
-                vmin = std::min(vmin, w); vmax = std::max(vmax, w);
-            }
-            if (ok && std::isfinite(umin) && std::isfinite(umax) && std::isfinite(vmin) && std::isfinite(vmax)) {
-                // pixel i covers u in [i, i + 1); row j covers v in [H - 1 - j, H - j); one pixel of slack each side
-                const double H = (double)p.height;
-                auto clampi = [](double x, double lo, double hi) { return (int32_t)std::max(lo, std::min(hi, x)); };
-                rc.cull_i0 = clampi(std::floor(umin) - 1.0, -1.0, (double)p.width);
-                rc.cull_i1 = clampi(std::floor(umax) + 1.0, -1.0, (double)p.width);
-                rc.cull_j0 = clampi(std::floor(H - 1.0 - vmax) - 1.0, -1.0, H);
-                rc.cull_j1 = clampi(std::floor(H - 1.0 - vmin) + 2.0, -1.0, H);
-            }
-        }
-    }
+    return ps;
+}
 
-    rc.dyn_refill_below = dyn_refill_below;
-    rc.dyn_steps = dyn_steps;
-    // rays of a path tracer are short (cfg5: ~4 node + ~2 triangle + ~1 instance records per segment = 2 - 3 rounds):
-    // a finished lane that waits several rounds for its wave costs more than the refill check
-    // if-if with 4 rounds per check: 87.4 ms; 8 rounds 95.2; while-while (SPT_STREAM_IFIF=0) 100 - 121 ms
-    rc.stream_rounds = std::max(1u, std::min(255u, env_u32("SPT_STREAM_ROUNDS", 4u))) | (env_u32("SPT_STREAM_IFIF", 1u) ? 0x100u : 0u);
-    rc.stream_refill_below = std::max(1u, std::min(64u, env_u32("SPT_STREAM_REFILL", 40u)));
-    rc.visits = sc->visits.as<unsigned long long>();
-    rc.debug_normal = (p.flags & SPT_RENDER_DEBUG_NORMAL) ? 1u : 0u;
-    rc.row_span = row_span_dev;
-    // tiles of this shard that intersect the screen-space bound (all of them with an environment)
-    uint32_t active_tiles = pix_blocks;
-    uint64_t live_pixels = n_pix;
-    if (sc->d.env_w == 0u) {
-        active_tiles = 0;
-        live_pixels = 0;
-        for (uint32_t r = 0; r < rows; ++r) {
-            const uint32_t strip = r / w_strip;
-            const int32_t j = (int32_t)(row_base + (strip * w_count + w_index) * w_strip + (r - strip * w_strip));
-            if (j >= rc.cull_j0 && j <= rc.cull_j1) {
-                int32_t i0 = std::max(rc.cull_i0, 0), i1 = std::min(rc.cull_i1, (int32_t)p.width - 1);
-                if (row_span_dev) { i0 = std::max(i0, sc->span_host[2 * (size_t)j]); i1 = std::min(i1, sc->span_host[2 * (size_t)j + 1]); }
-                live_pixels += (uint64_t)std::max(0, i1 - i0 + 1);
-            }
+// k_primary's early-outs for the camera: the bounding sphere of the instances relative to the eye, and the rectangle of the
+// image their world box projects to (the whole image without pixel_cull or a finite bound)
+void screen_bound(const spt_scene* sc, const spt_render_params& p, const spt_camera& cam, bool pixel_cull, RenderCtx& rc) {
+    double oc[3], d2 = 0;
+    for (int k = 0; k < 3; ++k) { oc[k] = sc->bs_center[k] - (double)cam.eye[k]; d2 += oc[k] * oc[k]; }
+    rc.bs_oc = f3{(float)oc[0], (float)oc[1], (float)oc[2]};
+    // a little extra slack for the f32 rounding of oc and of the test itself
+    rc.bs_c = (float)((d2 - sc->bs_radius * sc->bs_radius) * (1.0 - 1e-5));
+    rc.bs_valid = sc->bs_valid ? 1u : 0u;
+    // screen-space bound: project the 8 corners of the union of the instance boxes (double precision).
+    // A point P is seen through image coordinates (u, v) = ((x / aspect + 0.5) W, (y + 0.5) H) with
+    // x = half_cot * (P - eye).right / (P - eye).forward, y likewise with up (k_primary: pt.rs:269-271).
+    rc.cull_i0 = 0; rc.cull_i1 = (int32_t)p.width - 1; rc.cull_j0 = 0; rc.cull_j1 = (int32_t)p.height - 1;
+    if (!sc->bs_valid || !pixel_cull) return;
+    double umin = 1e300, umax = -1e300, vmin = 1e300, vmax = -1e300;
+    bool ok = true;
+    const double ext = std::max({sc->world_hi[0] - sc->world_lo[0], sc->world_hi[1] - sc->world_lo[1], sc->world_hi[2] - sc->world_lo[2], 1e-30});
+    for (int c = 0; c < 8 && ok; ++c) {
+        double v[3], z = 0, xr = 0, yu = 0;
+        for (int k = 0; k < 3; ++k) {
+            const double pad = 1e-4 * ext;   // covers the (tiny) padding of the device-side boxes
+            v[k] = (((c >> k) & 1) ? sc->world_hi[k] + pad : sc->world_lo[k] - pad) - (double)cam.eye[k];
+            z += v[k] * (double)cam.forward[k];
+            xr += v[k] * (double)cam.right[k];
+            yu += v[k] * (double)cam.up[k];
         }
-        for (uint32_t ty = 0; ty < tiles_y; ++ty)
-            for (uint32_t tx = 0; tx < tiles_x; ++tx) {
-                const int32_t i_lo = (int32_t)(tx * kTile), i_hi = (int32_t)std::min(p.width, (tx + 1) * kTile) - 1;
-                bool rows_in = false;
-                for (uint32_t r = ty * kTile; r < std::min(rows, (ty + 1) * kTile) && !rows_in; ++r) {
-                    const uint32_t strip = r / w_strip;
-                    const int32_t j = (int32_t)(row_base + (strip * w_count + w_index) * w_strip + (r - strip * w_strip));
-                    rows_in = j >= rc.cull_j0 && j <= rc.cull_j1 && i_hi >= rc.cull_i0 && i_lo <= rc.cull_i1;
-                    if (rows_in && row_span_dev) rows_in = i_hi >= sc->span_host[2 * (size_t)j] && i_lo <= sc->span_host[2 * (size_t)j + 1];
-                }
-                if (rows_in) ++active_tiles;
+        if (!(z > 1e-6 * ext)) { ok = false; break; }   // a corner beside / behind the eye: no finite bound
+        const double x = (double)cam.half_cot_half_fov * xr / z, y = (double)cam.half_cot_half_fov * yu / z;
+        const double u = (x / ((double)p.width / (double)p.height) + 0.5) * (double)p.width, w = (y + 0.5) * (double)p.height;
+        umin = std::min(umin, u); umax = std::max(umax, u);
+        vmin = std::min(vmin, w); vmax = std::max(vmax, w);
+    }
+    if (ok && std::isfinite(umin) && std::isfinite(umax) && std::isfinite(vmin) && std::isfinite(vmax)) {
+        // pixel i covers u in [i, i + 1); row j covers v in [H - 1 - j, H - j); one pixel of slack each side
+        const double H = (double)p.height;
+        auto clampi = [](double x, double lo, double hi) { return (int32_t)std::max(lo, std::min(hi, x)); };
+        rc.cull_i0 = clampi(std::floor(umin) - 1.0, -1.0, (double)p.width);
+        rc.cull_i1 = clampi(std::floor(umax) + 1.0, -1.0, (double)p.width);
+        rc.cull_j0 = clampi(std::floor(H - 1.0 - vmax) - 1.0, -1.0, H);
+        rc.cull_j1 = clampi(std::floor(H - 1.0 - vmin) + 2.0, -1.0, H);
+    }
+}
+
+// The pixels of rc's window inside the screen-space bound (and the row spans, when rc has them) and the tiles that
+// intersect it; every pixel and tile with an environment
+struct LiveCount {
+    uint32_t active_tiles;
+    uint64_t live_pixels;
+};
+LiveCount count_live(const spt_scene* sc, const RenderCtx& rc) {
+    if (sc->d.env_w != 0u) return LiveCount{rc.n_tiles, rc.n_pixels};
+    auto image_row = [&rc](uint32_t r) {   // global_row of kernels.h
+        const uint32_t strip = r / rc.strip_rows;
+        return (int32_t)(rc.row_base + (strip * rc.shard_count + rc.shard_index) * rc.strip_rows + (r - strip * rc.strip_rows));
+    };
+    LiveCount live{0u, 0u};
+    for (uint32_t r = 0; r < rc.rows; ++r) {
+        const int32_t j = image_row(r);
+        if (j >= rc.cull_j0 && j <= rc.cull_j1) {
+            int32_t i0 = std::max(rc.cull_i0, 0), i1 = std::min(rc.cull_i1, (int32_t)rc.width - 1);
+            if (rc.row_span) { i0 = std::max(i0, sc->span_host[2 * (size_t)j]); i1 = std::min(i1, sc->span_host[2 * (size_t)j + 1]); }
+            live.live_pixels += (uint64_t)std::max(0, i1 - i0 + 1);
+        }
+    }
+    for (uint32_t ty = 0; ty < rc.n_tiles / rc.tiles_x; ++ty)
+        for (uint32_t tx = 0; tx < rc.tiles_x; ++tx) {
+            const int32_t i_lo = (int32_t)(tx * kTile), i_hi = (int32_t)std::min(rc.width, (tx + 1) * kTile) - 1;
+            bool rows_in = false;
+            for (uint32_t r = ty * kTile; r < std::min(rc.rows, (ty + 1) * kTile) && !rows_in; ++r) {
+                const int32_t j = image_row(r);
+                rows_in = j >= rc.cull_j0 && j <= rc.cull_j1 && i_hi >= rc.cull_i0 && i_lo <= rc.cull_i1;
+                if (rows_in && rc.row_span) rows_in = i_hi >= sc->span_host[2 * (size_t)j] && i_lo <= sc->span_host[2 * (size_t)j + 1];
             }
+            if (rows_in) ++live.active_tiles;
+        }
+    return live;
+}
+
+// The primary kernel of a pass over `blocks` workgroups (one per tile, or per tile and sample chunk: kChunked).  The mask
+// argument (FilmMask) makes it an adaptive film's k_*<..., kMask>, which exists chunked and without visit counting only.
+template <bool kChunked, class... M>
+void launch_primary(const RenderRun& run, uint32_t blocks, const RenderCtx& rc, M... mask) {
+    constexpr bool kMask = sizeof...(M) != 0;
+    const spt_scene* const sc = run.sc;
+    void (*fn)(DScene, RenderCtx, M...);
+    if (run.stream_p) fn = k_primary_stream<kChunked, false, kMask, M...>;
+    else if (run.use_eye) fn = k_primary<true, kChunked, false, true, kMask, M...>;
+    else if (run.L) fn = k_primary<true, kChunked, false, false, kMask, M...>;
+    else fn = k_primary<false, kChunked, false, false, kMask, M...>;
+    if constexpr (!kMask) {   // (visits are only counted outside LDS, so never through the eye-relative copy)
+        if (run.count) fn = run.stream_p ? k_primary_stream<kChunked, true> : k_primary<false, kChunked, true>;
     }
+    hipLaunchKernelGGL(fn, dim3(blocks), dim3(kBlock), run.use_eye ? sc->eye_lds_bytes : run.lds, run.st, run.use_eye ? sc->eye_d : sc->d, rc, mask...);
+}
+
+// The sample chunks per tile and the primary kernel of one pass.  Returns whether the kernel was a chunked one (which
+// marks the samples that own a radiance slot in rc.slot_bits for the resolve).
+bool primary_pass(const RenderRun& run, RenderCtx& rc, const SampleTarget& tgt, uint32_t active_tiles, bool collect) {
+    spt_scene* const sc = run.sc;
+    // sample chunks per tile: aim at ~6144 busy workgroups (24 per CU; 4096 .. 8192 measured within 2 %) given the tiles inside the screen bound
+    // (an adaptive film: the tiles its last adapt left active; chunking does not change bits)
+    const uint32_t busy_tiles = tgt.mask.pixel ? std::min(active_tiles, tgt.mask_tiles) : active_tiles;
+    uint32_t want = std::min<uint32_t>(64u, (6144u + busy_tiles - 1u) / std::max(busy_tiles, 1u));
+    if (run.primary_chunks) want = run.primary_chunks;
+    want = std::max(1u, std::min(want, rc.pass_samples));
+    rc.chunk_samples = (rc.pass_samples + want - 1u) / want;
+    rc.chunk_samples = (rc.chunk_samples + 7u) / 8u * 8u;   // slot_bits: a group of 8 samples belongs to one chunk
+    rc.primary_chunks = (rc.pass_samples + rc.chunk_samples - 1u) / rc.chunk_samples;
+    // collect: every sample owns a slot, which is what the chunked kernel does.  Moments of a scene with an environment: the
+    // un-chunked kernel adds the misses before a pixel's first hit straight into its sum, past k_resolve<true>'s Q
+    // An adaptive film takes the chunked path only (its masked instances), whatever the chunk count.
+    const bool all_slots = collect || (tgt.sq != nullptr && sc->d.env_w != 0u) || tgt.mask.pixel != nullptr;
+    const bool chunked = rc.primary_chunks > 1u || all_slots;
+    rc.slot_bits = chunked ? sc->slot_bits.as<uint8_t>() : nullptr;
+    if (tgt.mask.pixel != nullptr) {
+        if (run.count) fail(SPT_ERR_INVALID_ARG, "render: an adaptive film does not count visits");
+        launch_primary<true>(run, rc.n_tiles * rc.primary_chunks, rc, tgt.mask);
+    } else if (chunked) {
+        launch_primary<true>(run, rc.n_tiles * rc.primary_chunks, rc);
+    } else {
+        launch_primary<false>(run, rc.n_tiles, rc);
+    }
+    return chunked;
+}
+
+using BounceFn = void (*)(DScene, RenderCtx, uint32_t);
+
+// k_shade<kFeat, kFirst, false, kTab, kGeoLds> of the general pipeline: the shading tables and the geometry from LDS, or
+// neither, or - levels 3 and 5 with the geometry in LDS and the tables not - the BSSRDF probe walking the LDS copy (kGeoLds)
+template <int kFeat>
+BounceFn shade_level(bool first, bool tab, bool geo_lds) {
+    if (tab) return first ? k_shade<kFeat, true, false, true, true> : k_shade<kFeat, false, false, true, true>;
+    if constexpr (kFeat == 3 || kFeat == 5)
+        if (geo_lds) return first ? k_shade<kFeat, true, false, false, true> : k_shade<kFeat, false, false, false, true>;
+    return first ? k_shade<kFeat, true, false, false, false> : k_shade<kFeat, false, false, false, false>;
+}
+
+// The shade kernel of bounce b.  tail_loop: the fused kernel that takes bounce 1 and every later one in one launch.
+BounceFn shade_kernel(const RenderRun& run, uint32_t b, bool tail_loop) {
+    const spt_scene* const sc = run.sc;
+    const bool first = b == 0;
+    if (run.fused) return first ? k_shade<0, true, true, true, true> : tail_loop ? k_shade<0, false, true, true, true, true> : k_shade<0, false, true, true, true>;
+    if (sc->simple) return shade_level<0>(first, run.tab, false);
+    if (!sc->textured) return shade_level<1>(first, run.tab, false);
+    if (!sc->subsurface) return shade_level<2>(first, run.tab, false);
+    if (!sc->has_probe) return shade_level<4>(first, run.tab, false);   // glints only: no probe, so the geometry's place does not matter
+    return sc->has_pndf ? shade_level<5>(first, run.tab, run.L) : shade_level<3>(first, run.tab, run.L);
+}
+
+// The shadow or the extension rays of a bounce: the kernels of one ray kind, [kCount] where visit counting makes two
+struct RayKernels {
+    BounceFn stream[2];     // the streaming walker (stream.h)
+    BounceFn dyn[2];        // persistent waves that refill
+    BounceFn mem[2];        // persistent waves, geometry from memory
+    BounceFn lds, lds_flat;   // geometry in LDS; kFlat: the scene's flat layout (flat.h)
+};
+const RayKernels kShadowRays{{k_shadow_stream<false>, k_shadow_stream<true>}, {k_shadow_dyn<false>, k_shadow_dyn<true>},
+                             {k_shadow<false, false>, k_shadow<false, true>}, k_shadow<true, false>, k_shadow<true, false, true>};
+const RayKernels kExtendRays{{k_extend_stream<false>, k_extend_stream<true>}, {k_extend_dyn<false>, k_extend_dyn<true>},
+                             {k_extend<false, false>, k_extend<false, true>}, k_extend<true, false>, k_extend<true, false, true>};
+
+void launch_rays(const RenderRun& run, const RayKernels& k, bool stream, bool dyn, hipStream_t s, const RenderCtx& ru, uint32_t b) {
+    const spt_scene* const sc = run.sc;
+    BounceFn fn = k.mem[run.count];
+    uint32_t blocks = kPersistentBlocks;
+    if (stream) { fn = k.stream[run.count]; blocks = run.kDynBlocks; }
+    else if (run.L) fn = sc->d.flat ? k.lds_flat : k.lds;
+    else if (dyn) { fn = k.dyn[run.count]; blocks = run.kDynBlocks; }
+    hipLaunchKernelGGL(fn, dim3(blocks), dim3(kBlock), run.lds, s, sc->d, ru, b);
+}
+
+// One bounce of a pass: shade, then shadow and extension rays.  Returns true when the fused pipeline's tail loop took every
+// later bounce along.
+bool bounce(RenderRun& run, const RenderCtx& rc, uint32_t b) {
+    spt_scene* const sc = run.sc;
+    const uint32_t max_depth = run.params->max_depth;
+    // the fused kernel: shade + shadow + extend of this bounce in one kernel; vertices of bounce b live in (qa, hits) for even
+    // b and in (qb, hits_next) for odd b.  Un-fused: the shade stage of bounce b reads the path records its predecessor
+    // wrote (ru.qa) through the hits' source indices and writes the next ones to ru.qb, which the extend stage traces: the
+    // two path queues swap roles every bounce, the hit queue is one buffer
+    RenderCtx ru = rc;
+    if (b & 1u) {
+        std::swap(ru.qa, ru.qb);
+        if (run.fused) std::swap(ru.hits, ru.hits_next);
+    }
+    // few vertices left after bounce 0 (seen by the previous pass with a counter readback): bounce 1 and
+    // everything after it in ONE launch, each lane following its path to the end (k_shade's kLoop)
+    const bool tail_loop = run.fused && b == 1 && run.tail_loop && sc->tail_vertices <= kTailLoopBelow;
+    // LDS: the traversal stack and geometry, also for the BSSRDF probe, which walks the BVH inside k_shade<3 | 5>
+    const size_t shade_lds = (run.fused || run.tab || sc->has_probe) ? run.lds : 0;
+    run.begin(b == 0 ? SPT_K_SHADE_FIRST : SPT_K_SHADE);
+    hipLaunchKernelGGL(shade_kernel(run, b, tail_loop), dim3(kPersistentBlocks), dim3(kBlock), shade_lds, run.st, sc->d, ru, b);
+    run.end();
+    if (run.fused) return tail_loop;
+    // k_shadow(b) and k_extend(b) are independent unless the scene has an environment (then a missing
+    // extension ray adds its term to the same radiance slot the shadow ray of that vertex adds to, and
+    // the reference's order of the two additions has to be kept): without one, the shadow kernel runs on
+    // a side stream next to the extension kernel and is joined before the next stage reads the slots.
+    const bool side = run.overlap && b + 1 < max_depth;
+    const hipStream_t ss = side ? sc->stream2 : run.st;
+    if (side) {
+        HIP_CHECK(hipEventRecord(sc->ev_fork, run.st));
+        HIP_CHECK(hipStreamWaitEvent(ss, sc->ev_fork, 0));
+    }
+    run.begin(SPT_K_SHADOW);
+    launch_rays(run, kShadowRays, run.stream_s, run.dyn_shadow, ss, ru, b);
+    run.end();
+    if (side) HIP_CHECK(hipEventRecord(sc->ev_join, ss));
+    if (b + 1 < max_depth) {
+        run.begin(SPT_K_EXTEND);
+        launch_rays(run, kExtendRays, run.stream_e, run.dyn_extend, run.st, ru, b);
+        run.end();
+    }
+    if (side) HIP_CHECK(hipStreamWaitEvent(run.st, sc->ev_join, 0));
+    return false;
+}
+
+// The resolve of a pass: k_resolve_bits after a chunked primary (rc.slot_bits), k_resolve after an un-chunked one; sq: the
+// sums of the squares too (SPT_FILM_MOMENTS)
+void launch_resolve(const RenderRun& run, const RenderCtx& rc, float* sq) {
+    const dim3 grid(rc.n_tiles), block(kBlock);
+    if (sq != nullptr) {
+        void (*const fn)(RenderCtx, float*) = rc.slot_bits ? k_resolve_bits<16u, true, float*> : k_resolve<true, float*>;
+        hipLaunchKernelGGL(fn, grid, block, 0, run.st, rc, sq);
+    } else {
+        void (*const fn)(RenderCtx) = rc.slot_bits ? (run.resolve32 ? k_resolve_bits<32u> : k_resolve_bits<16u>) : k_resolve<>;
+        hipLaunchKernelGGL(fn, grid, block, 0, run.st, rc);
+    }
+}
+
+// The pass counters of one pass into the call's statistics; the vertices of bounce 1 become the scene's tail-loop hint
+void read_counters(RenderRun& run, const RenderCtx& rc, size_t counts_words) {
+    const uint32_t max_depth = run.params->max_depth;
+    const std::vector<uint32_t>& h = run.h_counts;
+    run.h_counts.resize(counts_words);
+    HIP_CHECK(hipMemcpyAsync(run.h_counts.data(), rc.counts, counts_words * sizeof(uint32_t), hipMemcpyDeviceToHost, run.st));
+    HIP_CHECK(hipStreamSynchronize(run.st));
+    run.seg_closest += (uint64_t)rc.n_pixels * rc.pass_samples;
+    auto qsum = [&](uint32_t b, uint32_t q) {
+        uint64_t t = 0;
+        for (uint32_t s = 0; s < kShards; ++s) t += h[((size_t)(b * Q_KINDS + q) * kShards + s) * 32];
+        if (q == Q_HIT)     // the hit queue's other classes (bounce >= 1 of the general pipeline)
+            for (uint32_t c = 1; c < kClasses; ++c)
+                for (uint32_t s = 0; s < kShards; ++s) t += h[((size_t)(b * Q_KINDS + Q_HIT_CLASS1 + c - 1u) * kShards + s) * 32];
+        return t;
+    };
+    if (max_depth > 1) run.sc->tail_vertices = qsum(1, Q_HIT);
+    run.primary_hits += qsum(0, Q_HIT);
+    run.shadow_first += qsum(0, Q_SHADOW);
+    if (max_depth > 1) run.vertices_second += qsum(1, Q_HIT);
+    for (uint32_t b = 0; b < max_depth; ++b) {
+        run.path_vertices += qsum(b, Q_HIT);
+        run.seg_shadow += qsum(b, Q_SHADOW);
+        if (b + 1 < max_depth) run.seg_closest += qsum(b, Q_EXT);
+    }
+}
+
+// One window of whole image rows through the wavefront pipeline.  A shard is one window (row_base 0, the
+// strip formula of the ABI); a wide box filter renders bands of consecutive rows (w_count = w_strip = 1).
+// collect: keep every sample's radiance (3 planes [c][sample][pixel] in sc->rad) instead of summing it into
+// the film.  tgt: the samples of the plan this call adds and the sums they go to (see SampleTarget).  Returns the
+// context the resolve kernels of the caller need.
+RenderCtx trace_window(RenderRun& run, uint32_t row_base, uint32_t rows, uint32_t w_index, uint32_t w_count, uint32_t w_strip, bool collect,
+                       const SampleTarget& tgt) {
+    spt_scene* const sc = run.sc;
+    const spt_render_params& p = *run.params;
+    if ((uint64_t)rows * p.width > 0x7fffffffull) fail(SPT_ERR_UNSUPPORTED, "render: window larger than 2^31 pixels");
+    RenderCtx rc = plan_ctx(p, *run.cam, row_base, rows, w_index, w_count, w_strip);
+    const uint32_t n_pix = rc.n_pixels;
+    const PassShape ps = grow_workspace(sc, p, tgt.count, collect, run.fused, run.class_queues, tgt.sum, rc);
+    screen_bound(sc, p, *run.cam, run.pixel_cull, rc);
+    rc.dyn_refill_below = run.dyn_refill_below;
+    rc.dyn_steps = run.dyn_steps;
+    rc.stream_rounds = run.stream_rounds;
+    rc.stream_refill_below = run.stream_refill_below;
+    rc.visits = sc->visits.as<unsigned long long>();
+    rc.row_span = run.row_span_dev;
+    const LiveCount live = count_live(sc, rc);
     if (tgt.zero) {
-        HIP_CHECK(hipMemsetAsync(rc.film, 0, (size_t)n_pix * 3 * sizeof(float), st));
-        if (tgt.sq) HIP_CHECK(hipMemsetAsync(tgt.sq, 0, (size_t)n_pix * 3 * sizeof(float), st));
+        HIP_CHECK(hipMemsetAsync(rc.film, 0, (size_t)n_pix * 3 * sizeof(float), run.st));
+        if (tgt.sq) HIP_CHECK(hipMemsetAsync(tgt.sq, 0, (size_t)n_pix * 3 * sizeof(float), run.st));
     }
-    if (collect) HIP_CHECK(hipMemsetAsync(sc->rad.p, 0, (size_t)rad64 * 3 * sizeof(float), st));   // pixels outside the screen bound write no slots
+    if (collect) HIP_CHECK(hipMemsetAsync(sc->rad.p, 0, (size_t)ps.rad_slots * 3 * sizeof(float), run.st));   // pixels outside the screen bound write no slots
     bool chunked_any = false;
     // max_depth 0: `while curr_depth < self.max_depth` (pt.rs:48) never runs, every sample is black - environment included.
     // Nothing is traced: the film (and, for a wide box filter, the kept samples) stay at the zeros written above.  (The
     // passes below would mark the hits' radiance slots as owned and no shade launch would ever write them.)
     // Passes start anywhere in the plan (a film's increment at its first uncovered sample): the slot bits, the chunks and the
     // packed sample index of k_primary count from the pass's first sample, only the sampler sees the plan's index pass_first + s.
-    for (uint32_t s0 = tgt.first; s0 < (p.max_depth == 0u ? tgt.first : s_end); s0 += spp_pass) {
+    const uint32_t s_end = tgt.first + tgt.count;
+    for (uint32_t s0 = tgt.first; s0 < (p.max_depth == 0u ? tgt.first : s_end); s0 += ps.spp_pass) {
         rc.pass_first = s0;
-        rc.pass_samples = std::min(spp_pass, s_end - s0);
+        rc.pass_samples = std::min(ps.spp_pass, s_end - s0);
         rc.rad_plane = collect ? (size_t)p.spp * n_pix : (size_t)rc.pass_samples * n_pix;
-        rc.pack_first = (sc->d.n_instances < (1u << 20) && rc.pass_samples <= 4096u && std::getenv("SPT_NO_PACK_FIRST") == nullptr) ? 1u : 0u;
+        rc.pack_first = (run.pack_first && rc.pass_samples <= 4096u) ? 1u : 0u;
         rc.rad = sc->rad.as<float>() + (collect ? (size_t)(s0 - tgt.first) * n_pix : 0);
-        begin(SPT_K_OTHER);
-        HIP_CHECK(hipMemsetAsync(rc.counts, 0, counts_bytes, st));
-        end();
-        begin(SPT_K_PRIMARY);
-        // sample chunks per tile: aim at ~6144 busy workgroups (24 per CU; 4096 .. 8192 measured within 2 %) given the tiles inside the screen bound
-        rc.n_tiles = pix_blocks;
-        rc.primary_chunks = 1;
-        {
-            // (an adaptive film: the tiles its last adapt left active; chunking does not change bits)
-        const uint32_t busy_tiles = tgt.mask.pixel ? std::min(active_tiles, tgt.mask_tiles) : active_tiles;
-        uint32_t want = std::min<uint32_t>(64u, (6144u + busy_tiles - 1u) / std::max(busy_tiles, 1u));
-            if (const char* v = std::getenv("SPT_PRIMARY_CHUNKS")) want = (uint32_t)std::max(1, std::atoi(v));
-            want = std::max(1u, std::min(want, rc.pass_samples));
-            rc.chunk_samples = (rc.pass_samples + want - 1u) / want;
-            rc.chunk_samples = (rc.chunk_samples + 7u) / 8u * 8u;   // slot_bits: a group of 8 samples belongs to one chunk
-            rc.primary_chunks = (rc.pass_samples + rc.chunk_samples - 1u) / rc.chunk_samples;
-        }
-        const bool stream = sc->swalk && !L;
-        // which kernel classes the streaming walker serves (1 primary, 2 shadow, 4 extend).  Measured on cfg5, one box
-        // (gpurun_out r2j): extension rays 93.5 ms refilling state machine -> 87.4 ms streaming if-if; primary rays
-        // 8.8 -> 12.4 ms and shadow rays 9.8 -> 11.3 ms (coherent / short walks: the state machine's tighter loop wins)
-        const uint32_t stream_mask = env_u32("SPT_STREAM_MASK", SPT_WITH_BEZIER ? 6u : 4u);   // (patch scenes: shadow rays too, 214 -> 197 ms on t_catmull.json)
-        const bool stream_p = stream && (stream_mask & 1u), stream_s = stream && (stream_mask & 2u), stream_e = stream && (stream_mask & 4u);
-        rc.slot_bits = nullptr;
-        // collect: every sample owns a slot, which is what the chunked kernel does.  Moments of a scene with an environment: the
-        // un-chunked kernel adds the misses before a pixel's first hit straight into its sum, past k_resolve<true>'s Q
-        // An adaptive film takes the chunked path only (its masked instances), whatever the chunk count.
-        const bool all_slots = collect || (tgt.sq != nullptr && sc->d.env_w != 0u) || tgt.mask.pixel != nullptr;
-        if (tgt.mask.pixel != nullptr) {
-            if (count) fail(SPT_ERR_INVALID_ARG, "render: an adaptive film does not count visits");
-            chunked_any = true;
-            rc.slot_bits = sc->slot_bits.as<uint8_t>();
-            const dim3 grid(pix_blocks * rc.primary_chunks);
-            if (stream_p) hipLaunchKernelGGL((k_primary_stream<true, false, true, FilmMask>), grid, dim3(kBlock), lds, st, sc->d, rc, tgt.mask);
-            else if (L && use_eye) hipLaunchKernelGGL((k_primary<true, true, false, true, true, FilmMask>), grid, dim3(kBlock), sc->eye_lds_bytes, st, sc->eye_d, rc, tgt.mask);
-            else if (L) hipLaunchKernelGGL((k_primary<true, true, false, false, true, FilmMask>), grid, dim3(kBlock), lds, st, sc->d, rc, tgt.mask);
-            else hipLaunchKernelGGL((k_primary<false, true, false, false, true, FilmMask>), grid, dim3(kBlock), lds, st, sc->d, rc, tgt.mask);
-        } else if (rc.primary_chunks > 1u || all_slots) {
-            chunked_any = true;
-            rc.slot_bits = sc->slot_bits.as<uint8_t>();
-            if (stream_p && count) hipLaunchKernelGGL((k_primary_stream<true, true>), dim3(pix_blocks * rc.primary_chunks), dim3(kBlock), lds, st, sc->d, rc);
-            else if (stream_p) hipLaunchKernelGGL((k_primary_stream<true, false>), dim3(pix_blocks * rc.primary_chunks), dim3(kBlock), lds, st, sc->d, rc);
-            else if (L && use_eye) hipLaunchKernelGGL((k_primary<true, true, false, true>), dim3(pix_blocks * rc.primary_chunks), dim3(kBlock), sc->eye_lds_bytes, st, sc->eye_d, rc);
-            else if (L) hipLaunchKernelGGL((k_primary<true, true, false>), dim3(pix_blocks * rc.primary_chunks), dim3(kBlock), lds, st, sc->d, rc);
-            else if (count) hipLaunchKernelGGL((k_primary<false, true, true>), dim3(pix_blocks * rc.primary_chunks), dim3(kBlock), lds, st, sc->d, rc);
-            else hipLaunchKernelGGL((k_primary<false, true, false>), dim3(pix_blocks * rc.primary_chunks), dim3(kBlock), lds, st, sc->d, rc);
-        } else {
-            if (stream_p && count) hipLaunchKernelGGL((k_primary_stream<false, true>), dim3(pix_blocks), dim3(kBlock), lds, st, sc->d, rc);
-            else if (stream_p) hipLaunchKernelGGL((k_primary_stream<false, false>), dim3(pix_blocks), dim3(kBlock), lds, st, sc->d, rc);
-            else if (L && use_eye) hipLaunchKernelGGL((k_primary<true, false, false, true>), dim3(pix_blocks), dim3(kBlock), sc->eye_lds_bytes, st, sc->eye_d, rc);
-            else if (L) hipLaunchKernelGGL((k_primary<true, false, false>), dim3(pix_blocks), dim3(kBlock), lds, st, sc->d, rc);
-            else if (count) hipLaunchKernelGGL((k_primary<false, false, true>), dim3(pix_blocks), dim3(kBlock), lds, st, sc->d, rc);
-            else hipLaunchKernelGGL((k_primary<false, false, false>), dim3(pix_blocks), dim3(kBlock), lds, st, sc->d, rc);
-        }
-        end();
-        for (uint32_t b = 0; b < p.max_depth; ++b) {
-            begin(b == 0 ? SPT_K_SHADE_FIRST : SPT_K_SHADE);
-            if (fused) {
-                // shade + shadow + extend of this bounce in one kernel; vertices of bounce b live in
-                // (qa, hits) for even b and in (qb, hits_next) for odd b
-                RenderCtx rb = rc;
-                if (b & 1u) { std::swap(rb.qa, rb.qb); std::swap(rb.hits, rb.hits_next); }
-                // few vertices left after bounce 0 (seen by the previous pass with a counter readback): bounce 1 and
-                // everything after it in ONE launch, each lane following its path to the end (k_shade's kLoop)
-                const bool tail_loop = b == 1 && sc->tail_vertices <= kTailLoopBelow && std::getenv("SPT_NO_TAIL_LOOP") == nullptr;
-                if (b == 0) hipLaunchKernelGGL((k_shade<0, true, true, true, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, rb, b);
-                else if (tail_loop) hipLaunchKernelGGL((k_shade<0, false, true, true, true, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, rb, b);
-                else hipLaunchKernelGGL((k_shade<0, false, true, true, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, rb, b);
-                end();
-                if (tail_loop) break;
-                continue;
-            }
-            // un-fused: the shade stage of bounce b reads the path records its predecessor wrote (ru.qa) through the
-            // hits' source indices and writes the next ones to ru.qb, which the extend stage traces: the two path
-            // queues swap roles every bounce, the hit queue is one buffer
-            RenderCtx ru = rc;
-            if (b & 1u) std::swap(ru.qa, ru.qb);
-            const bool tab = sc->lds_tables && std::getenv("SPT_NO_LDS_TABLES") == nullptr;   // shading tables from LDS (tab_ld)
-            const size_t shade_lds = sc->has_probe ? lds : 0;   // the BSSRDF probe walks the BVH inside k_shade<3 | 5>: traversal stack
-#define SPT_LAUNCH_SHADE(FEAT)                                                                                                                 \
-if (tab) {                                                                                                                                 \
-    if (b == 0) hipLaunchKernelGGL((k_shade<FEAT, true, false, true, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, ru, b);  \
-    else hipLaunchKernelGGL((k_shade<FEAT, false, false, true, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, ru, b);        \
-} else {                                                                                                                                   \
-    if (b == 0) hipLaunchKernelGGL((k_shade<FEAT, true, false, false, false>), dim3(kPersistentBlocks), dim3(kBlock), shade_lds, st, sc->d, ru, b); \
-    else hipLaunchKernelGGL((k_shade<FEAT, false, false, false, false>), dim3(kPersistentBlocks), dim3(kBlock), shade_lds, st, sc->d, ru, b);       \
-}
-            if (sc->simple) { SPT_LAUNCH_SHADE(0) } else if (!sc->textured) { SPT_LAUNCH_SHADE(1) } else if (!sc->subsurface) { SPT_LAUNCH_SHADE(2) }
-            else if (!sc->has_probe) { SPT_LAUNCH_SHADE(4) }          // glints only: no probe, so the geometry's place does not matter
-            else if (tab || !L) { if (sc->has_pndf) { SPT_LAUNCH_SHADE(5) } else { SPT_LAUNCH_SHADE(3) } }
-            else if (sc->has_pndf) {   // geometry in LDS, tables not: the probe still walks the LDS copy (k_shade's kGeoLds)
-                if (b == 0) hipLaunchKernelGGL((k_shade<5, true, false, false, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, ru, b);
-                else hipLaunchKernelGGL((k_shade<5, false, false, false, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, ru, b);
-            } else {
-                if (b == 0) hipLaunchKernelGGL((k_shade<3, true, false, false, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, ru, b);
-                else hipLaunchKernelGGL((k_shade<3, false, false, false, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, ru, b);
-            }
-#undef SPT_LAUNCH_SHADE
-            end();
-            // k_shadow(b) and k_extend(b) are independent unless the scene has an environment (then a missing
-            // extension ray adds its term to the same radiance slot the shadow ray of that vertex adds to, and
-            // the reference's order of the two additions has to be kept): without one, the shadow kernel runs on
-            // a side stream next to the extension kernel and is joined before the next stage reads the slots.
-            const bool side = overlap && b + 1 < p.max_depth;
-            hipStream_t ss = side ? sc->stream2 : st;
-            if (side) {
-                HIP_CHECK(hipEventRecord(sc->ev_fork, st));
-                HIP_CHECK(hipStreamWaitEvent(ss, sc->ev_fork, 0));
-            }
-            begin(SPT_K_SHADOW);
-            if (stream_s && count) hipLaunchKernelGGL(k_shadow_stream<true>, dim3(kDynBlocks), dim3(kBlock), lds, ss, sc->d, ru, b);
-            else if (stream_s) hipLaunchKernelGGL(k_shadow_stream<false>, dim3(kDynBlocks), dim3(kBlock), lds, ss, sc->d, ru, b);
-            else if (L && sc->d.flat) hipLaunchKernelGGL((k_shadow<true, false, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, ss, sc->d, ru, b);
-            else if (L) hipLaunchKernelGGL((k_shadow<true, false>), dim3(kPersistentBlocks), dim3(kBlock), lds, ss, sc->d, ru, b);
-            else if (dyn_shadow && count) hipLaunchKernelGGL(k_shadow_dyn<true>, dim3(kDynBlocks), dim3(kBlock), lds, ss, sc->d, ru, b);
-            else if (dyn_shadow) hipLaunchKernelGGL(k_shadow_dyn<false>, dim3(kDynBlocks), dim3(kBlock), lds, ss, sc->d, ru, b);
-            else if (count) hipLaunchKernelGGL((k_shadow<false, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, ss, sc->d, ru, b);
-            else hipLaunchKernelGGL((k_shadow<false, false>), dim3(kPersistentBlocks), dim3(kBlock), lds, ss, sc->d, ru, b);
-            end();
-            if (side) HIP_CHECK(hipEventRecord(sc->ev_join, ss));
-            if (b + 1 < p.max_depth) {
-                begin(SPT_K_EXTEND);
-                if (stream_e && count) hipLaunchKernelGGL(k_extend_stream<true>, dim3(kDynBlocks), dim3(kBlock), lds, st, sc->d, ru, b);
-                else if (stream_e) hipLaunchKernelGGL(k_extend_stream<false>, dim3(kDynBlocks), dim3(kBlock), lds, st, sc->d, ru, b);
-                else if (L && sc->d.flat) hipLaunchKernelGGL((k_extend<true, false, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, ru, b);
-                else if (L) hipLaunchKernelGGL((k_extend<true, false>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, ru, b);
-                else if (dyn_extend && count) hipLaunchKernelGGL(k_extend_dyn<true>, dim3(kDynBlocks), dim3(kBlock), lds, st, sc->d, ru, b);
-                else if (dyn_extend) hipLaunchKernelGGL(k_extend_dyn<false>, dim3(kDynBlocks), dim3(kBlock), lds, st, sc->d, ru, b);
-                else if (count) hipLaunchKernelGGL((k_extend<false, true>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, ru, b);
-                else hipLaunchKernelGGL((k_extend<false, false>), dim3(kPersistentBlocks), dim3(kBlock), lds, st, sc->d, ru, b);
-                end();
-            }
-            if (side) HIP_CHECK(hipStreamWaitEvent(st, sc->ev_join, 0));
-        }
+        run.begin(SPT_K_OTHER);
+        HIP_CHECK(hipMemsetAsync(rc.counts, 0, ps.counts_words * sizeof(uint32_t), run.st));
+        run.end();
+        run.begin(SPT_K_PRIMARY);
+        chunked_any |= primary_pass(run, rc, tgt, live.active_tiles, collect);
+        run.end();
+        for (uint32_t b = 0; b < p.max_depth; ++b)
+            if (bounce(run, rc, b)) break;
         if (!collect) {
-            begin(SPT_K_RESOLVE);
-            if (tgt.sq != nullptr && rc.slot_bits != nullptr) hipLaunchKernelGGL((k_resolve_bits<16u, true, float*>), dim3(pix_blocks), dim3(kBlock), 0, st, rc, tgt.sq);
-            else if (tgt.sq != nullptr) hipLaunchKernelGGL((k_resolve<true, float*>), dim3(pix_blocks), dim3(kBlock), 0, st, rc, tgt.sq);
-            else if (rc.slot_bits != nullptr && env_u32("SPT_RESOLVE_BATCH", 16u) == 32u) hipLaunchKernelGGL(k_resolve_bits<32u>, dim3(pix_blocks), dim3(kBlock), 0, st, rc);
-            else if (rc.slot_bits != nullptr) hipLaunchKernelGGL(k_resolve_bits<16u>, dim3(pix_blocks), dim3(kBlock), 0, st, rc);
-            else hipLaunchKernelGGL(k_resolve<>, dim3(pix_blocks), dim3(kBlock), 0, st, rc);
-            end();
+            run.begin(SPT_K_RESOLVE);
+            launch_resolve(run, rc, tgt.sq);
+            run.end();
         }
-        if (stats) {
-            h_counts.resize(counts_words);
-            HIP_CHECK(hipMemcpyAsync(h_counts.data(), rc.counts, counts_bytes, hipMemcpyDeviceToHost, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-            seg_closest += (uint64_t)n_pix * rc.pass_samples;
-            auto qsum = [&](uint32_t b, uint32_t q) {
-                uint64_t t = 0;
-                for (uint32_t s = 0; s < kShards; ++s) t += h_counts[((size_t)(b * Q_KINDS + q) * kShards + s) * 32];
-                if (q == Q_HIT)     // the hit queue's other classes (bounce >= 1 of the general pipeline)
-                    for (uint32_t c = 1; c < kClasses; ++c)
-                        for (uint32_t s = 0; s < kShards; ++s) t += h_counts[((size_t)(b * Q_KINDS + Q_HIT_CLASS1 + c - 1u) * kShards + s) * 32];
-                return t;
-            };
-            if (p.max_depth > 1) sc->tail_vertices = qsum(1, Q_HIT);
-            primary_hits += qsum(0, Q_HIT);
-            shadow_first += qsum(0, Q_SHADOW);
-            if (p.max_depth > 1) vertices_second += qsum(1, Q_HIT);
-            for (uint32_t b = 0; b < p.max_depth; ++b) {
-                path_vertices += qsum(b, Q_HIT);
-                seg_shadow += qsum(b, Q_SHADOW);
-                if (b + 1 < p.max_depth) seg_closest += qsum(b, Q_EXT);
-            }
-        }
+        if (run.stats) read_counters(run, rc, ps.counts_words);
     }
     run.samples_traced += (uint64_t)n_pix * tgt.count;
-    if (chunked_any) run.live_samples += live_pixels * tgt.count;
+    if (chunked_any) run.live_samples += live.live_pixels * tgt.count;
     return rc;
 }
 
 }  // namespace
 
+extern "C" {
+
 spt_status spt_render(const spt_scene* scene_c, const spt_camera* cam, const spt_render_params* params,
                       float* rgb_mean_out, spt_render_stats* stats) {
     if (!scene_c || !cam || !params || !rgb_mean_out) { g_error = "render: null argument"; return SPT_ERR_INVALID_ARG; }
     spt_scene* sc = const_cast<spt_scene*>(scene_c);
-    if (sc->fwd) {
-        const spt_status st = sc->fwd->render(sc->inner, cam, params, rgb_mean_out, stats);
-        if (st != SPT_OK) g_error = sc->fwd->last_error();
-        return st;
-    }
+    if (sc->fwd) return forwarded(sc->fwd, sc->fwd->render(sc->inner, cam, params, rgb_mean_out, stats));
     std::lock_guard<std::mutex> lock(sc->mu);
-    try {
+    return guarded("render", [&] {
         const spt_render_params& p = *params;
         check_plan(p, "render");
         const uint32_t shard_count = p.shard_count ? p.shard_count : 1u, strip_rows = p.strip_rows ? p.strip_rows : 1u;
@@ -2078,22 +2168,18 @@ spt_status spt_render(const spt_scene* scene_c, const spt_camera* cam, const spt
         run.params = &p;
         run.stats = stats;
         run_setup(run);
-        const hipStream_t st = run.st;
-        const bool count = run.count;
         hipEvent_t ev_total0 = run.get_event(), ev_total1 = run.get_event();
-        HIP_CHECK(hipEventRecord(ev_total0, st));
+        HIP_CHECK(hipEventRecord(ev_total0, run.st));
         run_spans(run);
-        auto begin = [&](int cls) { run.begin(cls); };
-        auto end = [&]() { run.end(); };
         const SampleTarget whole{0u, p.spp, nullptr, nullptr, true};   // every sample of the plan, into the scene's film from zero
         if (R <= 0) {
             const RenderCtx rc = trace_window(run, 0, own_rows, p.shard_index, shard_count, strip_rows, false, whole);
-            begin(SPT_K_RESOLVE);
+            run.begin(SPT_K_RESOLVE);
             const dim3 grid((own_pix + kBlock - 1) / kBlock);
-            if (sc->copy_pending) HIP_CHECK(hipStreamWaitEvent(st, sc->ev_copy_done, 0));   // the previous frame's copy-out reads `out`
-            if (radius == 0.5f) hipLaunchKernelGGL(k_finish, dim3((own_pix * 3 + kBlock - 1) / kBlock), dim3(kBlock), 0, st, rc, sc->out.as<float>());
-            else hipLaunchKernelGGL(k_finish_box, grid, dim3(kBlock), 0, st, rc, sc->out.as<float>(), radius, R, 0u, p.spp);
-            end();
+            if (sc->copy_pending) HIP_CHECK(hipStreamWaitEvent(run.st, sc->ev_copy_done, 0));   // the previous frame's copy-out reads `out`
+            if (radius == 0.5f) hipLaunchKernelGGL(k_finish, dim3((own_pix * 3 + kBlock - 1) / kBlock), dim3(kBlock), 0, run.st, rc, sc->out.as<float>());
+            else hipLaunchKernelGGL(k_finish_box, grid, dim3(kBlock), 0, run.st, rc, sc->out.as<float>(), radius, R, 0u, p.spp);
+            run.end();
         } else {
             // Film::filter_pixel (film.rs:71-92) reads the samples of (2R+1)^2 pixels: each run of consecutive rows of
             // this shard is rendered as bands of whole rows with R rows of halo, all samples kept, then filtered.
@@ -2102,10 +2188,8 @@ spt_status spt_render(const spt_scene* scene_c, const spt_camera* cam, const spt
             std::vector<uint32_t> own;
             for (uint32_t j = 0; j < p.height; ++j)
                 if ((j / strip_rows) % shard_count == p.shard_index) own.push_back(j);
-            uint64_t budget = 8ull << 30;   // bytes of kept radiance per band
-            if (const char* v = std::getenv("SPT_BOX_BAND_BYTES")) budget = std::max<uint64_t>(1, std::strtoull(v, nullptr, 10));
             const uint64_t per_row = (uint64_t)p.width * p.spp * 3 * sizeof(float);
-            const uint64_t fit = std::max<uint64_t>(1, budget / per_row);
+            const uint64_t fit = std::max<uint64_t>(1, run.box_band_bytes / per_row);
             const uint32_t run_max = (uint32_t)std::min<uint64_t>(p.height, fit > 2ull * (uint64_t)R ? fit - 2ull * (uint64_t)R : 1ull);
             for (size_t k = 0; k < own.size();) {
                 size_t e = k + 1;
@@ -2113,36 +2197,33 @@ spt_status spt_render(const spt_scene* scene_c, const spt_camera* cam, const spt
                 const uint32_t j0 = own[k], j1 = own[e - 1] + 1u;
                 const uint32_t b0 = j0 >= (uint32_t)R ? j0 - (uint32_t)R : 0u, b1 = (uint32_t)std::min<uint64_t>(p.height, (uint64_t)j1 + (uint64_t)R);
                 const RenderCtx rc = trace_window(run, b0, b1 - b0, 0u, 1u, 1u, true, whole);
-                begin(SPT_K_RESOLVE);
+                run.begin(SPT_K_RESOLVE);
                 BoxJob job{sc->rad.as<float>(), b0, b1 - b0, j0, j1 - j0, sc->out.as<float>() + k * (size_t)p.width * 3, R, radius};
-                if (sc->copy_pending) HIP_CHECK(hipStreamWaitEvent(st, sc->ev_copy_done, 0));
-                hipLaunchKernelGGL(k_filter_box, dim3(((j1 - j0) * p.width + kBlock - 1) / kBlock), dim3(kBlock), 0, st, rc, job);
-                end();
+                if (sc->copy_pending) HIP_CHECK(hipStreamWaitEvent(run.st, sc->ev_copy_done, 0));
+                hipLaunchKernelGGL(k_filter_box, dim3(((j1 - j0) * p.width + kBlock - 1) / kBlock), dim3(kBlock), 0, run.st, rc, job);
+                run.end();
                 k = e;
             }
         }
         HIP_CHECK(hipGetLastError());
-        hipStream_t st_out = st;
+        hipStream_t st_out = run.st;
         if (async_out) {   // the copy-out leaves the compute stream: the next render's kernels run beside it
-            HIP_CHECK(hipEventRecord(sc->ev_out_ready, st));
+            HIP_CHECK(hipEventRecord(sc->ev_out_ready, run.st));
             HIP_CHECK(hipStreamWaitEvent(sc->stream_copy, sc->ev_out_ready, 0));
             st_out = sc->stream_copy;
         }
-        {
-            hipStream_t st = st_out;
-            const size_t strip_bytes = (size_t)strip_rows * p.width * 3 * sizeof(float);
-            if (p.out_strip_stride == 0 || p.out_strip_stride == strip_bytes) {
-                HIP_CHECK(hipMemcpyAsync(rgb_mean_out, sc->out.p, (size_t)own_pix * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
-            } else {
-                // strided copy-out: the shard's strips land strip by strip in a larger (full-image) film
-                if (p.out_strip_stride < strip_bytes) fail(SPT_ERR_INVALID_ARG, "render: out_strip_stride smaller than a strip");
-                const size_t full = own_rows / strip_rows, rest_rows = own_rows - full * strip_rows;
-                if (full)
-                    HIP_CHECK(hipMemcpy2DAsync(rgb_mean_out, p.out_strip_stride, sc->out.p, strip_bytes, strip_bytes, full, hipMemcpyDeviceToHost, st));
-                if (rest_rows)
-                    HIP_CHECK(hipMemcpyAsync((char*)rgb_mean_out + full * p.out_strip_stride, (const char*)sc->out.p + full * strip_bytes,
-                                             rest_rows * (size_t)p.width * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
-            }
+        const size_t strip_bytes = (size_t)strip_rows * p.width * 3 * sizeof(float);
+        if (p.out_strip_stride == 0 || p.out_strip_stride == strip_bytes) {
+            HIP_CHECK(hipMemcpyAsync(rgb_mean_out, sc->out.p, (size_t)own_pix * 3 * sizeof(float), hipMemcpyDeviceToHost, st_out));
+        } else {
+            // strided copy-out: the shard's strips land strip by strip in a larger (full-image) film
+            if (p.out_strip_stride < strip_bytes) fail(SPT_ERR_INVALID_ARG, "render: out_strip_stride smaller than a strip");
+            const size_t full = own_rows / strip_rows, rest_rows = own_rows - full * strip_rows;
+            if (full)
+                HIP_CHECK(hipMemcpy2DAsync(rgb_mean_out, p.out_strip_stride, sc->out.p, strip_bytes, strip_bytes, full, hipMemcpyDeviceToHost, st_out));
+            if (rest_rows)
+                HIP_CHECK(hipMemcpyAsync((char*)rgb_mean_out + full * p.out_strip_stride, (const char*)sc->out.p + full * strip_bytes,
+                                         rest_rows * (size_t)p.width * 3 * sizeof(float), hipMemcpyDeviceToHost, st_out));
         }
         if (async_out) {
             HIP_CHECK(hipEventRecord(sc->ev_copy_done, sc->stream_copy));
@@ -2150,9 +2231,9 @@ spt_status spt_render(const spt_scene* scene_c, const spt_camera* cam, const spt
             return SPT_OK;
         }
         unsigned long long h_visits[12] = {};
-        if (count) HIP_CHECK(hipMemcpyAsync(h_visits, sc->visits.p, sizeof h_visits, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipEventRecord(ev_total1, st));
-        HIP_CHECK(hipStreamSynchronize(st));
+        if (run.count) HIP_CHECK(hipMemcpyAsync(h_visits, sc->visits.p, sizeof h_visits, hipMemcpyDeviceToHost, run.st));
+        HIP_CHECK(hipEventRecord(ev_total1, run.st));
+        HIP_CHECK(hipStreamSynchronize(run.st));
         sc->copy_pending = false;   // (the finish kernels of this render waited for any copy-out still in flight)
         if (stats) {
             for (int c = 0; c < 3; ++c)
@@ -2172,44 +2253,30 @@ spt_status spt_render(const spt_scene* scene_c, const spt_camera* cam, const spt
             float ms = 0.0f;
             HIP_CHECK(hipEventElapsedTime(&ms, ev_total0, ev_total1));
             stats->gpu_ms = ms;
-            const bool debug_spans = std::getenv("SPT_DEBUG_SPANS") != nullptr;   // per-launch HIP-event times (profile mode)
             for (auto& sp : run.spans) {
                 float k = 0.0f;
                 HIP_CHECK(hipEventElapsedTime(&k, sc->events[sp.e0], sc->events[sp.e0 + 1]));
                 stats->kernel_ms[sp.cls] += k;
                 stats->kernel_launches[sp.cls] += 1;
-                if (debug_spans) std::fprintf(stderr, "[spt] span class %d: %.3f ms\n", sp.cls, k);
+                if (run.debug_spans) std::fprintf(stderr, "[spt] span class %d: %.3f ms\n", sp.cls, k);
             }
         }
         return SPT_OK;
-    } catch (const AbiError& e) {
-        g_error = e.msg;
-        return e.code;
-    } catch (const std::exception& e) {
-        g_error = std::string("render: ") + e.what();
-        return SPT_ERR_OUT_OF_MEMORY;
-    }
+    });
 }
 
 spt_status spt_render_wait(const spt_scene* scene_c) {
     if (!scene_c) { g_error = "render_wait: null argument"; return SPT_ERR_INVALID_ARG; }
     spt_scene* sc = const_cast<spt_scene*>(scene_c);
-    if (sc->fwd) {
-        const spt_status st = sc->fwd->render_wait(sc->inner);
-        if (st != SPT_OK) g_error = sc->fwd->last_error();
-        return st;
-    }
+    if (sc->fwd) return forwarded(sc->fwd, sc->fwd->render_wait(sc->inner));
     std::lock_guard<std::mutex> lock(sc->mu);
-    try {
+    return guarded("render_wait", [&] {
         HIP_CHECK(hipSetDevice(sc->device));
         HIP_CHECK(hipStreamSynchronize(sc->stream));
         HIP_CHECK(hipStreamSynchronize(sc->stream_copy));
         sc->copy_pending = false;
         return SPT_OK;
-    } catch (const AbiError& e) {
-        g_error = e.msg;
-        return e.code;
-    }
+    });
 }
 
 spt_status spt_film_create(const spt_scene* scene_c, const spt_camera* cam, const spt_render_params* params, uint32_t first_sample,
@@ -2219,8 +2286,8 @@ spt_status spt_film_create(const spt_scene* scene_c, const spt_camera* cam, cons
     spt_scene* sc = const_cast<spt_scene*>(scene_c);
     if (sc->fwd) {
         spt_film* inner = nullptr;
-        const spt_status st = sc->fwd->film_create(sc->inner, cam, params, first_sample, film_flags, &inner);
-        if (st != SPT_OK) { g_error = sc->fwd->last_error(); return st; }
+        const spt_status st = forwarded(sc->fwd, sc->fwd->film_create(sc->inner, cam, params, first_sample, film_flags, &inner));
+        if (st != SPT_OK) return st;
         spt_film* f = new (std::nothrow) spt_film;
         if (!f) { sc->fwd->film_destroy(inner); g_error = "film_create: out of host memory"; return SPT_ERR_OUT_OF_MEMORY; }
         f->fwd = sc->fwd;
@@ -2229,8 +2296,7 @@ spt_status spt_film_create(const spt_scene* scene_c, const spt_camera* cam, cons
         return SPT_OK;
     }
     std::lock_guard<std::mutex> lock(sc->mu);
-    spt_film* f = nullptr;
-    try {
+    return guarded("film_create", [&] {
         const spt_render_params& p = *params;
         check_plan(p, "film_create");
         if (film_flags & ~(uint32_t)SPT_FILM_MOMENTS) fail(SPT_ERR_INVALID_ARG, "film_create: unknown film flags");
@@ -2243,7 +2309,7 @@ spt_status spt_film_create(const spt_scene* scene_c, const spt_camera* cam, cons
         const uint64_t own_pix64 = (uint64_t)shard_row_count(p) * p.width;
         if (own_pix64 > 0x7fffffffull) fail(SPT_ERR_UNSUPPORTED, "film_create: shard larger than 2^31 pixels");
         HIP_CHECK(hipSetDevice(sc->device));
-        f = new spt_film;
+        auto f = std::make_unique<spt_film>();
         f->sc = sc;
         f->cam = *cam;
         f->plan = p;
@@ -2260,30 +2326,18 @@ spt_status spt_film_create(const spt_scene* scene_c, const spt_camera* cam, cons
             HIP_CHECK(hipMemsetAsync(f->sq.p, 0, f->sq.bytes, sc->stream));
         }
         HIP_CHECK(hipStreamSynchronize(sc->stream));
-        *out = f;
+        *out = f.release();
         return SPT_OK;
-    } catch (const AbiError& e) {
-        delete f;
-        g_error = e.msg;
-        return e.code;
-    } catch (const std::exception& e) {
-        delete f;
-        g_error = std::string("film_create: ") + e.what();
-        return SPT_ERR_OUT_OF_MEMORY;
-    }
+    });
 }
 
 spt_status spt_film_render(spt_film* f, uint32_t n_samples) {
     if (!f) { g_error = "film_render: null argument"; return SPT_ERR_INVALID_ARG; }
-    if (f->fwd) {
-        const spt_status st = f->fwd->film_render(f->inner, n_samples);
-        if (st != SPT_OK) g_error = f->fwd->last_error();
-        return st;
-    }
+    if (f->fwd) return forwarded(f->fwd, f->fwd->film_render(f->inner, n_samples));
     if (n_samples == 0) return SPT_OK;
     spt_scene* sc = f->sc;
     std::lock_guard<std::mutex> lock(sc->mu);
-    try {
+    return guarded("film_render", [&] {
         const spt_render_params& p = f->plan;
         // every check comes before the first change: a refused call leaves the film as it was
         if (p.flags & (SPT_RENDER_ASYNC | SPT_RENDER_PROFILE | SPT_RENDER_COUNT_VISITS))
@@ -2314,36 +2368,22 @@ spt_status spt_film_render(spt_film* f, uint32_t n_samples) {
         }
         f->done += n_samples;
         return SPT_OK;
-    } catch (const AbiError& e) {
-        g_error = e.msg;
-        return e.code;
-    } catch (const std::exception& e) {
-        g_error = std::string("film_render: ") + e.what();
-        return SPT_ERR_OUT_OF_MEMORY;
-    }
+    });
 }
 
 spt_status spt_film_samples(const spt_film* f, uint32_t* done) {
     if (!f || !done) { g_error = "film_samples: null argument"; return SPT_ERR_INVALID_ARG; }
-    if (f->fwd) {
-        const spt_status st = f->fwd->film_samples(f->inner, done);
-        if (st != SPT_OK) g_error = f->fwd->last_error();
-        return st;
-    }
+    if (f->fwd) return forwarded(f->fwd, f->fwd->film_samples(f->inner, done));
     *done = f->done;
     return SPT_OK;
 }
 
 spt_status spt_film_read(spt_film* f, uint32_t what, float* out) {
     if (!f || !out) { g_error = "film_read: null argument"; return SPT_ERR_INVALID_ARG; }
-    if (f->fwd) {
-        const spt_status st = f->fwd->film_read(f->inner, what, out);
-        if (st != SPT_OK) g_error = f->fwd->last_error();
-        return st;
-    }
+    if (f->fwd) return forwarded(f->fwd, f->fwd->film_read(f->inner, what, out));
     spt_scene* sc = f->sc;
     std::lock_guard<std::mutex> lock(sc->mu);
-    try {
+    return guarded("film_read", [&] {
         const spt_render_params& p = f->plan;
         if (what > SPT_FILM_VAR_OF_MEAN) fail(SPT_ERR_INVALID_ARG, "film_read: unknown SPT_FILM_* value");
         const bool moments = (f->flags & SPT_FILM_MOMENTS) != 0;
@@ -2363,13 +2403,7 @@ spt_status spt_film_read(spt_film* f, uint32_t what, float* out) {
             f->out.ensure(bytes);
             if (what == SPT_FILM_MEAN && f->radius != 0.5f) {
                 // k_finish_box over the covered samples: the context it reads is the plan's sampler and shard
-                RenderCtx rc{};
-                rc.width = p.width; rc.height = p.height; rc.spp = p.spp; rc.max_depth = p.max_depth;
-                rc.sampler = p.sampler; rc.division_x = p.division_x; rc.division_y = p.division_y;
-                rc.seed = p.seed;
-                rc.shard_index = p.shard_index; rc.shard_count = p.shard_count ? p.shard_count : 1u; rc.strip_rows = p.strip_rows ? p.strip_rows : 1u;
-                rc.n_pixels = n_pix;
-                rc.rows = f->rows;
+                RenderCtx rc = plan_ctx(p, f->cam, 0, f->rows, p.shard_index, p.shard_count ? p.shard_count : 1u, p.strip_rows ? p.strip_rows : 1u);
                 rc.film = f->sum.as<float>();
                 hipLaunchKernelGGL(k_finish_box, dim3((n_pix + kBlock - 1) / kBlock), dim3(kBlock), 0, st, rc, f->out.as<float>(), f->radius, f->R, f->first, f->done);
             } else if (f->adaptive) {   // radius 0.5 (spt_film_adapt refuses others): per-pixel sample counts
@@ -2386,25 +2420,15 @@ spt_status spt_film_read(spt_film* f, uint32_t what, float* out) {
         HIP_CHECK(hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
         return SPT_OK;
-    } catch (const AbiError& e) {
-        g_error = e.msg;
-        return e.code;
-    } catch (const std::exception& e) {
-        g_error = std::string("film_read: ") + e.what();
-        return SPT_ERR_OUT_OF_MEMORY;
-    }
+    });
 }
 
 spt_status spt_film_adapt(spt_film* f, float rel_error, float abs_floor, uint32_t min_samples, uint32_t* active_out) {
     if (!f) { g_error = "film_adapt: null argument"; return SPT_ERR_INVALID_ARG; }
-    if (f->fwd) {
-        const spt_status st = f->fwd->film_adapt(f->inner, rel_error, abs_floor, min_samples, active_out);
-        if (st != SPT_OK) g_error = f->fwd->last_error();
-        return st;
-    }
+    if (f->fwd) return forwarded(f->fwd, f->fwd->film_adapt(f->inner, rel_error, abs_floor, min_samples, active_out));
     spt_scene* sc = f->sc;
     std::lock_guard<std::mutex> lock(sc->mu);
-    try {
+    return guarded("film_adapt", [&] {
         const spt_render_params& p = f->plan;
         // every check comes before the first change: a refused call leaves the film as it was
         if (!(f->flags & SPT_FILM_MOMENTS)) fail(SPT_ERR_INVALID_ARG, "film_adapt: the film was created without SPT_FILM_MOMENTS (the criterion needs the sums of squares)");
@@ -2449,25 +2473,15 @@ spt_status spt_film_adapt(spt_film* f, float rel_error, float abs_floor, uint32_
         f->active_tiles = totals[1];
         if (active_out) *active_out = f->active;
         return SPT_OK;
-    } catch (const AbiError& e) {
-        g_error = e.msg;
-        return e.code;
-    } catch (const std::exception& e) {
-        g_error = std::string("film_adapt: ") + e.what();
-        return SPT_ERR_OUT_OF_MEMORY;
-    }
+    });
 }
 
 spt_status spt_film_read_counts(spt_film* f, uint32_t* out) {
     if (!f || !out) { g_error = "film_read_counts: null argument"; return SPT_ERR_INVALID_ARG; }
-    if (f->fwd) {
-        const spt_status st = f->fwd->film_read_counts(f->inner, out);
-        if (st != SPT_OK) g_error = f->fwd->last_error();
-        return st;
-    }
+    if (f->fwd) return forwarded(f->fwd, f->fwd->film_read_counts(f->inner, out));
     spt_scene* sc = f->sc;
     std::lock_guard<std::mutex> lock(sc->mu);
-    try {
+    return guarded("film_read_counts", [&] {
         const uint32_t n_pix = f->rows * f->plan.width;
         if (!f->adaptive) {
             std::fill(out, out + n_pix, f->done);
@@ -2481,13 +2495,7 @@ spt_status spt_film_read_counts(spt_film* f, uint32_t* out) {
         for (uint32_t i = 0; i < n_pix; ++i)
             if (mask[i]) out[i] = f->done;
         return SPT_OK;
-    } catch (const AbiError& e) {
-        g_error = e.msg;
-        return e.code;
-    } catch (const std::exception& e) {
-        g_error = std::string("film_read_counts: ") + e.what();
-        return SPT_ERR_OUT_OF_MEMORY;
-    }
+    });
 }
 
 void spt_film_destroy(spt_film* f) {
@@ -2507,39 +2515,28 @@ static spt_status trace_common(const spt_scene* scene_c, uint32_t n, const spt_r
     if (!scene_c || (n && (!rays || !out))) { g_error = "trace: null argument"; return SPT_ERR_INVALID_ARG; }
     if (n == 0) return SPT_OK;
     spt_scene* sc = const_cast<spt_scene*>(scene_c);
-    if (sc->fwd) {
-        const spt_status st = closest ? sc->fwd->trace_closest(sc->inner, n, rays, static_cast<spt_hit*>(out))
-                                      : sc->fwd->trace_any(sc->inner, n, rays, static_cast<uint8_t*>(out));
-        if (st != SPT_OK) g_error = sc->fwd->last_error();
-        return st;
-    }
+    if (sc->fwd)
+        return forwarded(sc->fwd, closest ? sc->fwd->trace_closest(sc->inner, n, rays, static_cast<spt_hit*>(out))
+                                          : sc->fwd->trace_any(sc->inner, n, rays, static_cast<uint8_t*>(out)));
     std::lock_guard<std::mutex> lock(sc->mu);
-    try {
+    return guarded("trace", [&] {
         HIP_CHECK(hipSetDevice(sc->device));
         sc->trace_in.ensure((size_t)n * sizeof(spt_ray));
         sc->trace_out.ensure((size_t)n * out_elem);
         hipStream_t st = sc->stream;
         HIP_CHECK(hipMemcpyAsync(sc->trace_in.p, rays, (size_t)n * sizeof(spt_ray), hipMemcpyHostToDevice, st));
-        const size_t lds = sc->lds_bytes;
-        dim3 grid((n + kBlock - 1) / kBlock);
-        if (sc->swalk && !sc->lds_geo) {
-            if (closest) hipLaunchKernelGGL(k_trace_closest_stream, grid, dim3(kBlock), lds, st, sc->d, n, sc->trace_in.as<spt_ray>(), sc->trace_out.as<spt_hit>());
-            else hipLaunchKernelGGL(k_trace_any_stream, grid, dim3(kBlock), lds, st, sc->d, n, sc->trace_in.as<spt_ray>(), sc->trace_out.as<uint8_t>());
-        } else if (closest) {
-            if (sc->lds_geo) hipLaunchKernelGGL(k_trace_closest<true>, grid, dim3(kBlock), lds, st, sc->d, n, sc->trace_in.as<spt_ray>(), sc->trace_out.as<spt_hit>());
-            else hipLaunchKernelGGL(k_trace_closest<false>, grid, dim3(kBlock), lds, st, sc->d, n, sc->trace_in.as<spt_ray>(), sc->trace_out.as<spt_hit>());
-        } else {
-            if (sc->lds_geo) hipLaunchKernelGGL(k_trace_any<true>, grid, dim3(kBlock), lds, st, sc->d, n, sc->trace_in.as<spt_ray>(), sc->trace_out.as<uint8_t>());
-            else hipLaunchKernelGGL(k_trace_any<false>, grid, dim3(kBlock), lds, st, sc->d, n, sc->trace_in.as<spt_ray>(), sc->trace_out.as<uint8_t>());
-        }
+        // the streaming walker, or the walker over the LDS-resident / memory geometry
+        const bool stream = sc->swalk && !sc->lds_geo;
+        auto launch = [&](auto kernel, auto* results) {
+            hipLaunchKernelGGL(kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), sc->lds_bytes, st, sc->d, n, sc->trace_in.as<spt_ray>(), results);
+        };
+        if (closest) launch(stream ? k_trace_closest_stream : sc->lds_geo ? k_trace_closest<true> : k_trace_closest<false>, sc->trace_out.as<spt_hit>());
+        else launch(stream ? k_trace_any_stream : sc->lds_geo ? k_trace_any<true> : k_trace_any<false>, sc->trace_out.as<uint8_t>());
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipMemcpyAsync(out, sc->trace_out.p, (size_t)n * out_elem, hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
         return SPT_OK;
-    } catch (const AbiError& e) {
-        g_error = e.msg;
-        return e.code;
-    }
+    });
 }
 
 spt_status spt_alloc_pinned(uint64_t bytes, void** out) {
@@ -2571,25 +2568,20 @@ void spt_free_pinned(void* p) {
 spt_status spt_debug_detmath(int32_t device, uint32_t fn, uint32_t n, const float* a, const float* b, float* out) {
     if (n && (!a || !b || !out)) { g_error = "debug_detmath: null argument"; return SPT_ERR_INVALID_ARG; }
     if (n == 0) return SPT_OK;
-    DeviceBuffer da, db, dout;
-    try {
+    return guarded("debug_detmath", [&] {
         int nd = usable_device_count();
         if (nd <= 0) fail(SPT_ERR_NO_DEVICE, "no HIP device is visible: libspt_hip has no CPU fallback");
         if (device < 0 || device >= nd) fail(SPT_ERR_NO_DEVICE, "device index out of range");
         HIP_CHECK(hipSetDevice(device));
+        DeviceBuffer da, db, dout;
         da.upload(a, n);
         db.upload(b, n);
         dout.alloc((size_t)n * sizeof(float));
         hipLaunchKernelGGL(k_detmath, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, 0, fn, n, da.as<float>(), db.as<float>(), dout.as<float>());
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipMemcpy(out, dout.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-        da.release(); db.release(); dout.release();
         return SPT_OK;
-    } catch (const AbiError& e) {
-        da.release(); db.release(); dout.release();
-        g_error = e.msg;
-        return e.code;
-    }
+    });
 }
 
 spt_status spt_debug_bxdf(const spt_scene* scene_c, int32_t device, const spt_material* mt, uint32_t op, uint32_t n, const float* wo,
@@ -2599,15 +2591,10 @@ spt_status spt_debug_bxdf(const spt_scene* scene_c, int32_t device, const spt_ma
         return SPT_ERR_INVALID_ARG;
     }
     spt_scene* sc = const_cast<spt_scene*>(scene_c);
-    if (sc && sc->fwd) {   // a patch scene lives in the other code object
-        const spt_status st = sc->fwd->debug_bxdf(sc->inner, device, mt, op, n, wo, wi_in, rng_state, wi_out, f_out, pdf_out, dir_out);
-        if (st != SPT_OK) g_error = sc->fwd->last_error();
-        return st;
-    }
+    if (sc && sc->fwd)   // a patch scene lives in the other code object
+        return forwarded(sc->fwd, sc->fwd->debug_bxdf(sc->inner, device, mt, op, n, wo, wi_in, rng_state, wi_out, f_out, pdf_out, dir_out));
     if (n == 0) return SPT_OK;
-    DeviceBuffer dwo, dwi, drng, dwio, df, dpdf, ddir;
-    auto release = [&]() { dwo.release(); dwi.release(); drng.release(); dwio.release(); df.release(); dpdf.release(); ddir.release(); };
-    try {
+    return guarded("debug_bxdf", [&] {
         if (mt->bxdf > SPT_BXDF_PNDF_PLASTIC) fail(SPT_ERR_INVALID_ARG, "debug_bxdf: unknown bxdf");
         if (mt->recipe != 0u) fail(SPT_ERR_INVALID_ARG, "debug_bxdf: the record must be a constant Bxdf (recipe 0)");
         const bool pndf = mt->bxdf == SPT_BXDF_PNDF_CONDUCTOR || mt->bxdf == SPT_BXDF_PNDF_PLASTIC;
@@ -2628,16 +2615,16 @@ spt_status spt_debug_bxdf(const spt_scene* scene_c, int32_t device, const spt_ma
         m.c2 = f3{mt->c2[0], mt->c2[1], mt->c2[2]};
         m.ax = mt->ax; m.ay = mt->ay; m.ior = mt->ior;
         m.fresnel = mt->fresnel; m.substrate = mt->substrate;
+        DeviceBuffer dwo, dwi, drng, dwio, df, dpdf, ddir;
         dwo.upload(wo, (size_t)n * 3);
         if (op == 0u) { drng.upload(rng_state, n); dwio.alloc((size_t)n * 3 * sizeof(float)); ddir.alloc((size_t)n * sizeof(int32_t)); }
         else dwi.upload(wi_in, (size_t)n * 3);
         df.alloc((size_t)n * 3 * sizeof(float));
         dpdf.alloc((size_t)n * sizeof(float));
         const dim3 grid((n + kBlock - 1) / kBlock);
-        if (pndf) hipLaunchKernelGGL(k_debug_bxdf<true>, grid, dim3(kBlock), 0, 0, sc->d, m, op, n, dwo.as<float>(), dwi.as<float>(), drng.as<uint64_t>(),
-                                     dwio.as<float>(), df.as<float>(), dpdf.as<float>(), ddir.as<int32_t>());
-        else hipLaunchKernelGGL(k_debug_bxdf<false>, grid, dim3(kBlock), 0, 0, DScene{}, m, op, n, dwo.as<float>(), dwi.as<float>(), drng.as<uint64_t>(),
-                                dwio.as<float>(), df.as<float>(), dpdf.as<float>(), ddir.as<int32_t>());
+        const auto kernel = pndf ? k_debug_bxdf<true> : k_debug_bxdf<false>;
+        hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, 0, pndf ? sc->d : DScene{}, m, op, n, dwo.as<float>(), dwi.as<float>(), drng.as<uint64_t>(),
+                           dwio.as<float>(), df.as<float>(), dpdf.as<float>(), ddir.as<int32_t>());
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipMemcpy(f_out, df.p, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost));
         HIP_CHECK(hipMemcpy(pdf_out, dpdf.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
@@ -2645,13 +2632,8 @@ spt_status spt_debug_bxdf(const spt_scene* scene_c, int32_t device, const spt_ma
             HIP_CHECK(hipMemcpy(wi_out, dwio.p, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost));
             HIP_CHECK(hipMemcpy(dir_out, ddir.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
         }
-        release();
         return SPT_OK;
-    } catch (const AbiError& e) {
-        release();
-        g_error = e.msg;
-        return e.code;
-    }
+    });
 }
 
 spt_status spt_trace_closest(const spt_scene* scene, uint32_t n, const spt_ray* rays, spt_hit* hits) {

@@ -99,7 +99,11 @@ spt_status spt_host_multi_create(const spt_scene_desc* desc, const spt_device_ap
                                  spt_host_multi** out);
 /* Renders the full image of `params` (its shard fields are overwritten: shard k of n_devices, `strip_rows` rows per strip, 0 = a
  * default that keeps the shares even) into film[height][width][3].  stats: NULL or n_devices entries (one per device; each
- * is written with params->stats_size bytes as spt_render does).  Synchronous: the film is complete on return. */
+ * is written with params->stats_size bytes as spt_render does).  Synchronous: the film is complete on return.
+ * Lifetime of `film`: with api->pin_host set, the film stays page-locked AFTER the call returns, so that a caller who renders
+ * into one buffer frame after frame pays for one registration.  The registration is dropped by the next spt_host_multi_render
+ * with another pointer or size (before it pins the new film) and by spt_host_multi_destroy.  Until one of the two, the film
+ * must stay mapped at that address: do not free or unmap it earlier. */
 spt_status spt_host_multi_render(spt_host_multi* m, const spt_camera* cam, const spt_render_params* params, uint32_t strip_rows,
                                  float* film, spt_render_stats* stats);
 uint32_t spt_host_multi_device_count(const spt_host_multi* m);

@@ -2159,11 +2159,15 @@ bool row_in_shard(const spt_render_params& p, uint32_t j) {
 extern "C" {
 
 // PathTracer::render (pt.rs:237-296): threads over contiguous row bands (util.rs:6-19)
-int oracle_render(const spt_scene_desc* desc, const spt_camera* cam, const spt_render_params* params, uint32_t flags,
-                  int32_t n_threads, float* rgb_mean_out, oracle_stats* stats) {
-    if (!desc || !cam || !params || !rgb_mean_out) return 1;
+// samples_out: instead of the film, the colour of every single sample s in [first_sample, first_sample + n_samples) of the
+// plan `params` (spp stays the plan's total), laid out (n_samples, rows, width, 3): what a progressive film sums
+static int render_impl(const spt_scene_desc* desc, const spt_camera* cam, const spt_render_params* params, uint32_t flags,
+                       int32_t n_threads, float* rgb_mean_out, oracle_stats* stats, uint32_t first_sample, uint32_t n_samples,
+                       float* samples_out) {
+    if (!desc || !cam || !params || (!rgb_mean_out && !samples_out)) return 1;
     const spt_render_params p = *params;
     if (p.width == 0 || p.height == 0 || p.spp == 0) return 1;
+    if (samples_out && ((uint64_t)first_sample + n_samples > p.spp)) return 1;
     if (p.sampler == SPT_SAMPLER_JITTERED && (p.division_x == 0 || p.division_x * p.division_y != p.spp)) return 1;
     std::vector<uint32_t> rows;
     for (uint32_t j = 0; j < p.height; ++j)
@@ -2203,7 +2207,19 @@ int oracle_render(const spt_scene_desc* desc, const spt_camera* cam, const spt_r
     // BoxFilter (boxf.rs:5-34); radius 0.5 without the flag
     const float radius = (p.flags & SPT_RENDER_BOX_RADIUS) ? p.filter_radius : 0.5f;
     uint64_t traced_rows = nrows;
-    if (radius == 0.5f) {
+    if (samples_out) {
+        run_threads([&](int t) {
+            Ctx cx{desc, f, Math{f.libm}, &counters[(size_t)t]};
+            for (uint32_t rr = (uint32_t)t; rr < nrows; rr += (uint32_t)n_threads)
+                for (uint32_t i = 0; i < p.width; ++i)
+                    for (uint32_t k = 0; k < n_samples; ++k) {
+                        float ox, oy;
+                        Color c = sample(cx, i, rows[rr], first_sample + k, &ox, &oy);
+                        float* o = samples_out + (((size_t)k * nrows + rr) * p.width + i) * 3;
+                        o[0] = c.r; o[1] = c.g; o[2] = c.b;
+                    }
+        });
+    } else if (radius == 0.5f) {
         // D3: radius_int = 0 and every weight is 1 (offsets lie in [0, 1)), so filter_pixel is the in-order sum of the
         // pixel's own samples over spp and the Vec of samples need not be kept
         run_threads([&](int t) {
@@ -2290,6 +2306,18 @@ int oracle_render(const spt_scene_desc* desc, const spt_camera* cam, const spt_r
         }
     }
     return 0;
+}
+
+int oracle_render(const spt_scene_desc* desc, const spt_camera* cam, const spt_render_params* params, uint32_t flags,
+                  int32_t n_threads, float* rgb_mean_out, oracle_stats* stats) {
+    if (!rgb_mean_out) return 1;
+    return render_impl(desc, cam, params, flags, n_threads, rgb_mean_out, stats, 0, 0, nullptr);
+}
+
+int oracle_render_samples(const spt_scene_desc* desc, const spt_camera* cam, const spt_render_params* params, uint32_t flags,
+                          int32_t n_threads, uint32_t first_sample, uint32_t n_samples, float* samples_out) {
+    if (!samples_out) return 1;
+    return render_impl(desc, cam, params, flags, n_threads, nullptr, nullptr, first_sample, n_samples, samples_out);
 }
 
 int oracle_trace_closest(const spt_scene_desc* desc, uint32_t flags, uint32_t n, const spt_ray* rays, spt_hit* hits) {

@@ -34,6 +34,10 @@ typedef struct oracle_stats {
 /* n_threads <= 0: 2 x hardware_concurrency, the reference's layout (src/renderer/pt.rs:243). */
 int oracle_render(const spt_scene_desc* desc, const spt_camera* cam, const spt_render_params* params, uint32_t flags,
                   int32_t n_threads, float* rgb_mean_out, oracle_stats* stats);
+/* The colour of every single sample s in [first_sample, first_sample + n_samples) of the plan `params` (spp stays the plan's
+ * total: jittered grid, R2 index, auxiliary-ray spread), laid out (n_samples, rows, width, 3): what a progressive film sums. */
+int oracle_render_samples(const spt_scene_desc* desc, const spt_camera* cam, const spt_render_params* params, uint32_t flags,
+                          int32_t n_threads, uint32_t first_sample, uint32_t n_samples, float* samples_out);
 int oracle_trace_closest(const spt_scene_desc* desc, uint32_t flags, uint32_t n, const spt_ray* rays, spt_hit* hits);
 int oracle_trace_any(const spt_scene_desc* desc, uint32_t flags, uint32_t n, const spt_ray* rays, uint8_t* occluded);
 

@@ -667,6 +667,7 @@ class MultiDevice:
         self.devices = [int(d) for d in devices]
         self._api = api if api is not None else hip_device_api()
         self._h = C.c_void_p()
+        self._film = None   # the film the library holds page-locked (spt_host.h): kept alive until it pins another or is destroyed
         desc = scene.desc
         devs = (C.c_int32 * len(self.devices))(*self.devices)
         _check_host(host_lib().spt_host_multi_create(C.byref(desc), C.byref(self._api), len(self.devices), devs, C.byref(self._h)))
@@ -680,7 +681,14 @@ class MultiDevice:
             film = np.zeros((config.height, config.width, 3), dtype=np.float32)
         assert film.shape == (config.height, config.width, 3) and film.dtype == np.float32 and film.flags["C_CONTIGUOUS"]
         stats = (RenderStats * len(self.devices))()
-        _check_host(host_lib().spt_host_multi_render(self._h, C.byref(cam), C.byref(p), strip_rows, film.ctypes.data, C.byref(stats)))
+        # the library unpins the film of the previous call and pins this one inside the call (spt_host.h), so the previous
+        # array may go once the call has succeeded; after a refusal either of the two may be the registered one: both stay
+        previous, self._film = self._film, film
+        try:
+            _check_host(host_lib().spt_host_multi_render(self._h, C.byref(cam), C.byref(p), strip_rows, film.ctypes.data, C.byref(stats)))
+        except SptError:
+            self._film = (previous, film)
+            raise
         self.last_stats = list(stats)
         if config.output_filename:
             write_image(config.output_filename, film)
@@ -690,6 +698,7 @@ class MultiDevice:
         if self._h:
             host_lib().spt_host_multi_destroy(self._h)
             self._h = C.c_void_p()
+        self._film = None   # after the destroy: it unpins the film
 
     def __del__(self):
         try:

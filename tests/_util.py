@@ -66,6 +66,8 @@ def oracle_lib():
         lib = C.CDLL(os.path.join(ROOT, "oracle", "liboracle.so"))
         lib.oracle_render.argtypes = [C.POINTER(spt.SceneDesc), C.POINTER(spt.Camera), C.POINTER(spt.RenderParams),
                                       C.c_uint32, C.c_int32, C.c_void_p, C.POINTER(OracleStats)]
+        lib.oracle_render_samples.argtypes = [C.POINTER(spt.SceneDesc), C.POINTER(spt.Camera), C.POINTER(spt.RenderParams),
+                                              C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p]
         lib.oracle_trace_closest.argtypes = [C.POINTER(spt.SceneDesc), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         lib.oracle_trace_any.argtypes = [C.POINTER(spt.SceneDesc), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         lib.oracle_bxdf_sample.argtypes = [C.POINTER(spt.Material), C.c_float * 3, C.c_uint64, C.c_uint32,
@@ -132,6 +134,67 @@ def oracle_render(scene, renderer, width, height, camera=None, flags=0, threads=
     rc = lib.oracle_render(C.byref(desc), C.byref(cam), C.byref(p), flags, threads, out.ctypes.data, C.byref(st))
     assert rc == 0
     return out, st
+
+
+def oracle_render_samples(scene, renderer, width, height, first_sample, n_samples, camera=None, flags=0, threads=0, shard_index=0,
+                          shard_count=1, strip_rows=16):
+    """The single samples [first_sample, first_sample + n_samples) of the plan `renderer` (spp stays the plan's total), one
+    (rows, width, 3) f32 colour array per sample: what a progressive film of that plan adds up."""
+    spt = load_pkg()
+    p = renderer.params(width, height, shard_index, shard_count, strip_rows)
+    rows = len(spt.shard_rows(height, shard_index, shard_count, strip_rows))
+    out = np.zeros((n_samples, rows, width, 3), dtype=np.float32)
+    cam = scene.get_camera(camera)
+    desc = scene.desc
+    rc = oracle_lib().oracle_render_samples(C.byref(desc), C.byref(cam), C.byref(p), flags, threads, first_sample, n_samples, out.ctypes.data)
+    assert rc == 0
+    return out
+
+
+# ---- what a progressive film holds, in float32 numpy one operation at a time (numpy does not contract) -----------------
+
+def same_words(a, b):
+    """Equal shape, NaN at the same positions, every other word equal."""
+    if a.shape != b.shape:
+        return False
+    if a.dtype != np.float32:
+        return bool(np.array_equal(a, b))
+    nan = np.isnan(b)
+    return bool(np.array_equal(nan, np.isnan(a)) and np.array_equal(a.view(np.uint32)[~nan], b.view(np.uint32)[~nan]))
+
+
+def film_add_sample(s, q, x, active=None):
+    """The film's sums after one more sample x (in sample order): s + x and q + x * x, for the `active` pixels only."""
+    s2, q2 = s + x, q + x * x
+    if active is not None:
+        s2, q2 = np.where(active[..., None], s2, s), np.where(active[..., None], q2, q)
+    return s2, q2
+
+
+def film_mean_and_variance(s, q, n):
+    """spt_film_read's MEAN and VAR_OF_MEAN from the sums of n samples (n: a number, or one count per pixel)."""
+    f32 = np.float32
+    n = np.asarray(n, dtype=np.float32)
+    if n.ndim:
+        n = n[..., None]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        inv = f32(1) / n
+        m = (s * inv).astype(np.float32)
+        v = (q * inv - m * m) * (f32(1) / (n - f32(1)))
+    v = np.where(v < 0, f32(0), v)
+    var = np.where(np.broadcast_to(n, s.shape) == 1, f32(np.inf), v).astype(np.float32)
+    return m, var
+
+
+def film_criterion(s, q, n, rel, floor):
+    """spt_abi.h's retirement test of spt_film_adapt in float32, one operation at a time."""
+    f32 = np.float32
+    r, r1 = f32(1) / f32(n), f32(1) / f32(n - 1)
+    m = s * r
+    v = (q * r - m * m) * r1
+    v = np.where(v < 0, f32(0), v)
+    tol = f32(rel) * np.abs(m) + f32(floor)
+    return np.all(v <= tol * tol, axis=-1)
 
 
 def oracle_bxdf_sample_n(mt, wo, rng_state, scene=None, flags=0):

@@ -15,7 +15,6 @@ import _util
 
 pytestmark = pytest.mark.gpu
 
-f32 = np.float32
 ENV_SWITCHES = ("SPT_NO_LDS_GEO", "SPT_STREAM_MASK", "SPT_PRIMARY_CHUNKS", "SPT_NO_EYE_BLOB")
 
 
@@ -38,14 +37,7 @@ def _same(a, b):
     return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
-def _criterion(s, q, n, rel, floor):
-    """spt_abi.h's retirement test in float32, one operation at a time (numpy does not contract)."""
-    r, r1 = f32(1) / f32(n), f32(1) / f32(n - 1)
-    m = s * r
-    v = (q * r - m * m) * r1
-    v = np.where(v < 0, f32(0), v)
-    tol = f32(rel) * np.abs(m) + f32(floor)
-    return np.all(v <= tol * tol, axis=-1)
+_criterion = _util.film_criterion   # spt_abi.h's retirement test in float32 (shared with tools/fuzz_sessions.py)
 
 
 def _auto_rel(s, q, n, active):

@@ -99,7 +99,6 @@ def test_moments_match_sequential_numpy(spt, scene_name, camera):
         with r.progressive(sc, cfg, first_sample=k) as one:
             one.render(1)
             xs.append(one.sum())
-    f32 = np.float32
     s = np.zeros_like(xs[0])
     q = np.zeros_like(xs[0])
     n = 0
@@ -107,20 +106,13 @@ def test_moments_match_sequential_numpy(spt, scene_name, camera):
         for inc in (1, 2, 5, 8):
             film.render(inc)
             for x in xs[n:n + inc]:
-                s = s + x
-                q = q + x * x
+                s, q = _util.film_add_sample(s, q, x)       # s + x, q + x * x (shared with tools/fuzz_sessions.py)
             n += inc
             assert film.samples == n
             assert _same(film.sum(), s), n
             assert _same(film.sum_sq(), q), n
-            inv = f32(1) / f32(n)
-            m = s * inv
+            m, var = _util.film_mean_and_variance(s, q, n)   # s / n; (q / n - m * m) / (n - 1) clamped at 0, inf at n = 1
             assert _same(film.mean(), m), n
-            if n == 1:
-                var = np.full_like(s, np.inf)
-            else:
-                v = (q * inv - m * m) * (f32(1) / f32(n - 1))
-                var = np.where(v < 0, f32(0), v).astype(np.float32)
             assert _same(film.variance_of_mean(), var), n
         assert _same(film.mean(), r.render_shard(sc, cfg))
     sc.close()

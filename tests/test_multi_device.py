@@ -6,9 +6,11 @@ the shard parameters every worker receives, the strided in-place assembly of the
 paths are the library's own code.  GPU half: the real libspt_hip.so functions, two workers on the box's one device, film
 equal to the single-device film bit for bit; and the `spt --devices 0,0` command line."""
 import ctypes as C
+import gc
 import os
 import subprocess
 import threading
+import weakref
 
 import numpy as np
 import pytest
@@ -21,12 +23,14 @@ CREATE = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p))
 DESTROY = C.CFUNCTYPE(None, C.c_void_p)
 RENDER = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.POINTER(spt.Camera), C.POINTER(spt.RenderParams), C.c_void_p, C.c_void_p)
 LAST_ERROR = C.CFUNCTYPE(C.c_void_p)
+PIN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_uint64)
+UNPIN = C.CFUNCTYPE(None, C.c_void_p)
 
 
 class StubDevices:
     """Stand-in for libspt_hip.so: `render` computes the shard with the CPU oracle and writes it where spt_render would."""
 
-    def __init__(self, scene, fail_render_shard=None, fail_create_device=None):
+    def __init__(self, scene, fail_render_shard=None, fail_create_device=None, record_pins=False):
         self.scene = scene
         self.calls = []
         self.created, self.destroyed = [], []
@@ -36,7 +40,19 @@ class StubDevices:
         self._create, self._destroy = CREATE(self.create), DESTROY(self.destroy)
         self._render, self._last = RENDER(self.render), LAST_ERROR(lambda: C.addressof(self._err))
         addr = lambda f: C.cast(f, C.c_void_p).value
-        self.api = spt.DeviceApi(addr(self._create), addr(self._destroy), addr(self._render), addr(self._last), None, None)
+        # record_pins: pin_host / unpin_host stand-ins that write ("pin", address, bytes) / ("unpin", address) into `events`,
+        # where the tests also note when a film array is finalized; otherwise the two optional entries stay NULL
+        self.events = []
+        self._pin, self._unpin = PIN(self.pin_host), UNPIN(self.unpin_host)
+        self.api = spt.DeviceApi(addr(self._create), addr(self._destroy), addr(self._render), addr(self._last),
+                                 addr(self._pin) if record_pins else None, addr(self._unpin) if record_pins else None)
+
+    def pin_host(self, p, nbytes):
+        self.events.append(("pin", p, nbytes))
+        return 0
+
+    def unpin_host(self, p):
+        self.events.append(("unpin", p))
 
     def create(self, desc, device, out):
         if device == self.fail_create_device:
@@ -152,6 +168,109 @@ def test_errors_come_back_with_the_device_that_failed():
     rc = spt.host_lib().spt_host_multi_render(md._h, C.byref(cam), C.byref(p), 0, film.ctypes.data, None)
     assert rc == 1 and b"ASYNC" in spt.host_lib().spt_host_last_error()
     md.close()
+
+
+def _watch(stub, film):
+    """Notes in the stub's event list when `film`'s memory goes (the array object owns it: np.zeros / np.full)."""
+    assert film.base is None and film.flags["OWNDATA"]
+    weakref.finalize(film, stub.events.append, ("freed", film.ctypes.data, film.nbytes))
+    return film.ctypes.data
+
+
+def _check_pin_events(events):
+    """(i) no film is freed while it is the registered one, (ii) unpin_host(p) only while the film at p is alive,
+    (iii) every pin has exactly one matching unpin, and at most one film is registered at a time."""
+    pinned, alive = None, set()
+    for k, ev in enumerate(events):
+        if ev[0] == "born":
+            alive.add(ev[1])
+        elif ev[0] == "freed":
+            assert pinned != ev[1], "event %d: the film at %#x was freed while page-locked: %s" % (k, ev[1], events)
+            alive.discard(ev[1])
+        elif ev[0] == "pin":
+            assert pinned is None, "event %d: a second registration while %#x is still pinned" % (k, pinned)
+            assert ev[1] in alive, "event %d: pin_host on memory that is not a live film" % k
+            pinned = ev[1]
+        else:
+            assert pinned == ev[1], "event %d: unpin_host(%#x) but the registered film is %r" % (k, ev[1], pinned)
+            assert ev[1] in alive, "event %d: unpin_host(%#x) on freed memory: %s" % (k, ev[1], events)
+            pinned = None
+    assert pinned is None, "a film is still page-locked after close()"
+    assert sum(e[0] == "pin" for e in events) == sum(e[0] == "unpin" for e in events)
+
+
+def test_pinned_film_is_never_freed_memory():
+    """MultiDevice.render(film=None) hands out a fresh array per call and the library keeps it page-locked after the call
+    (spt_host.h): the binding must keep that array alive until the library has dropped the registration."""
+    sc = _scene()
+    stub = StubDevices(sc, record_pins=True)
+    r = spt.PathTracer(max_depth=2, sampler=spt.SAMPLER_RANDOM, spp=1, seed=1)
+    cfg = spt.OutputConfig(40, 44, used_camera_name="main")
+    want, _ = _util.oracle_render(sc, r, 40, 44, camera="main")
+    md = spt.MultiDevice(sc, [0, 1], api=stub.api)
+    for _ in range(3):
+        n_before = len(stub.events)
+        film = md.render(r, cfg)
+        stub.events.insert(n_before, ("born", film.ctypes.data))     # allocated inside render(), before the pin
+        _watch(stub, film)
+        assert np.array_equal(film.view(np.uint32), want.view(np.uint32))
+        del film                                                    # the caller drops the array it was handed
+        gc.collect()
+    md.close()
+    gc.collect()
+    _check_pin_events(stub.events)
+    assert sum(e[0] == "pin" for e in stub.events) == 3 and sum(e[0] == "freed" for e in stub.events) == 3
+
+
+def test_caller_owned_film_is_pinned_once():
+    """The command line's pattern: the same film frame after frame costs one registration, dropped by close()."""
+    sc = _scene()
+    stub = StubDevices(sc, record_pins=True)
+    r = spt.PathTracer(max_depth=2, sampler=spt.SAMPLER_RANDOM, spp=1, seed=1)
+    cfg = spt.OutputConfig(40, 44, used_camera_name="main")
+    md = spt.MultiDevice(sc, [0, 1], api=stub.api)
+    film = np.zeros((44, 40, 3), dtype=np.float32)
+    stub.events.append(("born", film.ctypes.data))
+    addr = _watch(stub, film)
+    for _ in range(3):
+        assert md.render(r, cfg, film=film) is film
+        gc.collect()
+    assert stub.events == [("born", addr), ("pin", addr, film.nbytes)]
+    md.close()
+    assert stub.events[2:] == [("unpin", addr)]
+    del film
+    gc.collect()
+    _check_pin_events(stub.events)
+
+
+def test_alternating_films_of_two_shapes_are_repinned_in_order():
+    sc = _scene()
+    stub = StubDevices(sc, record_pins=True)
+    r = spt.PathTracer(max_depth=2, sampler=spt.SAMPLER_RANDOM, spp=1, seed=1)
+    md = spt.MultiDevice(sc, [0, 1, 2], api=stub.api)
+    films = {(40, 44): np.zeros((44, 40, 3), dtype=np.float32), (24, 20): np.zeros((20, 24, 3), dtype=np.float32)}
+    for f in films.values():
+        stub.events.append(("born", f.ctypes.data))
+        _watch(stub, f)
+    for k in range(4):
+        w, h = list(films)[k % 2]
+        got = md.render(r, spt.OutputConfig(w, h, used_camera_name="main"), film=films[(w, h)])
+        want, _ = _util.oracle_render(sc, r, w, h, camera="main")
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    # a fresh array in between (film=None), dropped at once, then a caller-owned one again
+    n_before = len(stub.events)
+    tmp = md.render(r, spt.OutputConfig(24, 20, used_camera_name="main"))
+    stub.events.insert(n_before, ("born", tmp.ctypes.data))
+    _watch(stub, tmp)
+    del tmp, got
+    gc.collect()
+    md.render(r, spt.OutputConfig(40, 44, used_camera_name="main"), film=films[(40, 44)])
+    gc.collect()
+    md.close()
+    films.clear()
+    gc.collect()
+    _check_pin_events(stub.events)
+    assert sum(e[0] == "pin" for e in stub.events) == 6
 
 
 @pytest.mark.gpu

@@ -477,6 +477,38 @@ spt_status spt_film_adapt(spt_film* film, float rel_error, float abs_floor, uint
 /* rows * width u32: the samples each pixel covers (done for active pixels). */
 spt_status spt_film_read_counts(spt_film* film, uint32_t* out);
 
+/* ---- denoising a film (additive to ABI v14: detect it by symbol) -------------------------------------------------------------
+ * spt_film_denoise READS two films and returns a filtered copy of the first one's mean; it changes neither.  The filter is a 5x5
+ * a-trous wavelet (B3 spline, h = 1/16, 1/4, 3/8, 1/4, 1/16) run `iterations` times with step 2^k, whose weights compare the
+ * luminance of two pixels with the variance of their means and - with a `guide` - the guide's values with the guide's variance.
+ * The guide is any second film of the same scene object, size and shard layout with SPT_FILM_MOMENTS: e.g. the same plan with
+ * SPT_RENDER_DEBUG_NORMAL, whose mean is the first-hit normal.  Exact f32, one rounded operation at a time, sums in this order:
+ *     m, v = SPT_FILM_MEAN, SPT_FILM_VAR_OF_MEAN of the film at the pixel's own sample count; g, u = those of the guide
+ *     lum(c) = (0.299f * c.r + 0.587f * c.g) + 0.114f * c.b
+ *     lv_0 = ((0.299f * 0.299f) * v.r + (0.587f * 0.587f) * v.g) + (0.114f * 0.114f) * v.b;   gv = (u.r + u.g) + u.b;   c_0 = m
+ *     for k = 0 .. iterations - 1, s = 1 << k, per pixel p, with ok(q) <=> c_k(q).rgb and lv_k(q) are all finite:
+ *         acc = 0; ws = 0; va = 0
+ *         for dy = -2 .. 2, for dx = -2 .. 2, q = p + s * (dx, dy), skipped when outside the image or !ok(q):
+ *             dl = lum(c_k(p)) - lum(c_k(q));   d = (dl * dl) / ((k_color * k_color) * (lv_k(p) + lv_k(q)) + eps_color)
+ *             guide: e = g(p) - g(q);   d = d + ((e.r * e.r + e.g * e.g) + e.b * e.b) / ((k_guide * k_guide) * (gv(p) + gv(q)) + eps_guide)
+ *             skipped unless d < 87.0f (a NaN too)
+ *             w = (h[dy + 2] * h[dx + 2]) * spt_exp(-d);   acc += w * c_k(q);   ws += w;   va += (w * w) * lv_k(q)
+ *         ok(p): c_{k+1}(p) = acc / ws, lv_{k+1}(p) = va / (ws * ws);   else both pass through
+ * A pixel that is not finite stays as it is and enters no other pixel's sum.  spt_exp is that of spt_detmath.h.
+ * Refusals leave both films usable: SPT_ERR_INVALID_ARG for a null film or out, a film or guide without SPT_FILM_MOMENTS or with
+ * fewer than 2 samples, guide == film, a guide of another scene object or with another width, height or shard layout, a guide
+ * served by the other library than the film's, params->size below the struct's, iterations outside 1 .. 8, a k or eps that is
+ * not finite and > 0; SPT_ERR_UNSUPPORTED for a box radius other than 0.5 on either film and for a plan with shard_count > 1 (a
+ * shard's packed rows are not neighbours in the image).  Synchronous; the workspace belongs to `film` and goes with it. */
+typedef struct spt_denoise_params {
+    uint32_t size;         /* sizeof(spt_denoise_params): the struct only grows at its tail */
+    uint32_t iterations;   /* 1 .. 8 */
+    float k_color, k_guide, eps_color, eps_guide;   /* finite and > 0 */
+} spt_denoise_params;
+/* out: rows * width * 3 f32, packed, like spt_film_read.  guide and params may be NULL (no guide term; the defaults
+ * iterations 5, k_color 2, k_guide 1, eps_color 1e-8, eps_guide 1e-2). */
+spt_status spt_film_denoise(spt_film* film, spt_film* guide, const spt_denoise_params* params, float* out);
+
 /* Seams below the renderer, for parity tests of rows a4/a6/a8/a9/a10:
  * Primitive::intersect / intersect_test of the scene aggregate on caller rays. */
 spt_status spt_trace_closest(const spt_scene* scene, uint32_t n, const spt_ray* rays, spt_hit* hits);

@@ -205,6 +205,12 @@ class RenderStats(C.Structure):
                 ("class_visits", (C.c_uint64 * 3) * 3)]
 
 
+class DenoiseParams(C.Structure):
+    """spt_denoise_params (spt_film_denoise); `size` is sizeof of the struct."""
+    _fields_ = [("size", C.c_uint32), ("iterations", C.c_uint32), ("k_color", C.c_float), ("k_guide", C.c_float),
+                ("eps_color", C.c_float), ("eps_guide", C.c_float)]
+
+
 HIT_DTYPE = np.dtype([("t", "<f4"), ("instance", "<i4"), ("prim", "<i4"), ("v", "<f4"), ("w", "<f4")])
 RAY_DTYPE = np.dtype([("o", "<f4", 3), ("t_min", "<f4"), ("d", "<f4", 3), ("t_max", "<f4")])
 
@@ -291,6 +297,8 @@ def hip_lib() -> C.CDLL:
         lib.spt_film_destroy.restype = None
         lib.spt_film_adapt.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_uint32, C.POINTER(C.c_uint32)]
         lib.spt_film_read_counts.argtypes = [C.c_void_p, C.c_void_p]
+        if hasattr(lib, "spt_film_denoise"):   # additive to ABI v14: an older library (SPT_LIB_DIR, A/B runs) may lack it
+            lib.spt_film_denoise.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p]
         lib.spt_debug_detmath.argtypes = [C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.spt_debug_bxdf.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Material), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -540,6 +548,11 @@ class PathTracer:
         return ProgressiveFilm(self, scene, config, device, first_sample, moments, shard_index, shard_count, strip_rows,
                                samples_per_pass, flags)
 
+    def guide_film(self, scene: Scene, config: OutputConfig, device: int = 0) -> "ProgressiveFilm":
+        """The guide of ProgressiveFilm.denoise: a film of the same plan with debug_normal (its mean is the first-hit normal
+        * 0.5 + 0.5) and moments (its variance tells the filter how far to trust it).  Render a few samples into it."""
+        return ProgressiveFilm(self, scene, config, device, moments=True, flags=RENDER_DEBUG_NORMAL)
+
     def wait(self, scene: Scene, device: int = 0) -> None:
         """spt_render_wait: every render_shard(..., wait=False) queued on the scene has delivered its film."""
         _check_hip(hip_lib().spt_render_wait(scene.device_scene(device)._h))
@@ -617,6 +630,17 @@ class ProgressiveFilm:
         follow these counts)."""
         out = np.zeros((self.rows, self.width), dtype=np.uint32)
         _check_hip(hip_lib().spt_film_read_counts(self._handle(), out.ctypes.data))
+        return out
+
+    def denoise(self, guide: Optional["ProgressiveFilm"] = None, iterations: int = 5, k_color: float = 2.0, k_guide: float = 1.0,
+                eps_color: float = 1e-8, eps_guide: float = 1e-2) -> np.ndarray:
+        """spt_film_denoise: the film's mean after `iterations` steps of an edge-aware 5x5 a-trous filter whose weights compare
+        luminance differences with the variance of the mean and, with a `guide` film (PathTracer.guide_film), the guide's
+        differences with its variance.  Needs moments=True and 2 samples on both films; changes neither.  (rows, width, 3) f32."""
+        out = np.zeros((self.rows, self.width, 3), dtype=np.float32)
+        params = DenoiseParams(C.sizeof(DenoiseParams), iterations, k_color, k_guide, eps_color, eps_guide)
+        _check_hip(hip_lib().spt_film_denoise(self._handle(), guide._handle() if guide is not None else None, C.byref(params),
+                                              out.ctypes.data))
         return out
 
     def _handle(self):

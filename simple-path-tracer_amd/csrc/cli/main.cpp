@@ -6,7 +6,9 @@
 // and progressive rendering on one device through a film object (spt_film_*): --preview-every K rewrites the image after every
 // K samples, --time-limit SEC stops after the increment during which SEC seconds have passed, --variance-out PATH.exr writes the
 // per-pixel variance of the mean, --adaptive REL [--adaptive-floor A] [--adaptive-min-samples N] retires converged pixels after
-// every increment (spt_film_adapt) and stops once none is active, --samples-out PATH.exr writes each pixel's sample count.  It loads the scene
+// every increment (spt_film_adapt) and stops once none is active, --samples-out PATH.exr writes each pixel's sample count,
+// --denoise [--denoise-iterations K] [--guide-samples N] [--noisy-out PATH] renders N samples of a first-hit normal film first and
+// writes every preview and the final image through the edge-aware filter (spt_film_denoise), the plain mean to PATH.  It loads the scene
 // with libspt_host, renders with libspt_hip (HIP kernels only) and writes the image; like the reference it reports the
 // time spent inside `render`.
 #include <algorithm>
@@ -24,7 +26,8 @@ static void usage() {
                  "usage: spt -s <scene.json> -r <renderer.json> -o <out.png> [-w 512] [-h 512] [-c camera]\n"
                  "           [--seed N] [--spp N] [--device D | --gpus N | --devices a,b,..] [--strip-rows R] [--debug-normal] [--bezier-ni]\n"
                  "           [--preview-every K] [--time-limit SEC] [--variance-out var.exr]\n"
-                 "           [--adaptive REL [--adaptive-floor A] [--adaptive-min-samples N]] [--samples-out counts.exr]\n");
+                 "           [--adaptive REL [--adaptive-floor A] [--adaptive-min-samples N]] [--samples-out counts.exr]\n"
+                 "           [--denoise [--denoise-iterations K] [--guide-samples N] [--noisy-out noisy.png]]\n");
 }
 
 int main(int argc, char** argv) {
@@ -39,6 +42,9 @@ int main(int argc, char** argv) {
     std::string variance_out, samples_out;
     double adaptive = -1.0, adaptive_floor = 0.0;   // adaptive < 0: off
     uint32_t adaptive_min = 16;
+    bool denoise = false;
+    uint32_t denoise_iterations = 5, guide_samples = 16;
+    std::string noisy_out;
     std::vector<int32_t> device_list;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -75,13 +81,17 @@ int main(int argc, char** argv) {
         else if (a == "--adaptive-floor") adaptive_floor = std::atof(next());
         else if (a == "--adaptive-min-samples") adaptive_min = (uint32_t)std::atoi(next());
         else if (a == "--samples-out") samples_out = next();
+        else if (a == "--denoise") denoise = true;
+        else if (a == "--denoise-iterations") { denoise_iterations = (uint32_t)std::atoi(next()); denoise = true; }
+        else if (a == "--guide-samples") { guide_samples = (uint32_t)std::atoi(next()); denoise = true; }
+        else if (a == "--noisy-out") { noisy_out = next(); denoise = true; }
         else { usage(); return 2; }
     }
     if (scene_path.empty() || renderer_path.empty() || out_path.empty()) { usage(); return 2; }
     const bool adaptive_on = adaptive >= 0.0;
-    const bool progressive = preview_every > 0 || time_limit > 0.0 || !variance_out.empty() || adaptive_on || !samples_out.empty();
+    const bool progressive = preview_every > 0 || time_limit > 0.0 || !variance_out.empty() || adaptive_on || !samples_out.empty() || denoise;
     if (progressive && gpus > 1) {
-        std::fprintf(stderr, "Error: --preview-every, --time-limit, --variance-out, --adaptive and --samples-out render on one device (a film object), "
+        std::fprintf(stderr, "Error: --preview-every, --time-limit, --variance-out, --adaptive, --samples-out and --denoise render on one device (a film object), "
                              "not on the %d of --gpus / --devices\n", gpus);
         return 2;
     }
@@ -162,25 +172,39 @@ int main(int argc, char** argv) {
             return 1;
         }
     }
-    auto write_film = [&]() {
-        std::vector<uint8_t> rgb8(film.size());
-        spt_host_film_to_rgb8(film.data(), (uint64_t)width * height, rgb8.data());
-        if (spt_host_write_image(out_path.c_str(), rgb8.data(), width, height) != SPT_OK)
+    auto write_image = [&](const std::string& path, const std::vector<float>& img) {
+        std::vector<uint8_t> rgb8(img.size());
+        spt_host_film_to_rgb8(img.data(), (uint64_t)width * height, rgb8.data());
+        if (spt_host_write_image(path.c_str(), rgb8.data(), width, height) != SPT_OK)
             std::printf("Failed to save image, err: %s\n", spt_host_last_error());  // printed and ignored, like pt.rs:292-294
     };
+    auto write_film = [&]() { write_image(out_path, film); };
     uint32_t done = 0;
     if (progressive) {
         // the film takes the plan's samples in increments; the mean after all of them has the bits of one spt_render
         spt_film* pf = nullptr;
+        spt_film* guide = nullptr;   // --denoise: the same plan with SPT_RENDER_DEBUG_NORMAL, a first-hit normal film
         auto film_fail = [&]() {
             std::fprintf(stderr, "Error: %s\n", spt_last_error());
+            if (guide) spt_film_destroy(guide);
             if (pf) spt_film_destroy(pf);
             spt_scene_destroy(ds);
             spt_host_scene_free(hs);
             return 1;
         };
-        const bool moments = !variance_out.empty() || adaptive_on;
+        const bool moments = !variance_out.empty() || adaptive_on || denoise;
         if (spt_film_create(ds, &cam, &params, 0, moments ? (uint32_t)SPT_FILM_MOMENTS : 0u, &pf) != SPT_OK) return film_fail();
+        const spt_denoise_params dn = {(uint32_t)sizeof(spt_denoise_params), denoise_iterations, 2.0f, 1.0f, 1e-8f, 1e-2f};
+        if (denoise) {   // the guide's samples come first: every preview is filtered with the whole guide
+            spt_render_params gp = params;
+            gp.flags |= SPT_RENDER_DEBUG_NORMAL;
+            if (spt_film_create(ds, &cam, &gp, 0, (uint32_t)SPT_FILM_MOMENTS, &guide) != SPT_OK) return film_fail();
+            if (spt_film_render(guide, std::max(2u, std::min(params.spp, guide_samples))) != SPT_OK) return film_fail();
+        }
+        // the image of a preview and of the end: the film's mean, or the filtered mean (after one sample there is no variance yet)
+        auto read_image = [&]() {
+            return denoise && done >= 2 ? spt_film_denoise(pf, guide, &dn, film.data()) : spt_film_read(pf, SPT_FILM_MEAN, film.data());
+        };
         const uint32_t inc = preview_every ? preview_every : ((time_limit > 0.0 || adaptive_on) ? std::max(1u, params.spp / 16u) : params.spp);
         uint32_t active = width * height;
         while (done < params.spp) {
@@ -192,11 +216,15 @@ int main(int argc, char** argv) {
             const bool out_of_time = time_limit > 0.0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() >= time_limit;
             if (done == params.spp || out_of_time || active == 0) break;
             if (preview_every) {
-                if (spt_film_read(pf, SPT_FILM_MEAN, film.data()) != SPT_OK) return film_fail();
+                if (read_image() != SPT_OK) return film_fail();
                 write_film();
             }
         }
-        if (spt_film_read(pf, SPT_FILM_MEAN, film.data()) != SPT_OK) return film_fail();
+        if (!noisy_out.empty()) {
+            if (spt_film_read(pf, SPT_FILM_MEAN, film.data()) != SPT_OK) return film_fail();
+            write_image(noisy_out, film);
+        }
+        if (read_image() != SPT_OK) return film_fail();
         if (adaptive_on) {
             std::fprintf(stderr, "Rendered %u of %u samples per pixel, %u of %u pixels active\n", done, params.spp, active, width * height);
         } else if (time_limit > 0.0) {
@@ -212,6 +240,7 @@ int main(int argc, char** argv) {
             if (spt_film_read(pf, SPT_FILM_VAR_OF_MEAN, var.data()) != SPT_OK) return film_fail();
             if (spt_host_write_exr(variance_out.c_str(), var.data(), width, height) != SPT_OK) {
                 std::fprintf(stderr, "Error: %s\n", spt_host_last_error());
+                if (guide) spt_film_destroy(guide);
                 spt_film_destroy(pf);
                 spt_scene_destroy(ds);
                 spt_host_scene_free(hs);
@@ -225,12 +254,14 @@ int main(int argc, char** argv) {
             for (size_t k = 0; k < counts.size(); ++k) rgb[3 * k] = rgb[3 * k + 1] = rgb[3 * k + 2] = (float)counts[k];
             if (spt_host_write_exr(samples_out.c_str(), rgb.data(), width, height) != SPT_OK) {
                 std::fprintf(stderr, "Error: %s\n", spt_host_last_error());
+                if (guide) spt_film_destroy(guide);
                 spt_film_destroy(pf);
                 spt_scene_destroy(ds);
                 spt_host_scene_free(hs);
                 return 1;
             }
         }
+        if (guide) spt_film_destroy(guide);
         spt_film_destroy(pf);
     }
     write_film();

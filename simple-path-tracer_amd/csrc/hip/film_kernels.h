@@ -223,6 +223,141 @@ __global__ void __launch_bounds__(256) k_film_adapt(uint32_t width, uint32_t row
     }
 }
 
+// ---------------------------------------------------------------------------- denoiser (spt_film_denoise)
+// An edge-aware 5x5 a-trous wavelet filter (B3 spline) over a film's mean, guided by the variance of that mean and, optionally,
+// by a second film (the guide: e.g. first-hit normals) and ITS variance.  The arithmetic is spelled out in spt_abi.h; every
+// operation below is one rounded f32 operation in that order, so a float32 restatement on the host gives the same bits.
+//
+// What the filter reads of one film: its sums and how many samples each pixel covers (mask == nullptr: `done` for all, the
+// reciprocals from the host; else an adaptive film's mask / counts / inv table, as in k_film_read_counts).
+struct DenoiseFilm {
+    const float* sum;
+    const float* sum_sq;
+    const uint8_t* mask;
+    const uint32_t* counts;
+    const float* inv;
+    uint32_t done;
+    float inv_n, inv_n1;
+};
+
+// SPT_FILM_MEAN and SPT_FILM_VAR_OF_MEAN of pixel lp, the operations of k_film_read / k_film_read_counts.
+SPT_DEV void denoise_film_pixel(const DenoiseFilm& f, uint32_t lp, f3* m_out, f3* v_out) {
+    uint32_t n = f.done;
+    float inv_n = f.inv_n, inv_n1 = f.inv_n1;
+    if (f.mask) {
+        n = f.mask[lp] ? f.done : f.counts[lp];
+        inv_n = f.inv[n];
+        inv_n1 = f.inv[n - 1u];
+    }
+    const f3 s = mk3(f.sum[3 * lp], f.sum[3 * lp + 1], f.sum[3 * lp + 2]);
+    const f3 q = mk3(f.sum_sq[3 * lp], f.sum_sq[3 * lp + 1], f.sum_sq[3 * lp + 2]);
+    const f3 m = mk3(s.x * inv_n, s.y * inv_n, s.z * inv_n);
+    *m_out = m;
+    if (n == 1u) { *v_out = mk3(__builtin_huge_valf(), __builtin_huge_valf(), __builtin_huge_valf()); return; }
+    *v_out = mk3(film_var_of_mean(m.x, q.x, inv_n, inv_n1), film_var_of_mean(m.y, q.y, inv_n, inv_n1), film_var_of_mean(m.z, q.z, inv_n, inv_n1));
+}
+
+// One lane per pixel: colour (r, g, b, lv) with lv the variance of the mean's luminance, and - kGuide - guide (gx, gy, gz, gv)
+// with gv the summed variance of the guide's channels.  One 16-byte store per pixel and array.
+template <bool kGuide>
+__global__ void __launch_bounds__(256) k_denoise_pack(uint32_t n_pixels, DenoiseFilm film, DenoiseFilm guide, float4* color_out, float4* guide_out) {
+    const uint32_t lp = blockIdx.x * blockDim.x + threadIdx.x;
+    if (lp >= n_pixels) return;
+    f3 m, v;
+    denoise_film_pixel(film, lp, &m, &v);
+    const float lv = ((0.299f * 0.299f) * v.x + (0.587f * 0.587f) * v.y) + (0.114f * 0.114f) * v.z;
+    color_out[lp] = make_float4(m.x, m.y, m.z, lv);
+    if constexpr (kGuide) {
+        f3 g, u;
+        denoise_film_pixel(guide, lp, &g, &u);
+        guide_out[lp] = make_float4(g.x, g.y, g.z, (u.x + u.y) + u.z);
+    }
+}
+
+// ok(q) of the specification: a pixel whose colour or luminance variance is not finite neither filters nor is filtered.
+SPT_DEV bool denoise_ok(const float4& c) { return spt_is_finite(c.x) && spt_is_finite(c.y) && spt_is_finite(c.z) && spt_is_finite(c.w); }
+
+struct DenoiseArgs {
+    uint32_t width, rows, tiles_x;
+    int32_t step;                     // 1 << k
+    float kc2, kg2, eps_c, eps_g;     // k_color^2, k_guide^2 (multiplied by the host), the two epsilons
+};
+
+// One tap of the filter: pixel q (colour record cq, guide record gq, spline weight hw) seen from pixel p, added to p's three sums.
+template <bool kGuide>
+SPT_DEV void denoise_tap(const DenoiseArgs& a, const float4& cp, const float4& gp, float l_p, const float4& cq, const float4& gq, float hw,
+                         f3& acc, float& ws, float& va) {
+    if (!denoise_ok(cq)) return;
+    const float dl = l_p - luminance(mk3(cq.x, cq.y, cq.z));
+    float d = (dl * dl) / (a.kc2 * (cp.w + cq.w) + a.eps_c);
+    if constexpr (kGuide) {
+        const float ex = gp.x - gq.x, ey = gp.y - gq.y, ez = gp.z - gq.z;
+        d = d + ((ex * ex + ey * ey) + ez * ez) / (a.kg2 * (gp.w + gq.w) + a.eps_g);
+    }
+    if (!(d < 87.0f)) return;   // (also a NaN; spt_exp(-d) is 0 beyond)
+    const float w = hw * spt_exp(-d);
+    acc = mk3(acc.x + w * cq.x, acc.y + w * cq.y, acc.z + w * cq.z);
+    ws = ws + w;
+    va = va + (w * w) * cq.w;
+}
+
+// What a pixel becomes after its 25 taps; kLast: packed RGB f32 (the film's read-out staging buffer), the variance is dropped.
+template <bool kLast>
+SPT_DEV void denoise_store(uint32_t lp, const float4& cp, const f3& acc, float ws, float va, float4* color_out, float* rgb_out) {
+    float4 r = cp;   // a pixel that is not ok passes through
+    if (denoise_ok(cp)) r = make_float4(acc.x / ws, acc.y / ws, acc.z / ws, va / (ws * ws));
+    if constexpr (kLast) {
+        rgb_out[3 * lp] = r.x; rgb_out[3 * lp + 1] = r.y; rgb_out[3 * lp + 2] = r.z;
+    } else {
+        color_out[lp] = r;
+    }
+}
+
+SPT_DEV float denoise_h(int32_t d) { return d == 0 ? 3.0f / 8.0f : ((d == -1 || d == 1) ? 1.0f / 4.0f : 1.0f / 16.0f); }   // the B3 spline
+
+// One a-trous iteration: one 256-lane block per 16x16 tile (k_primary's numbering), one lane per pixel, 25 taps at distance
+// `step`, rows top to bottom and left to right within a row: the order of the sums.  A tap is one 16-byte load of the colour record
+// and - kGuide - one of the guide record; the taps are independent, and one row of five (10 loads) is requested before its
+// arithmetic starts, which keeps the kernel under 128 VGPRs.  The re-reads of the neighbours hit L1 / L2: per iteration the kernel
+// moves 48 bytes per pixel with a guide (32 read + 16 written), 32 without.  A tap outside the image reads the lane's own pixel
+// and is not added.  The kernel is bound by its arithmetic (two divisions and one spt_exp per tap), not by these loads: staging the
+// tile's footprint in LDS for steps 1 and 2 was measured and changed nothing ("Denoising").
+template <bool kGuide, bool kLast>
+__global__ void __launch_bounds__(256) k_denoise_atrous(DenoiseArgs a, const float4* __restrict__ color_in, const float4* __restrict__ guide,
+                                                        float4* __restrict__ color_out, float* __restrict__ rgb_out) {
+    const uint32_t tile = blockIdx.x, tx = tile % a.tiles_x, ty = tile / a.tiles_x;
+    const int32_t x = (int32_t)(tx * 16u + (threadIdx.x % 16u)), y = (int32_t)(ty * 16u + (threadIdx.x / 16u));
+    if (x >= (int32_t)a.width || y >= (int32_t)a.rows) return;
+    const uint32_t lp = (uint32_t)y * a.width + (uint32_t)x;
+    const float4 cp = color_in[lp];
+    float4 gp = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if constexpr (kGuide) gp = guide[lp];
+    const float l_p = luminance(mk3(cp.x, cp.y, cp.z));
+    f3 acc = mk3(0, 0, 0);
+    float ws = 0.0f, va = 0.0f;
+#pragma unroll 1
+    for (int32_t dy = -2; dy <= 2; ++dy) {
+        const int32_t qy = y + a.step * dy;
+        const bool row_in = qy >= 0 && qy < (int32_t)a.rows;
+        float4 cq[5], gq[5];
+        bool in[5];
+#pragma unroll
+        for (int32_t k = 0; k < 5; ++k) {
+            const int32_t qx = x + a.step * (k - 2);
+            in[k] = row_in && qx >= 0 && qx < (int32_t)a.width;
+            const uint32_t lq = in[k] ? (uint32_t)qy * a.width + (uint32_t)qx : lp;
+            cq[k] = color_in[lq];
+            gq[k] = gp;
+            if constexpr (kGuide) gq[k] = guide[lq];
+        }
+        const float hy = denoise_h(dy);
+#pragma unroll
+        for (int32_t k = 0; k < 5; ++k)
+            if (in[k]) denoise_tap<kGuide>(a, cp, gp, l_p, cq[k], gq[k], hy * denoise_h(k - 2), acc, ws, va);
+    }
+    denoise_store<kLast>(lp, cp, acc, ws, va, color_out, rgb_out);
+}
+
 // radius_int >= 1: Film::filter_pixel (film.rs:71-92) over the kept samples of a band of whole rows.  Rows j, then
 // columns i, then the samples of that pixel in the order they were added, one running colour sum (the colour is NOT
 // weighted - film.rs:87 adds sample.color as is - only weight_sum looks at the offsets).

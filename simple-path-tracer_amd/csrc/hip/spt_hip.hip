@@ -509,6 +509,7 @@ struct BezierLib {
     decltype(&spt_film_destroy) film_destroy = nullptr;
     decltype(&spt_film_adapt) film_adapt = nullptr;
     decltype(&spt_film_read_counts) film_read_counts = nullptr;
+    decltype(&spt_film_denoise) film_denoise = nullptr;
     decltype(&spt_trace_closest) trace_closest = nullptr;
     decltype(&spt_trace_any) trace_any = nullptr;
     decltype(&spt_debug_bxdf) debug_bxdf = nullptr;
@@ -606,6 +607,8 @@ struct spt_film {
     DeviceBuffer totals;              // 2 u32 of k_film_adapt: active pixels, tiles with any
     DeviceBuffer inv;                 // (spp + 1) f32: inv[k] = 1.0f / (float)k as the host rounds it (inv[0] = 0, never read)
     uint32_t active = 0, active_tiles = 0;
+    // spt_film_denoise's workspace, made by its first call: two colour arrays (ping-pong) and the guide array, one float4 per pixel
+    DeviceBuffer dn_color[2], dn_guide;
 };
 
 namespace {
@@ -832,6 +835,7 @@ const BezierLib* bezier_lib() {
                          sym(lib.render_wait, "spt_render_wait") && sym(lib.film_create, "spt_film_create") && sym(lib.film_render, "spt_film_render") &&
                          sym(lib.film_samples, "spt_film_samples") && sym(lib.film_read, "spt_film_read") && sym(lib.film_destroy, "spt_film_destroy") &&
                          sym(lib.film_adapt, "spt_film_adapt") && sym(lib.film_read_counts, "spt_film_read_counts") &&
+                         sym(lib.film_denoise, "spt_film_denoise") &&
                          sym(lib.trace_closest, "spt_trace_closest") && sym(lib.trace_any, "spt_trace_any") && sym(lib.debug_bxdf, "spt_debug_bxdf") &&
                          sym(lib.last_error, "spt_last_error") && sym(version, "spt_abi_version");
         if (!all || version() != SPT_ABI_VERSION) {
@@ -2494,6 +2498,103 @@ spt_status spt_film_read_counts(spt_film* f, uint32_t* out) {
         HIP_CHECK(hipStreamSynchronize(sc->stream));
         for (uint32_t i = 0; i < n_pix; ++i)
             if (mask[i]) out[i] = f->done;
+        return SPT_OK;
+    });
+}
+
+// What k_denoise_pack reads of a film that covers at least 2 samples.
+static DenoiseFilm denoise_input(const spt_film* f) {
+    DenoiseFilm in{};
+    in.sum = f->sum.as<float>();
+    in.sum_sq = f->sq.as<float>();
+    in.done = f->done;
+    in.inv_n = 1.0f / (float)f->done;
+    in.inv_n1 = 1.0f / (float)(f->done - 1u);
+    if (f->adaptive) {
+        in.mask = f->mask.as<uint8_t>();
+        in.counts = f->counts.as<uint32_t>();
+        in.inv = f->inv.as<float>();
+    }
+    return in;
+}
+
+spt_status spt_film_denoise(spt_film* f, spt_film* guide, const spt_denoise_params* params, float* out) {
+    if (!f || !out) { g_error = "film_denoise: null argument"; return SPT_ERR_INVALID_ARG; }
+    if ((f->fwd != nullptr) != (guide ? guide->fwd != nullptr : f->fwd != nullptr)) {
+        g_error = "film_denoise: the film and the guide are served by different libraries (one scene has Bezier patches)";
+        return SPT_ERR_INVALID_ARG;
+    }
+    if (f->fwd) return forwarded(f->fwd, f->fwd->film_denoise(f->inner, guide ? guide->inner : nullptr, params, out));
+    spt_scene* sc = f->sc;
+    std::lock_guard<std::mutex> lock(sc->mu);
+    return guarded("film_denoise", [&] {
+        const spt_render_params& p = f->plan;
+        // every check comes before the first launch: a refused call leaves the workspace as it was, and it reads the films only
+        auto check_film = [](const spt_film* x, const char* who) {
+            if (!(x->flags & SPT_FILM_MOMENTS))
+                fail(SPT_ERR_INVALID_ARG, std::string("film_denoise: the ") + who + " was created without SPT_FILM_MOMENTS (the weights need the variance of the mean)");
+            if (x->done < 2) fail(SPT_ERR_INVALID_ARG, std::string("film_denoise: the ") + who + " covers fewer than 2 samples (no variance yet)");
+        };
+        check_film(f, "film");
+        if (guide) {
+            if (guide == f) fail(SPT_ERR_INVALID_ARG, "film_denoise: the guide is the film itself");
+            if (guide->sc != sc) fail(SPT_ERR_INVALID_ARG, "film_denoise: the guide belongs to another scene object");
+            check_film(guide, "guide");
+            const spt_render_params& g = guide->plan;
+            if (g.width != p.width || g.height != p.height) fail(SPT_ERR_INVALID_ARG, "film_denoise: the guide has another width or height");
+            if (g.shard_index != p.shard_index || (g.shard_count ? g.shard_count : 1u) != (p.shard_count ? p.shard_count : 1u) ||
+                (g.strip_rows ? g.strip_rows : 1u) != (p.strip_rows ? p.strip_rows : 1u) || guide->rows != f->rows)
+                fail(SPT_ERR_INVALID_ARG, "film_denoise: the guide has another shard layout");
+        }
+        spt_denoise_params dp{(uint32_t)sizeof(spt_denoise_params), 5u, 2.0f, 1.0f, 1e-8f, 1e-2f};
+        if (params) {
+            if (params->size < sizeof(spt_denoise_params)) fail(SPT_ERR_INVALID_ARG, "film_denoise: params->size is smaller than spt_denoise_params");
+            dp = *params;
+        }
+        if (dp.iterations < 1u || dp.iterations > 8u) fail(SPT_ERR_INVALID_ARG, "film_denoise: iterations must be 1 .. 8");
+        for (const float v : {dp.k_color, dp.k_guide, dp.eps_color, dp.eps_guide})
+            if (!std::isfinite(v) || !(v > 0.0f)) fail(SPT_ERR_INVALID_ARG, "film_denoise: k_color, k_guide, eps_color and eps_guide must be finite and > 0");
+        if (f->radius != 0.5f || (guide && guide->radius != 0.5f))
+            fail(SPT_ERR_UNSUPPORTED, "film_denoise: needs the box radius 0.5 on both films (every sample of the pixel weighs 1)");
+        if (p.shard_count > 1u) fail(SPT_ERR_UNSUPPORTED, "film_denoise: the plan has shard_count > 1 (a shard's packed rows are not neighbours in the image)");
+        if (f->rows == 0 || p.width == 0) return SPT_OK;
+        const uint32_t n_pix = f->rows * p.width;
+        HIP_CHECK(hipSetDevice(sc->device));
+        const hipStream_t st = sc->stream;
+        const size_t rec_bytes = (size_t)n_pix * sizeof(float4), out_bytes = (size_t)n_pix * 3 * sizeof(float);
+        f->dn_color[0].ensure(rec_bytes);
+        if (dp.iterations > 1u) f->dn_color[1].ensure(rec_bytes);
+        if (guide) f->dn_guide.ensure(rec_bytes);
+        f->out.ensure(out_bytes);
+        float4* color[2] = {f->dn_color[0].as<float4>(), dp.iterations > 1u ? f->dn_color[1].as<float4>() : nullptr};
+        float4* const gbuf = guide ? f->dn_guide.as<float4>() : nullptr;
+        const dim3 pack_grid((n_pix + kBlock - 1) / kBlock), block(kBlock);
+        if (guide) hipLaunchKernelGGL(k_denoise_pack<true>, pack_grid, block, 0, st, n_pix, denoise_input(f), denoise_input(guide), color[0], gbuf);
+        else hipLaunchKernelGGL(k_denoise_pack<false>, pack_grid, block, 0, st, n_pix, denoise_input(f), DenoiseFilm{}, color[0], gbuf);
+        HIP_CHECK(hipGetLastError());
+        DenoiseArgs a{};
+        a.width = p.width;
+        a.rows = f->rows;
+        a.tiles_x = (p.width + kTile - 1) / kTile;
+        a.kc2 = dp.k_color * dp.k_color;
+        a.kg2 = dp.k_guide * dp.k_guide;
+        a.eps_c = dp.eps_color;
+        a.eps_g = dp.eps_guide;
+        const dim3 grid(a.tiles_x * ((f->rows + kTile - 1) / kTile));
+        for (uint32_t k = 0; k < dp.iterations; ++k) {
+            a.step = (int32_t)(1u << k);
+            const float4* src = color[k & 1u];
+            float4* dst = color[(k + 1u) & 1u];
+            const bool last = k + 1u == dp.iterations;
+            auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, a, src, gbuf, dst, f->out.as<float>()); };
+            if (guide && last) launch(k_denoise_atrous<true, true>);
+            else if (guide) launch(k_denoise_atrous<true, false>);
+            else if (last) launch(k_denoise_atrous<false, true>);
+            else launch(k_denoise_atrous<false, false>);
+            HIP_CHECK(hipGetLastError());
+        }
+        HIP_CHECK(hipMemcpyAsync(out, f->out.p, out_bytes, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
         return SPT_OK;
     });
 }

@@ -509,6 +509,43 @@ typedef struct spt_denoise_params {
  * iterations 5, k_color 2, k_guide 1, eps_color 1e-8, eps_guide 1e-2). */
 spt_status spt_film_denoise(spt_film* film, spt_film* guide, const spt_denoise_params* params, float* out);
 
+/* ---- bucketed films: median-of-means read-outs (additive to ABI v14: detect it by symbol) ------------------------------------
+ * spt_film_buckets makes a film keep K = n_buckets bucket sums B_0 .. B_{K-1} per pixel and channel next to S (and Q).  The sample
+ * with plan index s (absolute in the plan: first_sample counts) adds into bucket j = s % K, B_j = B_j + x per channel, in sample
+ * order; a black sample adds nothing; B starts at +0.  S, Q, spt_film_adapt and spt_film_denoise of a bucketed film are those of
+ * the same film without buckets, and a film that never calls spt_film_buckets is a plain film, bit for bit.
+ * Counts (integer arithmetic): the pixel covers n_p samples - `done` for a plain film or an active pixel, the retired count of an
+ * adaptive film otherwise - and bucket j holds n_j = #{ s in [first_sample, first_sample + n_p) : s % K == j } of them.
+ * spt_film_read_robust, exact f32, one rounded operation at a time, no contraction, per pixel and channel, with
+ * r(k) = 1.0f / (float)k as the host rounds it and h = (K - 1) / 2:
+ *     n_p < K (some bucket is empty): the result is the plain mean S * r(n_p)
+ *     mu_j = B_j * r(n_j);   key_j = finite(mu_j) ? mu_j + 0.0f : +inf;   a_0 <= ... <= a_{K-1}: the keys sorted ascending
+ *     SPT_ROBUST_MON:  the result is a_h, the median of the bucket means
+ *     SPT_ROBUST_GMON: num = sum_{i = 0 .. K-1} (float)(i + 1) * a_i and den = sum_{i = 0 .. K-1} a_i, both from i = 0 upward, from 0
+ *         t = h                    if a_{K-1} is +inf (a bucket with a sample that is not finite)
+ *         else t = 0               if !(den > 0)
+ *         else G = (2.0f * num) / ((float)K * den) - ((float)(K + 1) / (float)K)      (the Gini coefficient of the bucket means)
+ *              t = 0               if !(G > 0)
+ *              t = h               if G * (float)h >= (float)h
+ *              t = (uint32_t)(G * (float)h)   otherwise
+ *         the result is (sum_{i = t .. K-1-t} a_i, from i = t upward) * r(K - 2t): the mean of the keys without the t lowest and
+ *         the t highest - the plain mean of the bucket means where they agree, their median where they do not
+ * A sample that is not finite spoils one bucket of K, not the pixel: K = 5, bucket means (0, 0, 0, 0, 10) give G = 0.8, t = 1 and
+ * the result 0 (MON 0, the plain mean 2); (1, 1, 1, 1, 1) give t = 0.
+ * Refusals leave the film exactly as it was.  spt_film_buckets: a null film, n_buckets even or outside 3 .. 15, a film that
+ * already covers samples (done > 0) or already has buckets (SPT_ERR_INVALID_ARG); a box radius other than 0.5
+ * (SPT_ERR_UNSUPPORTED); no memory (SPT_ERR_OUT_OF_MEMORY).  spt_film_read_buckets and spt_film_read_robust: a null film or out,
+ * a film without buckets, an unknown estimator, spt_film_read_robust while done == 0 (SPT_ERR_INVALID_ARG).  A film without rows
+ * returns SPT_OK and writes nothing.  Buckets go with any first_sample, shard layout, samples_per_pass, sampler, with and without
+ * SPT_FILM_MOMENTS and SPT_RENDER_DEBUG_NORMAL.  All three calls take the scene's lock and are synchronous. */
+/* Turns on K = n_buckets bucket sums.  Only while the film covers no sample (done == 0). */
+spt_status spt_film_buckets(spt_film* film, uint32_t n_buckets);
+/* [n_buckets][rows][width][3] f32: the bucket sums B_j, packed rows like spt_film_read. */
+spt_status spt_film_read_buckets(spt_film* film, float* out);
+enum { SPT_ROBUST_MON = 0, SPT_ROBUST_GMON = 1 };
+/* rows * width * 3 f32 */
+spt_status spt_film_read_robust(spt_film* film, uint32_t estimator, float* out);
+
 /* Seams below the renderer, for parity tests of rows a4/a6/a8/a9/a10:
  * Primitive::intersect / intersect_test of the scene aggregate on caller rays. */
 spt_status spt_trace_closest(const spt_scene* scene, uint32_t n, const spt_ray* rays, spt_hit* hits);

@@ -184,6 +184,7 @@ RENDER_ASYNC = 8
 RENDER_DEBUG_NORMAL = 16   # the reference's cargo feature `debug_normal` (Cargo.toml:34-36, pt.rs:113-118)
 FILM_MOMENTS = 1          # spt_film_create: also keep the per-channel sum of squared sample radiance (ABI v14)
 FILM_MEAN, FILM_SUM, FILM_SUM_SQ, FILM_VAR_OF_MEAN = 0, 1, 2, 3   # spt_film_read
+ROBUST_MON, ROBUST_GMON = 0, 1   # spt_film_read_robust: median of the bucket means, Gini-adaptive trimmed mean of them
 N_KERNELS = 7
 KERNEL_NAMES = ("primary", "shade", "shadow", "extend", "resolve", "other", "shade_first")
 
@@ -299,6 +300,10 @@ def hip_lib() -> C.CDLL:
         lib.spt_film_read_counts.argtypes = [C.c_void_p, C.c_void_p]
         if hasattr(lib, "spt_film_denoise"):   # additive to ABI v14: an older library (SPT_LIB_DIR, A/B runs) may lack it
             lib.spt_film_denoise.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p]
+        if hasattr(lib, "spt_film_buckets"):   # (the same)
+            lib.spt_film_buckets.argtypes = [C.c_void_p, C.c_uint32]
+            lib.spt_film_read_buckets.argtypes = [C.c_void_p, C.c_void_p]
+            lib.spt_film_read_robust.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         lib.spt_debug_detmath.argtypes = [C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.spt_debug_bxdf.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Material), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -540,13 +545,14 @@ class PathTracer:
 
     def progressive(self, scene: Scene, config: OutputConfig, device: int = 0, first_sample: int = 0, moments: bool = False,
                     shard_index: int = 0, shard_count: int = 1, strip_rows: int = 16, samples_per_pass: int = 0,
-                    flags: int = 0) -> "ProgressiveFilm":
+                    flags: int = 0, buckets: int = 0) -> "ProgressiveFilm":
         """A film that takes this renderer's samples in increments (spt_film_*): `spp` is the plan's total, each
         ProgressiveFilm.render(n) adds the next n samples, and after increments summing to spp (first_sample 0) mean() has the
         bits of render_shard with the same arguments.  moments=True also keeps the sums of squares (sum_sq, variance_of_mean).
-        `flags` are extra SPT_RENDER_* bits of the plan."""
+        `flags` are extra SPT_RENDER_* bits of the plan.  buckets=K (odd, 3 .. 15) also keeps K bucket sums per pixel (sample s of
+        the plan goes to bucket s % K) for bucket_sums() and robust_mean()."""
         return ProgressiveFilm(self, scene, config, device, first_sample, moments, shard_index, shard_count, strip_rows,
-                               samples_per_pass, flags)
+                               samples_per_pass, flags, buckets)
 
     def guide_film(self, scene: Scene, config: OutputConfig, device: int = 0) -> "ProgressiveFilm":
         """The guide of ProgressiveFilm.denoise: a film of the same plan with debug_normal (its mean is the first-hit normal
@@ -572,7 +578,7 @@ class ProgressiveFilm:
 
     def __init__(self, renderer: PathTracer, scene: Scene, config: OutputConfig, device: int = 0, first_sample: int = 0,
                  moments: bool = False, shard_index: int = 0, shard_count: int = 1, strip_rows: int = 16,
-                 samples_per_pass: int = 0, flags: int = 0):
+                 samples_per_pass: int = 0, flags: int = 0, buckets: int = 0):
         self._h = C.c_void_p()
         self._ds = scene.device_scene(device)
         self.scene = scene
@@ -586,6 +592,32 @@ class ProgressiveFilm:
         _check_hip(hip_lib().spt_film_create(self._ds._h, C.byref(self._cam), C.byref(self._params), first_sample,
                                              FILM_MOMENTS if moments else 0, C.byref(self._h)))
         self._ds._films.add(self)
+        self.n_buckets = 0
+        if buckets:
+            self.set_buckets(buckets)
+
+    def set_buckets(self, n_buckets: int) -> None:
+        """spt_film_buckets: K = n_buckets bucket sums per pixel (K odd, 3 .. 15) from the film's first sample on.  What the
+        `buckets=` keyword calls after the film is created; public for a caller that decides after creating the film, which
+        works until the first render and once (SptError otherwise, and for a box radius other than 0.5; the film stays usable)."""
+        _check_hip(hip_lib().spt_film_buckets(self._handle(), n_buckets))
+        self.n_buckets = n_buckets
+
+    def bucket_sums(self) -> np.ndarray:
+        """(K, rows, width, 3) f32: B_j, the sum of the covered samples whose plan index s has s % K == j, in sample order."""
+        out = np.zeros((self.n_buckets, self.rows, self.width, 3), dtype=np.float32)
+        _check_hip(hip_lib().spt_film_read_buckets(self._handle(), out.ctypes.data))
+        return out
+
+    def robust_mean(self, estimator: str = "gmon") -> np.ndarray:
+        """spt_film_read_robust: "mon", the median of the K bucket means, or "gmon", their mean without the t lowest and t highest,
+        t growing with their Gini coefficient (the plain mean of the bucket means where they agree, the median where they do
+        not).  A sample that is not finite spoils one bucket, not the pixel.  (rows, width, 3) f32."""
+        if estimator not in ("mon", "gmon"):
+            raise ValueError("robust_mean: estimator is 'mon' or 'gmon', not %r" % (estimator,))
+        out = np.zeros((self.rows, self.width, 3), dtype=np.float32)
+        _check_hip(hip_lib().spt_film_read_robust(self._handle(), ROBUST_MON if estimator == "mon" else ROBUST_GMON, out.ctypes.data))
+        return out
 
     def render(self, n: int) -> "ProgressiveFilm":
         """Adds the next n samples of the plan (synchronous)."""

@@ -8,7 +8,9 @@
 // per-pixel variance of the mean, --adaptive REL [--adaptive-floor A] [--adaptive-min-samples N] retires converged pixels after
 // every increment (spt_film_adapt) and stops once none is active, --samples-out PATH.exr writes each pixel's sample count,
 // --denoise [--denoise-iterations K] [--guide-samples N] [--noisy-out PATH] renders N samples of a first-hit normal film first and
-// writes every preview and the final image through the edge-aware filter (spt_film_denoise), the plain mean to PATH.  It loads the scene
+// writes every preview and the final image through the edge-aware filter (spt_film_denoise), the plain mean to PATH,
+// --robust K [--robust-estimator mon|gmon] [--mean-out PATH] keeps K bucket sums per pixel (spt_film_buckets) and writes every preview
+// and the final image from their median (mon) or Gini-adaptive trimmed mean (gmon, the default), the plain mean to PATH.  It loads the scene
 // with libspt_host, renders with libspt_hip (HIP kernels only) and writes the image; like the reference it reports the
 // time spent inside `render`.
 #include <algorithm>
@@ -27,7 +29,8 @@ static void usage() {
                  "           [--seed N] [--spp N] [--device D | --gpus N | --devices a,b,..] [--strip-rows R] [--debug-normal] [--bezier-ni]\n"
                  "           [--preview-every K] [--time-limit SEC] [--variance-out var.exr]\n"
                  "           [--adaptive REL [--adaptive-floor A] [--adaptive-min-samples N]] [--samples-out counts.exr]\n"
-                 "           [--denoise [--denoise-iterations K] [--guide-samples N] [--noisy-out noisy.png]]\n");
+                 "           [--denoise [--denoise-iterations K] [--guide-samples N] [--noisy-out noisy.png]]\n"
+                 "           [--robust K [--robust-estimator mon|gmon] [--mean-out mean.png]]   (K odd, 3 .. 15)\n");
 }
 
 int main(int argc, char** argv) {
@@ -45,6 +48,9 @@ int main(int argc, char** argv) {
     bool denoise = false;
     uint32_t denoise_iterations = 5, guide_samples = 16;
     std::string noisy_out;
+    bool robust = false;
+    int robust_k = 0;
+    std::string robust_estimator, mean_out;
     std::vector<int32_t> device_list;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -85,13 +91,33 @@ int main(int argc, char** argv) {
         else if (a == "--denoise-iterations") { denoise_iterations = (uint32_t)std::atoi(next()); denoise = true; }
         else if (a == "--guide-samples") { guide_samples = (uint32_t)std::atoi(next()); denoise = true; }
         else if (a == "--noisy-out") { noisy_out = next(); denoise = true; }
+        else if (a == "--robust") { robust_k = std::atoi(next()); robust = true; }
+        else if (a == "--robust-estimator") robust_estimator = next();
+        else if (a == "--mean-out") mean_out = next();
         else { usage(); return 2; }
     }
     if (scene_path.empty() || renderer_path.empty() || out_path.empty()) { usage(); return 2; }
     const bool adaptive_on = adaptive >= 0.0;
-    const bool progressive = preview_every > 0 || time_limit > 0.0 || !variance_out.empty() || adaptive_on || !samples_out.empty() || denoise;
+    if (!robust && (!robust_estimator.empty() || !mean_out.empty())) {
+        std::fprintf(stderr, "Error: --robust-estimator and --mean-out need --robust K\n");
+        return 2;
+    }
+    if (robust && (robust_k < 3 || robust_k > 15 || robust_k % 2 == 0)) {
+        std::fprintf(stderr, "Error: --robust %d: the bucket count must be odd and 3 .. 15\n", robust_k);
+        return 2;
+    }
+    if (robust && !robust_estimator.empty() && robust_estimator != "mon" && robust_estimator != "gmon") {
+        std::fprintf(stderr, "Error: --robust-estimator %s: mon or gmon\n", robust_estimator.c_str());
+        return 2;
+    }
+    if (robust && denoise) {
+        std::fprintf(stderr, "Error: --robust and --denoise exclude each other (the denoiser filters the plain mean)\n");
+        return 2;
+    }
+    const uint32_t estimator = robust_estimator == "mon" ? (uint32_t)SPT_ROBUST_MON : (uint32_t)SPT_ROBUST_GMON;
+    const bool progressive = preview_every > 0 || time_limit > 0.0 || !variance_out.empty() || adaptive_on || !samples_out.empty() || denoise || robust;
     if (progressive && gpus > 1) {
-        std::fprintf(stderr, "Error: --preview-every, --time-limit, --variance-out, --adaptive, --samples-out and --denoise render on one device (a film object), "
+        std::fprintf(stderr, "Error: --preview-every, --time-limit, --variance-out, --adaptive, --samples-out, --denoise and --robust render on one device (a film object), "
                              "not on the %d of --gpus / --devices\n", gpus);
         return 2;
     }
@@ -194,6 +220,7 @@ int main(int argc, char** argv) {
         };
         const bool moments = !variance_out.empty() || adaptive_on || denoise;
         if (spt_film_create(ds, &cam, &params, 0, moments ? (uint32_t)SPT_FILM_MOMENTS : 0u, &pf) != SPT_OK) return film_fail();
+        if (robust && spt_film_buckets(pf, (uint32_t)robust_k) != SPT_OK) return film_fail();
         const spt_denoise_params dn = {(uint32_t)sizeof(spt_denoise_params), denoise_iterations, 2.0f, 1.0f, 1e-8f, 1e-2f};
         if (denoise) {   // the guide's samples come first: every preview is filtered with the whole guide
             spt_render_params gp = params;
@@ -201,8 +228,10 @@ int main(int argc, char** argv) {
             if (spt_film_create(ds, &cam, &gp, 0, (uint32_t)SPT_FILM_MOMENTS, &guide) != SPT_OK) return film_fail();
             if (spt_film_render(guide, std::max(2u, std::min(params.spp, guide_samples))) != SPT_OK) return film_fail();
         }
-        // the image of a preview and of the end: the film's mean, or the filtered mean (after one sample there is no variance yet)
+        // the image of a preview and of the end: the film's mean, the filtered mean (after one sample there is no variance yet)
+        // or the robust read-out of the buckets
         auto read_image = [&]() {
+            if (robust) return spt_film_read_robust(pf, estimator, film.data());
             return denoise && done >= 2 ? spt_film_denoise(pf, guide, &dn, film.data()) : spt_film_read(pf, SPT_FILM_MEAN, film.data());
         };
         const uint32_t inc = preview_every ? preview_every : ((time_limit > 0.0 || adaptive_on) ? std::max(1u, params.spp / 16u) : params.spp);
@@ -223,6 +252,10 @@ int main(int argc, char** argv) {
         if (!noisy_out.empty()) {
             if (spt_film_read(pf, SPT_FILM_MEAN, film.data()) != SPT_OK) return film_fail();
             write_image(noisy_out, film);
+        }
+        if (!mean_out.empty()) {
+            if (spt_film_read(pf, SPT_FILM_MEAN, film.data()) != SPT_OK) return film_fail();
+            write_image(mean_out, film);
         }
         if (read_image() != SPT_OK) return film_fail();
         if (adaptive_on) {

@@ -102,6 +102,83 @@ __global__ void __launch_bounds__(256) k_resolve(RenderCtx rc, Sq... sq_arg) {
     if constexpr (kMoments) { sq[3 * lp] = sum_sq.x; sq[3 * lp + 1] = sum_sq.y; sq[3 * lp + 2] = sum_sq.z; }
 }
 
+// The bucket sums of a bucketed film (spt_film_buckets), after the resolve of the same pass and over the same radiance slots: one
+// lane per pixel.  Sample s of the pass has the plan index rc.pass_first + s and belongs to bucket (rc.pass_first + s) % K, so the
+// samples of bucket j are s_j, s_j + K, ... in increasing s, and the additions of one bucket are sequential in that order.
+// Different buckets do not depend on each other: the lane takes a group of up to kBucketGroup buckets at once (K <= 8: all of
+// them; else two groups of about K / 2), loads their sums together, then walks the rounds - round m holds the m-th sample of each
+// bucket of the group - requesting the slots of a round (kBits: their raw mask bytes too) together before it adds them, each to
+// its own register (every register index is a compile-time one; the bucket number only enters addresses), and stores the group
+// back.  Every slot is read once, with up to 8 samples (24 loads) in flight per lane, as in k_resolve.
+// kBits: after a chunked primary, where only the samples marked in slot_bits own a slot (the others were black and add
+// nothing); else after an un-chunked one, where the samples before first_slot were black (a bucketed film of a scene with an
+// environment takes the chunked primary, as a film with moments does) and every later one owns a slot.  An unmarked slot is
+// read (whatever it holds) and not added, as in k_resolve_bits.  A pixel that the pass did not trace (outside the screen bound,
+// or retired in an adaptive film) has first_slot == pass_samples and is left alone; a bucket without a sample in the pass too.
+// K, the bucket array and its plane stride (floats per bucket) are arguments of this kernel only: RenderCtx does not grow.
+constexpr uint32_t kBucketGroup = 8;
+
+template <bool kBits>
+__global__ void __launch_bounds__(256) k_resolve_buckets(RenderCtx rc, uint32_t K, float* buckets, size_t bucket_plane) {
+    const uint32_t lp = blockIdx.x * blockDim.x + threadIdx.x;
+    if (lp >= rc.n_pixels) return;
+    const uint32_t first = rc.first_slot[lp];
+    const uint32_t n = rc.pass_samples;
+    if (first >= n) return;
+    const size_t plane = rc.rad_plane, np = rc.n_pixels;
+    const float* rp = rc.rad + lp;
+    const uint8_t* bp = kBits ? rc.slot_bits + lp : nullptr;
+    const uint32_t phase = rc.pass_first % K;
+    const uint32_t n_groups = (K + kBucketGroup - 1u) / kBucketGroup, group = (K + n_groups - 1u) / n_groups;
+    for (uint32_t j0 = 0; j0 < K; j0 += group) {
+        const uint32_t in_group = min(group, K - j0);
+        // Straight-line code between the loads: a slot of the group that has no bucket (c >= in_group) or no sample left reads a
+        // clamped address (bucket K - 1, the pass's last sample) and its value is not used, so no branch separates the loads
+        // and all of a round's are requested before the first wait.
+        uint32_t s[kBucketGroup];     // the next sample of the pass in bucket j0 + c; >= n: none (left)
+        f3 sum[kBucketGroup];
+        uint32_t touched = 0u;
+#pragma unroll
+        for (uint32_t c = 0; c < kBucketGroup; ++c) {
+            const uint32_t j = j0 + c;
+            s[c] = c < in_group ? (j >= phase ? j - phase : j + K - phase) : n;
+            const float* bj = buckets + (size_t)min(j, K - 1u) * bucket_plane + 3 * (size_t)lp;
+            sum[c] = mk3(bj[0], bj[1], bj[2]);
+            if (s[c] < n) touched |= 1u << c;
+        }
+        uint32_t pending = touched;
+        // One round.  It is called once ahead of the loop, so that the first round's loads are requested together with the
+        // sums' loads above (one dependent round trip per round, the sums' included in the first).
+        auto round = [&]() {
+            float r[kBucketGroup], g[kBucketGroup], b[kBucketGroup];
+            uint32_t mb[kBucketGroup];   // kBits: the raw mask byte; the bit is taken in the add loop, as k_resolve_bits does
+#pragma unroll
+            for (uint32_t c = 0; c < kBucketGroup; ++c) {
+                const uint32_t sl = min(s[c], n - 1u);
+                const size_t ri = (size_t)sl * np;
+                mb[c] = kBits ? (uint32_t)bp[(size_t)(sl >> 3) * np] : 0u;
+                r[c] = rp[ri]; g[c] = rp[plane + ri]; b[c] = rp[2 * plane + ri];
+            }
+#pragma unroll
+            for (uint32_t c = 0; c < kBucketGroup; ++c) {
+                const bool live = s[c] < n;
+                const bool marked = live && (kBits ? ((mb[c] >> (s[c] & 7u)) & 1u) != 0u : s[c] >= first);
+                if (marked) sum[c] = sum[c] + mk3(r[c], g[c], b[c]);
+                if (live) s[c] += K;
+                if (s[c] >= n) pending &= ~(1u << c);
+            }
+        };
+        if (pending != 0u) round();
+        while (pending != 0u) round();
+#pragma unroll
+        for (uint32_t c = 0; c < kBucketGroup; ++c)
+            if ((touched >> c) & 1u) {
+                float* bj = buckets + (size_t)(j0 + c) * bucket_plane + 3 * (size_t)lp;
+                bj[0] = sum[c].x; bj[1] = sum[c].y; bj[2] = sum[c].z;
+            }
+    }
+}
+
 // film.rs:91: color / weight_sum  (Color / f32 = Color * (1/f32))
 __global__ void __launch_bounds__(256) k_finish(RenderCtx rc, float* out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -177,6 +254,88 @@ __global__ void __launch_bounds__(256) k_film_read_counts(uint32_t what, uint32_
     if (what == SPT_FILM_MEAN) { out[i] = m; return; }
     if (n == 1u) { out[i] = __builtin_huge_valf(); return; }
     out[i] = film_var_of_mean(m, sum_sq[i], inv_n, inv[n - 1u]);
+}
+
+// spt_film_read_robust: the median of the bucket means (SPT_ROBUST_MON) or their Gini-adaptive trimmed mean (SPT_ROBUST_GMON) of
+// a bucketed film, one lane per float (pixel and channel); the arithmetic is spelled out in spt_abi.h and every operation below
+// is one rounded f32 operation in that order.  The keys live in a fixed array of kMaxBuckets registers whose slots from K on hold
+// +inf: every index is a compile-time one (the loops are unrolled, K only enters as a predicate), and the sorting network -
+// odd-even transposition, kMaxBuckets rounds of compare and select - leaves the K keys in a[0 .. K - 1] in ascending order,
+// because nothing sorts behind a +inf.  A key is never a NaN nor -0, so the order is total and the sorted keys are unique.
+// The film covers [first, first + n) at the pixel: n = done (kCounts: while the pixel is active, else counts[px]), and bucket j
+// holds n_j = c(first + n) - c(first) samples with c(x) = x / K + (x % K > j), integer arithmetic.  The reciprocals come from the
+// host's table inv[k] = 1.0f / (float)k, k = 0 .. spp; kf = (float)K, gk = (float)(K + 1) / (float)K and hf = (float)((K - 1) / 2)
+// are rounded by the host too.
+constexpr uint32_t kMaxBuckets = 15;
+
+template <bool kCounts>
+__global__ void __launch_bounds__(256) k_film_read_robust(uint32_t estimator, uint32_t n_floats, uint32_t K, const float* sum, const float* buckets,
+                                                          size_t bucket_plane, uint32_t first, uint32_t done, const uint8_t* mask,
+                                                          const uint32_t* counts, const float* inv, float kf, float gk, float hf, float* out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_floats) return;
+    uint32_t n = done;
+    if constexpr (kCounts) {
+        const uint32_t px = i / 3u;
+        n = mask[px] ? done : counts[px];
+    }
+    if (n < K) { out[i] = sum[i] * inv[n]; return; }   // some bucket is empty: the plain mean
+    const uint32_t q0 = first / K, r0 = first % K, q1 = (first + n) / K, r1 = (first + n) % K;
+    // All loads first, without a branch between them.  n_j is d - 1, d or d + 1 with d = q1 - q0 (n >= K, so d >= 1), so three
+    // reciprocals of the table serve every bucket (the index d + 1 is clamped to n: n_j <= n); a slot from K on reads bucket
+    // K - 1 once more and its value is not used.  kMaxBuckets + 3 loads are requested together, the keys come after one wait.
+    const uint32_t d = q1 - q0;
+    float r_lo = inv[d - 1u], r_mid = inv[d], r_hi = inv[min(d + 1u, n)];
+    float a[kMaxBuckets], bsum[kMaxBuckets];
+#pragma unroll
+    for (uint32_t j = 0; j < kMaxBuckets; ++j) bsum[j] = buckets[(size_t)min(j, K - 1u) * bucket_plane + i];
+    // (one empty statement that names every loaded value: the scheduler otherwise holds some of the loads back until earlier
+    //  ones have been consumed, four dependent round trips instead of one)
+    asm volatile("" : "+v"(bsum[0]), "+v"(bsum[1]), "+v"(bsum[2]), "+v"(bsum[3]), "+v"(bsum[4]), "+v"(bsum[5]), "+v"(bsum[6]), "+v"(bsum[7]),
+                      "+v"(bsum[8]), "+v"(bsum[9]), "+v"(bsum[10]), "+v"(bsum[11]), "+v"(bsum[12]), "+v"(bsum[13]), "+v"(bsum[14]));
+    static_assert(kMaxBuckets == 15, "the statement above names 15 values");
+#pragma unroll
+    for (uint32_t j = 0; j < kMaxBuckets; ++j) {
+        const uint32_t up = r1 > j ? 1u : 0u, down = r0 > j ? 1u : 0u;   // n_j = d + up - down
+        const float rcp = up == down ? r_mid : (up != 0u ? r_hi : r_lo);
+        const float mu = bsum[j] * rcp;
+        a[j] = (j < K && spt_is_finite(mu)) ? mu + 0.0f : __builtin_huge_valf();
+    }
+#pragma unroll
+    for (uint32_t round = 0; round < kMaxBuckets; ++round) {
+#pragma unroll
+        for (uint32_t j = round & 1u; j + 1u < kMaxBuckets; j += 2u) {
+            const float lo = a[j], hi = a[j + 1u];
+            const bool swap = hi < lo;
+            a[j] = swap ? hi : lo;
+            a[j + 1u] = swap ? lo : hi;
+        }
+    }
+    const uint32_t h = (K - 1u) / 2u;
+    uint32_t t = h;
+    if (estimator == SPT_ROBUST_GMON) {
+        float num = 0.0f, den = 0.0f, top = 0.0f;
+#pragma unroll
+        for (uint32_t j = 0; j < kMaxBuckets; ++j)
+            if (j < K) {
+                num = num + (float)(j + 1u) * a[j];
+                den = den + a[j];
+                top = a[j];
+            }
+        if (top != __builtin_huge_valf()) {   // (a key is finite or +inf)
+            t = 0u;
+            if (den > 0.0f) {
+                const float G = (2.0f * num) / (kf * den) - gk;
+                if (G > 0.0f) t = (G * hf >= hf) ? h : (uint32_t)(G * hf);
+            }
+        }
+    }
+    float acc = 0.0f;
+#pragma unroll
+    for (uint32_t j = 0; j < kMaxBuckets; ++j)
+        if (j >= t && j + t < K) acc = acc + a[j];
+    // MON (and t == h): the one key a[h], which the sum above holds exactly (0 + a is a: no key is -0) and inv[1] is 1
+    out[i] = acc * inv[K - 2u * t];
 }
 
 // spt_film_adapt: one 256-lane block per 16x16 tile of the shard, k_primary's numbering (tile = tx + tiles_x * ty over the packed

@@ -70,6 +70,10 @@ struct DeviceBuffer {   // owning: freed with the scene object (the owner select
         p = nullptr;
         bytes = 0;
     }
+    void swap(DeviceBuffer& o) {
+        std::swap(p, o.p);
+        std::swap(bytes, o.bytes);
+    }
     template <class T>
     void upload(const T* src, size_t count) {
         alloc(std::max<size_t>(count * sizeof(T), 16));
@@ -510,6 +514,9 @@ struct BezierLib {
     decltype(&spt_film_adapt) film_adapt = nullptr;
     decltype(&spt_film_read_counts) film_read_counts = nullptr;
     decltype(&spt_film_denoise) film_denoise = nullptr;
+    decltype(&spt_film_buckets) film_buckets = nullptr;
+    decltype(&spt_film_read_buckets) film_read_buckets = nullptr;
+    decltype(&spt_film_read_robust) film_read_robust = nullptr;
     decltype(&spt_trace_closest) trace_closest = nullptr;
     decltype(&spt_trace_any) trace_any = nullptr;
     decltype(&spt_debug_bxdf) debug_bxdf = nullptr;
@@ -609,6 +616,10 @@ struct spt_film {
     uint32_t active = 0, active_tiles = 0;
     // spt_film_denoise's workspace, made by its first call: two colour arrays (ping-pong) and the guide array, one float4 per pixel
     DeviceBuffer dn_color[2], dn_guide;
+    // bucket sums (spt_film_buckets): n_buckets planes of rows * width * 3 f32, and the reciprocal table of the robust read-outs
+    uint32_t n_buckets = 0;           // K; 0: a film without buckets
+    DeviceBuffer buckets;             // B_j, j = 0 .. K - 1
+    DeviceBuffer b_inv;               // (spp + 1) f32: inv[k] = 1.0f / (float)k as the host rounds it (inv[0] = 0, never read)
 };
 
 namespace {
@@ -835,7 +846,8 @@ const BezierLib* bezier_lib() {
                          sym(lib.render_wait, "spt_render_wait") && sym(lib.film_create, "spt_film_create") && sym(lib.film_render, "spt_film_render") &&
                          sym(lib.film_samples, "spt_film_samples") && sym(lib.film_read, "spt_film_read") && sym(lib.film_destroy, "spt_film_destroy") &&
                          sym(lib.film_adapt, "spt_film_adapt") && sym(lib.film_read_counts, "spt_film_read_counts") &&
-                         sym(lib.film_denoise, "spt_film_denoise") &&
+                         sym(lib.film_denoise, "spt_film_denoise") && sym(lib.film_buckets, "spt_film_buckets") &&
+                         sym(lib.film_read_buckets, "spt_film_read_buckets") && sym(lib.film_read_robust, "spt_film_read_robust") &&
                          sym(lib.trace_closest, "spt_trace_closest") && sym(lib.trace_any, "spt_trace_any") && sym(lib.debug_bxdf, "spt_debug_bxdf") &&
                          sym(lib.last_error, "spt_last_error") && sym(version, "spt_abi_version");
         if (!all || version() != SPT_ABI_VERSION) {
@@ -1494,6 +1506,10 @@ struct SampleTarget {
     // an adaptive film (spt_film_adapt): only its active pixels are traced (k_primary*<..., kMask>); null: every pixel
     FilmMask mask{nullptr, nullptr};
     uint32_t mask_tiles = 0;  // tiles with an active pixel after the last adapt: what the primary chunk count is sized for
+    // a bucketed film (spt_film_buckets): its K bucket sums, `bucket_plane` floats apart (k_resolve_buckets); null: none
+    float* buckets = nullptr;
+    uint32_t n_buckets = 0;
+    size_t bucket_plane = 0;
 };
 
 // One call of the render loop: its plan, the kernel choices made once per call (run_setup), the profiling spans and the
@@ -1918,7 +1934,8 @@ bool primary_pass(const RenderRun& run, RenderCtx& rc, const SampleTarget& tgt, 
     // collect: every sample owns a slot, which is what the chunked kernel does.  Moments of a scene with an environment: the
     // un-chunked kernel adds the misses before a pixel's first hit straight into its sum, past k_resolve<true>'s Q
     // An adaptive film takes the chunked path only (its masked instances), whatever the chunk count.
-    const bool all_slots = collect || (tgt.sq != nullptr && sc->d.env_w != 0u) || tgt.mask.pixel != nullptr;
+    // Buckets of a scene with an environment: the same, those misses would pass k_resolve_buckets.
+    const bool all_slots = collect || ((tgt.sq != nullptr || tgt.buckets != nullptr) && sc->d.env_w != 0u) || tgt.mask.pixel != nullptr;
     const bool chunked = rc.primary_chunks > 1u || all_slots;
     rc.slot_bits = chunked ? sc->slot_bits.as<uint8_t>() : nullptr;
     if (tgt.mask.pixel != nullptr) {
@@ -2037,6 +2054,14 @@ void launch_resolve(const RenderRun& run, const RenderCtx& rc, float* sq) {
     }
 }
 
+// The bucket sums of a bucketed film, after the resolve of the same pass: the same slots once more, every sample into the bucket of
+// its plan index
+void launch_resolve_buckets(const RenderRun& run, const RenderCtx& rc, const SampleTarget& tgt) {
+    const dim3 grid(rc.n_tiles), block(kBlock);
+    void (*const fn)(RenderCtx, uint32_t, float*, size_t) = rc.slot_bits ? k_resolve_buckets<true> : k_resolve_buckets<false>;
+    hipLaunchKernelGGL(fn, grid, block, 0, run.st, rc, tgt.n_buckets, tgt.buckets, tgt.bucket_plane);
+}
+
 // The pass counters of one pass into the call's statistics; the vertices of bounce 1 become the scene's tail-loop hint
 void read_counters(RenderRun& run, const RenderCtx& rc, size_t counts_words) {
     const uint32_t max_depth = run.params->max_depth;
@@ -2114,6 +2139,7 @@ RenderCtx trace_window(RenderRun& run, uint32_t row_base, uint32_t rows, uint32_
         if (!collect) {
             run.begin(SPT_K_RESOLVE);
             launch_resolve(run, rc, tgt.sq);
+            if (tgt.buckets != nullptr) launch_resolve_buckets(run, rc, tgt);
             run.end();
         }
         if (run.stats) read_counters(run, rc, ps.counts_words);
@@ -2366,6 +2392,11 @@ spt_status spt_film_render(spt_film* f, uint32_t n_samples) {
                 inc.mask = FilmMask{f->mask.as<uint8_t>(), f->tile_active.as<uint32_t>()};
                 inc.mask_tiles = f->active_tiles;
             }
+            if (f->n_buckets != 0u) {
+                inc.buckets = f->buckets.as<float>();
+                inc.n_buckets = f->n_buckets;
+                inc.bucket_plane = (size_t)f->rows * p.width * 3;
+            }
             (void)trace_window(run, 0, f->rows, p.shard_index, shard_count, strip_rows, false, inc);
             HIP_CHECK(hipGetLastError());
             HIP_CHECK(hipStreamSynchronize(run.st));
@@ -2594,6 +2625,88 @@ spt_status spt_film_denoise(spt_film* f, spt_film* guide, const spt_denoise_para
             HIP_CHECK(hipGetLastError());
         }
         HIP_CHECK(hipMemcpyAsync(out, f->out.p, out_bytes, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        return SPT_OK;
+    });
+}
+
+spt_status spt_film_buckets(spt_film* f, uint32_t n_buckets) {
+    if (!f) { g_error = "film_buckets: null argument"; return SPT_ERR_INVALID_ARG; }
+    if (f->fwd) return forwarded(f->fwd, f->fwd->film_buckets(f->inner, n_buckets));
+    spt_scene* sc = f->sc;
+    std::lock_guard<std::mutex> lock(sc->mu);
+    return guarded("film_buckets", [&] {
+        const spt_render_params& p = f->plan;
+        // every check comes before the first change: a refused call leaves the film as it was
+        if (n_buckets < 3u || n_buckets > kMaxBuckets || (n_buckets & 1u) == 0u)
+            fail(SPT_ERR_INVALID_ARG, "film_buckets: n_buckets must be odd and 3 .. 15 (got " + std::to_string(n_buckets) + ")");
+        if (f->n_buckets != 0u) fail(SPT_ERR_INVALID_ARG, "film_buckets: the film already has buckets");
+        if (f->done != 0u) fail(SPT_ERR_INVALID_ARG, "film_buckets: the film already covers samples (buckets start with the film)");
+        if (f->radius != 0.5f) fail(SPT_ERR_UNSUPPORTED, "film_buckets: needs the box radius 0.5 (every sample of the pixel weighs 1)");
+        HIP_CHECK(hipSetDevice(sc->device));
+        const hipStream_t st = sc->stream;
+        const size_t bytes = (size_t)n_buckets * f->rows * p.width * 3 * sizeof(float);
+        DeviceBuffer buckets, inv_dev;   // the film gets them once everything has worked
+        std::vector<float> inv((size_t)p.spp + 1, 0.0f);
+        for (uint32_t k = 1; k <= p.spp; ++k) inv[k] = 1.0f / (float)k;
+        if (bytes != 0) {
+            buckets.alloc(bytes);
+            HIP_CHECK(hipMemsetAsync(buckets.p, 0, bytes, st));
+        }
+        inv_dev.alloc(inv.size() * sizeof(float));
+        HIP_CHECK(hipMemcpyAsync(inv_dev.p, inv.data(), inv.size() * sizeof(float), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipStreamSynchronize(st));   // `inv` is pageable
+        f->buckets.swap(buckets);
+        f->b_inv.swap(inv_dev);
+        f->n_buckets = n_buckets;
+        return SPT_OK;
+    });
+}
+
+spt_status spt_film_read_buckets(spt_film* f, float* out) {
+    if (!f || !out) { g_error = "film_read_buckets: null argument"; return SPT_ERR_INVALID_ARG; }
+    if (f->fwd) return forwarded(f->fwd, f->fwd->film_read_buckets(f->inner, out));
+    spt_scene* sc = f->sc;
+    std::lock_guard<std::mutex> lock(sc->mu);
+    return guarded("film_read_buckets", [&] {
+        if (f->n_buckets == 0u) fail(SPT_ERR_INVALID_ARG, "film_read_buckets: the film has no buckets (spt_film_buckets)");
+        const size_t bytes = (size_t)f->n_buckets * f->rows * f->plan.width * 3 * sizeof(float);
+        if (bytes == 0) return SPT_OK;
+        HIP_CHECK(hipSetDevice(sc->device));
+        HIP_CHECK(hipMemcpyAsync(out, f->buckets.p, bytes, hipMemcpyDeviceToHost, sc->stream));
+        HIP_CHECK(hipStreamSynchronize(sc->stream));
+        return SPT_OK;
+    });
+}
+
+spt_status spt_film_read_robust(spt_film* f, uint32_t estimator, float* out) {
+    if (!f || !out) { g_error = "film_read_robust: null argument"; return SPT_ERR_INVALID_ARG; }
+    if (f->fwd) return forwarded(f->fwd, f->fwd->film_read_robust(f->inner, estimator, out));
+    spt_scene* sc = f->sc;
+    std::lock_guard<std::mutex> lock(sc->mu);
+    return guarded("film_read_robust", [&] {
+        const spt_render_params& p = f->plan;
+        if (f->n_buckets == 0u) fail(SPT_ERR_INVALID_ARG, "film_read_robust: the film has no buckets (spt_film_buckets)");
+        if (estimator > SPT_ROBUST_GMON) fail(SPT_ERR_INVALID_ARG, "film_read_robust: unknown SPT_ROBUST_* value");
+        if (f->done == 0) fail(SPT_ERR_INVALID_ARG, "film_read_robust: the film covers no samples yet");
+        if (f->rows == 0 || p.width == 0) return SPT_OK;
+        const uint32_t n_pix = f->rows * p.width, K = f->n_buckets;
+        const size_t bytes = (size_t)n_pix * 3 * sizeof(float);
+        HIP_CHECK(hipSetDevice(sc->device));
+        const hipStream_t st = sc->stream;
+        f->out.ensure(bytes);
+        const float kf = (float)K, gk = (float)(K + 1u) / (float)K, hf = (float)((K - 1u) / 2u);
+        const dim3 grid((n_pix * 3 + kBlock - 1) / kBlock), block(kBlock);
+        if (f->adaptive)
+            hipLaunchKernelGGL(k_film_read_robust<true>, grid, block, 0, st, estimator, n_pix * 3u, K, f->sum.as<float>(), f->buckets.as<float>(),
+                               (size_t)n_pix * 3, f->first, f->done, f->mask.as<uint8_t>(), f->counts.as<uint32_t>(), f->b_inv.as<float>(), kf, gk, hf,
+                               f->out.as<float>());
+        else
+            hipLaunchKernelGGL(k_film_read_robust<false>, grid, block, 0, st, estimator, n_pix * 3u, K, f->sum.as<float>(), f->buckets.as<float>(),
+                               (size_t)n_pix * 3, f->first, f->done, (const uint8_t*)nullptr, (const uint32_t*)nullptr, f->b_inv.as<float>(), kf, gk, hf,
+                               f->out.as<float>());
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(out, f->out.p, bytes, hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
         return SPT_OK;
     });

@@ -577,6 +577,11 @@ spt_status spt_debug_detmath(int32_t device, uint32_t fn, uint32_t n, const floa
 spt_status spt_debug_bxdf(const spt_scene* scene, int32_t device, const spt_material* mt, uint32_t op, uint32_t n, const float* wo,
                           const float* wi_in, const uint64_t* rng_state, float* wi_out, float* f_out, float* pdf_out, int32_t* dir_out);
 
+/* Test seam (additive to ABI v14): how the scene's renders were scheduled since it was created.
+ *   what 0  passes whose resolve was queued on the film stream (the overlapped schedule of an SPT_RENDER_ASYNC spt_render)
+ *   what 1  passes that took the single-stream path (every other render, spt_film_render, SPT_NO_FILM_STREAM=1) */
+spt_status spt_debug_render_info(const spt_scene* scene, uint32_t what, uint64_t* out);
+
 const char* spt_last_error(void);
 uint32_t spt_abi_version(void);
 

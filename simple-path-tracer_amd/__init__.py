@@ -307,6 +307,8 @@ def hip_lib() -> C.CDLL:
         lib.spt_debug_detmath.argtypes = [C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.spt_debug_bxdf.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Material), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(lib, "spt_debug_render_info"):   # (the same)
+            lib.spt_debug_render_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
         _hip_lib = lib
     return _hip_lib
 
@@ -433,6 +435,12 @@ class DeviceScene:
         occ = np.zeros(rays.shape[0], dtype=np.uint8)
         _check_hip(hip_lib().spt_trace_any(self._h, rays.shape[0], rays.ctypes.data, occ.ctypes.data))
         return occ
+
+    def render_info(self, what: int) -> int:
+        """Test seam (spt_debug_render_info): 0 passes resolved on the film stream, 1 passes on the single-stream path."""
+        v = C.c_uint64(0)
+        _check_hip(hip_lib().spt_debug_render_info(self._h, what, C.byref(v)))
+        return int(v.value)
 
     def close(self) -> None:
         # an asynchronous frame may still be copying into one of the pinned film buffers: the scene goes first (its destroy

@@ -520,6 +520,7 @@ struct BezierLib {
     decltype(&spt_trace_closest) trace_closest = nullptr;
     decltype(&spt_trace_any) trace_any = nullptr;
     decltype(&spt_debug_bxdf) debug_bxdf = nullptr;
+    decltype(&spt_debug_render_info) debug_render_info = nullptr;
     decltype(&spt_last_error) last_error = nullptr;
 };
 
@@ -530,9 +531,21 @@ struct spt_scene {
     hipStream_t stream = nullptr;
     hipStream_t stream2 = nullptr;            // side stream: k_shadow(b) next to k_extend(b) (see bounce)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    hipStream_t stream_copy = nullptr;        // SPT_RENDER_ASYNC: the film's D2H copy, next to the following render's kernels
+    // SPT_RENDER_ASYNC: the film stream.  It carries the film's D2H copy next to the following render's kernels and, on the
+    // overlapped schedule (trace_window), the tail-loop shade launch, the resolve and the finish kernel of every pass next
+    // to the following pass's k_primary.  (No fourth stream: a process gets four hardware queues, the null stream included.)
+    hipStream_t stream_film = nullptr;
     hipEvent_t ev_out_ready = nullptr, ev_copy_done = nullptr;
     bool copy_pending = false;                // an asynchronous copy-out of `out` may still be in flight
+    // the overlapped schedule, per set of doubled pass buffers (consecutive passes alternate between the sets): "the main stream has finished its part
+    // of the pass" and "the film stream has finished the pass"; ev_film_idle: everything queued on the film stream so far
+    hipEvent_t ev_main[2] = {nullptr, nullptr}, ev_film[2] = {nullptr, nullptr}, ev_film_idle = nullptr;
+    bool film_recorded[2] = {false, false};   // ev_film[k] has been recorded: the set may still be read by the film stream
+    uint32_t next_set = 0;                    // the set the next overlapped pass takes: they alternate from pass to pass, across renders too
+    int tail_set = -1;                        // >= 0: ev_film[tail_set] covers a tail-loop launch that may still read qb / hit_*_next
+    bool film_pending = false;                // the main stream is not yet behind the film-stream kernels of an overlapped render (film_join)
+    bool film_inflight = false;               // ... and the host has not waited for them since (grow)
+    uint64_t passes_film = 0, passes_single = 0;   // spt_debug_render_info: passes resolved on the film stream / on the main stream
     bool bez_newton = false;                  // some patch asks for Newton's iteration (the pair kernel only clips)
     // what the last pass with a counter readback saw at bounce 1 (path vertices in all shards); ~0: never seen.  A hint
     // only: it picks between two kernels that compute the same film (k_shade's kLoop)
@@ -544,7 +557,9 @@ struct spt_scene {
     bool swalk = false;     // the streaming walker's tables (stream.h) were built: k_*_stream serve the scene
     size_t lds_bytes = 0;   // dynamic LDS per 256-thread block: traversal stack (+ geometry)
     // render workspace (grown on demand, reused between calls)
-    DeviceBuffer qa[5], qb[5], hit_f4, hit_inst, hit_f4_next, hit_inst_next, sh[3], counts, rad, film, first_slot, slot_bits, out;
+    // (counts, rad, first_slot, slot_bits: what the film stream reads of pass p while the main stream writes pass p + 1; set 1
+    //  is made by the first overlapped render)
+    DeviceBuffer qa[5], qb[5], hit_f4, hit_inst, hit_f4_next, hit_inst_next, sh[3], counts[2], rad[2], film, first_slot[2], slot_bits[2], out;
     DeviceBuffer trace_in, trace_out, visits, inst_class;
     std::mutex mu;
     double bs_center[3] = {0, 0, 0}, bs_radius = 0;  // bounding sphere of all instance boxes
@@ -585,7 +600,9 @@ struct spt_scene {
         if (ev_join) (void)hipEventDestroy(ev_join);
         if (ev_out_ready) (void)hipEventDestroy(ev_out_ready);
         if (ev_copy_done) (void)hipEventDestroy(ev_copy_done);
-        if (stream_copy) (void)hipStreamDestroy(stream_copy);
+        for (auto e : {ev_main[0], ev_main[1], ev_film[0], ev_film[1], ev_film_idle})
+            if (e) (void)hipEventDestroy(e);
+        if (stream_film) (void)hipStreamDestroy(stream_film);
         if (stream2) (void)hipStreamDestroy(stream2);
         if (stream) (void)hipStreamDestroy(stream);
     }
@@ -849,6 +866,7 @@ const BezierLib* bezier_lib() {
                          sym(lib.film_denoise, "spt_film_denoise") && sym(lib.film_buckets, "spt_film_buckets") &&
                          sym(lib.film_read_buckets, "spt_film_read_buckets") && sym(lib.film_read_robust, "spt_film_read_robust") &&
                          sym(lib.trace_closest, "spt_trace_closest") && sym(lib.trace_any, "spt_trace_any") && sym(lib.debug_bxdf, "spt_debug_bxdf") &&
+                         sym(lib.debug_render_info, "spt_debug_render_info") &&
                          sym(lib.last_error, "spt_last_error") && sym(version, "spt_abi_version");
         if (!all || version() != SPT_ABI_VERSION) {
             err = path + " does not export ABI version " + std::to_string(SPT_ABI_VERSION);
@@ -935,7 +953,9 @@ spt_status spt_scene_create(const spt_scene_desc* desc, int32_t device, spt_scen
         sc->device = device;
         HIP_CHECK(hipStreamCreateWithFlags(&sc->stream, hipStreamNonBlocking));
         HIP_CHECK(hipStreamCreateWithFlags(&sc->stream2, hipStreamNonBlocking));
-        HIP_CHECK(hipStreamCreateWithFlags(&sc->stream_copy, hipStreamNonBlocking));
+        HIP_CHECK(hipStreamCreateWithFlags(&sc->stream_film, hipStreamNonBlocking));
+        for (hipEvent_t* e : {&sc->ev_main[0], &sc->ev_main[1], &sc->ev_film[0], &sc->ev_film[1], &sc->ev_film_idle})
+            HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
         HIP_CHECK(hipEventCreateWithFlags(&sc->ev_out_ready, hipEventDisableTiming));
         HIP_CHECK(hipEventCreateWithFlags(&sc->ev_copy_done, hipEventDisableTiming));
         HIP_CHECK(hipEventCreateWithFlags(&sc->ev_fork, hipEventDisableTiming));
@@ -1429,7 +1449,7 @@ void spt_scene_destroy(spt_scene* scene) {
     if (!scene) return;
     (void)hipSetDevice(scene->device);
     (void)hipStreamSynchronize(scene->stream);
-    if (scene->stream_copy) (void)hipStreamSynchronize(scene->stream_copy);
+    if (scene->stream_film) (void)hipStreamSynchronize(scene->stream_film);
     // every DeviceBuffer member frees itself (a list here used to miss the buffers added later)
     delete scene;
 }
@@ -1529,6 +1549,8 @@ struct RenderRun {
     bool pixel_cull = false, row_spans = false;   // k_primary's screen-space rectangle, and the per-row spans inside it
     bool stream_p = false, stream_s = false, stream_e = false;   // the streaming walker serves primary / shadow / extension rays
     bool resolve32 = false;      // k_resolve_bits<32u> instead of <16u>
+    bool film_stream = false;    // the overlapped schedule is allowed (no SPT_NO_FILM_STREAM)
+    bool film_overlap = false;   // ... and this render takes it: tail launch, resolve, finish and copy-out on the film stream
     bool debug_spans = false;    // per-launch HIP-event times on stderr (profile mode)
     uint32_t primary_chunks = 0;   // sample chunks per primary tile; 0: sized to the busy tiles
     uint64_t box_band_bytes = 0;   // kept radiance per band of a wide box filter
@@ -1613,6 +1635,7 @@ void run_setup(RenderRun& run) {
     run.row_spans = run.pixel_cull && std::getenv("SPT_NO_ROW_SPANS") == nullptr;
     if (const char* v = std::getenv("SPT_PRIMARY_CHUNKS")) run.primary_chunks = (uint32_t)std::max(1, std::atoi(v));
     run.resolve32 = env_u32("SPT_RESOLVE_BATCH", 16u) == 32u;
+    run.film_stream = env_u32("SPT_NO_FILM_STREAM", 0u) == 0u;
     run.box_band_bytes = 8ull << 30;
     if (const char* v = std::getenv("SPT_BOX_BAND_BYTES")) run.box_band_bytes = std::max<uint64_t>(1, std::strtoull(v, nullptr, 10));
     run.debug_spans = std::getenv("SPT_DEBUG_SPANS") != nullptr;
@@ -1750,6 +1773,31 @@ RenderCtx plan_ctx(const spt_render_params& p, const spt_camera& cam, uint32_t r
     return rc;
 }
 
+// Every entry point that queues work on sc->stream and is not the overlapped schedule itself starts here: the main stream
+// waits for whatever an overlapped render left on the film stream (the scene's lock is held, its device selected).
+void film_join(spt_scene* sc) {
+    if (!sc->film_pending) return;
+    HIP_CHECK(hipEventRecord(sc->ev_film_idle, sc->stream_film));
+    HIP_CHECK(hipStreamWaitEvent(sc->stream, sc->ev_film_idle, 0));
+    sc->film_pending = false;
+    sc->film_recorded[0] = sc->film_recorded[1] = false;   // (the main stream is behind both sets' film-stream work now)
+    sc->tail_set = -1;
+}
+
+// Grows a workspace buffer (or `out`).  The old allocation may still be in use by an overlapped render on either stream:
+// both are drained first (growth is rare: the first render of a size).
+void grow(spt_scene* sc, DeviceBuffer& b, size_t n) {
+    if (n <= b.bytes) return;
+    if (sc->film_inflight) {
+        HIP_CHECK(hipStreamSynchronize(sc->stream));
+        HIP_CHECK(hipStreamSynchronize(sc->stream_film));
+        sc->film_inflight = sc->film_pending = sc->copy_pending = false;
+        sc->film_recorded[0] = sc->film_recorded[1] = false;
+        sc->tail_set = -1;
+    }
+    b.alloc(n);
+}
+
 // The passes of one window: their size, and the queues and counters they use.
 struct PassShape {
     uint32_t spp_pass;       // samples per pass
@@ -1791,36 +1839,52 @@ PassShape grow_workspace(spt_scene* sc, const spt_render_params& p, uint32_t n_s
     // the hit queue is binned by BxDF class for the general shade kernels (kernels.h, kClasses): class c lives c * cap
     // entries further.  Memory is what MI355X has (24 B x cap x 8 classes = 26 GB for a 128 M-sample pass)
     const uint32_t n_classes = (!fused && p.max_depth > 1 && cap * (uint64_t)kClasses <= 0xffffffffull && class_queues) ? kClasses : 1u;
-    for (int k = 0; k < 4; ++k) { sc->qa[k].ensure(cap * 16 * (k == 1 ? n_classes : 1u)); sc->qb[k].ensure(cap * 16); }   // (qa[1]: the compact bounce-0 records sit at their hit's index, in every class)
-    sc->qa[4].ensure(cap * 8);
-    sc->qb[4].ensure(cap * 8);
-    sc->hit_f4.ensure(cap * 16 * n_classes);
-    sc->hit_inst.ensure(cap * 8 * n_classes);
+    for (int k = 0; k < 4; ++k) { grow(sc, sc->qa[k], cap * 16 * (k == 1 ? n_classes : 1u)); grow(sc, sc->qb[k], cap * 16); }   // (qa[1]: the compact bounce-0 records sit at their hit's index, in every class)
+    grow(sc, sc->qa[4], cap * 8);
+    grow(sc, sc->qb[4], cap * 8);
+    grow(sc, sc->hit_f4, cap * 16 * n_classes);
+    grow(sc, sc->hit_inst, cap * 8 * n_classes);
     if (fused) {
-        sc->hit_f4_next.ensure(cap * 16);
-        sc->hit_inst_next.ensure(cap * 8);
+        grow(sc, sc->hit_f4_next, cap * 16);
+        grow(sc, sc->hit_inst_next, cap * 8);
     }
-    for (int k = 0; k < 3; ++k) sc->sh[k].ensure(cap * 16);
+    for (int k = 0; k < 3; ++k) grow(sc, sc->sh[k], cap * 16);
     ps.counts_words = (size_t)(p.max_depth + 1) * Q_KINDS * kShards * 32;
-    sc->counts.ensure(ps.counts_words * sizeof(uint32_t));
-    sc->rad.ensure((size_t)ps.rad_slots * 3 * sizeof(float));
-    float* const film_sum = sum ? sum : (sc->film.ensure((size_t)n_pix * 3 * sizeof(float)), sc->film.as<float>());
-    sc->first_slot.ensure((size_t)n_pix * sizeof(uint32_t));
-    sc->slot_bits.ensure((size_t)n_pix * ((ps.spp_pass + 7u) / 8u));
+    grow(sc, sc->counts[0], ps.counts_words * sizeof(uint32_t));
+    grow(sc, sc->rad[0], (size_t)ps.rad_slots * 3 * sizeof(float));
+    float* const film_sum = sum ? sum : (grow(sc, sc->film, (size_t)n_pix * 3 * sizeof(float)), sc->film.as<float>());
+    grow(sc, sc->first_slot[0], (size_t)n_pix * sizeof(uint32_t));
+    grow(sc, sc->slot_bits[0], (size_t)n_pix * ((ps.spp_pass + 7u) / 8u));
 
     rc.qa = PathQueue{sc->qa[0].as<float4>(), sc->qa[1].as<float4>(), sc->qa[2].as<float4>(), sc->qa[3].as<float4>(), sc->qa[4].as<uint2>()};
     rc.qb = PathQueue{sc->qb[0].as<float4>(), sc->qb[1].as<float4>(), sc->qb[2].as<float4>(), sc->qb[3].as<float4>(), sc->qb[4].as<uint2>()};
     rc.hits = HitQueue{sc->hit_f4.as<float4>(), sc->hit_inst.as<uint2>()};
     rc.hits_next = HitQueue{sc->hit_f4_next.as<float4>(), sc->hit_inst_next.as<uint2>()};
     rc.shadow = ShadowQueue{sc->sh[0].as<float4>(), sc->sh[1].as<float4>(), sc->sh[2].as<float4>()};
-    rc.counts = sc->counts.as<uint32_t>();
+    rc.counts = sc->counts[0].as<uint32_t>();
     rc.shard_cap = (uint32_t)shard_cap64;
     rc.n_classes = n_classes;
     rc.class_cap = (uint32_t)cap;
-    rc.rad = sc->rad.as<float>();
+    rc.rad = sc->rad[0].as<float>();
     rc.film = film_sum;
-    rc.first_slot = sc->first_slot.as<uint32_t>();
+    rc.first_slot = sc->first_slot[0].as<uint32_t>();
     return ps;
+}
+
+// The second set of the doubled pass buffers, sized like the first (grow_workspace).  False: no memory for it (the render
+// keeps the single-stream schedule).
+bool grow_second_set(spt_scene* sc) {
+    try {
+        grow(sc, sc->counts[1], sc->counts[0].bytes);
+        grow(sc, sc->rad[1], sc->rad[0].bytes);
+        grow(sc, sc->first_slot[1], sc->first_slot[0].bytes);
+        grow(sc, sc->slot_bits[1], sc->slot_bits[0].bytes);
+    } catch (const AbiError& e) {
+        if (e.code != SPT_ERR_OUT_OF_MEMORY) throw;
+        (void)hipGetLastError();
+        return false;
+    }
+    return true;
 }
 
 // k_primary's early-outs for the camera: the bounding sphere of the instances relative to the eye, and the rectangle of the
@@ -1920,7 +1984,7 @@ void launch_primary(const RenderRun& run, uint32_t blocks, const RenderCtx& rc, 
 
 // The sample chunks per tile and the primary kernel of one pass.  Returns whether the kernel was a chunked one (which
 // marks the samples that own a radiance slot in rc.slot_bits for the resolve).
-bool primary_pass(const RenderRun& run, RenderCtx& rc, const SampleTarget& tgt, uint32_t active_tiles, bool collect) {
+bool primary_pass(const RenderRun& run, RenderCtx& rc, const SampleTarget& tgt, uint32_t active_tiles, bool collect, uint8_t* slot_bits) {
     spt_scene* const sc = run.sc;
     // sample chunks per tile: aim at ~6144 busy workgroups (24 per CU; 4096 .. 8192 measured within 2 %) given the tiles inside the screen bound
     // (an adaptive film: the tiles its last adapt left active; chunking does not change bits)
@@ -1937,7 +2001,11 @@ bool primary_pass(const RenderRun& run, RenderCtx& rc, const SampleTarget& tgt, 
     // Buckets of a scene with an environment: the same, those misses would pass k_resolve_buckets.
     const bool all_slots = collect || ((tgt.sq != nullptr || tgt.buckets != nullptr) && sc->d.env_w != 0u) || tgt.mask.pixel != nullptr;
     const bool chunked = rc.primary_chunks > 1u || all_slots;
-    rc.slot_bits = chunked ? sc->slot_bits.as<uint8_t>() : nullptr;
+    rc.slot_bits = chunked ? slot_bits : nullptr;
+    if (!chunked && run.film_overlap) {   // the un-chunked kernel adds into rc.film itself: behind the film memset and every earlier resolve
+        HIP_CHECK(hipEventRecord(sc->ev_film_idle, sc->stream_film));
+        HIP_CHECK(hipStreamWaitEvent(run.st, sc->ev_film_idle, 0));
+    }
     if (tgt.mask.pixel != nullptr) {
         if (run.count) fail(SPT_ERR_INVALID_ARG, "render: an adaptive film does not count visits");
         launch_primary<true>(run, rc.n_tiles * rc.primary_chunks, rc, tgt.mask);
@@ -1997,7 +2065,14 @@ void launch_rays(const RenderRun& run, const RayKernels& k, bool stream, bool dy
 
 // One bounce of a pass: shade, then shadow and extension rays.  Returns true when the fused pipeline's tail loop took every
 // later bounce along.
-bool bounce(RenderRun& run, const RenderCtx& rc, uint32_t b) {
+// few vertices left after bounce 0 (seen by the previous pass with a counter readback): bounce 1 and
+// everything after it in ONE launch, each lane following its path to the end (k_shade's kLoop)
+bool takes_tail_loop(const RenderRun& run, uint32_t b) {
+    return run.fused && b == 1 && run.tail_loop && run.sc->tail_vertices <= kTailLoopBelow;
+}
+
+// `st`: the stream of the shade launch (the film stream for the tail-loop launch of the overlapped schedule, else run.st).
+bool bounce(RenderRun& run, const RenderCtx& rc, uint32_t b, hipStream_t st) {
     spt_scene* const sc = run.sc;
     const uint32_t max_depth = run.params->max_depth;
     // the fused kernel: shade + shadow + extend of this bounce in one kernel; vertices of bounce b live in (qa, hits) for even
@@ -2009,13 +2084,11 @@ bool bounce(RenderRun& run, const RenderCtx& rc, uint32_t b) {
         std::swap(ru.qa, ru.qb);
         if (run.fused) std::swap(ru.hits, ru.hits_next);
     }
-    // few vertices left after bounce 0 (seen by the previous pass with a counter readback): bounce 1 and
-    // everything after it in ONE launch, each lane following its path to the end (k_shade's kLoop)
-    const bool tail_loop = run.fused && b == 1 && run.tail_loop && sc->tail_vertices <= kTailLoopBelow;
+    const bool tail_loop = takes_tail_loop(run, b);
     // LDS: the traversal stack and geometry, also for the BSSRDF probe, which walks the BVH inside k_shade<3 | 5>
     const size_t shade_lds = (run.fused || run.tab || sc->has_probe) ? run.lds : 0;
     run.begin(b == 0 ? SPT_K_SHADE_FIRST : SPT_K_SHADE);
-    hipLaunchKernelGGL(shade_kernel(run, b, tail_loop), dim3(kPersistentBlocks), dim3(kBlock), shade_lds, run.st, sc->d, ru, b);
+    hipLaunchKernelGGL(shade_kernel(run, b, tail_loop), dim3(kPersistentBlocks), dim3(kBlock), shade_lds, st, sc->d, ru, b);
     run.end();
     if (run.fused) return tail_loop;
     // k_shadow(b) and k_extend(b) are independent unless the scene has an environment (then a missing
@@ -2043,14 +2116,14 @@ bool bounce(RenderRun& run, const RenderCtx& rc, uint32_t b) {
 
 // The resolve of a pass: k_resolve_bits after a chunked primary (rc.slot_bits), k_resolve after an un-chunked one; sq: the
 // sums of the squares too (SPT_FILM_MOMENTS)
-void launch_resolve(const RenderRun& run, const RenderCtx& rc, float* sq) {
+void launch_resolve(const RenderRun& run, const RenderCtx& rc, float* sq, hipStream_t st) {
     const dim3 grid(rc.n_tiles), block(kBlock);
     if (sq != nullptr) {
         void (*const fn)(RenderCtx, float*) = rc.slot_bits ? k_resolve_bits<16u, true, float*> : k_resolve<true, float*>;
-        hipLaunchKernelGGL(fn, grid, block, 0, run.st, rc, sq);
+        hipLaunchKernelGGL(fn, grid, block, 0, st, rc, sq);
     } else {
         void (*const fn)(RenderCtx) = rc.slot_bits ? (run.resolve32 ? k_resolve_bits<32u> : k_resolve_bits<16u>) : k_resolve<>;
-        hipLaunchKernelGGL(fn, grid, block, 0, run.st, rc);
+        hipLaunchKernelGGL(fn, grid, block, 0, st, rc);
     }
 }
 
@@ -2110,11 +2183,27 @@ RenderCtx trace_window(RenderRun& run, uint32_t row_base, uint32_t rows, uint32_
     rc.visits = sc->visits.as<unsigned long long>();
     rc.row_span = run.row_span_dev;
     const LiveCount live = count_live(sc, rc);
-    if (tgt.zero) {
-        HIP_CHECK(hipMemsetAsync(rc.film, 0, (size_t)n_pix * 3 * sizeof(float), run.st));
-        if (tgt.sq) HIP_CHECK(hipMemsetAsync(tgt.sq, 0, (size_t)n_pix * 3 * sizeof(float), run.st));
+    // The overlapped schedule (run.film_overlap, asked for by spt_render): the main stream traces pass p + 1 into one set of
+    // the doubled pass buffers while the film stream finishes pass p from the other - its tail-loop shade launch when that
+    // kernel is chosen, and its resolve.  Neither needs the vector ALU that k_primary keeps busy.  Without memory for the
+    // second set the render stays on the main stream.
+    if (run.film_overlap && !grow_second_set(sc)) {
+        run.film_overlap = false;
+        film_join(sc);
     }
-    if (collect) HIP_CHECK(hipMemsetAsync(sc->rad.p, 0, (size_t)ps.rad_slots * 3 * sizeof(float), run.st));   // pixels outside the screen bound write no slots
+    const bool ov = run.film_overlap;
+    const hipStream_t st_film = ov ? sc->stream_film : run.st;
+    if (ov) {
+        sc->film_pending = sc->film_inflight = true;
+        // the film stream starts behind what the main stream holds so far (an earlier single-stream render's use of the film)
+        HIP_CHECK(hipEventRecord(sc->ev_main[1], run.st));
+        HIP_CHECK(hipStreamWaitEvent(st_film, sc->ev_main[1], 0));
+    }
+    if (tgt.zero) {   // (overlapped: behind the previous frame's k_finish, ahead of this frame's first resolve, by stream order)
+        HIP_CHECK(hipMemsetAsync(rc.film, 0, (size_t)n_pix * 3 * sizeof(float), st_film));
+        if (tgt.sq) HIP_CHECK(hipMemsetAsync(tgt.sq, 0, (size_t)n_pix * 3 * sizeof(float), st_film));
+    }
+    if (collect) HIP_CHECK(hipMemsetAsync(sc->rad[0].p, 0, (size_t)ps.rad_slots * 3 * sizeof(float), run.st));   // pixels outside the screen bound write no slots
     bool chunked_any = false;
     // max_depth 0: `while curr_depth < self.max_depth` (pt.rs:48) never runs, every sample is black - environment included.
     // Nothing is traced: the film (and, for a wide box filter, the kept samples) stay at the zeros written above.  (The
@@ -2123,25 +2212,60 @@ RenderCtx trace_window(RenderRun& run, uint32_t row_base, uint32_t rows, uint32_
     // packed sample index of k_primary count from the pass's first sample, only the sampler sees the plan's index pass_first + s.
     const uint32_t s_end = tgt.first + tgt.count;
     for (uint32_t s0 = tgt.first; s0 < (p.max_depth == 0u ? tgt.first : s_end); s0 += ps.spp_pass) {
+        // (the sets alternate across renders too: a shard whose frame is ONE pass still traces beside the previous frame's resolve)
+        const uint32_t set = ov ? sc->next_set : 0u;
+        if (ov) sc->next_set ^= 1u;
+        rc.counts = sc->counts[set].as<uint32_t>();
+        rc.first_slot = sc->first_slot[set].as<uint32_t>();
+        // the film stream may still read this set: the pass before the previous one, of this render or an earlier one
+        if (ov && sc->film_recorded[set]) HIP_CHECK(hipStreamWaitEvent(run.st, sc->ev_film[set], 0));
         rc.pass_first = s0;
         rc.pass_samples = std::min(ps.spp_pass, s_end - s0);
         rc.rad_plane = collect ? (size_t)p.spp * n_pix : (size_t)rc.pass_samples * n_pix;
         rc.pack_first = (run.pack_first && rc.pass_samples <= 4096u) ? 1u : 0u;
-        rc.rad = sc->rad.as<float>() + (collect ? (size_t)(s0 - tgt.first) * n_pix : 0);
+        rc.rad = sc->rad[set].as<float>() + (collect ? (size_t)(s0 - tgt.first) * n_pix : 0);
         run.begin(SPT_K_OTHER);
         HIP_CHECK(hipMemsetAsync(rc.counts, 0, ps.counts_words * sizeof(uint32_t), run.st));
         run.end();
         run.begin(SPT_K_PRIMARY);
-        chunked_any |= primary_pass(run, rc, tgt, live.active_tiles, collect);
+        chunked_any |= primary_pass(run, rc, tgt, live.active_tiles, collect, sc->slot_bits[set].as<uint8_t>());
         run.end();
-        for (uint32_t b = 0; b < p.max_depth; ++b)
-            if (bounce(run, rc, b)) break;
+        bool handed_over = false;   // the film stream waits for the main stream's part of this pass
+        auto hand_over = [&] {
+            HIP_CHECK(hipEventRecord(sc->ev_main[set], run.st));
+            HIP_CHECK(hipStreamWaitEvent(st_film, sc->ev_main[set], 0));
+            handed_over = true;
+        };
+        bool tail_on_film = false;
+        for (uint32_t b = 0; b < p.max_depth; ++b) {
+            if (ov && takes_tail_loop(run, b)) {   // reads qb / hit_*_next and this set; the next k_primary writes neither
+                hand_over();
+                (void)bounce(run, rc, b, st_film);
+                tail_on_film = true;
+                break;
+            }
+            // bounce 0 writes qb / hit_*_next (un-fused: and the shadow queue), which a tail-loop launch still on the film
+            // stream reads; the later bounces of a pass without that launch ping-pong through the queues on the main stream
+            if (ov && b == 0u && sc->tail_set >= 0) {
+                HIP_CHECK(hipStreamWaitEvent(run.st, sc->ev_film[sc->tail_set], 0));
+                sc->tail_set = -1;
+            }
+            if (bounce(run, rc, b, run.st)) break;
+        }
         if (!collect) {
+            if (ov && !handed_over) hand_over();
             run.begin(SPT_K_RESOLVE);
-            launch_resolve(run, rc, tgt.sq);
+            launch_resolve(run, rc, tgt.sq, st_film);
             if (tgt.buckets != nullptr) launch_resolve_buckets(run, rc, tgt);
             run.end();
+            if (ov) {
+                HIP_CHECK(hipEventRecord(sc->ev_film[set], st_film));
+                sc->film_recorded[set] = true;
+                if (tail_on_film) sc->tail_set = (int)set;
+                ++sc->passes_film;
+            }
         }
+        if (!ov) ++sc->passes_single;
         if (run.stats) read_counters(run, rc, ps.counts_words);
     }
     run.samples_traced += (uint64_t)n_pix * tgt.count;
@@ -2190,7 +2314,7 @@ spt_status spt_render(const spt_scene* scene_c, const spt_camera* cam, const spt
         const float radius = plan_radius(p, "render");
         const int32_t R = (int32_t)std::ceil(radius - 0.5f);
         HIP_CHECK(hipSetDevice(sc->device));
-        sc->out.ensure((size_t)own_pix * 3 * sizeof(float));
+        grow(sc, sc->out, (size_t)own_pix * 3 * sizeof(float));
 
         RenderRun run;
         run.sc = sc;
@@ -2198,6 +2322,10 @@ spt_status spt_render(const spt_scene* scene_c, const spt_camera* cam, const spt
         run.params = &p;
         run.stats = stats;
         run_setup(run);
+        // an asynchronous frame without a wide box filter takes the overlapped schedule (trace_window); every other render
+        // starts behind whatever such a frame left on the film stream
+        run.film_overlap = async_out && R <= 0 && run.film_stream;
+        if (!run.film_overlap) film_join(sc);
         hipEvent_t ev_total0 = run.get_event(), ev_total1 = run.get_event();
         HIP_CHECK(hipEventRecord(ev_total0, run.st));
         run_spans(run);
@@ -2206,9 +2334,12 @@ spt_status spt_render(const spt_scene* scene_c, const spt_camera* cam, const spt
             const RenderCtx rc = trace_window(run, 0, own_rows, p.shard_index, shard_count, strip_rows, false, whole);
             run.begin(SPT_K_RESOLVE);
             const dim3 grid((own_pix + kBlock - 1) / kBlock);
-            if (sc->copy_pending) HIP_CHECK(hipStreamWaitEvent(run.st, sc->ev_copy_done, 0));   // the previous frame's copy-out reads `out`
-            if (radius == 0.5f) hipLaunchKernelGGL(k_finish, dim3((own_pix * 3 + kBlock - 1) / kBlock), dim3(kBlock), 0, run.st, rc, sc->out.as<float>());
-            else hipLaunchKernelGGL(k_finish_box, grid, dim3(kBlock), 0, run.st, rc, sc->out.as<float>(), radius, R, 0u, p.spp);
+            // overlapped (trace_window may have fallen back): behind the last resolve and the previous frame's copy-out by the
+            // film stream's order.  Else the previous frame's copy-out, which reads `out`, is waited for
+            const hipStream_t st_fin = run.film_overlap ? sc->stream_film : run.st;
+            if (!run.film_overlap && sc->copy_pending) HIP_CHECK(hipStreamWaitEvent(run.st, sc->ev_copy_done, 0));
+            if (radius == 0.5f) hipLaunchKernelGGL(k_finish, dim3((own_pix * 3 + kBlock - 1) / kBlock), dim3(kBlock), 0, st_fin, rc, sc->out.as<float>());
+            else hipLaunchKernelGGL(k_finish_box, grid, dim3(kBlock), 0, st_fin, rc, sc->out.as<float>(), radius, R, 0u, p.spp);
             run.end();
         } else {
             // Film::filter_pixel (film.rs:71-92) reads the samples of (2R+1)^2 pixels: each run of consecutive rows of
@@ -2228,7 +2359,7 @@ spt_status spt_render(const spt_scene* scene_c, const spt_camera* cam, const spt
                 const uint32_t b0 = j0 >= (uint32_t)R ? j0 - (uint32_t)R : 0u, b1 = (uint32_t)std::min<uint64_t>(p.height, (uint64_t)j1 + (uint64_t)R);
                 const RenderCtx rc = trace_window(run, b0, b1 - b0, 0u, 1u, 1u, true, whole);
                 run.begin(SPT_K_RESOLVE);
-                BoxJob job{sc->rad.as<float>(), b0, b1 - b0, j0, j1 - j0, sc->out.as<float>() + k * (size_t)p.width * 3, R, radius};
+                BoxJob job{sc->rad[0].as<float>(), b0, b1 - b0, j0, j1 - j0, sc->out.as<float>() + k * (size_t)p.width * 3, R, radius};
                 if (sc->copy_pending) HIP_CHECK(hipStreamWaitEvent(run.st, sc->ev_copy_done, 0));
                 hipLaunchKernelGGL(k_filter_box, dim3(((j1 - j0) * p.width + kBlock - 1) / kBlock), dim3(kBlock), 0, run.st, rc, job);
                 run.end();
@@ -2238,9 +2369,11 @@ spt_status spt_render(const spt_scene* scene_c, const spt_camera* cam, const spt
         HIP_CHECK(hipGetLastError());
         hipStream_t st_out = run.st;
         if (async_out) {   // the copy-out leaves the compute stream: the next render's kernels run beside it
-            HIP_CHECK(hipEventRecord(sc->ev_out_ready, run.st));
-            HIP_CHECK(hipStreamWaitEvent(sc->stream_copy, sc->ev_out_ready, 0));
-            st_out = sc->stream_copy;
+            if (!run.film_overlap) {   // (overlapped: the copy follows the finish kernel on the film stream)
+                HIP_CHECK(hipEventRecord(sc->ev_out_ready, run.st));
+                HIP_CHECK(hipStreamWaitEvent(sc->stream_film, sc->ev_out_ready, 0));
+            }
+            st_out = sc->stream_film;
         }
         const size_t strip_bytes = (size_t)strip_rows * p.width * 3 * sizeof(float);
         if (p.out_strip_stride == 0 || p.out_strip_stride == strip_bytes) {
@@ -2256,7 +2389,7 @@ spt_status spt_render(const spt_scene* scene_c, const spt_camera* cam, const spt
                                          rest_rows * (size_t)p.width * 3 * sizeof(float), hipMemcpyDeviceToHost, st_out));
         }
         if (async_out) {
-            HIP_CHECK(hipEventRecord(sc->ev_copy_done, sc->stream_copy));
+            HIP_CHECK(hipEventRecord(sc->ev_copy_done, sc->stream_film));
             sc->copy_pending = true;
             return SPT_OK;
         }
@@ -2264,7 +2397,7 @@ spt_status spt_render(const spt_scene* scene_c, const spt_camera* cam, const spt
         if (run.count) HIP_CHECK(hipMemcpyAsync(h_visits, sc->visits.p, sizeof h_visits, hipMemcpyDeviceToHost, run.st));
         HIP_CHECK(hipEventRecord(ev_total1, run.st));
         HIP_CHECK(hipStreamSynchronize(run.st));
-        sc->copy_pending = false;   // (the finish kernels of this render waited for any copy-out still in flight)
+        sc->copy_pending = sc->film_inflight = false;   // (the finish kernels of this render waited for any copy-out still in flight, film_join for the film stream)
         if (stats) {
             for (int c = 0; c < 3; ++c)
                 for (int k = 0; k < 3; ++k) stats->class_visits[c][k] = h_visits[3 * c + k];
@@ -2303,8 +2436,10 @@ spt_status spt_render_wait(const spt_scene* scene_c) {
     return guarded("render_wait", [&] {
         HIP_CHECK(hipSetDevice(sc->device));
         HIP_CHECK(hipStreamSynchronize(sc->stream));
-        HIP_CHECK(hipStreamSynchronize(sc->stream_copy));
-        sc->copy_pending = false;
+        HIP_CHECK(hipStreamSynchronize(sc->stream_film));
+        sc->copy_pending = sc->film_pending = sc->film_inflight = false;
+        sc->film_recorded[0] = sc->film_recorded[1] = false;
+        sc->tail_set = -1;
         return SPT_OK;
     });
 }
@@ -2381,6 +2516,7 @@ spt_status spt_film_render(spt_film* f, uint32_t n_samples) {
         // (an adaptive film without active pixels traces nothing: `done` still advances, every pixel keeps its n_p)
         if (f->rows != 0 && !(f->adaptive && f->active == 0)) {
             HIP_CHECK(hipSetDevice(sc->device));
+            film_join(sc);
             RenderRun run;
             run.sc = sc;
             run.cam = &f->cam;
@@ -2431,6 +2567,7 @@ spt_status spt_film_read(spt_film* f, uint32_t what, float* out) {
         const uint32_t n_pix = f->rows * p.width;
         const size_t bytes = (size_t)n_pix * 3 * sizeof(float);
         HIP_CHECK(hipSetDevice(sc->device));
+        film_join(sc);
         const hipStream_t st = sc->stream;
         const void* src = f->sum.p;
         if (what == SPT_FILM_SUM_SQ) src = f->sq.p;
@@ -2477,6 +2614,7 @@ spt_status spt_film_adapt(spt_film* f, float rel_error, float abs_floor, uint32_
             return SPT_OK;
         }
         HIP_CHECK(hipSetDevice(sc->device));
+        film_join(sc);
         const hipStream_t st = sc->stream;
         const uint32_t tiles_x = (p.width + kTile - 1) / kTile, n_tiles = tiles_x * ((f->rows + kTile - 1) / kTile);
         if (!f->adaptive) {   // every pixel active, every tile busy; the reciprocal table of the plan's sample counts
@@ -2524,6 +2662,7 @@ spt_status spt_film_read_counts(spt_film* f, uint32_t* out) {
         }
         std::vector<uint8_t> mask(n_pix);
         HIP_CHECK(hipSetDevice(sc->device));
+        film_join(sc);
         HIP_CHECK(hipMemcpyAsync(mask.data(), f->mask.p, n_pix, hipMemcpyDeviceToHost, sc->stream));
         HIP_CHECK(hipMemcpyAsync(out, f->counts.p, (size_t)n_pix * sizeof(uint32_t), hipMemcpyDeviceToHost, sc->stream));
         HIP_CHECK(hipStreamSynchronize(sc->stream));
@@ -2591,6 +2730,7 @@ spt_status spt_film_denoise(spt_film* f, spt_film* guide, const spt_denoise_para
         if (f->rows == 0 || p.width == 0) return SPT_OK;
         const uint32_t n_pix = f->rows * p.width;
         HIP_CHECK(hipSetDevice(sc->device));
+        film_join(sc);
         const hipStream_t st = sc->stream;
         const size_t rec_bytes = (size_t)n_pix * sizeof(float4), out_bytes = (size_t)n_pix * 3 * sizeof(float);
         f->dn_color[0].ensure(rec_bytes);
@@ -2644,6 +2784,7 @@ spt_status spt_film_buckets(spt_film* f, uint32_t n_buckets) {
         if (f->done != 0u) fail(SPT_ERR_INVALID_ARG, "film_buckets: the film already covers samples (buckets start with the film)");
         if (f->radius != 0.5f) fail(SPT_ERR_UNSUPPORTED, "film_buckets: needs the box radius 0.5 (every sample of the pixel weighs 1)");
         HIP_CHECK(hipSetDevice(sc->device));
+        film_join(sc);
         const hipStream_t st = sc->stream;
         const size_t bytes = (size_t)n_buckets * f->rows * p.width * 3 * sizeof(float);
         DeviceBuffer buckets, inv_dev;   // the film gets them once everything has worked
@@ -2673,6 +2814,7 @@ spt_status spt_film_read_buckets(spt_film* f, float* out) {
         const size_t bytes = (size_t)f->n_buckets * f->rows * f->plan.width * 3 * sizeof(float);
         if (bytes == 0) return SPT_OK;
         HIP_CHECK(hipSetDevice(sc->device));
+        film_join(sc);
         HIP_CHECK(hipMemcpyAsync(out, f->buckets.p, bytes, hipMemcpyDeviceToHost, sc->stream));
         HIP_CHECK(hipStreamSynchronize(sc->stream));
         return SPT_OK;
@@ -2693,6 +2835,7 @@ spt_status spt_film_read_robust(spt_film* f, uint32_t estimator, float* out) {
         const uint32_t n_pix = f->rows * p.width, K = f->n_buckets;
         const size_t bytes = (size_t)n_pix * 3 * sizeof(float);
         HIP_CHECK(hipSetDevice(sc->device));
+        film_join(sc);
         const hipStream_t st = sc->stream;
         f->out.ensure(bytes);
         const float kf = (float)K, gk = (float)(K + 1u) / (float)K, hf = (float)((K - 1u) / 2u);
@@ -2735,6 +2878,7 @@ static spt_status trace_common(const spt_scene* scene_c, uint32_t n, const spt_r
     std::lock_guard<std::mutex> lock(sc->mu);
     return guarded("trace", [&] {
         HIP_CHECK(hipSetDevice(sc->device));
+        film_join(sc);
         sc->trace_in.ensure((size_t)n * sizeof(spt_ray));
         sc->trace_out.ensure((size_t)n * out_elem);
         hipStream_t st = sc->stream;
@@ -2796,6 +2940,15 @@ spt_status spt_debug_detmath(int32_t device, uint32_t fn, uint32_t n, const floa
         HIP_CHECK(hipMemcpy(out, dout.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
         return SPT_OK;
     });
+}
+
+spt_status spt_debug_render_info(const spt_scene* scene_c, uint32_t what, uint64_t* out) {
+    if (!scene_c || !out || what > 1u) { g_error = "debug_render_info: null argument or unknown counter"; return SPT_ERR_INVALID_ARG; }
+    spt_scene* sc = const_cast<spt_scene*>(scene_c);
+    if (sc->fwd) return forwarded(sc->fwd, sc->fwd->debug_render_info(sc->inner, what, out));
+    std::lock_guard<std::mutex> lock(sc->mu);
+    *out = what == 0u ? sc->passes_film : sc->passes_single;
+    return SPT_OK;
 }
 
 spt_status spt_debug_bxdf(const spt_scene* scene_c, int32_t device, const spt_material* mt, uint32_t op, uint32_t n, const float* wo,

@@ -546,6 +546,21 @@ enum { SPT_ROBUST_MON = 0, SPT_ROBUST_GMON = 1 };
 /* rows * width * 3 f32 */
 spt_status spt_film_read_robust(spt_film* film, uint32_t estimator, float* out);
 
+/* ---- 8-bit read-out of a film (additive to ABI v14: detect it by symbol) -----------------------------------------------------
+ * What RendererT::render saves is an 8-bit image (Film::filter_to_image -> color_to_rgb, src/core/film.rs:94-99).
+ * spt_film_read_rgb8 makes the float image of `source` exactly as the matching float call does - SPT_READ_MEAN: spt_film_read
+ * SPT_FILM_MEAN (adaptive counts and a box radius other than 0.5 included), SPT_READ_ROBUST_MON / _GMON: spt_film_read_robust,
+ * SPT_READ_DENOISED: spt_film_denoise(film, guide, dn) - and returns its bytes, converted on the device in a pass of its own
+ * behind the read-out kernel: a quarter of the bytes cross to the host.  Per channel, exact f32, one rounded operation at a time:
+ *     c = x * 255.0f;   cl = c < 0 ? 0 : (c > 255 ? 255 : c);   byte = (cl != cl) ? 0 : (uint8_t)cl
+ * A NaN gives 0, +inf 255, -inf and -0 give 0, the conversion truncates (no gamma, no dithering: the reference has none).
+ * It changes nothing of the film: S, Q, buckets, mask and counts stay as they are.  Refusals are those of the matching float
+ * call, with its status, and leave the film as it was; an unknown source or a null film or out is SPT_ERR_INVALID_ARG.  A film
+ * without rows returns SPT_OK and writes nothing.  Synchronous; takes the scene's lock. */
+enum { SPT_READ_MEAN = 0, SPT_READ_ROBUST_MON = 1, SPT_READ_ROBUST_GMON = 2, SPT_READ_DENOISED = 3 };
+/* out: rows * width * 3 u8, packed.  guide / dn are read for SPT_READ_DENOISED only (both may be NULL, as in spt_film_denoise). */
+spt_status spt_film_read_rgb8(spt_film* film, uint32_t source, spt_film* guide, const spt_denoise_params* dn, uint8_t* out);
+
 /* Seams below the renderer, for parity tests of rows a4/a6/a8/a9/a10:
  * Primitive::intersect / intersect_test of the scene aggregate on caller rays. */
 spt_status spt_trace_closest(const spt_scene* scene, uint32_t n, const spt_ray* rays, spt_hit* hits);
@@ -565,6 +580,9 @@ void spt_unpin_host(void* p);
  * 2 log, 3 exp, 4 acos, 5 atan2(a,b), 6 asin, 7 round, 8 floor, 9 sqrt, 10 a/b, 11 max(a,b),
  * 12 min(a,b)), so the tests can check gfx950 returns the same bits as x86-64. */
 spt_status spt_debug_detmath(int32_t device, uint32_t fn, uint32_t n, const float* a, const float* b, float* out);
+
+/* Test seam (additive to ABI v14): the conversion kernel of spt_film_read_rgb8 on n caller floats. */
+spt_status spt_debug_pack_rgb8(int32_t device, uint32_t n, const float* in, uint8_t* out);
 
 /* Test seam (ABI v13) for rows a13-a16: BxdfT::{sample, bxdf, pdf} (src/bxdf/mod.rs:80-90) of ONE constant material record
  * (`recipe` 0), evaluated on the device for n inputs in the local shading frame (z = normal).

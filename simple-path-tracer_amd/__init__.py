@@ -182,6 +182,7 @@ RENDER_BOX_RADIUS = 2
 RENDER_COUNT_VISITS = 4
 RENDER_ASYNC = 8
 RENDER_DEBUG_NORMAL = 16   # the reference's cargo feature `debug_normal` (Cargo.toml:34-36, pt.rs:113-118)
+READ_SOURCES = {"mean": 0, "mon": 1, "gmon": 2, "denoised": 3}   # SPT_READ_* of spt_film_read_rgb8
 FILM_MOMENTS = 1          # spt_film_create: also keep the per-channel sum of squared sample radiance (ABI v14)
 FILM_MEAN, FILM_SUM, FILM_SUM_SQ, FILM_VAR_OF_MEAN = 0, 1, 2, 3   # spt_film_read
 ROBUST_MON, ROBUST_GMON = 0, 1   # spt_film_read_robust: median of the bucket means, Gini-adaptive trimmed mean of them
@@ -304,6 +305,9 @@ def hip_lib() -> C.CDLL:
             lib.spt_film_buckets.argtypes = [C.c_void_p, C.c_uint32]
             lib.spt_film_read_buckets.argtypes = [C.c_void_p, C.c_void_p]
             lib.spt_film_read_robust.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        if hasattr(lib, "spt_film_read_rgb8"):   # (the same)
+            lib.spt_film_read_rgb8.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p]
+            lib.spt_debug_pack_rgb8.argtypes = [C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]
         lib.spt_debug_detmath.argtypes = [C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.spt_debug_bxdf.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Material), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -627,6 +631,27 @@ class ProgressiveFilm:
         _check_hip(hip_lib().spt_film_read_robust(self._handle(), ROBUST_MON if estimator == "mon" else ROBUST_GMON, out.ctypes.data))
         return out
 
+    def read_rgb8(self, source: str = "mean", guide: Optional["ProgressiveFilm"] = None, **denoise_params) -> np.ndarray:
+        """spt_film_read_rgb8: film_to_rgb8 of mean() ("mean"), robust_mean("mon" / "gmon") or denoise(guide, **denoise_params)
+        ("denoised"), converted on the device: (rows, width, 3) u8, a quarter of the bytes of the float read-out.  Refused
+        where the float call is; the film is not changed."""
+        if source not in READ_SOURCES:
+            raise ValueError("read_rgb8: source is one of %s, not %r" % (", ".join(repr(k) for k in READ_SOURCES), source))
+        if source != "denoised" and (guide is not None or denoise_params):
+            raise ValueError("read_rgb8: guide and the denoiser's parameters go with source='denoised'")
+        params = None
+        if source == "denoised":
+            d = dict(iterations=5, k_color=2.0, k_guide=1.0, eps_color=1e-8, eps_guide=1e-2)
+            unknown = set(denoise_params) - set(d)
+            if unknown:
+                raise TypeError("read_rgb8: unknown denoise parameter(s) %s" % ", ".join(sorted(unknown)))
+            d.update(denoise_params)
+            params = C.byref(DenoiseParams(C.sizeof(DenoiseParams), d["iterations"], d["k_color"], d["k_guide"], d["eps_color"], d["eps_guide"]))
+        out = np.zeros((self.rows, self.width, 3), dtype=np.uint8)
+        _check_hip(hip_lib().spt_film_read_rgb8(self._handle(), READ_SOURCES[source], guide._handle() if guide is not None else None,
+                                                params, out.ctypes.data))
+        return out
+
     def render(self, n: int) -> "ProgressiveFilm":
         """Adds the next n samples of the plan (synchronous)."""
         _check_hip(hip_lib().spt_film_render(self._handle(), n))
@@ -802,15 +827,22 @@ def film_to_rgb8(film: np.ndarray) -> np.ndarray:
     return out
 
 
+def _as_rgb8(film: np.ndarray) -> np.ndarray:
+    """A float film through film_to_rgb8; a u8 image (ProgressiveFilm.read_rgb8) as it is."""
+    if film.dtype == np.uint8:
+        return np.ascontiguousarray(film)
+    return film_to_rgb8(film)
+
+
 def write_png(path: str, film: np.ndarray) -> None:
-    rgb8 = film_to_rgb8(film)
+    rgb8 = _as_rgb8(film)
     h, w = rgb8.shape[:2]
     _check_host(host_lib().spt_host_write_png(os.fspath(path).encode(), rgb8.ctypes.data, w, h))
 
 
 def write_image(path: str, film: np.ndarray) -> None:
-    """`image.save(path)` (src/renderer/pt.rs:292-294): png or jpg / jpeg by extension."""
-    rgb8 = film_to_rgb8(film)
+    """`image.save(path)` (src/renderer/pt.rs:292-294): png or jpg / jpeg by extension.  `film`: f32, or the u8 image itself."""
+    rgb8 = _as_rgb8(film)
     h, w = rgb8.shape[:2]
     _check_host(host_lib().spt_host_write_image(os.fspath(path).encode(), rgb8.ctypes.data, w, h))
 
@@ -945,6 +977,14 @@ def device_detmath(fn: int, a: np.ndarray, b: Optional[np.ndarray] = None, devic
     b = np.ascontiguousarray(b if b is not None else np.zeros_like(a), dtype=np.float32)
     out = np.zeros_like(a)
     _check_hip(hip_lib().spt_debug_detmath(device, fn, a.size, a.ctypes.data, b.ctypes.data, out.ctypes.data))
+    return out
+
+
+def debug_pack_rgb8(values: np.ndarray, device: int = 0) -> np.ndarray:
+    """Test seam (spt_debug_pack_rgb8): the device's conversion kernel on any number of f32 values; u8 of the same shape."""
+    values = np.ascontiguousarray(values, dtype=np.float32)
+    out = np.zeros(values.shape, dtype=np.uint8)
+    _check_hip(hip_lib().spt_debug_pack_rgb8(device, values.size, values.ctypes.data, out.ctypes.data))
     return out
 
 

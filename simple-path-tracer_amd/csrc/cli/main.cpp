@@ -12,7 +12,8 @@
 // --robust K [--robust-estimator mon|gmon] [--mean-out PATH] keeps K bucket sums per pixel (spt_film_buckets) and writes every preview
 // and the final image from their median (mon) or Gini-adaptive trimmed mean (gmon, the default), the plain mean to PATH.  It loads the scene
 // with libspt_host, renders with libspt_hip (HIP kernels only) and writes the image; like the reference it reports the
-// time spent inside `render`.
+// time spent inside `render`.  The images of a film (previews, the final image, --noisy-out, --mean-out) leave the device as the
+// 8-bit image the reference saves (spt_film_read_rgb8: a quarter of the float film's bytes); the EXR outputs stay float.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -204,7 +205,16 @@ int main(int argc, char** argv) {
         if (spt_host_write_image(path.c_str(), rgb8.data(), width, height) != SPT_OK)
             std::printf("Failed to save image, err: %s\n", spt_host_last_error());  // printed and ignored, like pt.rs:292-294
     };
-    auto write_film = [&]() { write_image(out_path, film); };
+    // a film's image comes from the device in 8 bits (spt_film_read_rgb8); a plain render's film is converted here
+    std::vector<uint8_t> film8;
+    auto write_image8 = [&](const std::string& path) {
+        if (spt_host_write_image(path.c_str(), film8.data(), width, height) != SPT_OK)
+            std::printf("Failed to save image, err: %s\n", spt_host_last_error());  // printed and ignored, like pt.rs:292-294
+    };
+    auto write_film = [&]() {
+        if (progressive) write_image8(out_path);
+        else write_image(out_path, film);
+    };
     uint32_t done = 0;
     if (progressive) {
         // the film takes the plan's samples in increments; the mean after all of them has the bits of one spt_render
@@ -230,9 +240,11 @@ int main(int argc, char** argv) {
         }
         // the image of a preview and of the end: the film's mean, the filtered mean (after one sample there is no variance yet)
         // or the robust read-out of the buckets
+        film8.resize(film.size());
         auto read_image = [&]() {
-            if (robust) return spt_film_read_robust(pf, estimator, film.data());
-            return denoise && done >= 2 ? spt_film_denoise(pf, guide, &dn, film.data()) : spt_film_read(pf, SPT_FILM_MEAN, film.data());
+            if (robust) return spt_film_read_rgb8(pf, estimator == (uint32_t)SPT_ROBUST_MON ? SPT_READ_ROBUST_MON : SPT_READ_ROBUST_GMON, nullptr, nullptr, film8.data());
+            return denoise && done >= 2 ? spt_film_read_rgb8(pf, SPT_READ_DENOISED, guide, &dn, film8.data())
+                                        : spt_film_read_rgb8(pf, SPT_READ_MEAN, nullptr, nullptr, film8.data());
         };
         const uint32_t inc = preview_every ? preview_every : ((time_limit > 0.0 || adaptive_on) ? std::max(1u, params.spp / 16u) : params.spp);
         uint32_t active = width * height;
@@ -250,12 +262,12 @@ int main(int argc, char** argv) {
             }
         }
         if (!noisy_out.empty()) {
-            if (spt_film_read(pf, SPT_FILM_MEAN, film.data()) != SPT_OK) return film_fail();
-            write_image(noisy_out, film);
+            if (spt_film_read_rgb8(pf, SPT_READ_MEAN, nullptr, nullptr, film8.data()) != SPT_OK) return film_fail();
+            write_image8(noisy_out);
         }
         if (!mean_out.empty()) {
-            if (spt_film_read(pf, SPT_FILM_MEAN, film.data()) != SPT_OK) return film_fail();
-            write_image(mean_out, film);
+            if (spt_film_read_rgb8(pf, SPT_READ_MEAN, nullptr, nullptr, film8.data()) != SPT_OK) return film_fail();
+            write_image8(mean_out);
         }
         if (read_image() != SPT_OK) return film_fail();
         if (adaptive_on) {

@@ -555,6 +555,31 @@ __global__ void __launch_bounds__(256) k_filter_box(RenderCtx rc, BoxJob job) {
     job.out[3 * (size_t)idx] = c.x; job.out[3 * (size_t)idx + 1] = c.y; job.out[3 * (size_t)idx + 2] = c.z;
 }
 
+// ---------------------------------------------------------------------------- RGB8 output
+// color_to_rgb (film.rs:94-99) of one channel, the arithmetic of spt_host_film_to_rgb8, one rounded operation at a time: Rust's
+// clamp keeps a NaN and `NaN as u8` is 0; +inf gives 255, -inf and -0 give 0; the conversion truncates.
+SPT_DEV uint32_t rgb8_byte(float x) {
+    const float c = x * 255.0f;
+    const float cl = c < 0.0f ? 0.0f : (c > 255.0f ? 255.0f : c);
+    return (cl != cl) ? 0u : (uint32_t)cl;
+}
+
+// The 8-bit image of a packed float buffer (spt_film_read_rgb8): a pass of its own behind the
+// read-out kernels, whose code stays what it was.  One lane takes four consecutive floats: one 16-byte load, four conversions,
+// one dword store (both buffers come from the allocator, so 16 * i and 4 * i are aligned).  The last lane of a buffer whose
+// length is no multiple of 4 takes its one to three elements singly.
+__global__ void __launch_bounds__(256) k_pack_rgb8(uint32_t n_floats, const float* in, uint8_t* out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (n_floats + 3u) / 4u) return;   // (n_floats <= 2^32 - 4: the grid's lane count fits 32 bits)
+    const uint32_t base = 4u * i;
+    if (n_floats - base >= 4u) {
+        const float4 v = *reinterpret_cast<const float4*>(in + base);
+        *reinterpret_cast<uint32_t*>(out + base) = rgb8_byte(v.x) | (rgb8_byte(v.y) << 8) | (rgb8_byte(v.z) << 16) | (rgb8_byte(v.w) << 24);
+    } else {
+        for (uint32_t k = base; k < n_floats; ++k) out[k] = (uint8_t)rgb8_byte(in[k]);
+    }
+}
+
 // ---------------------------------------------------------------------------- test seams
 template <bool kLds>
 __global__ void __launch_bounds__(256) k_trace_closest(DScene sc, uint32_t n, const spt_ray* rays, spt_hit* hits) {

@@ -517,6 +517,7 @@ struct BezierLib {
     decltype(&spt_film_buckets) film_buckets = nullptr;
     decltype(&spt_film_read_buckets) film_read_buckets = nullptr;
     decltype(&spt_film_read_robust) film_read_robust = nullptr;
+    decltype(&spt_film_read_rgb8) film_read_rgb8 = nullptr;
     decltype(&spt_trace_closest) trace_closest = nullptr;
     decltype(&spt_trace_any) trace_any = nullptr;
     decltype(&spt_debug_bxdf) debug_bxdf = nullptr;
@@ -623,6 +624,7 @@ struct spt_film {
     float radius = 0.5f;
     int32_t R = 0;                    // ceil(radius - 0.5) <= 0
     DeviceBuffer sum, sq, out;        // S, Q (SPT_FILM_MOMENTS) and the read-out staging buffer, rows * width * 3 f32 each
+    DeviceBuffer out8;                // spt_film_read_rgb8: the bytes of the staging buffer (k_pack_rgb8), rows * width * 3 u8
     // adaptive sampling (spt_film_adapt), made by its first call that can retire pixels; until then the film is a plain one
     bool adaptive = false;
     DeviceBuffer mask;                // per pixel u8: 1 active, 0 retired
@@ -865,6 +867,7 @@ const BezierLib* bezier_lib() {
                          sym(lib.film_adapt, "spt_film_adapt") && sym(lib.film_read_counts, "spt_film_read_counts") &&
                          sym(lib.film_denoise, "spt_film_denoise") && sym(lib.film_buckets, "spt_film_buckets") &&
                          sym(lib.film_read_buckets, "spt_film_read_buckets") && sym(lib.film_read_robust, "spt_film_read_robust") &&
+                         sym(lib.film_read_rgb8, "spt_film_read_rgb8") &&
                          sym(lib.trace_closest, "spt_trace_closest") && sym(lib.trace_any, "spt_trace_any") && sym(lib.debug_bxdf, "spt_debug_bxdf") &&
                          sym(lib.debug_render_info, "spt_debug_render_info") &&
                          sym(lib.last_error, "spt_last_error") && sym(version, "spt_abi_version");
@@ -1798,6 +1801,13 @@ void grow(spt_scene* sc, DeviceBuffer& b, size_t n) {
     b.alloc(n);
 }
 
+// k_pack_rgb8 over the n_floats floats of `in`, on `st` behind the kernel that wrote them.
+void launch_pack_rgb8(uint32_t n_floats, const float* in, uint8_t* out, hipStream_t st) {
+    const uint32_t lanes = (n_floats + 3u) / 4u;
+    hipLaunchKernelGGL(k_pack_rgb8, dim3((lanes + kBlock - 1) / kBlock), dim3(kBlock), 0, st, n_floats, in, out);
+    HIP_CHECK(hipGetLastError());
+}
+
 // The passes of one window: their size, and the queues and counters they use.
 struct PassShape {
     uint32_t spp_pass;       // samples per pass
@@ -2549,50 +2559,72 @@ spt_status spt_film_samples(const spt_film* f, uint32_t* done) {
     return SPT_OK;
 }
 
+// Where a film read-out goes: the floats as they are (f32), or - spt_film_read_rgb8 - their bytes (u8).  Exactly one is set.
+struct FilmReadOut {
+    float* f32;
+    uint8_t* u8;
+};
+
+// The end of every read-out: n_floats floats at `src` on the device (the staging buffer f->out for everything but the raw sums)
+// go to the host as they are, or through k_pack_rgb8 and the film's byte buffer.  Synchronous.
+static void film_deliver(spt_film* f, const void* src, size_t n_floats, const FilmReadOut& to, hipStream_t st) {
+    if (to.u8) {
+        if (n_floats > 0xfffffffcull) fail(SPT_ERR_UNSUPPORTED, "film_read_rgb8: shard larger than 2^32 - 4 bytes");
+        f->out8.ensure(n_floats);
+        launch_pack_rgb8((uint32_t)n_floats, static_cast<const float*>(src), f->out8.as<uint8_t>(), st);
+        HIP_CHECK(hipMemcpyAsync(to.u8, f->out8.p, n_floats, hipMemcpyDeviceToHost, st));
+    } else {
+        HIP_CHECK(hipMemcpyAsync(to.f32, src, n_floats * sizeof(float), hipMemcpyDeviceToHost, st));
+    }
+    HIP_CHECK(hipStreamSynchronize(st));
+}
+
+// spt_film_read behind its argument checks (the scene's lock is held)
+static spt_status film_read_locked(spt_film* f, uint32_t what, const FilmReadOut& to) {
+    spt_scene* sc = f->sc;
+    const spt_render_params& p = f->plan;
+    if (what > SPT_FILM_VAR_OF_MEAN) fail(SPT_ERR_INVALID_ARG, "film_read: unknown SPT_FILM_* value");
+    const bool moments = (f->flags & SPT_FILM_MOMENTS) != 0;
+    if ((what == SPT_FILM_SUM_SQ || what == SPT_FILM_VAR_OF_MEAN) && !moments)
+        fail(SPT_ERR_INVALID_ARG, "film_read: SUM_SQ / VAR_OF_MEAN need a film created with SPT_FILM_MOMENTS");
+    if (what == SPT_FILM_VAR_OF_MEAN && f->radius != 0.5f)
+        fail(SPT_ERR_UNSUPPORTED, "film_read: VAR_OF_MEAN needs the box radius 0.5 (every sample of the pixel weighs 1)");
+    if ((what == SPT_FILM_MEAN || what == SPT_FILM_VAR_OF_MEAN) && f->done == 0) fail(SPT_ERR_INVALID_ARG, "film_read: the film covers no samples yet");
+    if (f->rows == 0) return SPT_OK;
+    const uint32_t n_pix = f->rows * p.width;
+    const size_t bytes = (size_t)n_pix * 3 * sizeof(float);
+    HIP_CHECK(hipSetDevice(sc->device));
+    film_join(sc);
+    const hipStream_t st = sc->stream;
+    const void* src = f->sum.p;
+    if (what == SPT_FILM_SUM_SQ) src = f->sq.p;
+    if (what == SPT_FILM_MEAN || what == SPT_FILM_VAR_OF_MEAN) {
+        f->out.ensure(bytes);
+        if (what == SPT_FILM_MEAN && f->radius != 0.5f) {
+            // k_finish_box over the covered samples: the context it reads is the plan's sampler and shard
+            RenderCtx rc = plan_ctx(p, f->cam, 0, f->rows, p.shard_index, p.shard_count ? p.shard_count : 1u, p.strip_rows ? p.strip_rows : 1u);
+            rc.film = f->sum.as<float>();
+            hipLaunchKernelGGL(k_finish_box, dim3((n_pix + kBlock - 1) / kBlock), dim3(kBlock), 0, st, rc, f->out.as<float>(), f->radius, f->R, f->first, f->done);
+        } else if (f->adaptive) {   // radius 0.5 (spt_film_adapt refuses others): per-pixel sample counts
+            hipLaunchKernelGGL(k_film_read_counts, dim3((n_pix * 3 + kBlock - 1) / kBlock), dim3(kBlock), 0, st, what, n_pix * 3u, f->sum.as<float>(),
+                               f->sq.as<float>(), f->mask.as<uint8_t>(), f->counts.as<uint32_t>(), f->done, f->inv.as<float>(), f->out.as<float>());
+        } else {
+            const float inv_n = 1.0f / (float)f->done, inv_n1 = f->done > 1u ? 1.0f / (float)(f->done - 1u) : 0.0f;
+            hipLaunchKernelGGL(k_film_read, dim3((n_pix * 3 + kBlock - 1) / kBlock), dim3(kBlock), 0, st, what, n_pix * 3u, f->sum.as<float>(),
+                               moments ? f->sq.as<float>() : nullptr, f->done, inv_n, inv_n1, f->out.as<float>());
+        }
+        HIP_CHECK(hipGetLastError());
+        src = f->out.p;
+    }
+    film_deliver(f, src, (size_t)n_pix * 3, to, st);
+    return SPT_OK;
+}
+
 spt_status spt_film_read(spt_film* f, uint32_t what, float* out) {
     if (!f || !out) { g_error = "film_read: null argument"; return SPT_ERR_INVALID_ARG; }
     if (f->fwd) return forwarded(f->fwd, f->fwd->film_read(f->inner, what, out));
-    spt_scene* sc = f->sc;
-    std::lock_guard<std::mutex> lock(sc->mu);
-    return guarded("film_read", [&] {
-        const spt_render_params& p = f->plan;
-        if (what > SPT_FILM_VAR_OF_MEAN) fail(SPT_ERR_INVALID_ARG, "film_read: unknown SPT_FILM_* value");
-        const bool moments = (f->flags & SPT_FILM_MOMENTS) != 0;
-        if ((what == SPT_FILM_SUM_SQ || what == SPT_FILM_VAR_OF_MEAN) && !moments)
-            fail(SPT_ERR_INVALID_ARG, "film_read: SUM_SQ / VAR_OF_MEAN need a film created with SPT_FILM_MOMENTS");
-        if (what == SPT_FILM_VAR_OF_MEAN && f->radius != 0.5f)
-            fail(SPT_ERR_UNSUPPORTED, "film_read: VAR_OF_MEAN needs the box radius 0.5 (every sample of the pixel weighs 1)");
-        if ((what == SPT_FILM_MEAN || what == SPT_FILM_VAR_OF_MEAN) && f->done == 0) fail(SPT_ERR_INVALID_ARG, "film_read: the film covers no samples yet");
-        if (f->rows == 0) return SPT_OK;
-        const uint32_t n_pix = f->rows * p.width;
-        const size_t bytes = (size_t)n_pix * 3 * sizeof(float);
-        HIP_CHECK(hipSetDevice(sc->device));
-        film_join(sc);
-        const hipStream_t st = sc->stream;
-        const void* src = f->sum.p;
-        if (what == SPT_FILM_SUM_SQ) src = f->sq.p;
-        if (what == SPT_FILM_MEAN || what == SPT_FILM_VAR_OF_MEAN) {
-            f->out.ensure(bytes);
-            if (what == SPT_FILM_MEAN && f->radius != 0.5f) {
-                // k_finish_box over the covered samples: the context it reads is the plan's sampler and shard
-                RenderCtx rc = plan_ctx(p, f->cam, 0, f->rows, p.shard_index, p.shard_count ? p.shard_count : 1u, p.strip_rows ? p.strip_rows : 1u);
-                rc.film = f->sum.as<float>();
-                hipLaunchKernelGGL(k_finish_box, dim3((n_pix + kBlock - 1) / kBlock), dim3(kBlock), 0, st, rc, f->out.as<float>(), f->radius, f->R, f->first, f->done);
-            } else if (f->adaptive) {   // radius 0.5 (spt_film_adapt refuses others): per-pixel sample counts
-                hipLaunchKernelGGL(k_film_read_counts, dim3((n_pix * 3 + kBlock - 1) / kBlock), dim3(kBlock), 0, st, what, n_pix * 3u, f->sum.as<float>(),
-                                   f->sq.as<float>(), f->mask.as<uint8_t>(), f->counts.as<uint32_t>(), f->done, f->inv.as<float>(), f->out.as<float>());
-            } else {
-                const float inv_n = 1.0f / (float)f->done, inv_n1 = f->done > 1u ? 1.0f / (float)(f->done - 1u) : 0.0f;
-                hipLaunchKernelGGL(k_film_read, dim3((n_pix * 3 + kBlock - 1) / kBlock), dim3(kBlock), 0, st, what, n_pix * 3u, f->sum.as<float>(),
-                                   moments ? f->sq.as<float>() : nullptr, f->done, inv_n, inv_n1, f->out.as<float>());
-            }
-            HIP_CHECK(hipGetLastError());
-            src = f->out.p;
-        }
-        HIP_CHECK(hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        return SPT_OK;
-    });
+    std::lock_guard<std::mutex> lock(f->sc->mu);
+    return guarded("film_read", [&] { return film_read_locked(f, what, FilmReadOut{out, nullptr}); });
 }
 
 spt_status spt_film_adapt(spt_film* f, float rel_error, float abs_floor, uint32_t min_samples, uint32_t* active_out) {
@@ -2688,86 +2720,92 @@ static DenoiseFilm denoise_input(const spt_film* f) {
     return in;
 }
 
+// A film and its guide have to live in the same library (both handles are passed through, or neither).
+static bool denoise_libraries_differ(const spt_film* f, const spt_film* guide) {
+    if ((f->fwd != nullptr) == (guide ? guide->fwd != nullptr : f->fwd != nullptr)) return false;
+    g_error = "film_denoise: the film and the guide are served by different libraries (one scene has Bezier patches)";
+    return true;
+}
+
+// spt_film_denoise behind its argument checks (the scene's lock is held)
+static spt_status film_denoise_locked(spt_film* f, spt_film* guide, const spt_denoise_params* params, const FilmReadOut& to) {
+    spt_scene* sc = f->sc;
+    const spt_render_params& p = f->plan;
+    // every check comes before the first launch: a refused call leaves the workspace as it was, and it reads the films only
+    auto check_film = [](const spt_film* x, const char* who) {
+        if (!(x->flags & SPT_FILM_MOMENTS))
+            fail(SPT_ERR_INVALID_ARG, std::string("film_denoise: the ") + who + " was created without SPT_FILM_MOMENTS (the weights need the variance of the mean)");
+        if (x->done < 2) fail(SPT_ERR_INVALID_ARG, std::string("film_denoise: the ") + who + " covers fewer than 2 samples (no variance yet)");
+    };
+    check_film(f, "film");
+    if (guide) {
+        if (guide == f) fail(SPT_ERR_INVALID_ARG, "film_denoise: the guide is the film itself");
+        if (guide->sc != sc) fail(SPT_ERR_INVALID_ARG, "film_denoise: the guide belongs to another scene object");
+        check_film(guide, "guide");
+        const spt_render_params& g = guide->plan;
+        if (g.width != p.width || g.height != p.height) fail(SPT_ERR_INVALID_ARG, "film_denoise: the guide has another width or height");
+        if (g.shard_index != p.shard_index || (g.shard_count ? g.shard_count : 1u) != (p.shard_count ? p.shard_count : 1u) ||
+            (g.strip_rows ? g.strip_rows : 1u) != (p.strip_rows ? p.strip_rows : 1u) || guide->rows != f->rows)
+            fail(SPT_ERR_INVALID_ARG, "film_denoise: the guide has another shard layout");
+    }
+    spt_denoise_params dp{(uint32_t)sizeof(spt_denoise_params), 5u, 2.0f, 1.0f, 1e-8f, 1e-2f};
+    if (params) {
+        if (params->size < sizeof(spt_denoise_params)) fail(SPT_ERR_INVALID_ARG, "film_denoise: params->size is smaller than spt_denoise_params");
+        dp = *params;
+    }
+    if (dp.iterations < 1u || dp.iterations > 8u) fail(SPT_ERR_INVALID_ARG, "film_denoise: iterations must be 1 .. 8");
+    for (const float v : {dp.k_color, dp.k_guide, dp.eps_color, dp.eps_guide})
+        if (!std::isfinite(v) || !(v > 0.0f)) fail(SPT_ERR_INVALID_ARG, "film_denoise: k_color, k_guide, eps_color and eps_guide must be finite and > 0");
+    if (f->radius != 0.5f || (guide && guide->radius != 0.5f))
+        fail(SPT_ERR_UNSUPPORTED, "film_denoise: needs the box radius 0.5 on both films (every sample of the pixel weighs 1)");
+    if (p.shard_count > 1u) fail(SPT_ERR_UNSUPPORTED, "film_denoise: the plan has shard_count > 1 (a shard's packed rows are not neighbours in the image)");
+    if (f->rows == 0 || p.width == 0) return SPT_OK;
+    const uint32_t n_pix = f->rows * p.width;
+    HIP_CHECK(hipSetDevice(sc->device));
+    film_join(sc);
+    const hipStream_t st = sc->stream;
+    const size_t rec_bytes = (size_t)n_pix * sizeof(float4), out_bytes = (size_t)n_pix * 3 * sizeof(float);
+    f->dn_color[0].ensure(rec_bytes);
+    if (dp.iterations > 1u) f->dn_color[1].ensure(rec_bytes);
+    if (guide) f->dn_guide.ensure(rec_bytes);
+    f->out.ensure(out_bytes);
+    float4* color[2] = {f->dn_color[0].as<float4>(), dp.iterations > 1u ? f->dn_color[1].as<float4>() : nullptr};
+    float4* const gbuf = guide ? f->dn_guide.as<float4>() : nullptr;
+    const dim3 pack_grid((n_pix + kBlock - 1) / kBlock), block(kBlock);
+    if (guide) hipLaunchKernelGGL(k_denoise_pack<true>, pack_grid, block, 0, st, n_pix, denoise_input(f), denoise_input(guide), color[0], gbuf);
+    else hipLaunchKernelGGL(k_denoise_pack<false>, pack_grid, block, 0, st, n_pix, denoise_input(f), DenoiseFilm{}, color[0], gbuf);
+    HIP_CHECK(hipGetLastError());
+    DenoiseArgs a{};
+    a.width = p.width;
+    a.rows = f->rows;
+    a.tiles_x = (p.width + kTile - 1) / kTile;
+    a.kc2 = dp.k_color * dp.k_color;
+    a.kg2 = dp.k_guide * dp.k_guide;
+    a.eps_c = dp.eps_color;
+    a.eps_g = dp.eps_guide;
+    const dim3 grid(a.tiles_x * ((f->rows + kTile - 1) / kTile));
+    for (uint32_t k = 0; k < dp.iterations; ++k) {
+        a.step = (int32_t)(1u << k);
+        const float4* src = color[k & 1u];
+        float4* dst = color[(k + 1u) & 1u];
+        const bool last = k + 1u == dp.iterations;
+        auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, a, src, gbuf, dst, f->out.as<float>()); };
+        if (guide && last) launch(k_denoise_atrous<true, true>);
+        else if (guide) launch(k_denoise_atrous<true, false>);
+        else if (last) launch(k_denoise_atrous<false, true>);
+        else launch(k_denoise_atrous<false, false>);
+        HIP_CHECK(hipGetLastError());
+    }
+    film_deliver(f, f->out.p, (size_t)n_pix * 3, to, st);
+    return SPT_OK;
+}
+
 spt_status spt_film_denoise(spt_film* f, spt_film* guide, const spt_denoise_params* params, float* out) {
     if (!f || !out) { g_error = "film_denoise: null argument"; return SPT_ERR_INVALID_ARG; }
-    if ((f->fwd != nullptr) != (guide ? guide->fwd != nullptr : f->fwd != nullptr)) {
-        g_error = "film_denoise: the film and the guide are served by different libraries (one scene has Bezier patches)";
-        return SPT_ERR_INVALID_ARG;
-    }
+    if (denoise_libraries_differ(f, guide)) return SPT_ERR_INVALID_ARG;
     if (f->fwd) return forwarded(f->fwd, f->fwd->film_denoise(f->inner, guide ? guide->inner : nullptr, params, out));
-    spt_scene* sc = f->sc;
-    std::lock_guard<std::mutex> lock(sc->mu);
-    return guarded("film_denoise", [&] {
-        const spt_render_params& p = f->plan;
-        // every check comes before the first launch: a refused call leaves the workspace as it was, and it reads the films only
-        auto check_film = [](const spt_film* x, const char* who) {
-            if (!(x->flags & SPT_FILM_MOMENTS))
-                fail(SPT_ERR_INVALID_ARG, std::string("film_denoise: the ") + who + " was created without SPT_FILM_MOMENTS (the weights need the variance of the mean)");
-            if (x->done < 2) fail(SPT_ERR_INVALID_ARG, std::string("film_denoise: the ") + who + " covers fewer than 2 samples (no variance yet)");
-        };
-        check_film(f, "film");
-        if (guide) {
-            if (guide == f) fail(SPT_ERR_INVALID_ARG, "film_denoise: the guide is the film itself");
-            if (guide->sc != sc) fail(SPT_ERR_INVALID_ARG, "film_denoise: the guide belongs to another scene object");
-            check_film(guide, "guide");
-            const spt_render_params& g = guide->plan;
-            if (g.width != p.width || g.height != p.height) fail(SPT_ERR_INVALID_ARG, "film_denoise: the guide has another width or height");
-            if (g.shard_index != p.shard_index || (g.shard_count ? g.shard_count : 1u) != (p.shard_count ? p.shard_count : 1u) ||
-                (g.strip_rows ? g.strip_rows : 1u) != (p.strip_rows ? p.strip_rows : 1u) || guide->rows != f->rows)
-                fail(SPT_ERR_INVALID_ARG, "film_denoise: the guide has another shard layout");
-        }
-        spt_denoise_params dp{(uint32_t)sizeof(spt_denoise_params), 5u, 2.0f, 1.0f, 1e-8f, 1e-2f};
-        if (params) {
-            if (params->size < sizeof(spt_denoise_params)) fail(SPT_ERR_INVALID_ARG, "film_denoise: params->size is smaller than spt_denoise_params");
-            dp = *params;
-        }
-        if (dp.iterations < 1u || dp.iterations > 8u) fail(SPT_ERR_INVALID_ARG, "film_denoise: iterations must be 1 .. 8");
-        for (const float v : {dp.k_color, dp.k_guide, dp.eps_color, dp.eps_guide})
-            if (!std::isfinite(v) || !(v > 0.0f)) fail(SPT_ERR_INVALID_ARG, "film_denoise: k_color, k_guide, eps_color and eps_guide must be finite and > 0");
-        if (f->radius != 0.5f || (guide && guide->radius != 0.5f))
-            fail(SPT_ERR_UNSUPPORTED, "film_denoise: needs the box radius 0.5 on both films (every sample of the pixel weighs 1)");
-        if (p.shard_count > 1u) fail(SPT_ERR_UNSUPPORTED, "film_denoise: the plan has shard_count > 1 (a shard's packed rows are not neighbours in the image)");
-        if (f->rows == 0 || p.width == 0) return SPT_OK;
-        const uint32_t n_pix = f->rows * p.width;
-        HIP_CHECK(hipSetDevice(sc->device));
-        film_join(sc);
-        const hipStream_t st = sc->stream;
-        const size_t rec_bytes = (size_t)n_pix * sizeof(float4), out_bytes = (size_t)n_pix * 3 * sizeof(float);
-        f->dn_color[0].ensure(rec_bytes);
-        if (dp.iterations > 1u) f->dn_color[1].ensure(rec_bytes);
-        if (guide) f->dn_guide.ensure(rec_bytes);
-        f->out.ensure(out_bytes);
-        float4* color[2] = {f->dn_color[0].as<float4>(), dp.iterations > 1u ? f->dn_color[1].as<float4>() : nullptr};
-        float4* const gbuf = guide ? f->dn_guide.as<float4>() : nullptr;
-        const dim3 pack_grid((n_pix + kBlock - 1) / kBlock), block(kBlock);
-        if (guide) hipLaunchKernelGGL(k_denoise_pack<true>, pack_grid, block, 0, st, n_pix, denoise_input(f), denoise_input(guide), color[0], gbuf);
-        else hipLaunchKernelGGL(k_denoise_pack<false>, pack_grid, block, 0, st, n_pix, denoise_input(f), DenoiseFilm{}, color[0], gbuf);
-        HIP_CHECK(hipGetLastError());
-        DenoiseArgs a{};
-        a.width = p.width;
-        a.rows = f->rows;
-        a.tiles_x = (p.width + kTile - 1) / kTile;
-        a.kc2 = dp.k_color * dp.k_color;
-        a.kg2 = dp.k_guide * dp.k_guide;
-        a.eps_c = dp.eps_color;
-        a.eps_g = dp.eps_guide;
-        const dim3 grid(a.tiles_x * ((f->rows + kTile - 1) / kTile));
-        for (uint32_t k = 0; k < dp.iterations; ++k) {
-            a.step = (int32_t)(1u << k);
-            const float4* src = color[k & 1u];
-            float4* dst = color[(k + 1u) & 1u];
-            const bool last = k + 1u == dp.iterations;
-            auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, a, src, gbuf, dst, f->out.as<float>()); };
-            if (guide && last) launch(k_denoise_atrous<true, true>);
-            else if (guide) launch(k_denoise_atrous<true, false>);
-            else if (last) launch(k_denoise_atrous<false, true>);
-            else launch(k_denoise_atrous<false, false>);
-            HIP_CHECK(hipGetLastError());
-        }
-        HIP_CHECK(hipMemcpyAsync(out, f->out.p, out_bytes, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        return SPT_OK;
-    });
+    std::lock_guard<std::mutex> lock(f->sc->mu);
+    return guarded("film_denoise", [&] { return film_denoise_locked(f, guide, params, FilmReadOut{out, nullptr}); });
 }
 
 spt_status spt_film_buckets(spt_film* f, uint32_t n_buckets) {
@@ -2821,37 +2859,55 @@ spt_status spt_film_read_buckets(spt_film* f, float* out) {
     });
 }
 
+// spt_film_read_robust behind its argument checks (the scene's lock is held)
+static spt_status film_read_robust_locked(spt_film* f, uint32_t estimator, const FilmReadOut& to) {
+    spt_scene* sc = f->sc;
+    const spt_render_params& p = f->plan;
+    if (f->n_buckets == 0u) fail(SPT_ERR_INVALID_ARG, "film_read_robust: the film has no buckets (spt_film_buckets)");
+    if (estimator > SPT_ROBUST_GMON) fail(SPT_ERR_INVALID_ARG, "film_read_robust: unknown SPT_ROBUST_* value");
+    if (f->done == 0) fail(SPT_ERR_INVALID_ARG, "film_read_robust: the film covers no samples yet");
+    if (f->rows == 0 || p.width == 0) return SPT_OK;
+    const uint32_t n_pix = f->rows * p.width, K = f->n_buckets;
+    const size_t bytes = (size_t)n_pix * 3 * sizeof(float);
+    HIP_CHECK(hipSetDevice(sc->device));
+    film_join(sc);
+    const hipStream_t st = sc->stream;
+    f->out.ensure(bytes);
+    const float kf = (float)K, gk = (float)(K + 1u) / (float)K, hf = (float)((K - 1u) / 2u);
+    const dim3 grid((n_pix * 3 + kBlock - 1) / kBlock), block(kBlock);
+    if (f->adaptive)
+        hipLaunchKernelGGL(k_film_read_robust<true>, grid, block, 0, st, estimator, n_pix * 3u, K, f->sum.as<float>(), f->buckets.as<float>(),
+                           (size_t)n_pix * 3, f->first, f->done, f->mask.as<uint8_t>(), f->counts.as<uint32_t>(), f->b_inv.as<float>(), kf, gk, hf,
+                           f->out.as<float>());
+    else
+        hipLaunchKernelGGL(k_film_read_robust<false>, grid, block, 0, st, estimator, n_pix * 3u, K, f->sum.as<float>(), f->buckets.as<float>(),
+                           (size_t)n_pix * 3, f->first, f->done, (const uint8_t*)nullptr, (const uint32_t*)nullptr, f->b_inv.as<float>(), kf, gk, hf,
+                           f->out.as<float>());
+    HIP_CHECK(hipGetLastError());
+    film_deliver(f, f->out.p, (size_t)n_pix * 3, to, st);
+    return SPT_OK;
+}
+
 spt_status spt_film_read_robust(spt_film* f, uint32_t estimator, float* out) {
     if (!f || !out) { g_error = "film_read_robust: null argument"; return SPT_ERR_INVALID_ARG; }
     if (f->fwd) return forwarded(f->fwd, f->fwd->film_read_robust(f->inner, estimator, out));
-    spt_scene* sc = f->sc;
-    std::lock_guard<std::mutex> lock(sc->mu);
-    return guarded("film_read_robust", [&] {
-        const spt_render_params& p = f->plan;
-        if (f->n_buckets == 0u) fail(SPT_ERR_INVALID_ARG, "film_read_robust: the film has no buckets (spt_film_buckets)");
-        if (estimator > SPT_ROBUST_GMON) fail(SPT_ERR_INVALID_ARG, "film_read_robust: unknown SPT_ROBUST_* value");
-        if (f->done == 0) fail(SPT_ERR_INVALID_ARG, "film_read_robust: the film covers no samples yet");
-        if (f->rows == 0 || p.width == 0) return SPT_OK;
-        const uint32_t n_pix = f->rows * p.width, K = f->n_buckets;
-        const size_t bytes = (size_t)n_pix * 3 * sizeof(float);
-        HIP_CHECK(hipSetDevice(sc->device));
-        film_join(sc);
-        const hipStream_t st = sc->stream;
-        f->out.ensure(bytes);
-        const float kf = (float)K, gk = (float)(K + 1u) / (float)K, hf = (float)((K - 1u) / 2u);
-        const dim3 grid((n_pix * 3 + kBlock - 1) / kBlock), block(kBlock);
-        if (f->adaptive)
-            hipLaunchKernelGGL(k_film_read_robust<true>, grid, block, 0, st, estimator, n_pix * 3u, K, f->sum.as<float>(), f->buckets.as<float>(),
-                               (size_t)n_pix * 3, f->first, f->done, f->mask.as<uint8_t>(), f->counts.as<uint32_t>(), f->b_inv.as<float>(), kf, gk, hf,
-                               f->out.as<float>());
-        else
-            hipLaunchKernelGGL(k_film_read_robust<false>, grid, block, 0, st, estimator, n_pix * 3u, K, f->sum.as<float>(), f->buckets.as<float>(),
-                               (size_t)n_pix * 3, f->first, f->done, (const uint8_t*)nullptr, (const uint32_t*)nullptr, f->b_inv.as<float>(), kf, gk, hf,
-                               f->out.as<float>());
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpyAsync(out, f->out.p, bytes, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        return SPT_OK;
+    std::lock_guard<std::mutex> lock(f->sc->mu);
+    return guarded("film_read_robust", [&] { return film_read_robust_locked(f, estimator, FilmReadOut{out, nullptr}); });
+}
+
+// The 8-bit read-out: the float image of `source` exactly as the matching call above stages it, then k_pack_rgb8.
+spt_status spt_film_read_rgb8(spt_film* f, uint32_t source, spt_film* guide, const spt_denoise_params* dn, uint8_t* out) {
+    if (!f || !out) { g_error = "film_read_rgb8: null argument"; return SPT_ERR_INVALID_ARG; }
+    if (source > SPT_READ_DENOISED) { g_error = "film_read_rgb8: unknown SPT_READ_* value"; return SPT_ERR_INVALID_ARG; }
+    const bool denoised = source == SPT_READ_DENOISED;
+    if (denoised && denoise_libraries_differ(f, guide)) return SPT_ERR_INVALID_ARG;
+    if (f->fwd) return forwarded(f->fwd, f->fwd->film_read_rgb8(f->inner, source, denoised && guide ? guide->inner : nullptr, dn, out));
+    std::lock_guard<std::mutex> lock(f->sc->mu);
+    return guarded("film_read_rgb8", [&] {
+        const FilmReadOut to{nullptr, out};
+        if (denoised) return film_denoise_locked(f, guide, dn, to);
+        if (source == SPT_READ_MEAN) return film_read_locked(f, SPT_FILM_MEAN, to);
+        return film_read_robust_locked(f, source == SPT_READ_ROBUST_MON ? SPT_ROBUST_MON : SPT_ROBUST_GMON, to);
     });
 }
 
@@ -2938,6 +2994,24 @@ spt_status spt_debug_detmath(int32_t device, uint32_t fn, uint32_t n, const floa
         hipLaunchKernelGGL(k_detmath, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, 0, fn, n, da.as<float>(), db.as<float>(), dout.as<float>());
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipMemcpy(out, dout.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+        return SPT_OK;
+    });
+}
+
+spt_status spt_debug_pack_rgb8(int32_t device, uint32_t n, const float* in, uint8_t* out) {
+    if (n && (!in || !out)) { g_error = "debug_pack_rgb8: null argument"; return SPT_ERR_INVALID_ARG; }
+    if (n == 0) return SPT_OK;
+    return guarded("debug_pack_rgb8", [&] {
+        if (n > 0xfffffffcu) fail(SPT_ERR_UNSUPPORTED, "debug_pack_rgb8: more than 2^32 - 4 floats");
+        int nd = usable_device_count();
+        if (nd <= 0) fail(SPT_ERR_NO_DEVICE, "no HIP device is visible: libspt_hip has no CPU fallback");
+        if (device < 0 || device >= nd) fail(SPT_ERR_NO_DEVICE, "device index out of range");
+        HIP_CHECK(hipSetDevice(device));
+        DeviceBuffer din, dout;
+        din.upload(in, n);
+        dout.alloc(n);
+        launch_pack_rgb8(n, din.as<float>(), dout.as<uint8_t>(), 0);
+        HIP_CHECK(hipMemcpy(out, dout.p, n, hipMemcpyDeviceToHost));
         return SPT_OK;
     });
 }

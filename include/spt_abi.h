@@ -368,7 +368,20 @@ enum {
     SPT_RENDER_DEBUG_NORMAL = 16u  /* ABI v13: the reference's cargo feature `debug_normal` (Cargo.toml:34-36, src/renderer/pt.rs:113-118):
                                       a path's colour is `normal * 0.5 + 0.5` of the first surface it reaches (the world-space
                                       interpolated normal Instance::intersect leaves in the Intersection), nothing is shaded */
+    ,
+    SPT_RENDER_AOV_ALBEDO = 32u    /* additive to ABI v14 (detect it with spt_render_flags_supported): a path's colour is the ALBEDO `a` of
+                                      the first surface it reaches; nothing is shaded, the path ends there, and a miss is black even
+                                      with an environment.  `a` is read from the material record as evaluated at the hit (a per-hit
+                                      recipe's textures, the P-NDF fallbacks), the three floats as they are:
+                                        a = c0         SPT_BXDF_LAMBERT; the plastic lobes (MICROFACET_PLASTIC, SPECULAR_PLASTIC,
+                                                       PNDF_PLASTIC); the conductors (MICROFACET_CONDUCTOR, SPECULAR_CONDUCTOR,
+                                                       PNDF_CONDUCTOR) whose fresnel is SPT_FRESNEL_SCHLICK (r0 = c0)
+                                        a = (1, 1, 1)  every other lobe: conductors with ConductorFresnel, both dielectrics, pseudo
+                                      The surface's emission and its normal map do not enter.  Together with SPT_RENDER_DEBUG_NORMAL
+                                      the plan is refused (SPT_ERR_INVALID_ARG) by spt_render and spt_film_create */
 };
+/* The SPT_RENDER_* bits this library honours (additive to ABI v14: a library without the symbol ignores unknown bits silently). */
+spt_status spt_render_flags_supported(uint32_t* mask);
 
 #define SPT_N_KERNELS 7
 /* SHADE_FIRST: the shade launches of bounce 0 (one per pass, nearly all path vertices); SHADE: bounces >= 1 */
@@ -508,6 +521,35 @@ typedef struct spt_denoise_params {
 /* out: rows * width * 3 f32, packed, like spt_film_read.  guide and params may be NULL (no guide term; the defaults
  * iterations 5, k_color 2, k_guide 1, eps_color 1e-8, eps_guide 1e-2). */
 spt_status spt_film_denoise(spt_film* film, spt_film* guide, const spt_denoise_params* params, float* out);
+
+/* ---- denoising with an albedo film (additive to ABI v14: detect it by symbol) ------------------------------------------------------
+ * spt_film_denoise_job is spt_film_denoise with a second guide, an ALBEDO film (any film of the same scene object, size and shard
+ * layout with SPT_FILM_MOMENTS and at least 2 samples, e.g. the same plan with SPT_RENDER_AOV_ALBEDO), and with albedo
+ * demodulation.  With albedo == NULL and flags without SPT_DENOISE_DEMODULATE the result is the bits of
+ * spt_film_denoise(film, guide, params, out).  With an albedo film the specification above is extended, every step one rounded
+ * f32 operation, in this order:
+ *     al, ua = SPT_FILM_MEAN, SPT_FILM_VAR_OF_MEAN of the albedo film;   av = (ua.r + ua.g) + ua.b
+ *     per tap, behind the guide's term (if there is a guide):
+ *         e = al(p) - al(q);   d = d + ((e.r * e.r + e.g * e.g) + e.b * e.b) / ((k_albedo * k_albedo) * (av(p) + av(q)) + eps_albedo)
+ *     SPT_DENOISE_DEMODULATE (needs an albedo film), per channel: dem = al > eps_demod ? al : eps_demod (a NaN albedo gives the floor)
+ *         c_0 = m / dem;   v' = v / (dem * dem);   lv_0 from v' with the luminance weights above
+ *         after the last iteration out = c_K * dem, for every pixel (those that passed through included)
+ * The filter then never compares texture detail: it sees colour / albedo, and the albedo's detail comes back unblurred.
+ * SPT_DENOISE_OUT_RGB8: `out` receives rows * width * 3 u8, the conversion of spt_film_read_rgb8; else rows * width * 3 f32.
+ * Refusals are those of spt_film_denoise (the albedo film is checked exactly as the guide is), plus SPT_ERR_INVALID_ARG for a null
+ * job, job->size below offsetof(spt_denoise_job, k_albedo), albedo == film or albedo == guide, unknown flags, DEMODULATE without an
+ * albedo film, a k_albedo, eps_albedo or eps_demod that is not finite and > 0, and films that are not all served by the same
+ * library.  The films are read only; the workspace belongs to `film`.  Synchronous. */
+enum { SPT_DENOISE_DEMODULATE = 1u, SPT_DENOISE_OUT_RGB8 = 2u };
+typedef struct spt_denoise_job {
+    uint32_t size, flags;             /* sizeof(spt_denoise_job) as the caller was compiled; SPT_DENOISE_* */
+    spt_film* guide;                  /* as in spt_film_denoise, may be NULL */
+    spt_film* albedo;                 /* may be NULL */
+    const spt_denoise_params* params; /* may be NULL: the defaults */
+    float k_albedo, eps_albedo, eps_demod;   /* finite and > 0; the defaults 1, 1e-2, 1e-2 when size ends before them */
+    uint32_t pad;
+} spt_denoise_job;
+spt_status spt_film_denoise_job(spt_film* film, const spt_denoise_job* job, void* out);
 
 /* ---- bucketed films: median-of-means read-outs (additive to ABI v14: detect it by symbol) ------------------------------------
  * spt_film_buckets makes a film keep K = n_buckets bucket sums B_0 .. B_{K-1} per pixel and channel next to S (and Q).  The sample

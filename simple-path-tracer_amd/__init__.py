@@ -182,6 +182,8 @@ RENDER_BOX_RADIUS = 2
 RENDER_COUNT_VISITS = 4
 RENDER_ASYNC = 8
 RENDER_DEBUG_NORMAL = 16   # the reference's cargo feature `debug_normal` (Cargo.toml:34-36, pt.rs:113-118)
+RENDER_AOV_ALBEDO = 32     # a path's colour is the albedo of the first surface it reaches (spt_abi.h); see render_flags_supported()
+DENOISE_DEMODULATE, DENOISE_OUT_RGB8 = 1, 2   # spt_denoise_job.flags
 READ_SOURCES = {"mean": 0, "mon": 1, "gmon": 2, "denoised": 3}   # SPT_READ_* of spt_film_read_rgb8
 FILM_MOMENTS = 1          # spt_film_create: also keep the per-channel sum of squared sample radiance (ABI v14)
 FILM_MEAN, FILM_SUM, FILM_SUM_SQ, FILM_VAR_OF_MEAN = 0, 1, 2, 3   # spt_film_read
@@ -211,6 +213,13 @@ class DenoiseParams(C.Structure):
     """spt_denoise_params (spt_film_denoise); `size` is sizeof of the struct."""
     _fields_ = [("size", C.c_uint32), ("iterations", C.c_uint32), ("k_color", C.c_float), ("k_guide", C.c_float),
                 ("eps_color", C.c_float), ("eps_guide", C.c_float)]
+
+
+class DenoiseJob(C.Structure):
+    """spt_denoise_job (spt_film_denoise_job); `size` is sizeof of the struct."""
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("guide", C.c_void_p), ("albedo", C.c_void_p),
+                ("params", C.POINTER(DenoiseParams)), ("k_albedo", C.c_float), ("eps_albedo", C.c_float), ("eps_demod", C.c_float),
+                ("pad", C.c_uint32)]
 
 
 HIT_DTYPE = np.dtype([("t", "<f4"), ("instance", "<i4"), ("prim", "<i4"), ("v", "<f4"), ("w", "<f4")])
@@ -305,6 +314,9 @@ def hip_lib() -> C.CDLL:
             lib.spt_film_buckets.argtypes = [C.c_void_p, C.c_uint32]
             lib.spt_film_read_buckets.argtypes = [C.c_void_p, C.c_void_p]
             lib.spt_film_read_robust.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        if hasattr(lib, "spt_film_denoise_job"):   # (the same)
+            lib.spt_film_denoise_job.argtypes = [C.c_void_p, C.POINTER(DenoiseJob), C.c_void_p]
+            lib.spt_render_flags_supported.argtypes = [C.POINTER(C.c_uint32)]
         if hasattr(lib, "spt_film_read_rgb8"):   # (the same)
             lib.spt_film_read_rgb8.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p]
             lib.spt_debug_pack_rgb8.argtypes = [C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]
@@ -485,7 +497,8 @@ class PathTracer:
     """reference PathTracer{max_depth, pixel_sampler, filter} (src/renderer/pt.rs:24-37)."""
 
     def __init__(self, max_depth: int = 8, sampler: int = SAMPLER_RECURRENCE, spp: int = 256,
-                 division_x: int = 0, division_y: int = 0, filter_radius: float = 0.5, seed: int = 1, debug_normal: bool = False):
+                 division_x: int = 0, division_y: int = 0, filter_radius: float = 0.5, seed: int = 1, debug_normal: bool = False,
+                 aov_albedo: bool = False):
         self.max_depth = max_depth
         self.sampler = sampler
         self.spp = spp
@@ -494,6 +507,7 @@ class PathTracer:
         self.filter_radius = filter_radius
         self.seed = seed
         self.debug_normal = debug_normal   # a build of the reference with `--features debug_normal`: colour = normal * 0.5 + 0.5
+        self.aov_albedo = aov_albedo       # RENDER_AOV_ALBEDO: colour = the albedo of the first surface (not together with debug_normal)
         self.last_stats: Optional[RenderStats] = None
 
     def params(self, width: int, height: int, shard_index: int = 0, shard_count: int = 1, strip_rows: int = 16,
@@ -503,7 +517,7 @@ class PathTracer:
         p.sampler, p.division_x, p.division_y = self.sampler, self.division_x, self.division_y
         p.seed = self.seed
         p.shard_index, p.shard_count, p.strip_rows = shard_index, shard_count, strip_rows
-        p.samples_per_pass, p.flags = samples_per_pass, flags | (RENDER_DEBUG_NORMAL if self.debug_normal else 0)
+        p.samples_per_pass, p.flags = samples_per_pass, flags | (RENDER_DEBUG_NORMAL if self.debug_normal else 0) | (RENDER_AOV_ALBEDO if self.aov_albedo else 0)
         p.stats_size = C.sizeof(RenderStats)
         if self.filter_radius != 0.5:
             # BoxFilter of any radius (src/filter/boxf.rs): Film::filter_pixel sums the UNWEIGHTED colours of the
@@ -570,6 +584,11 @@ class PathTracer:
         """The guide of ProgressiveFilm.denoise: a film of the same plan with debug_normal (its mean is the first-hit normal
         * 0.5 + 0.5) and moments (its variance tells the filter how far to trust it).  Render a few samples into it."""
         return ProgressiveFilm(self, scene, config, device, moments=True, flags=RENDER_DEBUG_NORMAL)
+
+    def albedo_film(self, scene: Scene, config: OutputConfig, device: int = 0) -> "ProgressiveFilm":
+        """The albedo film of ProgressiveFilm.denoise_job: a film of the same plan with RENDER_AOV_ALBEDO (its mean is the
+        first-hit albedo) and moments.  Render a few samples into it."""
+        return ProgressiveFilm(self, scene, config, device, moments=True, flags=RENDER_AOV_ALBEDO)
 
     def wait(self, scene: Scene, device: int = 0) -> None:
         """spt_render_wait: every render_shard(..., wait=False) queued on the scene has delivered its film."""
@@ -706,6 +725,25 @@ class ProgressiveFilm:
         params = DenoiseParams(C.sizeof(DenoiseParams), iterations, k_color, k_guide, eps_color, eps_guide)
         _check_hip(hip_lib().spt_film_denoise(self._handle(), guide._handle() if guide is not None else None, C.byref(params),
                                               out.ctypes.data))
+        return out
+
+    def denoise_job(self, guide: Optional["ProgressiveFilm"] = None, albedo: Optional["ProgressiveFilm"] = None, demodulate: bool = False,
+                    rgb8: bool = False, **params) -> np.ndarray:
+        """spt_film_denoise_job: denoise() with a second guide, an `albedo` film (PathTracer.albedo_film), and - demodulate - the
+        filter run on mean / albedo with the albedo multiplied back, which keeps texture detail.  `params` are denoise()'s
+        keywords plus k_albedo, eps_albedo (the albedo term) and eps_demod (the floor of the divisor).  Without albedo and
+        demodulate it returns the bits of denoise(guide, ...).  (rows, width, 3) f32, or u8 with rgb8 (the conversion of read_rgb8)."""
+        d = dict(iterations=5, k_color=2.0, k_guide=1.0, eps_color=1e-8, eps_guide=1e-2, k_albedo=1.0, eps_albedo=1e-2, eps_demod=1e-2)
+        unknown = set(params) - set(d)
+        if unknown:
+            raise TypeError("denoise_job: unknown parameter(s) %s" % ", ".join(sorted(unknown)))
+        d.update(params)
+        dp = DenoiseParams(C.sizeof(DenoiseParams), d["iterations"], d["k_color"], d["k_guide"], d["eps_color"], d["eps_guide"])
+        job = DenoiseJob(C.sizeof(DenoiseJob), (DENOISE_DEMODULATE if demodulate else 0) | (DENOISE_OUT_RGB8 if rgb8 else 0),
+                         guide._handle() if guide is not None else None, albedo._handle() if albedo is not None else None, C.pointer(dp),
+                         d["k_albedo"], d["eps_albedo"], d["eps_demod"], 0)
+        out = np.zeros((self.rows, self.width, 3), dtype=np.uint8 if rgb8 else np.float32)
+        _check_hip(hip_lib().spt_film_denoise_job(self._handle(), C.byref(job), out.ctypes.data))
         return out
 
     def _handle(self):
@@ -1018,3 +1056,14 @@ def device_count() -> int:
     n = C.c_int32()
     _check_hip(hip_lib().spt_device_count(C.byref(n)))
     return n.value
+
+
+def render_flags_supported() -> int:
+    """spt_render_flags_supported: the RENDER_* bits the loaded library honours.  A library without the call (it ignores
+    unknown bits silently) honours the five flags up to RENDER_DEBUG_NORMAL."""
+    lib = hip_lib()
+    if not hasattr(lib, "spt_render_flags_supported"):
+        return RENDER_PROFILE | RENDER_BOX_RADIUS | RENDER_COUNT_VISITS | RENDER_ASYNC | RENDER_DEBUG_NORMAL
+    mask = C.c_uint32()
+    _check_hip(lib.spt_render_flags_supported(C.byref(mask)))
+    return mask.value

@@ -8,7 +8,9 @@
 // per-pixel variance of the mean, --adaptive REL [--adaptive-floor A] [--adaptive-min-samples N] retires converged pixels after
 // every increment (spt_film_adapt) and stops once none is active, --samples-out PATH.exr writes each pixel's sample count,
 // --denoise [--denoise-iterations K] [--guide-samples N] [--noisy-out PATH] renders N samples of a first-hit normal film first and
-// writes every preview and the final image through the edge-aware filter (spt_film_denoise), the plain mean to PATH,
+// writes every preview and the final image through the edge-aware filter (spt_film_denoise), the plain mean to PATH;
+// --guide normal|albedo|both picks the guide films (albedo: the same plan with SPT_RENDER_AOV_ALBEDO, spt_film_denoise_job),
+// --demodulate filters colour / albedo and multiplies the albedo back, --albedo-out PATH writes the albedo film's mean,
 // --robust K [--robust-estimator mon|gmon] [--mean-out PATH] keeps K bucket sums per pixel (spt_film_buckets) and writes every preview
 // and the final image from their median (mon) or Gini-adaptive trimmed mean (gmon, the default), the plain mean to PATH.  It loads the scene
 // with libspt_host, renders with libspt_hip (HIP kernels only) and writes the image; like the reference it reports the
@@ -30,7 +32,8 @@ static void usage() {
                  "           [--seed N] [--spp N] [--device D | --gpus N | --devices a,b,..] [--strip-rows R] [--debug-normal] [--bezier-ni]\n"
                  "           [--preview-every K] [--time-limit SEC] [--variance-out var.exr]\n"
                  "           [--adaptive REL [--adaptive-floor A] [--adaptive-min-samples N]] [--samples-out counts.exr]\n"
-                 "           [--denoise [--denoise-iterations K] [--guide-samples N] [--noisy-out noisy.png]]\n"
+                 "           [--denoise [--denoise-iterations K] [--guide-samples N] [--noisy-out noisy.png]\n"
+                 "            [--guide normal|albedo|both] [--demodulate] [--albedo-out albedo.png]]\n"
                  "           [--robust K [--robust-estimator mon|gmon] [--mean-out mean.png]]   (K odd, 3 .. 15)\n");
 }
 
@@ -48,7 +51,8 @@ int main(int argc, char** argv) {
     uint32_t adaptive_min = 16;
     bool denoise = false;
     uint32_t denoise_iterations = 5, guide_samples = 16;
-    std::string noisy_out;
+    std::string noisy_out, guide_mode = "normal", albedo_out;
+    bool demodulate = false;
     bool robust = false;
     int robust_k = 0;
     std::string robust_estimator, mean_out;
@@ -92,6 +96,9 @@ int main(int argc, char** argv) {
         else if (a == "--denoise-iterations") { denoise_iterations = (uint32_t)std::atoi(next()); denoise = true; }
         else if (a == "--guide-samples") { guide_samples = (uint32_t)std::atoi(next()); denoise = true; }
         else if (a == "--noisy-out") { noisy_out = next(); denoise = true; }
+        else if (a == "--guide") { guide_mode = next(); denoise = true; }
+        else if (a == "--demodulate") { demodulate = true; denoise = true; }
+        else if (a == "--albedo-out") { albedo_out = next(); denoise = true; }
         else if (a == "--robust") { robust_k = std::atoi(next()); robust = true; }
         else if (a == "--robust-estimator") robust_estimator = next();
         else if (a == "--mean-out") mean_out = next();
@@ -113,6 +120,15 @@ int main(int argc, char** argv) {
     }
     if (robust && denoise) {
         std::fprintf(stderr, "Error: --robust and --denoise exclude each other (the denoiser filters the plain mean)\n");
+        return 2;
+    }
+    if (guide_mode != "normal" && guide_mode != "albedo" && guide_mode != "both") {
+        std::fprintf(stderr, "Error: --guide %s: normal, albedo or both\n", guide_mode.c_str());
+        return 2;
+    }
+    const bool guide_normal = guide_mode != "albedo", guide_albedo = guide_mode != "normal";
+    if ((demodulate || !albedo_out.empty()) && !guide_albedo) {
+        std::fprintf(stderr, "Error: --demodulate and --albedo-out need the albedo film (--guide albedo or --guide both)\n");
         return 2;
     }
     const uint32_t estimator = robust_estimator == "mon" ? (uint32_t)SPT_ROBUST_MON : (uint32_t)SPT_ROBUST_GMON;
@@ -220,8 +236,10 @@ int main(int argc, char** argv) {
         // the film takes the plan's samples in increments; the mean after all of them has the bits of one spt_render
         spt_film* pf = nullptr;
         spt_film* guide = nullptr;   // --denoise: the same plan with SPT_RENDER_DEBUG_NORMAL, a first-hit normal film
-        auto film_fail = [&]() {
-            std::fprintf(stderr, "Error: %s\n", spt_last_error());
+        spt_film* albedo = nullptr;  // --guide albedo | both: the same plan with SPT_RENDER_AOV_ALBEDO, a first-hit albedo film
+        auto film_fail = [&](const char* why = nullptr) {
+            std::fprintf(stderr, "Error: %s\n", why ? why : spt_last_error());
+            if (albedo) spt_film_destroy(albedo);
             if (guide) spt_film_destroy(guide);
             if (pf) spt_film_destroy(pf);
             spt_scene_destroy(ds);
@@ -232,17 +250,35 @@ int main(int argc, char** argv) {
         if (spt_film_create(ds, &cam, &params, 0, moments ? (uint32_t)SPT_FILM_MOMENTS : 0u, &pf) != SPT_OK) return film_fail();
         if (robust && spt_film_buckets(pf, (uint32_t)robust_k) != SPT_OK) return film_fail();
         const spt_denoise_params dn = {(uint32_t)sizeof(spt_denoise_params), denoise_iterations, 2.0f, 1.0f, 1e-8f, 1e-2f};
-        if (denoise) {   // the guide's samples come first: every preview is filtered with the whole guide
+        if (denoise && guide_normal) {   // the guide's samples come first: every preview is filtered with the whole guide
             spt_render_params gp = params;
             gp.flags |= SPT_RENDER_DEBUG_NORMAL;
             if (spt_film_create(ds, &cam, &gp, 0, (uint32_t)SPT_FILM_MOMENTS, &guide) != SPT_OK) return film_fail();
             if (spt_film_render(guide, std::max(2u, std::min(params.spp, guide_samples))) != SPT_OK) return film_fail();
         }
+        if (denoise && guide_albedo) {
+            uint32_t honoured = 0;
+            if (spt_render_flags_supported(&honoured) != SPT_OK) return film_fail();
+            if (!(honoured & SPT_RENDER_AOV_ALBEDO)) return film_fail("this libspt_hip.so renders no albedo films");
+            spt_render_params ap = params;
+            ap.flags = (ap.flags & ~(uint32_t)SPT_RENDER_DEBUG_NORMAL) | SPT_RENDER_AOV_ALBEDO;
+            if (spt_film_create(ds, &cam, &ap, 0, (uint32_t)SPT_FILM_MOMENTS, &albedo) != SPT_OK) return film_fail();
+            if (spt_film_render(albedo, std::max(2u, std::min(params.spp, guide_samples))) != SPT_OK) return film_fail();
+        }
+        spt_denoise_job job;
+        std::memset(&job, 0, sizeof job);
+        job.size = (uint32_t)sizeof job;
+        job.flags = SPT_DENOISE_OUT_RGB8 | (demodulate ? (uint32_t)SPT_DENOISE_DEMODULATE : 0u);
+        job.guide = guide;
+        job.albedo = albedo;
+        job.params = &dn;
+        job.k_albedo = 1.0f; job.eps_albedo = 1e-2f; job.eps_demod = 1e-2f;
         // the image of a preview and of the end: the film's mean, the filtered mean (after one sample there is no variance yet)
         // or the robust read-out of the buckets
         film8.resize(film.size());
         auto read_image = [&]() {
             if (robust) return spt_film_read_rgb8(pf, estimator == (uint32_t)SPT_ROBUST_MON ? SPT_READ_ROBUST_MON : SPT_READ_ROBUST_GMON, nullptr, nullptr, film8.data());
+            if (denoise && done >= 2 && albedo) return spt_film_denoise_job(pf, &job, film8.data());
             return denoise && done >= 2 ? spt_film_read_rgb8(pf, SPT_READ_DENOISED, guide, &dn, film8.data())
                                         : spt_film_read_rgb8(pf, SPT_READ_MEAN, nullptr, nullptr, film8.data());
         };
@@ -265,6 +301,10 @@ int main(int argc, char** argv) {
             if (spt_film_read_rgb8(pf, SPT_READ_MEAN, nullptr, nullptr, film8.data()) != SPT_OK) return film_fail();
             write_image8(noisy_out);
         }
+        if (!albedo_out.empty()) {
+            if (spt_film_read_rgb8(albedo, SPT_READ_MEAN, nullptr, nullptr, film8.data()) != SPT_OK) return film_fail();
+            write_image8(albedo_out);
+        }
         if (!mean_out.empty()) {
             if (spt_film_read_rgb8(pf, SPT_READ_MEAN, nullptr, nullptr, film8.data()) != SPT_OK) return film_fail();
             write_image8(mean_out);
@@ -285,6 +325,7 @@ int main(int argc, char** argv) {
             if (spt_film_read(pf, SPT_FILM_VAR_OF_MEAN, var.data()) != SPT_OK) return film_fail();
             if (spt_host_write_exr(variance_out.c_str(), var.data(), width, height) != SPT_OK) {
                 std::fprintf(stderr, "Error: %s\n", spt_host_last_error());
+                if (albedo) spt_film_destroy(albedo);
                 if (guide) spt_film_destroy(guide);
                 spt_film_destroy(pf);
                 spt_scene_destroy(ds);
@@ -299,6 +340,7 @@ int main(int argc, char** argv) {
             for (size_t k = 0; k < counts.size(); ++k) rgb[3 * k] = rgb[3 * k + 1] = rgb[3 * k + 2] = (float)counts[k];
             if (spt_host_write_exr(samples_out.c_str(), rgb.data(), width, height) != SPT_OK) {
                 std::fprintf(stderr, "Error: %s\n", spt_host_last_error());
+                if (albedo) spt_film_destroy(albedo);
                 if (guide) spt_film_destroy(guide);
                 spt_film_destroy(pf);
                 spt_scene_destroy(ds);
@@ -306,6 +348,7 @@ int main(int argc, char** argv) {
                 return 1;
             }
         }
+        if (albedo) spt_film_destroy(albedo);
         if (guide) spt_film_destroy(guide);
         spt_film_destroy(pf);
     }

@@ -442,22 +442,33 @@ struct DenoiseArgs {
     float kc2, kg2, eps_c, eps_g;     // k_color^2, k_guide^2 (multiplied by the host), the two epsilons
 };
 
-// One tap of the filter: pixel q (colour record cq, guide record gq, spline weight hw) seen from pixel p, added to p's three sums.
+// The distance d of one tap before the cut-off: the luminance term and - kGuide - the guide's term (pixel q seen from pixel p).
 template <bool kGuide>
-SPT_DEV void denoise_tap(const DenoiseArgs& a, const float4& cp, const float4& gp, float l_p, const float4& cq, const float4& gq, float hw,
-                         f3& acc, float& ws, float& va) {
-    if (!denoise_ok(cq)) return;
+SPT_DEV float denoise_dist(const DenoiseArgs& a, const float4& cp, const float4& gp, float l_p, const float4& cq, const float4& gq) {
     const float dl = l_p - luminance(mk3(cq.x, cq.y, cq.z));
     float d = (dl * dl) / (a.kc2 * (cp.w + cq.w) + a.eps_c);
     if constexpr (kGuide) {
         const float ex = gp.x - gq.x, ey = gp.y - gq.y, ez = gp.z - gq.z;
         d = d + ((ex * ex + ey * ey) + ez * ez) / (a.kg2 * (gp.w + gq.w) + a.eps_g);
     }
+    return d;
+}
+
+// A tap at distance d with spline weight hw, added to p's three sums.
+SPT_DEV void denoise_add(float d, const float4& cq, float hw, f3& acc, float& ws, float& va) {
     if (!(d < 87.0f)) return;   // (also a NaN; spt_exp(-d) is 0 beyond)
     const float w = hw * spt_exp(-d);
     acc = mk3(acc.x + w * cq.x, acc.y + w * cq.y, acc.z + w * cq.z);
     ws = ws + w;
     va = va + (w * w) * cq.w;
+}
+
+// One tap of the filter: pixel q (colour record cq, guide record gq, spline weight hw) seen from pixel p, added to p's three sums.
+template <bool kGuide>
+SPT_DEV void denoise_tap(const DenoiseArgs& a, const float4& cp, const float4& gp, float l_p, const float4& cq, const float4& gq, float hw,
+                         f3& acc, float& ws, float& va) {
+    if (!denoise_ok(cq)) return;
+    denoise_add(denoise_dist<kGuide>(a, cp, gp, l_p, cq, gq), cq, hw, acc, ws, va);
 }
 
 // What a pixel becomes after its 25 taps; kLast: packed RGB f32 (the film's read-out staging buffer), the variance is dropped.
@@ -515,6 +526,98 @@ __global__ void __launch_bounds__(256) k_denoise_atrous(DenoiseArgs a, const flo
             if (in[k]) denoise_tap<kGuide>(a, cp, gp, l_p, cq[k], gq[k], hy * denoise_h(k - 2), acc, ws, va);
     }
     denoise_store<kLast>(lp, cp, acc, ws, va, color_out, rgb_out);
+}
+
+// ---- the albedo variants (spt_film_denoise_job with an albedo film) ----------------------------------------------------------
+// A third record per pixel, (al.r, al.g, al.b, av): the albedo film's mean and the summed variance of that mean.  Its term joins d
+// behind the guide's; with `demodulate` the colour record holds m / dem and the variance v / (dem * dem), dem = max(al, eps_demod)
+// per channel (a NaN albedo gives the floor), and the last iteration multiplies dem back.  spt_abi.h has the arithmetic.
+struct DenoiseAlbedo {
+    float ka2, eps_a, eps_d;   // k_albedo^2 (multiplied by the host), eps_albedo, eps_demod
+    uint32_t demodulate;
+};
+
+SPT_DEV f3 denoise_dem(const float4& al, float eps_d) {
+    return mk3(al.x > eps_d ? al.x : eps_d, al.y > eps_d ? al.y : eps_d, al.z > eps_d ? al.z : eps_d);
+}
+
+template <bool kGuide>
+__global__ void __launch_bounds__(256) k_denoise_pack_albedo(uint32_t n_pixels, DenoiseFilm film, DenoiseFilm guide, DenoiseFilm albedo, DenoiseAlbedo b,
+                                                             float4* color_out, float4* guide_out, float4* albedo_out) {
+    const uint32_t lp = blockIdx.x * blockDim.x + threadIdx.x;
+    if (lp >= n_pixels) return;
+    f3 m, v, al, ua;
+    denoise_film_pixel(film, lp, &m, &v);
+    denoise_film_pixel(albedo, lp, &al, &ua);
+    const float4 ar = make_float4(al.x, al.y, al.z, (ua.x + ua.y) + ua.z);
+    if (b.demodulate != 0u) {
+        const f3 dem = denoise_dem(ar, b.eps_d);
+        m = mk3(m.x / dem.x, m.y / dem.y, m.z / dem.z);
+        v = mk3(v.x / (dem.x * dem.x), v.y / (dem.y * dem.y), v.z / (dem.z * dem.z));
+    }
+    const float lv = ((0.299f * 0.299f) * v.x + (0.587f * 0.587f) * v.y) + (0.114f * 0.114f) * v.z;
+    color_out[lp] = make_float4(m.x, m.y, m.z, lv);
+    albedo_out[lp] = ar;
+    if constexpr (kGuide) {
+        f3 g, u;
+        denoise_film_pixel(guide, lp, &g, &u);
+        guide_out[lp] = make_float4(g.x, g.y, g.z, (u.x + u.y) + u.z);
+    }
+}
+
+// k_denoise_atrous with the albedo record: one more 16-byte load per tap (a row of five is 15 loads with a guide), the same order
+// of the sums.  kLast: the demodulated colour is multiplied by dem in the store, pass-through pixels included.
+template <bool kGuide, bool kLast>
+__global__ void __launch_bounds__(256) k_denoise_atrous_albedo(DenoiseArgs a, DenoiseAlbedo b, const float4* __restrict__ color_in,
+                                                               const float4* __restrict__ guide, const float4* __restrict__ albedo,
+                                                               float4* __restrict__ color_out, float* __restrict__ rgb_out) {
+    const uint32_t tile = blockIdx.x, tx = tile % a.tiles_x, ty = tile / a.tiles_x;
+    const int32_t x = (int32_t)(tx * 16u + (threadIdx.x % 16u)), y = (int32_t)(ty * 16u + (threadIdx.x / 16u));
+    if (x >= (int32_t)a.width || y >= (int32_t)a.rows) return;
+    const uint32_t lp = (uint32_t)y * a.width + (uint32_t)x;
+    const float4 cp = color_in[lp], ap = albedo[lp];
+    float4 gp = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if constexpr (kGuide) gp = guide[lp];
+    const float l_p = luminance(mk3(cp.x, cp.y, cp.z));
+    f3 acc = mk3(0, 0, 0);
+    float ws = 0.0f, va = 0.0f;
+#pragma unroll 1
+    for (int32_t dy = -2; dy <= 2; ++dy) {
+        const int32_t qy = y + a.step * dy;
+        const bool row_in = qy >= 0 && qy < (int32_t)a.rows;
+        float4 cq[5], gq[5], aq[5];
+        bool in[5];
+#pragma unroll
+        for (int32_t k = 0; k < 5; ++k) {
+            const int32_t qx = x + a.step * (k - 2);
+            in[k] = row_in && qx >= 0 && qx < (int32_t)a.width;
+            const uint32_t lq = in[k] ? (uint32_t)qy * a.width + (uint32_t)qx : lp;
+            cq[k] = color_in[lq];
+            aq[k] = albedo[lq];
+            gq[k] = gp;
+            if constexpr (kGuide) gq[k] = guide[lq];
+        }
+        const float hy = denoise_h(dy);
+#pragma unroll
+        for (int32_t k = 0; k < 5; ++k)
+            if (in[k] && denoise_ok(cq[k])) {
+                float d = denoise_dist<kGuide>(a, cp, gp, l_p, cq[k], gq[k]);
+                const float ex = ap.x - aq[k].x, ey = ap.y - aq[k].y, ez = ap.z - aq[k].z;
+                d = d + ((ex * ex + ey * ey) + ez * ez) / (b.ka2 * (ap.w + aq[k].w) + b.eps_a);
+                denoise_add(d, cq[k], hy * denoise_h(k - 2), acc, ws, va);
+            }
+    }
+    float4 r = cp;   // a pixel that is not ok passes through
+    if (denoise_ok(cp)) r = make_float4(acc.x / ws, acc.y / ws, acc.z / ws, va / (ws * ws));
+    if constexpr (kLast) {
+        if (b.demodulate != 0u) {
+            const f3 dem = denoise_dem(ap, b.eps_d);
+            r.x = r.x * dem.x; r.y = r.y * dem.y; r.z = r.z * dem.z;
+        }
+        rgb_out[3 * lp] = r.x; rgb_out[3 * lp + 1] = r.y; rgb_out[3 * lp + 2] = r.z;
+    } else {
+        color_out[lp] = r;
+    }
 }
 
 // radius_int >= 1: Film::filter_pixel (film.rs:71-92) over the kept samples of a band of whole rows.  Rows j, then

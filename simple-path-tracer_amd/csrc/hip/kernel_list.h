@@ -98,6 +98,12 @@
     X((k_shade<5, true, false, false, true>), SPT_ARGS_BOUNCE)       \
     X((k_shade<5, false, false, false, true>), SPT_ARGS_BOUNCE)
 
+// k_shade_albedo<kTex, kPndf>: the bounce-0 stage of an albedo plan (SPT_RENDER_AOV_ALBEDO)
+#define SPT_KERNELS_ALBEDO(X)                                        \
+    X((k_shade_albedo<false, false>), SPT_ARGS_BOUNCE)               \
+    X((k_shade_albedo<true, false>), SPT_ARGS_BOUNCE)                \
+    X((k_shade_albedo<true, true>), SPT_ARGS_BOUNCE)
+
 #if defined(SPT_INSTANTIATE_GROUP_PRIMARY)
 SPT_KERNELS_PRIMARY(SPT_DEFINE_KERNEL)
 #elif defined(SPT_INSTANTIATE_GROUP_RAYS)
@@ -120,6 +126,8 @@ SPT_KERNELS_SHADE4(SPT_DEFINE_KERNEL)
 SPT_KERNELS_SHADE5A(SPT_DEFINE_KERNEL)
 #elif defined(SPT_INSTANTIATE_GROUP_SHADE5B)
 SPT_KERNELS_SHADE5B(SPT_DEFINE_KERNEL)
+#elif defined(SPT_INSTANTIATE_GROUP_ALBEDO)
+SPT_KERNELS_ALBEDO(SPT_DEFINE_KERNEL)
 #else
 SPT_KERNELS_PRIMARY(SPT_DECLARE_KERNEL)
 SPT_KERNELS_RAYS(SPT_DECLARE_KERNEL)
@@ -132,4 +140,5 @@ SPT_KERNELS_SHADE3B(SPT_DECLARE_KERNEL)
 SPT_KERNELS_SHADE4(SPT_DECLARE_KERNEL)
 SPT_KERNELS_SHADE5A(SPT_DECLARE_KERNEL)
 SPT_KERNELS_SHADE5B(SPT_DECLARE_KERNEL)
+SPT_KERNELS_ALBEDO(SPT_DECLARE_KERNEL)
 #endif

@@ -907,6 +907,65 @@ __global__ void __launch_bounds__(256, (kFeat == 0 && kFirst && kFused && SPT_SH
     }   // classes
 }
 
+// ---------------------------------------------------------------------------- first-hit albedo (SPT_RENDER_AOV_ALBEDO)
+// The bounce-0 stage of an albedo plan, in k_shade<., kFirst>'s place: a path's colour is the albedo of the evaluated material
+// record of its first surface (mat_albedo), written to its radiance slot, and the path ends.  A kernel of its own rather than a
+// branch of k_shade: with the branch behind rc.debug_normal == 2 the general shade instances kept material_at's result alive
+// across it and gained scratch (k_shade<1, true>: 24 -> 124 bytes) and SGPR spills, which every plan would have paid for; this
+// way a plan without the flag runs the code it ran before.  It reads the compact records k_primary wrote (every class of the hit
+// queue) and the shading tables from memory; kTex: texcoords, the camera ray differentials and the per-hit recipes, as in
+// k_shade<2 ..>; kPndf: the glint footprint walk of material_at.  One material_at call site.
+template <bool kTex, bool kPndf>
+__global__ void __launch_bounds__(256) k_shade_albedo(DScene sc, RenderCtx rc, uint32_t bounce) {
+    const uint32_t shard = blockIdx.x % kShards;
+    const uint32_t qbase = shard * rc.shard_cap;
+    const uint32_t stride = (gridDim.x / kShards) * blockDim.x;
+    for (uint32_t cls = 0; cls < rc.n_classes; ++cls) {
+        const uint32_t n = *q_count(rc.counts, bounce, q_hit_kind(cls), shard);
+        const uint32_t hbase = cls * rc.class_cap + qbase;
+        for (uint32_t i = (blockIdx.x / kShards) * blockDim.x + threadIdx.x; i < n; i += stride) {
+            const uint32_t idx = hbase + i;
+            const float4 hv = rc.hits.t_v_w_prim[idx], b = rc.qa.d_pdf[idx];
+            const uint2 is = rc.hits.inst_src[idx];
+            const uint32_t slot = __float_as_uint(b.w);
+            DRay ray;
+            ray.o = rc.cam.eye; ray.t_min = kTMinEps;
+            ray.d = mk3(b);
+            DHit h;
+            h.t = hv.x; h.v = hv.y; h.w = hv.z; h.prim = __float_as_int(hv.w);
+            h.inst = rc.pack_first ? (int32_t)(is.x & 0xfffffu) : (int32_t)is.x;
+            DInter it = reconstruct_hit<kTex, false>(sc, ray, h);
+            if (kTex) {   // the auxiliary rays of the sample's pixel offsets, as k_shade<., kFirst> rebuilds them (pt.rs:51-53, 272-275)
+                uint32_t s_local, pix, j, col;
+                if (rc.pack_first) {
+                    s_local = is.x >> 20;
+                    pix = is.y;
+                    j = pix / rc.width; col = pix - j * rc.width;
+                } else {
+                    s_local = slot / rc.n_pixels;
+                    const uint32_t lp = slot - s_local * rc.n_pixels;
+                    const uint32_t row_local = lp / rc.width;
+                    col = lp - row_local * rc.width;
+                    j = global_row(rc, row_local);
+                    pix = j * rc.width + col;
+                }
+                DRng rng;
+                rng.s = spt_rng_seed(rc.seed, pix, rc.pass_first + s_local);
+                float ox, oy;
+                pixel_offset(rc, pix, rc.pass_first + s_local, rng, &ox, &oy);
+                const float x = (((float)col + ox) * rc.width_inv - 0.5f) * rc.aspect;
+                const float y = ((float)(rc.height - j - 1u) + oy) * rc.height_inv - 0.5f;
+                const f3 aux_xd = normalize((rc.cam.forward * rc.cam.half_cot + rc.cam.right * (x + rc.aux_dx)) + rc.cam.up * y);
+                const f3 aux_yd = normalize((rc.cam.forward * rc.cam.half_cot + rc.cam.right * x) + rc.cam.up * (y + rc.aux_dy));
+                calc_differential(it, ray, h.t, rc.cam.eye, aux_xd, rc.cam.eye, aux_yd);
+            }
+            const spt_surface sf = load_surface<false>(sc, it.surface);
+            const DMat mt = material_at<kTex, false, kPndf>(sc, sf.material, it);
+            rad_store(rc, slot, mat_albedo(mt));
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------- shadow
 // kFlat (with kLds, kCount off): the exhaustive loops of flat.h instead of the tree walk
 template <bool kLds, bool kCount = false, bool kFlat = false>

@@ -636,6 +636,14 @@ SPT_DEV DMat material_at(const DScene& sc, uint32_t m, const DInter& it) {
 SPT_DEV bool mat_is_delta(const DMat& m) {
     return m.bxdf == SPT_BXDF_SPECULAR_CONDUCTOR || m.bxdf == SPT_BXDF_SPECULAR_DIELECTRIC || m.bxdf == SPT_BXDF_PSEUDO;
 }
+// SPT_RENDER_AOV_ALBEDO (spt_abi.h): c0 where it is a reflectance - Lambert, the plastic lobes' substrate, a conductor with
+// SchlickFresnel (r0 = c0) - and white for every other lobe.  The floats as they are in the evaluated record.
+SPT_DEV f3 mat_albedo(const DMat& m) {
+    const bool plastic = m.bxdf == SPT_BXDF_MICROFACET_PLASTIC || m.bxdf == SPT_BXDF_SPECULAR_PLASTIC || m.bxdf == SPT_BXDF_PNDF_PLASTIC;
+    const bool conductor = m.bxdf == SPT_BXDF_MICROFACET_CONDUCTOR || m.bxdf == SPT_BXDF_SPECULAR_CONDUCTOR || m.bxdf == SPT_BXDF_PNDF_CONDUCTOR;
+    if (m.bxdf == SPT_BXDF_LAMBERT || plastic || (conductor && m.fresnel == SPT_FRESNEL_SCHLICK)) return m.c0;
+    return gray(1.0f);
+}
 SPT_DEV float pow5(float x) { return x * x * x * x * x; }
 SPT_DEV f3 mat_fresnel(const DMat& m, f3 i, f3 n) {  // fresnel.rs:29-59
     if (m.bxdf == SPT_BXDF_MICROFACET_CONDUCTOR || m.bxdf == SPT_BXDF_SPECULAR_CONDUCTOR || m.bxdf == SPT_BXDF_PNDF_CONDUCTOR) {

@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <array>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -514,6 +515,7 @@ struct BezierLib {
     decltype(&spt_film_adapt) film_adapt = nullptr;
     decltype(&spt_film_read_counts) film_read_counts = nullptr;
     decltype(&spt_film_denoise) film_denoise = nullptr;
+    decltype(&spt_film_denoise_job) film_denoise_job = nullptr;
     decltype(&spt_film_buckets) film_buckets = nullptr;
     decltype(&spt_film_read_buckets) film_read_buckets = nullptr;
     decltype(&spt_film_read_robust) film_read_robust = nullptr;
@@ -633,8 +635,9 @@ struct spt_film {
     DeviceBuffer totals;              // 2 u32 of k_film_adapt: active pixels, tiles with any
     DeviceBuffer inv;                 // (spp + 1) f32: inv[k] = 1.0f / (float)k as the host rounds it (inv[0] = 0, never read)
     uint32_t active = 0, active_tiles = 0;
-    // spt_film_denoise's workspace, made by its first call: two colour arrays (ping-pong) and the guide array, one float4 per pixel
-    DeviceBuffer dn_color[2], dn_guide;
+    // spt_film_denoise's workspace, made by its first call: two colour arrays (ping-pong) and the guide array, one float4 per pixel;
+    // the albedo array by the first spt_film_denoise_job with an albedo film
+    DeviceBuffer dn_color[2], dn_guide, dn_albedo;
     // bucket sums (spt_film_buckets): n_buckets planes of rows * width * 3 f32, and the reciprocal table of the robust read-outs
     uint32_t n_buckets = 0;           // K; 0: a film without buckets
     DeviceBuffer buckets;             // B_j, j = 0 .. K - 1
@@ -865,7 +868,7 @@ const BezierLib* bezier_lib() {
                          sym(lib.render_wait, "spt_render_wait") && sym(lib.film_create, "spt_film_create") && sym(lib.film_render, "spt_film_render") &&
                          sym(lib.film_samples, "spt_film_samples") && sym(lib.film_read, "spt_film_read") && sym(lib.film_destroy, "spt_film_destroy") &&
                          sym(lib.film_adapt, "spt_film_adapt") && sym(lib.film_read_counts, "spt_film_read_counts") &&
-                         sym(lib.film_denoise, "spt_film_denoise") && sym(lib.film_buckets, "spt_film_buckets") &&
+                         sym(lib.film_denoise, "spt_film_denoise") && sym(lib.film_denoise_job, "spt_film_denoise_job") && sym(lib.film_buckets, "spt_film_buckets") &&
                          sym(lib.film_read_buckets, "spt_film_read_buckets") && sym(lib.film_read_robust, "spt_film_read_robust") &&
                          sym(lib.film_read_rgb8, "spt_film_read_rgb8") &&
                          sym(lib.trace_closest, "spt_trace_closest") && sym(lib.trace_any, "spt_trace_any") && sym(lib.debug_bxdf, "spt_debug_bxdf") &&
@@ -1555,6 +1558,8 @@ struct RenderRun {
     bool film_stream = false;    // the overlapped schedule is allowed (no SPT_NO_FILM_STREAM)
     bool film_overlap = false;   // ... and this render takes it: tail launch, resolve, finish and copy-out on the film stream
     bool debug_spans = false;    // per-launch HIP-event times on stderr (profile mode)
+    bool albedo = false;         // SPT_RENDER_AOV_ALBEDO: paths end at their first surface, and the kernels get the scene without its environment
+    bool env = false;            // the scene the kernels see has an environment
     uint32_t primary_chunks = 0;   // sample chunks per primary tile; 0: sized to the busy tiles
     uint64_t box_band_bytes = 0;   // kept radiance per band of a wide box filter
     size_t lds = 0;
@@ -1593,13 +1598,15 @@ void run_setup(RenderRun& run) {
     const spt_camera* const cam = run.cam;
     run.st = sc->stream;
     run.profile = (p.flags & SPT_RENDER_PROFILE) != 0;
+    run.albedo = (p.flags & SPT_RENDER_AOV_ALBEDO) != 0;
+    run.env = sc->d.env_w != 0u && !run.albedo;
     // visit counters: only the kernels that fetch their geometry from memory count (an LDS-resident scene is read once
     // per workgroup whatever the rays do)
     run.count = (p.flags & SPT_RENDER_COUNT_VISITS) != 0 && !sc->lds_geo;
     sc->visits.ensure(12 * sizeof(unsigned long long));
     if (run.count) HIP_CHECK(hipMemsetAsync(sc->visits.p, 0, 12 * sizeof(unsigned long long), sc->stream));
     // per-kernel event timing needs one stream; so does a scene with an environment (see bounce)
-    run.overlap = !run.profile && sc->d.env_w == 0u && std::getenv("SPT_NO_OVERLAP") == nullptr;
+    run.overlap = !run.profile && !run.env && std::getenv("SPT_NO_OVERLAP") == nullptr;
     run.lds = sc->lds_bytes;
     run.L = sc->lds_geo;
     // primary rays of an LDS-resident scene through the eye-relative copy of its geometry (eye.h), remade when the eye has moved
@@ -1655,7 +1662,7 @@ void run_spans(RenderRun& run) {
     // from the leftmost to the rightmost hull point within one row of slack above and below, plus one pixel each side.
     // A pixel outside its row's span cannot see any instance with any sample (k_primary's `in_bounds`): the rotated
     // cube of the headline scene fills 19 % of the image, its world-space AABB's rectangle 25 %.
-    if (!sc->hull_corners.empty() && sc->d.env_w == 0u && run.row_spans) {
+    if (!sc->hull_corners.empty() && !run.env && run.row_spans) {
         std::vector<double> key = {(double)p.width, (double)p.height, (double)cam->half_cot_half_fov};
         for (int k = 0; k < 3; ++k) { key.push_back(cam->eye[k]); key.push_back(cam->forward[k]); key.push_back(cam->up[k]); key.push_back(cam->right[k]); }
         if (key != sc->span_key) {
@@ -1737,6 +1744,8 @@ void check_plan(const spt_render_params& p, const char* who) {
     const uint32_t shard_count = p.shard_count ? p.shard_count : 1u;
     if (p.shard_index >= shard_count) fail(SPT_ERR_INVALID_ARG, w + ": shard_index >= shard_count");
     if ((uint64_t)p.width * p.height > 0xffffffffull) fail(SPT_ERR_UNSUPPORTED, w + ": more than 2^32 pixels");
+    if ((p.flags & SPT_RENDER_DEBUG_NORMAL) && (p.flags & SPT_RENDER_AOV_ALBEDO))
+        fail(SPT_ERR_INVALID_ARG, w + ": SPT_RENDER_DEBUG_NORMAL and SPT_RENDER_AOV_ALBEDO exclude each other (a path has one colour)");
 }
 
 // BoxFilter (src/filter/boxf.rs:11-14): radius_int = ceil(radius - 0.5) neighbour pixels each way
@@ -1772,7 +1781,7 @@ RenderCtx plan_ctx(const spt_render_params& p, const spt_camera& cam, uint32_t r
         rc.aux_dx = rc.aspect * rc.width_inv * spp_sqrt_inv;
         rc.aux_dy = rc.height_inv * spp_sqrt_inv;
     }
-    rc.debug_normal = (p.flags & SPT_RENDER_DEBUG_NORMAL) ? 1u : 0u;
+    rc.debug_normal = (p.flags & SPT_RENDER_DEBUG_NORMAL) ? 1u : ((p.flags & SPT_RENDER_AOV_ALBEDO) ? 2u : 0u);
     return rc;
 }
 
@@ -1946,8 +1955,8 @@ struct LiveCount {
     uint32_t active_tiles;
     uint64_t live_pixels;
 };
-LiveCount count_live(const spt_scene* sc, const RenderCtx& rc) {
-    if (sc->d.env_w != 0u) return LiveCount{rc.n_tiles, rc.n_pixels};
+LiveCount count_live(const spt_scene* sc, bool env, const RenderCtx& rc) {
+    if (env) return LiveCount{rc.n_tiles, rc.n_pixels};
     auto image_row = [&rc](uint32_t r) {   // global_row of kernels.h
         const uint32_t strip = r / rc.strip_rows;
         return (int32_t)(rc.row_base + (strip * rc.shard_count + rc.shard_index) * rc.strip_rows + (r - strip * rc.strip_rows));
@@ -1975,6 +1984,14 @@ LiveCount count_live(const spt_scene* sc, const RenderCtx& rc) {
     return live;
 }
 
+// The scene as the primary kernel of this run sees it: an albedo plan (SPT_RENDER_AOV_ALBEDO) hides the environment, so a miss is
+// black and every host-side choice that asks "is there an environment" (run.env) agrees with the kernel.
+DScene run_scene(const RenderRun& run, bool eye) {
+    DScene d = eye ? run.sc->eye_d : run.sc->d;
+    if (run.albedo) d.env_w = d.env_h = 0u;
+    return d;
+}
+
 // The primary kernel of a pass over `blocks` workgroups (one per tile, or per tile and sample chunk: kChunked).  The mask
 // argument (FilmMask) makes it an adaptive film's k_*<..., kMask>, which exists chunked and without visit counting only.
 template <bool kChunked, class... M>
@@ -1989,7 +2006,7 @@ void launch_primary(const RenderRun& run, uint32_t blocks, const RenderCtx& rc, 
     if constexpr (!kMask) {   // (visits are only counted outside LDS, so never through the eye-relative copy)
         if (run.count) fn = run.stream_p ? k_primary_stream<kChunked, true> : k_primary<false, kChunked, true>;
     }
-    hipLaunchKernelGGL(fn, dim3(blocks), dim3(kBlock), run.use_eye ? sc->eye_lds_bytes : run.lds, run.st, run.use_eye ? sc->eye_d : sc->d, rc, mask...);
+    hipLaunchKernelGGL(fn, dim3(blocks), dim3(kBlock), run.use_eye ? sc->eye_lds_bytes : run.lds, run.st, run_scene(run, run.use_eye), rc, mask...);
 }
 
 // The sample chunks per tile and the primary kernel of one pass.  Returns whether the kernel was a chunked one (which
@@ -2009,7 +2026,7 @@ bool primary_pass(const RenderRun& run, RenderCtx& rc, const SampleTarget& tgt, 
     // un-chunked kernel adds the misses before a pixel's first hit straight into its sum, past k_resolve<true>'s Q
     // An adaptive film takes the chunked path only (its masked instances), whatever the chunk count.
     // Buckets of a scene with an environment: the same, those misses would pass k_resolve_buckets.
-    const bool all_slots = collect || ((tgt.sq != nullptr || tgt.buckets != nullptr) && sc->d.env_w != 0u) || tgt.mask.pixel != nullptr;
+    const bool all_slots = collect || ((tgt.sq != nullptr || tgt.buckets != nullptr) && run.env) || tgt.mask.pixel != nullptr;
     const bool chunked = rc.primary_chunks > 1u || all_slots;
     rc.slot_bits = chunked ? slot_bits : nullptr;
     if (!chunked && run.film_overlap) {   // the un-chunked kernel adds into rc.film itself: behind the film memset and every earlier resolve
@@ -2098,6 +2115,13 @@ bool bounce(RenderRun& run, const RenderCtx& rc, uint32_t b, hipStream_t st) {
     // LDS: the traversal stack and geometry, also for the BSSRDF probe, which walks the BVH inside k_shade<3 | 5>
     const size_t shade_lds = (run.fused || run.tab || sc->has_probe) ? run.lds : 0;
     run.begin(b == 0 ? SPT_K_SHADE_FIRST : SPT_K_SHADE);
+    if (run.albedo) {   // every path ends in k_shade_albedo: no shadow ray, no extension ray (trace_window launches bounce 0 only)
+        const bool pndf = sc->textured && sc->subsurface && sc->has_pndf;   // the scenes whose shade kernel is k_shade<4 | 5>
+        const BounceFn fn = pndf ? k_shade_albedo<true, true> : sc->textured ? k_shade_albedo<true, false> : k_shade_albedo<false, false>;
+        hipLaunchKernelGGL(fn, dim3(kPersistentBlocks), dim3(kBlock), 0, st, sc->d, ru, b);
+        run.end();
+        return false;
+    }
     hipLaunchKernelGGL(shade_kernel(run, b, tail_loop), dim3(kPersistentBlocks), dim3(kBlock), shade_lds, st, sc->d, ru, b);
     run.end();
     if (run.fused) return tail_loop;
@@ -2192,7 +2216,7 @@ RenderCtx trace_window(RenderRun& run, uint32_t row_base, uint32_t rows, uint32_
     rc.stream_refill_below = run.stream_refill_below;
     rc.visits = sc->visits.as<unsigned long long>();
     rc.row_span = run.row_span_dev;
-    const LiveCount live = count_live(sc, rc);
+    const LiveCount live = count_live(sc, run.env, rc);
     // The overlapped schedule (run.film_overlap, asked for by spt_render): the main stream traces pass p + 1 into one set of
     // the doubled pass buffers while the film stream finishes pass p from the other - its tail-loop shade launch when that
     // kernel is chosen, and its resolve.  Neither needs the vector ALU that k_primary keeps busy.  Without memory for the
@@ -2247,7 +2271,8 @@ RenderCtx trace_window(RenderRun& run, uint32_t row_base, uint32_t rows, uint32_
             handed_over = true;
         };
         bool tail_on_film = false;
-        for (uint32_t b = 0; b < p.max_depth; ++b) {
+        const uint32_t n_bounces = run.albedo ? std::min(p.max_depth, 1u) : p.max_depth;   // an albedo plan's paths end at their first surface
+        for (uint32_t b = 0; b < n_bounces; ++b) {
             if (ov && takes_tail_loop(run, b)) {   // reads qb / hit_*_next and this set; the next k_primary writes neither
                 hand_over();
                 (void)bounce(run, rc, b, st_film);
@@ -2727,10 +2752,19 @@ static bool denoise_libraries_differ(const spt_film* f, const spt_film* guide) {
     return true;
 }
 
-// spt_film_denoise behind its argument checks (the scene's lock is held)
-static spt_status film_denoise_locked(spt_film* f, spt_film* guide, const spt_denoise_params* params, const FilmReadOut& to) {
+// The albedo film of a spt_film_denoise_job and what the job says about it (null film: spt_film_denoise)
+struct DenoiseAlbedoJob {
+    spt_film* film = nullptr;
+    float k_albedo = 1.0f, eps_albedo = 1e-2f, eps_demod = 1e-2f;
+    bool demodulate = false;
+};
+
+// spt_film_denoise and spt_film_denoise_job behind their argument checks (the scene's lock is held)
+static spt_status film_denoise_locked(spt_film* f, spt_film* guide, const spt_denoise_params* params, const FilmReadOut& to,
+                                      const DenoiseAlbedoJob& aj = DenoiseAlbedoJob{}) {
     spt_scene* sc = f->sc;
     const spt_render_params& p = f->plan;
+    spt_film* const albedo = aj.film;
     // every check comes before the first launch: a refused call leaves the workspace as it was, and it reads the films only
     auto check_film = [](const spt_film* x, const char* who) {
         if (!(x->flags & SPT_FILM_MOMENTS))
@@ -2748,6 +2782,19 @@ static spt_status film_denoise_locked(spt_film* f, spt_film* guide, const spt_de
             (g.strip_rows ? g.strip_rows : 1u) != (p.strip_rows ? p.strip_rows : 1u) || guide->rows != f->rows)
             fail(SPT_ERR_INVALID_ARG, "film_denoise: the guide has another shard layout");
     }
+    if (albedo) {   // checked exactly as the guide is
+        if (albedo == f) fail(SPT_ERR_INVALID_ARG, "film_denoise_job: the albedo film is the film itself");
+        if (albedo == guide) fail(SPT_ERR_INVALID_ARG, "film_denoise_job: the albedo film is the guide");
+        if (albedo->sc != sc) fail(SPT_ERR_INVALID_ARG, "film_denoise_job: the albedo film belongs to another scene object");
+        check_film(albedo, "albedo film");
+        const spt_render_params& g = albedo->plan;
+        if (g.width != p.width || g.height != p.height) fail(SPT_ERR_INVALID_ARG, "film_denoise_job: the albedo film has another width or height");
+        if (g.shard_index != p.shard_index || (g.shard_count ? g.shard_count : 1u) != (p.shard_count ? p.shard_count : 1u) ||
+            (g.strip_rows ? g.strip_rows : 1u) != (p.strip_rows ? p.strip_rows : 1u) || albedo->rows != f->rows)
+            fail(SPT_ERR_INVALID_ARG, "film_denoise_job: the albedo film has another shard layout");
+    }
+    for (const float v : {aj.k_albedo, aj.eps_albedo, aj.eps_demod})   // (with or without an albedo film, as k_guide without a guide)
+        if (!std::isfinite(v) || !(v > 0.0f)) fail(SPT_ERR_INVALID_ARG, "film_denoise_job: k_albedo, eps_albedo and eps_demod must be finite and > 0");
     spt_denoise_params dp{(uint32_t)sizeof(spt_denoise_params), 5u, 2.0f, 1.0f, 1e-8f, 1e-2f};
     if (params) {
         if (params->size < sizeof(spt_denoise_params)) fail(SPT_ERR_INVALID_ARG, "film_denoise: params->size is smaller than spt_denoise_params");
@@ -2756,7 +2803,7 @@ static spt_status film_denoise_locked(spt_film* f, spt_film* guide, const spt_de
     if (dp.iterations < 1u || dp.iterations > 8u) fail(SPT_ERR_INVALID_ARG, "film_denoise: iterations must be 1 .. 8");
     for (const float v : {dp.k_color, dp.k_guide, dp.eps_color, dp.eps_guide})
         if (!std::isfinite(v) || !(v > 0.0f)) fail(SPT_ERR_INVALID_ARG, "film_denoise: k_color, k_guide, eps_color and eps_guide must be finite and > 0");
-    if (f->radius != 0.5f || (guide && guide->radius != 0.5f))
+    if (f->radius != 0.5f || (guide && guide->radius != 0.5f) || (albedo && albedo->radius != 0.5f))
         fail(SPT_ERR_UNSUPPORTED, "film_denoise: needs the box radius 0.5 on both films (every sample of the pixel weighs 1)");
     if (p.shard_count > 1u) fail(SPT_ERR_UNSUPPORTED, "film_denoise: the plan has shard_count > 1 (a shard's packed rows are not neighbours in the image)");
     if (f->rows == 0 || p.width == 0) return SPT_OK;
@@ -2768,11 +2815,19 @@ static spt_status film_denoise_locked(spt_film* f, spt_film* guide, const spt_de
     f->dn_color[0].ensure(rec_bytes);
     if (dp.iterations > 1u) f->dn_color[1].ensure(rec_bytes);
     if (guide) f->dn_guide.ensure(rec_bytes);
+    if (albedo) f->dn_albedo.ensure(rec_bytes);
     f->out.ensure(out_bytes);
     float4* color[2] = {f->dn_color[0].as<float4>(), dp.iterations > 1u ? f->dn_color[1].as<float4>() : nullptr};
     float4* const gbuf = guide ? f->dn_guide.as<float4>() : nullptr;
+    float4* const abuf = albedo ? f->dn_albedo.as<float4>() : nullptr;
+    const DenoiseAlbedo ab{aj.k_albedo * aj.k_albedo, aj.eps_albedo, aj.eps_demod, aj.demodulate ? 1u : 0u};
     const dim3 pack_grid((n_pix + kBlock - 1) / kBlock), block(kBlock);
-    if (guide) hipLaunchKernelGGL(k_denoise_pack<true>, pack_grid, block, 0, st, n_pix, denoise_input(f), denoise_input(guide), color[0], gbuf);
+    if (albedo) {
+        const DenoiseFilm gin = guide ? denoise_input(guide) : DenoiseFilm{};
+        auto pack = [&](auto kernel) { hipLaunchKernelGGL(kernel, pack_grid, block, 0, st, n_pix, denoise_input(f), gin, denoise_input(albedo), ab, color[0], gbuf, abuf); };
+        if (guide) pack(k_denoise_pack_albedo<true>);
+        else pack(k_denoise_pack_albedo<false>);
+    } else if (guide) hipLaunchKernelGGL(k_denoise_pack<true>, pack_grid, block, 0, st, n_pix, denoise_input(f), denoise_input(guide), color[0], gbuf);
     else hipLaunchKernelGGL(k_denoise_pack<false>, pack_grid, block, 0, st, n_pix, denoise_input(f), DenoiseFilm{}, color[0], gbuf);
     HIP_CHECK(hipGetLastError());
     DenoiseArgs a{};
@@ -2790,7 +2845,12 @@ static spt_status film_denoise_locked(spt_film* f, spt_film* guide, const spt_de
         float4* dst = color[(k + 1u) & 1u];
         const bool last = k + 1u == dp.iterations;
         auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, a, src, gbuf, dst, f->out.as<float>()); };
-        if (guide && last) launch(k_denoise_atrous<true, true>);
+        auto launch_albedo = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, a, ab, src, gbuf, abuf, dst, f->out.as<float>()); };
+        if (albedo && guide && last) launch_albedo(k_denoise_atrous_albedo<true, true>);
+        else if (albedo && guide) launch_albedo(k_denoise_atrous_albedo<true, false>);
+        else if (albedo && last) launch_albedo(k_denoise_atrous_albedo<false, true>);
+        else if (albedo) launch_albedo(k_denoise_atrous_albedo<false, false>);
+        else if (guide && last) launch(k_denoise_atrous<true, true>);
         else if (guide) launch(k_denoise_atrous<true, false>);
         else if (last) launch(k_denoise_atrous<false, true>);
         else launch(k_denoise_atrous<false, false>);
@@ -2806,6 +2866,39 @@ spt_status spt_film_denoise(spt_film* f, spt_film* guide, const spt_denoise_para
     if (f->fwd) return forwarded(f->fwd, f->fwd->film_denoise(f->inner, guide ? guide->inner : nullptr, params, out));
     std::lock_guard<std::mutex> lock(f->sc->mu);
     return guarded("film_denoise", [&] { return film_denoise_locked(f, guide, params, FilmReadOut{out, nullptr}); });
+}
+
+spt_status spt_film_denoise_job(spt_film* f, const spt_denoise_job* job, void* out) {
+    if (!f || !job || !out) { g_error = "film_denoise_job: null argument"; return SPT_ERR_INVALID_ARG; }
+    if (job->size < offsetof(spt_denoise_job, k_albedo)) { g_error = "film_denoise_job: job->size ends before k_albedo"; return SPT_ERR_INVALID_ARG; }
+    if (job->flags & ~(uint32_t)(SPT_DENOISE_DEMODULATE | SPT_DENOISE_OUT_RGB8)) { g_error = "film_denoise_job: unknown flags"; return SPT_ERR_INVALID_ARG; }
+    if ((job->flags & SPT_DENOISE_DEMODULATE) && !job->albedo) { g_error = "film_denoise_job: SPT_DENOISE_DEMODULATE needs an albedo film"; return SPT_ERR_INVALID_ARG; }
+    if (denoise_libraries_differ(f, job->guide) || denoise_libraries_differ(f, job->albedo)) return SPT_ERR_INVALID_ARG;
+    if (f->fwd) {   // the same job with the inner handles
+        spt_denoise_job inner{};
+        std::memcpy(&inner, job, std::min<size_t>(job->size, sizeof inner));
+        inner.size = (uint32_t)std::min<size_t>(job->size, sizeof inner);
+        inner.guide = job->guide ? job->guide->inner : nullptr;
+        inner.albedo = job->albedo ? job->albedo->inner : nullptr;
+        return forwarded(f->fwd, f->fwd->film_denoise_job(f->inner, &inner, out));
+    }
+    DenoiseAlbedoJob aj;
+    aj.film = job->albedo;
+    aj.demodulate = (job->flags & SPT_DENOISE_DEMODULATE) != 0;
+    // (the struct only grows at its tail: a float the caller's struct ends before keeps its default)
+    if (job->size >= offsetof(spt_denoise_job, k_albedo) + sizeof(float)) aj.k_albedo = job->k_albedo;
+    if (job->size >= offsetof(spt_denoise_job, eps_albedo) + sizeof(float)) aj.eps_albedo = job->eps_albedo;
+    if (job->size >= offsetof(spt_denoise_job, eps_demod) + sizeof(float)) aj.eps_demod = job->eps_demod;
+    const bool rgb8 = (job->flags & SPT_DENOISE_OUT_RGB8) != 0;
+    const FilmReadOut to{rgb8 ? nullptr : static_cast<float*>(out), rgb8 ? static_cast<uint8_t*>(out) : nullptr};
+    std::lock_guard<std::mutex> lock(f->sc->mu);
+    return guarded("film_denoise_job", [&] { return film_denoise_locked(f, job->guide, job->params, to, aj); });
+}
+
+spt_status spt_render_flags_supported(uint32_t* mask) {
+    if (!mask) { g_error = "render_flags_supported: null argument"; return SPT_ERR_INVALID_ARG; }
+    *mask = SPT_RENDER_PROFILE | SPT_RENDER_BOX_RADIUS | SPT_RENDER_COUNT_VISITS | SPT_RENDER_ASYNC | SPT_RENDER_DEBUG_NORMAL | SPT_RENDER_AOV_ALBEDO;
+    return SPT_OK;
 }
 
 spt_status spt_film_buckets(spt_film* f, uint32_t n_buckets) {

@@ -18,12 +18,14 @@ CXXFLAGS := -std=c++17 -O2 -fPIC -Wall -Wextra -ffp-contract=off -fno-fast-math 
 HIPFLAGS := -std=c++17 -O3 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -fno-slp-vectorize \
             -Wall -Wno-unused-function -Iinclude
 
-HOST_SRC := $(wildcard $(PKG)/csrc/host/*.cpp)
+# (multi_film_selftest.cpp has a main of its own: `make selftest`)
+SELFTEST_SRC := $(PKG)/csrc/host/multi_film_selftest.cpp
+HOST_SRC := $(filter-out $(SELFTEST_SRC),$(wildcard $(PKG)/csrc/host/*.cpp))
 HOST_HDR := $(wildcard $(PKG)/csrc/host/*.hpp) $(wildcard include/*.h)
 HIP_SRC  := $(wildcard $(PKG)/csrc/hip/*.hip)
 HIP_HDR  := $(wildcard $(PKG)/csrc/hip/*.h) $(wildcard include/*.h)
 
-.PHONY: all host hip hip-plain cli oracle clean
+.PHONY: all host hip hip-plain cli oracle selftest clean
 all: host oracle hip cli
 
 host: $(LIBDIR)/libspt_host.so
@@ -62,6 +64,19 @@ $(LIBDIR)/libspt_hip_bez.so: $(HIP_OBJ_BEZ)
 
 $(LIBDIR)/spt: $(PKG)/csrc/cli/main.cpp $(wildcard include/*.h) $(LIBDIR)/libspt_host.so $(LIBDIR)/libspt_hip.so
 	$(CXX) $(CXXFLAGS) -o $@ $< -L$(LIBDIR) -lspt_host -lspt_hip -Wl,-rpath,'$$ORIGIN'
+
+# The film fan-out of multi.cpp with stand-in devices, once under ThreadSanitizer and once under AddressSanitizer + UBSan: host code
+# only, stand-alone programs with the sanitizer runtimes linked in (tests/test_multi_film_selftest.py runs them)
+SELFTEST_DIR := build/selftest
+selftest: $(SELFTEST_DIR)/multi_film_selftest_tsan $(SELFTEST_DIR)/multi_film_selftest_asan
+
+$(SELFTEST_DIR)/multi_film_selftest_tsan: $(SELFTEST_SRC) $(PKG)/csrc/host/multi.cpp $(wildcard include/*.h)
+	@mkdir -p $(SELFTEST_DIR)
+	$(CXX) -std=c++17 -O1 -g -Wall -Wextra -ffp-contract=off -Iinclude -fsanitize=thread -static-libtsan -o $@ $(SELFTEST_SRC) $(PKG)/csrc/host/multi.cpp -lpthread
+
+$(SELFTEST_DIR)/multi_film_selftest_asan: $(SELFTEST_SRC) $(PKG)/csrc/host/multi.cpp $(wildcard include/*.h)
+	@mkdir -p $(SELFTEST_DIR)
+	$(CXX) -std=c++17 -O1 -g -Wall -Wextra -ffp-contract=off -Iinclude -fsanitize=address,undefined -fno-sanitize-recover=undefined -static-libasan -static-libubsan -o $@ $(SELFTEST_SRC) $(PKG)/csrc/host/multi.cpp -lpthread
 
 clean:
 	rm -rf $(LIBDIR) build oracle/*.so oracle/_ref

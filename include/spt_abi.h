@@ -551,6 +551,33 @@ typedef struct spt_denoise_job {
 } spt_denoise_job;
 spt_status spt_film_denoise_job(spt_film* film, const spt_denoise_job* job, void* out);
 
+/* ---- denoising caller-provided images (additive to ABI v14: detect it by symbol) ----------------------------------------------------
+ * spt_denoise_image is the filter of spt_film_denoise_job on images instead of films: what a caller has who assembled a full image
+ * from shard films (spt_host_multi_film_denoise, ranks that gathered a film), none of which could be filtered on its own.  The
+ * arithmetic is exactly the specification above, with m, v / g, u / al, ua taken from `mean`, `var` / `guide_mean`, `guide_var` /
+ * `albedo_mean`, `albedo_var`: rows * width * 3 f32 each, packed RGB, as SPT_FILM_MEAN and SPT_FILM_VAR_OF_MEAN return them.  The
+ * result has the bits of spt_film_denoise_job on films whose two read-outs are those arrays.  A +inf variance (a pixel with one
+ * sample) or a NaN makes the pixel pass through and enter no other pixel's sum: ok(q) above.
+ * The scene names the device and the stream; the call takes the scene's lock, its workspace (device images, page-locked staging,
+ * records) belongs to the scene and goes with it, and it touches neither spt_render's buffers nor any film.  The arrays go up
+ * with asynchronous copies, the host filling the staging slot of one array while the previous one is in flight.  Synchronous.
+ * Refusals leave nothing changed: SPT_ERR_INVALID_ARG for a null scene, job, out, mean or var, half a pair of guide or albedo
+ * arrays, job->size below offsetof(spt_image_denoise_job, k_albedo), unknown flags, DEMODULATE without the albedo arrays, and the
+ * params, k_* and eps_* checks of spt_film_denoise_job; SPT_ERR_UNSUPPORTED for more than 2^32 - 4 floats per image.
+ * width == 0 or rows == 0 returns SPT_OK and writes nothing. */
+typedef struct spt_image_denoise_job {
+    uint32_t size, flags;                    /* sizeof(spt_image_denoise_job) as the caller was compiled; SPT_DENOISE_* */
+    uint32_t width, rows;
+    const float *mean, *var;                 /* rows * width * 3 f32 each */
+    const float *guide_mean, *guide_var;     /* both NULL or both set */
+    const float *albedo_mean, *albedo_var;   /* both NULL or both set */
+    const spt_denoise_params* params;        /* may be NULL: the defaults */
+    float k_albedo, eps_albedo, eps_demod;   /* finite and > 0; the defaults 1, 1e-2, 1e-2 when size ends before them */
+    uint32_t pad;
+} spt_image_denoise_job;
+/* out: rows * width * 3 f32, or u8 with SPT_DENOISE_OUT_RGB8 */
+spt_status spt_denoise_image(const spt_scene* scene, const spt_image_denoise_job* job, void* out);
+
 /* ---- bucketed films: median-of-means read-outs (additive to ABI v14: detect it by symbol) ------------------------------------
  * spt_film_buckets makes a film keep K = n_buckets bucket sums B_0 .. B_{K-1} per pixel and channel next to S (and Q).  The sample
  * with plan index s (absolute in the plan: first_sample counts) adds into bucket j = s % K, B_j = B_j + x per channel, in sample

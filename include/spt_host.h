@@ -109,6 +109,78 @@ spt_status spt_host_multi_render(spt_host_multi* m, const spt_camera* cam, const
 uint32_t spt_host_multi_device_count(const spt_host_multi* m);
 void spt_host_multi_destroy(spt_host_multi* m);
 
+/* ---- a progressive film over the replicas of a spt_host_multi (additive: detect it by symbol) -----------------------------------
+ * A multi film is one shard film per replica - shard k of n, the interleaved strips of spt_host_multi_render - driven as one.
+ * A sample depends on (seed, pixel, plan index) only, so a shard film's S, Q, buckets, mask and counts are the rows of the whole
+ * film's, and every per-pixel call (render, adapt, the read-outs) is the same call on every shard, run side by side on the
+ * persistent workers of the spt_host_multi.  Every read-out returns the FULL image, height x width: each worker reads its shard's
+ * packed rows into a buffer the multi film owns and scatters the strips to their rows itself, so the scatter of one shard runs
+ * beside the device read of another.  The one call that needs neighbours, the denoiser, gathers SPT_FILM_MEAN and
+ * SPT_FILM_VAR_OF_MEAN of the film (and of the guide and albedo multi films) into full-image arrays the multi film owns and runs
+ * ONE denoise_image on replica 0's scene.  Every read-out and the denoised image have the bits of the same plan's single-device
+ * film, for every number of devices and every strip_rows, repeated device indices and shards without rows included.
+ * The film entry points arrive as a second table, so that stand-ins can drive the fan-out.  `size` is sizeof of the table as the
+ * caller was compiled (the table only grows at its tail); an entry that is NULL or lies behind `size` makes the multi call that
+ * needs it return SPT_ERR_UNSUPPORTED. */
+typedef struct spt_device_film_api {
+    uint32_t size, pad;
+    spt_status (*film_create)(const spt_scene* scene, const spt_camera* cam, const spt_render_params* params, uint32_t first_sample,
+                              uint32_t film_flags, spt_film** out);
+    void (*film_destroy)(spt_film* film);
+    spt_status (*film_render)(spt_film* film, uint32_t n_samples);
+    spt_status (*film_samples)(const spt_film* film, uint32_t* done);
+    spt_status (*film_read)(spt_film* film, uint32_t what, float* out);
+    spt_status (*film_read_counts)(spt_film* film, uint32_t* out);
+    spt_status (*film_adapt)(spt_film* film, float rel_error, float abs_floor, uint32_t min_samples, uint32_t* active_out);
+    spt_status (*film_buckets)(spt_film* film, uint32_t n_buckets);
+    spt_status (*film_read_robust)(spt_film* film, uint32_t estimator, float* out);
+    spt_status (*film_read_rgb8)(spt_film* film, uint32_t source, spt_film* guide, const spt_denoise_params* dn, uint8_t* out);
+    spt_status (*denoise_image)(const spt_scene* scene, const spt_image_denoise_job* job, void* out);
+    const char* (*last_error)(void);
+} spt_device_film_api;
+
+typedef struct spt_host_multi_film spt_host_multi_film;
+/* Creates shard film k of n on replica k, for every k (side by side on the workers).  `params` is the plan (its shard fields are
+ * overwritten; `strip_rows` as in spt_host_multi_render, 0 = its default; the plan's flags pass through, so a guide or albedo multi
+ * film is the same call with SPT_RENDER_DEBUG_NORMAL / SPT_RENDER_AOV_ALBEDO); first_sample and film_flags as in spt_film_create;
+ * n_buckets != 0: spt_film_buckets on every shard.  Refused as a whole, with no film left behind: null arguments, width or height 0,
+ * a plan with SPT_RENDER_ASYNC / PROFILE / COUNT_VISITS or an out_strip_stride (SPT_ERR_INVALID_ARG), and whatever a shard refuses
+ * (its status, its message behind "device D (shard k of n): ").  Destroy the multi film before its spt_host_multi; a multi film
+ * that is still alive at spt_host_multi_destroy loses its shard films there, refuses every later call (SPT_ERR_INVALID_ARG) and
+ * is still released by spt_host_multi_film_destroy. */
+spt_status spt_host_multi_film_create(spt_host_multi* m, const spt_device_film_api* film_api, const spt_camera* cam,
+                                      const spt_render_params* params, uint32_t strip_rows, uint32_t first_sample, uint32_t film_flags,
+                                      uint32_t n_buckets, spt_host_multi_film** out);
+/* spt_film_render / spt_film_adapt on every shard.  *active_out (may be NULL) is the sum over the shards.  When every shard
+ * refuses, the call is refused with the first shard's status and message and the multi film is as it was.  When some shards fail
+ * and others do not, the shards are out of step and the multi film is BROKEN: every later call except destroy returns
+ * SPT_ERR_INVALID_ARG with a message that says so and repeats the first error. */
+spt_status spt_host_multi_film_render(spt_host_multi_film* f, uint32_t n_samples);
+spt_status spt_host_multi_film_adapt(spt_host_multi_film* f, float rel_error, float abs_floor, uint32_t min_samples, uint32_t* active_out);
+spt_status spt_host_multi_film_samples(const spt_host_multi_film* f, uint32_t* done);
+/* The full image, height * width (* 3): spt_film_read / _read_counts / _read_robust / _read_rgb8 of every shard, scattered to its
+ * rows.  read_rgb8 takes SPT_READ_MEAN, SPT_READ_ROBUST_MON and SPT_READ_ROBUST_GMON; SPT_READ_DENOISED is SPT_ERR_INVALID_ARG
+ * (a shard cannot filter: spt_host_multi_film_denoise with SPT_DENOISE_OUT_RGB8 returns those bytes). */
+spt_status spt_host_multi_film_read(spt_host_multi_film* f, uint32_t what, float* image);
+spt_status spt_host_multi_film_read_counts(spt_host_multi_film* f, uint32_t* image);
+spt_status spt_host_multi_film_read_robust(spt_host_multi_film* f, uint32_t estimator, float* image);
+spt_status spt_host_multi_film_read_rgb8(spt_host_multi_film* f, uint32_t source, uint8_t* image);
+/* spt_denoise_job with multi films: the guide and the albedo film are multi films of the same spt_host_multi, width, height and
+ * strip layout (anything else: SPT_ERR_INVALID_ARG), both may be NULL. */
+typedef struct spt_host_multi_film_denoise_job {
+    uint32_t size, flags;             /* sizeof(spt_host_multi_film_denoise_job) as the caller was compiled; SPT_DENOISE_* */
+    spt_host_multi_film* guide;
+    spt_host_multi_film* albedo;
+    const spt_denoise_params* params; /* may be NULL: the defaults */
+    float k_albedo, eps_albedo, eps_demod;   /* the defaults 1, 1e-2, 1e-2 when size ends before them */
+    uint32_t pad;
+} spt_host_multi_film_denoise_job;
+/* image: height * width * 3 f32, or u8 with SPT_DENOISE_OUT_RGB8.  Gathers mean and variance of the mean of the film, the guide
+ * and the albedo film (every worker reads and scatters its shards' rows), then runs denoise_image on replica 0's scene: the bits of
+ * spt_film_denoise_job on the single-device films.  The films are read only. */
+spt_status spt_host_multi_film_denoise(spt_host_multi_film* f, const spt_host_multi_film_denoise_job* job, void* image);
+void spt_host_multi_film_destroy(spt_host_multi_film* f);   /* before spt_host_multi_destroy of its spt_host_multi (see above) */
+
 const char* spt_host_last_error(void);
 
 #ifdef __cplusplus

@@ -222,6 +222,21 @@ class DenoiseJob(C.Structure):
                 ("pad", C.c_uint32)]
 
 
+class ImageDenoiseJob(C.Structure):
+    """spt_image_denoise_job (spt_denoise_image); `size` is sizeof of the struct."""
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("width", C.c_uint32), ("rows", C.c_uint32),
+                ("mean", C.c_void_p), ("var", C.c_void_p), ("guide_mean", C.c_void_p), ("guide_var", C.c_void_p),
+                ("albedo_mean", C.c_void_p), ("albedo_var", C.c_void_p), ("params", C.POINTER(DenoiseParams)),
+                ("k_albedo", C.c_float), ("eps_albedo", C.c_float), ("eps_demod", C.c_float), ("pad", C.c_uint32)]
+
+
+class MultiFilmDenoiseJob(C.Structure):
+    """spt_host_multi_film_denoise_job (spt_host_multi_film_denoise): spt_denoise_job with multi films."""
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("guide", C.c_void_p), ("albedo", C.c_void_p),
+                ("params", C.POINTER(DenoiseParams)), ("k_albedo", C.c_float), ("eps_albedo", C.c_float), ("eps_demod", C.c_float),
+                ("pad", C.c_uint32)]
+
+
 HIT_DTYPE = np.dtype([("t", "<f4"), ("instance", "<i4"), ("prim", "<i4"), ("v", "<f4"), ("w", "<f4")])
 RAY_DTYPE = np.dtype([("o", "<f4", 3), ("t_min", "<f4"), ("d", "<f4", 3), ("t_max", "<f4")])
 
@@ -252,6 +267,19 @@ def host_lib() -> C.CDLL:
         lib.spt_host_multi_device_count.restype = C.c_uint32
         lib.spt_host_multi_destroy.argtypes = [C.c_void_p]
         lib.spt_host_multi_destroy.restype = None
+        if hasattr(lib, "spt_host_multi_film_create"):   # additive: an older library (SPT_LIB_DIR, A/B runs) may lack them
+            lib.spt_host_multi_film_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                       C.c_uint32, C.POINTER(C.c_void_p)]
+            lib.spt_host_multi_film_render.argtypes = [C.c_void_p, C.c_uint32]
+            lib.spt_host_multi_film_adapt.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_uint32, C.POINTER(C.c_uint32)]
+            lib.spt_host_multi_film_samples.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+            lib.spt_host_multi_film_read.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+            lib.spt_host_multi_film_read_counts.argtypes = [C.c_void_p, C.c_void_p]
+            lib.spt_host_multi_film_read_robust.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+            lib.spt_host_multi_film_read_rgb8.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+            lib.spt_host_multi_film_denoise.argtypes = [C.c_void_p, C.POINTER(MultiFilmDenoiseJob), C.c_void_p]
+            lib.spt_host_multi_film_destroy.argtypes = [C.c_void_p]
+            lib.spt_host_multi_film_destroy.restype = None
         lib.spt_host_load_scene.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
         lib.spt_host_scene_desc.argtypes = [C.c_void_p]
         lib.spt_host_scene_desc.restype = C.POINTER(SceneDesc)
@@ -320,6 +348,8 @@ def hip_lib() -> C.CDLL:
         if hasattr(lib, "spt_film_read_rgb8"):   # (the same)
             lib.spt_film_read_rgb8.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p]
             lib.spt_debug_pack_rgb8.argtypes = [C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]
+        if hasattr(lib, "spt_denoise_image"):   # (the same)
+            lib.spt_denoise_image.argtypes = [C.c_void_p, C.POINTER(ImageDenoiseJob), C.c_void_p]
         lib.spt_debug_detmath.argtypes = [C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.spt_debug_bxdf.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Material), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -783,6 +813,178 @@ def hip_device_api() -> DeviceApi:
                      addr(lib.spt_pin_host), addr(lib.spt_unpin_host))
 
 
+class DeviceFilmApi(C.Structure):
+    """spt_device_film_api (include/spt_host.h): the film entry points a multi film drives; `size` is sizeof of the table."""
+    _fields_ = [("size", C.c_uint32), ("pad", C.c_uint32), ("film_create", C.c_void_p), ("film_destroy", C.c_void_p),
+                ("film_render", C.c_void_p), ("film_samples", C.c_void_p), ("film_read", C.c_void_p), ("film_read_counts", C.c_void_p),
+                ("film_adapt", C.c_void_p), ("film_buckets", C.c_void_p), ("film_read_robust", C.c_void_p), ("film_read_rgb8", C.c_void_p),
+                ("denoise_image", C.c_void_p), ("last_error", C.c_void_p)]
+
+
+def hip_device_film_api() -> DeviceFilmApi:
+    """The film table filled with libspt_hip.so's own functions.  An entry point an older library lacks (they are additive to ABI
+    v14) stays NULL: the multi call that needs it then returns SPT_ERR_UNSUPPORTED."""
+    lib = hip_lib()
+    addr = lambda name: C.cast(getattr(lib, name), C.c_void_p).value if hasattr(lib, name) else None
+    return DeviceFilmApi(C.sizeof(DeviceFilmApi), 0, addr("spt_film_create"), addr("spt_film_destroy"), addr("spt_film_render"),
+                         addr("spt_film_samples"), addr("spt_film_read"), addr("spt_film_read_counts"), addr("spt_film_adapt"),
+                         addr("spt_film_buckets"), addr("spt_film_read_robust"), addr("spt_film_read_rgb8"),
+                         addr("spt_denoise_image"), addr("spt_last_error"))
+
+
+_DENOISE_DEFAULTS = dict(iterations=5, k_color=2.0, k_guide=1.0, eps_color=1e-8, eps_guide=1e-2, k_albedo=1.0, eps_albedo=1e-2, eps_demod=1e-2)
+
+
+def _denoise_keywords(who: str, params: dict) -> dict:
+    unknown = set(params) - set(_DENOISE_DEFAULTS)
+    if unknown:
+        raise TypeError("%s: unknown parameter(s) %s" % (who, ", ".join(sorted(unknown))))
+    d = dict(_DENOISE_DEFAULTS)
+    d.update(params)
+    return d
+
+
+def denoise_image(scene, mean: np.ndarray, var: np.ndarray, guide=None, albedo=None, demodulate: bool = False, rgb8: bool = False,
+                  **params) -> np.ndarray:
+    """spt_denoise_image: the filter of ProgressiveFilm.denoise_job on images instead of films.  `scene` (a Scene, whose device 0
+    replica is used, or a DeviceScene) names the device; `mean` / `var` are (rows, width, 3) f32 as mean() / variance_of_mean()
+    return them, `guide` and `albedo` (mean, var) pairs of the same shape.  The result has the bits of denoise_job on films with
+    those read-outs: (rows, width, 3) f32, or u8 with rgb8."""
+    ds = scene.device_scene(0) if isinstance(scene, Scene) else scene
+    d = _denoise_keywords("denoise_image", params)
+    mean = np.ascontiguousarray(mean, dtype=np.float32)
+    if mean.ndim != 3 or mean.shape[2] != 3:
+        raise ValueError("denoise_image: mean must have the shape (rows, width, 3)")
+    keep = [mean]
+
+    def arr(a, what):
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.shape != mean.shape:
+            raise ValueError("denoise_image: %s has the shape %r, the mean %r" % (what, a.shape, mean.shape))
+        keep.append(a)
+        return a.ctypes.data if a.size else keep[0].ctypes.data
+
+    dp = DenoiseParams(C.sizeof(DenoiseParams), d["iterations"], d["k_color"], d["k_guide"], d["eps_color"], d["eps_guide"])
+    job = ImageDenoiseJob(C.sizeof(ImageDenoiseJob), (DENOISE_DEMODULATE if demodulate else 0) | (DENOISE_OUT_RGB8 if rgb8 else 0),
+                          mean.shape[1], mean.shape[0], arr(mean, "mean"), arr(var, "var"),
+                          arr(guide[0], "guide mean") if guide is not None else None, arr(guide[1], "guide var") if guide is not None else None,
+                          arr(albedo[0], "albedo mean") if albedo is not None else None, arr(albedo[1], "albedo var") if albedo is not None else None,
+                          C.pointer(dp), d["k_albedo"], d["eps_albedo"], d["eps_demod"], 0)
+    out = np.zeros(mean.shape, dtype=np.uint8 if rgb8 else np.float32)
+    _check_hip(hip_lib().spt_denoise_image(ds._h, C.byref(job), out.ctypes.data if out.size else keep[0].ctypes.data))
+    return out
+
+
+class MultiFilm:
+    """A progressive film over the replicas of a MultiDevice (spt_host_multi_film_*): one shard film per replica, driven as one;
+    see MultiDevice.progressive.  The methods are ProgressiveFilm's and every read-out is the FULL image, with the bits of the
+    single-device film of the same plan."""
+
+    def __init__(self, multi: "MultiDevice", renderer: "PathTracer", config: OutputConfig, strip_rows: int = 0, first_sample: int = 0,
+                 moments: bool = False, flags: int = 0, buckets: int = 0, film_api: Optional[DeviceFilmApi] = None):
+        self._h = C.c_void_p()
+        self.multi = multi
+        self.first_sample = first_sample
+        self.width, self.height = config.width, config.height
+        self.n_buckets = buckets
+        self._api = film_api if film_api is not None else hip_device_film_api()
+        cam = multi.scene.get_camera(config.used_camera_name)
+        p = renderer.params(config.width, config.height, 0, 1, 16, 0, flags)
+        _check_host(host_lib().spt_host_multi_film_create(multi._h, C.byref(self._api), C.byref(cam), C.byref(p), strip_rows, first_sample,
+                                                          FILM_MOMENTS if moments else 0, buckets, C.byref(self._h)))
+        multi._films.add(self)
+
+    def _handle(self):
+        if not self._h:
+            raise SptError(1, "the multi film is closed")
+        return self._h
+
+    def render(self, n: int) -> "MultiFilm":
+        """Adds the next n samples of the plan to every shard (synchronous)."""
+        _check_host(host_lib().spt_host_multi_film_render(self._handle(), n))
+        return self
+
+    @property
+    def samples(self) -> int:
+        done = C.c_uint32()
+        _check_host(host_lib().spt_host_multi_film_samples(self._handle(), C.byref(done)))
+        return done.value
+
+    def read(self, what: int) -> np.ndarray:
+        """(height, width, 3) f32 of one FILM_* quantity."""
+        out = np.zeros((self.height, self.width, 3), dtype=np.float32)
+        _check_host(host_lib().spt_host_multi_film_read(self._handle(), what, out.ctypes.data))
+        return out
+
+    def mean(self) -> np.ndarray:
+        return self.read(FILM_MEAN)
+
+    def sum(self) -> np.ndarray:
+        return self.read(FILM_SUM)
+
+    def sum_sq(self) -> np.ndarray:
+        return self.read(FILM_SUM_SQ)
+
+    def variance_of_mean(self) -> np.ndarray:
+        return self.read(FILM_VAR_OF_MEAN)
+
+    def sample_counts(self) -> np.ndarray:
+        out = np.zeros((self.height, self.width), dtype=np.uint32)
+        _check_host(host_lib().spt_host_multi_film_read_counts(self._handle(), out.ctypes.data))
+        return out
+
+    def adapt(self, rel_error: float, abs_floor: float = 0.0, min_samples: int = 16) -> int:
+        """ProgressiveFilm.adapt on every shard; returns the pixels still active, summed over the shards."""
+        active = C.c_uint32()
+        _check_host(host_lib().spt_host_multi_film_adapt(self._handle(), rel_error, abs_floor, min_samples, C.byref(active)))
+        return active.value
+
+    def robust_mean(self, estimator: str = "gmon") -> np.ndarray:
+        if estimator not in ("mon", "gmon"):
+            raise ValueError("robust_mean: estimator is 'mon' or 'gmon', not %r" % (estimator,))
+        out = np.zeros((self.height, self.width, 3), dtype=np.float32)
+        _check_host(host_lib().spt_host_multi_film_read_robust(self._handle(), ROBUST_MON if estimator == "mon" else ROBUST_GMON, out.ctypes.data))
+        return out
+
+    def read_rgb8(self, source: str = "mean") -> np.ndarray:
+        """(height, width, 3) u8 of "mean", "mon" or "gmon"; "denoised" is refused: denoise_job(rgb8=True) returns those bytes."""
+        if source not in READ_SOURCES:
+            raise ValueError("read_rgb8: source is one of %s, not %r" % (", ".join(repr(k) for k in READ_SOURCES), source))
+        out = np.zeros((self.height, self.width, 3), dtype=np.uint8)
+        _check_host(host_lib().spt_host_multi_film_read_rgb8(self._handle(), READ_SOURCES[source], out.ctypes.data))
+        return out
+
+    def denoise_job(self, guide: Optional["MultiFilm"] = None, albedo: Optional["MultiFilm"] = None, demodulate: bool = False,
+                    rgb8: bool = False, **params) -> np.ndarray:
+        """ProgressiveFilm.denoise_job with multi films: mean and variance of the mean of the film, the guide and the albedo film
+        are gathered into full images and filtered by one spt_denoise_image on the first replica."""
+        d = _denoise_keywords("denoise_job", params)
+        dp = DenoiseParams(C.sizeof(DenoiseParams), d["iterations"], d["k_color"], d["k_guide"], d["eps_color"], d["eps_guide"])
+        job = MultiFilmDenoiseJob(C.sizeof(MultiFilmDenoiseJob), (DENOISE_DEMODULATE if demodulate else 0) | (DENOISE_OUT_RGB8 if rgb8 else 0),
+                                  guide._handle() if guide is not None else None, albedo._handle() if albedo is not None else None, C.pointer(dp),
+                                  d["k_albedo"], d["eps_albedo"], d["eps_demod"], 0)
+        out = np.zeros((self.height, self.width, 3), dtype=np.uint8 if rgb8 else np.float32)
+        _check_host(host_lib().spt_host_multi_film_denoise(self._handle(), C.byref(job), out.ctypes.data))
+        return out
+
+    def close(self) -> None:
+        if self._h:
+            host_lib().spt_host_multi_film_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self) -> "MultiFilm":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class MultiDevice:
     """One call, N devices, one film (spt_host_multi_*): a scene replica and a worker thread per device, interleaved row strips,
     every device's rows DMA-ed straight into the caller's film.  The reference's counterpart is the thread fan-out of
@@ -795,6 +997,7 @@ class MultiDevice:
         self._api = api if api is not None else hip_device_api()
         self._h = C.c_void_p()
         self._film = None   # the film the library holds page-locked (spt_host.h): kept alive until it pins another or is destroyed
+        self._films = weakref.WeakSet()   # MultiFilm objects on these replicas: destroyed before them
         desc = scene.desc
         devs = (C.c_int32 * len(self.devices))(*self.devices)
         _check_host(host_lib().spt_host_multi_create(C.byref(desc), C.byref(self._api), len(self.devices), devs, C.byref(self._h)))
@@ -821,7 +1024,17 @@ class MultiDevice:
             write_image(config.output_filename, film)
         return film
 
+    def progressive(self, renderer: "PathTracer", config: OutputConfig, strip_rows: int = 0, first_sample: int = 0, moments: bool = False,
+                    flags: int = 0, buckets: int = 0, film_api: Optional[DeviceFilmApi] = None) -> MultiFilm:
+        """PathTracer.progressive over all devices: a MultiFilm, one shard film per replica (shard k of n, strips of `strip_rows`
+        rows, 0 = render()'s default).  `flags` are extra SPT_RENDER_* bits of the plan: RENDER_DEBUG_NORMAL / RENDER_AOV_ALBEDO
+        with moments=True make the guide / albedo multi film of MultiFilm.denoise_job.  `film_api` defaults to libspt_hip.so's
+        functions; tests pass stand-ins."""
+        return MultiFilm(self, renderer, config, strip_rows, first_sample, moments, flags, buckets, film_api)
+
     def close(self) -> None:
+        for film in list(getattr(self, "_films", ())):
+            film.close()
         if self._h:
             host_lib().spt_host_multi_destroy(self._h)
             self._h = C.c_void_p()

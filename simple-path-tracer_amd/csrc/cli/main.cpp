@@ -16,6 +16,8 @@
 // with libspt_host, renders with libspt_hip (HIP kernels only) and writes the image; like the reference it reports the
 // time spent inside `render`.  The images of a film (previews, the final image, --noisy-out, --mean-out) leave the device as the
 // 8-bit image the reference saves (spt_film_read_rgb8: a quarter of the float film's bytes); the EXR outputs stay float.
+// --film-devices d0,d1,.. (an index may repeat) runs the same progressive loop over a multi film on those devices (one shard film per
+// device, spt_host_multi_film_*; the denoiser runs once on the gathered image, spt_denoise_image) and writes the same bytes.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -34,7 +36,170 @@ static void usage() {
                  "           [--adaptive REL [--adaptive-floor A] [--adaptive-min-samples N]] [--samples-out counts.exr]\n"
                  "           [--denoise [--denoise-iterations K] [--guide-samples N] [--noisy-out noisy.png]\n"
                  "            [--guide normal|albedo|both] [--demodulate] [--albedo-out albedo.png]]\n"
-                 "           [--robust K [--robust-estimator mon|gmon] [--mean-out mean.png]]   (K odd, 3 .. 15)\n");
+                 "           [--robust K [--robust-estimator mon|gmon] [--mean-out mean.png]]   (K odd, 3 .. 15)\n"
+                 "           [--film-devices a,b,..]   (the progressive options above over several devices)\n");
+}
+
+// "0,1,2" -> indices; false for an empty list, an empty item or anything but decimal digits
+static bool parse_device_list(const std::string& list, std::vector<int32_t>* out) {
+    out->clear();
+    if (list.empty()) return false;
+    for (size_t pos = 0; pos <= list.size();) {
+        const size_t comma = std::min(list.find(',', pos), list.size());
+        const std::string item = list.substr(pos, comma - pos);
+        if (item.empty() || item.size() > 6 || item.find_first_not_of("0123456789") != std::string::npos) return false;
+        out->push_back(std::atoi(item.c_str()));
+        pos = comma + 1;
+    }
+    return !out->empty();
+}
+
+// What the progressive loop needs to know: the command line's options, the plan and where the images go.
+struct ProgressiveJob {
+    spt_host_scene* hs;
+    spt_camera cam;
+    spt_render_params params;
+    std::vector<int32_t> devices;
+    uint32_t strip_rows, preview_every;
+    double time_limit;
+    bool adaptive_on;
+    double adaptive, adaptive_floor;
+    uint32_t adaptive_min;
+    bool denoise, guide_normal, guide_albedo, demodulate;
+    uint32_t denoise_iterations, guide_samples;
+    bool robust;
+    uint32_t robust_k, estimator;
+    std::string out_path, noisy_out, albedo_out, mean_out, variance_out, samples_out;
+};
+
+// The progressive loop of main() over a multi film (--film-devices): the same increments, the same decisions and the same
+// read-outs in the same order, every spt_film_* call replaced by its spt_host_multi_film_* counterpart.  Returns the exit code.
+static int progressive_on_devices(const ProgressiveJob& o) {
+    const uint32_t width = o.params.width, height = o.params.height;
+    const spt_render_params& params = o.params;
+    const spt_device_api api = {spt_scene_create, spt_scene_destroy, spt_render, spt_last_error, spt_pin_host, spt_unpin_host};
+    spt_device_film_api fapi;
+    std::memset(&fapi, 0, sizeof fapi);
+    fapi.size = (uint32_t)sizeof fapi;
+    fapi.film_create = spt_film_create;
+    fapi.film_destroy = spt_film_destroy;
+    fapi.film_render = spt_film_render;
+    fapi.film_samples = spt_film_samples;
+    fapi.film_read = spt_film_read;
+    fapi.film_read_counts = spt_film_read_counts;
+    fapi.film_adapt = spt_film_adapt;
+    fapi.film_buckets = spt_film_buckets;
+    fapi.film_read_robust = spt_film_read_robust;
+    fapi.film_read_rgb8 = spt_film_read_rgb8;
+    fapi.denoise_image = spt_denoise_image;
+    fapi.last_error = spt_last_error;
+    spt_host_multi* multi = nullptr;
+    spt_host_multi_film *pf = nullptr, *guide = nullptr, *albedo = nullptr;
+    auto finish = [&](int code) {
+        if (albedo) spt_host_multi_film_destroy(albedo);
+        if (guide) spt_host_multi_film_destroy(guide);
+        if (pf) spt_host_multi_film_destroy(pf);
+        if (multi) spt_host_multi_destroy(multi);
+        spt_host_scene_free(o.hs);
+        return code;
+    };
+    auto fail = [&](const char* why = nullptr) {
+        std::fprintf(stderr, "Error: %s\n", why ? why : spt_host_last_error());
+        return finish(1);
+    };
+    if (spt_host_multi_create(spt_host_scene_desc(o.hs), &api, (uint32_t)o.devices.size(), o.devices.data(), &multi) != SPT_OK) return fail();
+    std::fprintf(stderr, "Scene JSON is loaded successfully. Rendering a film on %zu device(s)...\n", o.devices.size());
+    const auto t0 = std::chrono::steady_clock::now();
+    const bool moments = !o.variance_out.empty() || o.adaptive_on || o.denoise;
+    if (spt_host_multi_film_create(multi, &fapi, &o.cam, &params, o.strip_rows, 0, moments ? (uint32_t)SPT_FILM_MOMENTS : 0u, o.robust ? o.robust_k : 0u, &pf) != SPT_OK)
+        return fail();
+    const spt_denoise_params dn = {(uint32_t)sizeof(spt_denoise_params), o.denoise_iterations, 2.0f, 1.0f, 1e-8f, 1e-2f};
+    const uint32_t n_guide = std::max(2u, std::min(params.spp, o.guide_samples));
+    if (o.denoise && o.guide_normal) {
+        spt_render_params gp = params;
+        gp.flags |= SPT_RENDER_DEBUG_NORMAL;
+        if (spt_host_multi_film_create(multi, &fapi, &o.cam, &gp, o.strip_rows, 0, (uint32_t)SPT_FILM_MOMENTS, 0, &guide) != SPT_OK) return fail();
+        if (spt_host_multi_film_render(guide, n_guide) != SPT_OK) return fail();
+    }
+    if (o.denoise && o.guide_albedo) {
+        uint32_t honoured = 0;
+        if (spt_render_flags_supported(&honoured) != SPT_OK) return fail(spt_last_error());
+        if (!(honoured & SPT_RENDER_AOV_ALBEDO)) return fail("this libspt_hip.so renders no albedo films");
+        spt_render_params ap = params;
+        ap.flags = (ap.flags & ~(uint32_t)SPT_RENDER_DEBUG_NORMAL) | SPT_RENDER_AOV_ALBEDO;
+        if (spt_host_multi_film_create(multi, &fapi, &o.cam, &ap, o.strip_rows, 0, (uint32_t)SPT_FILM_MOMENTS, 0, &albedo) != SPT_OK) return fail();
+        if (spt_host_multi_film_render(albedo, n_guide) != SPT_OK) return fail();
+    }
+    spt_host_multi_film_denoise_job job;
+    std::memset(&job, 0, sizeof job);
+    job.size = (uint32_t)sizeof job;
+    job.flags = SPT_DENOISE_OUT_RGB8 | (o.demodulate ? (uint32_t)SPT_DENOISE_DEMODULATE : 0u);
+    job.guide = guide;
+    job.albedo = albedo;
+    job.params = &dn;
+    job.k_albedo = 1.0f; job.eps_albedo = 1e-2f; job.eps_demod = 1e-2f;
+    std::vector<uint8_t> film8((size_t)width * height * 3);
+    auto write_image8 = [&](const std::string& path) {
+        if (spt_host_write_image(path.c_str(), film8.data(), width, height) != SPT_OK)
+            std::printf("Failed to save image, err: %s\n", spt_host_last_error());  // printed and ignored, like pt.rs:292-294
+    };
+    uint32_t done = 0;
+    auto read_image = [&]() {
+        if (o.robust) return spt_host_multi_film_read_rgb8(pf, o.estimator == (uint32_t)SPT_ROBUST_MON ? SPT_READ_ROBUST_MON : SPT_READ_ROBUST_GMON, film8.data());
+        if (o.denoise && done >= 2) return spt_host_multi_film_denoise(pf, &job, film8.data());
+        return spt_host_multi_film_read_rgb8(pf, SPT_READ_MEAN, film8.data());
+    };
+    const uint32_t inc = o.preview_every ? o.preview_every : ((o.time_limit > 0.0 || o.adaptive_on) ? std::max(1u, params.spp / 16u) : params.spp);
+    uint32_t active = width * height;
+    while (done < params.spp) {
+        const uint32_t n = std::min(inc, params.spp - done);
+        if (spt_host_multi_film_render(pf, n) != SPT_OK) return fail();
+        done += n;
+        if (o.adaptive_on && spt_host_multi_film_adapt(pf, (float)o.adaptive, (float)o.adaptive_floor, o.adaptive_min, &active) != SPT_OK) return fail();
+        const bool out_of_time = o.time_limit > 0.0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() >= o.time_limit;
+        if (done == params.spp || out_of_time || active == 0) break;
+        if (o.preview_every) {
+            if (read_image() != SPT_OK) return fail();
+            write_image8(o.out_path);
+        }
+    }
+    if (!o.noisy_out.empty()) {
+        if (spt_host_multi_film_read_rgb8(pf, SPT_READ_MEAN, film8.data()) != SPT_OK) return fail();
+        write_image8(o.noisy_out);
+    }
+    if (!o.albedo_out.empty()) {
+        if (spt_host_multi_film_read_rgb8(albedo, SPT_READ_MEAN, film8.data()) != SPT_OK) return fail();
+        write_image8(o.albedo_out);
+    }
+    if (!o.mean_out.empty()) {
+        if (spt_host_multi_film_read_rgb8(pf, SPT_READ_MEAN, film8.data()) != SPT_OK) return fail();
+        write_image8(o.mean_out);
+    }
+    if (read_image() != SPT_OK) return fail();
+    if (o.adaptive_on) {
+        std::fprintf(stderr, "Rendered %u of %u samples per pixel, %u of %u pixels active\n", done, params.spp, active, width * height);
+    } else if (o.time_limit > 0.0) {
+        std::fprintf(stderr, "Rendered %u of %u samples per pixel\n", done, params.spp);
+    }
+    if (o.time_limit > 0.0 && done < params.spp && params.sampler == SPT_SAMPLER_JITTERED)
+        std::fprintf(stderr, "Warning: the jittered sampler's %ux%u grid is walked row by row: these %u samples cover only its first rows\n",
+                     params.division_x, params.division_y, done);
+    if (!o.variance_out.empty()) {
+        std::vector<float> var((size_t)width * height * 3);
+        if (spt_host_multi_film_read(pf, SPT_FILM_VAR_OF_MEAN, var.data()) != SPT_OK) return fail();
+        if (spt_host_write_exr(o.variance_out.c_str(), var.data(), width, height) != SPT_OK) return fail();
+    }
+    if (!o.samples_out.empty()) {   // the samples each pixel covers, as f32 in all three channels
+        std::vector<uint32_t> counts((size_t)width * height);
+        if (spt_host_multi_film_read_counts(pf, counts.data()) != SPT_OK) return fail();
+        std::vector<float> rgb((size_t)width * height * 3);
+        for (size_t k = 0; k < counts.size(); ++k) rgb[3 * k] = rgb[3 * k + 1] = rgb[3 * k + 2] = (float)counts[k];
+        if (spt_host_write_exr(o.samples_out.c_str(), rgb.data(), width, height) != SPT_OK) return fail();
+    }
+    write_image8(o.out_path);
+    const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    std::fprintf(stderr, "Finished, time used: %.3fs (%.1f Msamples/s, %u samples per pixel)\n", sec, (double)width * height * done / (sec * 1e6), done);
+    return finish(0);
 }
 
 int main(int argc, char** argv) {
@@ -57,6 +222,8 @@ int main(int argc, char** argv) {
     int robust_k = 0;
     std::string robust_estimator, mean_out;
     std::vector<int32_t> device_list;
+    std::vector<int32_t> film_devices;
+    bool film_devices_given = false, film_devices_ok = true;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char* {
@@ -102,6 +269,7 @@ int main(int argc, char** argv) {
         else if (a == "--robust") { robust_k = std::atoi(next()); robust = true; }
         else if (a == "--robust-estimator") robust_estimator = next();
         else if (a == "--mean-out") mean_out = next();
+        else if (a == "--film-devices") { film_devices_given = true; film_devices_ok = parse_device_list(next(), &film_devices); }
         else { usage(); return 2; }
     }
     if (scene_path.empty() || renderer_path.empty() || out_path.empty()) { usage(); return 2; }
@@ -133,6 +301,19 @@ int main(int argc, char** argv) {
     }
     const uint32_t estimator = robust_estimator == "mon" ? (uint32_t)SPT_ROBUST_MON : (uint32_t)SPT_ROBUST_GMON;
     const bool progressive = preview_every > 0 || time_limit > 0.0 || !variance_out.empty() || adaptive_on || !samples_out.empty() || denoise || robust;
+    if (film_devices_given && !film_devices_ok) {
+        std::fprintf(stderr, "Error: --film-devices takes a list of device indices such as 0,1,2 (an index may repeat)\n");
+        return 2;
+    }
+    if (film_devices_given && gpus > 0) {
+        std::fprintf(stderr, "Error: --film-devices and --gpus / --devices exclude each other (--gpus renders one image in one call, --film-devices a film in increments)\n");
+        return 2;
+    }
+    if (film_devices_given && !progressive) {
+        std::fprintf(stderr, "Error: --film-devices needs a progressive option (--preview-every, --time-limit, --variance-out, --adaptive, --samples-out, --denoise or --robust); "
+                             "--gpus / --devices render a plain image on several devices\n");
+        return 2;
+    }
     if (progressive && gpus > 1) {
         std::fprintf(stderr, "Error: --preview-every, --time-limit, --variance-out, --adaptive, --samples-out, --denoise and --robust render on one device (a film object), "
                              "not on the %d of --gpus / --devices\n", gpus);
@@ -175,6 +356,18 @@ int main(int argc, char** argv) {
     params.shard_count = 1;
     params.strip_rows = 16;
     if (debug_normal) params.flags |= SPT_RENDER_DEBUG_NORMAL;
+    if (film_devices_given) {   // the progressive loop over a multi film: a second implementation of the loop below
+        ProgressiveJob o;
+        o.hs = hs; o.cam = cam; o.params = params; o.devices = film_devices;
+        o.strip_rows = strip_rows; o.preview_every = preview_every; o.time_limit = time_limit;
+        o.adaptive_on = adaptive_on; o.adaptive = adaptive; o.adaptive_floor = adaptive_floor; o.adaptive_min = adaptive_min;
+        o.denoise = denoise; o.guide_normal = guide_normal; o.guide_albedo = guide_albedo; o.demodulate = demodulate;
+        o.denoise_iterations = denoise_iterations; o.guide_samples = guide_samples;
+        o.robust = robust; o.robust_k = (uint32_t)robust_k; o.estimator = estimator;
+        o.out_path = out_path; o.noisy_out = noisy_out; o.albedo_out = albedo_out; o.mean_out = mean_out;
+        o.variance_out = variance_out; o.samples_out = samples_out;
+        return progressive_on_devices(o);
+    }
     std::vector<float> film((size_t)width * height * 3);
     std::vector<spt_render_stats> st((size_t)std::max(gpus, 1));
     std::memset(st.data(), 0, st.size() * sizeof(spt_render_stats));

@@ -565,6 +565,51 @@ __global__ void __launch_bounds__(256) k_denoise_pack_albedo(uint32_t n_pixels, 
     }
 }
 
+// The same records from caller-provided images (spt_denoise_image): planar RGB triplets as SPT_FILM_MEAN / SPT_FILM_VAR_OF_MEAN
+// return them, one array per quantity, instead of a film's sums.  One lane per pixel: one 12-byte load per array (the compiler
+// joins the triplet into a global_load_dwordx3; consecutive lanes read consecutive triplets, so a wave's load covers 768
+// contiguous bytes), the operations of k_denoise_pack / k_denoise_pack_albedo in their order, one 16-byte store per record.
+// The four instantiations take 9, 18, 22 and 24 VGPRs and no scratch.  The kernel moves 24 bytes in and 16 out per pixel and
+// array pair and does at most six divisions.  From those byte counts it should be bound by memory and small next to an a-trous
+// iteration (25 taps with two divisions and an exponential each); its time has not been measured.
+struct DenoiseImage {
+    const float* mean;          // m
+    const float* var;           // v
+    const float* guide_mean;    // g   (kGuide)
+    const float* guide_var;     // u
+    const float* albedo_mean;   // al  (kAlbedo)
+    const float* albedo_var;    // ua
+};
+
+SPT_DEV f3 denoise_image_rgb(const float* a, uint32_t lp) {
+    const size_t i = 3 * (size_t)lp;
+    return mk3(a[i], a[i + 1], a[i + 2]);
+}
+
+template <bool kGuide, bool kAlbedo>
+__global__ void __launch_bounds__(256) k_denoise_pack_image(uint32_t n_pixels, DenoiseImage in, DenoiseAlbedo b, float4* color_out,
+                                                            float4* guide_out, float4* albedo_out) {
+    const uint32_t lp = blockIdx.x * blockDim.x + threadIdx.x;
+    if (lp >= n_pixels) return;
+    f3 m = denoise_image_rgb(in.mean, lp), v = denoise_image_rgb(in.var, lp);
+    if constexpr (kAlbedo) {
+        const f3 al = denoise_image_rgb(in.albedo_mean, lp), ua = denoise_image_rgb(in.albedo_var, lp);
+        const float4 ar = make_float4(al.x, al.y, al.z, (ua.x + ua.y) + ua.z);
+        if (b.demodulate != 0u) {
+            const f3 dem = denoise_dem(ar, b.eps_d);
+            m = mk3(m.x / dem.x, m.y / dem.y, m.z / dem.z);
+            v = mk3(v.x / (dem.x * dem.x), v.y / (dem.y * dem.y), v.z / (dem.z * dem.z));
+        }
+        albedo_out[lp] = ar;
+    }
+    const float lv = ((0.299f * 0.299f) * v.x + (0.587f * 0.587f) * v.y) + (0.114f * 0.114f) * v.z;
+    color_out[lp] = make_float4(m.x, m.y, m.z, lv);
+    if constexpr (kGuide) {
+        const f3 g = denoise_image_rgb(in.guide_mean, lp), u = denoise_image_rgb(in.guide_var, lp);
+        guide_out[lp] = make_float4(g.x, g.y, g.z, (u.x + u.y) + u.z);
+    }
+}
+
 // k_denoise_atrous with the albedo record: one more 16-byte load per tap (a row of five is 15 loads with a guide), the same order
 // of the sums.  kLast: the demodulated colour is multiplied by dem in the store, pass-through pixels included.
 template <bool kGuide, bool kLast>

@@ -84,6 +84,26 @@ struct DeviceBuffer {   // owning: freed with the scene object (the owner select
     T* as() const { return reinterpret_cast<T*>(p); }
 };
 
+struct PinnedBuffer {   // owning, page-locked host memory: freed with the scene object, like a DeviceBuffer
+    void* p = nullptr;
+    size_t bytes = 0;
+    PinnedBuffer() = default;
+    PinnedBuffer(const PinnedBuffer&) = delete;
+    PinnedBuffer& operator=(const PinnedBuffer&) = delete;
+    ~PinnedBuffer() { release(); }
+    void ensure(size_t n) {
+        if (n <= bytes) return;
+        release();
+        HIP_CHECK(hipHostMalloc(&p, n, hipHostMallocDefault));
+        bytes = n;
+    }
+    void release() {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
+};
+
 uint32_t bvh_depth(const spt_bvh_node* nodes, uint32_t n_nodes, uint32_t root, uint32_t n_items, const char* what) {
     // iterative DFS; also validates indices so the kernels never read out of bounds
     if (n_nodes == 0) return 0;
@@ -520,6 +540,7 @@ struct BezierLib {
     decltype(&spt_film_read_buckets) film_read_buckets = nullptr;
     decltype(&spt_film_read_robust) film_read_robust = nullptr;
     decltype(&spt_film_read_rgb8) film_read_rgb8 = nullptr;
+    decltype(&spt_denoise_image) denoise_image = nullptr;
     decltype(&spt_trace_closest) trace_closest = nullptr;
     decltype(&spt_trace_any) trace_any = nullptr;
     decltype(&spt_debug_bxdf) debug_bxdf = nullptr;
@@ -564,6 +585,11 @@ struct spt_scene {
     //  is made by the first overlapped render)
     DeviceBuffer qa[5], qb[5], hit_f4, hit_inst, hit_f4_next, hit_inst_next, sh[3], counts[2], rad[2], film, first_slot[2], slot_bits[2], out;
     DeviceBuffer trace_in, trace_out, visits, inst_class;
+    // spt_denoise_image's workspace, made by its first call and reused: the up to six input images (planar RGB f32) and the
+    // page-locked staging buffer they go up through, the records of the a-trous kernels (two colour arrays, guide, albedo), the
+    // filtered image and its bytes.  No render and no film touches them
+    DeviceBuffer img_in[6], img_color[2], img_guide, img_albedo, img_out, img_out8;
+    PinnedBuffer img_stage;
     std::mutex mu;
     double bs_center[3] = {0, 0, 0}, bs_radius = 0;  // bounding sphere of all instance boxes
     double world_lo[3] = {0, 0, 0}, world_hi[3] = {0, 0, 0};   // their union
@@ -870,7 +896,7 @@ const BezierLib* bezier_lib() {
                          sym(lib.film_adapt, "spt_film_adapt") && sym(lib.film_read_counts, "spt_film_read_counts") &&
                          sym(lib.film_denoise, "spt_film_denoise") && sym(lib.film_denoise_job, "spt_film_denoise_job") && sym(lib.film_buckets, "spt_film_buckets") &&
                          sym(lib.film_read_buckets, "spt_film_read_buckets") && sym(lib.film_read_robust, "spt_film_read_robust") &&
-                         sym(lib.film_read_rgb8, "spt_film_read_rgb8") &&
+                         sym(lib.film_read_rgb8, "spt_film_read_rgb8") && sym(lib.denoise_image, "spt_denoise_image") &&
                          sym(lib.trace_closest, "spt_trace_closest") && sym(lib.trace_any, "spt_trace_any") && sym(lib.debug_bxdf, "spt_debug_bxdf") &&
                          sym(lib.debug_render_info, "spt_debug_render_info") &&
                          sym(lib.last_error, "spt_last_error") && sym(version, "spt_abi_version");
@@ -2592,17 +2618,19 @@ struct FilmReadOut {
 
 // The end of every read-out: n_floats floats at `src` on the device (the staging buffer f->out for everything but the raw sums)
 // go to the host as they are, or through k_pack_rgb8 and the film's byte buffer.  Synchronous.
-static void film_deliver(spt_film* f, const void* src, size_t n_floats, const FilmReadOut& to, hipStream_t st) {
+// (`out8`: the byte buffer of whoever owns `src` - a film's, or the scene's for spt_denoise_image.)
+static void deliver(DeviceBuffer& out8, const void* src, size_t n_floats, const FilmReadOut& to, hipStream_t st) {
     if (to.u8) {
         if (n_floats > 0xfffffffcull) fail(SPT_ERR_UNSUPPORTED, "film_read_rgb8: shard larger than 2^32 - 4 bytes");
-        f->out8.ensure(n_floats);
-        launch_pack_rgb8((uint32_t)n_floats, static_cast<const float*>(src), f->out8.as<uint8_t>(), st);
-        HIP_CHECK(hipMemcpyAsync(to.u8, f->out8.p, n_floats, hipMemcpyDeviceToHost, st));
+        out8.ensure(n_floats);
+        launch_pack_rgb8((uint32_t)n_floats, static_cast<const float*>(src), out8.as<uint8_t>(), st);
+        HIP_CHECK(hipMemcpyAsync(to.u8, out8.p, n_floats, hipMemcpyDeviceToHost, st));
     } else {
         HIP_CHECK(hipMemcpyAsync(to.f32, src, n_floats * sizeof(float), hipMemcpyDeviceToHost, st));
     }
     HIP_CHECK(hipStreamSynchronize(st));
 }
+static void film_deliver(spt_film* f, const void* src, size_t n_floats, const FilmReadOut& to, hipStream_t st) { deliver(f->out8, src, n_floats, to, st); }
 
 // spt_film_read behind its argument checks (the scene's lock is held)
 static spt_status film_read_locked(spt_film* f, uint32_t what, const FilmReadOut& to) {
@@ -2759,6 +2787,55 @@ struct DenoiseAlbedoJob {
     bool demodulate = false;
 };
 
+// The params, k_* and eps_* checks of spt_film_denoise_job (and spt_denoise_image); the parameters with the defaults filled in.
+static spt_denoise_params denoise_params_checked(const spt_denoise_params* params, const DenoiseAlbedoJob& aj) {
+    for (const float v : {aj.k_albedo, aj.eps_albedo, aj.eps_demod})   // (with or without an albedo film, as k_guide without a guide)
+        if (!std::isfinite(v) || !(v > 0.0f)) fail(SPT_ERR_INVALID_ARG, "film_denoise_job: k_albedo, eps_albedo and eps_demod must be finite and > 0");
+    spt_denoise_params dp{(uint32_t)sizeof(spt_denoise_params), 5u, 2.0f, 1.0f, 1e-8f, 1e-2f};
+    if (params) {
+        if (params->size < sizeof(spt_denoise_params)) fail(SPT_ERR_INVALID_ARG, "film_denoise: params->size is smaller than spt_denoise_params");
+        dp = *params;
+    }
+    if (dp.iterations < 1u || dp.iterations > 8u) fail(SPT_ERR_INVALID_ARG, "film_denoise: iterations must be 1 .. 8");
+    for (const float v : {dp.k_color, dp.k_guide, dp.eps_color, dp.eps_guide})
+        if (!std::isfinite(v) || !(v > 0.0f)) fail(SPT_ERR_INVALID_ARG, "film_denoise: k_color, k_guide, eps_color and eps_guide must be finite and > 0");
+    return dp;
+}
+
+// The iterations of the filter over packed records: color[0] holds c_0 / lv_0, gbuf / abuf the guide's and the albedo's records
+// (null: no such term); the last iteration writes width * rows * 3 f32 to rgb_out.
+static void denoise_iterate(hipStream_t st, uint32_t width, uint32_t rows, const spt_denoise_params& dp, const DenoiseAlbedo& ab,
+                            float4* const color[2], const float4* gbuf, const float4* abuf, float* rgb_out) {
+    const bool guide = gbuf != nullptr, albedo = abuf != nullptr;
+    const dim3 block(kBlock);
+    DenoiseArgs a{};
+    a.width = width;
+    a.rows = rows;
+    a.tiles_x = (width + kTile - 1) / kTile;
+    a.kc2 = dp.k_color * dp.k_color;
+    a.kg2 = dp.k_guide * dp.k_guide;
+    a.eps_c = dp.eps_color;
+    a.eps_g = dp.eps_guide;
+    const dim3 grid(a.tiles_x * ((rows + kTile - 1) / kTile));
+    for (uint32_t k = 0; k < dp.iterations; ++k) {
+        a.step = (int32_t)(1u << k);
+        const float4* src = color[k & 1u];
+        float4* dst = color[(k + 1u) & 1u];
+        const bool last = k + 1u == dp.iterations;
+        auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, a, src, gbuf, dst, rgb_out); };
+        auto launch_albedo = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, a, ab, src, gbuf, abuf, dst, rgb_out); };
+        if (albedo && guide && last) launch_albedo(k_denoise_atrous_albedo<true, true>);
+        else if (albedo && guide) launch_albedo(k_denoise_atrous_albedo<true, false>);
+        else if (albedo && last) launch_albedo(k_denoise_atrous_albedo<false, true>);
+        else if (albedo) launch_albedo(k_denoise_atrous_albedo<false, false>);
+        else if (guide && last) launch(k_denoise_atrous<true, true>);
+        else if (guide) launch(k_denoise_atrous<true, false>);
+        else if (last) launch(k_denoise_atrous<false, true>);
+        else launch(k_denoise_atrous<false, false>);
+        HIP_CHECK(hipGetLastError());
+    }
+}
+
 // spt_film_denoise and spt_film_denoise_job behind their argument checks (the scene's lock is held)
 static spt_status film_denoise_locked(spt_film* f, spt_film* guide, const spt_denoise_params* params, const FilmReadOut& to,
                                       const DenoiseAlbedoJob& aj = DenoiseAlbedoJob{}) {
@@ -2793,16 +2870,7 @@ static spt_status film_denoise_locked(spt_film* f, spt_film* guide, const spt_de
             (g.strip_rows ? g.strip_rows : 1u) != (p.strip_rows ? p.strip_rows : 1u) || albedo->rows != f->rows)
             fail(SPT_ERR_INVALID_ARG, "film_denoise_job: the albedo film has another shard layout");
     }
-    for (const float v : {aj.k_albedo, aj.eps_albedo, aj.eps_demod})   // (with or without an albedo film, as k_guide without a guide)
-        if (!std::isfinite(v) || !(v > 0.0f)) fail(SPT_ERR_INVALID_ARG, "film_denoise_job: k_albedo, eps_albedo and eps_demod must be finite and > 0");
-    spt_denoise_params dp{(uint32_t)sizeof(spt_denoise_params), 5u, 2.0f, 1.0f, 1e-8f, 1e-2f};
-    if (params) {
-        if (params->size < sizeof(spt_denoise_params)) fail(SPT_ERR_INVALID_ARG, "film_denoise: params->size is smaller than spt_denoise_params");
-        dp = *params;
-    }
-    if (dp.iterations < 1u || dp.iterations > 8u) fail(SPT_ERR_INVALID_ARG, "film_denoise: iterations must be 1 .. 8");
-    for (const float v : {dp.k_color, dp.k_guide, dp.eps_color, dp.eps_guide})
-        if (!std::isfinite(v) || !(v > 0.0f)) fail(SPT_ERR_INVALID_ARG, "film_denoise: k_color, k_guide, eps_color and eps_guide must be finite and > 0");
+    const spt_denoise_params dp = denoise_params_checked(params, aj);
     if (f->radius != 0.5f || (guide && guide->radius != 0.5f) || (albedo && albedo->radius != 0.5f))
         fail(SPT_ERR_UNSUPPORTED, "film_denoise: needs the box radius 0.5 on both films (every sample of the pixel weighs 1)");
     if (p.shard_count > 1u) fail(SPT_ERR_UNSUPPORTED, "film_denoise: the plan has shard_count > 1 (a shard's packed rows are not neighbours in the image)");
@@ -2830,32 +2898,7 @@ static spt_status film_denoise_locked(spt_film* f, spt_film* guide, const spt_de
     } else if (guide) hipLaunchKernelGGL(k_denoise_pack<true>, pack_grid, block, 0, st, n_pix, denoise_input(f), denoise_input(guide), color[0], gbuf);
     else hipLaunchKernelGGL(k_denoise_pack<false>, pack_grid, block, 0, st, n_pix, denoise_input(f), DenoiseFilm{}, color[0], gbuf);
     HIP_CHECK(hipGetLastError());
-    DenoiseArgs a{};
-    a.width = p.width;
-    a.rows = f->rows;
-    a.tiles_x = (p.width + kTile - 1) / kTile;
-    a.kc2 = dp.k_color * dp.k_color;
-    a.kg2 = dp.k_guide * dp.k_guide;
-    a.eps_c = dp.eps_color;
-    a.eps_g = dp.eps_guide;
-    const dim3 grid(a.tiles_x * ((f->rows + kTile - 1) / kTile));
-    for (uint32_t k = 0; k < dp.iterations; ++k) {
-        a.step = (int32_t)(1u << k);
-        const float4* src = color[k & 1u];
-        float4* dst = color[(k + 1u) & 1u];
-        const bool last = k + 1u == dp.iterations;
-        auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, a, src, gbuf, dst, f->out.as<float>()); };
-        auto launch_albedo = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, a, ab, src, gbuf, abuf, dst, f->out.as<float>()); };
-        if (albedo && guide && last) launch_albedo(k_denoise_atrous_albedo<true, true>);
-        else if (albedo && guide) launch_albedo(k_denoise_atrous_albedo<true, false>);
-        else if (albedo && last) launch_albedo(k_denoise_atrous_albedo<false, true>);
-        else if (albedo) launch_albedo(k_denoise_atrous_albedo<false, false>);
-        else if (guide && last) launch(k_denoise_atrous<true, true>);
-        else if (guide) launch(k_denoise_atrous<true, false>);
-        else if (last) launch(k_denoise_atrous<false, true>);
-        else launch(k_denoise_atrous<false, false>);
-        HIP_CHECK(hipGetLastError());
-    }
+    denoise_iterate(st, p.width, f->rows, dp, ab, color, gbuf, abuf, f->out.as<float>());
     film_deliver(f, f->out.p, (size_t)n_pix * 3, to, st);
     return SPT_OK;
 }
@@ -2893,6 +2936,79 @@ spt_status spt_film_denoise_job(spt_film* f, const spt_denoise_job* job, void* o
     const FilmReadOut to{rgb8 ? nullptr : static_cast<float*>(out), rgb8 ? static_cast<uint8_t*>(out) : nullptr};
     std::lock_guard<std::mutex> lock(f->sc->mu);
     return guarded("film_denoise_job", [&] { return film_denoise_locked(f, job->guide, job->params, to, aj); });
+}
+
+// The filter of spt_film_denoise_job on caller-provided images: the arrays go up through the scene's page-locked staging buffer,
+// k_denoise_pack_image makes the records, and the a-trous kernels, k_pack_rgb8 and the copy-out are those of the film calls.
+spt_status spt_denoise_image(const spt_scene* scene_c, const spt_image_denoise_job* job, void* out) {
+    if (!scene_c || !job || !out) { g_error = "denoise_image: null argument"; return SPT_ERR_INVALID_ARG; }
+    if (job->size < offsetof(spt_image_denoise_job, k_albedo)) { g_error = "denoise_image: job->size ends before k_albedo"; return SPT_ERR_INVALID_ARG; }
+    if (!job->mean || !job->var) { g_error = "denoise_image: null mean or var array"; return SPT_ERR_INVALID_ARG; }
+    if ((job->guide_mean != nullptr) != (job->guide_var != nullptr)) { g_error = "denoise_image: guide_mean and guide_var go together (both or neither)"; return SPT_ERR_INVALID_ARG; }
+    if ((job->albedo_mean != nullptr) != (job->albedo_var != nullptr)) { g_error = "denoise_image: albedo_mean and albedo_var go together (both or neither)"; return SPT_ERR_INVALID_ARG; }
+    if (job->flags & ~(uint32_t)(SPT_DENOISE_DEMODULATE | SPT_DENOISE_OUT_RGB8)) { g_error = "denoise_image: unknown flags"; return SPT_ERR_INVALID_ARG; }
+    if ((job->flags & SPT_DENOISE_DEMODULATE) && !job->albedo_mean) { g_error = "denoise_image: SPT_DENOISE_DEMODULATE needs the albedo arrays"; return SPT_ERR_INVALID_ARG; }
+    spt_scene* sc = const_cast<spt_scene*>(scene_c);
+    if (sc->fwd) return forwarded(sc->fwd, sc->fwd->denoise_image(sc->inner, job, out));
+    DenoiseAlbedoJob aj;
+    aj.demodulate = (job->flags & SPT_DENOISE_DEMODULATE) != 0;
+    // (the struct only grows at its tail: a float the caller's struct ends before keeps its default)
+    if (job->size >= offsetof(spt_image_denoise_job, k_albedo) + sizeof(float)) aj.k_albedo = job->k_albedo;
+    if (job->size >= offsetof(spt_image_denoise_job, eps_albedo) + sizeof(float)) aj.eps_albedo = job->eps_albedo;
+    if (job->size >= offsetof(spt_image_denoise_job, eps_demod) + sizeof(float)) aj.eps_demod = job->eps_demod;
+    const bool rgb8 = (job->flags & SPT_DENOISE_OUT_RGB8) != 0;
+    const FilmReadOut to{rgb8 ? nullptr : static_cast<float*>(out), rgb8 ? static_cast<uint8_t*>(out) : nullptr};
+    std::lock_guard<std::mutex> lock(sc->mu);
+    return guarded("denoise_image", [&] {
+        // every check comes before the first allocation, copy or launch: a refused call leaves the workspace as it was
+        const spt_denoise_params dp = denoise_params_checked(job->params, aj);
+        const uint64_t n_pix64 = (uint64_t)job->width * job->rows;
+        if (n_pix64 * 3u > 0xfffffffcull) fail(SPT_ERR_UNSUPPORTED, "denoise_image: image larger than 2^32 - 4 floats");
+        if (n_pix64 == 0) return SPT_OK;
+        const uint32_t n_pix = (uint32_t)n_pix64;
+        const bool guide = job->guide_mean != nullptr, albedo = job->albedo_mean != nullptr;
+        const float* const src[6] = {job->mean, job->var, job->guide_mean, job->guide_var, job->albedo_mean, job->albedo_var};
+        const size_t img_bytes = (size_t)n_pix * 3 * sizeof(float), rec_bytes = (size_t)n_pix * sizeof(float4);
+        HIP_CHECK(hipSetDevice(sc->device));
+        film_join(sc);
+        const hipStream_t st = sc->stream;
+        sc->img_stage.ensure(img_bytes * (2u + (guide ? 2u : 0u) + (albedo ? 2u : 0u)));
+        for (int k = 0; k < 6; ++k)
+            if (src[k]) sc->img_in[k].ensure(img_bytes);
+        sc->img_color[0].ensure(rec_bytes);
+        if (dp.iterations > 1u) sc->img_color[1].ensure(rec_bytes);
+        if (guide) sc->img_guide.ensure(rec_bytes);
+        if (albedo) sc->img_albedo.ensure(rec_bytes);
+        sc->img_out.ensure(img_bytes);
+        // Each array has a slot of its own in the staging buffer: the host copies array k + 1 into its slot while the DMA of
+        // array k is in flight, and nothing waits before the end of the call (which is why no slot is reused within it)
+        char* slot = static_cast<char*>(sc->img_stage.p);
+        for (int k = 0; k < 6; ++k) {
+            if (!src[k]) continue;
+            std::memcpy(slot, src[k], img_bytes);
+            HIP_CHECK(hipMemcpyAsync(sc->img_in[k].p, slot, img_bytes, hipMemcpyHostToDevice, st));
+            slot += img_bytes;
+        }
+        DenoiseImage in{};
+        in.mean = sc->img_in[0].as<float>();
+        in.var = sc->img_in[1].as<float>();
+        if (guide) { in.guide_mean = sc->img_in[2].as<float>(); in.guide_var = sc->img_in[3].as<float>(); }
+        if (albedo) { in.albedo_mean = sc->img_in[4].as<float>(); in.albedo_var = sc->img_in[5].as<float>(); }
+        float4* color[2] = {sc->img_color[0].as<float4>(), dp.iterations > 1u ? sc->img_color[1].as<float4>() : nullptr};
+        float4* const gbuf = guide ? sc->img_guide.as<float4>() : nullptr;
+        float4* const abuf = albedo ? sc->img_albedo.as<float4>() : nullptr;
+        const DenoiseAlbedo ab{aj.k_albedo * aj.k_albedo, aj.eps_albedo, aj.eps_demod, aj.demodulate ? 1u : 0u};
+        const dim3 pack_grid((n_pix + kBlock - 1) / kBlock), block(kBlock);
+        auto pack = [&](auto kernel) { hipLaunchKernelGGL(kernel, pack_grid, block, 0, st, n_pix, in, ab, color[0], gbuf, abuf); };
+        if (guide && albedo) pack(k_denoise_pack_image<true, true>);
+        else if (albedo) pack(k_denoise_pack_image<false, true>);
+        else if (guide) pack(k_denoise_pack_image<true, false>);
+        else pack(k_denoise_pack_image<false, false>);
+        HIP_CHECK(hipGetLastError());
+        denoise_iterate(st, job->width, job->rows, dp, ab, color, gbuf, abuf, sc->img_out.as<float>());
+        deliver(sc->img_out8, sc->img_out.p, (size_t)n_pix * 3, to, st);
+        return SPT_OK;
+    });
 }
 
 spt_status spt_render_flags_supported(uint32_t* mask) {

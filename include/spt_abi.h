@@ -446,10 +446,13 @@ spt_status spt_shard_rows(const spt_render_params* params, uint32_t* rows);
  * next samples of that plan in sample order, so increments summing to spp (first_sample 0) give the bits of one spt_render.
  * The film covers the samples [first_sample, first_sample + done).  Plans with SPT_RENDER_ASYNC / PROFILE / COUNT_VISITS or a
  * non-packed out_strip_stride are refused by spt_film_render (SPT_ERR_INVALID_ARG); a box filter that reaches neighbouring
- * pixels (ceil(radius - 0.5) >= 1) by spt_film_create (SPT_ERR_UNSUPPORTED).  Film calls take the scene's lock and never
+ * pixels (ceil(radius - 0.5) >= 1) by spt_film_create (SPT_ERR_UNSUPPORTED) unless the film keeps its samples
+ * (SPT_FILM_KEEP_SAMPLES).  Film calls take the scene's lock and never
  * touch the buffers of spt_render (an asynchronous copy-out may be reading them); a film is destroyed before its scene. */
 typedef struct spt_film spt_film;
-enum { SPT_FILM_MOMENTS = 1u };   /* also keep the per-channel sum of squared sample radiance (SUM_SQ, VAR_OF_MEAN) */
+enum { SPT_FILM_MOMENTS = 1u, SPT_FILM_KEEP_SAMPLES = 2u };   /* MOMENTS: also keep the per-channel sum of squared sample radiance
+                                                                 (SUM_SQ, VAR_OF_MEAN); KEEP_SAMPLES: see "films that keep
+                                                                 their samples" below */
 enum {
     SPT_FILM_MEAN = 0,            /* what spt_render returns for the covered samples: S * (1 / done), or S * (1 / wsum) for a box
                                      radius other than 0.5 (wsum = covered samples whose offset lies in the box); done > 0 */
@@ -467,6 +470,34 @@ spt_status spt_film_samples(const spt_film* film, uint32_t* done);
 /* One of SPT_FILM_*: the shard's rows packed, rows * width * 3 f32 (spt_shard_rows of the plan). */
 spt_status spt_film_read(spt_film* film, uint32_t what, float* out);
 void spt_film_destroy(spt_film* film);   /* before spt_scene_destroy of its scene */
+
+/* ---- films that keep their samples (additive to ABI v14: detect it by the flag) ----------------------------------------------------
+ * SPT_FILM_KEEP_SAMPLES is a bit of spt_film_create's film_flags; a library without it refuses the bit as an unknown film flag
+ * (SPT_ERR_INVALID_ARG).  Such a film keeps no running sums.  It keeps the radiance of every covered sample s in [first_sample,
+ * first_sample + done) for every STORED row: the shard's own rows plus R = ceil(radius - 0.5) halo rows above and below every run of
+ * consecutive own rows, clipped to the image.  Halo rows are traced again by this film, as spt_render does; a sample is a pure function
+ * of (seed, pixel, plan index), so every copy of a row has the same bits and no shard needs another.  The store costs
+ * stored rows * width * done * 12 bytes on the device and grows with every spt_film_render.
+ * With the bit, spt_film_create takes every radius spt_render takes.  spt_film_read(SPT_FILM_MEAN) is Film::filter_pixel over the
+ * covered samples, one rounded f32 operation at a time:
+ *     color = 0; weight_sum = 0
+ *     for dj = -R .. R, for di = -R .. R (pixels outside the image skipped), for the pixel's samples in increasing plan index:
+ *         color += x (unweighted);  weight_sum += box_weight (1.0f if the sample's offset lies within the radius of the
+ *                                                             reading pixel, else 0.0f)
+ *     mean = color * (1.0f / weight_sum)
+ * and SPT_FILM_SUM is `color`.  When the film covers the plan's [0, spp) the mean has the bits of spt_render with the same params, at
+ * any radius and however the samples were cut into increments; for R < 0 both loops are empty and the mean is 0 * (1 / 0).  The
+ * weights are 0.0f or 1.0f, so in f32 weight_sum equals min(count, 2^24) whatever the order of the additions: the library counts
+ * in integers and clamps.  spt_film_read_rgb8(SPT_READ_MEAN) returns the bytes of that float read-out.
+ * spt_film_read_samples returns the kept radiance itself: [count][rows][width][3] f32, the OWN rows packed like spt_film_read, plane k
+ * the sample with plan index first + k.  A black sample, a pixel outside the screen bound and a plan with max_depth 0 give 0.
+ * count == 0 or a film without rows: SPT_OK, nothing written.
+ * Refusals leave the film as it was.  SPT_ERR_INVALID_ARG: KEEP_SAMPLES together with SPT_FILM_MOMENTS; spt_film_read_samples on a
+ * null film or out, on a film without the flag, or with a range outside [first_sample, first_sample + done); spt_film_buckets on a
+ * sample-keeping film.  spt_film_adapt, spt_film_denoise* and SUM_SQ / VAR_OF_MEAN are refused as for every film without moments,
+ * spt_film_read_robust as for every film without buckets.  SPT_ERR_UNSUPPORTED: more than 2^31 - 1 stored pixels.
+ * SPT_ERR_OUT_OF_MEMORY: an increment whose store cannot be allocated; done does not advance. */
+spt_status spt_film_read_samples(spt_film* film, uint32_t first, uint32_t count, float* out);
 
 /* ---- adaptive sampling of a film (additive to ABI v14: detect it by symbol) -------------------------------------------------
  * spt_film_adapt, called between increments, RETIRES every still-active pixel whose error estimate meets the tolerance; a
@@ -666,7 +697,9 @@ spt_status spt_debug_bxdf(const spt_scene* scene, int32_t device, const spt_mate
 
 /* Test seam (additive to ABI v14): how the scene's renders were scheduled since it was created.
  *   what 0  passes whose resolve was queued on the film stream (the overlapped schedule of an SPT_RENDER_ASYNC spt_render)
- *   what 1  passes that took the single-stream path (every other render, spt_film_render, SPT_NO_FILM_STREAM=1) */
+ *   what 1  passes that took the single-stream path (every other render, spt_film_render, SPT_NO_FILM_STREAM=1)
+ *   what 2  nanoseconds the read-out kernels of the last spt_film_read / spt_film_read_rgb8 of a sample-keeping film
+ *           (SPT_FILM_KEEP_SAMPLES) of the scene took on the device (0: none yet) */
 spt_status spt_debug_render_info(const spt_scene* scene, uint32_t what, uint64_t* out);
 
 const char* spt_last_error(void);

@@ -186,6 +186,7 @@ RENDER_AOV_ALBEDO = 32     # a path's colour is the albedo of the first surface 
 DENOISE_DEMODULATE, DENOISE_OUT_RGB8 = 1, 2   # spt_denoise_job.flags
 READ_SOURCES = {"mean": 0, "mon": 1, "gmon": 2, "denoised": 3}   # SPT_READ_* of spt_film_read_rgb8
 FILM_MOMENTS = 1          # spt_film_create: also keep the per-channel sum of squared sample radiance (ABI v14)
+FILM_KEEP_SAMPLES = 2     # spt_film_create: keep every sample's radiance (any box radius; spt_film_read_samples)
 FILM_MEAN, FILM_SUM, FILM_SUM_SQ, FILM_VAR_OF_MEAN = 0, 1, 2, 3   # spt_film_read
 ROBUST_MON, ROBUST_GMON = 0, 1   # spt_film_read_robust: median of the bucket means, Gini-adaptive trimmed mean of them
 N_KERNELS = 7
@@ -348,6 +349,8 @@ def hip_lib() -> C.CDLL:
         if hasattr(lib, "spt_film_read_rgb8"):   # (the same)
             lib.spt_film_read_rgb8.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p]
             lib.spt_debug_pack_rgb8.argtypes = [C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]
+        if hasattr(lib, "spt_film_read_samples"):   # (the same)
+            lib.spt_film_read_samples.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         if hasattr(lib, "spt_denoise_image"):   # (the same)
             lib.spt_denoise_image.argtypes = [C.c_void_p, C.POINTER(ImageDenoiseJob), C.c_void_p]
         lib.spt_debug_detmath.argtypes = [C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -483,7 +486,8 @@ class DeviceScene:
         return occ
 
     def render_info(self, what: int) -> int:
-        """Test seam (spt_debug_render_info): 0 passes resolved on the film stream, 1 passes on the single-stream path."""
+        """Test seam (spt_debug_render_info): 0 passes resolved on the film stream, 1 passes on the single-stream path;
+        2 the ns the kernels of the last read-out of a sample-keeping film of the scene took on the device."""
         v = C.c_uint64(0)
         _check_hip(hip_lib().spt_debug_render_info(self._h, what, C.byref(v)))
         return int(v.value)
@@ -601,14 +605,16 @@ class PathTracer:
 
     def progressive(self, scene: Scene, config: OutputConfig, device: int = 0, first_sample: int = 0, moments: bool = False,
                     shard_index: int = 0, shard_count: int = 1, strip_rows: int = 16, samples_per_pass: int = 0,
-                    flags: int = 0, buckets: int = 0) -> "ProgressiveFilm":
+                    flags: int = 0, keep_samples: bool = False, buckets: int = 0) -> "ProgressiveFilm":
         """A film that takes this renderer's samples in increments (spt_film_*): `spp` is the plan's total, each
         ProgressiveFilm.render(n) adds the next n samples, and after increments summing to spp (first_sample 0) mean() has the
         bits of render_shard with the same arguments.  moments=True also keeps the sums of squares (sum_sq, variance_of_mean).
         `flags` are extra SPT_RENDER_* bits of the plan.  buckets=K (odd, 3 .. 15) also keeps K bucket sums per pixel (sample s of
-        the plan goes to bucket s % K) for bucket_sums() and robust_mean()."""
+        the plan goes to bucket s % K) for bucket_sums() and robust_mean().  keep_samples=True keeps every sample's radiance
+        instead of running sums (FILM_KEEP_SAMPLES): the film then takes a box radius that reaches neighbouring pixels, kept()
+        returns the samples, and moments, buckets, adapt and denoise are refused."""
         return ProgressiveFilm(self, scene, config, device, first_sample, moments, shard_index, shard_count, strip_rows,
-                               samples_per_pass, flags, buckets)
+                               samples_per_pass, flags, keep_samples=keep_samples, buckets=buckets)
 
     def guide_film(self, scene: Scene, config: OutputConfig, device: int = 0) -> "ProgressiveFilm":
         """The guide of ProgressiveFilm.denoise: a film of the same plan with debug_normal (its mean is the first-hit normal
@@ -639,7 +645,7 @@ class ProgressiveFilm:
 
     def __init__(self, renderer: PathTracer, scene: Scene, config: OutputConfig, device: int = 0, first_sample: int = 0,
                  moments: bool = False, shard_index: int = 0, shard_count: int = 1, strip_rows: int = 16,
-                 samples_per_pass: int = 0, flags: int = 0, buckets: int = 0):
+                 samples_per_pass: int = 0, flags: int = 0, keep_samples: bool = False, buckets: int = 0):
         self._h = C.c_void_p()
         self._ds = scene.device_scene(device)
         self.scene = scene
@@ -651,7 +657,7 @@ class ProgressiveFilm:
         _check_hip(hip_lib().spt_shard_rows(C.byref(self._params), C.byref(rows)))
         self.rows = rows.value
         _check_hip(hip_lib().spt_film_create(self._ds._h, C.byref(self._cam), C.byref(self._params), first_sample,
-                                             FILM_MOMENTS if moments else 0, C.byref(self._h)))
+                                             (FILM_MOMENTS if moments else 0) | (FILM_KEEP_SAMPLES if keep_samples else 0), C.byref(self._h)))
         self._ds._films.add(self)
         self.n_buckets = 0
         if buckets:
@@ -699,6 +705,18 @@ class ProgressiveFilm:
         out = np.zeros((self.rows, self.width, 3), dtype=np.uint8)
         _check_hip(hip_lib().spt_film_read_rgb8(self._handle(), READ_SOURCES[source], guide._handle() if guide is not None else None,
                                                 params, out.ctypes.data))
+        return out
+
+    def kept(self, first: Optional[int] = None, count: Optional[int] = None) -> np.ndarray:
+        """spt_film_read_samples of a keep_samples=True film: (count, rows, width, 3) f32, the radiance of the samples with plan
+        index first .. first + count - 1 on the own rows; by default everything the film covers."""
+        if first is None:
+            first = self.first_sample
+        if count is None:
+            count = self.first_sample + self.samples - first
+        out = np.zeros((max(count, 0), self.rows, self.width, 3), dtype=np.float32)
+        spare = np.zeros(1, dtype=np.float32)   # (an empty result: the call still wants a pointer, and checks its range)
+        _check_hip(hip_lib().spt_film_read_samples(self._handle(), first, count, out.ctypes.data if out.size else spare.ctypes.data))
         return out
 
     def render(self, n: int) -> "ProgressiveFilm":
@@ -881,7 +899,8 @@ class MultiFilm:
     single-device film of the same plan."""
 
     def __init__(self, multi: "MultiDevice", renderer: "PathTracer", config: OutputConfig, strip_rows: int = 0, first_sample: int = 0,
-                 moments: bool = False, flags: int = 0, buckets: int = 0, film_api: Optional[DeviceFilmApi] = None):
+                 moments: bool = False, flags: int = 0, buckets: int = 0, film_api: Optional[DeviceFilmApi] = None,
+                 keep_samples: bool = False):
         self._h = C.c_void_p()
         self.multi = multi
         self.first_sample = first_sample
@@ -891,7 +910,8 @@ class MultiFilm:
         cam = multi.scene.get_camera(config.used_camera_name)
         p = renderer.params(config.width, config.height, 0, 1, 16, 0, flags)
         _check_host(host_lib().spt_host_multi_film_create(multi._h, C.byref(self._api), C.byref(cam), C.byref(p), strip_rows, first_sample,
-                                                          FILM_MOMENTS if moments else 0, buckets, C.byref(self._h)))
+                                                          (FILM_MOMENTS if moments else 0) | (FILM_KEEP_SAMPLES if keep_samples else 0), buckets,
+                                                          C.byref(self._h)))
         multi._films.add(self)
 
     def _handle(self):
@@ -1025,12 +1045,13 @@ class MultiDevice:
         return film
 
     def progressive(self, renderer: "PathTracer", config: OutputConfig, strip_rows: int = 0, first_sample: int = 0, moments: bool = False,
-                    flags: int = 0, buckets: int = 0, film_api: Optional[DeviceFilmApi] = None) -> MultiFilm:
+                    flags: int = 0, buckets: int = 0, film_api: Optional[DeviceFilmApi] = None, keep_samples: bool = False) -> MultiFilm:
         """PathTracer.progressive over all devices: a MultiFilm, one shard film per replica (shard k of n, strips of `strip_rows`
         rows, 0 = render()'s default).  `flags` are extra SPT_RENDER_* bits of the plan: RENDER_DEBUG_NORMAL / RENDER_AOV_ALBEDO
         with moments=True make the guide / albedo multi film of MultiFilm.denoise_job.  `film_api` defaults to libspt_hip.so's
-        functions; tests pass stand-ins."""
-        return MultiFilm(self, renderer, config, strip_rows, first_sample, moments, flags, buckets, film_api)
+        functions; tests pass stand-ins.  keep_samples=True: shard films that keep their samples (PathTracer.progressive), each
+        tracing its own halo rows, so a box radius that reaches neighbouring pixels works over several devices too."""
+        return MultiFilm(self, renderer, config, strip_rows, first_sample, moments, flags, buckets, film_api, keep_samples)
 
     def close(self) -> None:
         for film in list(getattr(self, "_films", ())):

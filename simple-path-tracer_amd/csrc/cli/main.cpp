@@ -18,8 +18,11 @@
 // 8-bit image the reference saves (spt_film_read_rgb8: a quarter of the float film's bytes); the EXR outputs stay float.
 // --film-devices d0,d1,.. (an index may repeat) runs the same progressive loop over a multi film on those devices (one shard film per
 // device, spt_host_multi_film_*; the denoiser runs once on the gathered image, spt_denoise_image) and writes the same bytes.
+// A renderer whose box filter reaches neighbouring pixels (ceil(radius - 0.5) >= 1) gets a film that keeps its samples
+// (SPT_FILM_KEEP_SAMPLES): --preview-every, --time-limit and --film-devices work with it, the options that need moments or buckets exit with code 2.
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -70,6 +73,7 @@ struct ProgressiveJob {
     bool robust;
     uint32_t robust_k, estimator;
     std::string out_path, noisy_out, albedo_out, mean_out, variance_out, samples_out;
+    uint32_t keep_flag;   // SPT_FILM_KEEP_SAMPLES for a box filter that reaches neighbouring pixels, else 0
 };
 
 // The progressive loop of main() over a multi film (--film-devices): the same increments, the same decisions and the same
@@ -111,7 +115,7 @@ static int progressive_on_devices(const ProgressiveJob& o) {
     std::fprintf(stderr, "Scene JSON is loaded successfully. Rendering a film on %zu device(s)...\n", o.devices.size());
     const auto t0 = std::chrono::steady_clock::now();
     const bool moments = !o.variance_out.empty() || o.adaptive_on || o.denoise;
-    if (spt_host_multi_film_create(multi, &fapi, &o.cam, &params, o.strip_rows, 0, moments ? (uint32_t)SPT_FILM_MOMENTS : 0u, o.robust ? o.robust_k : 0u, &pf) != SPT_OK)
+    if (spt_host_multi_film_create(multi, &fapi, &o.cam, &params, o.strip_rows, 0, (moments ? (uint32_t)SPT_FILM_MOMENTS : 0u) | o.keep_flag, o.robust ? o.robust_k : 0u, &pf) != SPT_OK)
         return fail();
     const spt_denoise_params dn = {(uint32_t)sizeof(spt_denoise_params), o.denoise_iterations, 2.0f, 1.0f, 1e-8f, 1e-2f};
     const uint32_t n_guide = std::max(2u, std::min(params.spp, o.guide_samples));
@@ -344,6 +348,17 @@ int main(int argc, char** argv) {
         return 1;
     }
     if (spp_override && params.sampler != SPT_SAMPLER_JITTERED) params.spp = spp_override;
+    // A box filter that reaches neighbouring pixels (ceil(radius - 0.5) >= 1): its film keeps the samples (SPT_FILM_KEEP_SAMPLES),
+    // which previews, time limits and several devices can use.  What needs moments or buckets cannot: the library would refuse
+    // (spt_film_create with SPT_FILM_MOMENTS, spt_film_buckets), so the run ends here, before any sample is traced
+    const bool wide_box = progressive && (params.flags & SPT_RENDER_BOX_RADIUS) && std::ceil(params.filter_radius - 0.5f) >= 1.0f;
+    if (wide_box && (!variance_out.empty() || adaptive_on || !samples_out.empty() || denoise || robust)) {
+        std::fprintf(stderr, "Error: --variance-out, --adaptive, --samples-out, --denoise and --robust need a box filter within one pixel; the renderer's radius %g "
+                             "reaches neighbouring pixels (--preview-every, --time-limit and --film-devices work with it)\n", (double)params.filter_radius);
+        spt_host_scene_free(hs);
+        return 2;
+    }
+    const uint32_t keep_flag = wide_box ? (uint32_t)SPT_FILM_KEEP_SAMPLES : 0u;
     spt_camera cam;
     if (spt_host_scene_camera(hs, camera.empty() ? nullptr : camera.c_str(), &cam) != SPT_OK) {
         std::fprintf(stderr, "Error: %s\n", spt_host_last_error());
@@ -366,6 +381,7 @@ int main(int argc, char** argv) {
         o.robust = robust; o.robust_k = (uint32_t)robust_k; o.estimator = estimator;
         o.out_path = out_path; o.noisy_out = noisy_out; o.albedo_out = albedo_out; o.mean_out = mean_out;
         o.variance_out = variance_out; o.samples_out = samples_out;
+        o.keep_flag = keep_flag;
         return progressive_on_devices(o);
     }
     std::vector<float> film((size_t)width * height * 3);
@@ -440,7 +456,7 @@ int main(int argc, char** argv) {
             return 1;
         };
         const bool moments = !variance_out.empty() || adaptive_on || denoise;
-        if (spt_film_create(ds, &cam, &params, 0, moments ? (uint32_t)SPT_FILM_MOMENTS : 0u, &pf) != SPT_OK) return film_fail();
+        if (spt_film_create(ds, &cam, &params, 0, (moments ? (uint32_t)SPT_FILM_MOMENTS : 0u) | keep_flag, &pf) != SPT_OK) return film_fail();
         if (robust && spt_film_buckets(pf, (uint32_t)robust_k) != SPT_OK) return film_fail();
         const spt_denoise_params dn = {(uint32_t)sizeof(spt_denoise_params), denoise_iterations, 2.0f, 1.0f, 1e-8f, 1e-2f};
         if (denoise && guide_normal) {   // the guide's samples come first: every preview is filtered with the whole guide

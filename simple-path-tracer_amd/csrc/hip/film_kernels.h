@@ -703,6 +703,102 @@ __global__ void __launch_bounds__(256) k_filter_box(RenderCtx rc, BoxJob job) {
     job.out[3 * (size_t)idx] = c.x; job.out[3 * (size_t)idx + 1] = c.y; job.out[3 * (size_t)idx + 2] = c.z;
 }
 
+// ---------------------------------------------------------------------------- sample-keeping films (SPT_FILM_KEEP_SAMPLES)
+// A film that keeps its samples owns, per run of consecutive own rows, the radiance of every covered sample of the run's stored
+// rows (the own rows and R halo rows each way): one chunk per wavefront pass, three planes [c][sample in pass][stored pixel] as the
+// pass wrote them.  The chunks of a run cover the film's samples in increasing plan index without gaps.
+struct KeptChunk {
+    const float* rad;   // 3 planes of `count` samples, count * stored pixels floats apart
+    uint32_t first;     // plan index of the chunk's first sample
+    uint32_t count;     // its samples
+};
+
+struct KeptJob {
+    const KeptChunk* chunks;        // the run's chunk table, on the device
+    uint32_t n_chunks;
+    uint32_t band_base, band_rows;  // image rows the chunks hold
+    uint32_t out_j0, out_rows;      // image rows to filter
+    float* out;                     // first pixel of row out_j0 in the packed output of the shard
+    int32_t R;
+    float radius;
+    uint32_t mean;                  // 1: colour * (1 / weight_sum) (SPT_FILM_MEAN); 0: the colour (SPT_FILM_SUM)
+};
+
+// The read-out of a sample-keeping film: Film::filter_pixel (film.rs:71-92) over the kept samples, the loops of k_filter_box with
+// the samples of a pixel walked chunk by chunk (increasing plan index).  One lane per output pixel; consecutive lanes read
+// consecutive floats of every plane.  The colour chain is sequential by specification, the loads are not: kBatch samples (3 kBatch
+// loads) are requested together before the first is added, as in k_resolve; the host picks kBatch by R.
+// weight_sum adds 0.0f or 1.0f per sample, which in f32 is min(count, 2^24) whatever the order: the kernel counts in integers.
+// Every sample's offset is derived again per neighbour that reads it, as k_filter_box does.  (The measurements behind kBatch, and
+// the count table that was tried instead of the RNG: DESIGN.md, "Films that keep their samples".)
+template <uint32_t kBatch>
+__global__ void __launch_bounds__(256) k_film_filter_box(RenderCtx rc, KeptJob job) {
+    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= job.out_rows * rc.width) return;
+    const uint32_t row = idx / rc.width, x = idx - row * rc.width;
+    const int32_t y = (int32_t)(job.out_j0 + row);
+    const size_t n_band = (size_t)job.band_rows * rc.width;
+    f3 sum = mk3(0, 0, 0);
+    unsigned long long inside = 0ull;
+    for (int32_t dj = -job.R; dj <= job.R; ++dj) {
+        const int32_t jj = y + dj;
+        if (jj < 0 || jj >= (int32_t)rc.height) continue;
+        for (int32_t di = -job.R; di <= job.R; ++di) {
+            const int32_t ii = (int32_t)x + di;
+            if (ii < 0 || ii >= (int32_t)rc.width) continue;
+            const uint32_t pixel = (uint32_t)jj * rc.width + (uint32_t)ii;
+            const size_t lp = (size_t)((uint32_t)jj - job.band_base) * rc.width + (uint32_t)ii;
+            for (uint32_t c = 0; c < job.n_chunks; ++c) {
+                const KeptChunk ch = job.chunks[c];
+                const size_t plane = (size_t)ch.count * n_band;
+                const float* rp = ch.rad + lp;
+                uint32_t s = 0;
+                for (; s + kBatch <= ch.count; s += kBatch) {
+                    float r[kBatch], g[kBatch], b[kBatch];
+#pragma unroll
+                    for (uint32_t k = 0; k < kBatch; ++k) {
+                        const size_t ri = (size_t)(s + k) * n_band;
+                        r[k] = rp[ri]; g[k] = rp[plane + ri]; b[k] = rp[2 * plane + ri];
+                    }
+#pragma unroll
+                    for (uint32_t k = 0; k < kBatch; ++k) {
+                        sum = sum + mk3(r[k], g[k], b[k]);
+                        if (box_weight(rc, pixel, ch.first + s + k, di, dj, job.radius) != 0.0f) ++inside;
+                    }
+                }
+                for (; s < ch.count; ++s) {
+                    const size_t ri = (size_t)s * n_band;
+                    sum = sum + mk3(rp[ri], rp[plane + ri], rp[2 * plane + ri]);
+                    if (box_weight(rc, pixel, ch.first + s, di, dj, job.radius) != 0.0f) ++inside;
+                }
+            }
+        }
+    }
+    f3 c = sum;
+    if (job.mean) {
+        const float wsum = (float)(inside < (1ull << 24) ? inside : (1ull << 24));
+        c = sum * (1.0f / wsum);
+    }
+    job.out[3 * (size_t)idx] = c.x; job.out[3 * (size_t)idx + 1] = c.y; job.out[3 * (size_t)idx + 2] = c.z;
+}
+
+// spt_film_read_samples: the own rows of `count` kept samples from plan index `first`, [k][own row][x][3].  One lane per float of
+// one sample plane; blockIdx.y walks the samples.  The chunk holding sample first + k is found by a walk over the (short) table.
+__global__ void __launch_bounds__(256) k_film_read_kept(KeptJob job, uint32_t width, uint32_t first, size_t out_plane) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)job.out_rows * width * 3u) return;
+    const uint32_t s = first + blockIdx.y;
+    const size_t px = i / 3u, c = i - 3u * px;
+    const size_t n_band = (size_t)job.band_rows * width;
+    const size_t lp = (size_t)(job.out_j0 - job.band_base) * width + px;
+    float v = 0.0f;
+    for (uint32_t k = 0; k < job.n_chunks; ++k) {
+        const KeptChunk ch = job.chunks[k];
+        if (s >= ch.first && s - ch.first < ch.count) { v = ch.rad[(size_t)c * ch.count * n_band + (size_t)(s - ch.first) * n_band + lp]; break; }
+    }
+    job.out[(size_t)blockIdx.y * out_plane + i] = v;
+}
+
 // ---------------------------------------------------------------------------- RGB8 output
 // color_to_rgb (film.rs:94-99) of one channel, the arithmetic of spt_host_film_to_rgb8, one rounded operation at a time: Rust's
 // clamp keeps a NaN and `NaN as u8` is 0; +inf gives 255, -inf and -0 give 0; the conversion truncates.

@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <functional>
 #include <limits>
 #include <memory>
@@ -540,6 +541,7 @@ struct BezierLib {
     decltype(&spt_film_read_buckets) film_read_buckets = nullptr;
     decltype(&spt_film_read_robust) film_read_robust = nullptr;
     decltype(&spt_film_read_rgb8) film_read_rgb8 = nullptr;
+    decltype(&spt_film_read_samples) film_read_samples = nullptr;
     decltype(&spt_denoise_image) denoise_image = nullptr;
     decltype(&spt_trace_closest) trace_closest = nullptr;
     decltype(&spt_trace_any) trace_any = nullptr;
@@ -570,6 +572,10 @@ struct spt_scene {
     bool film_pending = false;                // the main stream is not yet behind the film-stream kernels of an overlapped render (film_join)
     bool film_inflight = false;               // ... and the host has not waited for them since (grow)
     uint64_t passes_film = 0, passes_single = 0;   // spt_debug_render_info: passes resolved on the film stream / on the main stream
+    // ... and what the kernels of a sample-keeping film's last read-out (k_film_filter_box) took on the device, in ns, between the
+    // two events below (made by the first such film)
+    uint64_t keep_read_ns = 0;
+    hipEvent_t ev_keep[2] = {nullptr, nullptr};
     bool bez_newton = false;                  // some patch asks for Newton's iteration (the pair kernel only clips)
     // what the last pass with a counter readback saw at bounce 1 (path vertices in all shards); ~0: never seen.  A hint
     // only: it picks between two kernels that compute the same film (k_shade's kLoop)
@@ -629,7 +635,7 @@ struct spt_scene {
         if (ev_join) (void)hipEventDestroy(ev_join);
         if (ev_out_ready) (void)hipEventDestroy(ev_out_ready);
         if (ev_copy_done) (void)hipEventDestroy(ev_copy_done);
-        for (auto e : {ev_main[0], ev_main[1], ev_film[0], ev_film[1], ev_film_idle})
+        for (auto e : {ev_main[0], ev_main[1], ev_film[0], ev_film[1], ev_film_idle, ev_keep[0], ev_keep[1]})
             if (e) (void)hipEventDestroy(e);
         if (stream_film) (void)hipStreamDestroy(stream_film);
         if (stream2) (void)hipStreamDestroy(stream2);
@@ -668,6 +674,17 @@ struct spt_film {
     uint32_t n_buckets = 0;           // K; 0: a film without buckets
     DeviceBuffer buckets;             // B_j, j = 0 .. K - 1
     DeviceBuffer b_inv;               // (spp + 1) f32: inv[k] = 1.0f / (float)k as the host rounds it (inv[0] = 0, never read)
+    // a film that keeps its samples (SPT_FILM_KEEP_SAMPLES): no running sums; per run of consecutive own rows the radiance of every
+    // covered sample of the run's stored rows (own rows + R halo rows each way, clipped to the image), one chunk per wavefront pass
+    struct KeptRun {
+        uint32_t j0 = 0, j1 = 0;      // own image rows [j0, j1)
+        uint32_t b0 = 0, b1 = 0;      // stored image rows [b0, b1)
+        size_t out_row = 0;           // the run's first own row in the shard's packed rows
+        std::vector<std::unique_ptr<DeviceBuffer>> chunks;   // 3 planes [c][sample in pass][stored pixel] each
+        std::vector<KeptChunk> table;                        // what the kernels read of them, and its device copy
+        DeviceBuffer table_dev;
+    };
+    std::deque<KeptRun> runs;       // (a KeptRun does not move: it owns device buffers)
 };
 
 namespace {
@@ -896,7 +913,8 @@ const BezierLib* bezier_lib() {
                          sym(lib.film_adapt, "spt_film_adapt") && sym(lib.film_read_counts, "spt_film_read_counts") &&
                          sym(lib.film_denoise, "spt_film_denoise") && sym(lib.film_denoise_job, "spt_film_denoise_job") && sym(lib.film_buckets, "spt_film_buckets") &&
                          sym(lib.film_read_buckets, "spt_film_read_buckets") && sym(lib.film_read_robust, "spt_film_read_robust") &&
-                         sym(lib.film_read_rgb8, "spt_film_read_rgb8") && sym(lib.denoise_image, "spt_denoise_image") &&
+                         sym(lib.film_read_rgb8, "spt_film_read_rgb8") && sym(lib.film_read_samples, "spt_film_read_samples") &&
+                         sym(lib.denoise_image, "spt_denoise_image") &&
                          sym(lib.trace_closest, "spt_trace_closest") && sym(lib.trace_any, "spt_trace_any") && sym(lib.debug_bxdf, "spt_debug_bxdf") &&
                          sym(lib.debug_render_info, "spt_debug_render_info") &&
                          sym(lib.last_error, "spt_last_error") && sym(version, "spt_abi_version");
@@ -1562,6 +1580,9 @@ struct SampleTarget {
     float* buckets = nullptr;
     uint32_t n_buckets = 0;
     size_t bucket_plane = 0;
+    // a sample-keeping film (collect): the radiance chunk of every pass of this call, sized by pass_samples_of and zeroed by the
+    // caller; the passes write there, not to the scene's sc->rad.  null: the scene's workspace
+    float* const* keep = nullptr;
 };
 
 // One call of the render loop: its plan, the kernel choices made once per call (run_setup), the profiling spans and the
@@ -1853,17 +1874,21 @@ struct PassShape {
 // Sizes the passes of the window of rc (plan_ctx) that add `n_samples` samples, grows the scene's workspace to them and binds
 // it and the window's tiles into rc.  sum: the running sums the passes add to (null: the scene's workspace film).
 // collect: every sample of the window is kept (wide box filter), else only the samples of one pass.
+// samples per pass of a window of n_pix pixels that adds n_samples: keep the queues around a few million entries
+uint32_t pass_samples_of(const spt_render_params& p, uint32_t n_pix, uint32_t n_samples) {
+    uint32_t spp_pass = p.samples_per_pass;
+    if (spp_pass == 0) {
+        const uint64_t target = 128ull << 20;
+        spp_pass = (uint32_t)std::max<uint64_t>(1, target / n_pix);
+    }
+    return std::min(spp_pass, n_samples);   // (a film's increment: what is left of it)
+}
+
 PassShape grow_workspace(spt_scene* sc, const spt_render_params& p, uint32_t n_samples, bool collect, bool fused, bool class_queues, float* sum,
-                         RenderCtx& rc) {
+                         bool own_rad, RenderCtx& rc) {
     const uint32_t n_pix = rc.n_pixels;
     PassShape ps{};
-    // samples per pass: keep the queues around a few million entries
-    ps.spp_pass = p.samples_per_pass;
-    if (ps.spp_pass == 0) {
-        const uint64_t target = 128ull << 20;
-        ps.spp_pass = (uint32_t)std::max<uint64_t>(1, target / n_pix);
-    }
-    ps.spp_pass = std::min(ps.spp_pass, n_samples);   // (a film's increment: what is left of it)
+    ps.spp_pass = pass_samples_of(p, n_pix, n_samples);
     // queue shards: shard s holds what the primary tiles mapped to it can emit, which also bounds
     // every later generation of that shard
     const uint32_t tiles_y = (rc.rows + kTile - 1) / kTile;
@@ -1896,7 +1921,7 @@ PassShape grow_workspace(spt_scene* sc, const spt_render_params& p, uint32_t n_s
     for (int k = 0; k < 3; ++k) grow(sc, sc->sh[k], cap * 16);
     ps.counts_words = (size_t)(p.max_depth + 1) * Q_KINDS * kShards * 32;
     grow(sc, sc->counts[0], ps.counts_words * sizeof(uint32_t));
-    grow(sc, sc->rad[0], (size_t)ps.rad_slots * 3 * sizeof(float));
+    if (!own_rad) grow(sc, sc->rad[0], (size_t)ps.rad_slots * 3 * sizeof(float));   // (own_rad: the passes write the caller's chunks, SampleTarget::keep)
     float* const film_sum = sum ? sum : (grow(sc, sc->film, (size_t)n_pix * 3 * sizeof(float)), sc->film.as<float>());
     grow(sc, sc->first_slot[0], (size_t)n_pix * sizeof(uint32_t));
     grow(sc, sc->slot_bits[0], (size_t)n_pix * ((ps.spp_pass + 7u) / 8u));
@@ -2234,7 +2259,7 @@ RenderCtx trace_window(RenderRun& run, uint32_t row_base, uint32_t rows, uint32_
     if ((uint64_t)rows * p.width > 0x7fffffffull) fail(SPT_ERR_UNSUPPORTED, "render: window larger than 2^31 pixels");
     RenderCtx rc = plan_ctx(p, *run.cam, row_base, rows, w_index, w_count, w_strip);
     const uint32_t n_pix = rc.n_pixels;
-    const PassShape ps = grow_workspace(sc, p, tgt.count, collect, run.fused, run.class_queues, tgt.sum, rc);
+    const PassShape ps = grow_workspace(sc, p, tgt.count, collect && tgt.keep == nullptr, run.fused, run.class_queues, tgt.sum, tgt.keep != nullptr, rc);
     screen_bound(sc, p, *run.cam, run.pixel_cull, rc);
     rc.dyn_refill_below = run.dyn_refill_below;
     rc.dyn_steps = run.dyn_steps;
@@ -2263,7 +2288,7 @@ RenderCtx trace_window(RenderRun& run, uint32_t row_base, uint32_t rows, uint32_
         HIP_CHECK(hipMemsetAsync(rc.film, 0, (size_t)n_pix * 3 * sizeof(float), st_film));
         if (tgt.sq) HIP_CHECK(hipMemsetAsync(tgt.sq, 0, (size_t)n_pix * 3 * sizeof(float), st_film));
     }
-    if (collect) HIP_CHECK(hipMemsetAsync(sc->rad[0].p, 0, (size_t)ps.rad_slots * 3 * sizeof(float), run.st));   // pixels outside the screen bound write no slots
+    if (collect && tgt.keep == nullptr) HIP_CHECK(hipMemsetAsync(sc->rad[0].p, 0, (size_t)ps.rad_slots * 3 * sizeof(float), run.st));   // pixels outside the screen bound write no slots
     bool chunked_any = false;
     // max_depth 0: `while curr_depth < self.max_depth` (pt.rs:48) never runs, every sample is black - environment included.
     // Nothing is traced: the film (and, for a wide box filter, the kept samples) stay at the zeros written above.  (The
@@ -2283,7 +2308,12 @@ RenderCtx trace_window(RenderRun& run, uint32_t row_base, uint32_t rows, uint32_
         rc.pass_samples = std::min(ps.spp_pass, s_end - s0);
         rc.rad_plane = collect ? (size_t)p.spp * n_pix : (size_t)rc.pass_samples * n_pix;
         rc.pack_first = (run.pack_first && rc.pass_samples <= 4096u) ? 1u : 0u;
-        rc.rad = sc->rad[set].as<float>() + (collect ? (size_t)(s0 - tgt.first) * n_pix : 0);
+        if (tgt.keep != nullptr) {   // a sample-keeping film: the pass's own chunk, laid out like a pass that is not kept
+            rc.rad_plane = (size_t)rc.pass_samples * n_pix;
+            rc.rad = tgt.keep[(s0 - tgt.first) / ps.spp_pass];
+        } else {
+            rc.rad = sc->rad[set].as<float>() + (collect ? (size_t)(s0 - tgt.first) * n_pix : 0);
+        }
         run.begin(SPT_K_OTHER);
         HIP_CHECK(hipMemsetAsync(rc.counts, 0, ps.counts_words * sizeof(uint32_t), run.st));
         run.end();
@@ -2332,6 +2362,93 @@ RenderCtx trace_window(RenderRun& run, uint32_t row_base, uint32_t rows, uint32_
     run.samples_traced += (uint64_t)n_pix * tgt.count;
     if (chunked_any) run.live_samples += live.live_pixels * tgt.count;
     return rc;
+}
+
+// ---- sample-keeping films (SPT_FILM_KEEP_SAMPLES) ----
+// The device time between the scene's two ev_keep events, both reached (spt_debug_render_info)
+uint64_t keep_elapsed_ns(spt_scene* sc) {
+    float ms = 0.0f;
+    HIP_CHECK(hipEventElapsedTime(&ms, sc->ev_keep[0], sc->ev_keep[1]));
+    return (uint64_t)((double)ms * 1e6);
+}
+
+// The runs of a new film: every run of consecutive own rows with max(R, 0) halo rows each way, as spt_render's band loop cuts them
+// (a run is never split: the store is what the film is for).  The scene's lock is held.
+void make_kept_runs(spt_film* f) {
+    spt_scene* const sc = f->sc;
+    const spt_render_params& p = f->plan;
+    const uint32_t shard_count = p.shard_count ? p.shard_count : 1u, strip_rows = p.strip_rows ? p.strip_rows : 1u;
+    const uint32_t halo = (uint32_t)std::max(f->R, 0);
+    std::vector<uint32_t> own;
+    for (uint32_t j = 0; j < p.height; ++j)
+        if ((j / strip_rows) % shard_count == p.shard_index) own.push_back(j);
+    uint64_t stored = 0;
+    for (size_t k = 0; k < own.size();) {
+        size_t e = k + 1;
+        while (e < own.size() && own[e] == own[e - 1] + 1u) ++e;
+        spt_film::KeptRun& r = f->runs.emplace_back();
+        r.j0 = own[k]; r.j1 = own[e - 1] + 1u;
+        r.b0 = r.j0 >= halo ? r.j0 - halo : 0u;
+        r.b1 = (uint32_t)std::min<uint64_t>(p.height, (uint64_t)r.j1 + halo);
+        r.out_row = k;
+        stored += (uint64_t)(r.b1 - r.b0) * p.width;
+        k = e;
+    }
+    if (stored > 0x7fffffffull) fail(SPT_ERR_UNSUPPORTED, "film_create: a sample-keeping film of more than 2^31 - 1 stored pixels (own rows and halo rows)");
+    for (hipEvent_t& e : sc->ev_keep)
+        if (!e) HIP_CHECK(hipEventCreate(&e));
+}
+
+// One increment of a sample-keeping film: per run, the chunks of its passes are allocated and zeroed (collect mode writes no slot
+// for a black sample or a pixel outside the screen bound), one trace_window in collect mode fills them.  The film changes only after
+// every run has worked: an increment that fails (no memory for a chunk) leaves it as it was.
+void kept_render(spt_film* f, RenderRun& run, uint32_t n_samples) {
+    const spt_render_params& p = f->plan;
+    const uint32_t s_first = f->first + f->done;
+    struct NewChunks {
+        std::vector<std::unique_ptr<DeviceBuffer>> bufs;
+        std::vector<KeptChunk> table;
+        DeviceBuffer table_dev;
+    };
+    std::vector<NewChunks> fresh(f->runs.size());
+    for (size_t k = 0; k < f->runs.size(); ++k) {
+        spt_film::KeptRun& r = f->runs[k];
+        NewChunks& nc = fresh[k];
+        const uint32_t n_band = (r.b1 - r.b0) * p.width;
+        const uint32_t spp_pass = pass_samples_of(p, n_band, n_samples);
+        std::vector<float*> ptrs;
+        for (uint32_t s0 = 0; s0 < n_samples; s0 += spp_pass) {
+            const uint32_t n = std::min(spp_pass, n_samples - s0);
+            auto buf = std::make_unique<DeviceBuffer>();
+            buf->alloc((size_t)n * n_band * 3 * sizeof(float));
+            HIP_CHECK(hipMemsetAsync(buf->p, 0, buf->bytes, run.st));
+            ptrs.push_back(buf->as<float>());
+            nc.table.push_back(KeptChunk{buf->as<float>(), s_first + s0, n});
+            nc.bufs.push_back(std::move(buf));
+        }
+        SampleTarget inc{s_first, n_samples, nullptr, nullptr, false};
+        inc.keep = ptrs.data();
+        (void)trace_window(run, r.b0, r.b1 - r.b0, 0u, 1u, 1u, true, inc);
+        HIP_CHECK(hipGetLastError());
+        // the chunk table the read-outs will take: the old entries and the new ones
+        std::vector<KeptChunk> table = r.table;
+        table.insert(table.end(), nc.table.begin(), nc.table.end());
+        nc.table.swap(table);
+        nc.table_dev.alloc(nc.table.size() * sizeof(KeptChunk));
+        HIP_CHECK(hipMemcpyAsync(nc.table_dev.p, nc.table.data(), nc.table.size() * sizeof(KeptChunk), hipMemcpyHostToDevice, run.st));
+    }
+    HIP_CHECK(hipStreamSynchronize(run.st));   // (the tables are pageable; every trace has worked)
+    for (size_t k = 0; k < f->runs.size(); ++k) {
+        spt_film::KeptRun& r = f->runs[k];
+        for (auto& b : fresh[k].bufs) r.chunks.push_back(std::move(b));
+        r.table.swap(fresh[k].table);
+        r.table_dev.swap(fresh[k].table_dev);
+    }
+}
+
+// What the kernels of a sample-keeping film read of one of its runs; `out`: the run's first own row in a packed buffer
+KeptJob kept_job(const spt_film* f, const spt_film::KeptRun& r, float* out, bool mean) {
+    return KeptJob{r.table_dev.as<KeptChunk>(), (uint32_t)r.table.size(), r.b0, r.b1 - r.b0, r.j0, r.j1 - r.j0, out, f->R, f->radius, mean ? 1u : 0u};
 }
 
 }  // namespace
@@ -2525,13 +2642,17 @@ spt_status spt_film_create(const spt_scene* scene_c, const spt_camera* cam, cons
     return guarded("film_create", [&] {
         const spt_render_params& p = *params;
         check_plan(p, "film_create");
-        if (film_flags & ~(uint32_t)SPT_FILM_MOMENTS) fail(SPT_ERR_INVALID_ARG, "film_create: unknown film flags");
+        if (film_flags & ~(uint32_t)(SPT_FILM_MOMENTS | SPT_FILM_KEEP_SAMPLES)) fail(SPT_ERR_INVALID_ARG, "film_create: unknown film flags");
+        const bool keep = (film_flags & SPT_FILM_KEEP_SAMPLES) != 0;
+        if (keep && (film_flags & SPT_FILM_MOMENTS))
+            fail(SPT_ERR_INVALID_ARG, "film_create: SPT_FILM_KEEP_SAMPLES and SPT_FILM_MOMENTS exclude each other (the moments assume every sample of a pixel weighs 1)");
         if (first_sample > p.spp) fail(SPT_ERR_INVALID_ARG, "film_create: first_sample past the plan's spp");
         const float radius = plan_radius(p, "film_create");
         const int32_t R = (int32_t)std::ceil(radius - 0.5f);
         // Film::filter_pixel of a wider box adds the samples of the neighbouring pixels into ONE running sum, pixel after pixel:
-        // the sum after n samples is not a prefix of the sum after n + k, so it cannot be extended bit-exactly
-        if (R >= 1) fail(SPT_ERR_UNSUPPORTED, "film_create: a box filter reaching neighbouring pixels (ceil(radius - 0.5) >= 1) cannot be rendered in increments");
+        // the sum after n samples is not a prefix of the sum after n + k, so it cannot be extended bit-exactly.  (A film that keeps
+        // its samples can: SPT_FILM_KEEP_SAMPLES)
+        if (R >= 1 && !keep) fail(SPT_ERR_UNSUPPORTED, "film_create: a box filter reaching neighbouring pixels (ceil(radius - 0.5) >= 1) cannot be rendered in increments");
         const uint64_t own_pix64 = (uint64_t)shard_row_count(p) * p.width;
         if (own_pix64 > 0x7fffffffull) fail(SPT_ERR_UNSUPPORTED, "film_create: shard larger than 2^31 pixels");
         HIP_CHECK(hipSetDevice(sc->device));
@@ -2544,6 +2665,11 @@ spt_status spt_film_create(const spt_scene* scene_c, const spt_camera* cam, cons
         f->rows = shard_row_count(p);
         f->radius = radius;
         f->R = R;
+        if (keep) {
+            make_kept_runs(f.get());
+            *out = f.release();
+            return SPT_OK;
+        }
         const size_t bytes = (size_t)own_pix64 * 3 * sizeof(float);
         f->sum.alloc(bytes);
         HIP_CHECK(hipMemsetAsync(f->sum.p, 0, f->sum.bytes, sc->stream));
@@ -2584,6 +2710,11 @@ spt_status spt_film_render(spt_film* f, uint32_t n_samples) {
             run.params = &p;
             run_setup(run);
             run_spans(run);
+            if (f->flags & SPT_FILM_KEEP_SAMPLES) {
+                kept_render(f, run, n_samples);
+                f->done += n_samples;
+                return SPT_OK;
+            }
             SampleTarget inc{f->first + f->done, n_samples, f->sum.as<float>(), (f->flags & SPT_FILM_MOMENTS) ? f->sq.as<float>() : nullptr, false};
             if (f->adaptive) {
                 inc.mask = FilmMask{f->mask.as<uint8_t>(), f->tile_active.as<uint32_t>()};
@@ -2649,6 +2780,23 @@ static spt_status film_read_locked(spt_film* f, uint32_t what, const FilmReadOut
     HIP_CHECK(hipSetDevice(sc->device));
     film_join(sc);
     const hipStream_t st = sc->stream;
+    if (f->flags & SPT_FILM_KEEP_SAMPLES) {   // (SUM_SQ / VAR_OF_MEAN were refused above: such a film has no moments)
+        // Film::filter_pixel over the kept samples, run by run: SUM is the colour, MEAN the colour * (1 / weight_sum)
+        f->out.ensure(bytes);
+        HIP_CHECK(hipEventRecord(sc->ev_keep[0], st));
+        for (const auto& r : f->runs) {
+            const RenderCtx rc = plan_ctx(p, f->cam, r.b0, r.b1 - r.b0, 0u, 1u, 1u);
+            const KeptJob job = kept_job(f, r, f->out.as<float>() + r.out_row * (size_t)p.width * 3, what == SPT_FILM_MEAN);
+            const dim3 grid(((r.j1 - r.j0) * p.width + kBlock - 1) / kBlock);
+            // samples requested together per lane: 8 up to R = 1, 1 from R = 2 on (measured, see k_film_filter_box)
+            hipLaunchKernelGGL(f->R >= 2 ? k_film_filter_box<1u> : k_film_filter_box<8u>, grid, dim3(kBlock), 0, st, rc, job);
+        }
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipEventRecord(sc->ev_keep[1], st));
+        film_deliver(f, f->out.p, (size_t)n_pix * 3, to, st);
+        sc->keep_read_ns = keep_elapsed_ns(sc);
+        return SPT_OK;
+    }
     const void* src = f->sum.p;
     if (what == SPT_FILM_SUM_SQ) src = f->sq.p;
     if (what == SPT_FILM_MEAN || what == SPT_FILM_VAR_OF_MEAN) {
@@ -3025,6 +3173,7 @@ spt_status spt_film_buckets(spt_film* f, uint32_t n_buckets) {
     return guarded("film_buckets", [&] {
         const spt_render_params& p = f->plan;
         // every check comes before the first change: a refused call leaves the film as it was
+        if (f->flags & SPT_FILM_KEEP_SAMPLES) fail(SPT_ERR_INVALID_ARG, "film_buckets: a film that keeps its samples (SPT_FILM_KEEP_SAMPLES) has no bucket sums");
         if (n_buckets < 3u || n_buckets > kMaxBuckets || (n_buckets & 1u) == 0u)
             fail(SPT_ERR_INVALID_ARG, "film_buckets: n_buckets must be odd and 3 .. 15 (got " + std::to_string(n_buckets) + ")");
         if (f->n_buckets != 0u) fail(SPT_ERR_INVALID_ARG, "film_buckets: the film already has buckets");
@@ -3117,6 +3266,40 @@ spt_status spt_film_read_rgb8(spt_film* f, uint32_t source, spt_film* guide, con
         if (denoised) return film_denoise_locked(f, guide, dn, to);
         if (source == SPT_READ_MEAN) return film_read_locked(f, SPT_FILM_MEAN, to);
         return film_read_robust_locked(f, source == SPT_READ_ROBUST_MON ? SPT_ROBUST_MON : SPT_ROBUST_GMON, to);
+    });
+}
+
+spt_status spt_film_read_samples(spt_film* f, uint32_t first, uint32_t count, float* out) {
+    if (!f || !out) { g_error = "film_read_samples: null argument"; return SPT_ERR_INVALID_ARG; }
+    if (f->fwd) return forwarded(f->fwd, f->fwd->film_read_samples(f->inner, first, count, out));
+    spt_scene* sc = f->sc;
+    std::lock_guard<std::mutex> lock(sc->mu);
+    return guarded("film_read_samples", [&] {
+        const spt_render_params& p = f->plan;
+        if (!(f->flags & SPT_FILM_KEEP_SAMPLES)) fail(SPT_ERR_INVALID_ARG, "film_read_samples: the film was created without SPT_FILM_KEEP_SAMPLES");
+        if (first < f->first || (uint64_t)first + count > (uint64_t)f->first + f->done)
+            fail(SPT_ERR_INVALID_ARG, "film_read_samples: samples [" + std::to_string(first) + ", " + std::to_string((uint64_t)first + count) +
+                                          ") are not all covered (the film covers [" + std::to_string(f->first) + ", " + std::to_string(f->first + f->done) + "))");
+        if (count == 0 || f->rows == 0) return SPT_OK;
+        HIP_CHECK(hipSetDevice(sc->device));
+        film_join(sc);
+        const hipStream_t st = sc->stream;
+        // staged through the film's read-out buffer, up to 256 MB (and the grid's 65535 planes) at a time
+        const size_t plane = (size_t)f->rows * p.width * 3;
+        const uint32_t batch = (uint32_t)std::max<size_t>(1, std::min<size_t>(65535, (256u << 20) / (plane * sizeof(float))));
+        f->out.ensure(plane * sizeof(float) * std::min(batch, count));
+        for (uint32_t k0 = 0; k0 < count; k0 += batch) {
+            const uint32_t n = std::min(batch, count - k0);
+            for (const auto& r : f->runs) {
+                const KeptJob job = kept_job(f, r, f->out.as<float>() + r.out_row * (size_t)p.width * 3, false);
+                const size_t floats = (size_t)(r.j1 - r.j0) * p.width * 3;
+                hipLaunchKernelGGL(k_film_read_kept, dim3((uint32_t)((floats + kBlock - 1) / kBlock), n), dim3(kBlock), 0, st, job, p.width, first + k0, plane);
+            }
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipMemcpyAsync(out + (size_t)k0 * plane, f->out.p, (size_t)n * plane * sizeof(float), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipStreamSynchronize(st));
+        }
+        return SPT_OK;
     });
 }
 
@@ -3226,11 +3409,11 @@ spt_status spt_debug_pack_rgb8(int32_t device, uint32_t n, const float* in, uint
 }
 
 spt_status spt_debug_render_info(const spt_scene* scene_c, uint32_t what, uint64_t* out) {
-    if (!scene_c || !out || what > 1u) { g_error = "debug_render_info: null argument or unknown counter"; return SPT_ERR_INVALID_ARG; }
+    if (!scene_c || !out || what > 2u) { g_error = "debug_render_info: null argument or unknown counter"; return SPT_ERR_INVALID_ARG; }
     spt_scene* sc = const_cast<spt_scene*>(scene_c);
     if (sc->fwd) return forwarded(sc->fwd, sc->fwd->debug_render_info(sc->inner, what, out));
     std::lock_guard<std::mutex> lock(sc->mu);
-    *out = what == 0u ? sc->passes_film : sc->passes_single;
+    *out = what == 0u ? sc->passes_film : what == 1u ? sc->passes_single : sc->keep_read_ns;
     return SPT_OK;
 }
 

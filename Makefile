@@ -25,7 +25,7 @@ HOST_HDR := $(wildcard $(PKG)/csrc/host/*.hpp) $(wildcard include/*.h)
 HIP_SRC  := $(wildcard $(PKG)/csrc/hip/*.hip)
 HIP_HDR  := $(wildcard $(PKG)/csrc/hip/*.h) $(wildcard include/*.h)
 
-.PHONY: all host hip hip-plain cli oracle selftest clean
+.PHONY: all host hip hip-plain cli oracle selftest out-layout-check clean
 all: host oracle hip cli
 
 host: $(LIBDIR)/libspt_host.so
@@ -77,6 +77,13 @@ $(SELFTEST_DIR)/multi_film_selftest_tsan: $(SELFTEST_SRC) $(PKG)/csrc/host/multi
 $(SELFTEST_DIR)/multi_film_selftest_asan: $(SELFTEST_SRC) $(PKG)/csrc/host/multi.cpp $(wildcard include/*.h)
 	@mkdir -p $(SELFTEST_DIR)
 	$(CXX) -std=c++17 -O1 -g -Wall -Wextra -ffp-contract=off -Iinclude -fsanitize=address,undefined -fno-sanitize-recover=undefined -static-libasan -static-libubsan -o $@ $(SELFTEST_SRC) $(PKG)/csrc/host/multi.cpp -lpthread
+
+# csrc/hip/out_layout.h (where k_finish_host stores a film's floats) against a plain loop over rows, under AddressSanitizer + UBSan:
+# a stand-alone host program (tests/test_out_layout.py runs it)
+out-layout-check: $(SELFTEST_DIR)/out_layout_check
+$(SELFTEST_DIR)/out_layout_check: tests/out_layout_check.cpp $(PKG)/csrc/hip/out_layout.h
+	@mkdir -p $(SELFTEST_DIR)
+	$(CXX) -std=c++17 -O1 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -static-libasan -static-libubsan -o $@ $<
 
 clean:
 	rm -rf $(LIBDIR) build oracle/*.so oracle/_ref

@@ -699,7 +699,9 @@ spt_status spt_debug_bxdf(const spt_scene* scene, int32_t device, const spt_mate
  *   what 0  passes whose resolve was queued on the film stream (the overlapped schedule of an SPT_RENDER_ASYNC spt_render)
  *   what 1  passes that took the single-stream path (every other render, spt_film_render, SPT_NO_FILM_STREAM=1)
  *   what 2  nanoseconds the read-out kernels of the last spt_film_read / spt_film_read_rgb8 of a sample-keeping film
- *           (SPT_FILM_KEEP_SAMPLES) of the scene took on the device (0: none yet) */
+ *           (SPT_FILM_KEEP_SAMPLES) of the scene took on the device (0: none yet)
+ *   what 3  frames of spt_render delivered without the runtime's copy: the finish kernel stored the image into rgb_mean_out
+ *           itself (an SPT_RENDER_ASYNC frame on the overlapped schedule, radius 0.5, page-locked destination, no SPT_NO_DIRECT_OUT=1) */
 spt_status spt_debug_render_info(const spt_scene* scene, uint32_t what, uint64_t* out);
 
 const char* spt_last_error(void);

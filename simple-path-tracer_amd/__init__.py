@@ -487,7 +487,8 @@ class DeviceScene:
 
     def render_info(self, what: int) -> int:
         """Test seam (spt_debug_render_info): 0 passes resolved on the film stream, 1 passes on the single-stream path;
-        2 the ns the kernels of the last read-out of a sample-keeping film of the scene took on the device."""
+        2 the ns the kernels of the last read-out of a sample-keeping film of the scene took on the device; 3 frames whose
+        finish kernel stored the image into the (page-locked) output buffer itself, without the runtime's copy."""
         v = C.c_uint64(0)
         _check_hip(hip_lib().spt_debug_render_info(self._h, what, C.byref(v)))
         return int(v.value)

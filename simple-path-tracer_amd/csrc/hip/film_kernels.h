@@ -2,6 +2,7 @@
 // kernel templates of kernels.h are instantiated in their own translation units, see kernel_list.h).
 #pragma once
 #include "kernels.h"
+#include "out_layout.h"
 
 // ---------------------------------------------------------------------------- resolve
 // k_resolve for passes of the chunked k_primary (slot bits; the only form the headline workload runs).
@@ -184,6 +185,38 @@ __global__ void __launch_bounds__(256) k_finish(RenderCtx rc, float* out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= rc.n_pixels * 3u) return;
     out[i] = rc.film[i] * rc.spp_inv;
+}
+
+// k_finish with the caller's buffer as its destination: `dst` is the device-visible address of spt_render's rgb_mean_out (pinned
+// host memory, checked per call by spt_render), so the image needs neither the scene's `out` buffer nor the runtime's copy, whose
+// blit kernel holds up the k_primary beside it for as long as it runs (profiles/r05_copy_probe.md).  The same product for every
+// float; out_layout.h says where a float goes (packed, or strip by strip in a larger film) and cuts the destination into
+// 16-byte stores with dword stores at the ragged ends of a segment.  Grid-stride over the windows.
+// kFinishHostGrid: FEW workgroups on purpose.  MEASURED (profiles/r05_copy_probe.md, a k_primary-shaped kernel of 0.55 ms beside a copy kernel of
+// 12.6 MB into pinned memory): 256 or 4096 workgroups lengthen it to 0.72 ms, as the runtime's blit kernel does; 32 to 0.62 - 0.65; 4 leave it at
+// 0.55 and take 0.6 - 0.76 ms themselves, which the film stream has.  Plain against non-temporal stores: no difference beyond the ranges; plain.
+constexpr uint32_t kFinishHostGrid = 4;
+constexpr bool kFinishHostNonTemporal = false;
+typedef float finish_v4 __attribute__((ext_vector_type(4)));
+
+__global__ void __launch_bounds__(256) k_finish_host(RenderCtx rc, OutLayout lay, float* dst) {
+    const uint64_t items = out_layout_items(lay);
+    for (uint64_t item = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; item < items; item += (uint64_t)gridDim.x * blockDim.x) {
+        const OutWindow w = out_window(lay, item);
+        const float* src = rc.film + w.src;
+        if (w.count == 4u) {
+            const finish_v4 v = {src[0] * rc.spp_inv, src[1] * rc.spp_inv, src[2] * rc.spp_inv, src[3] * rc.spp_inv};
+            finish_v4* to = reinterpret_cast<finish_v4*>(dst + w.dst);
+            if (kFinishHostNonTemporal) __builtin_nontemporal_store(v, to);
+            else *to = v;
+        } else {
+            for (uint32_t k = 0; k < w.count; ++k) {
+                const float v = src[k] * rc.spp_inv;
+                if (kFinishHostNonTemporal) __builtin_nontemporal_store(v, dst + w.dst + k);
+                else dst[w.dst + k] = v;
+            }
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------- general box filter

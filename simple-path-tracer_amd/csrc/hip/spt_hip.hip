@@ -572,6 +572,7 @@ struct spt_scene {
     bool film_pending = false;                // the main stream is not yet behind the film-stream kernels of an overlapped render (film_join)
     bool film_inflight = false;               // ... and the host has not waited for them since (grow)
     uint64_t passes_film = 0, passes_single = 0;   // spt_debug_render_info: passes resolved on the film stream / on the main stream
+    uint64_t frames_direct = 0;                    // ... and frames whose finish kernel stored into the caller's buffer (no copy-out)
     // ... and what the kernels of a sample-keeping film's last read-out (k_film_filter_box) took on the device, in ns, between the
     // two events below (made by the first such film)
     uint64_t keep_read_ns = 0;
@@ -1604,6 +1605,8 @@ struct RenderRun {
     bool resolve32 = false;      // k_resolve_bits<32u> instead of <16u>
     bool film_stream = false;    // the overlapped schedule is allowed (no SPT_NO_FILM_STREAM)
     bool film_overlap = false;   // ... and this render takes it: tail launch, resolve, finish and copy-out on the film stream
+    bool direct_out = false;     // k_finish_host may store into a pinned rgb_mean_out (no SPT_NO_DIRECT_OUT)
+    uint32_t direct_grid = 0;    // ... over this many workgroups at the most (kFinishHostGrid, or SPT_DIRECT_OUT_GRID for A/B runs)
     bool debug_spans = false;    // per-launch HIP-event times on stderr (profile mode)
     bool albedo = false;         // SPT_RENDER_AOV_ALBEDO: paths end at their first surface, and the kernels get the scene without its environment
     bool env = false;            // the scene the kernels see has an environment
@@ -1693,6 +1696,8 @@ void run_setup(RenderRun& run) {
     if (const char* v = std::getenv("SPT_PRIMARY_CHUNKS")) run.primary_chunks = (uint32_t)std::max(1, std::atoi(v));
     run.resolve32 = env_u32("SPT_RESOLVE_BATCH", 16u) == 32u;
     run.film_stream = env_u32("SPT_NO_FILM_STREAM", 0u) == 0u;
+    run.direct_out = env_u32("SPT_NO_DIRECT_OUT", 0u) == 0u;
+    run.direct_grid = std::max(1u, env_u32("SPT_DIRECT_OUT_GRID", kFinishHostGrid));
     run.box_band_bytes = 8ull << 30;
     if (const char* v = std::getenv("SPT_BOX_BAND_BYTES")) run.box_band_bytes = std::max<uint64_t>(1, std::strtoull(v, nullptr, 10));
     run.debug_spans = std::getenv("SPT_DEBUG_SPANS") != nullptr;
@@ -2451,6 +2456,22 @@ KeptJob kept_job(const spt_film* f, const spt_film::KeptRun& r, float* out, bool
     return KeptJob{r.table_dev.as<KeptChunk>(), (uint32_t)r.table.size(), r.b0, r.b1 - r.b0, r.j0, r.j1 - r.j0, out, f->R, f->radius, mean ? 1u : 0u};
 }
 
+// The device-visible address of spt_render's destination when k_finish_host may store into it, else nullptr (the frame then
+// takes the runtime's copy): the first and the last byte of the span the shard writes must both be mapped for the device, exactly
+// that span apart - pageable memory, a buffer pinned only in part and two unrelated mappings all fail one of the three.  Asked anew
+// for every call: the caller may unpin or free the buffer between two renders.
+float* direct_destination(const spt_render_params& p, uint32_t own_rows, uint32_t strip_rows, float* host, OutLayout* lay) {
+    if (((uintptr_t)host & 3u) != 0u || (p.out_strip_stride & 3u) != 0u) return nullptr;
+    void *d_first = nullptr, *d_last = nullptr;
+    if (hipHostGetDevicePointer(&d_first, host, 0) != hipSuccess || !d_first) { (void)hipGetLastError(); return nullptr; }
+    *lay = out_layout(own_rows, p.width, strip_rows, p.out_strip_stride, (uint64_t)(uintptr_t)d_first);
+    const uint64_t span = out_layout_span(*lay) * sizeof(float);
+    if (span == 0u) return nullptr;
+    if (hipHostGetDevicePointer(&d_last, (char*)host + (span - 1u), 0) != hipSuccess || !d_last) { (void)hipGetLastError(); return nullptr; }
+    if ((uintptr_t)d_last - (uintptr_t)d_first != span - 1u) return nullptr;
+    return (float*)d_first;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2493,6 +2514,8 @@ spt_status spt_render(const spt_scene* scene_c, const spt_camera* cam, const spt
         const int32_t R = (int32_t)std::ceil(radius - 0.5f);
         HIP_CHECK(hipSetDevice(sc->device));
         grow(sc, sc->out, (size_t)own_pix * 3 * sizeof(float));
+        const size_t strip_bytes = (size_t)strip_rows * p.width * 3 * sizeof(float);
+        if (p.out_strip_stride != 0 && p.out_strip_stride < strip_bytes) fail(SPT_ERR_INVALID_ARG, "render: out_strip_stride smaller than a strip");
 
         RenderRun run;
         run.sc = sc;
@@ -2507,6 +2530,11 @@ spt_status spt_render(const spt_scene* scene_c, const spt_camera* cam, const spt
         hipEvent_t ev_total0 = run.get_event(), ev_total1 = run.get_event();
         HIP_CHECK(hipEventRecord(ev_total0, run.st));
         run_spans(run);
+        // radius 0.5 into pinned memory on the overlapped schedule: the finish kernel stores the image into the caller's buffer itself
+        // (k_finish_host).  Overlapped frames only: the kernel is slow by design (few workgroups, film_kernels.h) and belongs on the
+        // film stream beside the next frame, not on the critical path of a synchronous or single-stream render
+        OutLayout direct_lay{};
+        float* const direct_dst = radius == 0.5f && run.direct_out && run.film_overlap ? direct_destination(p, own_rows, strip_rows, rgb_mean_out, &direct_lay) : nullptr;
         const SampleTarget whole{0u, p.spp, nullptr, nullptr, true};   // every sample of the plan, into the scene's film from zero
         if (R <= 0) {
             const RenderCtx rc = trace_window(run, 0, own_rows, p.shard_index, shard_count, strip_rows, false, whole);
@@ -2516,7 +2544,10 @@ spt_status spt_render(const spt_scene* scene_c, const spt_camera* cam, const spt
             // film stream's order.  Else the previous frame's copy-out, which reads `out`, is waited for
             const hipStream_t st_fin = run.film_overlap ? sc->stream_film : run.st;
             if (!run.film_overlap && sc->copy_pending) HIP_CHECK(hipStreamWaitEvent(run.st, sc->ev_copy_done, 0));
-            if (radius == 0.5f) hipLaunchKernelGGL(k_finish, dim3((own_pix * 3 + kBlock - 1) / kBlock), dim3(kBlock), 0, st_fin, rc, sc->out.as<float>());
+            if (radius == 0.5f && direct_dst) {
+                const uint64_t blocks = (out_layout_items(direct_lay) + kBlock - 1) / kBlock;
+                hipLaunchKernelGGL(k_finish_host, dim3((uint32_t)std::min<uint64_t>(blocks, run.direct_grid)), dim3(kBlock), 0, st_fin, rc, direct_lay, direct_dst);
+            } else if (radius == 0.5f) hipLaunchKernelGGL(k_finish, dim3((own_pix * 3 + kBlock - 1) / kBlock), dim3(kBlock), 0, st_fin, rc, sc->out.as<float>());
             else hipLaunchKernelGGL(k_finish_box, grid, dim3(kBlock), 0, st_fin, rc, sc->out.as<float>(), radius, R, 0u, p.spp);
             run.end();
         } else {
@@ -2553,18 +2584,32 @@ spt_status spt_render(const spt_scene* scene_c, const spt_camera* cam, const spt
             }
             st_out = sc->stream_film;
         }
-        const size_t strip_bytes = (size_t)strip_rows * p.width * 3 * sizeof(float);
-        if (p.out_strip_stride == 0 || p.out_strip_stride == strip_bytes) {
-            HIP_CHECK(hipMemcpyAsync(rgb_mean_out, sc->out.p, (size_t)own_pix * 3 * sizeof(float), hipMemcpyDeviceToHost, st_out));
+        if (direct_dst) {
+            ++sc->frames_direct;   // the image is where it belongs: the events below make it visible to the host
         } else {
+            const size_t row_bytes = (size_t)p.width * 3 * sizeof(float);
+            const bool packed = p.out_strip_stride == 0 || p.out_strip_stride == strip_bytes;
             // strided copy-out: the shard's strips land strip by strip in a larger (full-image) film
-            if (p.out_strip_stride < strip_bytes) fail(SPT_ERR_INVALID_ARG, "render: out_strip_stride smaller than a strip");
             const size_t full = own_rows / strip_rows, rest_rows = own_rows - full * strip_rows;
-            if (full)
-                HIP_CHECK(hipMemcpy2DAsync(rgb_mean_out, p.out_strip_stride, sc->out.p, strip_bytes, strip_bytes, full, hipMemcpyDeviceToHost, st_out));
-            if (rest_rows)
-                HIP_CHECK(hipMemcpyAsync((char*)rgb_mean_out + full * p.out_strip_stride, (const char*)sc->out.p + full * strip_bytes,
-                                         rest_rows * (size_t)p.width * 3 * sizeof(float), hipMemcpyDeviceToHost, st_out));
+            hipError_t e = hipSuccess;
+            if (packed) e = hipMemcpyAsync(rgb_mean_out, sc->out.p, (size_t)own_pix * 3 * sizeof(float), hipMemcpyDeviceToHost, st_out);
+            else {
+                if (full) e = hipMemcpy2DAsync(rgb_mean_out, p.out_strip_stride, sc->out.p, strip_bytes, strip_bytes, full, hipMemcpyDeviceToHost, st_out);
+                if (e == hipSuccess && rest_rows)
+                    e = hipMemcpyAsync((char*)rgb_mean_out + full * p.out_strip_stride, (const char*)sc->out.p + full * strip_bytes, rest_rows * row_bytes,
+                                       hipMemcpyDeviceToHost, st_out);
+            }
+            if (e == hipErrorInvalidValue) {
+                // the runtime refuses a destination that is page-locked only in part (a film that straddles the end of a pinned
+                // region): through a pageable buffer of the library's own, synchronously - the film is complete when this returns
+                (void)hipGetLastError();
+                std::vector<float> staged((size_t)own_pix * 3);
+                HIP_CHECK(hipStreamSynchronize(st_out));
+                HIP_CHECK(hipMemcpy(staged.data(), sc->out.p, staged.size() * sizeof(float), hipMemcpyDeviceToHost));
+                const size_t stride = packed ? strip_bytes : (size_t)p.out_strip_stride;
+                for (uint32_t r = 0; r < own_rows; ++r)
+                    std::memcpy((char*)rgb_mean_out + (r / strip_rows) * stride + (r % strip_rows) * row_bytes, staged.data() + (size_t)r * p.width * 3, row_bytes);
+            } else HIP_CHECK(e);
         }
         if (async_out) {
             HIP_CHECK(hipEventRecord(sc->ev_copy_done, sc->stream_film));
@@ -3409,11 +3454,11 @@ spt_status spt_debug_pack_rgb8(int32_t device, uint32_t n, const float* in, uint
 }
 
 spt_status spt_debug_render_info(const spt_scene* scene_c, uint32_t what, uint64_t* out) {
-    if (!scene_c || !out || what > 2u) { g_error = "debug_render_info: null argument or unknown counter"; return SPT_ERR_INVALID_ARG; }
+    if (!scene_c || !out || what > 3u) { g_error = "debug_render_info: null argument or unknown counter"; return SPT_ERR_INVALID_ARG; }
     spt_scene* sc = const_cast<spt_scene*>(scene_c);
     if (sc->fwd) return forwarded(sc->fwd, sc->fwd->debug_render_info(sc->inner, what, out));
     std::lock_guard<std::mutex> lock(sc->mu);
-    *out = what == 0u ? sc->passes_film : what == 1u ? sc->passes_single : sc->keep_read_ns;
+    *out = what == 0u ? sc->passes_film : what == 1u ? sc->passes_single : what == 2u ? sc->keep_read_ns : sc->frames_direct;
     return SPT_OK;
 }
 

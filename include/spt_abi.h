@@ -666,6 +666,60 @@ spt_status spt_film_read_rgb8(spt_film* film, uint32_t source, spt_film* guide, 
 spt_status spt_trace_closest(const spt_scene* scene, uint32_t n, const spt_ray* rays, spt_hit* hits);
 spt_status spt_trace_any(const spt_scene* scene, uint32_t n, const spt_ray* rays, uint8_t* occluded);
 
+/* ---- radiance along caller-provided rays (additive to ABI v14: detect it by symbol) ---------------------------------------------
+ * spt_radiance is the integrator without the camera: PathTracer::trace_ray (src/renderer/pt.rs:39-210) for rays the caller made,
+ * under the scene's light sampler.  Everything the film calls compute per camera sample is computed here per ray, by the same
+ * kernels from bounce 0 on; only the pinhole camera and the pixel grid are gone.
+ * Per path: x(i, k) is trace_ray for the ray (o, d, t_min) of record i with the job's max_depth.  Its RNG starts at
+ * spt_rng_seed(seed, stream_a, stream_b + k) (include/spt_detmath.h), advanced by rng_skip draws before the path starts (a camera
+ * sample of the random sampler has drawn its two pixel offsets by then: rng_skip = 2).  Depth 0 is a camera ray's: emission and
+ * the environment get weight 1, a miss adds 0 + (1 * env) * 1.  t_min holds for the first segment only (the integrator's own
+ * epsilon after it); d is taken as it is, unit length is the caller's business.  max_depth == 0: every path is 0.
+ * Per ray: out_i = ((0 + x(i, 0)) + x(i, 1) + ... + x(i, S - 1)) * (1.0f / (float)S) with S = repeats, added in k order, every
+ * operation a rounded f32 operation, per channel.
+ * Textures and glints: with `aux`, a scene that samples textures computes the differentials of the depth-0 hit from the ray's two
+ * auxiliary rays, Intersection::calc_differential with (rx_o, rx_d, ry_o, ry_d); without it the first hit is textured as the
+ * reference textures every later hit, without differentials.  Scenes that sample no texture never read `aux`.
+ * hits_out[i] is what spt_trace_closest returns for (o, t_min, d, f32::MAX).
+ * A ray's result depends on its own record and the job's scalar fields only: not on its place in the array, its neighbours,
+ * rays_per_pass or how the call is cut into passes.
+ * Pointers are host pointers by default; the rays go up through page-locked staging in two slots (the host checks and fills one
+ * while the other is in flight) and the results come back when every pass has run.  With SPT_RADIANCE_DEVICE_POINTERS rays, aux,
+ * rgb_out and hits_out are device memory on the scene's device (the base address of each is checked with hipPointerGetAttributes,
+ * rays and aux for 16-byte, rgb_out and hits_out for 4-byte alignment; that each allocation holds n_rays records is the caller's
+ * business, as with any pointer of this ABI): the caller has finished producing them before the call, the library has finished
+ * writing when it returns.
+ * Refusals write nothing and leave the scene usable.  SPT_ERR_INVALID_ARG: a null scene or job; null rays or rgb_out while
+ * n_rays > 0; size below sizeof(spt_radiance_job); unknown flags; repeats == 0; a host ray whose o, d or t_min is not finite or
+ * whose d is all zero (the message names the first such index); a device pointer that is not device memory of the scene's device
+ * or not aligned as above.
+ * SPT_ERR_UNSUPPORTED: max_depth > 255.  n_rays == 0 returns SPT_OK and does nothing.
+ * Synchronous.  Takes the scene's lock, starts behind whatever an asynchronous spt_render left on the film stream, shares the
+ * render workspace, and touches neither spt_render's film / out buffers nor any film.  Scenes with Bezier patches are served. */
+typedef struct spt_path_ray {      /* 48 B */
+    float o[3]; float t_min;       /* first segment only */
+    float d[3]; uint32_t stream_a;
+    uint32_t stream_b; uint32_t pad[3];
+} spt_path_ray;
+typedef struct spt_ray_aux {       /* 64 B: the two auxiliary rays of Intersection::calc_differential */
+    float rx_o[3], pad0, rx_d[3], pad1, ry_o[3], pad2, ry_d[3], pad3;
+} spt_ray_aux;
+enum { SPT_RADIANCE_DEVICE_POINTERS = 1u };
+typedef struct spt_radiance_job {
+    uint32_t size, flags;          /* sizeof(spt_radiance_job) as the caller was compiled (the struct only grows at its tail); SPT_RADIANCE_* */
+    uint64_t n_rays;
+    const spt_path_ray* rays;
+    const spt_ray_aux* aux;        /* NULL, or n_rays records */
+    uint32_t repeats;              /* S >= 1 paths per ray */
+    uint32_t max_depth;
+    uint64_t seed;
+    uint32_t rng_skip;             /* draws discarded from every stream before the path starts */
+    uint32_t rays_per_pass;        /* tuning, 0 = default */
+    float* rgb_out;                /* n_rays * 3 f32 */
+    spt_hit* hits_out;             /* NULL, or n_rays records: the closest hit of each ray's first segment */
+} spt_radiance_job;
+spt_status spt_radiance(const spt_scene* scene, const spt_radiance_job* job);
+
 /* Page-locked host memory for rgb_mean_out: lets the final device-to-host copy of the film run as one
  * DMA at PCIe rate instead of being staged through the runtime's bounce buffers.  Optional: any host
  * pointer is accepted by spt_render. */

@@ -9,7 +9,7 @@ Mirrors the reference's host-side surface for the path
 
 `render` runs the hand-written HIP kernels of libspt_hip.so.  There is no CPU
 fallback: if the library or a gfx950 device is missing the call raises.
-PyTorch is not involved in this module at all (ctypes + numpy only).
+ctypes + numpy only; PyTorch is imported in one place, when DeviceScene.radiance is handed torch tensors.
 """
 from __future__ import annotations
 
@@ -240,6 +240,19 @@ class MultiFilmDenoiseJob(C.Structure):
 
 HIT_DTYPE = np.dtype([("t", "<f4"), ("instance", "<i4"), ("prim", "<i4"), ("v", "<f4"), ("w", "<f4")])
 RAY_DTYPE = np.dtype([("o", "<f4", 3), ("t_min", "<f4"), ("d", "<f4", 3), ("t_max", "<f4")])
+# spt_radiance: spt_path_ray (48 B) and spt_ray_aux (64 B)
+PATH_RAY_DTYPE = np.dtype([("o", "<f4", 3), ("t_min", "<f4"), ("d", "<f4", 3), ("stream_a", "<u4"), ("stream_b", "<u4"), ("pad", "<u4", 3)])
+RAY_AUX_DTYPE = np.dtype([("rx_o", "<f4", 3), ("pad0", "<f4"), ("rx_d", "<f4", 3), ("pad1", "<f4"), ("ry_o", "<f4", 3), ("pad2", "<f4"),
+                          ("ry_d", "<f4", 3), ("pad3", "<f4")])
+RADIANCE_DEVICE_POINTERS = 1
+CAMERA_T_MIN = 1e-4   # Ray::T_MIN_EPS, the t_min of a camera ray (kTMinEps)
+
+
+class RadianceJob(C.Structure):
+    """spt_radiance_job (spt_radiance); `size` is sizeof of the struct."""
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("n_rays", C.c_uint64), ("rays", C.c_void_p), ("aux", C.c_void_p),
+                ("repeats", C.c_uint32), ("max_depth", C.c_uint32), ("seed", C.c_uint64), ("rng_skip", C.c_uint32),
+                ("rays_per_pass", C.c_uint32), ("rgb_out", C.c_void_p), ("hits_out", C.c_void_p)]
 
 
 # ---- library loading -----------------------------------------------------------------
@@ -353,6 +366,8 @@ def hip_lib() -> C.CDLL:
             lib.spt_film_read_samples.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         if hasattr(lib, "spt_denoise_image"):   # (the same)
             lib.spt_denoise_image.argtypes = [C.c_void_p, C.POINTER(ImageDenoiseJob), C.c_void_p]
+        if hasattr(lib, "spt_radiance"):   # (the same)
+            lib.spt_radiance.argtypes = [C.c_void_p, C.POINTER(RadianceJob)]
         lib.spt_debug_detmath.argtypes = [C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.spt_debug_bxdf.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Material), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -484,6 +499,51 @@ class DeviceScene:
         occ = np.zeros(rays.shape[0], dtype=np.uint8)
         _check_hip(hip_lib().spt_trace_any(self._h, rays.shape[0], rays.ctypes.data, occ.ctypes.data))
         return occ
+
+    def radiance(self, rays, aux=None, repeats: int = 1, max_depth: int = 8, seed: int = 1, rng_skip: int = 0, rays_per_pass: int = 0,
+                 hits: bool = False):
+        """spt_radiance: the radiance arriving along caller rays, (n, 3) f32; with `hits` also the closest hit of every ray's first
+        segment, as a second result.  rays / aux are PATH_RAY_DTYPE / RAY_AUX_DTYPE arrays (see perspective_rays and the other
+        generators), or contiguous float32 torch tensors on the scene's device of shape (n, 12) / (n, 16) holding the same records
+        (stream_a / stream_b as bit patterns): then the producer's current stream is synchronised, the library reads and writes
+        device memory and the results are tensors, the hits an (n, 5) int32 tensor of the spt_hit words."""
+        lib = hip_lib()
+        if not hasattr(lib, "spt_radiance"):
+            raise SptError(4, "this libspt_hip.so has no spt_radiance")
+        job = RadianceJob(size=C.sizeof(RadianceJob), repeats=repeats, max_depth=max_depth, seed=seed, rng_skip=rng_skip, rays_per_pass=rays_per_pass)
+        if type(rays).__module__.split(".")[0] == "torch":
+            import torch
+            for t, words, what in ((rays, 12, "rays"), (aux, 16, "aux")):
+                if t is None:
+                    continue
+                if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != words or not t.is_contiguous():
+                    raise ValueError("%s: a contiguous float32 (n, %d) tensor is expected" % (what, words))
+                if t.device.type != "cuda" or t.device.index != self.device:
+                    raise ValueError("%s: the tensor must live on the scene's device (cuda:%d)" % (what, self.device))
+            n = rays.shape[0]
+            if aux is not None and aux.shape[0] != n:
+                raise ValueError("aux: one record per ray is expected")
+            out = torch.empty((n, 3), dtype=torch.float32, device=rays.device)
+            hit = torch.empty((n, 5), dtype=torch.int32, device=rays.device) if hits else None
+            torch.cuda.current_stream(rays.device).synchronize()   # the rays are complete before the library's stream reads them
+            job.flags, job.n_rays = RADIANCE_DEVICE_POINTERS, n
+            job.rays, job.aux = rays.data_ptr() if n else None, aux.data_ptr() if aux is not None and n else None
+            job.rgb_out, job.hits_out = out.data_ptr() if n else None, hit.data_ptr() if hits and n else None
+            _check_hip(lib.spt_radiance(self._h, C.byref(job)))
+            return (out, hit) if hits else out
+        rays = np.ascontiguousarray(rays, dtype=PATH_RAY_DTYPE).reshape(-1)
+        n = rays.shape[0]
+        if aux is not None:
+            aux = np.ascontiguousarray(aux, dtype=RAY_AUX_DTYPE).reshape(-1)
+            if aux.shape[0] != n:
+                raise ValueError("aux: one record per ray is expected")
+        out = np.zeros((n, 3), dtype=np.float32)
+        hit = np.zeros(n, dtype=HIT_DTYPE) if hits else None
+        job.n_rays = n
+        job.rays, job.aux = rays.ctypes.data, aux.ctypes.data if aux is not None else None
+        job.rgb_out, job.hits_out = out.ctypes.data, hit.ctypes.data if hits else None
+        _check_hip(lib.spt_radiance(self._h, C.byref(job)))
+        return (out, hit) if hits else out
 
     def render_info(self, what: int) -> int:
         """Test seam (spt_debug_render_info): 0 passes resolved on the film stream, 1 passes on the single-stream path;
@@ -1082,6 +1142,134 @@ def make_camera(eye, forward, up, fov_degrees: float) -> Camera:
         cam.eye[k], cam.forward[k], cam.up[k], cam.right[k] = float(e[k]), float(f[k]), float(u[k]), float(r[k])
     cam.half_cot_half_fov = float(f32(0.5) / f32(np.tan(f32(np.radians(fov_degrees)) * f32(0.5))))
     return cam
+
+
+# ---- ray generators for DeviceScene.radiance ------------------------------------------------------------------------------
+# Pixel offsets are (H, W, 2) or (count, H, W, 2) f32 in [0, 1); the rays come back as (count, H, W) PATH_RAY_DTYPE records with
+# t_min = CAMERA_T_MIN and the streams of a camera plan: stream_a = j * W + i (the pixel), stream_b = first_sample + s.
+
+def _offsets4(offsets, width: int, height: int) -> np.ndarray:
+    off = np.asarray(offsets, dtype=np.float32)
+    if off.ndim == 3:
+        off = off[None]
+    if off.ndim != 4 or off.shape[1:] != (height, width, 2):
+        raise ValueError("offsets: (height, width, 2) or (count, height, width, 2) is expected")
+    return off
+
+
+def _plan_rays(count: int, width: int, height: int, first_sample: int) -> np.ndarray:
+    rays = np.zeros((count, height, width), dtype=PATH_RAY_DTYPE)
+    rays["t_min"] = np.float32(CAMERA_T_MIN)
+    rays["stream_a"] = (np.arange(height, dtype=np.uint32)[:, None] * np.uint32(width) + np.arange(width, dtype=np.uint32)[None, :])[None]
+    rays["stream_b"] = (np.uint32(first_sample) + np.arange(count, dtype=np.uint32))[:, None, None]
+    return rays
+
+
+def _unit64(v: np.ndarray) -> np.ndarray:
+    """Directions normalised in float64 and rounded once: |d|^2 is within 2^-23 of 1."""
+    v = np.asarray(v, dtype=np.float64)
+    return (v / np.sqrt(np.sum(v * v, axis=-1, keepdims=True))).astype(np.float32)
+
+
+def perspective_rays(camera: Camera, width: int, height: int, offsets, aux_spp: Optional[int] = None, *, first_sample: int = 0):
+    """The camera rays of a plan, bit for bit: pt.rs:269-271 and PerspectiveCamera::generate_ray (camera/perspective.rs:40-47) in
+    float32 numpy, one rounded operation at a time.  `offsets` are the plan's pixel offsets of the samples first_sample, ... .
+    With aux_spp (the plan's spp) the auxiliary rays of generate_ray_with_aux_ray (pt.rs:272-275) come back too, as
+    RAY_AUX_DTYPE records of the same shape: (rays, aux)."""
+    f32 = np.float32
+    off = _offsets4(offsets, width, height)
+    fwd, up, right, eye = (np.array(list(v), dtype=f32) for v in (camera.forward, camera.up, camera.right, camera.eye))
+    hc = f32(camera.half_cot_half_fov)
+    aspect = f32(width) / f32(height)
+    width_inv, height_inv = f32(1) / f32(width), f32(1) / f32(height)
+    col = np.arange(width, dtype=np.uint32).astype(f32)[None, None, :]
+    row = (np.uint32(height) - np.arange(height, dtype=np.uint32) - np.uint32(1)).astype(f32)[None, :, None]
+    x = ((col + off[..., 0]) * width_inv - f32(0.5)) * aspect
+    y = (row + off[..., 1]) * height_inv - f32(0.5)
+
+    def direction(x, y):
+        v = [(fwd[k] * hc + right[k] * x) + up[k] * y for k in range(3)]
+        length = np.sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2])
+        return np.stack([c / length for c in v], axis=-1).astype(f32)
+
+    rays = _plan_rays(off.shape[0], width, height, first_sample)
+    rays["o"] = eye
+    rays["d"] = direction(x, y)
+    if aux_spp is None:
+        return rays
+    spp_sqrt_inv = f32(1) / np.sqrt(f32(aux_spp))
+    aux_dx, aux_dy = aspect * width_inv * spp_sqrt_inv, height_inv * spp_sqrt_inv
+    aux = np.zeros(rays.shape, dtype=RAY_AUX_DTYPE)
+    aux["rx_o"] = eye
+    aux["ry_o"] = eye
+    aux["rx_d"] = direction(x + aux_dx, y)
+    aux["ry_d"] = direction(x, y + aux_dy)
+    return rays, aux
+
+
+def _screen_xy(off: np.ndarray, width: int, height: int):
+    """x in [-aspect / 2, aspect / 2) to the right and y in (-0.5, 0.5] upwards (row 0 on top), as pt.rs:269-271, in float64."""
+    col = np.arange(width, dtype=np.float64)[None, None, :]
+    row = (height - 1 - np.arange(height, dtype=np.float64))[None, :, None]
+    return ((col + off[..., 0]) / width - 0.5) * (width / height), (row + off[..., 1]) / height - 0.5
+
+
+def orthographic_rays(camera: Camera, width: int, height: int, offsets, view_height: float, *, first_sample: int = 0) -> np.ndarray:
+    """Parallel rays along camera.forward.  The image plane passes through camera.eye; screen coordinates are those of the
+    perspective camera (x to camera.right, y to camera.up, row 0 on top) scaled so that the image is view_height world units
+    high: o = eye + (right * x + up * y) * view_height, d = forward normalised.  half_cot_half_fov is not used."""
+    off = _offsets4(offsets, width, height)
+    x, y = _screen_xy(off, width, height)
+    fwd, up, right, eye = (np.array(list(v), dtype=np.float64) for v in (camera.forward, camera.up, camera.right, camera.eye))
+    rays = _plan_rays(off.shape[0], width, height, first_sample)
+    rays["o"] = (eye + (right * x[..., None] + up * y[..., None]) * float(view_height)).astype(np.float32)
+    rays["d"] = _unit64(fwd)
+    return rays
+
+
+def panorama_rays(origin, width: int, height: int, offsets, *, first_sample: int = 0) -> np.ndarray:
+    """Equirectangular rays from `origin`, in the environment map's own parametrisation (environment.rs:128-133: theta =
+    acos(d.y), phi = atan2(d.x, d.z) + pi): row j looks at theta = (j + oy) / height * pi, so row 0 starts at theta 0 (+y, the
+    top pole) and the last row ends at theta pi (-y); column i looks at phi = (i + ox) / width * 2 pi, so the seam phi = 0 at the
+    left edge of column 0 looks along -z, the image centre phi = pi along +z, and phi = pi / 2 along -x."""
+    off = _offsets4(offsets, width, height)
+    theta = (np.arange(height, dtype=np.float64)[None, :, None] + off[..., 1]) / height * np.pi
+    phi = (np.arange(width, dtype=np.float64)[None, None, :] + off[..., 0]) / width * (2.0 * np.pi)
+    st = np.sin(theta)
+    d = np.stack([st * np.sin(phi - np.pi), np.cos(theta), st * np.cos(phi - np.pi)], axis=-1)
+    rays = _plan_rays(off.shape[0], width, height, first_sample)
+    rays["o"] = np.asarray(origin, dtype=np.float32)
+    rays["d"] = _unit64(d)
+    return rays
+
+
+def thin_lens_rays(camera: Camera, width: int, height: int, offsets, lens_uv, lens_radius: float, focus_distance: float, *,
+                   first_sample: int = 0) -> np.ndarray:
+    """The perspective camera behind a thin lens.  The pinhole ray through screen point (x, y) meets the plane of focus -
+    focus_distance along camera.forward from the eye - at F = eye + (forward * half_cot + right * x + up * y) * (focus_distance /
+    half_cot); the ray starts on the lens at o = eye + (right * lx + up * ly) * lens_radius, where (lx, ly) is lens_uv (shaped like
+    offsets, in [0, 1)^2) mapped to the unit disk by Shirley's concentric map, and d = normalize(F - o).  lens_radius 0 gives
+    the pinhole's rays up to rounding."""
+    off = _offsets4(offsets, width, height)
+    uv = _offsets4(lens_uv, width, height).astype(np.float64) * 2.0 - 1.0
+    if uv.shape != off.shape:
+        raise ValueError("lens_uv: the shape of offsets is expected")
+    a, b = uv[..., 0], uv[..., 1]
+    wide = np.abs(a) > np.abs(b)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = np.where(wide, a, b)
+        ang = np.where(wide, (np.pi / 4) * (b / a), np.pi / 2 - (np.pi / 4) * (a / b))
+    ang = np.where((a == 0) & (b == 0), 0.0, ang)
+    lx, ly = r * np.cos(ang), r * np.sin(ang)
+    x, y = _screen_xy(off, width, height)
+    fwd, up, right, eye = (np.array(list(v), dtype=np.float64) for v in (camera.forward, camera.up, camera.right, camera.eye))
+    hc = float(camera.half_cot_half_fov)
+    focus = eye + (fwd * hc + right * x[..., None] + up * y[..., None]) * (float(focus_distance) / hc)
+    o = eye + (right * lx[..., None] + up * ly[..., None]) * float(lens_radius)
+    rays = _plan_rays(off.shape[0], width, height, first_sample)
+    rays["o"] = o.astype(np.float32)
+    rays["d"] = _unit64(focus - o)
+    return rays
 
 
 def load_renderer(path: str, seed: int = 1) -> PathTracer:

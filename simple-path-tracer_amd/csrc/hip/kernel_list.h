@@ -104,6 +104,23 @@
     X((k_shade_albedo<true, false>), SPT_ARGS_BOUNCE)                \
     X((k_shade_albedo<true, true>), SPT_ARGS_BOUNCE)
 
+// k_shade<kFeat, false, false, kTab, kGeoLds, false, kAux = true, RayAux>: bounce 0 of spt_radiance with auxiliary rays, the textured levels
+#define SPT_ARGS_BOUNCE_AUX (DScene, RenderCtx, uint32_t, RayAux)
+#define SPT_KERNELS_SHADE2X(X)                                                                \
+    X((k_shade<2, false, false, true, true, false, true, RayAux>), SPT_ARGS_BOUNCE_AUX)       \
+    X((k_shade<2, false, false, false, false, false, true, RayAux>), SPT_ARGS_BOUNCE_AUX)
+#define SPT_KERNELS_SHADE3X(X)                                                                \
+    X((k_shade<3, false, false, true, true, false, true, RayAux>), SPT_ARGS_BOUNCE_AUX)       \
+    X((k_shade<3, false, false, false, false, false, true, RayAux>), SPT_ARGS_BOUNCE_AUX)     \
+    X((k_shade<3, false, false, false, true, false, true, RayAux>), SPT_ARGS_BOUNCE_AUX)
+#define SPT_KERNELS_SHADE4X(X)                                                                \
+    X((k_shade<4, false, false, true, true, false, true, RayAux>), SPT_ARGS_BOUNCE_AUX)       \
+    X((k_shade<4, false, false, false, false, false, true, RayAux>), SPT_ARGS_BOUNCE_AUX)
+#define SPT_KERNELS_SHADE5X(X)                                                                \
+    X((k_shade<5, false, false, true, true, false, true, RayAux>), SPT_ARGS_BOUNCE_AUX)       \
+    X((k_shade<5, false, false, false, false, false, true, RayAux>), SPT_ARGS_BOUNCE_AUX)     \
+    X((k_shade<5, false, false, false, true, false, true, RayAux>), SPT_ARGS_BOUNCE_AUX)
+
 #if defined(SPT_INSTANTIATE_GROUP_PRIMARY)
 SPT_KERNELS_PRIMARY(SPT_DEFINE_KERNEL)
 #elif defined(SPT_INSTANTIATE_GROUP_RAYS)
@@ -128,6 +145,14 @@ SPT_KERNELS_SHADE5A(SPT_DEFINE_KERNEL)
 SPT_KERNELS_SHADE5B(SPT_DEFINE_KERNEL)
 #elif defined(SPT_INSTANTIATE_GROUP_ALBEDO)
 SPT_KERNELS_ALBEDO(SPT_DEFINE_KERNEL)
+#elif defined(SPT_INSTANTIATE_GROUP_SHADE2X)
+SPT_KERNELS_SHADE2X(SPT_DEFINE_KERNEL)
+#elif defined(SPT_INSTANTIATE_GROUP_SHADE3X)
+SPT_KERNELS_SHADE3X(SPT_DEFINE_KERNEL)
+#elif defined(SPT_INSTANTIATE_GROUP_SHADE4X)
+SPT_KERNELS_SHADE4X(SPT_DEFINE_KERNEL)
+#elif defined(SPT_INSTANTIATE_GROUP_SHADE5X)
+SPT_KERNELS_SHADE5X(SPT_DEFINE_KERNEL)
 #else
 SPT_KERNELS_PRIMARY(SPT_DECLARE_KERNEL)
 SPT_KERNELS_RAYS(SPT_DECLARE_KERNEL)
@@ -141,4 +166,8 @@ SPT_KERNELS_SHADE4(SPT_DECLARE_KERNEL)
 SPT_KERNELS_SHADE5A(SPT_DECLARE_KERNEL)
 SPT_KERNELS_SHADE5B(SPT_DECLARE_KERNEL)
 SPT_KERNELS_ALBEDO(SPT_DECLARE_KERNEL)
+SPT_KERNELS_SHADE2X(SPT_DECLARE_KERNEL)
+SPT_KERNELS_SHADE3X(SPT_DECLARE_KERNEL)
+SPT_KERNELS_SHADE4X(SPT_DECLARE_KERNEL)
+SPT_KERNELS_SHADE5X(SPT_DECLARE_KERNEL)
 #endif

@@ -495,9 +495,17 @@ SPT_DEV void rad_store(const RenderCtx& rc, uint32_t slot, f3 c) {
                              // MEASURED at 3 (168 VGPRs, 5 - 9 spilled): cfg4 shade_first 20.9 -> 19.5 ms, cfg5 10.9 -> 9.5.  The later-bounce instance
                              // (206 VGPRs) would spill 110 - 140 at 3 waves: cfg4 22.1 -> 24.5 ms, so it stays unbounded
 #endif
-template <int kFeat, bool kFirst, bool kFused = false, bool kTab = kFused, bool kGeoLds = kTab, bool kLoop = false>
-__global__ void __launch_bounds__(256, (kFeat == 0 && kFirst && kFused && SPT_SHADE0_WAVES) ? SPT_SHADE0_WAVES : ((kFeat == 3 || kFeat == 4) ? SPT_SHADE_HEAVY_WAVES : ((kFeat == 1 && kFirst && SPT_SHADE1_WAVES) ? SPT_SHADE1_WAVES : 1))) k_shade(DScene sc, RenderCtx rc, uint32_t bounce) {
+// kAux (spt_radiance on a textured scene, bounce 0 only): the vertices are the first hits of caller rays with full path records
+// (kFirst off), and the one extra argument names the rays' auxiliary rays, from which the hit's differentials are computed as
+// kFirst computes them from the camera's.  Without kAux there is no extra argument and the kernel's code stays what it was.
+struct RayAux {
+    const float4* rec;   // 4 float4 per ray of the pass (spt_ray_aux); a path's ray is its radiance slot modulo rc.n_pixels
+};
+template <int kFeat, bool kFirst, bool kFused = false, bool kTab = kFused, bool kGeoLds = kTab, bool kLoop = false, bool kAux = false, class... A>
+__global__ void __launch_bounds__(256, (kFeat == 0 && kFirst && kFused && SPT_SHADE0_WAVES) ? SPT_SHADE0_WAVES : ((kFeat == 3 || kFeat == 4) ? SPT_SHADE_HEAVY_WAVES : ((kFeat == 1 && kFirst && SPT_SHADE1_WAVES) ? SPT_SHADE1_WAVES : 1))) k_shade(DScene sc, RenderCtx rc, uint32_t bounce, A... aux_arg) {
     static_assert(!kLoop || (kFused && !kFirst), "the in-kernel bounce loop exists for the fused kernels of bounce >= 1");
+    static_assert(sizeof...(A) == (kAux ? 1u : 0u), "k_shade<..., kAux = true> takes the pass's RayAux, every other instance nothing more");
+    static_assert(!kAux || (kFeat >= 2 && !kFirst && !kFused), "auxiliary rays serve the un-fused textured levels, on full path records");
     // kFeat 3: Subsurface substrates (the probe), 4: position-normal distributions (the glint walks), 5: both
     constexpr bool kSimple = kFeat == 0, kTex = kFeat >= 2, kSubsurface = kFeat == 3 || kFeat == 5, kPndf = kFeat == 4 || kFeat == 5;
     const uint32_t shard = blockIdx.x % kShards;
@@ -652,6 +660,10 @@ __global__ void __launch_bounds__(256, (kFeat == 0 && kFirst && kFused && SPT_SH
             if (does_hit) {
                 it = reconstruct_hit<kTex, kTab>(sc, ray, h);
                 if (kTex && kFirst) calc_differential(it, ray, h.t, rc.cam.eye, aux_xd, rc.cam.eye, aux_yd);   // pt.rs:51-53
+                if constexpr (kAux) {   // the same from the caller's auxiliary rays
+                    const float4* const ar = (aux_arg, ...).rec + 4u * (size_t)(slot % rc.n_pixels);
+                    calc_differential(it, ray, h.t, mk3(ar[0]), mk3(ar[1]), mk3(ar[2]), mk3(ar[3]));
+                }
             }
 
             if (!kSimple && medium >= 0) {  // pt.rs:56-96

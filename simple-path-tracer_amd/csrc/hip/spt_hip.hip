@@ -22,6 +22,7 @@
 
 #include "kernel_list.h"   // the heavy kernel templates: declared here, compiled in inst_*.hip
 #include "film_kernels.h"
+#include "radiance_kernels.h"
 
 namespace {
 
@@ -545,6 +546,7 @@ struct BezierLib {
     decltype(&spt_denoise_image) denoise_image = nullptr;
     decltype(&spt_trace_closest) trace_closest = nullptr;
     decltype(&spt_trace_any) trace_any = nullptr;
+    decltype(&spt_radiance) radiance = nullptr;
     decltype(&spt_debug_bxdf) debug_bxdf = nullptr;
     decltype(&spt_debug_render_info) debug_render_info = nullptr;
     decltype(&spt_last_error) last_error = nullptr;
@@ -597,6 +599,11 @@ struct spt_scene {
     // filtered image and its bytes.  No render and no film touches them
     DeviceBuffer img_in[6], img_color[2], img_guide, img_albedo, img_out, img_out8;
     PinnedBuffer img_stage;
+    // spt_radiance's own buffers, made by its first call and reused: the rays (and auxiliary rays) of a pass on the device and the
+    // two page-locked slots they go up through, the results of a call with host pointers, and the events that say a slot's copy is done
+    DeviceBuffer ray_in, ray_aux_in, ray_rgb, ray_hits;
+    PinnedBuffer ray_stage[2];
+    hipEvent_t ev_ray[2] = {nullptr, nullptr};
     std::mutex mu;
     double bs_center[3] = {0, 0, 0}, bs_radius = 0;  // bounding sphere of all instance boxes
     double world_lo[3] = {0, 0, 0}, world_hi[3] = {0, 0, 0};   // their union
@@ -636,7 +643,7 @@ struct spt_scene {
         if (ev_join) (void)hipEventDestroy(ev_join);
         if (ev_out_ready) (void)hipEventDestroy(ev_out_ready);
         if (ev_copy_done) (void)hipEventDestroy(ev_copy_done);
-        for (auto e : {ev_main[0], ev_main[1], ev_film[0], ev_film[1], ev_film_idle, ev_keep[0], ev_keep[1]})
+        for (auto e : {ev_main[0], ev_main[1], ev_film[0], ev_film[1], ev_film_idle, ev_keep[0], ev_keep[1], ev_ray[0], ev_ray[1]})
             if (e) (void)hipEventDestroy(e);
         if (stream_film) (void)hipStreamDestroy(stream_film);
         if (stream2) (void)hipStreamDestroy(stream2);
@@ -916,7 +923,7 @@ const BezierLib* bezier_lib() {
                          sym(lib.film_read_buckets, "spt_film_read_buckets") && sym(lib.film_read_robust, "spt_film_read_robust") &&
                          sym(lib.film_read_rgb8, "spt_film_read_rgb8") && sym(lib.film_read_samples, "spt_film_read_samples") &&
                          sym(lib.denoise_image, "spt_denoise_image") &&
-                         sym(lib.trace_closest, "spt_trace_closest") && sym(lib.trace_any, "spt_trace_any") && sym(lib.debug_bxdf, "spt_debug_bxdf") &&
+                         sym(lib.trace_closest, "spt_trace_closest") && sym(lib.trace_any, "spt_trace_any") && sym(lib.radiance, "spt_radiance") && sym(lib.debug_bxdf, "spt_debug_bxdf") &&
                          sym(lib.debug_render_info, "spt_debug_render_info") &&
                          sym(lib.last_error, "spt_last_error") && sym(version, "spt_abi_version");
         if (!all || version() != SPT_ABI_VERSION) {
@@ -1608,6 +1615,8 @@ struct RenderRun {
     bool direct_out = false;     // k_finish_host may store into a pinned rgb_mean_out (no SPT_NO_DIRECT_OUT)
     uint32_t direct_grid = 0;    // ... over this many workgroups at the most (kFinishHostGrid, or SPT_DIRECT_OUT_GRID for A/B runs)
     bool debug_spans = false;    // per-launch HIP-event times on stderr (profile mode)
+    bool rays = false;           // spt_radiance: no camera, every bounce shaded from full path records (k_shade<., kFirst = false>)
+    const float4* ray_aux = nullptr;   // ... and the auxiliary rays of the pass for the bounce-0 launch of a textured scene (kAux); null: none
     bool albedo = false;         // SPT_RENDER_AOV_ALBEDO: paths end at their first surface, and the kernels get the scene without its environment
     bool env = false;            // the scene the kernels see has an environment
     uint32_t primary_chunks = 0;   // sample chunks per primary tile; 0: sized to the busy tiles
@@ -1660,7 +1669,7 @@ void run_setup(RenderRun& run) {
     run.lds = sc->lds_bytes;
     run.L = sc->lds_geo;
     // primary rays of an LDS-resident scene through the eye-relative copy of its geometry (eye.h), remade when the eye has moved
-    run.use_eye = run.L && !run.count && sc->eye_ok && std::getenv("SPT_NO_EYE_BLOB") == nullptr;
+    run.use_eye = !run.rays && run.L && !run.count && sc->eye_ok && std::getenv("SPT_NO_EYE_BLOB") == nullptr;
     if (run.use_eye && (!sc->eye_valid || std::memcmp(sc->eye_key, cam->eye, sizeof(sc->eye_key)) != 0)) make_eye_blob(sc, cam->eye);
     // refilling persistent waves for large scenes: on for shadow rays (any-hit walks end at very
     // different times: 10.9 -> 8.8 ms on the 1 M-triangle scene), off for extension rays (28 vs 20 ms)
@@ -1889,6 +1898,38 @@ uint32_t pass_samples_of(const spt_render_params& p, uint32_t n_pix, uint32_t n_
     return std::min(spp_pass, n_samples);   // (a film's increment: what is left of it)
 }
 
+// The path, hit and shadow queues and the pass counters of passes whose queue shards hold shard_cap entries (cap = kShards * shard_cap
+// in all), grown and bound into rc: what a window of pixels (grow_workspace) and a pass of caller rays (spt_radiance) share.
+// compact_first: the bounce-0 records are k_primary's compact ones, which sit at their hit's index in every class of the hit queue.
+// Returns the words of the pass counters.
+size_t grow_queues(spt_scene* sc, size_t cap, uint32_t shard_cap, uint32_t max_depth, bool fused, bool class_queues, bool compact_first, RenderCtx& rc) {
+    // the hit queue is binned by BxDF class for the general shade kernels (kernels.h, kClasses): class c lives c * cap
+    // entries further.  Memory is what MI355X has (24 B x cap x 8 classes = 26 GB for a 128 M-sample pass)
+    const uint32_t n_classes = (!fused && max_depth > 1 && cap * (uint64_t)kClasses <= 0xffffffffull && class_queues) ? kClasses : 1u;
+    for (int k = 0; k < 4; ++k) { grow(sc, sc->qa[k], cap * 16 * (k == 1 && compact_first ? n_classes : 1u)); grow(sc, sc->qb[k], cap * 16); }
+    grow(sc, sc->qa[4], cap * 8);
+    grow(sc, sc->qb[4], cap * 8);
+    grow(sc, sc->hit_f4, cap * 16 * n_classes);
+    grow(sc, sc->hit_inst, cap * 8 * n_classes);
+    if (fused) {
+        grow(sc, sc->hit_f4_next, cap * 16);
+        grow(sc, sc->hit_inst_next, cap * 8);
+    }
+    for (int k = 0; k < 3; ++k) grow(sc, sc->sh[k], cap * 16);
+    const size_t counts_words = (size_t)(max_depth + 1) * Q_KINDS * kShards * 32;
+    grow(sc, sc->counts[0], counts_words * sizeof(uint32_t));
+    rc.qa = PathQueue{sc->qa[0].as<float4>(), sc->qa[1].as<float4>(), sc->qa[2].as<float4>(), sc->qa[3].as<float4>(), sc->qa[4].as<uint2>()};
+    rc.qb = PathQueue{sc->qb[0].as<float4>(), sc->qb[1].as<float4>(), sc->qb[2].as<float4>(), sc->qb[3].as<float4>(), sc->qb[4].as<uint2>()};
+    rc.hits = HitQueue{sc->hit_f4.as<float4>(), sc->hit_inst.as<uint2>()};
+    rc.hits_next = HitQueue{sc->hit_f4_next.as<float4>(), sc->hit_inst_next.as<uint2>()};
+    rc.shadow = ShadowQueue{sc->sh[0].as<float4>(), sc->sh[1].as<float4>(), sc->sh[2].as<float4>()};
+    rc.counts = sc->counts[0].as<uint32_t>();
+    rc.shard_cap = shard_cap;
+    rc.n_classes = n_classes;
+    rc.class_cap = (uint32_t)cap;
+    return counts_words;
+}
+
 PassShape grow_workspace(spt_scene* sc, const spt_render_params& p, uint32_t n_samples, bool collect, bool fused, bool class_queues, float* sum,
                          bool own_rad, RenderCtx& rc) {
     const uint32_t n_pix = rc.n_pixels;
@@ -1911,35 +1952,12 @@ PassShape grow_workspace(spt_scene* sc, const spt_render_params& p, uint32_t n_s
     const size_t cap = (size_t)cap64;
     ps.rad_slots = (uint64_t)n_pix * (collect ? p.spp : ps.spp_pass);
 
-    // the hit queue is binned by BxDF class for the general shade kernels (kernels.h, kClasses): class c lives c * cap
-    // entries further.  Memory is what MI355X has (24 B x cap x 8 classes = 26 GB for a 128 M-sample pass)
-    const uint32_t n_classes = (!fused && p.max_depth > 1 && cap * (uint64_t)kClasses <= 0xffffffffull && class_queues) ? kClasses : 1u;
-    for (int k = 0; k < 4; ++k) { grow(sc, sc->qa[k], cap * 16 * (k == 1 ? n_classes : 1u)); grow(sc, sc->qb[k], cap * 16); }   // (qa[1]: the compact bounce-0 records sit at their hit's index, in every class)
-    grow(sc, sc->qa[4], cap * 8);
-    grow(sc, sc->qb[4], cap * 8);
-    grow(sc, sc->hit_f4, cap * 16 * n_classes);
-    grow(sc, sc->hit_inst, cap * 8 * n_classes);
-    if (fused) {
-        grow(sc, sc->hit_f4_next, cap * 16);
-        grow(sc, sc->hit_inst_next, cap * 8);
-    }
-    for (int k = 0; k < 3; ++k) grow(sc, sc->sh[k], cap * 16);
-    ps.counts_words = (size_t)(p.max_depth + 1) * Q_KINDS * kShards * 32;
-    grow(sc, sc->counts[0], ps.counts_words * sizeof(uint32_t));
+    ps.counts_words = grow_queues(sc, cap, (uint32_t)shard_cap64, p.max_depth, fused, class_queues, true, rc);
     if (!own_rad) grow(sc, sc->rad[0], (size_t)ps.rad_slots * 3 * sizeof(float));   // (own_rad: the passes write the caller's chunks, SampleTarget::keep)
     float* const film_sum = sum ? sum : (grow(sc, sc->film, (size_t)n_pix * 3 * sizeof(float)), sc->film.as<float>());
     grow(sc, sc->first_slot[0], (size_t)n_pix * sizeof(uint32_t));
     grow(sc, sc->slot_bits[0], (size_t)n_pix * ((ps.spp_pass + 7u) / 8u));
 
-    rc.qa = PathQueue{sc->qa[0].as<float4>(), sc->qa[1].as<float4>(), sc->qa[2].as<float4>(), sc->qa[3].as<float4>(), sc->qa[4].as<uint2>()};
-    rc.qb = PathQueue{sc->qb[0].as<float4>(), sc->qb[1].as<float4>(), sc->qb[2].as<float4>(), sc->qb[3].as<float4>(), sc->qb[4].as<uint2>()};
-    rc.hits = HitQueue{sc->hit_f4.as<float4>(), sc->hit_inst.as<uint2>()};
-    rc.hits_next = HitQueue{sc->hit_f4_next.as<float4>(), sc->hit_inst_next.as<uint2>()};
-    rc.shadow = ShadowQueue{sc->sh[0].as<float4>(), sc->sh[1].as<float4>(), sc->sh[2].as<float4>()};
-    rc.counts = sc->counts[0].as<uint32_t>();
-    rc.shard_cap = (uint32_t)shard_cap64;
-    rc.n_classes = n_classes;
-    rc.class_cap = (uint32_t)cap;
     rc.rad = sc->rad[0].as<float>();
     rc.film = film_sum;
     rc.first_slot = sc->first_slot[0].as<uint32_t>();
@@ -2115,13 +2133,30 @@ BounceFn shade_level(bool first, bool tab, bool geo_lds) {
 // The shade kernel of bounce b.  tail_loop: the fused kernel that takes bounce 1 and every later one in one launch.
 BounceFn shade_kernel(const RenderRun& run, uint32_t b, bool tail_loop) {
     const spt_scene* const sc = run.sc;
-    const bool first = b == 0;
+    const bool first = b == 0 && !run.rays;   // (caller rays: bounce 0 has full path records too, radiance_kernels.h)
     if (run.fused) return first ? k_shade<0, true, true, true, true> : tail_loop ? k_shade<0, false, true, true, true, true> : k_shade<0, false, true, true, true>;
     if (sc->simple) return shade_level<0>(first, run.tab, false);
     if (!sc->textured) return shade_level<1>(first, run.tab, false);
     if (!sc->subsurface) return shade_level<2>(first, run.tab, false);
     if (!sc->has_probe) return shade_level<4>(first, run.tab, false);   // glints only: no probe, so the geometry's place does not matter
     return sc->has_pndf ? shade_level<5>(first, run.tab, run.L) : shade_level<3>(first, run.tab, run.L);
+}
+
+// k_shade<kFeat, false, false, kTab, kGeoLds, false, kAux = true>: bounce 0 of spt_radiance with auxiliary rays on a textured scene, chosen
+// as shade_level / shade_kernel choose the plain instances
+using BounceAuxFn = void (*)(DScene, RenderCtx, uint32_t, RayAux);
+template <int kFeat>
+BounceAuxFn shade_aux_level(bool tab, bool geo_lds) {
+    if (tab) return k_shade<kFeat, false, false, true, true, false, true, RayAux>;
+    if constexpr (kFeat == 3 || kFeat == 5)
+        if (geo_lds) return k_shade<kFeat, false, false, false, true, false, true, RayAux>;
+    return k_shade<kFeat, false, false, false, false, false, true, RayAux>;
+}
+BounceAuxFn shade_aux_kernel(const RenderRun& run) {
+    const spt_scene* const sc = run.sc;
+    if (!sc->subsurface) return shade_aux_level<2>(run.tab, false);
+    if (!sc->has_probe) return shade_aux_level<4>(run.tab, false);
+    return sc->has_pndf ? shade_aux_level<5>(run.tab, run.L) : shade_aux_level<3>(run.tab, run.L);
 }
 
 // The shadow or the extension rays of a bounce: the kernels of one ray kind, [kCount] where visit counting makes two
@@ -2178,7 +2213,10 @@ bool bounce(RenderRun& run, const RenderCtx& rc, uint32_t b, hipStream_t st) {
         run.end();
         return false;
     }
-    hipLaunchKernelGGL(shade_kernel(run, b, tail_loop), dim3(kPersistentBlocks), dim3(kBlock), shade_lds, st, sc->d, ru, b);
+    if (run.ray_aux != nullptr && b == 0u && sc->textured && !sc->simple && !run.fused)
+        hipLaunchKernelGGL(shade_aux_kernel(run), dim3(kPersistentBlocks), dim3(kBlock), shade_lds, st, sc->d, ru, b, RayAux{run.ray_aux});
+    else
+        hipLaunchKernelGGL(shade_kernel(run, b, tail_loop), dim3(kPersistentBlocks), dim3(kBlock), shade_lds, st, sc->d, ru, b);
     run.end();
     if (run.fused) return tail_loop;
     // k_shadow(b) and k_extend(b) are independent unless the scene has an environment (then a missing
@@ -3386,6 +3424,179 @@ static spt_status trace_common(const spt_scene* scene_c, uint32_t n, const spt_r
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipMemcpyAsync(out, sc->trace_out.p, (size_t)n * out_elem, hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
+        return SPT_OK;
+    });
+}
+
+// ---- radiance along caller rays (spt_radiance) ----
+// The queues, counters and radiance slots of a pass of n rays x reps repetitions, grown and bound into rc as grow_workspace does for
+// a window of pixels.  A queue shard holds what the intake workgroups mapped to it can append (radiance_kernels.h).
+static size_t grow_ray_workspace(spt_scene* sc, uint32_t n, uint32_t reps, uint32_t max_depth, bool fused, bool class_queues, RenderCtx& rc) {
+    const uint64_t blocks = ((uint64_t)n + kBlock - 1) / kBlock, per_shard = (blocks + kShards - 1) / kShards;
+    const uint64_t shard_cap64 = per_shard * kBlock * std::max(reps, 1u), cap64 = shard_cap64 * kShards;
+    if (cap64 > 0x7fffffffull) fail(SPT_ERR_UNSUPPORTED, "radiance: pass too large (lower rays_per_pass)");
+    const size_t counts_words = grow_queues(sc, (size_t)cap64, (uint32_t)shard_cap64, max_depth, fused, class_queues, false, rc);
+    grow(sc, sc->rad[0], (size_t)n * std::max(reps, 1u) * 3 * sizeof(float));
+    rc.rad = sc->rad[0].as<float>();
+    return counts_words;
+}
+
+// `p` is device memory on the scene's device, aligned to 16 bytes where `align16` (records loaded as float4), else to 4
+static void check_device_pointer(const spt_scene* sc, const void* p, const char* what, bool align16) {
+    hipPointerAttribute_t at;
+    std::memset(&at, 0, sizeof at);
+    const hipError_t e = hipPointerGetAttributes(&at, p);
+    if (e != hipSuccess) (void)hipGetLastError();
+    if (e != hipSuccess || at.type != hipMemoryTypeDevice || at.device != sc->device)
+        fail(SPT_ERR_INVALID_ARG, std::string("radiance: SPT_RADIANCE_DEVICE_POINTERS and `") + what + "` is not device memory on the scene's device");
+    if ((reinterpret_cast<uintptr_t>(p) & (align16 ? 15u : 3u)) != 0)
+        fail(SPT_ERR_INVALID_ARG, std::string("radiance: device pointer `") + what + "` is not " + (align16 ? "16" : "4") + "-byte aligned");
+}
+
+spt_status spt_radiance(const spt_scene* scene_c, const spt_radiance_job* job) {
+    if (!scene_c || !job) { g_error = "radiance: null argument"; return SPT_ERR_INVALID_ARG; }
+    if (job->size < sizeof(spt_radiance_job)) { g_error = "radiance: job->size is below sizeof(spt_radiance_job)"; return SPT_ERR_INVALID_ARG; }
+    if (job->flags & ~(uint32_t)SPT_RADIANCE_DEVICE_POINTERS) { g_error = "radiance: unknown flags"; return SPT_ERR_INVALID_ARG; }
+    if (job->repeats == 0) { g_error = "radiance: repeats must be >= 1"; return SPT_ERR_INVALID_ARG; }
+    if (job->n_rays != 0 && (!job->rays || !job->rgb_out)) { g_error = "radiance: null rays or rgb_out"; return SPT_ERR_INVALID_ARG; }
+    if (job->max_depth > 255) { g_error = "radiance: max_depth > 255"; return SPT_ERR_UNSUPPORTED; }
+    spt_scene* sc = const_cast<spt_scene*>(scene_c);
+    if (sc->fwd) return forwarded(sc->fwd, sc->fwd->radiance(sc->inner, job));
+    if (job->n_rays == 0) return SPT_OK;
+    std::lock_guard<std::mutex> lock(sc->mu);
+    return guarded("radiance", [&] {
+        const uint64_t n_rays = job->n_rays;
+        const uint32_t S = job->repeats;
+        const bool dev = (job->flags & SPT_RADIANCE_DEVICE_POINTERS) != 0;
+        const bool want_hits = job->hits_out != nullptr;
+        if (n_rays > (1ull << 40)) fail(SPT_ERR_UNSUPPORTED, "radiance: more than 2^40 rays");
+        HIP_CHECK(hipSetDevice(sc->device));
+        if (dev) {   // every check comes before the first allocation, copy or launch
+            check_device_pointer(sc, job->rays, "rays", true);
+            if (job->aux) check_device_pointer(sc, job->aux, "aux", true);
+            check_device_pointer(sc, job->rgb_out, "rgb_out", false);
+            if (want_hits) check_device_pointer(sc, job->hits_out, "hits_out", false);
+        }
+        film_join(sc);
+        spt_render_params plan{};      // what run_setup and bounce read of a plan
+        plan.max_depth = job->max_depth;
+        const spt_camera no_camera{};
+        RenderRun run;
+        run.sc = sc;
+        run.cam = &no_camera;
+        run.params = &plan;
+        run.rays = true;
+        run_setup(run);
+        const hipStream_t st = run.st;
+        // auxiliary rays are read by the textured shade levels only
+        const bool use_aux = job->aux != nullptr && sc->textured && !sc->simple && !run.fused && job->max_depth > 0;
+
+        // Passes of P rays x chunks of R repetitions, around 2^22 paths each.  A shard's capacity comes in steps of kShards * kBlock
+        // rays, so the default P is a multiple of that
+        constexpr uint64_t kStep = (uint64_t)kShards * kBlock, kTargetPaths = 1ull << 22;
+        uint64_t P64 = job->rays_per_pass ? job->rays_per_pass : std::max(kStep, kTargetPaths / S / kStep * kStep);
+        P64 = std::min(P64, n_rays);
+        const uint32_t P = (uint32_t)P64;
+        const uint64_t P_up = (P64 + kStep - 1) / kStep * kStep;
+        const uint32_t R = (uint32_t)std::min<uint64_t>(S, std::max<uint64_t>(1, 2 * kTargetPaths / P_up));
+        if (P_up * R > 0x7fffffffull) fail(SPT_ERR_UNSUPPORTED, "radiance: pass too large (lower rays_per_pass)");
+
+        RenderCtx rc{};
+        rc.max_depth = job->max_depth;
+        rc.seed = job->seed;
+        rc.spp = S;
+        const size_t counts_words = grow_ray_workspace(sc, P, job->max_depth ? R : 0u, job->max_depth, run.fused, run.class_queues, rc);
+        rc.dyn_refill_below = run.dyn_refill_below;
+        rc.dyn_steps = run.dyn_steps;
+        rc.stream_rounds = run.stream_rounds;
+        rc.stream_refill_below = run.stream_refill_below;
+        rc.visits = sc->visits.as<unsigned long long>();
+        float* rgb_dev = job->rgb_out;
+        spt_hit* hits_dev = job->hits_out;
+        if (!dev) {
+            const size_t in_bytes = (size_t)P * sizeof(spt_path_ray), aux_bytes = use_aux ? (size_t)P * sizeof(spt_ray_aux) : 0;
+            for (int k = 0; k < 2; ++k) {
+                sc->ray_stage[k].ensure(in_bytes + aux_bytes);
+                if (!sc->ev_ray[k]) HIP_CHECK(hipEventCreateWithFlags(&sc->ev_ray[k], hipEventDisableTiming));
+            }
+            sc->ray_in.ensure(in_bytes);
+            if (use_aux) sc->ray_aux_in.ensure(aux_bytes);
+            sc->ray_rgb.ensure((size_t)n_rays * 3 * sizeof(float));
+            if (want_hits) sc->ray_hits.ensure((size_t)n_rays * sizeof(spt_hit));
+            rgb_dev = sc->ray_rgb.as<float>();
+            hits_dev = want_hits ? sc->ray_hits.as<spt_hit>() : nullptr;
+        }
+        const bool stream = sc->swalk && !sc->lds_geo;   // the walkers of spt_trace_closest
+        const float inv = 1.0f / (float)S;
+        uint64_t pass = 0;
+        for (uint64_t r0 = 0; r0 < n_rays; r0 += P, ++pass) {
+            const uint32_t n = (uint32_t)std::min<uint64_t>(P, n_rays - r0);
+            RayJob rj{};
+            rj.seed = job->seed;
+            rj.n = n;
+            rj.rng_skip = job->rng_skip;
+            rj.rgb_out = rgb_dev + 3 * r0;
+            const float4* aux_dev = nullptr;
+            if (dev) {
+                rj.rays = reinterpret_cast<const float4*>(job->rays + r0);
+                if (use_aux) aux_dev = reinterpret_cast<const float4*>(job->aux + r0);
+            } else {
+                // the slot's previous copy (two passes ago) has left it; the host checks and fills it beside the pass in flight
+                PinnedBuffer& slot = sc->ray_stage[pass & 1u];
+                if (pass >= 2) HIP_CHECK(hipEventSynchronize(sc->ev_ray[pass & 1u]));
+                spt_path_ray* const dst = static_cast<spt_path_ray*>(slot.p);
+                const spt_path_ray* const src = job->rays + r0;
+                for (uint32_t i = 0; i < n; ++i) {
+                    const spt_path_ray& r = src[i];
+                    const bool finite = std::isfinite(r.o[0]) && std::isfinite(r.o[1]) && std::isfinite(r.o[2]) && std::isfinite(r.d[0]) &&
+                                        std::isfinite(r.d[1]) && std::isfinite(r.d[2]) && std::isfinite(r.t_min);
+                    if (!finite || (r.d[0] == 0.0f && r.d[1] == 0.0f && r.d[2] == 0.0f)) {
+                        HIP_CHECK(hipStreamSynchronize(st));   // the earlier passes wrote the library's own buffers only
+                        fail(SPT_ERR_INVALID_ARG, "radiance: ray " + std::to_string(r0 + i) + (finite ? " has an all-zero direction" : " has a non-finite o, d or t_min"));
+                    }
+                    dst[i] = r;
+                }
+                const size_t in_bytes = (size_t)n * sizeof(spt_path_ray);
+                HIP_CHECK(hipMemcpyAsync(sc->ray_in.p, slot.p, in_bytes, hipMemcpyHostToDevice, st));
+                if (use_aux) {
+                    char* const aux_slot = static_cast<char*>(slot.p) + (size_t)P * sizeof(spt_path_ray);
+                    std::memcpy(aux_slot, job->aux + r0, (size_t)n * sizeof(spt_ray_aux));
+                    HIP_CHECK(hipMemcpyAsync(sc->ray_aux_in.p, aux_slot, (size_t)n * sizeof(spt_ray_aux), hipMemcpyHostToDevice, st));
+                    aux_dev = sc->ray_aux_in.as<float4>();
+                }
+                HIP_CHECK(hipEventRecord(sc->ev_ray[pass & 1u], st));
+                rj.rays = sc->ray_in.as<float4>();
+            }
+            run.ray_aux = aux_dev;
+            rc.n_pixels = n;
+            const dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
+            // max_depth 0: `while curr_depth < self.max_depth` (pt.rs:48) never runs, every path is 0; the intake still reports the hits
+            const uint32_t k_end = job->max_depth ? S : 0u;
+            for (uint64_t k0 = 0; k0 == 0u || k0 < k_end; k0 += R) {
+                rj.k_first = (uint32_t)k0;
+                rj.reps = (uint32_t)std::min<uint64_t>(R, k_end - std::min<uint64_t>(k0, k_end));
+                rj.hits_out = (k0 == 0u && hits_dev) ? hits_dev + r0 : nullptr;
+                rc.pass_first = (uint32_t)k0;
+                rc.pass_samples = rj.reps;
+                rc.rad_plane = (size_t)std::max(rj.reps, 1u) * n;
+                if (rj.reps != 0u || rj.hits_out != nullptr) {
+                    HIP_CHECK(hipMemsetAsync(rc.counts, 0, counts_words * sizeof(uint32_t), st));
+                    hipLaunchKernelGGL(stream ? k_ray_intake_stream : sc->lds_geo ? k_ray_intake<true> : k_ray_intake<false>, grid, block, sc->lds_bytes, st,
+                                       sc->d, rc, rj);
+                    HIP_CHECK(hipGetLastError());
+                }
+                for (uint32_t b = 0; b < (rj.reps ? job->max_depth : 0u); ++b)
+                    if (bounce(run, rc, b, st)) break;
+                hipLaunchKernelGGL(k_ray_finish, grid, block, 0, st, rc, rj, k0 == 0u ? 1u : 0u, k0 + R >= k_end ? 1u : 0u, inv);
+                HIP_CHECK(hipGetLastError());
+            }
+        }
+        if (!dev) {   // the device-to-host path of the film read-outs
+            if (want_hits) HIP_CHECK(hipMemcpyAsync(job->hits_out, sc->ray_hits.p, (size_t)n_rays * sizeof(spt_hit), hipMemcpyDeviceToHost, st));
+            deliver(sc->img_out8, sc->ray_rgb.p, (size_t)n_rays * 3, FilmReadOut{job->rgb_out, nullptr}, st);
+        } else {
+            HIP_CHECK(hipStreamSynchronize(st));
+        }
         return SPT_OK;
     });
 }

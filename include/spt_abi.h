@@ -499,6 +499,50 @@ void spt_film_destroy(spt_film* film);   /* before spt_scene_destroy of its scen
  * SPT_ERR_OUT_OF_MEMORY: an increment whose store cannot be allocated; done does not advance. */
 spt_status spt_film_read_samples(spt_film* film, uint32_t first, uint32_t count, float* out);
 
+/* ---- reconstruction filters of a sample-keeping film (additive to ABI v14: detect it by symbol) -----------------------------------
+ * spt_film_filter chooses the filter of later spt_film_read(SPT_FILM_MEAN | SPT_FILM_SUM) and spt_film_read_rgb8(SPT_READ_MEAN)
+ * calls on a film created with SPT_FILM_KEEP_SAMPLES.  It may be called at any time, any number of times; it launches nothing and
+ * changes nothing of what the film keeps (done, the kept samples and spt_film_read_samples stay as they are).  SPT_FILTER_BOX
+ * restores the state after spt_film_create, the reference's box at the plan's radius (radius, p0, p1 ignored); a film that never
+ * calls spt_film_filter is read exactly as described above.
+ * The plan's filter_radius still decides the stored halo, R = ceil(radius_plan - 0.5) rows.  A filter of support radius r needs
+ * Rf = max(ceil(r - 0.5), 0) <= max(R, 0); because every copy of a row has the same bits, a film of a wider plan read under a
+ * filter has the bits of a film whose plan radius is r.
+ * The weighted read-out, every step one rounded f32 operation, no contraction, in this order:
+ *     color = 0; wsum = 0
+ *     for dj = -Rf .. Rf, for di = -Rf .. Rf (pixels outside the image skipped), for that pixel's covered samples in increasing
+ *     plan index:
+ *         ax = |(float)di + (ox - 0.5f)|;  ay = |(float)dj + (oy - 0.5f)|     (ox, oy: the sample's pixel offset, as the box derives it)
+ *         skipped unless ax <= r and ay <= r
+ *         w = f(ax) * f(ay);   skipped when w == 0.0f
+ *         color.c = color.c + w * x.c   (c = r, g, b);   wsum = wsum + w
+ *     SPT_FILM_SUM = color;   SPT_FILM_MEAN = color * (1.0f / wsum)
+ *   TENT      f(a) = r - a
+ *   GAUSSIAN  e_r = spt_exp(-(alpha * (r * r)));  g = spt_exp(-(alpha * (a * a))) - e_r;  f(a) = g < 0 ? 0 : g
+ *             (spt_exp of spt_detmath.h)
+ *   MITCHELL  t = (2.0f * a) / r, in [0, 2].  Seven coefficients are made once on the host: B and C widened to double, each
+ *             expression below evaluated in double as written, left to right, and rounded once to f32.
+ *               t > 1:      c3 = (-B - 6*C) / 6;  c2 = (6*B + 30*C) / 6;  c1 = (-12*B - 48*C) / 6;  c0 = (8*B + 24*C) / 6
+ *                           f = ((c3 * t + c2) * t + c1) * t + c0
+ *               otherwise:  q3 = (12 - 9*B - 6*C) / 6;  q2 = (-18 + 12*B + 6*C) / 6;  q0 = (6 - 2*B) / 6
+ *                           f = ((q3 * t + q2) * t) * t + q0
+ *             Negative lobes are kept: w may be negative.
+ * Unlike the box, a sample outside the support, or one of weight 0, enters neither sum: a non-finite sample spoils only the pixels
+ * whose support it lies in.
+ * Refusals leave the film and its current filter as they were, all SPT_ERR_INVALID_ARG: a null film or desc; desc->size below
+ * sizeof(spt_filter_desc); an unknown type; a film without SPT_FILM_KEEP_SAMPLES; for the types other than the box: r not finite
+ * or <= 0, Rf above the film's stored halo (the message names the plan radius that would do), GAUSSIAN with alpha not finite or
+ * <= 0, MITCHELL with B or C not finite.  Takes the scene's lock. */
+enum { SPT_FILTER_BOX = 0, SPT_FILTER_TENT = 1, SPT_FILTER_GAUSSIAN = 2, SPT_FILTER_MITCHELL = 3 };
+typedef struct spt_filter_desc {
+    uint32_t size;     /* sizeof(spt_filter_desc) as the caller was compiled; the struct only grows at its tail */
+    uint32_t type;     /* SPT_FILTER_* */
+    float radius;      /* support radius r, in pixels */
+    float p0, p1;      /* GAUSSIAN: p0 = alpha.  MITCHELL: p0 = B, p1 = C.  Otherwise ignored */
+    uint32_t pad;
+} spt_filter_desc;     /* 24 B */
+spt_status spt_film_filter(spt_film* film, const spt_filter_desc* desc);
+
 /* ---- adaptive sampling of a film (additive to ABI v14: detect it by symbol) -------------------------------------------------
  * spt_film_adapt, called between increments, RETIRES every still-active pixel whose error estimate meets the tolerance; a
  * retired pixel stays retired.  Later spt_film_render calls trace only the active pixels; a retired pixel keeps its S, its Q and

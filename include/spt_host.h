@@ -48,6 +48,14 @@ spt_status spt_host_scene_set_bezier_newton(spt_host_scene* scene, int32_t newto
  * and the box-filter radius. */
 spt_status spt_host_load_renderer(const char* renderer_json_path, spt_render_params* params,
                                   float* filter_radius);
+/* spt_host_load_renderer that also takes the weighted filters of spt_film_filter (spt_abi.h), which the function above refuses
+ * as unknown types.  "filter" is one of
+ *     {"type": "box", "radius": r}      {"type": "gaussian", "radius": r, "alpha": a}          alpha optional, 2.0
+ *     {"type": "tent", "radius": r}     {"type": "mitchell", "radius": r, "b": B, "c": C}      radius optional, 2.0; b, c 1/3
+ * (numbers are floats: an integer literal is a schema error).  *filter receives the desc to hand to spt_film_filter;
+ * params->filter_radius is r, with SPT_RENDER_BOX_RADIUS when r != 0.5: the halo a sample-keeping film stores. */
+spt_status spt_host_load_renderer_filter(const char* renderer_json_path, spt_render_params* params,
+                                         spt_filter_desc* filter);
 
 /* u8 = (clamp(c*255, 0, 255)) as u8 — truncation, no gamma (src/core/film.rs:94-99). */
 void spt_host_film_to_rgb8(const float* rgb_mean, uint64_t n_pixels, uint8_t* rgb8_out);

@@ -188,6 +188,7 @@ READ_SOURCES = {"mean": 0, "mon": 1, "gmon": 2, "denoised": 3}   # SPT_READ_* of
 FILM_MOMENTS = 1          # spt_film_create: also keep the per-channel sum of squared sample radiance (ABI v14)
 FILM_KEEP_SAMPLES = 2     # spt_film_create: keep every sample's radiance (any box radius; spt_film_read_samples)
 FILM_MEAN, FILM_SUM, FILM_SUM_SQ, FILM_VAR_OF_MEAN = 0, 1, 2, 3   # spt_film_read
+FILTER_TYPES = {"box": 0, "tent": 1, "gaussian": 2, "mitchell": 3}   # SPT_FILTER_* of spt_film_filter
 ROBUST_MON, ROBUST_GMON = 0, 1   # spt_film_read_robust: median of the bucket means, Gini-adaptive trimmed mean of them
 N_KERNELS = 7
 KERNEL_NAMES = ("primary", "shade", "shadow", "extend", "resolve", "other", "shade_first")
@@ -199,6 +200,24 @@ class RenderParams(C.Structure):
                 ("seed", C.c_uint64), ("shard_index", C.c_uint32), ("shard_count", C.c_uint32),
                 ("strip_rows", C.c_uint32), ("samples_per_pass", C.c_uint32), ("flags", C.c_uint32),
                 ("out_strip_stride", C.c_uint64), ("filter_radius", C.c_float), ("stats_size", C.c_uint32)]
+
+
+class FilterDesc(C.Structure):
+    """spt_filter_desc (spt_film_filter): p0 is the Gaussian's alpha or Mitchell's B, p1 Mitchell's C."""
+    _fields_ = [("size", C.c_uint32), ("type", C.c_uint32), ("radius", C.c_float), ("p0", C.c_float), ("p1", C.c_float), ("pad", C.c_uint32)]
+
+
+def filter_desc(kind: str, radius: Optional[float] = None, alpha: float = 2.0, b: float = 1.0 / 3.0, c: float = 1.0 / 3.0) -> FilterDesc:
+    """The FilterDesc of a filter by name ("box", "tent", "gaussian", "mitchell") with the renderer file's defaults: alpha 2,
+    b = c = 1/3, Mitchell's radius 2."""
+    if kind not in FILTER_TYPES:
+        raise ValueError("filter: kind is one of %s, not %r" % (", ".join(repr(k) for k in FILTER_TYPES), kind))
+    if radius is None:
+        if kind in ("tent", "gaussian"):
+            raise ValueError("filter: %r needs a radius" % (kind,))
+        radius = 2.0 if kind == "mitchell" else 0.0   # (the box ignores it)
+    p0, p1 = (alpha, 0.0) if kind == "gaussian" else (b, c) if kind == "mitchell" else (0.0, 0.0)
+    return FilterDesc(C.sizeof(FilterDesc), FILTER_TYPES[kind], radius, p0, p1, 0)
 
 
 class RenderStats(C.Structure):
@@ -301,6 +320,8 @@ def host_lib() -> C.CDLL:
         lib.spt_host_scene_free.argtypes = [C.c_void_p]
         lib.spt_host_scene_free.restype = None
         lib.spt_host_load_renderer.argtypes = [C.c_char_p, C.POINTER(RenderParams), C.POINTER(C.c_float)]
+        if hasattr(lib, "spt_host_load_renderer_filter"):   # (a library built before the weighted filters lacks it)
+            lib.spt_host_load_renderer_filter.argtypes = [C.c_char_p, C.POINTER(RenderParams), C.POINTER(FilterDesc)]
         lib.spt_host_film_to_rgb8.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
         lib.spt_host_film_to_rgb8.restype = None
         lib.spt_host_write_png.argtypes = [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32]
@@ -362,6 +383,8 @@ def hip_lib() -> C.CDLL:
         if hasattr(lib, "spt_film_read_rgb8"):   # (the same)
             lib.spt_film_read_rgb8.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p]
             lib.spt_debug_pack_rgb8.argtypes = [C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]
+        if hasattr(lib, "spt_film_filter"):   # (the same)
+            lib.spt_film_filter.argtypes = [C.c_void_p, C.POINTER(FilterDesc)]
         if hasattr(lib, "spt_film_read_samples"):   # (the same)
             lib.spt_film_read_samples.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         if hasattr(lib, "spt_denoise_image"):   # (the same)
@@ -593,13 +616,20 @@ class PathTracer:
 
     def __init__(self, max_depth: int = 8, sampler: int = SAMPLER_RECURRENCE, spp: int = 256,
                  division_x: int = 0, division_y: int = 0, filter_radius: float = 0.5, seed: int = 1, debug_normal: bool = False,
-                 aov_albedo: bool = False):
+                 aov_albedo: bool = False, filter_type: str = "box", filter_params: Optional[dict] = None):
         self.max_depth = max_depth
         self.sampler = sampler
         self.spp = spp
         self.division_x = division_x
         self.division_y = division_y
         self.filter_radius = filter_radius
+        # the reconstruction filter: "box" (the reference's, at filter_radius) or a weighted one of spt_film_filter ("tent",
+        # "gaussian", "mitchell") with support radius filter_radius and filter_params (alpha / b, c).  A weighted filter is served
+        # by films that keep their samples: progressive(keep_samples=True) and render_shard
+        if filter_type not in FILTER_TYPES:
+            raise ValueError("PathTracer: filter_type is one of %s, not %r" % (", ".join(repr(k) for k in FILTER_TYPES), filter_type))
+        self.filter_type = filter_type
+        self.filter_params = dict(filter_params or {})
         self.seed = seed
         self.debug_normal = debug_normal   # a build of the reference with `--features debug_normal`: colour = normal * 0.5 + 0.5
         self.aov_albedo = aov_albedo       # RENDER_AOV_ALBEDO: colour = the albedo of the first surface (not together with debug_normal)
@@ -607,6 +637,9 @@ class PathTracer:
 
     def params(self, width: int, height: int, shard_index: int = 0, shard_count: int = 1, strip_rows: int = 16,
                samples_per_pass: int = 0, flags: int = 0) -> RenderParams:
+        """The plan of a shard.  It carries filter_radius only: a weighted filter_type is no field of spt_render_params, it is
+        applied by spt_film_filter to a sample-keeping film of this plan, so whoever hands the plan to spt_render refuses a
+        weighted filter first (render_shard goes through such a film, MultiDevice.render raises)."""
         p = RenderParams()
         p.width, p.height, p.spp, p.max_depth = width, height, self.spp, self.max_depth
         p.sampler, p.division_x, p.division_y = self.sampler, self.division_x, self.division_y
@@ -631,7 +664,17 @@ class PathTracer:
         with the same shape overwrites (no per-call allocation, DMA-speed copy-out).
         count_visits=True runs the counting instantiations of the traversal kernels (last_stats.node_visits, ...).
         wait=False (SPT_RENDER_ASYNC): returns once the work is queued; the returned buffer is valid after `self.wait(scene)`
-        or after a later wait=True call on the scene; no stats (last_stats keeps the previous synchronous call's)."""
+        or after a later wait=True call on the scene; no stats (last_stats keeps the previous synchronous call's).
+        With a weighted filter_type the shard is rendered through a sample-keeping film (one increment, one read-out): film=,
+        wait=False, profile and count_visits are refused (SptError), reuse_output is ignored (the result is a fresh array, not
+        the scene's pinned buffer) and last_stats is left as it was."""
+        if self.filter_type != "box":
+            # a weighted filter reads kept samples: one sample-keeping film, one increment, one read-out
+            if film is not None or not wait or profile or count_visits:
+                raise SptError(2, "render_shard: a %s filter renders through a sample-keeping film, which takes no film=, wait=False, "
+                                  "profile or count_visits" % self.filter_type)
+            with self.progressive(scene, config, device, 0, False, shard_index, shard_count, strip_rows, samples_per_pass, keep_samples=True) as pf:
+                return pf.render(self.spp).mean()
         ds = scene.device_scene(device)
         cam = scene.get_camera(config.used_camera_name)
         p = self.params(config.width, config.height, shard_index, shard_count, strip_rows, samples_per_pass,
@@ -673,7 +716,8 @@ class PathTracer:
         `flags` are extra SPT_RENDER_* bits of the plan.  buckets=K (odd, 3 .. 15) also keeps K bucket sums per pixel (sample s of
         the plan goes to bucket s % K) for bucket_sums() and robust_mean().  keep_samples=True keeps every sample's radiance
         instead of running sums (FILM_KEEP_SAMPLES): the film then takes a box radius that reaches neighbouring pixels, kept()
-        returns the samples, and moments, buckets, adapt and denoise are refused."""
+        returns the samples, and moments, buckets, adapt and denoise are refused.  Such a film is read under this renderer's
+        filter_type (ProgressiveFilm.set_filter changes it later); without keep_samples a weighted filter is refused."""
         return ProgressiveFilm(self, scene, config, device, first_sample, moments, shard_index, shard_count, strip_rows,
                                samples_per_pass, flags, keep_samples=keep_samples, buckets=buckets)
 
@@ -708,6 +752,8 @@ class ProgressiveFilm:
                  moments: bool = False, shard_index: int = 0, shard_count: int = 1, strip_rows: int = 16,
                  samples_per_pass: int = 0, flags: int = 0, keep_samples: bool = False, buckets: int = 0):
         self._h = C.c_void_p()
+        if renderer.filter_type != "box" and not keep_samples:
+            raise SptError(1, "a %s filter needs a film that keeps its samples (keep_samples=True)" % renderer.filter_type)
         self._ds = scene.device_scene(device)
         self.scene = scene
         self.first_sample = first_sample
@@ -723,6 +769,23 @@ class ProgressiveFilm:
         self.n_buckets = 0
         if buckets:
             self.set_buckets(buckets)
+        if renderer.filter_type != "box":
+            try:
+                self.set_filter(renderer.filter_type, radius=renderer.filter_radius, **renderer.filter_params)
+            except Exception:
+                self.close()
+                raise
+
+    def set_filter(self, kind: str, radius: Optional[float] = None, alpha: float = 2.0, b: float = 1.0 / 3.0, c: float = 1.0 / 3.0) -> None:
+        """spt_film_filter: the reconstruction filter of later mean(), sum() and read_rgb8("mean") calls of a keep_samples=True
+        film: "tent" and "gaussian" (alpha) of support `radius`, "mitchell" (b, c; radius 2 by default), or "box", which
+        restores the reference's box at the plan's radius.  Nothing is traced again; the radius may not reach past the halo rows
+        the plan's filter_radius made the film store (SptError, and the film keeps its filter)."""
+        lib = hip_lib()
+        if not hasattr(lib, "spt_film_filter"):
+            raise SptError(2, "libspt_hip.so does not export spt_film_filter")
+        desc = filter_desc(kind, radius, alpha, b, c)
+        _check_hip(lib.spt_film_filter(self._handle(), C.byref(desc)))
 
     def set_buckets(self, n_buckets: int) -> None:
         """spt_film_buckets: K = n_buckets bucket sums per pixel (K odd, 3 .. 15) from the film's first sample on.  What the
@@ -968,6 +1031,8 @@ class MultiFilm:
         self.width, self.height = config.width, config.height
         self.n_buckets = buckets
         self._api = film_api if film_api is not None else hip_device_film_api()
+        if renderer.filter_type != "box":   # (spt_device_film_api has no entry for spt_film_filter)
+            raise SptError(2, "films over several devices are read under the box filter only, not %r" % (renderer.filter_type,))
         cam = multi.scene.get_camera(config.used_camera_name)
         p = renderer.params(config.width, config.height, 0, 1, 16, 0, flags)
         _check_host(host_lib().spt_host_multi_film_create(multi._h, C.byref(self._api), C.byref(cam), C.byref(p), strip_rows, first_sample,
@@ -1085,7 +1150,11 @@ class MultiDevice:
 
     def render(self, renderer: "PathTracer", config: OutputConfig, strip_rows: int = 0, film: Optional[np.ndarray] = None,
                samples_per_pass: int = 0) -> np.ndarray:
-        """RendererT::render over all devices: the (H, W, 3) f32 film (a caller-owned `film` is filled in place)."""
+        """RendererT::render over all devices: the (H, W, 3) f32 film (a caller-owned `film` is filled in place).  A renderer
+        with a weighted filter_type is refused (SptError): spt_render knows the box only, and the plan carries just the radius."""
+        if renderer.filter_type != "box":   # (params() would hand spt_render the reference's box at the filter's radius)
+            raise SptError(4, "MultiDevice.render: spt_render over several devices filters with the box only, not %r "
+                              "(render_shard serves a weighted filter on one device)" % (renderer.filter_type,))
         cam = self.scene.get_camera(config.used_camera_name)
         p = renderer.params(config.width, config.height, 0, 1, 16, samples_per_pass)
         if film is None:
@@ -1275,8 +1344,15 @@ def thin_lens_rays(camera: Camera, width: int, height: int, offsets, lens_uv, le
 def load_renderer(path: str, seed: int = 1) -> PathTracer:
     """loader::load_renderer (src/loader/json.rs:19-51)."""
     p = RenderParams()
+    lib = host_lib()
+    if hasattr(lib, "spt_host_load_renderer_filter"):   # also takes the weighted filters of spt_film_filter
+        fd = FilterDesc()
+        _check_host(lib.spt_host_load_renderer_filter(os.fspath(path).encode(), C.byref(p), C.byref(fd)))
+        kind = [k for k, v in FILTER_TYPES.items() if v == fd.type][0]
+        extra = {"alpha": fd.p0} if kind == "gaussian" else {"b": fd.p0, "c": fd.p1} if kind == "mitchell" else {}
+        return PathTracer(p.max_depth, p.sampler, p.spp, p.division_x, p.division_y, fd.radius, seed, filter_type=kind, filter_params=extra)
     radius = C.c_float()
-    _check_host(host_lib().spt_host_load_renderer(os.fspath(path).encode(), C.byref(p), C.byref(radius)))
+    _check_host(lib.spt_host_load_renderer(os.fspath(path).encode(), C.byref(p), C.byref(radius)))
     return PathTracer(p.max_depth, p.sampler, p.spp, p.division_x, p.division_y, radius.value, seed)
 
 

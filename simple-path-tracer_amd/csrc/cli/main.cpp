@@ -20,6 +20,8 @@
 // device, spt_host_multi_film_*; the denoiser runs once on the gathered image, spt_denoise_image) and writes the same bytes.
 // A renderer whose box filter reaches neighbouring pixels (ceil(radius - 0.5) >= 1) gets a film that keeps its samples
 // (SPT_FILM_KEEP_SAMPLES): --preview-every, --time-limit and --film-devices work with it, the options that need moments or buckets exit with code 2.
+// A renderer with a weighted filter ("tent", "gaussian", "mitchell") always renders through such a film plus spt_film_filter, the plain
+// run included; --preview-every and --time-limit work with it, the options above and --film-devices exit with code 2.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -304,18 +306,13 @@ int main(int argc, char** argv) {
         return 2;
     }
     const uint32_t estimator = robust_estimator == "mon" ? (uint32_t)SPT_ROBUST_MON : (uint32_t)SPT_ROBUST_GMON;
-    const bool progressive = preview_every > 0 || time_limit > 0.0 || !variance_out.empty() || adaptive_on || !samples_out.empty() || denoise || robust;
+    bool progressive = preview_every > 0 || time_limit > 0.0 || !variance_out.empty() || adaptive_on || !samples_out.empty() || denoise || robust;
     if (film_devices_given && !film_devices_ok) {
         std::fprintf(stderr, "Error: --film-devices takes a list of device indices such as 0,1,2 (an index may repeat)\n");
         return 2;
     }
     if (film_devices_given && gpus > 0) {
         std::fprintf(stderr, "Error: --film-devices and --gpus / --devices exclude each other (--gpus renders one image in one call, --film-devices a film in increments)\n");
-        return 2;
-    }
-    if (film_devices_given && !progressive) {
-        std::fprintf(stderr, "Error: --film-devices needs a progressive option (--preview-every, --time-limit, --variance-out, --adaptive, --samples-out, --denoise or --robust); "
-                             "--gpus / --devices render a plain image on several devices\n");
         return 2;
     }
     if (progressive && gpus > 1) {
@@ -342,12 +339,36 @@ int main(int argc, char** argv) {
     if (bezier_ni) spt_host_scene_set_bezier_newton(hs, 1);   // `cargo build --features bezier_ni`
     spt_render_params params;
     std::memset(&params, 0, sizeof params);
-    float radius = 0.5f;
-    if (spt_host_load_renderer(renderer_path.c_str(), &params, &radius) != SPT_OK) {
+    spt_filter_desc filter;
+    if (spt_host_load_renderer_filter(renderer_path.c_str(), &params, &filter) != SPT_OK) {
         std::fprintf(stderr, "Error: %s\n", spt_host_last_error());
         return 1;
     }
     if (spp_override && params.sampler != SPT_SAMPLER_JITTERED) params.spp = spp_override;
+    // A weighted filter (tent, gaussian, mitchell) is a read-out of kept samples: the run always goes through one sample-keeping film
+    // plus spt_film_filter, the plain run included (in increments of spp / 16).  What assumes that every sample of a pixel
+    // weighs 1, and films over several devices, cannot serve it
+    const bool weighted = filter.type != SPT_FILTER_BOX;
+    if (weighted) {
+        if (!variance_out.empty() || adaptive_on || !samples_out.empty() || denoise || robust || film_devices_given || gpus > 1) {
+            std::fprintf(stderr, "Error: --variance-out, --adaptive, --samples-out, --denoise, --robust, --film-devices and several --gpus / --devices need the box "
+                                 "filter; the renderer's filter is weighted (--preview-every and --time-limit work with it)\n");
+            spt_host_scene_free(hs);
+            return 2;
+        }
+        if (gpus == 1) {
+            device = device_list.empty() ? 0 : device_list[0];
+            gpus = 0;
+        }
+        progressive = true;
+    }
+    // (after the renderer file is read: under a weighted filter the refusal above is the one that applies)
+    if (film_devices_given && !progressive) {
+        std::fprintf(stderr, "Error: --film-devices needs a progressive option (--preview-every, --time-limit, --variance-out, --adaptive, --samples-out, --denoise or --robust); "
+                             "--gpus / --devices render a plain image on several devices\n");
+        spt_host_scene_free(hs);
+        return 2;
+    }
     // A box filter that reaches neighbouring pixels (ceil(radius - 0.5) >= 1): its film keeps the samples (SPT_FILM_KEEP_SAMPLES),
     // which previews, time limits and several devices can use.  What needs moments or buckets cannot: the library would refuse
     // (spt_film_create with SPT_FILM_MOMENTS, spt_film_buckets), so the run ends here, before any sample is traced
@@ -358,7 +379,7 @@ int main(int argc, char** argv) {
         spt_host_scene_free(hs);
         return 2;
     }
-    const uint32_t keep_flag = wide_box ? (uint32_t)SPT_FILM_KEEP_SAMPLES : 0u;
+    const uint32_t keep_flag = (wide_box || weighted) ? (uint32_t)SPT_FILM_KEEP_SAMPLES : 0u;
     spt_camera cam;
     if (spt_host_scene_camera(hs, camera.empty() ? nullptr : camera.c_str(), &cam) != SPT_OK) {
         std::fprintf(stderr, "Error: %s\n", spt_host_last_error());
@@ -457,6 +478,7 @@ int main(int argc, char** argv) {
         };
         const bool moments = !variance_out.empty() || adaptive_on || denoise;
         if (spt_film_create(ds, &cam, &params, 0, (moments ? (uint32_t)SPT_FILM_MOMENTS : 0u) | keep_flag, &pf) != SPT_OK) return film_fail();
+        if (weighted && spt_film_filter(pf, &filter) != SPT_OK) return film_fail();
         if (robust && spt_film_buckets(pf, (uint32_t)robust_k) != SPT_OK) return film_fail();
         const spt_denoise_params dn = {(uint32_t)sizeof(spt_denoise_params), denoise_iterations, 2.0f, 1.0f, 1e-8f, 1e-2f};
         if (denoise && guide_normal) {   // the guide's samples come first: every preview is filtered with the whole guide
@@ -491,7 +513,8 @@ int main(int argc, char** argv) {
             return denoise && done >= 2 ? spt_film_read_rgb8(pf, SPT_READ_DENOISED, guide, &dn, film8.data())
                                         : spt_film_read_rgb8(pf, SPT_READ_MEAN, nullptr, nullptr, film8.data());
         };
-        const uint32_t inc = preview_every ? preview_every : ((time_limit > 0.0 || adaptive_on) ? std::max(1u, params.spp / 16u) : params.spp);
+        // (a weighted filter's plain run takes its one film in sixteenths too: the read-out does not depend on the increments)
+        const uint32_t inc = preview_every ? preview_every : ((time_limit > 0.0 || adaptive_on || weighted) ? std::max(1u, params.spp / 16u) : params.spp);
         uint32_t active = width * height;
         while (done < params.spp) {
             const uint32_t n = std::min(inc, params.spp - done);

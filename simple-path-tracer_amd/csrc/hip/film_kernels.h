@@ -815,6 +815,105 @@ __global__ void __launch_bounds__(256) k_film_filter_box(RenderCtx rc, KeptJob j
     job.out[3 * (size_t)idx] = c.x; job.out[3 * (size_t)idx + 1] = c.y; job.out[3 * (size_t)idx + 2] = c.z;
 }
 
+// ---- weighted reconstruction filters over the kept samples (spt_film_filter) ----
+// What a filter's f(a) reads besides the radius: GAUSSIAN a[0] = alpha, a[1] = e_r = spt_exp(-(alpha * (r * r))), made on the host
+// (spt_exp has the same bits there); MITCHELL a[0..3] = c3, c2, c1, c0 and a[4..6] = q3, q2, q0, rounded once from double.
+struct FilterCoef {
+    float a[7];
+};
+
+// f(a) of include/spt_abi.h ("reconstruction filters"), 0 <= a <= r, one rounded operation at a time
+template <uint32_t kType>
+SPT_DEV float filter_f(const FilterCoef& fc, float r, float a) {
+    if constexpr (kType == SPT_FILTER_TENT) {
+        return r - a;
+    } else if constexpr (kType == SPT_FILTER_GAUSSIAN) {
+        const float g = spt_exp(-(fc.a[0] * (a * a))) - fc.a[1];
+        return g < 0.0f ? 0.0f : g;
+    } else {
+        const float t = (2.0f * a) / r;
+        if (t > 1.0f) return ((fc.a[0] * t + fc.a[1]) * t + fc.a[2]) * t + fc.a[3];
+        return ((fc.a[4] * t + fc.a[5]) * t) * t + fc.a[6];
+    }
+}
+
+// The weight of sample s of `pixel` seen from a pixel (di, dj) away, 0.0f for a sample outside the support: the offsets as
+// box_weight derives them, the support test before any filter evaluation.
+template <uint32_t kType>
+SPT_DEV float filter_weight(const RenderCtx& rc, const FilterCoef& fc, uint32_t pixel, uint32_t s, int32_t di, int32_t dj, float r) {
+    DRng rng;
+    rng.s.state = 0ull;
+    if (rc.sampler != SPT_SAMPLER_RECURRENCE) rng.s = spt_rng_seed(rc.seed, pixel, s);
+    float ox, oy;
+    pixel_offset(rc, pixel, s, rng, &ox, &oy);
+    const float ax = fabsf((float)di + (ox - 0.5f)), ay = fabsf((float)dj + (oy - 0.5f));
+    if (!(ax <= r && ay <= r)) return 0.0f;
+    return filter_f<kType>(fc, r, ax) * filter_f<kType>(fc, r, ay);
+}
+
+// The read-out of a sample-keeping film under a weighted filter: the loops of k_film_filter_box over job.R = Rf rings, job.radius = r.
+// One lane per output pixel; consecutive lanes read consecutive floats of every plane.  The colour and wsum chains are sequential by
+// specification; per batch of kBatch samples the 3 kBatch loads are requested together and the kBatch weights (offset derivation,
+// support test, two filter evaluations) are made before the first sample enters the chain, so the chain itself is one multiply
+// and one add per channel.  A sample of weight 0 (outside the support included) enters neither sum.
+// Every sample's offset is derived again per tap with the RNG, as the box does: a per-read table of offsets (stored pixels x
+// samples x 8 B, filled by a kernel of its own) was measured and lost by 1.6 - 1.7 x, and kBatch 4 is level with 8 and ahead of 1
+// for the filters that do arithmetic ("Reconstruction filters").
+template <uint32_t kType, uint32_t kBatch>
+__global__ void __launch_bounds__(256) k_film_filter_weighted(RenderCtx rc, KeptJob job, FilterCoef fc) {
+    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= job.out_rows * rc.width) return;
+    const uint32_t row = idx / rc.width, x = idx - row * rc.width;
+    const int32_t y = (int32_t)(job.out_j0 + row);
+    const size_t n_band = (size_t)job.band_rows * rc.width;
+    const float rad = job.radius;
+    f3 sum = mk3(0, 0, 0);
+    float wsum = 0.0f;
+    for (int32_t dj = -job.R; dj <= job.R; ++dj) {
+        const int32_t jj = y + dj;
+        if (jj < 0 || jj >= (int32_t)rc.height) continue;
+        for (int32_t di = -job.R; di <= job.R; ++di) {
+            const int32_t ii = (int32_t)x + di;
+            if (ii < 0 || ii >= (int32_t)rc.width) continue;
+            const uint32_t pixel = (uint32_t)jj * rc.width + (uint32_t)ii;
+            const size_t lp = (size_t)((uint32_t)jj - job.band_base) * rc.width + (uint32_t)ii;
+            for (uint32_t c = 0; c < job.n_chunks; ++c) {
+                const KeptChunk ch = job.chunks[c];
+                const size_t plane = (size_t)ch.count * n_band;
+                const float* rp = ch.rad + lp;
+                uint32_t s = 0;
+                for (; s + kBatch <= ch.count; s += kBatch) {
+                    float r[kBatch], g[kBatch], b[kBatch], w[kBatch];
+#pragma unroll
+                    for (uint32_t k = 0; k < kBatch; ++k) {
+                        const size_t ri = (size_t)(s + k) * n_band;
+                        r[k] = rp[ri]; g[k] = rp[plane + ri]; b[k] = rp[2 * plane + ri];
+                    }
+#pragma unroll
+                    for (uint32_t k = 0; k < kBatch; ++k) w[k] = filter_weight<kType>(rc, fc, pixel, ch.first + s + k, di, dj, rad);
+#pragma unroll
+                    for (uint32_t k = 0; k < kBatch; ++k)
+                        if (w[k] != 0.0f) {
+                            sum.x = sum.x + w[k] * r[k]; sum.y = sum.y + w[k] * g[k]; sum.z = sum.z + w[k] * b[k];
+                            wsum = wsum + w[k];
+                        }
+                }
+                for (; s < ch.count; ++s) {
+                    const size_t ri = (size_t)s * n_band;
+                    const float w = filter_weight<kType>(rc, fc, pixel, ch.first + s, di, dj, rad);
+                    if (w != 0.0f) {
+                        sum.x = sum.x + w * rp[ri]; sum.y = sum.y + w * rp[plane + ri]; sum.z = sum.z + w * rp[2 * plane + ri];
+                        wsum = wsum + w;
+                    }
+                }
+            }
+        }
+    }
+    f3 c = sum;
+    if (job.mean) c = sum * (1.0f / wsum);
+    job.out[3 * (size_t)idx] = c.x; job.out[3 * (size_t)idx + 1] = c.y; job.out[3 * (size_t)idx + 2] = c.z;
+}
+
 // spt_film_read_samples: the own rows of `count` kept samples from plan index `first`, [k][own row][x][3].  One lane per float of
 // one sample plane; blockIdx.y walks the samples.  The chunk holding sample first + k is found by a walk over the (short) table.
 __global__ void __launch_bounds__(256) k_film_read_kept(KeptJob job, uint32_t width, uint32_t first, size_t out_plane) {

@@ -543,6 +543,7 @@ struct BezierLib {
     decltype(&spt_film_read_robust) film_read_robust = nullptr;
     decltype(&spt_film_read_rgb8) film_read_rgb8 = nullptr;
     decltype(&spt_film_read_samples) film_read_samples = nullptr;
+    decltype(&spt_film_filter) film_filter = nullptr;   // (resolved if present: a library without it serves every other call)
     decltype(&spt_denoise_image) denoise_image = nullptr;
     decltype(&spt_trace_closest) trace_closest = nullptr;
     decltype(&spt_trace_any) trace_any = nullptr;
@@ -575,7 +576,7 @@ struct spt_scene {
     bool film_inflight = false;               // ... and the host has not waited for them since (grow)
     uint64_t passes_film = 0, passes_single = 0;   // spt_debug_render_info: passes resolved on the film stream / on the main stream
     uint64_t frames_direct = 0;                    // ... and frames whose finish kernel stored into the caller's buffer (no copy-out)
-    // ... and what the kernels of a sample-keeping film's last read-out (k_film_filter_box) took on the device, in ns, between the
+    // ... and what the kernels of a sample-keeping film's last read-out (k_film_filter_box, k_film_filter_weighted) took on the device, in ns, between the
     // two events below (made by the first such film)
     uint64_t keep_read_ns = 0;
     hipEvent_t ev_keep[2] = {nullptr, nullptr};
@@ -693,6 +694,11 @@ struct spt_film {
         DeviceBuffer table_dev;
     };
     std::deque<KeptRun> runs;       // (a KeptRun does not move: it owns device buffers)
+    // the reconstruction filter of the read-outs (spt_film_filter); SPT_FILTER_BOX: the reference's box at the plan's radius
+    uint32_t filter_type = SPT_FILTER_BOX;
+    float filter_radius = 0.5f;       // r
+    int32_t filter_R = 0;             // Rf = max(ceil(r - 0.5), 0) <= max(R, 0)
+    FilterCoef filter_coef{};
 };
 
 namespace {
@@ -926,6 +932,7 @@ const BezierLib* bezier_lib() {
                          sym(lib.trace_closest, "spt_trace_closest") && sym(lib.trace_any, "spt_trace_any") && sym(lib.radiance, "spt_radiance") && sym(lib.debug_bxdf, "spt_debug_bxdf") &&
                          sym(lib.debug_render_info, "spt_debug_render_info") &&
                          sym(lib.last_error, "spt_last_error") && sym(version, "spt_abi_version");
+        (void)sym(lib.film_filter, "spt_film_filter");
         if (!all || version() != SPT_ABI_VERSION) {
             err = path + " does not export ABI version " + std::to_string(SPT_ABI_VERSION);
             return;
@@ -2494,6 +2501,18 @@ KeptJob kept_job(const spt_film* f, const spt_film::KeptRun& r, float* out, bool
     return KeptJob{r.table_dev.as<KeptChunk>(), (uint32_t)r.table.size(), r.b0, r.b1 - r.b0, r.j0, r.j1 - r.j0, out, f->R, f->radius, mean ? 1u : 0u};
 }
 
+// The read-out of one run under the film's weighted filter (spt_film_filter): the job of the box with Rf and r in the place of the
+// plan's R and radius.  Samples requested together per lane: kFilterBatch ("Reconstruction filters").
+constexpr uint32_t kFilterBatch = 4u;
+void launch_filter_weighted(const spt_film* f, dim3 grid, hipStream_t st, const RenderCtx& rc, KeptJob job) {
+    job.R = f->filter_R;
+    job.radius = f->filter_radius;
+    auto* k = k_film_filter_weighted<SPT_FILTER_TENT, kFilterBatch>;
+    if (f->filter_type == SPT_FILTER_GAUSSIAN) k = k_film_filter_weighted<SPT_FILTER_GAUSSIAN, kFilterBatch>;
+    if (f->filter_type == SPT_FILTER_MITCHELL) k = k_film_filter_weighted<SPT_FILTER_MITCHELL, kFilterBatch>;
+    hipLaunchKernelGGL(k, grid, dim3(kBlock), 0, st, rc, job, f->filter_coef);
+}
+
 // The device-visible address of spt_render's destination when k_finish_host may store into it, else nullptr (the frame then
 // takes the runtime's copy): the first and the last byte of the span the shard writes must both be mapped for the device, exactly
 // that span apart - pageable memory, a buffer pinned only in part and two unrelated mappings all fail one of the three.  Asked anew
@@ -2871,6 +2890,10 @@ static spt_status film_read_locked(spt_film* f, uint32_t what, const FilmReadOut
             const RenderCtx rc = plan_ctx(p, f->cam, r.b0, r.b1 - r.b0, 0u, 1u, 1u);
             const KeptJob job = kept_job(f, r, f->out.as<float>() + r.out_row * (size_t)p.width * 3, what == SPT_FILM_MEAN);
             const dim3 grid(((r.j1 - r.j0) * p.width + kBlock - 1) / kBlock);
+            if (f->filter_type != SPT_FILTER_BOX) {
+                launch_filter_weighted(f, grid, st, rc, job);
+                continue;
+            }
             // samples requested together per lane: 8 up to R = 1, 1 from R = 2 on (measured, see k_film_filter_box)
             hipLaunchKernelGGL(f->R >= 2 ? k_film_filter_box<1u> : k_film_filter_box<8u>, grid, dim3(kBlock), 0, st, rc, job);
         }
@@ -3349,6 +3372,54 @@ spt_status spt_film_read_rgb8(spt_film* f, uint32_t source, spt_film* guide, con
         if (denoised) return film_denoise_locked(f, guide, dn, to);
         if (source == SPT_READ_MEAN) return film_read_locked(f, SPT_FILM_MEAN, to);
         return film_read_robust_locked(f, source == SPT_READ_ROBUST_MON ? SPT_ROBUST_MON : SPT_ROBUST_GMON, to);
+    });
+}
+
+spt_status spt_film_filter(spt_film* f, const spt_filter_desc* desc) {
+    if (!f || !desc) { g_error = "film_filter: null argument"; return SPT_ERR_INVALID_ARG; }
+    if (f->fwd) {
+        if (!f->fwd->film_filter) { g_error = "film_filter: libspt_hip_bez.so does not export spt_film_filter"; return SPT_ERR_UNSUPPORTED; }
+        return forwarded(f->fwd, f->fwd->film_filter(f->inner, desc));
+    }
+    std::lock_guard<std::mutex> lock(f->sc->mu);
+    return guarded("film_filter", [&] {
+        // every check comes before the first change: a refused call leaves the film and its filter as they were
+        if (desc->size < sizeof(spt_filter_desc)) fail(SPT_ERR_INVALID_ARG, "film_filter: desc->size is below sizeof(spt_filter_desc)");
+        if (desc->type > SPT_FILTER_MITCHELL) fail(SPT_ERR_INVALID_ARG, "film_filter: unknown SPT_FILTER_* value");
+        if (!(f->flags & SPT_FILM_KEEP_SAMPLES)) fail(SPT_ERR_INVALID_ARG, "film_filter: the film was created without SPT_FILM_KEEP_SAMPLES");
+        if (desc->type == SPT_FILTER_BOX) {
+            f->filter_type = SPT_FILTER_BOX;
+            return SPT_OK;
+        }
+        const float r = desc->radius;
+        if (!std::isfinite(r) || r <= 0.0f) fail(SPT_ERR_INVALID_ARG, "film_filter: the radius must be finite and > 0");
+        const float rf = std::max(std::ceil(r - 0.5f), 0.0f);
+        const int32_t halo = std::max(f->R, 0);
+        if (rf > (float)halo)
+            fail(SPT_ERR_INVALID_ARG, "film_filter: radius " + std::to_string(r) + " reads " + std::to_string((double)rf) + " neighbouring rows, the film stores " +
+                                          std::to_string(halo) + " (create it with the plan's filter_radius " + std::to_string(r) + " or more)");
+        FilterCoef fc{};
+        if (desc->type == SPT_FILTER_GAUSSIAN) {
+            const float alpha = desc->p0;
+            if (!std::isfinite(alpha) || alpha <= 0.0f) fail(SPT_ERR_INVALID_ARG, "film_filter: the Gaussian's alpha must be finite and > 0");
+            fc.a[0] = alpha;
+            fc.a[1] = spt_exp(-(alpha * (r * r)));
+        } else if (desc->type == SPT_FILTER_MITCHELL) {
+            if (!std::isfinite(desc->p0) || !std::isfinite(desc->p1)) fail(SPT_ERR_INVALID_ARG, "film_filter: Mitchell's B and C must be finite");
+            const double B = (double)desc->p0, C = (double)desc->p1;
+            fc.a[0] = (float)((-B - 6 * C) / 6);
+            fc.a[1] = (float)((6 * B + 30 * C) / 6);
+            fc.a[2] = (float)((-12 * B - 48 * C) / 6);
+            fc.a[3] = (float)((8 * B + 24 * C) / 6);
+            fc.a[4] = (float)((12 - 9 * B - 6 * C) / 6);
+            fc.a[5] = (float)((-18 + 12 * B + 6 * C) / 6);
+            fc.a[6] = (float)((6 - 2 * B) / 6);
+        }
+        f->filter_type = desc->type;
+        f->filter_radius = r;
+        f->filter_R = (int32_t)rf;
+        f->filter_coef = fc;
+        return SPT_OK;
     });
 }
 

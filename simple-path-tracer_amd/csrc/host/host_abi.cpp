@@ -93,9 +93,10 @@ void spt_host_scene_free(spt_host_scene* scene) {
 }
 
 // loader::load_renderer (src/loader/json.rs:19-51) + create_sampler_from_params
-// (src/pixel_sampler/mod.rs:28-43) + create_filter_from_params (src/filter/mod.rs:19-32)
-spt_status spt_host_load_renderer(const char* path, spt_render_params* params, float* filter_radius) {
-    if (!path || !params) { set_error("load_renderer: null argument"); return SPT_ERR_INVALID_ARG; }
+// (src/pixel_sampler/mod.rs:28-43) + create_filter_from_params (src/filter/mod.rs:19-32).
+// filter == nullptr: spt_host_load_renderer, which knows the reference's box only; else spt_host_load_renderer_filter, which also
+// takes the weighted filters of spt_film_filter and returns the desc.
+static spt_status load_renderer(const char* path, spt_render_params* params, float* filter_radius, spt_filter_desc* filter) {
     try {
         std::ifstream f(path, std::ios::binary);
         if (!f) throw HostError(SPT_HOST_ERR_IO, std::string("cannot open '") + path + "'");
@@ -131,8 +132,32 @@ spt_status spt_host_load_renderer(const char* path, spt_render_params* params, f
         const JsonValue* fv = root.get("filter");
         if (!fv || fv->kind != JsonValue::Object) throw HostError(SPT_HOST_ERR_SCHEMA, "renderer - There is no 'filter' field");
         std::string fty = need(fv, "type", JsonValue::String, "filter", "string")->s;
-        if (fty != "box") throw HostError(SPT_HOST_ERR_SCHEMA, "filter: unknown type '" + fty + "'");
-        float radius = (float)need(fv, "radius", JsonValue::Float, "filter-box", "float")->f;
+        spt_filter_desc fd{};
+        fd.size = (uint32_t)sizeof(spt_filter_desc);
+        // a number that may be left out; like every float of the loader, an integer literal is a schema error
+        auto opt = [&](const char* key, const char* owner, float dflt) {
+            return fv->get(key) ? (float)need(fv, key, JsonValue::Float, owner, "float")->f : dflt;
+        };
+        float radius;
+        if (fty == "box") {
+            fd.type = SPT_FILTER_BOX;
+            radius = (float)need(fv, "radius", JsonValue::Float, "filter-box", "float")->f;
+        } else if (filter && fty == "tent") {
+            fd.type = SPT_FILTER_TENT;
+            radius = (float)need(fv, "radius", JsonValue::Float, "filter-tent", "float")->f;
+        } else if (filter && fty == "gaussian") {
+            fd.type = SPT_FILTER_GAUSSIAN;
+            radius = (float)need(fv, "radius", JsonValue::Float, "filter-gaussian", "float")->f;
+            fd.p0 = opt("alpha", "filter-gaussian", 2.0f);
+        } else if (filter && fty == "mitchell") {
+            fd.type = SPT_FILTER_MITCHELL;
+            radius = opt("radius", "filter-mitchell", 2.0f);
+            fd.p0 = opt("b", "filter-mitchell", 1.0f / 3.0f);
+            fd.p1 = opt("c", "filter-mitchell", 1.0f / 3.0f);
+        } else {
+            throw HostError(SPT_HOST_ERR_SCHEMA, "filter: unknown type '" + fty + "'");
+        }
+        fd.radius = radius;
         const JsonValue* ty = root.get("type");
         if (!ty) throw HostError(SPT_HOST_ERR_SCHEMA, "renderer - There is no 'type' field");
         if (ty->kind != JsonValue::String) throw HostError(SPT_HOST_ERR_SCHEMA, "renderer - 'type' shoule be string");
@@ -142,15 +167,27 @@ spt_status spt_host_load_renderer(const char* path, spt_render_params* params, f
         params->spp = spp;
         params->division_x = dx;
         params->division_y = dy;
-        // BoxFilter::new (src/filter/boxf.rs:11-14): any radius; 0.5 is the plain per-pixel mean
+        // BoxFilter::new (src/filter/boxf.rs:11-14): any radius; 0.5 is the plain per-pixel mean.  (A weighted filter's radius
+        // decides the halo a sample-keeping film stores.)
         params->filter_radius = radius;
         if (radius != 0.5f) params->flags |= SPT_RENDER_BOX_RADIUS;
         if (filter_radius) *filter_radius = radius;
+        if (filter) *filter = fd;
         return SPT_OK;
     } catch (const HostError& e) {
         set_error(e.msg);
         return e.code;
     }
+}
+
+spt_status spt_host_load_renderer(const char* path, spt_render_params* params, float* filter_radius) {
+    if (!path || !params) { set_error("load_renderer: null argument"); return SPT_ERR_INVALID_ARG; }
+    return load_renderer(path, params, filter_radius, nullptr);
+}
+
+spt_status spt_host_load_renderer_filter(const char* path, spt_render_params* params, spt_filter_desc* filter) {
+    if (!path || !params || !filter) { set_error("load_renderer_filter: null argument"); return SPT_ERR_INVALID_ARG; }
+    return load_renderer(path, params, nullptr, filter);
 }
 
 }  // extern "C"

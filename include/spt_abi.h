@@ -429,6 +429,33 @@ spt_status spt_device_count(int32_t* count);
 spt_status spt_scene_create(const spt_scene_desc* desc, int32_t device, spt_scene** out);
 void spt_scene_destroy(spt_scene* scene);
 
+/* spt_scene_update (additive to ABI v14: detect it by its symbol): moves instances and lights of a live scene without a rebuild.
+ * The call replaces four fields of the descriptor the scene was created from - tlas_nodes, instances, lights, light_alias - and
+ * keeps everything else (meshes, BLAS, triangles, spheres, patches, surfaces, materials, media, textures, P-NDF tables, the
+ * environment, aggregate, light_sampler, env_light_index).  After SPT_OK every later call on the scene (spt_render, spt_film_*,
+ * spt_trace_closest / _any, spt_radiance) returns the words a scene freshly created from the edited descriptor returns.
+ *   - n_instances and n_lights must equal the creation's counts; the light at env_light_index keeps its type.  The arrays may be
+ *     permuted (they are in the leaf order of tlas_nodes): spt_light::instance, spt_instance::light and spt_hit::instance refer to
+ *     the new order.  The new arrays get every check spt_scene_create applies to these fields.
+ *   - A scene created without Bezier instances refuses an update that introduces one (SPT_ERR_UNSUPPORTED); so is an update after
+ *     which the traversal geometry no longer fits the form chosen at creation ("recreate the scene").
+ *   - While a spt_film of the scene is alive the call is refused (SPT_ERR_INVALID_ARG): a film accumulates samples of one scene.
+ *   - On any failure the scene is exactly as before.
+ *   - Ordering: the uploads are queued on the scene's render stream.  Frames queued earlier with SPT_RENDER_ASYNC deliver the old
+ *     scene's image, frames queued later the new one; the host waits only when the staging slot of the previous update is still
+ *     being copied.
+ *   - Cost: no triangle is read and no BLAS rebuilt.  Unless the traversal geometry is LDS-resident (<= 32 KB, re-uploaded whole),
+ *     the bytes copied to the device are bounded by the instance and light counts (spt_debug_render_info, counter 5). */
+typedef struct spt_scene_update_desc {
+    uint32_t size;                 /* sizeof(spt_scene_update_desc) AS THE CALLER WAS COMPILED */
+    uint32_t flags;                /* 0 */
+    uint32_t n_tlas_nodes;  const spt_bvh_node* tlas_nodes;
+    uint32_t n_instances;   const spt_instance* instances;   /* in the leaf order of tlas_nodes, as in spt_scene_desc */
+    uint32_t n_lights;      const spt_light* lights;
+    spt_alias_table light_alias;   /* POWER_IS scenes only, n = n_lights */
+} spt_scene_update_desc;
+spt_status spt_scene_update(spt_scene* scene, const spt_scene_update_desc* u);
+
 /* The hot path: RendererT::render for one image shard.  rgb_mean_out receives
  * shard_rows*width*3 f32 = per-pixel mean radiance (Film::filter_pixel with the
  * box filter, src/core/film.rs:71-92: the sum of the samples of the (2 ceil(radius - 0.5) + 1)^2 pixels around it
@@ -799,7 +826,9 @@ spt_status spt_debug_bxdf(const spt_scene* scene, int32_t device, const spt_mate
  *   what 2  nanoseconds the read-out kernels of the last spt_film_read / spt_film_read_rgb8 of a sample-keeping film
  *           (SPT_FILM_KEEP_SAMPLES) of the scene took on the device (0: none yet)
  *   what 3  frames of spt_render delivered without the runtime's copy: the finish kernel stored the image into rgb_mean_out
- *           itself (an SPT_RENDER_ASYNC frame on the overlapped schedule, radius 0.5, page-locked destination, no SPT_NO_DIRECT_OUT=1) */
+ *           itself (an SPT_RENDER_ASYNC frame on the overlapped schedule, radius 0.5, page-locked destination, no SPT_NO_DIRECT_OUT=1)
+ *   what 4  spt_scene_update calls applied to the scene (a library without spt_scene_update refuses 4 and 5)
+ *   what 5  bytes the last spt_scene_update copied to the device (0: none yet) */
 spt_status spt_debug_render_info(const spt_scene* scene, uint32_t what, uint64_t* out);
 
 const char* spt_last_error(void);

@@ -44,6 +44,33 @@ void spt_host_scene_free(spt_host_scene* scene);
  * process-wide default applies (clipping, or Newton when the environment variable SPT_BEZIER_NI is set to a non-zero value). */
 spt_status spt_host_scene_set_bezier_newton(spt_host_scene* scene, int32_t newton);
 
+/* Animating a loaded scene (the arrays spt_scene_update takes).  The loader is the only place that knows how an instance record
+ * follows from a transform (Instance::new), what a shape light's power is under it, how the TLAS orders the instances and what
+ * the alias table over the lights' powers is: these calls run that same finalisation again.  After a call that returns SPT_OK,
+ * spt_host_scene_desc is the descriptor spt_host_load_scene would produce for the same scene file with the new transforms (or
+ * light) written into it: tlas_nodes, instances (their order too), lights and light_alias, bit for bit; every other array is
+ * untouched and keeps its address.  The four arrays may move: read the descriptor again.  A refused call leaves the scene as
+ * it was. */
+/* The index of the instance called `name` in the CURRENT descriptor (the order changes with the transforms).
+ * SPT_HOST_ERR_SCHEMA: no such instance. */
+spt_status spt_host_scene_instance_index(const spt_host_scene* scene, const char* name, uint32_t* index);
+/* New object-to-world transforms of n named instances: fwd holds n x 12 floats in the layout of spt_instance::fwd (the three
+ * columns of the 3x3 part, then the translation).  SPT_HOST_ERR_SCHEMA: an unknown name; SPT_ERR_INVALID_ARG: a transform that is
+ * not invertible or yields a box that is not finite, or a name given twice. */
+spt_status spt_host_scene_set_transforms(spt_host_scene* scene, uint32_t n, const char* const* names, const float* fwd);
+/* Replaces the directional, point or spot light called `name` (the type must stay; `power` is set from the strength as the
+ * loader sets it, `instance` is ignored). */
+spt_status spt_host_scene_set_light(spt_host_scene* scene, const char* name, const spt_light* light);
+/* `spt --animate FILE`: {"frames": [ {"<instance name>": <transform object in the scene file's own syntax: matrix, scale, rotate,
+ * translate>, ...}, ... ]}, checked against `scene` (SPT_HOST_ERR_SCHEMA: a malformed file, an unknown instance).
+ * spt_host_animation_apply hands frame `frame`'s transforms to spt_host_scene_set_transforms; instances a frame does not name
+ * keep the transform they have. */
+typedef struct spt_host_animation spt_host_animation;
+spt_status spt_host_animation_load(const char* path, const spt_host_scene* scene, spt_host_animation** out);
+uint32_t spt_host_animation_frames(const spt_host_animation* animation);
+spt_status spt_host_animation_apply(const spt_host_animation* animation, uint32_t frame, spt_host_scene* scene);
+void spt_host_animation_free(spt_host_animation* animation);
+
 /* Fills max_depth, spp, sampler, division_x/y of *params (other fields untouched)
  * and the box-filter radius. */
 spt_status spt_host_load_renderer(const char* renderer_json_path, spt_render_params* params,

@@ -276,6 +276,15 @@ class RadianceJob(C.Structure):
 
 # ---- library loading -----------------------------------------------------------------
 
+class SceneUpdateDesc(C.Structure):
+    """spt_scene_update_desc (spt_scene_update); `size` is sizeof of the struct."""
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32),
+                ("n_tlas_nodes", C.c_uint32), ("tlas_nodes", C.POINTER(BvhNode)),
+                ("n_instances", C.c_uint32), ("instances", C.POINTER(Instance)),
+                ("n_lights", C.c_uint32), ("lights", C.POINTER(Light)),
+                ("light_alias", AliasTable)]
+
+
 def _load(name: str) -> C.CDLL:
     path = os.path.join(LIB_DIR, name)
     if not os.path.exists(path):
@@ -319,6 +328,10 @@ def host_lib() -> C.CDLL:
         lib.spt_host_scene_camera.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(Camera)]
         lib.spt_host_scene_free.argtypes = [C.c_void_p]
         lib.spt_host_scene_free.restype = None
+        if hasattr(lib, "spt_host_scene_set_transforms"):   # (the same)
+            lib.spt_host_scene_instance_index.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint32)]
+            lib.spt_host_scene_set_transforms.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_char_p), C.c_void_p]
+            lib.spt_host_scene_set_light.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(Light)]
         lib.spt_host_load_renderer.argtypes = [C.c_char_p, C.POINTER(RenderParams), C.POINTER(C.c_float)]
         if hasattr(lib, "spt_host_load_renderer_filter"):   # (a library built before the weighted filters lacks it)
             lib.spt_host_load_renderer_filter.argtypes = [C.c_char_p, C.POINTER(RenderParams), C.POINTER(FilterDesc)]
@@ -391,6 +404,8 @@ def hip_lib() -> C.CDLL:
             lib.spt_denoise_image.argtypes = [C.c_void_p, C.POINTER(ImageDenoiseJob), C.c_void_p]
         if hasattr(lib, "spt_radiance"):   # (the same)
             lib.spt_radiance.argtypes = [C.c_void_p, C.POINTER(RadianceJob)]
+        if hasattr(lib, "spt_scene_update"):   # (the same)
+            lib.spt_scene_update.argtypes = [C.c_void_p, C.POINTER(SceneUpdateDesc)]
         lib.spt_debug_detmath.argtypes = [C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.spt_debug_bxdf.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Material), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -458,10 +473,51 @@ class Scene:
         buf = C.string_at(ptr, n * C.sizeof(ty))
         return np.frombuffer(buf, dtype=np.dtype(ty)).copy()
 
+    def _dynamic_host(self):
+        lib = host_lib()
+        if not hasattr(lib, "spt_host_scene_set_transforms"):
+            raise SptError(4, "this libspt_host.so cannot edit a loaded scene (no spt_host_scene_set_transforms)")
+        return lib
+
+    def instance_index(self, name: str) -> int:
+        """The index of the instance called `name` in the CURRENT descriptor (set_transforms reorders the instances)."""
+        index = C.c_uint32(0)
+        _check_host(self._dynamic_host().spt_host_scene_instance_index(self._h, name.encode(), C.byref(index)))
+        return int(index.value)
+
+    def set_transforms(self, transforms) -> None:
+        """spt_host_scene_set_transforms: {instance name: object-to-world transform}, each 12 floats in the layout of
+        spt_instance::fwd (three columns, then the translation) or a 3x4 matrix [M | t].  The descriptor becomes the one the
+        loader makes of the scene file with these transforms written in; a refused call leaves it as it was.  A DeviceScene
+        keeps rendering the old state until its update()."""
+        lib = self._dynamic_host()
+        names = list(transforms)
+        fwd = np.zeros((len(names), 12), dtype=np.float32)
+        for i, name in enumerate(names):
+            m = np.asarray(transforms[name], dtype=np.float32)
+            if m.shape == (3, 4):
+                m = m.T.reshape(12)      # rows of [M | t] -> columns
+            if m.shape != (12,):
+                raise ValueError("%s: 12 floats or a 3x4 matrix are expected" % name)
+            fwd[i] = m
+        c_names = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+        _check_host(lib.spt_host_scene_set_transforms(self._h, len(names), c_names, fwd.ctypes.data))
+
+    def set_light(self, name: str, light: "Light") -> None:
+        """spt_host_scene_set_light: replaces the directional, point or spot light called `name` (same type)."""
+        _check_host(self._dynamic_host().spt_host_scene_set_light(self._h, name.encode(), C.byref(light)))
+
     def device_scene(self, device: int = 0) -> "DeviceScene":
         if device not in self._device_scenes:
             self._device_scenes[device] = DeviceScene(self, device)
         return self._device_scenes[device]
+
+    def close_device_scene(self, device: int = 0) -> None:
+        """Destroys the device scene on `device`, if there is one (spt_render_wait + spt_scene_destroy); the next device_scene(device)
+        creates it again from the descriptor as it then stands."""
+        ds = self._device_scenes.pop(device, None)
+        if ds is not None:
+            ds.close()
 
     def close(self) -> None:
         for ds in self._device_scenes.values():
@@ -568,10 +624,55 @@ class DeviceScene:
         _check_hip(lib.spt_radiance(self._h, C.byref(job)))
         return (out, hit) if hits else out
 
+    def update(self) -> None:
+        """spt_scene_update with the Scene's current tlas_nodes, instances, lights and light alias table (after
+        Scene.set_transforms / set_light): the device scene then behaves like one freshly created from the Scene.  Frames queued
+        before with SPT_RENDER_ASYNC still deliver the old state.  The scene's films must be closed first."""
+        d = self.scene.desc
+        u = SceneUpdateDesc(size=C.sizeof(SceneUpdateDesc), flags=0, n_tlas_nodes=d.n_tlas_nodes, tlas_nodes=d.tlas_nodes,
+                            n_instances=d.n_instances, instances=d.instances, n_lights=d.n_lights, lights=d.lights, light_alias=d.light_alias)
+        self._update(u)
+
+    def update_arrays(self, instances, lights, tlas_nodes=None, light_alias=None) -> None:
+        """spt_scene_update for callers who edit the records themselves: `instances` / `lights` / `tlas_nodes` are arrays of the
+        Instance / Light / BvhNode records (as Scene.array returns them; the instances in the leaf order of tlas_nodes),
+        light_alias the (props, u, k) arrays of a power_is scene.  None: the Scene's current ones."""
+        d = self.scene.desc
+        keep = []
+
+        def records(a, ty):
+            a = np.ascontiguousarray(a, dtype=np.dtype(ty)).reshape(-1)
+            keep.append(a)
+            return a.shape[0], C.cast(a.ctypes.data, C.POINTER(ty))
+
+        u = SceneUpdateDesc(size=C.sizeof(SceneUpdateDesc), flags=0)
+        u.n_instances, u.instances = records(instances, Instance)
+        u.n_lights, u.lights = records(lights, Light)
+        if tlas_nodes is None:
+            u.n_tlas_nodes, u.tlas_nodes = d.n_tlas_nodes, d.tlas_nodes
+        else:
+            u.n_tlas_nodes, u.tlas_nodes = records(tlas_nodes, BvhNode)
+        if light_alias is None:
+            u.light_alias = d.light_alias
+        else:
+            props, uu, k = light_alias
+            n, u.light_alias.props = records(props, C.c_float)
+            _, u.light_alias.u = records(uu, C.c_float)
+            _, u.light_alias.k = records(k, C.c_uint32)
+            u.light_alias.n = n
+        self._update(u)
+
+    def _update(self, u: "SceneUpdateDesc") -> None:
+        lib = hip_lib()
+        if not hasattr(lib, "spt_scene_update"):
+            raise SptError(4, "this libspt_hip.so has no spt_scene_update")
+        _check_hip(lib.spt_scene_update(self._h, C.byref(u)))
+
     def render_info(self, what: int) -> int:
         """Test seam (spt_debug_render_info): 0 passes resolved on the film stream, 1 passes on the single-stream path;
         2 the ns the kernels of the last read-out of a sample-keeping film of the scene took on the device; 3 frames whose
-        finish kernel stored the image into the (page-locked) output buffer itself, without the runtime's copy."""
+        finish kernel stored the image into the (page-locked) output buffer itself, without the runtime's copy; 4 the
+        spt_scene_update calls applied to the scene; 5 the bytes the last of them copied to the device."""
         v = C.c_uint64(0)
         _check_hip(hip_lib().spt_debug_render_info(self._h, what, C.byref(v)))
         return int(v.value)

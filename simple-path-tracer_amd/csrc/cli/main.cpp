@@ -42,7 +42,8 @@ static void usage() {
                  "           [--denoise [--denoise-iterations K] [--guide-samples N] [--noisy-out noisy.png]\n"
                  "            [--guide normal|albedo|both] [--demodulate] [--albedo-out albedo.png]]\n"
                  "           [--robust K [--robust-estimator mon|gmon] [--mean-out mean.png]]   (K odd, 3 .. 15)\n"
-                 "           [--film-devices a,b,..]   (the progressive options above over several devices)\n");
+                 "           [--film-devices a,b,..]   (the progressive options above over several devices)\n"
+                 "           [--animate frames.json]   (one plain image <out>_NNNN per frame: {\"frames\": [{\"<instance>\": {<transform>}, ..}, ..]})\n");
 }
 
 // "0,1,2" -> indices; false for an empty list, an empty item or anything but decimal digits
@@ -227,6 +228,7 @@ int main(int argc, char** argv) {
     bool robust = false;
     int robust_k = 0;
     std::string robust_estimator, mean_out;
+    std::string animate_path;
     std::vector<int32_t> device_list;
     std::vector<int32_t> film_devices;
     bool film_devices_given = false, film_devices_ok = true;
@@ -275,6 +277,7 @@ int main(int argc, char** argv) {
         else if (a == "--robust") { robust_k = std::atoi(next()); robust = true; }
         else if (a == "--robust-estimator") robust_estimator = next();
         else if (a == "--mean-out") mean_out = next();
+        else if (a == "--animate") animate_path = next();
         else if (a == "--film-devices") { film_devices_given = true; film_devices_ok = parse_device_list(next(), &film_devices); }
         else { usage(); return 2; }
     }
@@ -315,6 +318,11 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "Error: --film-devices and --gpus / --devices exclude each other (--gpus renders one image in one call, --film-devices a film in increments)\n");
         return 2;
     }
+    if (!animate_path.empty() && (gpus > 1 || film_devices_given || progressive)) {
+        std::fprintf(stderr, "Error: --animate renders plain frames on one device: not with several --gpus / --devices, --film-devices, --preview-every, --time-limit, "
+                             "--variance-out, --adaptive, --samples-out, --denoise or --robust\n");
+        return 2;
+    }
     if (progressive && gpus > 1) {
         std::fprintf(stderr, "Error: --preview-every, --time-limit, --variance-out, --adaptive, --samples-out, --denoise and --robust render on one device (a film object), "
                              "not on the %d of --gpus / --devices\n", gpus);
@@ -349,6 +357,28 @@ int main(int argc, char** argv) {
     // plus spt_film_filter, the plain run included (in increments of spp / 16).  What assumes that every sample of a pixel
     // weighs 1, and films over several devices, cannot serve it
     const bool weighted = filter.type != SPT_FILTER_BOX;
+    if (weighted && !animate_path.empty()) {
+        std::fprintf(stderr, "Error: --animate needs the box filter; the renderer's filter is weighted (a read-out of one film)\n");
+        spt_host_scene_free(hs);
+        return 2;
+    }
+    // --animate FILE: the frames are read and checked against the scene before any device is touched
+    spt_host_animation* animation = nullptr;
+    struct AnimationOwner {   // freed on every way out of main
+        spt_host_animation*& a;
+        ~AnimationOwner() { spt_host_animation_free(a); }
+    } animation_owner{animation};
+    if (!animate_path.empty()) {
+        if (spt_host_animation_load(animate_path.c_str(), hs, &animation) != SPT_OK) {
+            std::fprintf(stderr, "Error: %s\n", spt_host_last_error());
+            spt_host_scene_free(hs);
+            return 2;
+        }
+        if (gpus == 1) {
+            device = device_list.empty() ? 0 : device_list[0];
+            gpus = 0;
+        }
+    }
     if (weighted) {
         if (!variance_out.empty() || adaptive_on || !samples_out.empty() || denoise || robust || film_devices_given || gpus > 1) {
             std::fprintf(stderr, "Error: --variance-out, --adaptive, --samples-out, --denoise, --robust, --film-devices and several --gpus / --devices need the box "
@@ -440,6 +470,44 @@ int main(int argc, char** argv) {
         }
         std::fprintf(stderr, "Scene JSON is loaded successfully. Rendering...\n");
         t0 = std::chrono::steady_clock::now();
+        if (animation) {
+            // one device scene for all frames: every frame moves its instances (spt_host_scene_set_transforms through the
+            // animation), hands the new arrays to spt_scene_update and renders the plain run into <out stem>_%04d<ext>
+            const size_t slash = out_path.find_last_of('/'), dot = out_path.find_last_of('.');
+            const bool has_ext = dot != std::string::npos && (slash == std::string::npos || dot > slash);
+            const std::string stem = has_ext ? out_path.substr(0, dot) : out_path, ext = has_ext ? out_path.substr(dot) : std::string();
+            auto anim_fail = [&](const char* msg) {
+                std::fprintf(stderr, "Error: %s\n", msg);
+                spt_scene_destroy(ds);
+                spt_host_scene_free(hs);
+                return 1;
+            };
+            const uint32_t n_frames = spt_host_animation_frames(animation);
+            for (uint32_t f = 0; f < n_frames; ++f) {
+                if (spt_host_animation_apply(animation, f, hs) != SPT_OK) return anim_fail(spt_host_last_error());
+                const spt_scene_desc* dsc = spt_host_scene_desc(hs);
+                spt_scene_update_desc up;
+                std::memset(&up, 0, sizeof up);
+                up.size = (uint32_t)sizeof up;
+                up.n_tlas_nodes = dsc->n_tlas_nodes; up.tlas_nodes = dsc->tlas_nodes;
+                up.n_instances = dsc->n_instances; up.instances = dsc->instances;
+                up.n_lights = dsc->n_lights; up.lights = dsc->lights;
+                up.light_alias = dsc->light_alias;
+                if (spt_scene_update(ds, &up) != SPT_OK) return anim_fail(spt_last_error());
+                if (spt_render(ds, &cam, &params, film.data(), st.data()) != SPT_OK) return anim_fail(spt_last_error());
+                char num[16];
+                std::snprintf(num, sizeof num, "_%04u", f);
+                std::vector<uint8_t> rgb8(film.size());
+                spt_host_film_to_rgb8(film.data(), (uint64_t)width * height, rgb8.data());
+                if (spt_host_write_image((stem + num + ext).c_str(), rgb8.data(), width, height) != SPT_OK)
+                    std::printf("Failed to save image, err: %s\n", spt_host_last_error());  // printed and ignored, like pt.rs:292-294
+            }
+            const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            std::fprintf(stderr, "Finished, time used: %.3fs (%u frames)\n", sec, n_frames);
+            spt_scene_destroy(ds);
+            spt_host_scene_free(hs);
+            return 0;
+        }
         if (!progressive && spt_render(ds, &cam, &params, film.data(), st.data()) != SPT_OK) {
             std::fprintf(stderr, "Error: %s\n", spt_last_error());
             return 1;

@@ -408,7 +408,9 @@ uint32_t build_wide(const spt_bvh_node* nodes, uint32_t root, std::vector<float4
 // with exactly the f32 decode arithmetic of node4_test.
 // `stack_need` receives the worst-case number of simultaneously pending entries of a near-first walk: a
 // node with n children leaves n - 1 of them pending while the first is descended, in whatever order.
-uint32_t build_n4(const spt_bvh_node* nodes, uint32_t root, std::vector<float4>& out, uint32_t* stack_need, const char* what) {
+// `base`: the node index of out[0] (spt_scene_update builds the streaming walker's TLAS into an array of its own that sits behind
+// the BLAS nodes on the device).
+uint32_t build_n4(const spt_bvh_node* nodes, uint32_t root, std::vector<float4>& out, uint32_t* stack_need, const char* what, uint32_t base = 0u) {
     *stack_need = 0;
     auto leaf_ref = [&](const spt_bvh_node& nd) -> uint32_t {
         uint32_t cnt = nd.b & ~SPT_LEAF_FLAG;
@@ -424,7 +426,7 @@ uint32_t build_n4(const spt_bvh_node* nodes, uint32_t root, std::vector<float4>&
     struct Item { uint32_t node32, n4; };
     std::vector<Item> st;
     auto alloc = [&]() -> uint32_t {
-        uint32_t i = (uint32_t)(out.size() / 4);
+        uint32_t i = base + (uint32_t)(out.size() / 4);
         out.resize(out.size() + 4, make_float4(0, 0, 0, 0));
         return i;
     };
@@ -490,17 +492,17 @@ uint32_t build_n4(const spt_bvh_node* nodes, uint32_t root, std::vector<float4>&
         }
         auto pack4 = [](const uint32_t q[4]) { return q[0] | (q[1] << 8) | (q[2] << 16) | (q[3] << 24); };
         auto as_f = [](uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; };
-        float4* f = &out[(size_t)it.n4 * 4];
+        float4* f = &out[(size_t)(it.n4 - base) * 4];
         f[0] = make_float4(par.bmin[0], par.bmin[1], par.bmin[2], as_f(eb[0] | (eb[1] << 8) | (eb[2] << 16) | (n << 24)));
         f[1] = make_float4(as_f(pack4(qlo[0])), as_f(pack4(qlo[1])), as_f(pack4(qlo[2])), as_f(pack4(qhi[0])));
         f[2] = make_float4(as_f(pack4(qhi[1])), as_f(pack4(qhi[2])), as_f(refs[0]), as_f(refs[1]));
         f[3] = make_float4(as_f(refs[2]), as_f(refs[3]), 0.0f, 0.0f);
     }
     // children are allocated after their parent, so one reverse sweep sees every child before its parent
-    const uint32_t end_n4 = (uint32_t)(out.size() / 4);
+    const uint32_t end_n4 = base + (uint32_t)(out.size() / 4);
     std::vector<uint32_t> need(end_n4 - root_n4, 0u);
     for (uint32_t i = end_n4; i-- > root_n4;) {
-        const float4* f = &out[(size_t)i * 4];
+        const float4* f = &out[(size_t)(i - base) * 4];
         uint32_t hdr, refs[4];
         std::memcpy(&hdr, &f[0].w, 4);
         std::memcpy(&refs[0], &f[2].z, 4);
@@ -548,9 +550,64 @@ struct BezierLib {
     decltype(&spt_trace_closest) trace_closest = nullptr;
     decltype(&spt_trace_any) trace_any = nullptr;
     decltype(&spt_radiance) radiance = nullptr;
+    decltype(&spt_scene_update) scene_update = nullptr;   // (resolved if present, like film_filter)
     decltype(&spt_debug_bxdf) debug_bxdf = nullptr;
     decltype(&spt_debug_render_info) debug_render_info = nullptr;
     decltype(&spt_last_error) last_error = nullptr;
+};
+
+// What spt_scene_update needs again of the descriptor a scene was created from, and of what spt_scene_create derived from the
+// part of it that an update keeps: the scene's own copy, nothing of the caller's memory.
+struct SceneFixed {
+    uint32_t aggregate = 0, light_sampler = 0, n_instances = 0, n_lights = 0, n_meshes = 0, n_spheres = 0, n_surfaces = 0, n_bezier_patches = 0, n_tris = 0;
+    int32_t env_light_index = -1;
+    uint32_t env_light_type = 0;      // the type of lights[env_light_index] at creation
+    bool has_env = false;
+    bool own_bvh = true;              // SPT_REFERENCE_BVH was not set
+    bool n4 = false;                  // the large-scene form: compressed 4-wide BLAS nodes, dynamic sections behind the static ones
+    uint32_t blas_depth = 0;          // of the caller's BLAS trees
+    uint32_t own_blas_depth = 0;      // of the device-built ones
+    uint32_t max_blas_need = 0;       // pending entries of a walk of the 4-wide BLAS
+    uint32_t blas_f4 = 0;             // the BLAS nodes of the form in use, in float4
+    size_t tables_bytes = 0;          // what the shading tables add behind an LDS-resident blob
+    bool simple_fixed = false, fused_fixed = false;   // spt_scene::simple / ::fused but for the lights' types
+    std::vector<uint32_t> mesh_tris;                  // triangle count per mesh
+    std::vector<spt_sphere> spheres;
+    std::vector<uint8_t> surf_class, surf_emissive;   // per surface: the shade class of its material, luminance of its emission > 0
+    std::vector<std::array<double, 6>> mesh_box;      // object-space bounds of every mesh's vertices (lo, hi)
+    std::vector<float4> mesh_rec;                     // the blob's mesh records of the form in use
+    // LDS-resident scenes only (<= 32 KB): the static sections of the blob, which an update writes again with the dynamic ones
+    std::vector<float4> wblas, tri_sec, attr_sec, surf_sec, mat_sec;
+    uint32_t tail_first = 0, tail_cap = 0;            // n4: where the dynamic sections start in the blob and what the allocation holds of them (float4)
+};
+
+// The four arrays an update replaces, as spt_scene_create and spt_scene_update both read them (the caller's memory)
+struct DynView {
+    uint32_t aggregate, light_sampler;
+    uint32_t n_tlas_nodes, n_instances, n_lights, n_spheres, n_meshes, n_bezier_patches, n_surfaces;
+    bool has_env;
+    const spt_bvh_node* tlas_nodes;
+    const spt_instance* instances;
+    const spt_light* lights;
+    spt_alias_table light_alias;
+    const uint8_t* surf_emissive;
+};
+
+// Everything of a scene that depends on where its instances and lights are: built on the host from a DynView, then committed
+struct SceneDynamic {
+    uint32_t tlas_root = 0, s_root = 0, n_tlas_nodes = 0, stack_cap = 0, flat = 0;
+    float tlas_lo[3] = {0, 0, 0}, tlas_hi[3] = {0, 0, 0};
+    uint32_t o_sinst = 0, o_tlas = 0, o_inst = 0, o_mesh = 0, o_sph = 0, o_blas = 0, o_tri = 0, o_tord = 0, o_attr = 0, o_surf = 0, o_mat = 0, o_light = 0;
+    uint32_t geo_f4 = 0;
+    uint32_t tail_first = 0;          // large-scene form: where the sections an update rewrites start (dyn_layout)
+    bool swalk = false, lds_tables = false, fused = false, simple = false, eye_ok = false;
+    std::vector<uint8_t> cls;
+    std::vector<uint32_t> tlas_order;
+    std::vector<float4> wtlas, stlas, sinst;
+    std::vector<float4> blob;         // the whole blob (LDS-resident scenes, creation) or the dynamic sections from SceneFixed::tail_first
+    double bs_center[3] = {0, 0, 0}, bs_radius = 0, world_lo[3] = {0, 0, 0}, world_hi[3] = {0, 0, 0};
+    bool bs_valid = false;
+    std::vector<std::array<double, 24>> hull_corners;
 };
 
 struct spt_scene {
@@ -636,6 +693,14 @@ struct spt_scene {
     bool textured = false;  // a material recipe, normal map or emissive map samples textures per hit (k_shade<2, .>)
     DeviceBuffer textures, tex_prog, tex_root, tex_chain, images, image_levels, texels, recipes;
     std::vector<hipEvent_t> events;
+    // spt_scene_update: the creation's fixed part, the films alive on the scene, the page-locked slot the dynamic part goes up
+    // through and the event that says the slot's copies are done; what spt_debug_render_info reports of the updates
+    SceneFixed fixed;
+    uint32_t live_films = 0;
+    PinnedBuffer upd_stage;
+    hipEvent_t ev_upd = nullptr;
+    bool upd_recorded = false;
+    uint64_t updates = 0, update_bytes = 0;
     ~spt_scene() {
         if (fwd) { fwd->destroy(inner); return; }
         (void)hipSetDevice(device);
@@ -644,7 +709,7 @@ struct spt_scene {
         if (ev_join) (void)hipEventDestroy(ev_join);
         if (ev_out_ready) (void)hipEventDestroy(ev_out_ready);
         if (ev_copy_done) (void)hipEventDestroy(ev_copy_done);
-        for (auto e : {ev_main[0], ev_main[1], ev_film[0], ev_film[1], ev_film_idle, ev_keep[0], ev_keep[1], ev_ray[0], ev_ray[1]})
+        for (auto e : {ev_main[0], ev_main[1], ev_film[0], ev_film[1], ev_film_idle, ev_keep[0], ev_keep[1], ev_ray[0], ev_ray[1], ev_upd})
             if (e) (void)hipEventDestroy(e);
         if (stream_film) (void)hipStreamDestroy(stream_film);
         if (stream2) (void)hipStreamDestroy(stream2);
@@ -703,6 +768,63 @@ struct spt_film {
 
 namespace {
 
+bool surface_emits(const spt_surface& sf) { return 0.299f * sf.emissive[0] + 0.587f * sf.emissive[1] + 0.114f * sf.emissive[2] > 0.0f; }
+
+DynView dyn_view(const spt_scene_desc& s, const uint8_t* surf_emissive) {
+    return DynView{s.aggregate, s.light_sampler, s.n_tlas_nodes, s.n_instances, s.n_lights, s.n_spheres, s.n_meshes, s.n_bezier_patches, s.n_surfaces,
+                   s.env.width != 0 && s.env.height != 0, s.tlas_nodes, s.instances, s.lights, s.light_alias, surf_emissive};
+}
+
+// The checks of the arrays an update replaces: spt_scene_create ("scene desc") and spt_scene_update ("scene_update") share them
+void validate_instances(const DynView& s, const char* who) {
+    const std::string w(who);
+    for (uint32_t i = 0; i < s.n_instances; ++i) {
+        const spt_instance& in = s.instances[i];
+        if (in.prim_type == SPT_PRIM_SPHERE) {
+            if (in.prim_id >= s.n_spheres) fail(SPT_ERR_INVALID_ARG, w + ": instance sphere index out of range");
+        } else if (in.prim_type == SPT_PRIM_MESH) {
+            if (in.prim_id >= s.n_meshes) fail(SPT_ERR_INVALID_ARG, w + ": instance mesh index out of range");
+        } else if (in.prim_type == SPT_PRIM_BEZIER) {
+            if (!SPT_WITH_BEZIER) fail(SPT_ERR_UNSUPPORTED, w + ": Bezier instances are served by libspt_hip_bez.so");   // not reached: spt_scene_create forwards
+            if (in.prim_id >= s.n_bezier_patches) fail(SPT_ERR_INVALID_ARG, w + ": instance Bezier patch index out of range");
+            // CubicBezier::sample / pdf / surface_area are `unimplemented!` in the reference (bezier.rs:180-190)
+            if (in.light >= 0) fail(SPT_ERR_UNSUPPORTED, w + ": a Bezier patch cannot be a shape light");
+        } else {
+            fail(SPT_ERR_INVALID_ARG, w + ": bad instance prim_type");
+        }
+        if (in.surface >= s.n_surfaces) fail(SPT_ERR_INVALID_ARG, w + ": instance surface index out of range");
+        if (in.light >= (int32_t)s.n_lights) fail(SPT_ERR_INVALID_ARG, w + ": instance light index out of range");
+        if (in.light >= 0 && (s.lights[in.light].type != SPT_LIGHT_SHAPE || s.lights[in.light].instance != i))
+            fail(SPT_ERR_INVALID_ARG, w + ": instance light does not name the shape light of this instance");
+        // pdf_shape_light of the power_is sampler looks the instance up in its light map (power_is.rs:84-86; the reference
+        // panics on a missing key): an emissive instance that is not a light would index light_alias.props[-1]
+        if (s.light_sampler == SPT_LIGHT_SAMPLER_POWER_IS && in.light < 0) {
+            if (s.surf_emissive[in.surface])
+                fail(SPT_ERR_INVALID_ARG, w + ": power_is light sampler and an emissive instance without a shape light");
+        }
+    }
+}
+
+void validate_lights(const DynView& s, const char* who) {
+    const std::string w(who);
+    for (uint32_t i = 0; i < s.n_lights; ++i) {
+        const spt_light& l = s.lights[i];
+        if (l.type > SPT_LIGHT_ENV) fail(SPT_ERR_INVALID_ARG, w + ": unknown light type");
+        if (l.type == SPT_LIGHT_SHAPE && l.instance >= s.n_instances) fail(SPT_ERR_INVALID_ARG, w + ": shape light instance out of range");
+        if (l.type == SPT_LIGHT_ENV && !s.has_env) fail(SPT_ERR_INVALID_ARG, w + ": env light without env map");
+    }
+}
+
+void validate_light_alias(const DynView& s, const char* who) {
+    const std::string w(who);
+    if (s.light_sampler == SPT_LIGHT_SAMPLER_POWER_IS && s.n_lights) {
+        if (s.light_alias.n != s.n_lights || !s.light_alias.props || !s.light_alias.u || !s.light_alias.k)
+            fail(SPT_ERR_INVALID_ARG, w + ": power_is sampler needs an alias table over the lights");
+        for (uint32_t i = 0; i < s.n_lights; ++i)
+            if (s.light_alias.k[i] >= s.n_lights) fail(SPT_ERR_INVALID_ARG, w + ": light alias index out of range");
+    }
+}
+
 void validate(const spt_scene_desc& s) {
     if (s.abi_version != SPT_ABI_VERSION) fail(SPT_ERR_INVALID_ARG, "scene desc: abi_version mismatch");
     if (s.aggregate > SPT_AGGREGATE_BVH) fail(SPT_ERR_INVALID_ARG, "scene desc: bad aggregate");
@@ -727,32 +849,10 @@ void validate(const spt_scene_desc& s) {
     need(s.lights, s.n_lights, "lights");
     if (s.n_instances && s.aggregate == SPT_AGGREGATE_BVH && s.n_tlas_nodes == 0)
         fail(SPT_ERR_INVALID_ARG, "scene desc: bvh aggregate without TLAS nodes");
-    for (uint32_t i = 0; i < s.n_instances; ++i) {
-        const spt_instance& in = s.instances[i];
-        if (in.prim_type == SPT_PRIM_SPHERE) {
-            if (in.prim_id >= s.n_spheres) fail(SPT_ERR_INVALID_ARG, "scene desc: instance sphere index out of range");
-        } else if (in.prim_type == SPT_PRIM_MESH) {
-            if (in.prim_id >= s.n_meshes) fail(SPT_ERR_INVALID_ARG, "scene desc: instance mesh index out of range");
-        } else if (in.prim_type == SPT_PRIM_BEZIER) {
-            if (!SPT_WITH_BEZIER) fail(SPT_ERR_UNSUPPORTED, "scene desc: Bezier instances are served by libspt_hip_bez.so");   // not reached: spt_scene_create forwards
-            if (in.prim_id >= s.n_bezier_patches) fail(SPT_ERR_INVALID_ARG, "scene desc: instance Bezier patch index out of range");
-            // CubicBezier::sample / pdf / surface_area are `unimplemented!` in the reference (bezier.rs:180-190)
-            if (in.light >= 0) fail(SPT_ERR_UNSUPPORTED, "scene desc: a Bezier patch cannot be a shape light");
-        } else {
-            fail(SPT_ERR_INVALID_ARG, "scene desc: bad instance prim_type");
-        }
-        if (in.surface >= s.n_surfaces) fail(SPT_ERR_INVALID_ARG, "scene desc: instance surface index out of range");
-        if (in.light >= (int32_t)s.n_lights) fail(SPT_ERR_INVALID_ARG, "scene desc: instance light index out of range");
-        if (in.light >= 0 && (s.lights[in.light].type != SPT_LIGHT_SHAPE || s.lights[in.light].instance != i))
-            fail(SPT_ERR_INVALID_ARG, "scene desc: instance light does not name the shape light of this instance");
-        // pdf_shape_light of the power_is sampler looks the instance up in its light map (power_is.rs:84-86; the reference
-        // panics on a missing key): an emissive instance that is not a light would index light_alias.props[-1]
-        if (s.light_sampler == SPT_LIGHT_SAMPLER_POWER_IS && in.light < 0) {
-            const spt_surface& sf = s.surfaces[in.surface];
-            if (0.299f * sf.emissive[0] + 0.587f * sf.emissive[1] + 0.114f * sf.emissive[2] > 0.0f)
-                fail(SPT_ERR_INVALID_ARG, "scene desc: power_is light sampler and an emissive instance without a shape light");
-        }
-    }
+    std::vector<uint8_t> emissive(s.n_surfaces, 0);
+    for (uint32_t i = 0; i < s.n_surfaces; ++i) emissive[i] = surface_emits(s.surfaces[i]) ? 1 : 0;
+    const DynView v = dyn_view(s, emissive.data());
+    validate_instances(v, "scene desc");
     for (uint32_t i = 0; i < s.n_meshes; ++i) {
         const spt_mesh& m = s.meshes[i];
         if (m.root >= s.n_blas_nodes || (uint64_t)m.tri_first + m.tri_count > s.n_tris || m.tri_count == 0)
@@ -856,20 +956,10 @@ void validate(const spt_scene_desc& s) {
     for (uint32_t i = 0; i < s.n_surfaces; ++i)
         if (s.surfaces[i].normal_map > s.n_textures || s.surfaces[i].emissive_map > s.n_textures)
             fail(SPT_ERR_INVALID_ARG, "scene desc: surface map out of range");
-    for (uint32_t i = 0; i < s.n_lights; ++i) {
-        const spt_light& l = s.lights[i];
-        if (l.type > SPT_LIGHT_ENV) fail(SPT_ERR_INVALID_ARG, "scene desc: unknown light type");
-        if (l.type == SPT_LIGHT_SHAPE && l.instance >= s.n_instances) fail(SPT_ERR_INVALID_ARG, "scene desc: shape light instance out of range");
-        if (l.type == SPT_LIGHT_ENV && (s.env.width == 0 || s.env.height == 0)) fail(SPT_ERR_INVALID_ARG, "scene desc: env light without env map");
-    }
+    validate_lights(v, "scene desc");
     if (s.env_light_index >= (int32_t)s.n_lights) fail(SPT_ERR_INVALID_ARG, "scene desc: env_light_index out of range");
     if (s.light_sampler > SPT_LIGHT_SAMPLER_POWER_IS) fail(SPT_ERR_INVALID_ARG, "scene desc: bad light_sampler");
-    if (s.light_sampler == SPT_LIGHT_SAMPLER_POWER_IS && s.n_lights) {
-        if (s.light_alias.n != s.n_lights || !s.light_alias.props || !s.light_alias.u || !s.light_alias.k)
-            fail(SPT_ERR_INVALID_ARG, "scene desc: power_is sampler needs an alias table over the lights");
-        for (uint32_t i = 0; i < s.n_lights; ++i)
-            if (s.light_alias.k[i] >= s.n_lights) fail(SPT_ERR_INVALID_ARG, "scene desc: light alias index out of range");
-    }
+    validate_light_alias(v, "scene desc");
     if (s.env.width || s.env.height) {
         uint64_t n = (uint64_t)s.env.width * s.env.height;
         if (n == 0 || n > 0x7fffffffull) fail(SPT_ERR_INVALID_ARG, "scene desc: bad env size");
@@ -880,6 +970,334 @@ void validate(const spt_scene_desc& s) {
     }
 }
 
+// ---- the instance-dependent part of a scene (spt_scene_create, spt_scene_update) ----------------------------------------
+uint8_t shade_class(const spt_scene_desc& s, const spt_material& m) {
+    // the class a hit is queued under for the shade stage of bounce >= 1 (kernels.h, kClasses): by the code path its material
+    // takes through mat_sample / mat_eval / mat_pdf and by whether it has a light sample at all
+    uint32_t b = m.bxdf;
+    if (m.recipe != 0u) {      // evaluated per hit: the kind the recipe usually resolves to
+        switch (s.material_recipes[m.recipe - 1u].type) {
+        case SPT_MAT_LAMBERT: b = SPT_BXDF_LAMBERT; break;
+        case SPT_MAT_CONDUCTOR: b = SPT_BXDF_MICROFACET_CONDUCTOR; break;
+        case SPT_MAT_DIELECTRIC: b = SPT_BXDF_MICROFACET_DIELECTRIC; break;
+        default: b = SPT_BXDF_MICROFACET_PLASTIC; break;
+        }
+    }
+    switch (b) {
+    case SPT_BXDF_LAMBERT: return 0;
+    case SPT_BXDF_MICROFACET_CONDUCTOR: return 1;
+    case SPT_BXDF_SPECULAR_CONDUCTOR: return 2;
+    case SPT_BXDF_MICROFACET_DIELECTRIC: return 3;
+    case SPT_BXDF_SPECULAR_DIELECTRIC: return 4;
+    case SPT_BXDF_PSEUDO: return 5;
+    default: return 6;       // the plastic / PBR lobes, glints
+    }
+}
+
+bool only_delta_lights(const DynView& s) {
+    bool delta = true;
+    for (uint32_t i = 0; i < s.n_lights; ++i) delta = delta && s.lights[i].type <= SPT_LIGHT_SPOT;
+    return delta;
+}
+
+constexpr uint32_t kBlock = 256;
+constexpr size_t kStackBytes = (size_t)kLdsStack * 2 * kBlock * sizeof(uint32_t);   // (ref, t0) per LDS level
+
+// The trees over the instances, the streaming walker's entries and the instances' classes.
+void dyn_trees(const SceneFixed& fx, const DynView& s, bool n4, SceneDynamic& dy) {
+    // stack need: reference-order traversal holds at most depth+1 entries per level of nesting
+    uint32_t tlas_depth = 0;
+    if (s.aggregate == SPT_AGGREGATE_BVH) tlas_depth = bvh_depth(s.tlas_nodes, s.n_tlas_nodes, 0, s.n_instances, "tlas");
+    // near-first traversal pushes at most one (far) child per 2-wide level (4-wide trees: see build_n4)
+    const uint32_t cap = tlas_depth + fx.blas_depth + 2;
+    if (!fx.own_bvh && cap > kLdsStack + kSpillStack) fail(SPT_ERR_UNSUPPORTED, "BVH deeper than the traversal stack (48 levels)");
+    if (tlas_depth + 2 > kLdsStack + kSpillStack) fail(SPT_ERR_UNSUPPORTED, "TLAS deeper than the traversal stack (48 levels)");
+    dy.stack_cap = cap;
+    dy.n_tlas_nodes = s.n_tlas_nodes;
+    dy.cls.assign(std::max<uint32_t>(s.n_instances, 1u), 0);
+    for (uint32_t i = 0; i < s.n_instances; ++i) dy.cls[i] = fx.surf_class[s.instances[i].surface];
+    dy.wtlas.clear();
+    dy.tlas_root = 0;
+    for (int k = 0; k < 3; ++k) { dy.tlas_lo[k] = 0.0f; dy.tlas_hi[k] = 0.0f; }
+    // TLAS leaf slot -> instance index: identity for the caller's tree (its leaves index the instance array) and
+    // for a GROUP aggregate, the leaf order of the device-built tree otherwise
+    dy.tlas_order.resize(s.n_instances);
+    for (uint32_t i = 0; i < s.n_instances; ++i) dy.tlas_order[i] = i;
+    std::vector<spt_bvh_node> own_tlas;
+    if (s.aggregate == SPT_AGGREGATE_BVH && s.n_tlas_nodes) {
+        if (fx.own_bvh && s.n_instances) {
+            build_sah_tlas(s.instances, s.n_instances, own_tlas, dy.tlas_order);   // boxes padded by the builder
+            tlas_depth = bvh_depth(own_tlas.data(), (uint32_t)own_tlas.size(), 0, s.n_instances, "device tlas");
+            if (tlas_depth + 2 > kLdsStack + kSpillStack) fail(SPT_ERR_UNSUPPORTED, "device TLAS deeper than the traversal stack (48 levels)");
+        }
+        const spt_bvh_node* tlas_src = own_tlas.empty() ? s.tlas_nodes : own_tlas.data();
+        const uint32_t sup = build_wide(tlas_src, 0, dy.wtlas, 0xffffffffu, "tlas", false);
+        std::memcpy(&dy.tlas_root, &dy.wtlas[(size_t)sup * 4].w, 4);      // left child of the super-root = real root
+        for (int k = 0; k < 3; ++k) { dy.tlas_lo[k] = tlas_src[0].bmin[k]; dy.tlas_hi[k] = tlas_src[0].bmax[k]; }
+    }
+    if (fx.own_bvh && fx.n_meshes && tlas_depth + fx.own_blas_depth + 2 > kLdsStack + kSpillStack)
+        fail(SPT_ERR_UNSUPPORTED, "device BVH deeper than the traversal stack (48 levels)");
+    if (n4 && fx.n_meshes && tlas_depth + fx.max_blas_need + 2 > kLdsStack + kSpillStack)
+        fail(SPT_ERR_UNSUPPORTED, "4-wide BVH needs more than the traversal stack (48 entries)");
+    // streaming walker (stream.h): a 4-wide TLAS behind the BLAS nodes (refs of both levels index one array) and
+    // 96-byte instance entry records in its leaf order.  Its boxes only cull (quantised outward, relaxed
+    // test), so one tree serves both BVH modes and a GROUP aggregate alike.
+    dy.swalk = false;
+    dy.s_root = 0u;
+    dy.stlas.clear();
+    dy.sinst.clear();
+    if (n4 && s.n_instances) {
+        try {
+            std::vector<spt_bvh_node> group_tlas;
+            std::vector<uint32_t> s_order = dy.tlas_order;
+            const spt_bvh_node* src = nullptr;
+            if (s.aggregate == SPT_AGGREGATE_BVH && s.n_tlas_nodes) {
+                src = own_tlas.empty() ? s.tlas_nodes : own_tlas.data();
+            } else {
+                build_sah_tlas(s.instances, s.n_instances, group_tlas, s_order);
+                src = group_tlas.data();
+                for (int k = 0; k < 3; ++k) { dy.tlas_lo[k] = src[0].bmin[k]; dy.tlas_hi[k] = src[0].bmax[k]; }
+            }
+            uint32_t need_t = 0;
+            dy.s_root = build_n4(src, 0, dy.stlas, &need_t, "tlas", fx.blas_f4 / 4u);
+            // + 1: a TLAS leaf of several instances keeps its remaining instances as one extra entry
+            if (need_t + fx.max_blas_need + 3 > kLdsStack + kSpillStack) fail(SPT_ERR_UNSUPPORTED, "4-wide TLAS + BLAS need more than the traversal stack");
+            dy.sinst.assign((size_t)s.n_instances * 6, make_float4(0, 0, 0, 0));
+            auto as_f = [](uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; };
+            for (uint32_t slot = 0; slot < s.n_instances; ++slot) {
+                const uint32_t ii = s_order[slot];
+                const spt_instance& in = s.instances[ii];
+                float4* r = &dy.sinst[(size_t)slot * 6];
+                std::memcpy(r, in.inv, 48);
+                r[3] = make_float4(as_f(ii), as_f(in.prim_type), as_f(in.prim_id), 0.0f);
+                if (in.prim_type == SPT_PRIM_MESH) { r[4] = fx.mesh_rec[2 * in.prim_id]; r[5] = fx.mesh_rec[2 * in.prim_id + 1]; }
+                else if (in.prim_type == SPT_PRIM_SPHERE) { const spt_sphere& sp = fx.spheres[in.prim_id]; r[4] = make_float4(sp.center[0], sp.center[1], sp.center[2], sp.radius); }
+            }
+            dy.swalk = std::getenv("SPT_NO_STREAM") == nullptr;
+            // (patches under the caller's exact boxes: only the reference's visit order reproduces which near misses it loses)
+            if (!fx.own_bvh && fx.n_bezier_patches != 0) dy.swalk = false;
+        } catch (const AbiError&) {
+            dy.stlas.clear();   // e.g. an instance box too large to quantise: the walkers of trace.h serve the scene
+            dy.sinst.clear();
+            dy.swalk = false;
+        }
+    }
+}
+
+// Where the sections of the traversal blob sit, in float4.  LDS-resident form: [sinst | tlas | instances | meshes | spheres | blas |
+// tri | order] and, when they fit, the shading tables [attr | surfaces | materials | lights].  Large-scene form (n4): the sections
+// an update keeps first, [meshes | spheres | tri | blas], then the ones it rewrites in place, [4-wide TLAS | sinst | tlas |
+// instances | order] (the 4-wide TLAS directly behind the BLAS nodes: refs of both levels index one array from o_blas).
+// Returns the length without the tables.
+size_t dyn_layout(const SceneFixed& fx, SceneDynamic& dy, bool n4, bool tables) {
+    auto f4 = [](size_t bytes) { return (bytes + 15) / 16; };
+    size_t at = 0;
+    auto put = [&](size_t n) { const size_t off = at; at += n; return (uint32_t)off; };
+    const size_t n = fx.n_instances;
+    const size_t inst_f4 = f4(n * sizeof(spt_instance)), mesh_f4 = fx.mesh_rec.size(), sph_f4 = f4((size_t)fx.n_spheres * sizeof(spt_sphere)),
+                 tri_f4 = f4((size_t)fx.n_tris * sizeof(spt_tri_pos)), ord_f4 = f4(n * sizeof(uint32_t));
+    if (!n4) {
+        dy.o_sinst = put(dy.sinst.size());
+        dy.o_tlas = put(dy.wtlas.size());
+        dy.o_inst = put(inst_f4);
+        dy.o_mesh = put(mesh_f4);
+        dy.o_sph = put(sph_f4);
+        dy.o_blas = put(fx.blas_f4);
+        dy.o_tri = put(tri_f4);
+        dy.o_tord = put(ord_f4);
+    } else {
+        dy.o_mesh = put(mesh_f4);
+        dy.o_sph = put(sph_f4);
+        dy.o_tri = put(tri_f4);
+        dy.o_blas = put(fx.blas_f4);
+        if (at > 0x7fffffffull / 16) fail(SPT_ERR_UNSUPPORTED, "scene geometry larger than 32 GiB");
+        dy.tail_first = (uint32_t)at;
+        put(dy.stlas.size());
+        dy.o_sinst = put(dy.sinst.size());
+        dy.o_tlas = put(dy.wtlas.size());
+        dy.o_inst = put(inst_f4);
+        dy.o_tord = put(ord_f4);
+    }
+    const size_t plain = at;
+    dy.o_attr = dy.o_surf = dy.o_mat = dy.o_light = 0;
+    if (tables) {
+        dy.o_attr = put(fx.attr_sec.size());
+        dy.o_surf = put(fx.surf_sec.size());
+        dy.o_mat = put(fx.mat_sec.size());
+        dy.o_light = put(f4((size_t)fx.n_lights * sizeof(spt_light)));
+    }
+    if (at > 0x7fffffffull / 16) fail(SPT_ERR_UNSUPPORTED, "scene geometry larger than 32 GiB");
+    dy.geo_f4 = (uint32_t)at;
+    return plain;
+}
+
+// The static sections of the blob as spt_scene_create has them at hand (a large scene's are not kept)
+struct StaticSections {
+    const float4* wblas;
+    const void* tri;
+};
+
+// Writes the sections from float4 `first` on into dy.blob (first = 0: the whole blob, which needs `st`).
+void dyn_fill(const SceneFixed& fx, const DynView& s, SceneDynamic& dy, bool n4, uint32_t first, const StaticSections* st) {
+    dy.blob.assign((size_t)dy.geo_f4 - first, make_float4(0, 0, 0, 0));
+    auto write = [&](uint32_t off, const void* src, size_t bytes) {
+        if (bytes) std::memcpy(&dy.blob[off - first], src, bytes);
+    };
+    if (first == 0) {
+        write(dy.o_mesh, fx.mesh_rec.data(), fx.mesh_rec.size() * 16);
+        write(dy.o_sph, fx.spheres.data(), fx.spheres.size() * sizeof(spt_sphere));
+        write(dy.o_blas, st->wblas, (size_t)fx.blas_f4 * 16);
+        write(dy.o_tri, st->tri, (size_t)fx.n_tris * sizeof(spt_tri_pos));
+    }
+    if (n4) write(dy.o_blas + fx.blas_f4, dy.stlas.data(), dy.stlas.size() * 16);
+    write(dy.o_sinst, dy.sinst.data(), dy.sinst.size() * 16);
+    write(dy.o_tlas, dy.wtlas.data(), dy.wtlas.size() * 16);
+    {   // the instance records as they are, pad[0] carrying the instance's class (hit_push<true> reads it from the staged copy)
+        std::vector<spt_instance> inst_copy(s.instances, s.instances + s.n_instances);
+        for (uint32_t i = 0; i < s.n_instances; ++i) { const uint32_t c = dy.cls[i]; std::memcpy(&inst_copy[i].pad[0], &c, 4); }
+        write(dy.o_inst, inst_copy.data(), (size_t)s.n_instances * sizeof(spt_instance));
+    }
+    write(dy.o_tord, dy.tlas_order.data(), dy.tlas_order.size() * sizeof(uint32_t));
+    if (dy.lds_tables) {
+        write(dy.o_attr, fx.attr_sec.data(), fx.attr_sec.size() * 16);
+        write(dy.o_surf, fx.surf_sec.data(), fx.surf_sec.size() * 16);
+        write(dy.o_mat, fx.mat_sec.data(), fx.mat_sec.size() * 16);
+        write(dy.o_light, s.lights, (size_t)s.n_lights * sizeof(spt_light));
+    }
+}
+
+// The choices that follow from the instances and the lights once the form of the geometry is known (`plain_f4`: the blob without
+// the shading tables), and the layout with the tables when they fit.
+void dyn_decide(const SceneFixed& fx, const DynView& s, SceneDynamic& dy, bool lds_geo, size_t plain_f4, size_t n_blas_ranges) {
+    // a handful of primitives: every lane tests all of them (flat.h) instead of walking the trees.  The budget is in
+    // triangle tests per ray (an instanced mesh counts once per instance, a sphere as one); SPT_FLAT_BUDGET=0 turns it off.
+    {
+        uint64_t cost = 0;
+        bool ok = lds_geo && fx.own_bvh && fx.n_bezier_patches == 0 && fx.n_tris < 65536u;   // (the caller's exact trees are walked as they are)
+        for (uint32_t i = 0; i < s.n_instances && ok; ++i) {
+            const spt_instance& in = s.instances[i];
+            if (in.prim_type == SPT_PRIM_MESH) cost += fx.mesh_tris[in.prim_id];
+            else if (in.prim_type == SPT_PRIM_SPHERE) cost += 1;
+            else ok = false;
+        }
+        const char* fb = std::getenv("SPT_FLAT_BUDGET");
+        dy.flat = ok && s.n_instances != 0 && cost <= (fb ? (uint64_t)std::atoi(fb) : (uint64_t)kFlatBudget) ? 1u : 0u;
+    }
+    const bool delta_lights = only_delta_lights(s);
+    // fused bounces (k_shade<0, ., kFused>): LDS-resident geometry + the lean simple-scene shade kernel, and
+    // the shading tables must fit behind the geometry too (see tab_ld in shading.h)
+    dy.lds_tables = lds_geo && plain_f4 * 16 + fx.tables_bytes <= 32u * 1024u && kStackBytes + plain_f4 * 16 + fx.tables_bytes <= 64u * 1024u;
+    dy.fused = dy.lds_tables && fx.fused_fixed && delta_lights;
+    dy.simple = fx.simple_fixed && delta_lights;
+    if (dy.lds_tables) dyn_layout(fx, dy, false, true);
+    {   // eye.h: an eye-relative copy per camera position is possible when every box has ONE origin to be relative to
+        bool ok = lds_geo && fx.own_bvh && fx.n_bezier_patches == 0 && fx.n_tris < 65536u && s.n_instances != 0 && std::getenv("SPT_NO_EYE_BLOB") == nullptr;
+        std::vector<uint32_t> mesh_uses(fx.n_meshes, 0u);
+        for (uint32_t i = 0; i < s.n_instances && ok; ++i) {
+            const spt_instance& in = s.instances[i];
+            if (in.prim_type == SPT_PRIM_MESH) ok = ++mesh_uses[in.prim_id] == 1u;
+            else ok = in.prim_type == SPT_PRIM_SPHERE;   // (a sphere's relative centre rides in its instance record: primitives may be shared)
+        }
+        const size_t eye_bytes = ((size_t)dy.geo_f4 + fx.n_tris) * 16;
+        dy.eye_ok = ok && eye_bytes <= 36u * 1024u && kStackBytes + eye_bytes <= 64u * 1024u && n_blas_ranges == fx.n_meshes;
+    }
+}
+
+// The bounding sphere of all instance boxes, their union and the 8 world-space corners of every instance's object-space box
+void dyn_bounds(const SceneFixed& fx, const DynView& s, SceneDynamic& dy) {
+    dy.bs_valid = false;
+    dy.hull_corners.clear();
+    if (!s.n_instances) return;
+    double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+    bool finite = true;
+    for (uint32_t i = 0; i < s.n_instances; ++i) {
+        const double margin = bezier_box_margin(s.instances[i]);   // the screen-space bound and the bounding sphere cull too
+        for (int k = 0; k < 3; ++k) {
+            lo[k] = std::min(lo[k], (double)s.instances[i].bmin[k] - margin);
+            hi[k] = std::max(hi[k], (double)s.instances[i].bmax[k] + margin);
+            finite = finite && std::isfinite(s.instances[i].bmin[k]) && std::isfinite(s.instances[i].bmax[k]);
+        }
+    }
+    double r2 = 0;
+    for (int k = 0; k < 3; ++k) {
+        dy.bs_center[k] = 0.5 * (lo[k] + hi[k]);
+        dy.world_lo[k] = lo[k];
+        dy.world_hi[k] = hi[k];
+        r2 += 0.25 * (hi[k] - lo[k]) * (hi[k] - lo[k]);
+    }
+    dy.bs_radius = std::sqrt(r2) * 1.001 + 1e-4;
+    dy.bs_valid = finite && std::isfinite(dy.bs_radius) && dy.bs_radius < 1e18;
+    // Object-space boxes for the per-row spans: the exact bounds of a mesh's vertices / a sphere (kept from creation), padded
+    // a little, carried to world space by the instance matrix (a rotated cube's world AABB is far larger than its silhouette).
+    // Patches keep their (margin-widened) world box: the clipping test accepts near misses (bezier_box_margin).
+    if (dy.bs_valid && s.n_instances <= 256u) {
+        dy.hull_corners.resize(s.n_instances);
+        for (uint32_t i = 0; i < s.n_instances && !dy.hull_corners.empty(); ++i) {
+            const spt_instance& in = s.instances[i];
+            double olo[3] = {1e300, 1e300, 1e300}, ohi[3] = {-1e300, -1e300, -1e300};
+            bool object_space = true;
+            if (in.prim_type == SPT_PRIM_MESH) {
+                for (int k = 0; k < 3; ++k) { olo[k] = fx.mesh_box[in.prim_id][k]; ohi[k] = fx.mesh_box[in.prim_id][3 + k]; }
+            } else if (in.prim_type == SPT_PRIM_SPHERE) {
+                const spt_sphere& sp = fx.spheres[in.prim_id];
+                for (int k = 0; k < 3; ++k) { olo[k] = (double)sp.center[k] - std::fabs((double)sp.radius); ohi[k] = (double)sp.center[k] + std::fabs((double)sp.radius); }
+            } else {
+                object_space = false;
+                const double margin = bezier_box_margin(in);
+                for (int k = 0; k < 3; ++k) { olo[k] = (double)in.bmin[k] - margin; ohi[k] = (double)in.bmax[k] + margin; }
+            }
+            double ext = 1e-30;
+            for (int k = 0; k < 3; ++k) ext = std::max(ext, ohi[k] - olo[k]);
+            bool ok = true;
+            for (int c = 0; c < 8; ++c) {
+                double o[3];
+                for (int k = 0; k < 3; ++k) o[k] = ((c >> k) & 1) ? ohi[k] + 1e-4 * ext : olo[k] - 1e-4 * ext;
+                for (int r = 0; r < 3; ++r) {
+                    double w = o[r];
+                    if (object_space) w = (double)in.fwd[r] * o[0] + (double)in.fwd[3 + r] * o[1] + (double)in.fwd[6 + r] * o[2] + (double)in.fwd[9 + r];
+                    dy.hull_corners[i][3 * c + r] = w;
+                    ok = ok && std::isfinite(w);
+                }
+            }
+            if (!ok) dy.hull_corners.clear();
+        }
+    }
+}
+
+// The host side of a committed SceneDynamic: the DScene fields, the kernel choices and the caches that depend on the instances
+// (the device copies are the caller's business: spt_scene_create uploads, spt_scene_update queues copies on the render stream)
+void dyn_commit_host(spt_scene* sc, SceneDynamic& dy, bool lds_geo) {
+    DScene& d = sc->d;
+    d.n_tlas_nodes = dy.n_tlas_nodes;
+    d.stack_cap = dy.stack_cap;
+    d.tlas_root = dy.tlas_root;
+    d.s_root = dy.s_root;
+    d.flat = dy.flat;
+    for (int k = 0; k < 3; ++k) { d.tlas_lo[k] = dy.tlas_lo[k]; d.tlas_hi[k] = dy.tlas_hi[k]; }
+    d.o_sinst = dy.o_sinst; d.o_tlas = dy.o_tlas; d.o_inst = dy.o_inst; d.o_mesh = dy.o_mesh; d.o_sph = dy.o_sph; d.o_blas = dy.o_blas;
+    d.o_tri = dy.o_tri; d.o_tord = dy.o_tord; d.o_attr = dy.o_attr; d.o_surf = dy.o_surf; d.o_mat = dy.o_mat; d.o_light = dy.o_light;
+    d.geo_f4 = dy.geo_f4;
+    d.lds_f4 = lds_geo ? d.geo_f4 : 0u;   // large scene: global fetches only (see trace.h)
+    sc->lds_bytes = kStackBytes + (size_t)d.lds_f4 * 16;
+    sc->swalk = dy.swalk;
+    sc->lds_tables = dy.lds_tables;
+    sc->fused = dy.fused;
+    sc->simple = dy.simple;
+    sc->eye_ok = dy.eye_ok;
+    sc->eye_valid = false;      // (its key is the eye position alone)
+    sc->span_key.clear();       // (... the camera and the image size)
+    if (dy.eye_ok) {
+        sc->host_blob = dy.blob;
+        sc->wtlas_f4 = (uint32_t)dy.wtlas.size();
+    } else {
+        sc->host_blob.clear();
+    }
+    for (int k = 0; k < 3; ++k) { sc->bs_center[k] = dy.bs_center[k]; sc->world_lo[k] = dy.world_lo[k]; sc->world_hi[k] = dy.world_hi[k]; }
+    sc->bs_radius = dy.bs_radius;
+    sc->bs_valid = dy.bs_valid;
+    sc->hull_corners = std::move(dy.hull_corners);
+}
+
 uint32_t shard_row_count(const spt_render_params& p) {
     uint32_t sc = p.shard_count ? p.shard_count : 1u, sr = p.strip_rows ? p.strip_rows : 1u;
     uint32_t rows = 0;
@@ -888,7 +1306,6 @@ uint32_t shard_row_count(const spt_render_params& p) {
     return rows;
 }
 
-constexpr uint32_t kBlock = 256;
 // Grid of the queue kernels (grid-stride over a queue shard).  Sizing it to exactly the resident workgroups of
 // each kernel (hipOccupancyMaxActiveBlocksPerMultiprocessor: 768 for the 144-VGPR fused shade kernel) was MEASURED
 // no better (cfg2 60.5 / 61.8 / 62.1 Gsamples/s for 1 / 2 / 3 resident rounds vs 62.4 with this fixed grid, cfg4 4.49
@@ -933,6 +1350,7 @@ const BezierLib* bezier_lib() {
                          sym(lib.debug_render_info, "spt_debug_render_info") &&
                          sym(lib.last_error, "spt_last_error") && sym(version, "spt_abi_version");
         (void)sym(lib.film_filter, "spt_film_filter");
+        (void)sym(lib.scene_update, "spt_scene_update");
         if (!all || version() != SPT_ABI_VERSION) {
             err = path + " does not export ABI version " + std::to_string(SPT_ABI_VERSION);
             return;
@@ -1026,18 +1444,41 @@ spt_status spt_scene_create(const spt_scene_desc* desc, int32_t device, spt_scen
         HIP_CHECK(hipEventCreateWithFlags(&sc->ev_fork, hipEventDisableTiming));
         HIP_CHECK(hipEventCreateWithFlags(&sc->ev_join, hipEventDisableTiming));
         const spt_scene_desc& s = *desc;
-        // stack need: reference-order traversal holds at most depth+1 entries per level of nesting
-        uint32_t tlas_depth = 0, blas_depth = 0;
-        if (s.aggregate == SPT_AGGREGATE_BVH) tlas_depth = bvh_depth(s.tlas_nodes, s.n_tlas_nodes, 0, s.n_instances, "tlas");
+        SceneFixed& fx = sc->fixed;
+        fx.aggregate = s.aggregate; fx.light_sampler = s.light_sampler;
+        fx.n_instances = s.n_instances; fx.n_lights = s.n_lights; fx.n_meshes = s.n_meshes; fx.n_spheres = s.n_spheres;
+        fx.n_surfaces = s.n_surfaces; fx.n_bezier_patches = s.n_bezier_patches; fx.n_tris = s.n_tris;
+        fx.env_light_index = s.env_light_index;
+        fx.env_light_type = s.env_light_index >= 0 ? s.lights[s.env_light_index].type : 0u;
+        fx.has_env = s.env.width != 0 && s.env.height != 0;
         for (uint32_t i = 0; i < s.n_meshes; ++i) {
             // each BLAS must index triangles inside its own mesh range
-            blas_depth = std::max(blas_depth, bvh_depth(s.blas_nodes, s.n_blas_nodes, s.meshes[i].root, s.n_tris, "blas"));
+            fx.blas_depth = std::max(fx.blas_depth, bvh_depth(s.blas_nodes, s.n_blas_nodes, s.meshes[i].root, s.n_tris, "blas"));
         }
-        // near-first traversal pushes at most one (far) child per 2-wide level (4-wide trees: see build_n4)
         const bool own_bvh = std::getenv("SPT_REFERENCE_BVH") == nullptr;   // see build_sah_blas
-        uint32_t cap = tlas_depth + blas_depth + 2;
-        if (!own_bvh && cap > kLdsStack + kSpillStack) fail(SPT_ERR_UNSUPPORTED, "BVH deeper than the traversal stack (48 levels)");
-        if (tlas_depth + 2 > kLdsStack + kSpillStack) fail(SPT_ERR_UNSUPPORTED, "TLAS deeper than the traversal stack (48 levels)");
+        fx.own_bvh = own_bvh;
+        fx.spheres.assign(s.spheres, s.spheres + s.n_spheres);
+        fx.mesh_tris.resize(s.n_meshes);
+        fx.mesh_box.resize(s.n_meshes);
+        for (uint32_t i = 0; i < s.n_meshes; ++i) {   // (the per-row spans' object-space boxes: an update reads no triangle)
+            const spt_mesh& m = s.meshes[i];
+            fx.mesh_tris[i] = m.tri_count;
+            double olo[3] = {1e300, 1e300, 1e300}, ohi[3] = {-1e300, -1e300, -1e300};
+            for (uint32_t t = m.tri_first; t < m.tri_first + m.tri_count; ++t) {
+                const float* v[3] = {s.tri_pos[t].p0, s.tri_pos[t].p1, s.tri_pos[t].p2};
+                for (int c = 0; c < 3; ++c)
+                    for (int k = 0; k < 3; ++k) { olo[k] = std::min(olo[k], (double)v[c][k]); ohi[k] = std::max(ohi[k], (double)v[c][k]); }
+            }
+            for (int k = 0; k < 3; ++k) { fx.mesh_box[i][k] = olo[k]; fx.mesh_box[i][3 + k] = ohi[k]; }
+        }
+        fx.surf_class.resize(s.n_surfaces);
+        fx.surf_emissive.resize(s.n_surfaces);
+        for (uint32_t i = 0; i < s.n_surfaces; ++i) {
+            fx.surf_class[i] = shade_class(s, s.materials[s.surfaces[i].material]);
+            fx.surf_emissive[i] = surface_emits(s.surfaces[i]) ? 1 : 0;
+        }
+        const DynView view = dyn_view(s, fx.surf_emissive.data());
+        SceneDynamic dy;
         sc->tri_pos.upload(s.tri_pos, s.n_tris);
         sc->tri_attr.upload(s.tri_attr, s.n_tris);
         sc->instances.upload(s.instances, s.n_instances);
@@ -1082,7 +1523,6 @@ spt_status spt_scene_create(const spt_scene_desc* desc, int32_t device, spt_scen
         d.light_k = sc->light_k.as<uint32_t>();
         d.env_px = sc->env_px.as<float4>();
         d.env_uk = sc->env_uk.as<uint2>();
-        d.n_tlas_nodes = s.n_tlas_nodes;
         d.n_instances = s.n_instances;
         d.n_lights = s.n_lights;
         d.n_meshes = s.n_meshes;
@@ -1092,63 +1532,9 @@ spt_status spt_scene_create(const spt_scene_desc* desc, int32_t device, spt_scen
         d.env_w = s.env.width;
         d.env_h = s.env.height;
         for (int i = 0; i < 3; ++i) d.env_scale[i] = s.env.scale[i];
-        d.stack_cap = cap;
         d.fast_slab = own_bvh ? 1u : 0u;
-        // the class a hit on each instance is queued under for the shade stage of bounce >= 1 (kernels.h, kClasses): by the code
-        // path its material takes through mat_sample / mat_eval / mat_pdf and by whether it has a light sample at all
-        std::vector<uint8_t> cls(std::max<uint32_t>(s.n_instances, 1u), 0);
-        for (uint32_t i = 0; i < s.n_instances; ++i) {
-            const spt_material& m = s.materials[s.surfaces[s.instances[i].surface].material];
-            uint32_t b = m.bxdf;
-            if (m.recipe != 0u) {      // evaluated per hit: the kind the recipe usually resolves to
-                switch (s.material_recipes[m.recipe - 1u].type) {
-                case SPT_MAT_LAMBERT: b = SPT_BXDF_LAMBERT; break;
-                case SPT_MAT_CONDUCTOR: b = SPT_BXDF_MICROFACET_CONDUCTOR; break;
-                case SPT_MAT_DIELECTRIC: b = SPT_BXDF_MICROFACET_DIELECTRIC; break;
-                default: b = SPT_BXDF_MICROFACET_PLASTIC; break;
-                }
-            }
-            switch (b) {
-            case SPT_BXDF_LAMBERT: cls[i] = 0; break;
-            case SPT_BXDF_MICROFACET_CONDUCTOR: cls[i] = 1; break;
-            case SPT_BXDF_SPECULAR_CONDUCTOR: cls[i] = 2; break;
-            case SPT_BXDF_MICROFACET_DIELECTRIC: cls[i] = 3; break;
-            case SPT_BXDF_SPECULAR_DIELECTRIC: cls[i] = 4; break;
-            case SPT_BXDF_PSEUDO: cls[i] = 5; break;
-            default: cls[i] = 6; break;       // the plastic / PBR lobes, glints
-            }
-        }
-        sc->inst_class.upload(cls.data(), cls.size());
-        d.inst_class = sc->inst_class.as<uint8_t>();
         {
-            // one float4 blob for everything the traversal touches: [tlas | instances | meshes | spheres | blas | tri]
-            std::vector<float4> blob;
-            auto append = [&](const void* src, size_t bytes) {
-                uint32_t off = (uint32_t)blob.size();
-                size_t n4 = (bytes + 15) / 16;
-                blob.resize(blob.size() + n4, make_float4(0, 0, 0, 0));
-                if (bytes) std::memcpy(&blob[off], src, bytes);
-                return off;
-            };
-            std::vector<float4> wtlas;
-            d.tlas_root = 0;
-            for (int k = 0; k < 3; ++k) { d.tlas_lo[k] = 0.0f; d.tlas_hi[k] = 0.0f; }
-            // TLAS leaf slot -> instance index: identity for the caller's tree (its leaves index the instance array) and
-            // for a GROUP aggregate, the leaf order of the device-built tree otherwise
-            std::vector<uint32_t> tlas_order(s.n_instances);
-            for (uint32_t i = 0; i < s.n_instances; ++i) tlas_order[i] = i;
-            std::vector<spt_bvh_node> own_tlas;
-            if (s.aggregate == SPT_AGGREGATE_BVH && s.n_tlas_nodes) {
-                if (own_bvh && s.n_instances) {
-                    build_sah_tlas(s.instances, s.n_instances, own_tlas, tlas_order);   // boxes padded by the builder
-                    tlas_depth = bvh_depth(own_tlas.data(), (uint32_t)own_tlas.size(), 0, s.n_instances, "device tlas");
-                    if (tlas_depth + 2 > kLdsStack + kSpillStack) fail(SPT_ERR_UNSUPPORTED, "device TLAS deeper than the traversal stack (48 levels)");
-                }
-                const spt_bvh_node* tlas_src = own_tlas.empty() ? s.tlas_nodes : own_tlas.data();
-                const uint32_t sup = build_wide(tlas_src, 0, wtlas, 0xffffffffu, "tlas", false);
-                std::memcpy(&d.tlas_root, &wtlas[(size_t)sup * 4].w, 4);      // left child of the super-root = real root
-                for (int k = 0; k < 3; ++k) { d.tlas_lo[k] = tlas_src[0].bmin[k]; d.tlas_hi[k] = tlas_src[0].bmax[k]; }
-            }
+            // one float4 blob for everything the traversal touches (see dyn_layout)
             // BLAS: 2-wide full-precision nodes when the whole scene fits LDS, compressed 4-wide nodes otherwise
             // own binned-SAH BLAS per mesh (see build_sah_blas), or the ABI trees as they are
             std::vector<spt_bvh_node> own_nodes;
@@ -1158,8 +1544,7 @@ spt_status spt_scene_create(const spt_scene_desc* desc, int32_t device, spt_scen
                 for (uint32_t i = 0; i < s.n_meshes; ++i) {
                     own_roots[i] = (uint32_t)own_nodes.size();
                     build_sah_blas(s.tri_pos, s.meshes[i].tri_first, s.meshes[i].tri_count, own_nodes, tri_order);
-                    const uint32_t depth = bvh_depth(own_nodes.data(), (uint32_t)own_nodes.size(), own_roots[i], s.n_tris, "device blas");
-                    if (tlas_depth + depth + 2 > kLdsStack + kSpillStack) fail(SPT_ERR_UNSUPPORTED, "device BVH deeper than the traversal stack (48 levels)");
+                    fx.own_blas_depth = std::max(fx.own_blas_depth, bvh_depth(own_nodes.data(), (uint32_t)own_nodes.size(), own_roots[i], s.n_tris, "device blas"));
                 }
             }
             const spt_bvh_node* blas_src = own_bvh ? own_nodes.data() : s.blas_nodes;
@@ -1172,12 +1557,12 @@ spt_status spt_scene_create(const spt_scene_desc* desc, int32_t device, spt_scen
                 for (int k = 0; k < 3; ++k) { dst.p1[k] = src.p1[k] - src.p0[k]; dst.p2[k] = src.p2[k] - src.p0[k]; }   // e1, e2 of triangle.rs:125-126
                 std::memcpy(&dst.pad0, &tri_order[i], 4);
             }
-            auto assemble = [&](bool n4) {
-                blob.clear();
+            std::vector<float4> wblas;
+            auto build_blas = [&](bool n4) {   // the BLAS nodes and the mesh records of one form
                 sc->blas_range.clear();
-                std::vector<float4> wblas;
-                std::vector<float4> mesh_rec((size_t)s.n_meshes * 2, make_float4(0, 0, 0, 0));   // (root.lo, root ref) (root.hi, -)
-                uint32_t max_blas_need = 0;
+                wblas.clear();
+                fx.mesh_rec.assign((size_t)s.n_meshes * 2, make_float4(0, 0, 0, 0));   // (root.lo, root ref) (root.hi, -)
+                fx.max_blas_need = 0;
                 for (uint32_t i = 0; i < s.n_meshes; ++i) {
                     const uint32_t mesh_root = own_bvh ? own_roots[i] : s.meshes[i].root;
                     const spt_bvh_node& rn = blas_src[mesh_root];
@@ -1185,9 +1570,7 @@ spt_status spt_scene_create(const spt_scene_desc* desc, int32_t device, spt_scen
                     if (n4) {
                         uint32_t need = 0;
                         root_ref = build_n4(blas_src, mesh_root, wblas, &need, "blas");
-                        max_blas_need = std::max(max_blas_need, need);
-                        if (tlas_depth + need + 2 > kLdsStack + kSpillStack)
-                            fail(SPT_ERR_UNSUPPORTED, "4-wide BVH needs more than the traversal stack (48 entries)");
+                        fx.max_blas_need = std::max(fx.max_blas_need, need);
                     } else {
                         const uint32_t first_node = (uint32_t)(wblas.size() / 4);
                         const uint32_t sup = build_wide(blas_src, mesh_root, wblas, 0u, "blas");
@@ -1196,73 +1579,22 @@ spt_status spt_scene_create(const spt_scene_desc* desc, int32_t device, spt_scen
                     }
                     float rf;
                     std::memcpy(&rf, &root_ref, 4);
-                    mesh_rec[2 * i] = make_float4(rn.bmin[0], rn.bmin[1], rn.bmin[2], rf);
+                    fx.mesh_rec[2 * i] = make_float4(rn.bmin[0], rn.bmin[1], rn.bmin[2], rf);
                     // (flat.h: the mesh's range in the blob's triangle copy, when it fits 16 + 16 bits)
                     const spt_mesh& mm = s.meshes[i];
                     const uint32_t range = (mm.tri_first < 65536u && mm.tri_count < 65536u) ? (mm.tri_first | (mm.tri_count << 16)) : 0u;
                     float range_f;
                     std::memcpy(&range_f, &range, 4);
-                    mesh_rec[2 * i + 1] = make_float4(rn.bmax[0], rn.bmax[1], rn.bmax[2], range_f);
+                    fx.mesh_rec[2 * i + 1] = make_float4(rn.bmax[0], rn.bmax[1], rn.bmax[2], range_f);
                 }
-                // streaming walker (stream.h): a 4-wide TLAS behind the BLAS nodes (refs of both levels index one array) and
-                // 96-byte instance entry records in its leaf order.  Its boxes only cull (quantised outward, relaxed
-                // test), so one tree serves both BVH modes and a GROUP aggregate alike.
-                sc->swalk = false;
-                d.s_root = 0u;
-                std::vector<float4> sinst;
-                if (n4 && s.n_instances) {
-                    const size_t blas_f4 = wblas.size();
-                    try {
-                        std::vector<spt_bvh_node> group_tlas;
-                        std::vector<uint32_t> s_order = tlas_order;
-                        const spt_bvh_node* src = nullptr;
-                        if (s.aggregate == SPT_AGGREGATE_BVH && s.n_tlas_nodes) {
-                            src = own_tlas.empty() ? s.tlas_nodes : own_tlas.data();
-                        } else {
-                            build_sah_tlas(s.instances, s.n_instances, group_tlas, s_order);
-                            src = group_tlas.data();
-                            for (int k = 0; k < 3; ++k) { d.tlas_lo[k] = src[0].bmin[k]; d.tlas_hi[k] = src[0].bmax[k]; }
-                        }
-                        uint32_t need_t = 0;
-                        d.s_root = build_n4(src, 0, wblas, &need_t, "tlas");
-                        // + 1: a TLAS leaf of several instances keeps its remaining instances as one extra entry
-                        if (need_t + max_blas_need + 3 > kLdsStack + kSpillStack) fail(SPT_ERR_UNSUPPORTED, "4-wide TLAS + BLAS need more than the traversal stack");
-                        sinst.assign((size_t)s.n_instances * 6, make_float4(0, 0, 0, 0));
-                        auto as_f = [](uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; };
-                        for (uint32_t slot = 0; slot < s.n_instances; ++slot) {
-                            const uint32_t ii = s_order[slot];
-                            const spt_instance& in = s.instances[ii];
-                            float4* r = &sinst[(size_t)slot * 6];
-                            std::memcpy(r, in.inv, 48);
-                            r[3] = make_float4(as_f(ii), as_f(in.prim_type), as_f(in.prim_id), 0.0f);
-                            if (in.prim_type == SPT_PRIM_MESH) { r[4] = mesh_rec[2 * in.prim_id]; r[5] = mesh_rec[2 * in.prim_id + 1]; }
-                            else if (in.prim_type == SPT_PRIM_SPHERE) { const spt_sphere& sp = s.spheres[in.prim_id]; r[4] = make_float4(sp.center[0], sp.center[1], sp.center[2], sp.radius); }
-                        }
-                        sc->swalk = std::getenv("SPT_NO_STREAM") == nullptr;
-                        // (patches under the caller's exact boxes: only the reference's visit order reproduces which near misses it loses)
-                        if (!own_bvh && s.n_bezier_patches != 0) sc->swalk = false;
-                    } catch (const AbiError&) {
-                        wblas.resize(blas_f4);   // e.g. an instance box too large to quantise: the walkers of trace.h serve the scene
-                        sinst.clear();
-                        sc->swalk = false;
-                    }
-                }
-                d.o_sinst = append(sinst.data(), sinst.size() * 16);
-                d.o_tlas = append(wtlas.data(), wtlas.size() * 16);
-                {   // the instance records as they are, pad[0] carrying the instance's class (hit_push<true> reads it from the staged copy)
-                    std::vector<spt_instance> inst_copy(s.instances, s.instances + s.n_instances);
-                    for (uint32_t i = 0; i < s.n_instances; ++i) { const uint32_t c = cls[i]; std::memcpy(&inst_copy[i].pad[0], &c, 4); }
-                    d.o_inst = append(inst_copy.data(), (size_t)s.n_instances * sizeof(spt_instance));
-                }
-                d.o_mesh = append(mesh_rec.data(), mesh_rec.size() * 16);
-                d.o_sph = append(s.spheres, (size_t)s.n_spheres * sizeof(spt_sphere));
-                d.o_blas = append(wblas.data(), wblas.size() * 16);
-                d.o_tri = append(tri_blob.data(), (size_t)s.n_tris * sizeof(spt_tri_pos));
-                d.o_tord = append(tlas_order.data(), tlas_order.size() * sizeof(uint32_t));
+                if (wblas.size() > 0x7fffffffull / 16) fail(SPT_ERR_UNSUPPORTED, "scene geometry larger than 32 GiB");
+                fx.blas_f4 = (uint32_t)wblas.size();
+                fx.n4 = n4;
             };
-            const size_t stack_bytes = (size_t)kLdsStack * 2 * kBlock * sizeof(uint32_t);   // (ref, t0) per LDS level
-            assemble(false);
-            sc->lds_geo = blob.size() * 16 <= 32u * 1024u && stack_bytes + blob.size() * 16 <= 64u * 1024u;
+            build_blas(false);
+            dyn_trees(fx, view, false, dy);
+            size_t plain_f4 = dyn_layout(fx, dy, false, false);
+            sc->lds_geo = plain_f4 * 16 <= 32u * 1024u && kStackBytes + plain_f4 * 16 <= 64u * 1024u;
             if (std::getenv("SPT_NO_LDS_GEO")) sc->lds_geo = false;   // tests: drive small scenes through the large-scene path
             // patches: the streaming walkers of the large-scene path refill lanes whose patch test is over (measured,
             // t_bezier.json 512^2 @ 64 spp: 177 ms LDS-resident nested walkers, 147 ms here; SPT_BEZ_LDS=1 for the former)
@@ -1270,72 +1602,56 @@ spt_status spt_scene_create(const spt_scene_desc* desc, int32_t device, spt_scen
             //  misses of a patch the reference's own culling loses - see bezier_box_margin; the compressed 4-wide form of
             //  the caller's trees, which serves scenes beyond LDS in that mode, can differ from it in such a pixel)
             if (SPT_WITH_BEZIER && own_bvh && std::getenv("SPT_BEZ_LDS") == nullptr) sc->lds_geo = false;
-            if (!sc->lds_geo) assemble(true);
-            // a handful of primitives: every lane tests all of them (flat.h) instead of walking the trees.  The budget is in
-            // triangle tests per ray (an instanced mesh counts once per instance, a sphere as one); SPT_FLAT_BUDGET=0 turns it off.
-            {
-                uint64_t cost = 0;
-                bool ok = sc->lds_geo && own_bvh && s.n_bezier_patches == 0 && s.n_tris < 65536u;   // (the caller's exact trees are walked as they are)
-                for (uint32_t i = 0; i < s.n_instances && ok; ++i) {
-                    const spt_instance& in = s.instances[i];
-                    if (in.prim_type == SPT_PRIM_MESH) cost += s.meshes[in.prim_id].tri_count;
-                    else if (in.prim_type == SPT_PRIM_SPHERE) cost += 1;
-                    else ok = false;
-                }
-                const char* fb = std::getenv("SPT_FLAT_BUDGET");
-                d.flat = ok && s.n_instances != 0 && cost <= (fb ? (uint64_t)std::atoi(fb) : (uint64_t)kFlatBudget) ? 1u : 0u;
+            if (!sc->lds_geo) {
+                build_blas(true);
+                dyn_trees(fx, view, true, dy);
+                plain_f4 = dyn_layout(fx, dy, true, false);
+                fx.tail_first = dy.tail_first;
             }
-            // fused bounces (k_shade<0, ., kFused>): LDS-resident geometry + the lean simple-scene shade kernel, and
-            // the shading tables must fit behind the geometry too (see tab_ld in shading.h)
+            fx.tables_bytes = (size_t)s.n_tris * sizeof(spt_tri_attr) + (size_t)s.n_surfaces * sizeof(spt_surface) +
+                              (size_t)s.n_materials * sizeof(spt_material) + (size_t)s.n_lights * sizeof(spt_light) + 64;
             {
                 bool simple_scene = s.env.width == 0 && s.n_lights > 0;
                 for (uint32_t i = 0; i < s.n_materials; ++i) simple_scene = simple_scene && s.materials[i].bxdf == SPT_BXDF_LAMBERT && s.materials[i].recipe == 0;
-                for (uint32_t i = 0; i < s.n_lights; ++i) simple_scene = simple_scene && s.lights[i].type <= SPT_LIGHT_SPOT;
                 for (uint32_t i = 0; i < s.n_surfaces; ++i) {
                     const spt_surface& sf = s.surfaces[i];
                     float lum = 0.299f * sf.emissive[0] + 0.587f * sf.emissive[1] + 0.114f * sf.emissive[2];
                     simple_scene = simple_scene && sf.inside_medium < 0 && !(lum > 0.0f) && sf.normal_map == 0 && sf.emissive_map == 0;
                 }
-                const size_t extra = (size_t)s.n_tris * sizeof(spt_tri_attr) + (size_t)s.n_surfaces * sizeof(spt_surface) +
-                                     (size_t)s.n_materials * sizeof(spt_material) + (size_t)s.n_lights * sizeof(spt_light) + 64;
-                sc->lds_tables = sc->lds_geo && blob.size() * 16 + extra <= 32u * 1024u && stack_bytes + blob.size() * 16 + extra <= 64u * 1024u;
-                sc->fused = sc->lds_tables && simple_scene;
-                if (sc->lds_tables) {
-                    d.o_attr = append(s.tri_attr, (size_t)s.n_tris * sizeof(spt_tri_attr));
-                    d.o_surf = append(s.surfaces, (size_t)s.n_surfaces * sizeof(spt_surface));
-                    d.o_mat = append(s.materials, (size_t)s.n_materials * sizeof(spt_material));
-                    d.o_light = append(s.lights, (size_t)s.n_lights * sizeof(spt_light));
-                }
+                fx.fused_fixed = simple_scene;
             }
-            if (blob.size() > 0x7fffffffull / 16) fail(SPT_ERR_UNSUPPORTED, "scene geometry larger than 32 GiB");
-            {   // eye.h: an eye-relative copy per camera position is possible when every box has ONE origin to be relative to
-                bool ok = sc->lds_geo && own_bvh && s.n_bezier_patches == 0 && s.n_tris < 65536u && s.n_instances != 0 && std::getenv("SPT_NO_EYE_BLOB") == nullptr;
-                std::vector<uint32_t> mesh_uses(s.n_meshes, 0u);
-                for (uint32_t i = 0; i < s.n_instances && ok; ++i) {
-                    const spt_instance& in = s.instances[i];
-                    if (in.prim_type == SPT_PRIM_MESH) ok = ++mesh_uses[in.prim_id] == 1u;
-                    else ok = in.prim_type == SPT_PRIM_SPHERE;   // (a sphere's relative centre rides in its instance record: primitives may be shared)
-                }
-                const size_t eye_bytes = (blob.size() + s.n_tris) * 16;
-                ok = ok && eye_bytes <= 36u * 1024u && stack_bytes + eye_bytes <= 64u * 1024u && sc->blas_range.size() == s.n_meshes;
-                sc->eye_ok = ok;
-                sc->eye_valid = false;
-                if (ok) {
-                    sc->host_blob = blob;
-                    sc->wtlas_f4 = (uint32_t)wtlas.size();
-                } else {
-                    sc->host_blob.clear();
-                }
+            if (sc->lds_geo) {   // (<= 32 KB: an update writes the whole blob again)
+                auto section = [](std::vector<float4>& v, const void* src, size_t bytes) {
+                    v.assign((bytes + 15) / 16, make_float4(0, 0, 0, 0));
+                    if (bytes) std::memcpy(v.data(), src, bytes);
+                };
+                fx.wblas = wblas;
+                section(fx.tri_sec, tri_blob.data(), (size_t)s.n_tris * sizeof(spt_tri_pos));
+                section(fx.attr_sec, s.tri_attr, (size_t)s.n_tris * sizeof(spt_tri_attr));
+                section(fx.surf_sec, s.surfaces, (size_t)s.n_surfaces * sizeof(spt_surface));
+                section(fx.mat_sec, s.materials, (size_t)s.n_materials * sizeof(spt_material));
             }
-            sc->geo.upload(blob.data(), blob.size());
+            // (sc->simple needs the texture and subsurface choices below: the first value here is fixed up after them)
+            dyn_decide(fx, view, dy, sc->lds_geo, plain_f4, sc->blas_range.size());
+            const StaticSections st{wblas.data(), tri_blob.data()};
+            dyn_fill(fx, view, dy, fx.n4, 0u, &st);
+            dyn_bounds(fx, view, dy);
+            sc->inst_class.upload(dy.cls.data(), dy.cls.size());
+            d.inst_class = sc->inst_class.as<uint8_t>();
+            // the allocation holds what an update may write: 64 KB of an LDS-resident blob; behind a large scene's static sections
+            // the dynamic ones of any tree over n instances (4-wide TLAS <= 4 (n - 1), entries 6 n, 2-wide TLAS <= 4 n + 4,
+            // records 12 n, order n / 4 float4), or what the caller's tree takes now if that is more
+            if (fx.n4) {
+                const size_t n = s.n_instances;
+                fx.tail_cap = (uint32_t)std::min<size_t>(0x7fffffffu, std::max<size_t>((size_t)dy.geo_f4 - fx.tail_first, 4 * n + 6 * n + 4 * n + 4 + 12 * n + (n + 3) / 4));
+            }
+            const size_t geo_bytes = fx.n4 ? ((size_t)fx.tail_first + fx.tail_cap) * 16 : std::max<size_t>(dy.blob.size() * 16, 64u * 1024u);
+            sc->geo.alloc(std::max<size_t>(geo_bytes, 16));
+            if (!dy.blob.empty()) HIP_CHECK(hipMemcpy(sc->geo.p, dy.blob.data(), dy.blob.size() * 16, hipMemcpyHostToDevice));
             d.geo = sc->geo.as<float4>();
-            d.geo_f4 = (uint32_t)blob.size();
-            d.lds_f4 = sc->lds_geo ? d.geo_f4 : 0u;   // large scene: global fetches only (see trace.h)
-            sc->lds_bytes = stack_bytes + (size_t)d.lds_f4 * 16;
         }
         bool simple = s.env.width == 0 && s.n_lights > 0;
         for (uint32_t i = 0; i < s.n_materials; ++i) simple = simple && s.materials[i].bxdf == SPT_BXDF_LAMBERT;
-        for (uint32_t i = 0; i < s.n_lights; ++i) simple = simple && s.lights[i].type <= SPT_LIGHT_SPOT;
         for (uint32_t i = 0; i < s.n_surfaces; ++i) {
             const spt_surface& sf = s.surfaces[i];
             float lum = 0.299f * sf.emissive[0] + 0.587f * sf.emissive[1] + 0.114f * sf.emissive[2];
@@ -1442,69 +1758,9 @@ spt_status spt_scene_create(const spt_scene_desc* desc, int32_t device, spt_scen
             d.texels = sc->texels.as<uint32_t>();
             d.recipes = sc->recipes.as<uint4>();
         }
-        sc->simple = simple;
-        if (s.n_instances) {
-            double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-            bool finite = true;
-            for (uint32_t i = 0; i < s.n_instances; ++i) {
-                const double margin = bezier_box_margin(s.instances[i]);   // the screen-space bound and the bounding sphere cull too
-                for (int k = 0; k < 3; ++k) {
-                    lo[k] = std::min(lo[k], (double)s.instances[i].bmin[k] - margin);
-                    hi[k] = std::max(hi[k], (double)s.instances[i].bmax[k] + margin);
-                    finite = finite && std::isfinite(s.instances[i].bmin[k]) && std::isfinite(s.instances[i].bmax[k]);
-                }
-            }
-            double r2 = 0;
-            for (int k = 0; k < 3; ++k) {
-                sc->bs_center[k] = 0.5 * (lo[k] + hi[k]);
-                sc->world_lo[k] = lo[k];
-                sc->world_hi[k] = hi[k];
-                r2 += 0.25 * (hi[k] - lo[k]) * (hi[k] - lo[k]);
-            }
-            sc->bs_radius = std::sqrt(r2) * 1.001 + 1e-4;
-            sc->bs_valid = finite && std::isfinite(sc->bs_radius) && sc->bs_radius < 1e18;
-            // Object-space boxes for the per-row spans: the exact bounds of a mesh's vertices / a sphere, padded a little,
-            // carried to world space by the instance matrix (a rotated cube's world AABB is far larger than its silhouette).
-            // Patches keep their (margin-widened) world box: the clipping test accepts near misses (bezier_box_margin).
-            if (sc->bs_valid && s.n_instances <= 256u) {
-                sc->hull_corners.resize(s.n_instances);
-                for (uint32_t i = 0; i < s.n_instances && !sc->hull_corners.empty(); ++i) {
-                    const spt_instance& in = s.instances[i];
-                    double olo[3] = {1e300, 1e300, 1e300}, ohi[3] = {-1e300, -1e300, -1e300};
-                    bool object_space = true;
-                    if (in.prim_type == SPT_PRIM_MESH) {
-                        const spt_mesh& m = s.meshes[in.prim_id];
-                        for (uint32_t t = m.tri_first; t < m.tri_first + m.tri_count; ++t) {
-                            const float* v[3] = {s.tri_pos[t].p0, s.tri_pos[t].p1, s.tri_pos[t].p2};
-                            for (int c = 0; c < 3; ++c)
-                                for (int k = 0; k < 3; ++k) { olo[k] = std::min(olo[k], (double)v[c][k]); ohi[k] = std::max(ohi[k], (double)v[c][k]); }
-                        }
-                        if (m.tri_count == 0) { for (int k = 0; k < 3; ++k) { olo[k] = 0; ohi[k] = 0; } }
-                    } else if (in.prim_type == SPT_PRIM_SPHERE) {
-                        const spt_sphere& sp = s.spheres[in.prim_id];
-                        for (int k = 0; k < 3; ++k) { olo[k] = (double)sp.center[k] - std::fabs((double)sp.radius); ohi[k] = (double)sp.center[k] + std::fabs((double)sp.radius); }
-                    } else {
-                        object_space = false;
-                        const double margin = bezier_box_margin(in);
-                        for (int k = 0; k < 3; ++k) { olo[k] = (double)in.bmin[k] - margin; ohi[k] = (double)in.bmax[k] + margin; }
-                    }
-                    double ext = 1e-30;
-                    for (int k = 0; k < 3; ++k) ext = std::max(ext, ohi[k] - olo[k]);
-                    bool ok = true;
-                    for (int c = 0; c < 8; ++c) {
-                        double o[3];
-                        for (int k = 0; k < 3; ++k) o[k] = ((c >> k) & 1) ? ohi[k] + 1e-4 * ext : olo[k] - 1e-4 * ext;
-                        for (int r = 0; r < 3; ++r) {
-                            double w = o[r];
-                            if (object_space) w = (double)in.fwd[r] * o[0] + (double)in.fwd[3 + r] * o[1] + (double)in.fwd[6 + r] * o[2] + (double)in.fwd[9 + r];
-                            sc->hull_corners[i][3 * c + r] = w;
-                            ok = ok && std::isfinite(w);
-                        }
-                    }
-                    if (!ok) sc->hull_corners.clear();
-                }
-            }
-        }
+        fx.simple_fixed = simple;   // (... but for the lights' types, which an update may change)
+        dy.simple = simple && only_delta_lights(view);
+        dyn_commit_host(sc.get(), dy, sc->lds_geo);
         *out = sc.release();
         return SPT_OK;
     });
@@ -2533,6 +2789,90 @@ float* direct_destination(const spt_render_params& p, uint32_t own_rows, uint32_
 
 extern "C" {
 
+// spt_scene_update: everything of the scene that depends on its instances and lights is built again on the host from the new
+// arrays (dyn_trees ... dyn_bounds, the functions spt_scene_create runs), then committed: the device copies through one page-locked
+// slot, by copies queued on the render stream behind the kernels of the frames queued so far, the host side last.  Nothing of the
+// scene is touched before the first copy is queued, so a refused update leaves it as it was.
+spt_status spt_scene_update(spt_scene* sc, const spt_scene_update_desc* u) {
+    if (!sc || !u) { g_error = "scene_update: null argument"; return SPT_ERR_INVALID_ARG; }
+    if (u->size < sizeof(spt_scene_update_desc)) { g_error = "scene_update: size is smaller than spt_scene_update_desc"; return SPT_ERR_INVALID_ARG; }
+    if (sc->fwd) {
+        if (!sc->fwd->scene_update) { g_error = "scene_update: libspt_hip_bez.so does not export spt_scene_update"; return SPT_ERR_UNSUPPORTED; }
+        return forwarded(sc->fwd, sc->fwd->scene_update(sc->inner, u));
+    }
+    std::lock_guard<std::mutex> lock(sc->mu);
+    return guarded("scene_update", [&] {
+        const SceneFixed& fx = sc->fixed;
+        if (u->flags != 0u) fail(SPT_ERR_INVALID_ARG, "scene_update: unknown flags");
+        if (sc->live_films != 0u) fail(SPT_ERR_INVALID_ARG, "scene_update: destroy the scene's films first (a film accumulates samples of one scene)");
+        if (u->n_instances != fx.n_instances) fail(SPT_ERR_INVALID_ARG, "scene_update: n_instances differs from the scene's (objects cannot appear or vanish)");
+        if (u->n_lights != fx.n_lights) fail(SPT_ERR_INVALID_ARG, "scene_update: n_lights differs from the scene's");
+        if ((u->n_tlas_nodes && !u->tlas_nodes) || (u->n_instances && !u->instances) || (u->n_lights && !u->lights)) fail(SPT_ERR_INVALID_ARG, "scene_update: null array");
+        if (u->n_instances && fx.aggregate == SPT_AGGREGATE_BVH && u->n_tlas_nodes == 0) fail(SPT_ERR_INVALID_ARG, "scene_update: bvh aggregate without TLAS nodes");
+        const DynView view{fx.aggregate, fx.light_sampler, u->n_tlas_nodes, u->n_instances, u->n_lights, fx.n_spheres, fx.n_meshes, fx.n_bezier_patches, fx.n_surfaces,
+                           fx.has_env, u->tlas_nodes, u->instances, u->lights, u->light_alias, fx.surf_emissive.data()};
+        validate_instances(view, "scene_update");
+        validate_lights(view, "scene_update");
+        if (fx.env_light_index >= 0 && u->lights[fx.env_light_index].type != fx.env_light_type)
+            fail(SPT_ERR_INVALID_ARG, "scene_update: the light at env_light_index may not change its type");
+        validate_light_alias(view, "scene_update");
+        // the new state, on the host
+        SceneDynamic dy;
+        dyn_trees(fx, view, fx.n4, dy);
+        const size_t plain_f4 = dyn_layout(fx, dy, fx.n4, false);   // (the static sections have not moved: dy.tail_first == fx.tail_first)
+        if (sc->lds_geo && !(plain_f4 * 16 <= 32u * 1024u && kStackBytes + plain_f4 * 16 <= 64u * 1024u))
+            fail(SPT_ERR_UNSUPPORTED, "scene_update: the traversal geometry would no longer fit LDS, where the scene's BLAS nodes are laid out for: recreate the scene");
+        if (fx.n4 && (size_t)dy.geo_f4 - fx.tail_first > fx.tail_cap)
+            fail(SPT_ERR_UNSUPPORTED, "scene_update: the caller's TLAS needs more room than the scene reserved: recreate the scene");
+        dyn_decide(fx, view, dy, sc->lds_geo, plain_f4, sc->blas_range.size());
+        const StaticSections st{fx.wblas.data(), fx.tri_sec.data()};
+        dyn_fill(fx, view, dy, fx.n4, fx.n4 ? fx.tail_first : 0u, &st);
+        dyn_bounds(fx, view, dy);
+        // the slot: [instances | classes | lights | alias props, u, k | blob]
+        const bool pis = fx.light_sampler == SPT_LIGHT_SAMPLER_POWER_IS && fx.n_lights != 0;
+        struct Part { void* dst; const void* src; size_t bytes, at; };
+        std::vector<Part> parts;
+        size_t total = 0;
+        auto part = [&](void* dst, const void* src, size_t bytes) {
+            if (!bytes) return;
+            parts.push_back(Part{dst, src, bytes, total});
+            total += (bytes + 15) / 16 * 16;
+        };
+        part(sc->instances.p, u->instances, (size_t)fx.n_instances * sizeof(spt_instance));
+        part(sc->inst_class.p, dy.cls.data(), fx.n_instances);
+        part(sc->lights.p, u->lights, (size_t)fx.n_lights * sizeof(spt_light));
+        if (pis) {
+            part(sc->light_props.p, u->light_alias.props, (size_t)fx.n_lights * sizeof(float));
+            part(sc->light_u.p, u->light_alias.u, (size_t)fx.n_lights * sizeof(float));
+            part(sc->light_k.p, u->light_alias.k, (size_t)fx.n_lights * sizeof(uint32_t));
+        }
+        part(sc->geo.as<float4>() + (fx.n4 ? fx.tail_first : 0u), dy.blob.data(), dy.blob.size() * 16);
+        if ((fx.n4 ? (size_t)fx.tail_first * 16 : 0) + dy.blob.size() * 16 > sc->geo.bytes) fail(SPT_ERR_UNSUPPORTED, "scene_update: the geometry blob outgrew its allocation: recreate the scene");
+        HIP_CHECK(hipSetDevice(sc->device));
+        if (!sc->ev_upd) HIP_CHECK(hipEventCreateWithFlags(&sc->ev_upd, hipEventDisableTiming));
+        if (sc->upd_recorded) HIP_CHECK(hipEventSynchronize(sc->ev_upd));   // the previous update's copies still read the slot
+        sc->upd_recorded = false;
+        sc->upd_stage.ensure(std::max<size_t>(total, 16));
+        for (const Part& pt : parts) std::memcpy(static_cast<char*>(sc->upd_stage.p) + pt.at, pt.src, pt.bytes);
+        // Of what an overlapped render leaves on the film stream only a tail-loop launch reads the scene (the resolves, the finish
+        // kernel and the copy-out read the render workspace): the copies go behind that launch, as the next frame's bounce 0 would,
+        // and the copy-out of the previous frame goes on beside them and beside the next frame's kernels
+        if (sc->tail_set >= 0) {
+            HIP_CHECK(hipStreamWaitEvent(sc->stream, sc->ev_film[sc->tail_set], 0));
+            sc->tail_set = -1;
+        }
+        for (const Part& pt : parts)
+            HIP_CHECK(hipMemcpyAsync(pt.dst, static_cast<const char*>(sc->upd_stage.p) + pt.at, pt.bytes, hipMemcpyHostToDevice, sc->stream));
+        HIP_CHECK(hipEventRecord(sc->ev_upd, sc->stream));
+        sc->upd_recorded = true;
+        dyn_commit_host(sc, dy, sc->lds_geo);
+        ++sc->updates;
+        sc->update_bytes = 0;
+        for (const Part& pt : parts) sc->update_bytes += pt.bytes;
+        return SPT_OK;
+    });
+}
+
 spt_status spt_render(const spt_scene* scene_c, const spt_camera* cam, const spt_render_params* params,
                       float* rgb_mean_out, spt_render_stats* stats) {
     if (!scene_c || !cam || !params || !rgb_mean_out) { g_error = "render: null argument"; return SPT_ERR_INVALID_ARG; }
@@ -2770,6 +3110,7 @@ spt_status spt_film_create(const spt_scene* scene_c, const spt_camera* cam, cons
         if (keep) {
             make_kept_runs(f.get());
             *out = f.release();
+            ++sc->live_films;
             return SPT_OK;
         }
         const size_t bytes = (size_t)own_pix64 * 3 * sizeof(float);
@@ -2781,6 +3122,7 @@ spt_status spt_film_create(const spt_scene* scene_c, const spt_camera* cam, cons
         }
         HIP_CHECK(hipStreamSynchronize(sc->stream));
         *out = f.release();
+        ++sc->live_films;
         return SPT_OK;
     });
 }
@@ -3467,6 +3809,7 @@ void spt_film_destroy(spt_film* f) {
     std::lock_guard<std::mutex> lock(f->sc->mu);
     (void)hipSetDevice(f->sc->device);
     (void)hipStreamSynchronize(f->sc->stream);   // (every film call is synchronous; nothing of this film is queued)
+    if (f->sc->live_films) --f->sc->live_films;
     delete f;
 }
 
@@ -3736,11 +4079,11 @@ spt_status spt_debug_pack_rgb8(int32_t device, uint32_t n, const float* in, uint
 }
 
 spt_status spt_debug_render_info(const spt_scene* scene_c, uint32_t what, uint64_t* out) {
-    if (!scene_c || !out || what > 3u) { g_error = "debug_render_info: null argument or unknown counter"; return SPT_ERR_INVALID_ARG; }
+    if (!scene_c || !out || what > 5u) { g_error = "debug_render_info: null argument or unknown counter"; return SPT_ERR_INVALID_ARG; }
     spt_scene* sc = const_cast<spt_scene*>(scene_c);
     if (sc->fwd) return forwarded(sc->fwd, sc->fwd->debug_render_info(sc->inner, what, out));
     std::lock_guard<std::mutex> lock(sc->mu);
-    *out = what == 0u ? sc->passes_film : what == 1u ? sc->passes_single : what == 2u ? sc->keep_read_ns : sc->frames_direct;
+    *out = what == 0u ? sc->passes_film : what == 1u ? sc->passes_single : what == 2u ? sc->keep_read_ns : what == 3u ? sc->frames_direct : what == 4u ? sc->updates : sc->update_bytes;
     return SPT_OK;
 }
 

@@ -22,6 +22,34 @@ struct spt_host_scene {
     HostScene* hs;
 };
 
+struct spt_host_animation {
+    Animation* an;
+};
+
+// The body of an entry point that edits a scene: a HostError becomes its status and message
+template <class Body>
+static spt_status host_guarded(const char* who, Body&& body) {
+    try {
+        body();
+        return SPT_OK;
+    } catch (const HostError& e) {
+        set_error(e.msg);
+        return e.code;
+    } catch (const std::exception& e) {
+        set_error(std::string(who) + ": " + e.what());
+        return SPT_HOST_ERR_PARSE;
+    }
+}
+
+static Affine affine_of(const float* f) {
+    Affine a;
+    a.m.c0 = {f[0], f[1], f[2]};
+    a.m.c1 = {f[3], f[4], f[5]};
+    a.m.c2 = {f[6], f[7], f[8]};
+    a.t = {f[9], f[10], f[11]};
+    return a;
+}
+
 extern "C" {
 
 const char* spt_host_last_error(void) { return g_error.c_str(); }
@@ -69,6 +97,51 @@ spt_status spt_host_scene_set_bezier_newton(spt_host_scene* scene, int32_t newto
     if (!scene) { set_error("scene_set_bezier_newton: null argument"); return SPT_ERR_INVALID_ARG; }
     for (spt_bezier_patch& bp : scene->hs->bezier_patches) bp.cp[0][0][3] = newton ? SPT_BEZIER_NEWTON : 0.0f;   // the desc points at this array
     return SPT_OK;
+}
+
+spt_status spt_host_scene_instance_index(const spt_host_scene* scene, const char* name, uint32_t* index) {
+    if (!scene || !name || !index) { set_error("scene_instance_index: null argument"); return SPT_ERR_INVALID_ARG; }
+    auto it = scene->hs->inst_index.find(name);
+    if (it == scene->hs->inst_index.end()) { set_error(std::string("There is no instance named '") + name + "'"); return SPT_HOST_ERR_SCHEMA; }
+    *index = it->second;
+    return SPT_OK;
+}
+
+spt_status spt_host_scene_set_transforms(spt_host_scene* scene, uint32_t n, const char* const* names, const float* fwd) {
+    if (!scene || (n && (!names || !fwd))) { set_error("scene_set_transforms: null argument"); return SPT_ERR_INVALID_ARG; }
+    return host_guarded("scene_set_transforms", [&] {
+        std::vector<std::pair<std::string, Affine>> moves;
+        for (uint32_t i = 0; i < n; ++i) {
+            if (!names[i]) throw HostError(SPT_ERR_INVALID_ARG, "scene_set_transforms: null name");
+            moves.emplace_back(names[i], affine_of(fwd + 12 * (size_t)i));
+        }
+        scene->hs->set_transforms(moves);
+    });
+}
+
+spt_status spt_host_scene_set_light(spt_host_scene* scene, const char* name, const spt_light* light) {
+    if (!scene || !name || !light) { set_error("scene_set_light: null argument"); return SPT_ERR_INVALID_ARG; }
+    return host_guarded("scene_set_light", [&] { scene->hs->set_light(name, *light); });
+}
+
+spt_status spt_host_animation_load(const char* path, const spt_host_scene* scene, spt_host_animation** out) {
+    if (!path || !scene || !out) { set_error("animation_load: null argument"); return SPT_ERR_INVALID_ARG; }
+    *out = nullptr;
+    return host_guarded("animation_load", [&] { *out = new spt_host_animation{load_animation(path, *scene->hs)}; });
+}
+
+uint32_t spt_host_animation_frames(const spt_host_animation* animation) { return animation ? (uint32_t)animation->an->frames.size() : 0u; }
+
+spt_status spt_host_animation_apply(const spt_host_animation* animation, uint32_t frame, spt_host_scene* scene) {
+    if (!animation || !scene) { set_error("animation_apply: null argument"); return SPT_ERR_INVALID_ARG; }
+    if (frame >= animation->an->frames.size()) { set_error("animation_apply: no such frame"); return SPT_ERR_INVALID_ARG; }
+    return host_guarded("animation_apply", [&] { scene->hs->set_transforms(animation->an->frames[frame]); });
+}
+
+void spt_host_animation_free(spt_host_animation* animation) {
+    if (!animation) return;
+    delete animation->an;
+    delete animation;
 }
 
 // Scene::get_camera (src/core/scene.rs:29-41): by name, or the only one

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../../include/spt_host.h"
+#include "hmath.hpp"
 
 namespace spt_host {
 
@@ -15,6 +16,10 @@ struct HostError {
     std::string msg;
     HostError(spt_status c, std::string m) : code(c), msg(std::move(m)) {}
 };
+
+// One instance as the loader made it (Instance::new), with what making it again under another transform needs
+struct InstRec { spt_instance inst; Affine trans; std::string name; Box prim_box; };
+InstRec make_instance_rec(const std::string& name, const Affine& trans, uint32_t prim_type, uint32_t prim_id, const Box& prim_box, uint32_t surf);
 
 struct HostScene {
     std::vector<spt_bvh_node> tlas_nodes, blas_nodes;
@@ -49,9 +54,22 @@ struct HostScene {
     std::map<std::string, size_t> camera_index;
     spt_scene_desc desc;
     void finalize_desc();
+    // What the part of the descriptor that depends on the instances' transforms and the named lights is made from (kept for
+    // spt_host_scene_set_transforms / _set_light): the instances and the named lights by name, the average emission per surface
+    std::map<std::string, InstRec> inst_recs;         // name-sorted (Q7: reference order is HashMap order)
+    std::map<std::string, spt_light> named_lights;
+    std::vector<V3> avg_emissive;
+    std::map<std::string, uint32_t> inst_index;       // name -> index in `instances` as they stand
+    float instance_area(const InstRec& r) const;
+    // tlas_nodes, instances (in TLAS leaf order), lights, the light alias table and desc from the three members above
+    void finalize_dynamic();
+    void set_transforms(const std::vector<std::pair<std::string, Affine>>& moves);   // all or nothing (HostError)
+    void set_light(const std::string& name, const spt_light& light);
 };
 
 HostScene* load_scene_file(const std::string& path);
+struct Animation { std::vector<std::vector<std::pair<std::string, Affine>>> frames; };
+Animation* load_animation(const std::string& path, const HostScene& hs);
 // pndf.cpp: the Gaussian terms and trees of one pndf_conductor material (PndfConductor::new), appended to the scene
 uint32_t build_pndf(HostScene& hs, uint32_t base_normal_texture, float sigma_r, float h, const std::string& label);
 // catmull.cpp: 16 control points (x, y, z) per bicubic patch of the Catmull-Clark surface of an ASCII PLY control mesh

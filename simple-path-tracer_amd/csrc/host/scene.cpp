@@ -14,6 +14,7 @@
 #include <fstream>
 #include <functional>
 #include <map>
+#include <memory>
 #include <set>
 #include <sstream>
 #include <stdexcept>
@@ -389,6 +390,20 @@ bool jvec(const JsonValue* v, size_t n, float* out) {
     return true;
 }
 
+// The transform keys of an instance (Instance::load, src/primitive/instance.rs:19-51): matrix, then scale, rotate, translate
+Affine transform_from_params(Params& p) {
+    const float deg = 3.14159265358979323846f / 180.0f;
+    Affine trans;
+    if (p.contains("matrix")) trans = p.get_matrix("matrix");
+    if (p.contains("scale")) trans = from_scale(p.get_float3("scale")) * trans;
+    if (p.contains("rotate")) {
+        V3 r = p.get_float3("rotate");
+        trans = from_rotation_z(r.z * deg) * from_rotation_x(r.x * deg) * from_rotation_y(r.y * deg) * trans;
+    }
+    if (p.contains("translate")) trans = from_translation(p.get_float3("translate")) * trans;
+    return trans;
+}
+
 struct PrimRec { uint32_t type; uint32_t id; Box box; };
 constexpr uint32_t kPrimCatmullClark = 100u;   // host-only kind: PrimRec::id indexes Loader::catmulls; its patches become Bezier instances
 struct SurfaceRec { uint32_t index; bool emissive; };
@@ -411,7 +426,7 @@ struct SceneBuilder {
     std::map<std::string, std::string> unsupported_materials, unsupported_prims;
     std::map<std::string, PrimRec> prims;
     std::vector<V3> avg_emissive;                     // per surface
-    struct InstRec { spt_instance inst; Affine trans; std::string name; };
+    using InstRec = spt_host::InstRec;
     struct CatmullRec { std::string ply_path, label; uint32_t fas_times = 4; bool loaded = false; uint32_t first_patch = 0, n_patches = 0; };
     std::vector<CatmullRec> catmulls;
     std::set<std::string> catmull_instances;
@@ -993,15 +1008,7 @@ struct SceneBuilder {
         p.set_name("instance");
         std::string name = p.get_str("name");
         p.set_name("instance-" + name);
-        const float deg = 3.14159265358979323846f / 180.0f;
-        Affine trans;
-        if (p.contains("matrix")) trans = p.get_matrix("matrix");
-        if (p.contains("scale")) trans = from_scale(p.get_float3("scale")) * trans;
-        if (p.contains("rotate")) {
-            V3 r = p.get_float3("rotate");
-            trans = from_rotation_z(r.z * deg) * from_rotation_x(r.x * deg) * from_rotation_y(r.y * deg) * trans;
-        }
-        if (p.contains("translate")) trans = from_translation(p.get_float3("translate")) * trans;
+        const Affine trans = transform_from_params(p);
         if (determinant(trans.m) == 0.0f) warn(p.name() + ": transform matrix is singular");
         uint32_t surf;
         if (p.contains("surface")) {
@@ -1062,35 +1069,8 @@ struct SceneBuilder {
         p.check_unused();
     }
 
-    // Instance::new (src/primitive/instance.rs:53-85)
     InstRec make_instance(const std::string& name, const Affine& trans, const PrimRec& prim, uint32_t surf) {
-        InstRec rec;
-        rec.name = name;
-        rec.trans = trans;
-        spt_instance& in = rec.inst;
-        std::memset(&in, 0, sizeof in);
-        Affine inv = inverse(trans);
-        M3 it3 = transpose(inv.m);  // Transform::new: trans_it = inverse.matrix3.transpose()
-        auto put = [](float* dst, const Affine& a) {
-            const V3 cols[4] = {a.m.c0, a.m.c1, a.m.c2, a.t};
-            for (int c = 0; c < 4; ++c) { dst[3 * c] = cols[c].x; dst[3 * c + 1] = cols[c].y; dst[3 * c + 2] = cols[c].z; }
-        };
-        put(in.inv, inv);
-        put(in.fwd, trans);
-        const V3 nc[3] = {it3.c0, it3.c1, it3.c2};
-        for (int c = 0; c < 3; ++c) { in.nrm[3 * c] = nc[c].x; in.nrm[3 * c + 1] = nc[c].y; in.nrm[3 * c + 2] = nc[c].z; }
-        in.prim_type = prim.type;
-        in.prim_id = prim.id;
-        in.surface = surf;
-        in.light = -1;
-        // Bbox::transformed_by (src/core/bbox.rs:40-61): the 8 corners
-        const Box& pb = prim.box;
-        Box wb;
-        for (int c = 0; c < 8; ++c)
-            wb.grow(trans.point({(c & 4) ? pb.hi.x : pb.lo.x, (c & 2) ? pb.hi.y : pb.lo.y, (c & 1) ? pb.hi.z : pb.lo.z}));
-        in.bmin[0] = wb.lo.x; in.bmin[1] = wb.lo.y; in.bmin[2] = wb.lo.z;
-        in.bmax[0] = wb.hi.x; in.bmax[1] = wb.hi.y; in.bmax[2] = wb.hi.z;
-        return rec;
+        return make_instance_rec(name, trans, prim.type, prim.id, prim.box, surf);
     }
 
     // light::create_light_from_params (src/light/mod.rs:37-59)
@@ -1597,30 +1577,6 @@ struct SceneBuilder {
                 if (root.kind == JsonValue::Int) visit(root.i, M4(), 0);
     }
 
-    float instance_area(const InstRec& r) {
-        const spt_instance& in = r.inst;
-        if (in.prim_type == SPT_PRIM_BEZIER)   // the reference reaches `unimplemented!` (bezier.rs:188-190) when it builds the ShapeLight
-            throw HostError(SPT_HOST_ERR_UNSUPPORTED, "instance '" + r.name + "': an emissive surface on a cubic_bezier primitive (CubicBezier::surface_area is unimplemented in the reference)");
-        if (in.prim_type == SPT_PRIM_SPHERE) {
-            float rad = hs.spheres[in.prim_id].radius * 0.5f;
-            V3 v0 = r.trans.vector({-rad, -rad, -rad}), v1 = r.trans.vector({-rad, -rad, rad});
-            V3 v2 = r.trans.vector({-rad, rad, -rad}), v3 = r.trans.vector({rad, -rad, -rad});
-            auto d2 = [](V3 a, V3 b) { V3 d = a - b; return dot(d, d); };
-            float a2 = d2(v0, v1), b2 = d2(v0, v2), c2 = d2(v0, v3);
-            return 4.0f * 3.14159265358979323846f * std::sqrt((a2 * b2 + b2 * c2 + c2 * a2) / 3.0f);
-        }
-        const spt_mesh& m = hs.meshes[in.prim_id];
-        float sum = 0.0f;
-        for (uint32_t t = m.tri_first; t < m.tri_first + m.tri_count; ++t) {
-            const spt_tri_pos& tp = hs.tri_pos[t];
-            V3 p0 = r.trans.point({tp.p0[0], tp.p0[1], tp.p0[2]});
-            V3 p1 = r.trans.point({tp.p1[0], tp.p1[1], tp.p1[2]});
-            V3 p2 = r.trans.point({tp.p2[0], tp.p2[1], tp.p2[2]});
-            sum += length(cross(p1 - p0, p2 - p0)) * 0.5f;
-        }
-        return sum;
-    }
-
     void finish(const JsonValue& root) {
         // aggregate: "group" | "bvh" (default bvh(4,16))  (scene_resources.rs:85-103)
         uint32_t aggregate = SPT_AGGREGATE_BVH;
@@ -1639,78 +1595,213 @@ struct SceneBuilder {
         }
         if (hs.cameras.empty()) throw HostError(SPT_HOST_ERR_SCHEMA, "At least one camera is needed");
 
-        // instances in name order, then TLAS
-        std::vector<const InstRec*> recs;
-        for (auto& kv : instances) recs.push_back(&kv.second);
-        std::vector<Box> boxes(recs.size());
-        for (size_t i = 0; i < recs.size(); ++i) {
-            const spt_instance& in = recs[i]->inst;
-            boxes[i].lo = {in.bmin[0], in.bmin[1], in.bmin[2]};
-            boxes[i].hi = {in.bmax[0], in.bmax[1], in.bmax[2]};
-        }
-        std::vector<const InstRec*> ordered;
-        if (aggregate == SPT_AGGREGATE_GROUP || recs.empty()) {
-            spt_bvh_node root_node;
-            std::memset(&root_node, 0, sizeof root_node);
-            Box all;
-            for (auto& b : boxes) all.grow(b);
-            root_node.bmin[0] = all.lo.x; root_node.bmin[1] = all.lo.y; root_node.bmin[2] = all.lo.z;
-            root_node.bmax[0] = all.hi.x; root_node.bmax[1] = all.hi.y; root_node.bmax[2] = all.hi.z;
-            root_node.a = 0;
-            root_node.b = SPT_LEAF_FLAG | (uint32_t)recs.size();
-            hs.tlas_nodes.push_back(root_node);
-            ordered = recs;
-        } else {
-            BvhBuildResult bvh = BvhBuilder(boxes, 4, 16).build();
-            hs.tlas_nodes = bvh.nodes;
-            for (uint32_t k : bvh.order) ordered.push_back(recs[k]);
-        }
-        std::map<std::string, uint32_t> inst_index;
-        for (auto* r : ordered) {
-            inst_index[r->name] = (uint32_t)hs.instances.size();
-            hs.instances.push_back(r->inst);
-        }
-
-        // lights: named lights (incl. "$env") in name order, then one ShapeLight per emissive
-        // instance in name order (scene_resources.rs:105-122)
-        int32_t env_index = -1;
-        for (auto& kv : lights) {
-            if (kv.second.type == SPT_LIGHT_ENV) env_index = (int32_t)hs.lights.size();
-            hs.lights.push_back(kv.second);
-        }
-        for (auto& kv : instances) {
-            const InstRec& r = kv.second;
-            // Surface::is_emissive (surface.rs:45-47) looks at the CONSTANT emissive only: a surface with emissive > 0 and an
-            // all-black emissive_map is still a light (it takes a slot of the sampler and of the alias table); the map's
-            // average only enters ShapeLight::power (shape_light.rs:79-82)
-            const spt_surface& sfc = hs.surfaces[r.inst.surface];
-            V3 em = avg_emissive[r.inst.surface];
-            if (luminance(V3{sfc.emissive[0], sfc.emissive[1], sfc.emissive[2]}) > 0.0f) {
-                spt_light l;
-                std::memset(&l, 0, sizeof l);
-                l.type = SPT_LIGHT_SHAPE;
-                l.instance = inst_index[r.name];
-                l.power = instance_area(r) * luminance(em);
-                hs.instances[l.instance].light = (int32_t)hs.lights.size();
-                hs.lights.push_back(l);
-            }
-        }
         hs.aggregate = aggregate;
         hs.light_sampler = sampler;
-        hs.env_light_index = env_index;
-        if (sampler == SPT_LIGHT_SAMPLER_POWER_IS) {
-            // PowerIsLightSampler::new (src/light_sampler/power_is.rs:24-46)
-            size_t n = hs.lights.size();
-            hs.light_props.assign(n, 0.0f);
-            float sum = 0.0f;
-            for (size_t i = 0; i < n; ++i) { hs.light_props[i] = hs.lights[i].power; sum += hs.light_props[i]; }
-            float sum_inv = 1.0f / sum;
-            for (auto& pr : hs.light_props) pr *= sum_inv;
-            build_alias(hs.light_props, hs.light_u, hs.light_k);
-        }
-        hs.finalize_desc();
+        hs.inst_recs = std::move(instances);
+        hs.named_lights = std::move(lights);
+        hs.avg_emissive = std::move(avg_emissive);
+        hs.finalize_dynamic();
     }
 };
+
+// Instance::new (src/primitive/instance.rs:53-85)
+InstRec make_instance_rec(const std::string& name, const Affine& trans, uint32_t prim_type, uint32_t prim_id, const Box& prim_box, uint32_t surf) {
+    InstRec rec;
+    rec.name = name;
+    rec.trans = trans;
+    spt_instance& in = rec.inst;
+    std::memset(&in, 0, sizeof in);
+    Affine inv = inverse(trans);
+    M3 it3 = transpose(inv.m);  // Transform::new: trans_it = inverse.matrix3.transpose()
+    auto put = [](float* dst, const Affine& a) {
+        const V3 cols[4] = {a.m.c0, a.m.c1, a.m.c2, a.t};
+        for (int c = 0; c < 4; ++c) { dst[3 * c] = cols[c].x; dst[3 * c + 1] = cols[c].y; dst[3 * c + 2] = cols[c].z; }
+    };
+    put(in.inv, inv);
+    put(in.fwd, trans);
+    const V3 nc[3] = {it3.c0, it3.c1, it3.c2};
+    for (int c = 0; c < 3; ++c) { in.nrm[3 * c] = nc[c].x; in.nrm[3 * c + 1] = nc[c].y; in.nrm[3 * c + 2] = nc[c].z; }
+    in.prim_type = prim_type;
+    in.prim_id = prim_id;
+    in.surface = surf;
+    in.light = -1;
+    // Bbox::transformed_by (src/core/bbox.rs:40-61): the 8 corners
+    const Box& pb = prim_box;
+    rec.prim_box = prim_box;
+    Box wb;
+    for (int c = 0; c < 8; ++c)
+        wb.grow(trans.point({(c & 4) ? pb.hi.x : pb.lo.x, (c & 2) ? pb.hi.y : pb.lo.y, (c & 1) ? pb.hi.z : pb.lo.z}));
+    in.bmin[0] = wb.lo.x; in.bmin[1] = wb.lo.y; in.bmin[2] = wb.lo.z;
+    in.bmax[0] = wb.hi.x; in.bmax[1] = wb.hi.y; in.bmax[2] = wb.hi.z;
+    return rec;
+}
+
+
+float HostScene::instance_area(const InstRec& r) const {
+    const spt_instance& in = r.inst;
+    if (in.prim_type == SPT_PRIM_BEZIER)   // the reference reaches `unimplemented!` (bezier.rs:188-190) when it builds the ShapeLight
+        throw HostError(SPT_HOST_ERR_UNSUPPORTED, "instance '" + r.name + "': an emissive surface on a cubic_bezier primitive (CubicBezier::surface_area is unimplemented in the reference)");
+    if (in.prim_type == SPT_PRIM_SPHERE) {
+        float rad = spheres[in.prim_id].radius * 0.5f;
+        V3 v0 = r.trans.vector({-rad, -rad, -rad}), v1 = r.trans.vector({-rad, -rad, rad});
+        V3 v2 = r.trans.vector({-rad, rad, -rad}), v3 = r.trans.vector({rad, -rad, -rad});
+        auto d2 = [](V3 a, V3 b) { V3 d = a - b; return dot(d, d); };
+        float a2 = d2(v0, v1), b2 = d2(v0, v2), c2 = d2(v0, v3);
+        return 4.0f * 3.14159265358979323846f * std::sqrt((a2 * b2 + b2 * c2 + c2 * a2) / 3.0f);
+    }
+    const spt_mesh& m = meshes[in.prim_id];
+    float sum = 0.0f;
+    for (uint32_t t = m.tri_first; t < m.tri_first + m.tri_count; ++t) {
+        const spt_tri_pos& tp = tri_pos[t];
+        V3 p0 = r.trans.point({tp.p0[0], tp.p0[1], tp.p0[2]});
+        V3 p1 = r.trans.point({tp.p1[0], tp.p1[1], tp.p1[2]});
+        V3 p2 = r.trans.point({tp.p2[0], tp.p2[1], tp.p2[2]});
+        sum += length(cross(p1 - p0, p2 - p0)) * 0.5f;
+    }
+    return sum;
+}
+
+
+// The part of SceneBuilder::finish that depends on where the instances are: run by the loader, and again by
+// spt_host_scene_set_transforms / _set_light
+void HostScene::finalize_dynamic() {
+    tlas_nodes.clear();
+    instances.clear();
+    lights.clear();
+    light_props.clear(); light_u.clear(); light_k.clear();
+    // instances in name order, then TLAS
+    std::vector<const InstRec*> recs;
+    for (auto& kv : inst_recs) recs.push_back(&kv.second);
+    std::vector<Box> boxes(recs.size());
+    for (size_t i = 0; i < recs.size(); ++i) {
+        const spt_instance& in = recs[i]->inst;
+        boxes[i].lo = {in.bmin[0], in.bmin[1], in.bmin[2]};
+        boxes[i].hi = {in.bmax[0], in.bmax[1], in.bmax[2]};
+    }
+    std::vector<const InstRec*> ordered;
+    if (aggregate == SPT_AGGREGATE_GROUP || recs.empty()) {
+        spt_bvh_node root_node;
+        std::memset(&root_node, 0, sizeof root_node);
+        Box all;
+        for (auto& b : boxes) all.grow(b);
+        root_node.bmin[0] = all.lo.x; root_node.bmin[1] = all.lo.y; root_node.bmin[2] = all.lo.z;
+        root_node.bmax[0] = all.hi.x; root_node.bmax[1] = all.hi.y; root_node.bmax[2] = all.hi.z;
+        root_node.a = 0;
+        root_node.b = SPT_LEAF_FLAG | (uint32_t)recs.size();
+        tlas_nodes.push_back(root_node);
+        ordered = recs;
+    } else {
+        BvhBuildResult bvh = BvhBuilder(boxes, 4, 16).build();
+        tlas_nodes = bvh.nodes;
+        for (uint32_t k : bvh.order) ordered.push_back(recs[k]);
+    }
+    inst_index.clear();
+    for (auto* r : ordered) {
+        inst_index[r->name] = (uint32_t)instances.size();
+        instances.push_back(r->inst);
+    }
+
+    // lights: named lights (incl. "$env") in name order, then one ShapeLight per emissive
+    // instance in name order (scene_resources.rs:105-122)
+    int32_t env_index = -1;
+    for (auto& kv : named_lights) {
+        if (kv.second.type == SPT_LIGHT_ENV) env_index = (int32_t)lights.size();
+        lights.push_back(kv.second);
+    }
+    for (auto& kv : inst_recs) {
+        const InstRec& r = kv.second;
+        // Surface::is_emissive (surface.rs:45-47) looks at the CONSTANT emissive only: a surface with emissive > 0 and an
+        // all-black emissive_map is still a light (it takes a slot of the sampler and of the alias table); the map's
+        // average only enters ShapeLight::power (shape_light.rs:79-82)
+        const spt_surface& sfc = surfaces[r.inst.surface];
+        V3 em = avg_emissive[r.inst.surface];
+        if (luminance(V3{sfc.emissive[0], sfc.emissive[1], sfc.emissive[2]}) > 0.0f) {
+            spt_light l;
+            std::memset(&l, 0, sizeof l);
+            l.type = SPT_LIGHT_SHAPE;
+            l.instance = inst_index[r.name];
+            l.power = instance_area(r) * luminance(em);
+            instances[l.instance].light = (int32_t)lights.size();
+            lights.push_back(l);
+        }
+    }
+    env_light_index = env_index;
+    if (light_sampler == SPT_LIGHT_SAMPLER_POWER_IS) {
+        // PowerIsLightSampler::new (src/light_sampler/power_is.rs:24-46)
+        size_t n = lights.size();
+        light_props.assign(n, 0.0f);
+        float sum = 0.0f;
+        for (size_t i = 0; i < n; ++i) { light_props[i] = lights[i].power; sum += light_props[i]; }
+        float sum_inv = 1.0f / sum;
+        for (auto& pr : light_props) pr *= sum_inv;
+        SceneBuilder::build_alias(light_props, light_u, light_k);
+    }
+    finalize_desc();
+}
+
+// spt_host_scene_set_transforms: the named instances made again under their new transforms (Instance::new), then the loader's own
+// finalisation.  Everything is checked before anything is replaced.
+void HostScene::set_transforms(const std::vector<std::pair<std::string, Affine>>& moves) {
+    std::vector<std::pair<InstRec*, InstRec>> made;
+    std::set<std::string> named;
+    for (const auto& mv : moves) {
+        auto it = inst_recs.find(mv.first);
+        if (it == inst_recs.end()) throw HostError(SPT_HOST_ERR_SCHEMA, "There is no instance named '" + mv.first + "'");
+        if (!named.insert(mv.first).second) throw HostError(SPT_ERR_INVALID_ARG, "instance '" + mv.first + "' is named twice");
+        const InstRec& old = it->second;
+        const float det = determinant(mv.second.m);
+        if (!std::isfinite(det) || det == 0.0f) throw HostError(SPT_ERR_INVALID_ARG, "instance '" + mv.first + "': the transform is not invertible");
+        InstRec rec = make_instance_rec(old.name, mv.second, old.inst.prim_type, old.inst.prim_id, old.prim_box, old.inst.surface);
+        bool finite = true;
+        for (int k = 0; k < 12; ++k) finite = finite && std::isfinite(rec.inst.inv[k]) && std::isfinite(rec.inst.fwd[k]);
+        for (int k = 0; k < 3; ++k) finite = finite && std::isfinite(rec.inst.bmin[k]) && std::isfinite(rec.inst.bmax[k]) && std::fabs(rec.inst.bmin[k]) < 3.0e38f && std::fabs(rec.inst.bmax[k]) < 3.0e38f;
+        if (!finite) throw HostError(SPT_ERR_INVALID_ARG, "instance '" + mv.first + "': the transform is not invertible or its box is not finite");
+        made.emplace_back(&it->second, std::move(rec));
+    }
+    std::vector<InstRec> saved;
+    for (auto& m : made) { saved.push_back(*m.first); *m.first = std::move(m.second); }
+    try {
+        finalize_dynamic();
+    } catch (...) {   // (a shape light's area, say: nothing the checks above let through is known to get here)
+        for (size_t i = 0; i < made.size(); ++i) *made[i].first = saved[i];
+        finalize_dynamic();
+        throw;
+    }
+}
+
+void HostScene::set_light(const std::string& name, const spt_light& light) {
+    auto it = named_lights.find(name);
+    if (it == named_lights.end()) throw HostError(SPT_HOST_ERR_SCHEMA, "There is no light named '" + name + "'");
+    if (light.type > SPT_LIGHT_SPOT || light.type != it->second.type)
+        throw HostError(SPT_ERR_INVALID_ARG, "light '" + name + "': a directional, point or spot light of the same type is expected");
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(light.pos[k]) || !std::isfinite(light.dir[k]) || !std::isfinite(light.strength[k]))
+            throw HostError(SPT_ERR_INVALID_ARG, "light '" + name + "': not finite");
+    it->second = light;
+    it->second.power = luminance({light.strength[0], light.strength[1], light.strength[2]});   // as load_light sets it
+    finalize_dynamic();
+}
+
+// `spt --animate FILE`: {"frames": [ {"<instance name>": {matrix / scale / rotate / translate as in the scene file}, ...}, ... ]}
+Animation* load_animation(const std::string& path, const HostScene& hs) {
+    JsonValue root = parse_json_file(path);
+    const JsonValue* frames = root.kind == JsonValue::Object ? root.get("frames") : nullptr;
+    if (!frames || frames->kind != JsonValue::Array) throw HostError(SPT_HOST_ERR_SCHEMA, path + ": an object with an array 'frames' is expected");
+    std::unique_ptr<Animation> an(new Animation());
+    for (const JsonValue& fr : frames->arr) {
+        if (fr.kind != JsonValue::Object) throw HostError(SPT_HOST_ERR_SCHEMA, path + ": a frame must be an object of instance name -> transform");
+        an->frames.emplace_back();
+        for (auto& kv : fr.obj) {
+            if (!hs.inst_recs.count(kv.first)) throw HostError(SPT_HOST_ERR_SCHEMA, path + ": there is no instance named '" + kv.first + "'");
+            if (kv.second.kind != JsonValue::Object) throw HostError(SPT_HOST_ERR_SCHEMA, path + ": the transform of '" + kv.first + "' must be an object");
+            Params p(kv.second, path);
+            p.set_name("animate-" + kv.first);
+            an->frames.back().emplace_back(kv.first, transform_from_params(p));
+            if (p.num_unused()) throw HostError(SPT_HOST_ERR_SCHEMA, path + ": '" + kv.first + "' has keys that are no transform (matrix, scale, rotate, translate)");
+        }
+    }
+    return an.release();
+}
 
 void HostScene::finalize_desc() {
     std::memset(&desc, 0, sizeof desc);

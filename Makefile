@@ -25,7 +25,7 @@ HOST_HDR := $(wildcard $(PKG)/csrc/host/*.hpp) $(wildcard include/*.h)
 HIP_SRC  := $(wildcard $(PKG)/csrc/hip/*.hip)
 HIP_HDR  := $(wildcard $(PKG)/csrc/hip/*.h) $(wildcard include/*.h)
 
-.PHONY: all host hip hip-plain cli oracle selftest out-layout-check clean
+.PHONY: all host hip hip-plain cli oracle selftest out-layout-check scene-build-check clean
 all: host oracle hip cli
 
 host: $(LIBDIR)/libspt_host.so
@@ -39,11 +39,20 @@ $(LIBDIR)/libspt_host.so: $(HOST_SRC) $(HOST_HDR)
 	@mkdir -p $(LIBDIR)
 	$(CXX) $(CXXFLAGS) -shared -o $@ $(HOST_SRC) -lz -lpthread
 
-# one object per translation unit (spt_hip.hip = host side + film kernels, inst_*.hip = groups of kernel instantiations,
-# see csrc/hip/kernel_list.h), compiled side by side with `make -jN`
+# one object per translation unit (spt_hip.hip = the runtime side: device, streams, uploads, scheduling + film kernels,
+# inst_*.hip = groups of kernel instantiations, see csrc/hip/kernel_list.h; scene_build.cpp = the scene builder, host code
+# without a HIP call, see csrc/hip/scene_build.h), compiled side by side with `make -jN`
 OBJDIR   := build/hip
-HIP_OBJ     := $(patsubst $(PKG)/csrc/hip/%.hip,$(OBJDIR)/plain/%.o,$(HIP_SRC))
-HIP_OBJ_BEZ := $(patsubst $(PKG)/csrc/hip/%.hip,$(OBJDIR)/bez/%.o,$(HIP_SRC))
+BUILD_SRC := $(PKG)/csrc/hip/scene_build.cpp
+BUILD_OBJ := $(OBJDIR)/scene_build.o
+HIP_OBJ     := $(patsubst $(PKG)/csrc/hip/%.hip,$(OBJDIR)/plain/%.o,$(HIP_SRC)) $(BUILD_OBJ)
+HIP_OBJ_BEZ := $(patsubst $(PKG)/csrc/hip/%.hip,$(OBJDIR)/bez/%.o,$(HIP_SRC)) $(BUILD_OBJ)
+
+# the builder's float arithmetic (box padding, SAH costs, the 4-wide quantisation) reaches the films: the compiler, the mode and
+# the flags of the host side of spt_hip.hip, and that side alone (no device pass).  Nothing in it depends on SPT_WITH_BEZIER, so both libraries link the one object
+$(BUILD_OBJ): $(BUILD_SRC) $(HIP_HDR)
+	@mkdir -p $(dir $@)
+	$(HIPCC) -x hip --offload-host-only $(HIPFLAGS) -c -o $@ $<
 
 $(OBJDIR)/plain/%.o: $(PKG)/csrc/hip/%.hip $(HIP_HDR)
 	@mkdir -p $(dir $@)
@@ -84,6 +93,16 @@ out-layout-check: $(SELFTEST_DIR)/out_layout_check
 $(SELFTEST_DIR)/out_layout_check: tests/out_layout_check.cpp $(PKG)/csrc/hip/out_layout.h
 	@mkdir -p $(SELFTEST_DIR)
 	$(CXX) -std=c++17 -O1 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -static-libasan -static-libubsan -o $@ $<
+
+# The scene builder on its own, under AddressSanitizer + UBSan, over scene files that libspt_host.so loads: layout, references,
+# "an update writes what a creation writes", determinism and the refusals (tests/test_scene_build.py writes the scenes and runs it)
+ROCM_PATH ?= $(shell hipconfig --rocmpath 2>/dev/null || echo /opt/rocm)
+scene-build-check: $(SELFTEST_DIR)/scene_build_check
+$(SELFTEST_DIR)/scene_build_check: tests/scene_build_check.cpp $(BUILD_SRC) $(HIP_HDR) $(LIBDIR)/libspt_host.so
+	@mkdir -p $(SELFTEST_DIR)
+	$(CXX) -std=c++17 -O1 -g -Wall -Wextra -ffp-contract=off -fno-fast-math -Iinclude -I$(PKG)/csrc/hip -D__HIP_PLATFORM_AMD__ -isystem $(ROCM_PATH)/include \
+	    -fsanitize=address,undefined -fno-sanitize-recover=undefined -static-libasan -static-libubsan -o $@ tests/scene_build_check.cpp $(BUILD_SRC) \
+	    -L$(LIBDIR) -lspt_host -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
 
 clean:
 	rm -rf $(LIBDIR) build oracle/*.so oracle/_ref

@@ -26,8 +26,9 @@
 // Every function here must be called by ALL 64 lanes of a wave (`active` says which of them carry a ray).
 #pragma once
 #include "stream.h"   // lds_u64
+#include "scene_consts.h"   // kFlatBudget
 
-constexpr uint32_t kFlatBudget = 32;         // triangle tests per ray up to which a scene is walked exhaustively
+// (kFlatBudget, the triangle tests per ray up to which a scene is walked exhaustively: scene_consts.h)
 constexpr uint32_t kFlatTransposeMin = 4;    // meshes of at least this many (and at most 64) triangles: box test + transposition
 
 SPT_DEV uint32_t flat_uniform(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }

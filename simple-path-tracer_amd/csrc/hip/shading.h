@@ -13,6 +13,7 @@
 // material, so the kernels switch on a POD material record instead.
 #pragma once
 #include "trace.h"
+#include "scene_consts.h"   // TEXOP_*
 #include "../../../include/spt_pndf.h"
 
 struct DRng {
@@ -212,7 +213,7 @@ SPT_DEV void calc_differential(DInter& it, const DRay& ray, float t, f3 xo, f3 x
 // sRGB decode act on the top of a 4-deep value stack kept in registers (the host refuses deeper
 // programs).  An image leaf carries the chain of TexInputModifiers above it (outermost first), which it
 // applies to the hit's TextureInput in the reference's order before sampling.
-enum { TEXOP_SCALAR = 0, TEXOP_IMAGE = 1, TEXOP_ADD = 2, TEXOP_SUB = 3, TEXOP_MUL = 4, TEXOP_DIV = 5, TEXOP_SRGB = 6 };
+// (the TEXOP_* instructions: scene_consts.h)
 
 struct DTexIn {  // TextureInput (mod.rs:50-62) as From<&Intersection> fills it (mod.rs:143-157)
     f3 position, normal, tangent, bitangent;

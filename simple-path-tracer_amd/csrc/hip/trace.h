@@ -17,6 +17,7 @@
 // divisions per node; it only culls, the returned hit is unaffected.
 #pragma once
 #include "device_math.h"
+#include "scene_consts.h"   // kLeaf, kLdsStack, kSpillStack
 #include "bezier.h"
 
 struct DScene {
@@ -244,7 +245,7 @@ SPT_DEV DRay to_object(const DScene& sc, uint32_t inst, const DRay& r, uint32_t*
 // matters for exactly equal hit distances: the closest hit is defined as the minimum over
 // (t, instance, prim) and boxes are culled with t0 <= t_best, which is independent of the order
 // (the oracle's ORACLE_TIE_MIN_ID mode applies the same rule).
-constexpr uint32_t kLeaf = 0x80000000u;
+// (kLeaf: scene_consts.h)
 SPT_DEV uint32_t leaf_first(uint32_t ref) { return ref & 0x07ffffffu; }
 SPT_DEV uint32_t leaf_count(uint32_t ref) { return (ref >> 27) & 15u; }
 
@@ -268,8 +269,7 @@ SPT_DEV bool slab_t0(float4 lo, float4 hi, f3 o, f3 inv_d, float t_min, float* t
 // order keeps the live stack short (it only grows where BOTH children are hit), so the spill is
 // rarely touched, and LDS per workgroup stays at 16 KiB whatever the tree depth — a full-depth LDS
 // stack (58 KiB for the 1 M-triangle scene) would cap the CU at two workgroups.
-constexpr uint32_t kLdsStack = 8;
-constexpr uint32_t kSpillStack = 40;
+// (kLdsStack = 8, kSpillStack = 40: scene_consts.h)
 struct TStack {
     uint32_t sp = 0;
     uint2* spill;   // kSpillStack private entries owned by the caller (kept out of this struct so that

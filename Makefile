@@ -25,7 +25,7 @@ HOST_HDR := $(wildcard $(PKG)/csrc/host/*.hpp) $(wildcard include/*.h)
 HIP_SRC  := $(wildcard $(PKG)/csrc/hip/*.hip)
 HIP_HDR  := $(wildcard $(PKG)/csrc/hip/*.h) $(wildcard include/*.h)
 
-.PHONY: all host hip hip-plain cli oracle selftest out-layout-check scene-build-check clean
+.PHONY: all host hip hip-plain cli oracle selftest out-layout-check scene-build-check scene-deform-refit-check clean
 all: host oracle hip cli
 
 host: $(LIBDIR)/libspt_host.so
@@ -103,6 +103,14 @@ $(SELFTEST_DIR)/scene_build_check: tests/scene_build_check.cpp $(BUILD_SRC) $(HI
 	$(CXX) -std=c++17 -O1 -g -Wall -Wextra -ffp-contract=off -fno-fast-math -Iinclude -I$(PKG)/csrc/hip -D__HIP_PLATFORM_AMD__ -isystem $(ROCM_PATH)/include \
 	    -fsanitize=address,undefined -fno-sanitize-recover=undefined -static-libasan -static-libubsan -o $@ tests/scene_build_check.cpp $(BUILD_SRC) \
 	    -L$(LIBDIR) -lspt_host -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
+
+# The refit arithmetic of spt_scene_deform's kernels (csrc/hip/scene_refit.h) under the kernels' level schedule, on the CPU, over
+# trees the builder makes: a stand-alone host program under AddressSanitizer + UBSan (tests/test_scene_deform_refit.py runs it)
+scene-deform-refit-check: $(SELFTEST_DIR)/scene_deform_refit_check
+$(SELFTEST_DIR)/scene_deform_refit_check: tests/scene_deform_refit_check.cpp $(BUILD_SRC) $(HIP_HDR)
+	@mkdir -p $(SELFTEST_DIR)
+	$(CXX) -std=c++17 -O1 -g -Wall -Wextra -ffp-contract=off -fno-fast-math -Iinclude -I$(PKG)/csrc/hip -D__HIP_PLATFORM_AMD__ -isystem $(ROCM_PATH)/include \
+	    -fsanitize=address,undefined -fno-sanitize-recover=undefined -static-libasan -static-libubsan -o $@ tests/scene_deform_refit_check.cpp $(BUILD_SRC)
 
 clean:
 	rm -rf $(LIBDIR) build oracle/*.so oracle/_ref

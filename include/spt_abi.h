@@ -456,6 +456,28 @@ typedef struct spt_scene_update_desc {
 } spt_scene_update_desc;
 spt_status spt_scene_update(spt_scene* scene, const spt_scene_update_desc* u);
 
+/* spt_scene_deform (additive to ABI v14: detect it by its symbol): moves the vertices of meshes of a live scene.  Each named
+ * mesh gets new tri_pos (and, if given, tri_attr) records for its whole range, in the order of the creation's descriptor: counts
+ * and topology stay.  `u` is required - the instances' world boxes, a shape light's power and the alias table change with the
+ * geometry - and gets every check and every meaning spt_scene_update gives it; n_meshes == 0 is spt_scene_update(scene, u).
+ * After SPT_OK every later call on the scene returns the words a scene freshly created from the edited descriptor returns (but
+ * for the triangle test's own grazing-ray false positives that any two trees over the same triangles can differ in).
+ *   - Large scenes: the triangles are rewritten and the library's BLAS is refitted on the device, topology unchanged (no host
+ *     build).  A tree refitted after a large deformation is walked more slowly than a rebuilt one: recreate the scene then.
+ *     Scenes small enough to be walked from LDS get the named meshes' trees built again on the host.
+ *   - Refused, the scene exactly as before: SPT_ERR_INVALID_ARG for a null array, a mesh index out of range or named twice, a
+ *     wrong tri_count, a position that is not finite, a live film; SPT_ERR_UNSUPPORTED for a scene created under
+ *     SPT_REFERENCE_BVH=1 (it walks the caller's trees), and when the geometry no longer fits the form chosen at creation.
+ *   - Ordering: as spt_scene_update.  Counter 4 of spt_debug_render_info counts the call, counter 5 reports its bytes: at most
+ *     the update's + 192 per triangle of the named meshes + 64; no triangle of another mesh is uploaded or read. */
+typedef struct spt_mesh_deform {
+    uint32_t mesh;                 /* index into the creation's meshes[] */
+    uint32_t tri_count;            /* must equal meshes[mesh].tri_count */
+    const spt_tri_pos*  tri_pos;   /* tri_count records, record k replaces triangle meshes[mesh].tri_first + k */
+    const spt_tri_attr* tri_attr;  /* same order; NULL: the attributes stay */
+} spt_mesh_deform;
+spt_status spt_scene_deform(spt_scene* scene, const spt_scene_update_desc* u, uint32_t n_meshes, const spt_mesh_deform* meshes);
+
 /* The hot path: RendererT::render for one image shard.  rgb_mean_out receives
  * shard_rows*width*3 f32 = per-pixel mean radiance (Film::filter_pixel with the
  * box filter, src/core/film.rs:71-92: the sum of the samples of the (2 ceil(radius - 0.5) + 1)^2 pixels around it
@@ -828,7 +850,11 @@ spt_status spt_debug_bxdf(const spt_scene* scene, int32_t device, const spt_mate
  *   what 3  frames of spt_render delivered without the runtime's copy: the finish kernel stored the image into rgb_mean_out
  *           itself (an SPT_RENDER_ASYNC frame on the overlapped schedule, radius 0.5, page-locked destination, no SPT_NO_DIRECT_OUT=1)
  *   what 4  spt_scene_update calls applied to the scene (a library without spt_scene_update refuses 4 and 5)
- *   what 5  bytes the last spt_scene_update copied to the device (0: none yet) */
+ *   what 5  bytes the last spt_scene_update copied to the device (0: none yet)
+ *   what 6  ns the copies and kernels of the last spt_scene_deform that named a mesh took on the device (0: none yet); waits for
+ *           them (a library without spt_scene_deform refuses 6).  Like every counter here a debug seam for the measuring tools
+ *           (tools/scene_deform_cost.py), not part of what spt_scene_deform promises: it may change without an ABI version
+ * spt_scene_deform counts as an update in 4 and reports its bytes in 5. */
 spt_status spt_debug_render_info(const spt_scene* scene, uint32_t what, uint64_t* out);
 
 const char* spt_last_error(void);

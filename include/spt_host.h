@@ -61,6 +61,22 @@ spt_status spt_host_scene_set_transforms(spt_host_scene* scene, uint32_t n, cons
 /* Replaces the directional, point or spot light called `name` (the type must stay; `power` is set from the strength as the
  * loader sets it, `instance` is ignored). */
 spt_status spt_host_scene_set_light(spt_host_scene* scene, const char* name, const spt_light* light);
+/* Deforming a loaded mesh (spt_scene_deform takes the result to a live device scene).  `primitive_name` names a `trimesh`
+ * primitive of a JSON scene; its vertices are in the OBJ loader's single-index order (one vertex per distinct v/vt/vn tuple, in
+ * first-seen order).  SPT_HOST_ERR_SCHEMA: no such primitive; SPT_HOST_ERR_UNSUPPORTED: a glTF primitive or a Catmull-Clark
+ * surface.
+ *   _mesh_index: the primitive's index in the descriptor's meshes[] (a helper for callers that name meshes to spt_scene_deform,
+ *     such as the Python binding; nothing else depends on it).
+ *   _mesh_positions: n_vertices, and 3 floats per vertex into `out` unless it is NULL.
+ *   _set_mesh_positions: new positions (and normals; NULL keeps them).  Tangents are computed again, the mesh's tri_pos /
+ *     tri_attr range is rewritten in place (triangle k stays the same face), the boxes of its blas_nodes are refitted over the
+ *     unchanged topology, and every instance of it, the TLAS, the shape lights' power and the alias table follow as in
+ *     spt_host_scene_set_transforms.  SPT_ERR_INVALID_ARG: a wrong count or a value that is not finite; the scene is unchanged.
+ *     Setting the file's own positions again gives the loaded descriptor back byte for byte. */
+spt_status spt_host_scene_mesh_index(const spt_host_scene* scene, const char* primitive_name, uint32_t* mesh);
+spt_status spt_host_scene_mesh_positions(const spt_host_scene* scene, const char* primitive_name, uint32_t* n_vertices, float* out /* may be NULL */);
+spt_status spt_host_scene_set_mesh_positions(spt_host_scene* scene, const char* primitive_name, uint32_t n_vertices, const float* positions,
+                                             const float* normals /* NULL: keep */);
 /* `spt --animate FILE`: {"frames": [ {"<instance name>": <transform object in the scene file's own syntax: matrix, scale, rotate,
  * translate>, ...}, ... ]}, checked against `scene` (SPT_HOST_ERR_SCHEMA: a malformed file, an unknown instance).
  * spt_host_animation_apply hands frame `frame`'s transforms to spt_host_scene_set_transforms; instances a frame does not name

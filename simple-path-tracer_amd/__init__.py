@@ -285,6 +285,11 @@ class SceneUpdateDesc(C.Structure):
                 ("light_alias", AliasTable)]
 
 
+class MeshDeform(C.Structure):
+    """spt_mesh_deform (spt_scene_deform): new tri_pos (and tri_attr, or NULL) records for the whole range of one mesh."""
+    _fields_ = [("mesh", C.c_uint32), ("tri_count", C.c_uint32), ("tri_pos", C.POINTER(TriPos)), ("tri_attr", C.POINTER(TriAttr))]
+
+
 def _load(name: str) -> C.CDLL:
     path = os.path.join(LIB_DIR, name)
     if not os.path.exists(path):
@@ -332,6 +337,10 @@ def host_lib() -> C.CDLL:
             lib.spt_host_scene_instance_index.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint32)]
             lib.spt_host_scene_set_transforms.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_char_p), C.c_void_p]
             lib.spt_host_scene_set_light.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(Light)]
+        if hasattr(lib, "spt_host_scene_set_mesh_positions"):   # (the same)
+            lib.spt_host_scene_mesh_positions.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint32), C.c_void_p]
+            lib.spt_host_scene_set_mesh_positions.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_void_p, C.c_void_p]
+            lib.spt_host_scene_mesh_index.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint32)]
         lib.spt_host_load_renderer.argtypes = [C.c_char_p, C.POINTER(RenderParams), C.POINTER(C.c_float)]
         if hasattr(lib, "spt_host_load_renderer_filter"):   # (a library built before the weighted filters lacks it)
             lib.spt_host_load_renderer_filter.argtypes = [C.c_char_p, C.POINTER(RenderParams), C.POINTER(FilterDesc)]
@@ -406,6 +415,8 @@ def hip_lib() -> C.CDLL:
             lib.spt_radiance.argtypes = [C.c_void_p, C.POINTER(RadianceJob)]
         if hasattr(lib, "spt_scene_update"):   # (the same)
             lib.spt_scene_update.argtypes = [C.c_void_p, C.POINTER(SceneUpdateDesc)]
+        if hasattr(lib, "spt_scene_deform"):   # (the same)
+            lib.spt_scene_deform.argtypes = [C.c_void_p, C.POINTER(SceneUpdateDesc), C.c_uint32, C.POINTER(MeshDeform)]
         lib.spt_debug_detmath.argtypes = [C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.spt_debug_bxdf.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Material), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -435,6 +446,7 @@ class Scene:
         _check_host(host_lib().spt_host_load_scene(os.fspath(path).encode(), C.byref(self._h)))
         self.path = os.fspath(path)
         self._device_scenes = {}
+        self._mesh_gen = {}   # mesh index -> how often set_mesh_positions has edited it (a DeviceScene compares with what it has seen)
 
     @property
     def desc(self) -> SceneDesc:
@@ -507,6 +519,46 @@ class Scene:
         """spt_host_scene_set_light: replaces the directional, point or spot light called `name` (same type)."""
         _check_host(self._dynamic_host().spt_host_scene_set_light(self._h, name.encode(), C.byref(light)))
 
+    def _mesh_host(self):
+        lib = host_lib()
+        if not hasattr(lib, "spt_host_scene_set_mesh_positions"):
+            raise SptError(4, "this libspt_host.so cannot deform a loaded mesh (no spt_host_scene_set_mesh_positions)")
+        return lib
+
+    def mesh_index(self, name: str) -> int:
+        """The index in the descriptor's meshes[] of the trimesh primitive called `name`."""
+        index = C.c_uint32(0)
+        _check_host(self._mesh_host().spt_host_scene_mesh_index(self._h, name.encode(), C.byref(index)))
+        return int(index.value)
+
+    def mesh_positions(self, name: str) -> np.ndarray:
+        """spt_host_scene_mesh_positions: the (n_vertices, 3) f32 vertex positions of the trimesh primitive `name`, in the OBJ
+        loader's single-index vertex order."""
+        lib = self._mesh_host()
+        n = C.c_uint32(0)
+        _check_host(lib.spt_host_scene_mesh_positions(self._h, name.encode(), C.byref(n), None))
+        out = np.zeros((n.value, 3), dtype=np.float32)
+        _check_host(lib.spt_host_scene_mesh_positions(self._h, name.encode(), C.byref(n), out.ctypes.data))
+        return out
+
+    def set_mesh_positions(self, name: str, positions, normals=None) -> None:
+        """spt_host_scene_set_mesh_positions: new vertex positions (and normals, or None to keep them) for the trimesh primitive
+        `name`; triangles, uvs and counts stay.  The descriptor becomes the one the loader makes of these vertices (tangents,
+        triangle records, the caller-side BLAS boxes, instance boxes, TLAS, shape-light power, alias table); a refused call leaves
+        it as it was.  The mesh is marked dirty: a DeviceScene keeps the old geometry until its update()."""
+        lib = self._mesh_host()
+        mesh = self.mesh_index(name)
+        pos = np.ascontiguousarray(positions, dtype=np.float32)
+        if pos.ndim != 2 or pos.shape[1] != 3:
+            raise ValueError("positions: an (n_vertices, 3) array is expected")
+        nrm = None
+        if normals is not None:
+            nrm = np.ascontiguousarray(normals, dtype=np.float32)
+            if nrm.shape != pos.shape:
+                raise ValueError("normals: one normal per position is expected")
+        _check_host(lib.spt_host_scene_set_mesh_positions(self._h, name.encode(), pos.shape[0], pos.ctypes.data, nrm.ctypes.data if nrm is not None else None))
+        self._mesh_gen[mesh] = self._mesh_gen.get(mesh, 0) + 1
+
     def device_scene(self, device: int = 0) -> "DeviceScene":
         if device not in self._device_scenes:
             self._device_scenes[device] = DeviceScene(self, device)
@@ -554,6 +606,7 @@ class DeviceScene:
         self._pinned = {}
         self._films = weakref.WeakSet()   # ProgressiveFilm objects on this scene: destroyed before it
         desc = scene.desc
+        self._mesh_seen = dict(scene._mesh_gen)
         _check_hip(hip_lib().spt_scene_create(C.byref(desc), device, C.byref(self._h)))
 
     def film_buffer(self, rows: int, width: int) -> np.ndarray:
@@ -631,12 +684,27 @@ class DeviceScene:
         d = self.scene.desc
         u = SceneUpdateDesc(size=C.sizeof(SceneUpdateDesc), flags=0, n_tlas_nodes=d.n_tlas_nodes, tlas_nodes=d.tlas_nodes,
                             n_instances=d.n_instances, instances=d.instances, n_lights=d.n_lights, lights=d.lights, light_alias=d.light_alias)
-        self._update(u)
+        dirty = sorted(m for m, gen in self.scene._mesh_gen.items() if self._mesh_seen.get(m) != gen)
+        if not dirty:
+            self._update(u)
+            return
+        # meshes edited by Scene.set_mesh_positions since this device scene last saw them: their records as the Scene has them now
+        edits = (MeshDeform * len(dirty))()
+        for e, m in zip(edits, dirty):
+            mesh = d.meshes[m]
+            e.mesh, e.tri_count = m, mesh.tri_count
+            e.tri_pos = C.cast(C.addressof(d.tri_pos[mesh.tri_first]), C.POINTER(TriPos))
+            e.tri_attr = C.cast(C.addressof(d.tri_attr[mesh.tri_first]), C.POINTER(TriAttr))
+        self._deform(u, edits)
+        for m in dirty:
+            self._mesh_seen[m] = self.scene._mesh_gen[m]
 
-    def update_arrays(self, instances, lights, tlas_nodes=None, light_alias=None) -> None:
+    def update_arrays(self, instances, lights, tlas_nodes=None, light_alias=None, meshes=None) -> None:
         """spt_scene_update for callers who edit the records themselves: `instances` / `lights` / `tlas_nodes` are arrays of the
         Instance / Light / BvhNode records (as Scene.array returns them; the instances in the leaf order of tlas_nodes),
-        light_alias the (props, u, k) arrays of a power_is scene.  None: the Scene's current ones."""
+        light_alias the (props, u, k) arrays of a power_is scene.  None: the Scene's current ones.  `meshes`: {mesh index:
+        (tri_pos, tri_attr or None)} arrays of TriPos / TriAttr records for the mesh's whole range - then the call is
+        spt_scene_deform."""
         d = self.scene.desc
         keep = []
 
@@ -660,7 +728,18 @@ class DeviceScene:
             _, u.light_alias.u = records(uu, C.c_float)
             _, u.light_alias.k = records(k, C.c_uint32)
             u.light_alias.n = n
-        self._update(u)
+        if meshes is None:
+            self._update(u)
+            return
+        edits = (MeshDeform * max(len(meshes), 1))()
+        for e, (m, (tri_pos, tri_attr)) in zip(edits, meshes.items()):
+            e.mesh = m
+            e.tri_count, e.tri_pos = records(tri_pos, TriPos)
+            if tri_attr is not None:
+                n_attr, e.tri_attr = records(tri_attr, TriAttr)
+                if n_attr != e.tri_count:
+                    raise ValueError("mesh %d: one tri_attr record per tri_pos record is expected" % m)
+        self._deform(u, edits, len(meshes))
 
     def _update(self, u: "SceneUpdateDesc") -> None:
         lib = hip_lib()
@@ -668,11 +747,18 @@ class DeviceScene:
             raise SptError(4, "this libspt_hip.so has no spt_scene_update")
         _check_hip(lib.spt_scene_update(self._h, C.byref(u)))
 
+    def _deform(self, u: "SceneUpdateDesc", edits, n=None) -> None:
+        lib = hip_lib()
+        if not hasattr(lib, "spt_scene_deform"):
+            raise SptError(4, "this libspt_hip.so has no spt_scene_deform")
+        _check_hip(lib.spt_scene_deform(self._h, C.byref(u), len(edits) if n is None else n, edits))
+
     def render_info(self, what: int) -> int:
         """Test seam (spt_debug_render_info): 0 passes resolved on the film stream, 1 passes on the single-stream path;
         2 the ns the kernels of the last read-out of a sample-keeping film of the scene took on the device; 3 frames whose
         finish kernel stored the image into the (page-locked) output buffer itself, without the runtime's copy; 4 the
-        spt_scene_update calls applied to the scene; 5 the bytes the last of them copied to the device."""
+        spt_scene_update / spt_scene_deform calls applied to the scene; 5 the bytes the last of them copied to the device; 6 the
+        ns the copies and kernels of the last spt_scene_deform that named a mesh took on the device (waits for them)."""
         v = C.c_uint64(0)
         _check_hip(hip_lib().spt_debug_render_info(self._h, what, C.byref(v)))
         return int(v.value)

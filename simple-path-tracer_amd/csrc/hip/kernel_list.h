@@ -2,6 +2,7 @@
 // (csrc/hip/inst_*.hip define SPT_INSTANTIATE_GROUP_x and get explicit instantiation DEFINITIONS; spt_hip.hip, which
 // only launches them, gets explicit instantiation DECLARATIONS so that it compiles none of them).  One monolithic
 // .hip took ~4 minutes per library build; split this way the groups compile side by side.
+// (inst_deform.hip is a unit of the same kind without templates: spt_scene_deform's kernels, declared in deform_kernels.h.)
 #pragma once
 #include "kernels.h"
 

@@ -11,6 +11,7 @@
 
 #include "../../../include/spt_detmath.h"   // spt_ss_cdf_entry
 #include "../../../include/spt_pndf.h"      // SPT_PNDF_STACK
+#include "scene_refit.h"
 
 namespace scene_build {
 
@@ -74,9 +75,8 @@ uint32_t bvh_depth(const spt_bvh_node* nodes, uint32_t n_nodes, uint32_t root, u
 // 2.6 to 3.5 ms (measured).  The slab test only fails for a ray that the triangle test accepts when the
 // hit lies within the rounding error of a box EDGE (two slabs barely overlapping), so this small pad
 // already makes a wrongly culled hit a ~1e-8-per-ray event.
-inline float box_pad(float lo, float hi) {
-    return (hi - lo) * 1.52587890625e-5f /* 2^-16 */ + std::max(std::fabs(lo), std::fabs(hi)) * 9.5367431640625e-7f /* 2^-20 */ + 1e-30f;
-}
+// (the arithmetic lives in scene_refit.h: the refit kernels of spt_scene_deform pad with the same function)
+inline float box_pad(float lo, float hi) { return refit_pad(lo, hi); }
 struct SahTri {
     float lo[3], hi[3], c[3];
     uint32_t id;
@@ -84,11 +84,11 @@ struct SahTri {
 void build_sah(std::vector<SahTri>& t, uint32_t tri_first, uint32_t max_leaf, float traversal_cost, bool debug, std::vector<spt_bvh_node>& nodes,
                std::vector<uint32_t>& order, const char* what);
 
-void build_sah_blas(const spt_tri_pos* tris, uint32_t tri_first, uint32_t tri_count, const BuildOptions& opt, std::vector<spt_bvh_node>& nodes,
-                    std::vector<uint32_t>& order /* slot (absolute) -> ABI triangle index, filled for this mesh's range */) {
+void build_sah_blas(const spt_tri_pos* mesh_tris /* the mesh's own records */, uint32_t tri_first, uint32_t tri_count, const BuildOptions& opt,
+                    std::vector<spt_bvh_node>& nodes, std::vector<uint32_t>& order /* slot (absolute) -> ABI triangle index, filled for this mesh's range */) {
     std::vector<SahTri> t(tri_count);
     for (uint32_t i = 0; i < tri_count; ++i) {
-        const spt_tri_pos& p = tris[tri_first + i];
+        const spt_tri_pos& p = mesh_tris[i];
         for (int k = 0; k < 3; ++k) {
             t[i].lo[k] = std::min(p.p0[k], std::min(p.p1[k], p.p2[k]));
             t[i].hi[k] = std::max(p.p0[k], std::max(p.p1[k], p.p2[k]));
@@ -328,9 +328,12 @@ uint32_t build_wide(const spt_bvh_node* nodes, uint32_t root, std::vector<float4
 // `stack_need` receives the worst-case number of simultaneously pending entries of a near-first walk: a
 // node with n children leaves n - 1 of them pending while the first is descended, in whatever order.
 // `base`: the node index of out[0] (spt_scene_update builds the streaming walker's TLAS into an array of its own that sits behind
-// the BLAS nodes on the device).
-uint32_t build_n4(const spt_bvh_node* nodes, uint32_t root, std::vector<float4>& out, uint32_t* stack_need, const char* what, uint32_t base = 0u) {
+// the BLAS nodes on the device).  `height`: receives the height of the root node (0: all its children are leaves, also for a
+// root that is a leaf ref) - the number of levels above the lowest that a bottom-up refit of the tree takes.
+uint32_t build_n4(const spt_bvh_node* nodes, uint32_t root, std::vector<float4>& out, uint32_t* stack_need, const char* what, uint32_t base = 0u,
+                  uint32_t* height = nullptr) {
     *stack_need = 0;
+    if (height) *height = 0;
     auto leaf_ref = [&](const spt_bvh_node& nd) -> uint32_t {
         uint32_t cnt = nd.b & ~SPT_LEAF_FLAG;
         if (cnt > 15u) fail(SPT_ERR_UNSUPPORTED, std::string(what) + ": BVH leaf with more than 15 items");
@@ -419,7 +422,7 @@ uint32_t build_n4(const spt_bvh_node* nodes, uint32_t root, std::vector<float4>&
     }
     // children are allocated after their parent, so one reverse sweep sees every child before its parent
     const uint32_t end_n4 = base + (uint32_t)(out.size() / 4);
-    std::vector<uint32_t> need(end_n4 - root_n4, 0u);
+    std::vector<uint32_t> need(end_n4 - root_n4, 0u), hgt(height ? end_n4 - root_n4 : 0u, 0u);
     for (uint32_t i = end_n4; i-- > root_n4;) {
         const float4* f = &out[(size_t)(i - base) * 4];
         uint32_t hdr, refs[4];
@@ -431,10 +434,14 @@ uint32_t build_n4(const spt_bvh_node* nodes, uint32_t root, std::vector<float4>&
         const uint32_t n = hdr >> 24;
         uint32_t deepest = 0;
         for (uint32_t c = 0; c < n; ++c)
-            if (!(refs[c] & kLeaf)) deepest = std::max(deepest, need[refs[c] - root_n4]);
+            if (!(refs[c] & kLeaf)) {
+                deepest = std::max(deepest, need[refs[c] - root_n4]);
+                if (height) hgt[i - root_n4] = std::max(hgt[i - root_n4], hgt[refs[c] - root_n4] + 1u);
+            }
         need[i - root_n4] = n - 1 + deepest;
     }
     *stack_need = need[0];
+    if (height) *height = hgt[0];
     return root_n4;
 }
 
@@ -1017,10 +1024,12 @@ void fixed_of_desc(const spt_scene_desc& s, const BuildOptions& opt, SceneFixed&
     fx.own_bvh = !opt.reference_bvh;   // see build_sah_blas
     fx.spheres.assign(s.spheres, s.spheres + s.n_spheres);
     fx.mesh_tris.resize(s.n_meshes);
+    fx.mesh_first.resize(s.n_meshes);
     fx.mesh_box.resize(s.n_meshes);
     for (uint32_t i = 0; i < s.n_meshes; ++i) {   // (the per-row spans' object-space boxes: an update reads no triangle)
         const spt_mesh& m = s.meshes[i];
         fx.mesh_tris[i] = m.tri_count;
+        fx.mesh_first[i] = m.tri_first;
         double olo[3] = {1e300, 1e300, 1e300}, ohi[3] = {-1e300, -1e300, -1e300};
         for (uint32_t t = m.tri_first; t < m.tri_first + m.tri_count; ++t) {
             const float* v[3] = {s.tri_pos[t].p0, s.tri_pos[t].p1, s.tri_pos[t].p2};
@@ -1051,26 +1060,52 @@ void blas_source(const spt_scene_desc& s, const BuildOptions& opt, SceneFixed& f
     src.roots.assign(s.n_meshes, 0u);
     src.tri_order.resize(s.n_tris);
     for (uint32_t i = 0; i < s.n_tris; ++i) src.tri_order[i] = i;
+    fx.mesh_depth.assign(s.n_meshes, 0u);
     for (uint32_t i = 0; i < s.n_meshes; ++i) {
         if (!fx.own_bvh) { src.roots[i] = s.meshes[i].root; continue; }
         src.roots[i] = (uint32_t)src.own_nodes.size();
-        build_sah_blas(s.tri_pos, s.meshes[i].tri_first, s.meshes[i].tri_count, opt, src.own_nodes, src.tri_order);
-        fx.own_blas_depth = std::max(fx.own_blas_depth, bvh_depth(src.own_nodes.data(), (uint32_t)src.own_nodes.size(), src.roots[i], s.n_tris, "device blas"));
+        build_sah_blas(s.tri_pos + s.meshes[i].tri_first, s.meshes[i].tri_first, s.meshes[i].tri_count, opt, src.own_nodes, src.tri_order);
+        fx.mesh_depth[i] = bvh_depth(src.own_nodes.data(), (uint32_t)src.own_nodes.size(), src.roots[i], s.n_tris, "device blas");
+        fx.own_blas_depth = std::max(fx.own_blas_depth, fx.mesh_depth[i]);
     }
     src.nodes = fx.own_bvh ? src.own_nodes.data() : s.blas_nodes;
 }
 
 // triangles in leaf order of the tree that is walked, ABI index in the first vertex's pad lane
+spt_tri_pos leaf_order_record(const spt_tri_pos& src, uint32_t abi_index) {
+    spt_tri_pos dst = src;
+    for (int k = 0; k < 3; ++k) { dst.p1[k] = src.p1[k] - src.p0[k]; dst.p2[k] = src.p2[k] - src.p0[k]; }   // e1, e2 of triangle.rs:125-126
+    std::memcpy(&dst.pad0, &abi_index, 4);
+    return dst;
+}
+
 std::vector<spt_tri_pos> leaf_order_triangles(const spt_scene_desc& s, const std::vector<uint32_t>& tri_order) {
     std::vector<spt_tri_pos> tri_blob(s.n_tris);
-    for (uint32_t i = 0; i < s.n_tris; ++i) {
-        const spt_tri_pos& src = s.tri_pos[tri_order[i]];
-        spt_tri_pos& dst = tri_blob[i];
-        dst = src;
-        for (int k = 0; k < 3; ++k) { dst.p1[k] = src.p1[k] - src.p0[k]; dst.p2[k] = src.p2[k] - src.p0[k]; }   // e1, e2 of triangle.rs:125-126
-        std::memcpy(&dst.pad0, &tri_order[i], 4);
-    }
+    for (uint32_t i = 0; i < s.n_tris; ++i) tri_blob[i] = leaf_order_record(s.tri_pos[tri_order[i]], tri_order[i]);
     return tri_blob;
+}
+
+// (root.lo, root ref) (root.hi, the mesh's range in the blob's triangle copy when it fits 16 + 16 bits: flat.h)
+void set_mesh_record(SceneFixed& fx, uint32_t mesh, const float* lo, const float* hi, uint32_t root_ref) {
+    const uint32_t first = fx.mesh_first[mesh], count = fx.mesh_tris[mesh];
+    const uint32_t range = (first < 65536u && count < 65536u) ? (first | (count << 16)) : 0u;
+    float rf, range_f;
+    std::memcpy(&rf, &root_ref, 4);
+    std::memcpy(&range_f, &range, 4);
+    fx.mesh_rec[2 * mesh] = make_float4(lo[0], lo[1], lo[2], rf);
+    fx.mesh_rec[2 * mesh + 1] = make_float4(hi[0], hi[1], hi[2], range_f);
+}
+
+// One mesh's nodes of the LDS-resident form, appended to `wblas`, with its range and its record (spt_scene_create per mesh;
+// spt_scene_deform for the meshes it names)
+void build_wide_mesh(const spt_bvh_node* nodes, uint32_t mesh_root, uint32_t mesh, SceneFixed& fx, std::vector<float4>& wblas,
+                     std::vector<std::pair<uint32_t, uint32_t>>& blas_range) {
+    const uint32_t first_node = (uint32_t)(wblas.size() / 4);
+    const uint32_t sup = build_wide(nodes, mesh_root, wblas, 0u, "blas");
+    uint32_t root_ref;
+    std::memcpy(&root_ref, &wblas[(size_t)sup * 4].w, 4);
+    blas_range.emplace_back(first_node, (uint32_t)(wblas.size() / 4));
+    set_mesh_record(fx, mesh, nodes[mesh_root].bmin, nodes[mesh_root].bmax, root_ref);
 }
 
 // The BLAS nodes and the mesh records of one form.  BLAS: 2-wide full-precision nodes when the whole scene fits LDS, compressed
@@ -1080,31 +1115,22 @@ void build_blas(const spt_scene_desc& s, const BlasSource& src, bool n4, StaticB
     std::vector<float4>& wblas = sb.wblas;
     sb.blas_range.clear();
     wblas.clear();
-    fx.mesh_rec.assign((size_t)s.n_meshes * 2, make_float4(0, 0, 0, 0));   // (root.lo, root ref) (root.hi, -)
+    fx.mesh_rec.assign((size_t)s.n_meshes * 2, make_float4(0, 0, 0, 0));
     fx.max_blas_need = 0;
+    fx.n4_nodes.clear();
     for (uint32_t i = 0; i < s.n_meshes; ++i) {
         const uint32_t mesh_root = src.roots[i];
-        const spt_bvh_node& rn = src.nodes[mesh_root];
-        uint32_t root_ref;
         if (n4) {
-            uint32_t need = 0;
-            root_ref = build_n4(src.nodes, mesh_root, wblas, &need, "blas");
-            fx.max_blas_need = std::max(fx.max_blas_need, need);
-        } else {
+            // (first node, nodes, height of the root node: what a refit of the mesh launches its kernels over - spt_scene_deform)
+            uint32_t need = 0, height = 0;
             const uint32_t first_node = (uint32_t)(wblas.size() / 4);
-            const uint32_t sup = build_wide(src.nodes, mesh_root, wblas, 0u, "blas");
-            std::memcpy(&root_ref, &wblas[(size_t)sup * 4].w, 4);
-            sb.blas_range.emplace_back(first_node, (uint32_t)(wblas.size() / 4));
+            const uint32_t root_ref = build_n4(src.nodes, mesh_root, wblas, &need, "blas", 0u, &height);
+            fx.max_blas_need = std::max(fx.max_blas_need, need);
+            fx.n4_nodes.push_back({first_node, (uint32_t)(wblas.size() / 4) - first_node, height});
+            set_mesh_record(fx, i, src.nodes[mesh_root].bmin, src.nodes[mesh_root].bmax, root_ref);
+        } else {
+            build_wide_mesh(src.nodes, mesh_root, i, fx, wblas, sb.blas_range);
         }
-        float rf;
-        std::memcpy(&rf, &root_ref, 4);
-        fx.mesh_rec[2 * i] = make_float4(rn.bmin[0], rn.bmin[1], rn.bmin[2], rf);
-        // (flat.h: the mesh's range in the blob's triangle copy, when it fits 16 + 16 bits)
-        const spt_mesh& mm = s.meshes[i];
-        const uint32_t range = (mm.tri_first < 65536u && mm.tri_count < 65536u) ? (mm.tri_first | (mm.tri_count << 16)) : 0u;
-        float range_f;
-        std::memcpy(&range_f, &range, 4);
-        fx.mesh_rec[2 * i + 1] = make_float4(rn.bmax[0], rn.bmax[1], rn.bmax[2], range_f);
     }
     if (wblas.size() > 0x7fffffffull / 16) fail(SPT_ERR_UNSUPPORTED, "scene geometry larger than 32 GiB");
     fx.blas_f4 = (uint32_t)wblas.size();
@@ -1203,6 +1229,100 @@ StaticBuild build_static(const spt_scene_desc& s, const BuildOptions& opt) {
     }
     if (sb.textured) sb.tex = compile_textures(s);
     return sb;
+}
+
+// ---- spt_scene_deform: the part of the static build that follows one mesh's vertices ---------------------------------------
+namespace {
+
+// the raw bounds of the new positions; the object-space box of the per-row spans goes into fx.mesh_box
+RefitBox deformed_bounds(SceneFixed& fx, const spt_mesh_deform& e) {
+    RefitBox raw = refit_empty();
+    for (uint32_t t = 0; t < e.tri_count; ++t) refit_grow_tri(raw, e.tri_pos[t].p0, e.tri_pos[t].p1, e.tri_pos[t].p2);
+    for (int k = 0; k < 3; ++k) { fx.mesh_box[e.mesh][k] = (double)raw.lo[k]; fx.mesh_box[e.mesh][3 + k] = (double)raw.hi[k]; }
+    return raw;
+}
+
+}  // namespace
+
+void validate_deform(const SceneFixed& fx, uint32_t n_meshes, const spt_mesh_deform* meshes) {
+    if (n_meshes && !meshes) fail(SPT_ERR_INVALID_ARG, "scene_deform: null array");
+    std::vector<uint8_t> named(fx.n_meshes, 0);
+    for (uint32_t i = 0; i < n_meshes; ++i) {
+        const spt_mesh_deform& e = meshes[i];
+        if (e.mesh >= fx.n_meshes) fail(SPT_ERR_INVALID_ARG, "scene_deform: mesh index out of range");
+        if (named[e.mesh]++) fail(SPT_ERR_INVALID_ARG, "scene_deform: a mesh is named twice");
+        // (a creation refuses a mesh without triangles; checked here too: the kernels' grids are sized by the count)
+        if (e.tri_count == 0u || e.tri_count != fx.mesh_tris[e.mesh]) fail(SPT_ERR_INVALID_ARG, "scene_deform: tri_count differs from the mesh's (triangles cannot appear or vanish)");
+        if (!e.tri_pos) fail(SPT_ERR_INVALID_ARG, "scene_deform: null array");
+        for (uint32_t t = 0; t < e.tri_count; ++t)
+            for (int k = 0; k < 3; ++k)
+                if (!std::isfinite(e.tri_pos[t].p0[k]) || !std::isfinite(e.tri_pos[t].p1[k]) || !std::isfinite(e.tri_pos[t].p2[k]))
+                    fail(SPT_ERR_INVALID_ARG, "scene_deform: a position is not finite");
+    }
+    if (n_meshes && !fx.own_bvh)
+        fail(SPT_ERR_UNSUPPORTED, "scene_deform: the scene walks the caller's trees (SPT_REFERENCE_BVH): the library owns none to refit");
+}
+
+std::vector<RefitBox> deform_fixed_n4(SceneFixed& fx, uint32_t n_meshes, const spt_mesh_deform* meshes) {
+    std::vector<RefitBox> roots(n_meshes);
+    for (uint32_t i = 0; i < n_meshes; ++i) {
+        const RefitBox box = refit_padded(deformed_bounds(fx, meshes[i]));
+        // every node's extent is at most the mesh's own (see scene_refit.h): the one refusal the refit kernels could meet
+        for (int k = 0; k < 3; ++k)
+            if (refit_exponent(box.hi[k] - box.lo[k]) > 120) fail(SPT_ERR_UNSUPPORTED, "scene_deform: node extent too large to quantise");
+        uint32_t root_ref;
+        std::memcpy(&root_ref, &fx.mesh_rec[2 * meshes[i].mesh].w, 4);
+        set_mesh_record(fx, meshes[i].mesh, box.lo, box.hi, root_ref);
+        roots[i] = box;
+    }
+    return roots;
+}
+
+void deform_fixed_lds(SceneFixed& fx, std::vector<std::pair<uint32_t, uint32_t>>& blas_range, uint32_t n_meshes, const spt_mesh_deform* meshes,
+                      const BuildOptions& opt) {
+    if (blas_range.size() != fx.n_meshes) fail(SPT_ERR_UNSUPPORTED, "scene_deform: the scene keeps no node range per mesh");
+    std::vector<const spt_mesh_deform*> edit(fx.n_meshes, nullptr);
+    for (uint32_t i = 0; i < n_meshes; ++i) edit[meshes[i].mesh] = &meshes[i];
+    std::vector<float4> wblas;
+    std::vector<std::pair<uint32_t, uint32_t>> ranges;
+    spt_tri_pos* tri_sec = reinterpret_cast<spt_tri_pos*>(fx.tri_sec.data());
+    spt_tri_attr* attr_sec = reinterpret_cast<spt_tri_attr*>(fx.attr_sec.data());
+    for (uint32_t m = 0; m < fx.n_meshes; ++m) {
+        const uint32_t first = fx.mesh_first[m], count = fx.mesh_tris[m];
+        if (!edit[m]) {
+            // the nodes as they are, behind whatever the meshes before them take now: refs to nodes index the whole array
+            const uint32_t old_first = blas_range[m].first, nodes = blas_range[m].second - old_first, new_first = (uint32_t)(wblas.size() / 4);
+            const uint32_t delta = new_first - old_first;
+            auto moved = [delta](float& w) {
+                uint32_t ref;
+                std::memcpy(&ref, &w, 4);
+                if (!(ref & kLeaf)) { ref += delta; std::memcpy(&w, &ref, 4); }
+            };
+            wblas.insert(wblas.end(), fx.wblas.begin() + (size_t)old_first * 4, fx.wblas.begin() + (size_t)blas_range[m].second * 4);
+            for (uint32_t j = 0; j < nodes; ++j) {
+                float4* f = &wblas[((size_t)new_first + j) * 4];
+                moved(f[0].w);
+                if (j != 0u) moved(f[1].w);   // (the super-root has no right child: build_wide)
+            }
+            moved(fx.mesh_rec[2 * m].w);
+            ranges.emplace_back(new_first, new_first + nodes);
+            continue;
+        }
+        const spt_mesh_deform& e = *edit[m];
+        std::vector<spt_bvh_node> nodes;
+        std::vector<uint32_t> order((size_t)first + count, 0u);
+        build_sah_blas(e.tri_pos, first, count, opt, nodes, order);
+        fx.mesh_depth[m] = bvh_depth(nodes.data(), (uint32_t)nodes.size(), 0u, fx.n_tris, "device blas");
+        build_wide_mesh(nodes.data(), 0u, m, fx, wblas, ranges);
+        for (uint32_t slot = first; slot < first + count; ++slot) tri_sec[slot] = leaf_order_record(e.tri_pos[order[slot] - first], order[slot]);
+        if (e.tri_attr) std::memcpy(static_cast<void*>(attr_sec + first), e.tri_attr, (size_t)count * sizeof(spt_tri_attr));
+        deformed_bounds(fx, e);
+    }
+    fx.own_blas_depth = 0;
+    for (uint32_t d : fx.mesh_depth) fx.own_blas_depth = std::max(fx.own_blas_depth, d);
+    fx.wblas = std::move(wblas);
+    fx.blas_f4 = (uint32_t)fx.wblas.size();
+    blas_range = std::move(ranges);
 }
 
 }  // namespace scene_build

@@ -16,6 +16,7 @@
 #include "../../../include/spt_abi.h"
 #include "abi_error.h"
 #include "scene_consts.h"
+#include "scene_refit.h"
 
 namespace scene_build {
 
@@ -52,6 +53,10 @@ struct SceneFixed {
     size_t tables_bytes = 0;          // what the shading tables add behind an LDS-resident blob
     bool simple_fixed = false, fused_fixed = false;   // spt_scene::simple / ::fused but for the lights' types
     std::vector<uint32_t> mesh_tris;                  // triangle count per mesh
+    std::vector<uint32_t> mesh_first;                 // ... and its first triangle (ABI index and leaf-order slot alike)
+    std::vector<uint32_t> mesh_depth;                 // depth of the device-built tree per mesh (own_bvh)
+    // n4, per mesh: its first 4-wide node, its nodes and the height of its root node (spt_scene_deform refits level by level)
+    std::vector<std::array<uint32_t, 3>> n4_nodes;
     std::vector<spt_sphere> spheres;
     std::vector<uint8_t> surf_class, surf_emissive;   // per surface: the shade class of its material, luminance of its emission > 0
     std::vector<std::array<double, 6>> mesh_box;      // object-space bounds of every mesh's vertices (lo, hi)
@@ -134,5 +139,15 @@ StaticBuild build_static(const spt_scene_desc& s, const BuildOptions& opt);
 // the static sections, with which the whole blob is written (a creation; every update of the LDS-resident form); nullptr: the
 // blob from fx.tail_first on (an update of the large-scene form, which keeps no copy of its static sections).
 SceneDynamic build_dynamic(const SceneFixed& fx, const DynView& s, const BuildOptions& opt, bool lds_geo, size_t n_blas_ranges, const StaticSections* st);
+
+// spt_scene_deform.  The checks of the named meshes against the scene (every refusal that needs no build).
+void validate_deform(const SceneFixed& fx, uint32_t n_meshes, const spt_mesh_deform* meshes);
+// Large-scene form: what the host keeps of a named mesh - its object-space box and its record with pad(bounds of the whole
+// mesh), which contains every box the refit kernels make (scene_refit.h).  Returns that box per named mesh.
+std::vector<RefitBox> deform_fixed_n4(SceneFixed& fx, uint32_t n_meshes, const spt_mesh_deform* meshes);
+// LDS-resident form: the named meshes' static sections built again with the creation's functions (binned-SAH tree, wide nodes,
+// leaf-order triangles, attributes, record, box, depth), the other meshes' nodes moved to where they now start.
+void deform_fixed_lds(SceneFixed& fx, std::vector<std::pair<uint32_t, uint32_t>>& blas_range, uint32_t n_meshes, const spt_mesh_deform* meshes,
+                      const BuildOptions& opt);
 
 }  // namespace scene_build

@@ -23,6 +23,7 @@
 #include "kernel_list.h"   // the heavy kernel templates: declared here, compiled in inst_*.hip
 #include "film_kernels.h"
 #include "radiance_kernels.h"
+#include "deform_kernels.h"   // spt_scene_deform's kernels: declared here, compiled in inst_deform.hip
 #include "abi_error.h"     // AbiError, fail
 #include "scene_build.h"   // everything a scene derives from its descriptor on the host
 
@@ -136,6 +137,7 @@ struct BezierLib {
     decltype(&spt_trace_any) trace_any = nullptr;
     decltype(&spt_radiance) radiance = nullptr;
     decltype(&spt_scene_update) scene_update = nullptr;   // (resolved if present, like film_filter)
+    decltype(&spt_scene_deform) scene_deform = nullptr;   // (the same)
     decltype(&spt_debug_bxdf) debug_bxdf = nullptr;
     decltype(&spt_debug_render_info) debug_render_info = nullptr;
     decltype(&spt_last_error) last_error = nullptr;
@@ -233,6 +235,12 @@ struct spt_scene {
     hipEvent_t ev_upd = nullptr;
     bool upd_recorded = false;
     uint64_t updates = 0, update_bytes = 0;
+    // spt_scene_deform on a large scene, made by its first call: the refit's raw bounds and height per BLAS node, and per mesh
+    // whether its nodes' heights have been derived (k_refit_heights)
+    DeviceBuffer refit_raw, refit_height;
+    std::vector<uint8_t> refit_heights_known;
+    hipEvent_t ev_deform[2] = {nullptr, nullptr};   // around the copies and kernels of the last call that named meshes (counter 6)
+    bool deform_timed = false;
     ~spt_scene() {
         if (fwd) { fwd->destroy(inner); return; }
         (void)hipSetDevice(device);
@@ -241,7 +249,7 @@ struct spt_scene {
         if (ev_join) (void)hipEventDestroy(ev_join);
         if (ev_out_ready) (void)hipEventDestroy(ev_out_ready);
         if (ev_copy_done) (void)hipEventDestroy(ev_copy_done);
-        for (auto e : {ev_main[0], ev_main[1], ev_film[0], ev_film[1], ev_film_idle, ev_keep[0], ev_keep[1], ev_ray[0], ev_ray[1], ev_upd})
+        for (auto e : {ev_main[0], ev_main[1], ev_film[0], ev_film[1], ev_film_idle, ev_keep[0], ev_keep[1], ev_ray[0], ev_ray[1], ev_upd, ev_deform[0], ev_deform[1]})
             if (e) (void)hipEventDestroy(e);
         if (stream_film) (void)hipStreamDestroy(stream_film);
         if (stream2) (void)hipStreamDestroy(stream2);
@@ -387,6 +395,7 @@ const BezierLib* bezier_lib() {
                          sym(lib.last_error, "spt_last_error") && sym(version, "spt_abi_version");
         (void)sym(lib.film_filter, "spt_film_filter");
         (void)sym(lib.scene_update, "spt_scene_update");
+        (void)sym(lib.scene_deform, "spt_scene_deform");
         if (!all || version() != SPT_ABI_VERSION) {
             err = path + " does not export ABI version " + std::to_string(SPT_ABI_VERSION);
             return;
@@ -1644,46 +1653,50 @@ float* direct_destination(const spt_render_params& p, uint32_t own_rows, uint32_
     return (float*)d_first;
 }
 
-}  // namespace
-
-extern "C" {
-
-// spt_scene_update: everything of the scene that depends on its instances and lights is built again on the host from the new
-// arrays (build_dynamic of scene_build.h, the function spt_scene_create runs), then committed: the device copies through one page-locked
-// slot, by copies queued on the render stream behind the kernels of the frames queued so far, the host side last.  Nothing of the
-// scene is touched before the first copy is queued, so a refused update leaves it as it was.
-spt_status spt_scene_update(spt_scene* sc, const spt_scene_update_desc* u) {
-    if (!sc || !u) { g_error = "scene_update: null argument"; return SPT_ERR_INVALID_ARG; }
-    if (u->size < sizeof(spt_scene_update_desc)) { g_error = "scene_update: size is smaller than spt_scene_update_desc"; return SPT_ERR_INVALID_ARG; }
-    if (sc->fwd) {
-        if (!sc->fwd->scene_update) { g_error = "scene_update: libspt_hip_bez.so does not export spt_scene_update"; return SPT_ERR_UNSUPPORTED; }
-        return forwarded(sc->fwd, sc->fwd->scene_update(sc->inner, u));
-    }
-    std::lock_guard<std::mutex> lock(sc->mu);
-    return guarded("scene_update", [&] {
+// spt_scene_update and spt_scene_deform under the scene's lock (`who` names the call in the messages; n_meshes == 0: an update).
+// Everything of the scene that depends on its instances and lights is built again on the host from the new arrays (build_dynamic
+// of scene_build.h, the function spt_scene_create runs), then committed: the device copies through one page-locked slot, by copies
+// queued on the render stream behind the kernels of the frames queued so far, the host side last.  A deformation first makes the
+// fixed part of the named meshes again, in a copy (scene_build.h, deform_fixed_*): on a large scene that is a box per mesh, and the
+// call queues the triangles' copies and the refit kernels (deform_kernels.h) in front of the dynamic sections' copies; an
+// LDS-resident scene's blob is written whole as by any update.  Nothing of the scene is touched before the first copy is queued,
+// so a refused call leaves it as it was.
+spt_status update_locked(spt_scene* sc, const spt_scene_update_desc* u, uint32_t n_meshes, const spt_mesh_deform* meshes, const char* who) {
+    const std::string w(who);
+    return guarded(who, [&] {
         const BuildOptions opt = build_options();
-        const SceneFixed& fx = sc->fixed;
-        if (u->flags != 0u) fail(SPT_ERR_INVALID_ARG, "scene_update: unknown flags");
-        if (sc->live_films != 0u) fail(SPT_ERR_INVALID_ARG, "scene_update: destroy the scene's films first (a film accumulates samples of one scene)");
-        if (u->n_instances != fx.n_instances) fail(SPT_ERR_INVALID_ARG, "scene_update: n_instances differs from the scene's (objects cannot appear or vanish)");
-        if (u->n_lights != fx.n_lights) fail(SPT_ERR_INVALID_ARG, "scene_update: n_lights differs from the scene's");
-        if ((u->n_tlas_nodes && !u->tlas_nodes) || (u->n_instances && !u->instances) || (u->n_lights && !u->lights)) fail(SPT_ERR_INVALID_ARG, "scene_update: null array");
-        if (u->n_instances && fx.aggregate == SPT_AGGREGATE_BVH && u->n_tlas_nodes == 0) fail(SPT_ERR_INVALID_ARG, "scene_update: bvh aggregate without TLAS nodes");
+        if (u->flags != 0u) fail(SPT_ERR_INVALID_ARG, w + ": unknown flags");
+        if (sc->live_films != 0u) fail(SPT_ERR_INVALID_ARG, w + ": destroy the scene's films first (a film accumulates samples of one scene)");
+        if (u->n_instances != sc->fixed.n_instances) fail(SPT_ERR_INVALID_ARG, w + ": n_instances differs from the scene's (objects cannot appear or vanish)");
+        if (u->n_lights != sc->fixed.n_lights) fail(SPT_ERR_INVALID_ARG, w + ": n_lights differs from the scene's");
+        if ((u->n_tlas_nodes && !u->tlas_nodes) || (u->n_instances && !u->instances) || (u->n_lights && !u->lights)) fail(SPT_ERR_INVALID_ARG, w + ": null array");
+        if (u->n_instances && sc->fixed.aggregate == SPT_AGGREGATE_BVH && u->n_tlas_nodes == 0) fail(SPT_ERR_INVALID_ARG, w + ": bvh aggregate without TLAS nodes");
+        validate_deform(sc->fixed, n_meshes, meshes);
+        // a deformation: the fixed part with the named meshes made again, committed with the rest
+        SceneFixed deformed;
+        std::vector<std::pair<uint32_t, uint32_t>> blas_range = sc->blas_range;
+        std::vector<RefitBox> root_box;
+        if (n_meshes) {
+            deformed = sc->fixed;
+            if (deformed.n4) root_box = deform_fixed_n4(deformed, n_meshes, meshes);
+            else deform_fixed_lds(deformed, blas_range, n_meshes, meshes, opt);
+        }
+        const SceneFixed& fx = n_meshes ? deformed : sc->fixed;
         const DynView view{fx.aggregate, fx.light_sampler, u->n_tlas_nodes, u->n_instances, u->n_lights, fx.n_spheres, fx.n_meshes, fx.n_bezier_patches, fx.n_surfaces,
                            fx.has_env, u->tlas_nodes, u->instances, u->lights, u->light_alias, fx.surf_emissive.data()};
-        validate_instances(view, opt, "scene_update");
-        validate_lights(view, "scene_update");
+        validate_instances(view, opt, who);
+        validate_lights(view, who);
         if (fx.env_light_index >= 0 && u->lights[fx.env_light_index].type != fx.env_light_type)
-            fail(SPT_ERR_INVALID_ARG, "scene_update: the light at env_light_index may not change its type");
-        validate_light_alias(view, "scene_update");
+            fail(SPT_ERR_INVALID_ARG, w + ": the light at env_light_index may not change its type");
+        validate_light_alias(view, who);
         // the new state, on the host (nothing of it is committed before the refusals below)
         const StaticSections st{fx.wblas.data(), fx.tri_sec.data()};
-        SceneDynamic dy = build_dynamic(fx, view, opt, sc->lds_geo, sc->blas_range.size(), fx.n4 ? nullptr : &st);
+        SceneDynamic dy = build_dynamic(fx, view, opt, sc->lds_geo, blas_range.size(), fx.n4 ? nullptr : &st);
         if (sc->lds_geo && !lds_fits(dy.plain_f4))
-            fail(SPT_ERR_UNSUPPORTED, "scene_update: the traversal geometry would no longer fit LDS, where the scene's BLAS nodes are laid out for: recreate the scene");
+            fail(SPT_ERR_UNSUPPORTED, w + ": the traversal geometry would no longer fit LDS, where the scene's BLAS nodes are laid out for: recreate the scene");
         if (fx.n4 && (size_t)dy.geo_f4 - fx.tail_first > fx.tail_cap)
-            fail(SPT_ERR_UNSUPPORTED, "scene_update: the caller's TLAS needs more room than the scene reserved: recreate the scene");
-        // the slot: [instances | classes | lights | alias props, u, k | blob]
+            fail(SPT_ERR_UNSUPPORTED, w + ": the caller's TLAS needs more room than the scene reserved: recreate the scene");
+        // the slot: [triangles and attributes of the named meshes | instances | classes | lights | alias props, u, k | blob]
         const bool pis = fx.light_sampler == SPT_LIGHT_SAMPLER_POWER_IS && fx.n_lights != 0;
         struct Part { void* dst; const void* src; size_t bytes, at; };
         std::vector<Part> parts;
@@ -1693,6 +1706,12 @@ spt_status spt_scene_update(spt_scene* sc, const spt_scene_update_desc* u) {
             parts.push_back(Part{dst, src, bytes, total});
             total += (bytes + 15) / 16 * 16;
         };
+        for (uint32_t i = 0; i < n_meshes; ++i) {   // the ABI-order arrays the shade kernels (and the refit kernels) read
+            const spt_mesh_deform& e = meshes[i];
+            part(sc->tri_pos.as<spt_tri_pos>() + fx.mesh_first[e.mesh], e.tri_pos, (size_t)e.tri_count * sizeof(spt_tri_pos));
+            if (e.tri_attr) part(sc->tri_attr.as<spt_tri_attr>() + fx.mesh_first[e.mesh], e.tri_attr, (size_t)e.tri_count * sizeof(spt_tri_attr));
+        }
+        const size_t geometry_parts = parts.size();
         part(sc->instances.p, u->instances, (size_t)fx.n_instances * sizeof(spt_instance));
         part(sc->inst_class.p, dy.cls.data(), fx.n_instances);
         part(sc->lights.p, u->lights, (size_t)fx.n_lights * sizeof(spt_light));
@@ -1702,12 +1721,22 @@ spt_status spt_scene_update(spt_scene* sc, const spt_scene_update_desc* u) {
             part(sc->light_k.p, u->light_alias.k, (size_t)fx.n_lights * sizeof(uint32_t));
         }
         part(sc->geo.as<float4>() + (fx.n4 ? fx.tail_first : 0u), dy.blob.data(), dy.blob.size() * 16);
-        if ((fx.n4 ? (size_t)fx.tail_first * 16 : 0) + dy.blob.size() * 16 > sc->geo.bytes) fail(SPT_ERR_UNSUPPORTED, "scene_update: the geometry blob outgrew its allocation: recreate the scene");
+        if ((fx.n4 ? (size_t)fx.tail_first * 16 : 0) + dy.blob.size() * 16 > sc->geo.bytes) fail(SPT_ERR_UNSUPPORTED, w + ": the geometry blob outgrew its allocation: recreate the scene");
         HIP_CHECK(hipSetDevice(sc->device));
         if (!sc->ev_upd) HIP_CHECK(hipEventCreateWithFlags(&sc->ev_upd, hipEventDisableTiming));
         if (sc->upd_recorded) HIP_CHECK(hipEventSynchronize(sc->ev_upd));   // the previous update's copies still read the slot
         sc->upd_recorded = false;
         sc->upd_stage.ensure(std::max<size_t>(total, 16));
+        // the refit's scratch, made by the first deformation of a large scene: raw bounds and a height per BLAS node
+        const bool refit = n_meshes != 0 && fx.n4;
+        const size_t n_nodes = fx.blas_f4 / 4u;
+        if (refit && n_nodes != 0 && !sc->refit_raw.p) {
+            sc->refit_raw.alloc(n_nodes * sizeof(RefitBox));
+            sc->refit_height.alloc(n_nodes);
+            sc->refit_heights_known.assign(fx.n_meshes, 0);
+        }
+        if (n_meshes && !sc->ev_deform[0])
+            for (hipEvent_t& e : sc->ev_deform) HIP_CHECK(hipEventCreate(&e));
         for (const Part& pt : parts) std::memcpy(static_cast<char*>(sc->upd_stage.p) + pt.at, pt.src, pt.bytes);
         // Of what an overlapped render leaves on the film stream only a tail-loop launch reads the scene (the resolves, the finish
         // kernel and the copy-out read the render workspace): the copies go behind that launch, as the next frame's bounce 0 would,
@@ -1716,16 +1745,78 @@ spt_status spt_scene_update(spt_scene* sc, const spt_scene_update_desc* u) {
             HIP_CHECK(hipStreamWaitEvent(sc->stream, sc->ev_film[sc->tail_set], 0));
             sc->tail_set = -1;
         }
-        for (const Part& pt : parts)
+        auto queue_copy = [&](const Part& pt) {
             HIP_CHECK(hipMemcpyAsync(pt.dst, static_cast<const char*>(sc->upd_stage.p) + pt.at, pt.bytes, hipMemcpyHostToDevice, sc->stream));
+        };
+        // the named meshes' triangles, then (large scene) their kernels, then the dynamic sections: the streaming walker's entries
+        // carry the mesh records' new boxes, so a frame sees either all of a deformation or none of it
+        if (n_meshes) HIP_CHECK(hipEventRecord(sc->ev_deform[0], sc->stream));
+        for (size_t k = 0; k < geometry_parts; ++k) queue_copy(parts[k]);
+        for (uint32_t i = 0; refit && i < n_meshes; ++i) {
+            const uint32_t mesh = meshes[i].mesh;
+            DeformMesh dm{};
+            dm.geo = sc->geo.as<float4>();
+            dm.tri_pos = sc->tri_pos.as<float4>();
+            dm.raw = sc->refit_raw.as<RefitBox>();
+            dm.height = sc->refit_height.as<uint8_t>();
+            dm.o_tri = sc->d.o_tri; dm.o_blas = sc->d.o_blas; dm.o_mesh = sc->d.o_mesh;   // (static sections: no update moves them)
+            dm.mesh = mesh;
+            dm.tri_first = fx.mesh_first[mesh]; dm.tri_count = fx.mesh_tris[mesh];
+            dm.node_first = fx.n4_nodes[mesh][0]; dm.node_count = fx.n4_nodes[mesh][1];
+            for (int k = 0; k < 3; ++k) { dm.root_lo[k] = root_box[i].lo[k]; dm.root_hi[k] = root_box[i].hi[k]; }
+            const uint32_t levels = fx.n4_nodes[mesh][2] + 1u;
+            const dim3 tri_grid((dm.tri_count + kBlock - 1u) / kBlock), node_grid((dm.node_count + kBlock - 1u) / kBlock);
+            hipLaunchKernelGGL(k_deform_tris, tri_grid, dim3(kBlock), 0, sc->stream, dm);
+            if (dm.node_count == 0u) continue;   // the root is a leaf: the mesh record's box is all there is
+            if (!sc->refit_heights_known[mesh]) {
+                hipLaunchKernelGGL(k_refit_heights, node_grid, dim3(kBlock), 0, sc->stream, dm, (uint32_t)kRefitUnknown);
+                for (uint32_t level = 1; level < levels; ++level) hipLaunchKernelGGL(k_refit_heights, node_grid, dim3(kBlock), 0, sc->stream, dm, level);
+                sc->refit_heights_known[mesh] = 1;
+            }
+            for (uint32_t level = 0; level < levels; ++level) hipLaunchKernelGGL(k_refit_level, node_grid, dim3(kBlock), 0, sc->stream, dm, level);
+        }
+        if (refit) HIP_CHECK(hipGetLastError());
+        for (size_t k = geometry_parts; k < parts.size(); ++k) queue_copy(parts[k]);
         HIP_CHECK(hipEventRecord(sc->ev_upd, sc->stream));
         sc->upd_recorded = true;
+        if (n_meshes) {
+            HIP_CHECK(hipEventRecord(sc->ev_deform[1], sc->stream));
+            sc->deform_timed = true;
+            sc->fixed = std::move(deformed);
+            sc->blas_range = std::move(blas_range);
+        }
         dyn_commit_host(sc, dy, sc->lds_geo);
         ++sc->updates;
         sc->update_bytes = 0;
         for (const Part& pt : parts) sc->update_bytes += pt.bytes;
         return SPT_OK;
     });
+}
+
+}  // namespace
+
+extern "C" {
+
+spt_status spt_scene_update(spt_scene* sc, const spt_scene_update_desc* u) {
+    if (!sc || !u) { g_error = "scene_update: null argument"; return SPT_ERR_INVALID_ARG; }
+    if (u->size < sizeof(spt_scene_update_desc)) { g_error = "scene_update: size is smaller than spt_scene_update_desc"; return SPT_ERR_INVALID_ARG; }
+    if (sc->fwd) {
+        if (!sc->fwd->scene_update) { g_error = "scene_update: libspt_hip_bez.so does not export spt_scene_update"; return SPT_ERR_UNSUPPORTED; }
+        return forwarded(sc->fwd, sc->fwd->scene_update(sc->inner, u));
+    }
+    std::lock_guard<std::mutex> lock(sc->mu);
+    return update_locked(sc, u, 0u, nullptr, "scene_update");
+}
+
+spt_status spt_scene_deform(spt_scene* sc, const spt_scene_update_desc* u, uint32_t n_meshes, const spt_mesh_deform* meshes) {
+    if (!sc || !u) { g_error = "scene_deform: null argument"; return SPT_ERR_INVALID_ARG; }
+    if (u->size < sizeof(spt_scene_update_desc)) { g_error = "scene_deform: size is smaller than spt_scene_update_desc"; return SPT_ERR_INVALID_ARG; }
+    if (sc->fwd) {
+        if (!sc->fwd->scene_deform) { g_error = "scene_deform: libspt_hip_bez.so does not export spt_scene_deform"; return SPT_ERR_UNSUPPORTED; }
+        return forwarded(sc->fwd, sc->fwd->scene_deform(sc->inner, u, n_meshes, meshes));
+    }
+    std::lock_guard<std::mutex> lock(sc->mu);
+    return update_locked(sc, u, n_meshes, meshes, "scene_deform");
 }
 
 spt_status spt_render(const spt_scene* scene_c, const spt_camera* cam, const spt_render_params* params,
@@ -2934,10 +3025,22 @@ spt_status spt_debug_pack_rgb8(int32_t device, uint32_t n, const float* in, uint
 }
 
 spt_status spt_debug_render_info(const spt_scene* scene_c, uint32_t what, uint64_t* out) {
-    if (!scene_c || !out || what > 5u) { g_error = "debug_render_info: null argument or unknown counter"; return SPT_ERR_INVALID_ARG; }
+    if (!scene_c || !out || what > 6u) { g_error = "debug_render_info: null argument or unknown counter"; return SPT_ERR_INVALID_ARG; }
     spt_scene* sc = const_cast<spt_scene*>(scene_c);
     if (sc->fwd) return forwarded(sc->fwd, sc->fwd->debug_render_info(sc->inner, what, out));
     std::lock_guard<std::mutex> lock(sc->mu);
+    if (what == 6u) {   // waits for the last deformation's copies and kernels
+        return guarded("debug_render_info", [&] {
+            *out = 0;
+            if (!sc->deform_timed) return SPT_OK;
+            HIP_CHECK(hipSetDevice(sc->device));
+            HIP_CHECK(hipEventSynchronize(sc->ev_deform[1]));
+            float ms = 0.0f;
+            HIP_CHECK(hipEventElapsedTime(&ms, sc->ev_deform[0], sc->ev_deform[1]));
+            *out = (uint64_t)((double)ms * 1e6);
+            return SPT_OK;
+        });
+    }
     *out = what == 0u ? sc->passes_film : what == 1u ? sc->passes_single : what == 2u ? sc->keep_read_ns : what == 3u ? sc->frames_direct : what == 4u ? sc->updates : sc->update_bytes;
     return SPT_OK;
 }

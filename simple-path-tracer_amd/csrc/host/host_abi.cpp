@@ -124,6 +124,25 @@ spt_status spt_host_scene_set_light(spt_host_scene* scene, const char* name, con
     return host_guarded("scene_set_light", [&] { scene->hs->set_light(name, *light); });
 }
 
+spt_status spt_host_scene_mesh_index(const spt_host_scene* scene, const char* primitive_name, uint32_t* mesh) {
+    if (!scene || !primitive_name || !mesh) { set_error("scene_mesh_index: null argument"); return SPT_ERR_INVALID_ARG; }
+    return host_guarded("scene_mesh_index", [&] { *mesh = scene->hs->mesh_source(primitive_name).mesh; });
+}
+
+spt_status spt_host_scene_mesh_positions(const spt_host_scene* scene, const char* primitive_name, uint32_t* n_vertices, float* out) {
+    if (!scene || !primitive_name || !n_vertices) { set_error("scene_mesh_positions: null argument"); return SPT_ERR_INVALID_ARG; }
+    return host_guarded("scene_mesh_positions", [&] {
+        const MeshSource& src = scene->hs->mesh_source(primitive_name);
+        *n_vertices = (uint32_t)src.pos.size();
+        for (size_t i = 0; out && i < src.pos.size(); ++i) { out[3 * i] = src.pos[i].x; out[3 * i + 1] = src.pos[i].y; out[3 * i + 2] = src.pos[i].z; }
+    });
+}
+
+spt_status spt_host_scene_set_mesh_positions(spt_host_scene* scene, const char* primitive_name, uint32_t n_vertices, const float* positions, const float* normals) {
+    if (!scene || !primitive_name || !positions) { set_error("scene_set_mesh_positions: null argument"); return SPT_ERR_INVALID_ARG; }
+    return host_guarded("scene_set_mesh_positions", [&] { scene->hs->set_mesh_positions(primitive_name, n_vertices, positions, normals); });
+}
+
 spt_status spt_host_animation_load(const char* path, const spt_host_scene* scene, spt_host_animation** out) {
     if (!path || !scene || !out) { set_error("animation_load: null argument"); return SPT_ERR_INVALID_ARG; }
     *out = nullptr;

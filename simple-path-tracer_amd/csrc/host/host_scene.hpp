@@ -21,6 +21,16 @@ struct HostError {
 struct InstRec { spt_instance inst; Affine trans; std::string name; Box prim_box; };
 InstRec make_instance_rec(const std::string& name, const Affine& trans, uint32_t prim_type, uint32_t prim_id, const Box& prim_box, uint32_t surf);
 
+// A trimesh primitive of a JSON scene as the OBJ loader made it (single-index vertices), with the triangle order its BLAS build
+// chose: what spt_host_scene_set_mesh_positions makes the mesh's records from again
+struct MeshSource {
+    uint32_t mesh = 0;                  // index in HostScene::meshes
+    std::vector<V3> pos, nrm;
+    std::vector<float> uv;              // 2 per vertex
+    std::vector<uint32_t> idx;          // 3 per face
+    std::vector<uint32_t> order;        // triangle k of the mesh's range is face order[k]
+};
+
 struct HostScene {
     std::vector<spt_bvh_node> tlas_nodes, blas_nodes;
     std::vector<spt_instance> instances;
@@ -65,6 +75,13 @@ struct HostScene {
     void finalize_dynamic();
     void set_transforms(const std::vector<std::pair<std::string, Affine>>& moves);   // all or nothing (HostError)
     void set_light(const std::string& name, const spt_light& light);
+    // spt_host_scene_mesh_positions / _set_mesh_positions: the trimesh primitives by name; the names of the meshes that cannot
+    // be edited (glTF primitives, Catmull-Clark surfaces)
+    std::map<std::string, MeshSource> mesh_sources;
+    std::map<std::string, std::string> fixed_meshes;   // name -> why not
+    const MeshSource& mesh_source(const std::string& name) const;   // HostError: unknown name, a mesh that cannot be edited
+    MeshSource& mesh_source(const std::string& name);
+    void set_mesh_positions(const std::string& name, uint32_t n_vertices, const float* positions, const float* normals);   // all or nothing
 };
 
 HostScene* load_scene_file(const std::string& path);

@@ -322,6 +322,20 @@ void calc_tangents(ObjMesh& m) {
         }
 }
 
+// the two records of face `t` of a mesh (TriMesh::new, src/primitive/triangle.rs:42-55)
+void face_records(const ObjMesh& m, uint32_t t, spt_tri_pos& tp, spt_tri_attr& ta) {
+    std::memset(&tp, 0, sizeof tp);
+    std::memset(&ta, 0, sizeof ta);
+    float* pp[3] = {tp.p0, tp.p1, tp.p2};
+    for (int c = 0; c < 3; ++c) {
+        uint32_t vi = m.idx[3 * t + c];
+        pp[c][0] = m.pos[vi].x; pp[c][1] = m.pos[vi].y; pp[c][2] = m.pos[vi].z;
+        ta.n[c][0] = m.nrm[vi].x; ta.n[c][1] = m.nrm[vi].y; ta.n[c][2] = m.nrm[vi].z;
+        ta.t[c][0] = m.tan[vi].x; ta.t[c][1] = m.tan[vi].y; ta.t[c][2] = m.tan[vi].z;
+        ta.b[c][0] = m.bit[vi].x; ta.b[c][1] = m.bit[vi].y; ta.b[c][2] = m.bit[vi].z;
+        ta.uv[c][0] = m.uv[2 * vi]; ta.uv[c][1] = m.uv[2 * vi + 1];
+    }
+}
 
 // ---- glTF 2.0 import helpers (role of the `gltf` crate's import(), reference src/loader/gltf.rs:19-20) ----
 std::vector<uint8_t> base64_decode(const std::string& in, const std::string& what) {
@@ -880,9 +894,13 @@ struct SceneBuilder {
             hs.spheres.push_back(s);
         } else if (ty == "trimesh") {
             ObjMesh m = load_obj(p.get_file_path("obj_file"));
+            MeshSource src;   // (before calc_tangents: a deformation starts from the OBJ loader's vertices again)
+            src.pos = m.pos; src.nrm = m.nrm; src.uv = m.uv; src.idx = m.idx;
             calc_tangents(m);
             rec.type = SPT_PRIM_MESH;
-            rec.id = add_mesh(m, rec.box);
+            rec.id = add_mesh(m, rec.box, &src.order);
+            src.mesh = rec.id;
+            hs.mesh_sources[name] = std::move(src);
         } else if (ty == "cubic_bezier") {
             // CubicBezier::load / ::new (src/primitive/bezier.rs:24-38, 136-148): 4 x 4 control points, the box of the hull
             spt_bezier_patch bp;
@@ -901,6 +919,7 @@ struct SceneBuilder {
             cr.fas_times = p.contains("fas_times") ? (uint32_t)std::max(0, p.get_int("fas_times")) : 4u;
             cr.label = p.name();
             rec.type = kPrimCatmullClark;
+            hs.fixed_meshes[name] = "a Catmull-Clark surface";
             rec.id = (uint32_t)catmulls.size();
             catmulls.push_back(cr);
         } else {
@@ -912,7 +931,7 @@ struct SceneBuilder {
     }
 
     // TriMesh::new (src/primitive/triangle.rs:42-55): triangles -> BLAS(4, 16), leaf order
-    uint32_t add_mesh(const ObjMesh& m, Box& root_box) {
+    uint32_t add_mesh(const ObjMesh& m, Box& root_box, std::vector<uint32_t>* order_out = nullptr) {
         uint32_t ntri = (uint32_t)(m.idx.size() / 3);
         if (ntri == 0) throw HostError(SPT_HOST_ERR_SCHEMA, "trimesh without triangles");
         std::vector<Box> boxes(ntri);
@@ -930,23 +949,13 @@ struct SceneBuilder {
             hs.blas_nodes.push_back(nd);
         }
         for (uint32_t k = 0; k < ntri; ++k) {
-            uint32_t t = bvh.order[k];
             spt_tri_pos tp;
             spt_tri_attr ta;
-            std::memset(&tp, 0, sizeof tp);
-            std::memset(&ta, 0, sizeof ta);
-            float* pp[3] = {tp.p0, tp.p1, tp.p2};
-            for (int c = 0; c < 3; ++c) {
-                uint32_t vi = m.idx[3 * t + c];
-                pp[c][0] = m.pos[vi].x; pp[c][1] = m.pos[vi].y; pp[c][2] = m.pos[vi].z;
-                ta.n[c][0] = m.nrm[vi].x; ta.n[c][1] = m.nrm[vi].y; ta.n[c][2] = m.nrm[vi].z;
-                ta.t[c][0] = m.tan[vi].x; ta.t[c][1] = m.tan[vi].y; ta.t[c][2] = m.tan[vi].z;
-                ta.b[c][0] = m.bit[vi].x; ta.b[c][1] = m.bit[vi].y; ta.b[c][2] = m.bit[vi].z;
-                ta.uv[c][0] = m.uv[2 * vi]; ta.uv[c][1] = m.uv[2 * vi + 1];
-            }
+            face_records(m, bvh.order[k], tp, ta);
             hs.tri_pos.push_back(tp);
             hs.tri_attr.push_back(ta);
         }
+        if (order_out) *order_out = bvh.order;
         const spt_bvh_node& r = hs.blas_nodes[mesh.root];
         root_box.lo = {r.bmin[0], r.bmin[1], r.bmin[2]};
         root_box.hi = {r.bmax[0], r.bmax[1], r.bmax[2]};
@@ -1470,6 +1479,7 @@ struct SceneBuilder {
                     GPrim g;
                     g.rec.type = SPT_PRIM_MESH;
                     g.rec.id = add_mesh(m, g.rec.box);
+                    hs.fixed_meshes[prim_name] = "a glTF primitive";
                     g.material = index_of(prim, "material");
                     prims_of.push_back(g);
                     ++pi;
@@ -1780,6 +1790,105 @@ void HostScene::set_light(const std::string& name, const spt_light& light) {
     it->second = light;
     it->second.power = luminance({light.strength[0], light.strength[1], light.strength[2]});   // as load_light sets it
     finalize_dynamic();
+}
+
+const MeshSource& HostScene::mesh_source(const std::string& name) const {
+    auto it = mesh_sources.find(name);
+    if (it != mesh_sources.end()) return it->second;
+    auto fm = fixed_meshes.find(name);
+    if (fm != fixed_meshes.end()) throw HostError(SPT_HOST_ERR_UNSUPPORTED, "primitive '" + name + "' is " + fm->second + ": only trimesh primitives of a JSON scene can be deformed");
+    throw HostError(SPT_HOST_ERR_SCHEMA, "There is no trimesh primitive named '" + name + "'");
+}
+
+MeshSource& HostScene::mesh_source(const std::string& name) {
+    auto it = mesh_sources.find(name);
+    if (it != mesh_sources.end()) return it->second;
+    static_cast<const HostScene*>(this)->mesh_source(name);   // throws: the refusals are the const overload's
+    throw HostError(SPT_HOST_ERR_SCHEMA, "There is no trimesh primitive named '" + name + "'");
+}
+
+// spt_host_scene_set_mesh_positions: the mesh's records made again from the new vertices as the loader makes them (tangents,
+// then the two records per face in the triangle order its BLAS build chose), the boxes of its BLAS refitted over the same
+// topology, every instance of it made again under its transform, then the loader's own finalisation.  Everything is made
+// before anything is replaced.
+void HostScene::set_mesh_positions(const std::string& name, uint32_t n_vertices, const float* positions, const float* normals) {
+    MeshSource& src = mesh_source(name);
+    if (n_vertices != src.pos.size()) throw HostError(SPT_ERR_INVALID_ARG, "primitive '" + name + "': " + std::to_string(src.pos.size()) + " vertices are expected");
+    for (size_t i = 0; i < (size_t)n_vertices * 3; ++i)
+        if (!std::isfinite(positions[i]) || (normals && !std::isfinite(normals[i]))) throw HostError(SPT_ERR_INVALID_ARG, "primitive '" + name + "': a value is not finite");
+    ObjMesh m;
+    m.pos.resize(n_vertices);
+    m.nrm = src.nrm;
+    for (uint32_t i = 0; i < n_vertices; ++i) {
+        m.pos[i] = {positions[3 * i], positions[3 * i + 1], positions[3 * i + 2]};
+        if (normals) m.nrm[i] = {normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]};
+    }
+    m.uv = src.uv;
+    m.idx = src.idx;
+    m.tan.assign(n_vertices, V3{1, 0, 0});   // MeshVertex::default, as load_obj leaves them for calc_tangents
+    m.bit.assign(n_vertices, V3{0, 1, 0});
+    calc_tangents(m);
+    const spt_mesh mesh = meshes[src.mesh];
+    std::vector<spt_tri_pos> new_pos(mesh.tri_count);
+    std::vector<spt_tri_attr> new_attr(mesh.tri_count);
+    for (uint32_t k = 0; k < mesh.tri_count; ++k) face_records(m, src.order[k], new_pos[k], new_attr[k]);
+    // the caller-side BLAS: children sit behind their parent (BvhBuilder), so one reverse sweep sees them first
+    std::vector<spt_bvh_node> new_nodes(blas_nodes.begin() + mesh.root, blas_nodes.begin() + mesh.root + mesh.node_count);
+    for (uint32_t j = mesh.node_count; j-- > 0;) {
+        spt_bvh_node& nd = new_nodes[j];
+        Box b;
+        if (nd.b & SPT_LEAF_FLAG) {
+            const uint32_t cnt = nd.b & ~SPT_LEAF_FLAG;
+            for (uint32_t t = nd.a - mesh.tri_first; t < nd.a - mesh.tri_first + cnt; ++t) {
+                b.grow({new_pos[t].p0[0], new_pos[t].p0[1], new_pos[t].p0[2]});
+                b.grow({new_pos[t].p1[0], new_pos[t].p1[1], new_pos[t].p1[2]});
+                b.grow({new_pos[t].p2[0], new_pos[t].p2[1], new_pos[t].p2[2]});
+            }
+        } else {
+            if (nd.a - mesh.root <= j || nd.b - mesh.root <= j) throw HostError(SPT_HOST_ERR_UNSUPPORTED, "primitive '" + name + "': its BLAS is not in parent-first order");
+            for (uint32_t c : {nd.a - mesh.root, nd.b - mesh.root}) {
+                b.grow({new_nodes[c].bmin[0], new_nodes[c].bmin[1], new_nodes[c].bmin[2]});
+                b.grow({new_nodes[c].bmax[0], new_nodes[c].bmax[1], new_nodes[c].bmax[2]});
+            }
+        }
+        nd.bmin[0] = b.lo.x; nd.bmin[1] = b.lo.y; nd.bmin[2] = b.lo.z;
+        nd.bmax[0] = b.hi.x; nd.bmax[1] = b.hi.y; nd.bmax[2] = b.hi.z;
+    }
+    Box root_box;
+    root_box.lo = {new_nodes[0].bmin[0], new_nodes[0].bmin[1], new_nodes[0].bmin[2]};
+    root_box.hi = {new_nodes[0].bmax[0], new_nodes[0].bmax[1], new_nodes[0].bmax[2]};
+    std::vector<std::pair<InstRec*, InstRec>> made;
+    for (auto& kv : inst_recs) {
+        const InstRec& old = kv.second;
+        if (old.inst.prim_type != SPT_PRIM_MESH || old.inst.prim_id != src.mesh) continue;
+        InstRec rec = make_instance_rec(old.name, old.trans, old.inst.prim_type, old.inst.prim_id, root_box, old.inst.surface);
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(rec.inst.bmin[k]) || !std::isfinite(rec.inst.bmax[k]) || std::fabs(rec.inst.bmin[k]) >= 3.0e38f || std::fabs(rec.inst.bmax[k]) >= 3.0e38f)
+                throw HostError(SPT_ERR_INVALID_ARG, "primitive '" + name + "': the box of instance '" + old.name + "' is not finite");
+        made.emplace_back(&kv.second, std::move(rec));
+    }
+    // commit; what finalize_dynamic could still refuse (a shape light's area) puts everything back
+    std::vector<spt_tri_pos> old_pos(tri_pos.begin() + mesh.tri_first, tri_pos.begin() + mesh.tri_first + mesh.tri_count);
+    std::vector<spt_tri_attr> old_attr(tri_attr.begin() + mesh.tri_first, tri_attr.begin() + mesh.tri_first + mesh.tri_count);
+    std::vector<spt_bvh_node> old_nodes(blas_nodes.begin() + mesh.root, blas_nodes.begin() + mesh.root + mesh.node_count);
+    std::vector<InstRec> saved;
+    auto put = [&](const std::vector<spt_tri_pos>& p, const std::vector<spt_tri_attr>& a, const std::vector<spt_bvh_node>& n) {
+        std::copy(p.begin(), p.end(), tri_pos.begin() + mesh.tri_first);
+        std::copy(a.begin(), a.end(), tri_attr.begin() + mesh.tri_first);
+        std::copy(n.begin(), n.end(), blas_nodes.begin() + mesh.root);
+    };
+    put(new_pos, new_attr, new_nodes);
+    for (auto& mk : made) { saved.push_back(*mk.first); *mk.first = std::move(mk.second); }
+    try {
+        finalize_dynamic();
+    } catch (...) {
+        put(old_pos, old_attr, old_nodes);
+        for (size_t i = 0; i < made.size(); ++i) *made[i].first = saved[i];
+        finalize_dynamic();
+        throw;
+    }
+    src.pos = std::move(m.pos);
+    src.nrm = std::move(m.nrm);
 }
 
 // `spt --animate FILE`: {"frames": [ {"<instance name>": {matrix / scale / rotate / translate as in the scene file}, ...}, ... ]}

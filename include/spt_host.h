@@ -108,6 +108,15 @@ spt_status spt_host_write_jpeg(const char* path, const uint8_t* rgb8, uint32_t w
 /* `image.save(path)` (src/renderer/pt.rs:292-294): the extension picks the format - png, jpg / jpeg */
 spt_status spt_host_write_image(const char* path, const uint8_t* rgb8, uint32_t width, uint32_t height);
 
+/* The conservative block-versus-triangle test of include/spt_block_cand.h on the host, for checking it without a device.  A block
+ * is the 16 columns x 4 local rows one wave of the primary kernel owns in the shard (shard_index, shard_count, strip_rows; `rows`
+ * local rows): block = 4 * (tile_x + tiles_x * tile_y) + wave.  `inv` / `fwd` are the instance's spt_instance matrices, tri_pos
+ * 9 floats (p0, p1, p2, object space) per triangle, at most 64.  Bit k of *mask_out is set unless no camera ray of the block's
+ * pixels can hit triangle k. */
+spt_status spt_host_block_candidates(const spt_camera* cam, uint32_t width, uint32_t height, uint32_t shard_index, uint32_t shard_count,
+                                     uint32_t strip_rows, uint32_t rows, uint32_t block, const float* inv, const float* fwd, uint32_t n_tris,
+                                     const float* tri_pos, uint64_t* mask_out);
+
 /* OpenEXR scanline I/O (RGB f32 / f16; reads NO_COMPRESSION / RLE / ZIPS / ZIP / PIZ / PXR24, writes uncompressed) for
  * `environment {type: "exr"}` (get_exr_image, src/core/loader.rs:374-390). */
 spt_status spt_host_read_exr(const char* path, uint32_t* width, uint32_t* height, float** rgb_out);

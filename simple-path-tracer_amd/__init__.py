@@ -341,6 +341,9 @@ def host_lib() -> C.CDLL:
             lib.spt_host_scene_mesh_positions.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint32), C.c_void_p]
             lib.spt_host_scene_set_mesh_positions.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_void_p, C.c_void_p]
             lib.spt_host_scene_mesh_index.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint32)]
+        if hasattr(lib, "spt_host_block_candidates"):   # (the same)
+            lib.spt_host_block_candidates.argtypes = [C.POINTER(Camera)] + [C.c_uint32] * 7 + [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                                                                             C.POINTER(C.c_uint64)]
         lib.spt_host_load_renderer.argtypes = [C.c_char_p, C.POINTER(RenderParams), C.POINTER(C.c_float)]
         if hasattr(lib, "spt_host_load_renderer_filter"):   # (a library built before the weighted filters lacks it)
             lib.spt_host_load_renderer_filter.argtypes = [C.c_char_p, C.POINTER(RenderParams), C.POINTER(FilterDesc)]
@@ -1383,6 +1386,21 @@ class MultiDevice:
             self.close()
         except Exception:
             pass
+
+
+def block_candidates(camera: Camera, width: int, height: int, block: int, inv, fwd, tri_pos, shard_index: int = 0, shard_count: int = 1,
+                     strip_rows: int = 16, rows: Optional[int] = None) -> int:
+    """The candidate mask of one block (16 columns x 4 local rows: block = 4 * tile + wave) of a shard, by the test the primary
+    kernel's masks are made with (include/spt_block_cand.h), on the host.  inv / fwd: 12 floats each (spt_instance); tri_pos: (n, 9)
+    object-space vertices, n <= 64.  Bit k is set unless no camera ray of the block can hit triangle k."""
+    inv, fwd = (np.ascontiguousarray(m, dtype=np.float32).reshape(12) for m in (inv, fwd))
+    tri = np.ascontiguousarray(tri_pos, dtype=np.float32).reshape(-1, 9)
+    if rows is None:
+        rows = len(shard_rows(height, shard_index, shard_count, strip_rows))
+    mask = C.c_uint64(0)
+    _check_host(host_lib().spt_host_block_candidates(C.byref(camera), width, height, shard_index, shard_count, strip_rows, rows, block,
+                                                     inv.ctypes.data, fwd.ctypes.data, len(tri), tri.ctypes.data, C.byref(mask)))
+    return int(mask.value)
 
 
 def make_camera(eye, forward, up, fov_degrees: float) -> Camera:

@@ -151,3 +151,37 @@ SPT_DEV DHit eye_trace_closest(const DScene& sc, f3 dw, float t_min, float t_max
     }
     return h;
 }
+
+// The closest hit among the triangle slots of `cand` (k_block_candidates: bit k = slot k of the staged eye-relative blob; every
+// instance is a triangle mesh), for a ray from the eye with world direction dw.  `cand` is wave-uniform, so both loops are scalar
+// and every lane of the wave runs the same tests: no box test, no stack.  tri_test_eye and the acceptance rule are those of
+// eye_instance_closest, and the minimum over (t, instance, primitive) does not depend on the order, so the hit is the walk's bit
+// for bit.
+SPT_DEV DHit eye_cand_closest(const DScene& sc, uint64_t cand, f3 dw, float t_min, float t_max) {
+    DHit h;
+    h.t = t_max; h.inst = -1; h.prim = -1; h.v = 0.0f; h.w = 0.0f;
+    for (uint32_t inst = 0; inst < sc.n_instances; ++inst) {
+        const uint32_t I = sc.o_inst + 12u * inst;
+        const uint32_t prim_id = __builtin_amdgcn_readfirstlane(__float_as_uint(geo_ld<true>(sc, I + 8u).z));
+        const uint32_t range = __builtin_amdgcn_readfirstlane(__float_as_uint(geo_ld<true>(sc, sc.o_mesh + 2u * prim_id + 1u).w));
+        const uint32_t first = range & 0xffffu, count = range >> 16;
+        uint64_t m = first < 64u ? (cand >> first) & (count >= 64u ? ~0ull : ((1ull << count) - 1ull)) : 0ull;
+        if (m == 0ull) continue;
+        const float4 m0 = geo_ld<true>(sc, I), m1 = geo_ld<true>(sc, I + 1u), m2 = geo_ld<true>(sc, I + 2u);
+        const float inv[12] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w, m2.x, m2.y, m2.z, m2.w};
+        const f3 od = xf_vector(inv, dw);   // not renormalised: t is shared between the spaces (ray.rs:33-41)
+        do {
+            const uint32_t i = first + (uint32_t)__builtin_ctzll(m);
+            m &= m - 1ull;
+            const uint32_t o = sc.o_tri + 3u * i;
+            const float4 a = geo_ld<true>(sc, o);
+            float t, v, w;
+            const bool ok = tri_test_eye(a, geo_ld<true>(sc, o + 1u), geo_ld<true>(sc, o + 2u), geo_ld<true>(sc, sc.o_eye + i), od, &t, &v, &w);
+            const int32_t id = __float_as_int(a.w);
+            if (ok && t > t_min && (t < h.t || (t == h.t && h.inst >= 0 && key_less((int32_t)inst, id, h)))) {  // triangle.rs:187
+                h.t = t; h.inst = (int32_t)inst; h.prim = id; h.v = v; h.w = w;
+            }
+        } while (m != 0ull);
+    }
+    return h;
+}

@@ -14,7 +14,7 @@
 #define SPT_ARGS_BOUNCE (DScene, RenderCtx, uint32_t)
 #define SPT_ARGS_PRIMARY_MASK (DScene, RenderCtx, FilmMask)
 
-// k_primary<kLds, kChunked, kCount, kEye, kMask>  (kMask: adaptive films, chunked only)
+// k_primary<kLds, kChunked, kCount, kEye, kMask, M...>  (kMask: adaptive films, chunked only; M: the types of the extra arguments)
 #define SPT_KERNELS_PRIMARY(X)                          \
     X((k_primary<true, false, false>), SPT_ARGS_PRIMARY)  \
     X((k_primary<true, true, false>), SPT_ARGS_PRIMARY)   \
@@ -27,6 +27,17 @@
     X((k_primary<true, true, false, true, true, FilmMask>), SPT_ARGS_PRIMARY_MASK)  \
     X((k_primary<true, true, false, false, true, FilmMask>), SPT_ARGS_PRIMARY_MASK) \
     X((k_primary<false, true, false, false, true, FilmMask>), SPT_ARGS_PRIMARY_MASK)
+
+// k_primary<true, kChunked, false, kEye = true, kMask, [FilmMask,] BlockCand>: camera rays against per-block candidate masks, and the
+// kernel that makes the masks
+#define SPT_ARGS_PRIMARY_CAND (DScene, RenderCtx, BlockCand)
+#define SPT_ARGS_PRIMARY_MASK_CAND (DScene, RenderCtx, FilmMask, BlockCand)
+#define SPT_ARGS_BLOCK_CAND (DScene, RenderCtx, uint64_t*, uint32_t)
+#define SPT_KERNELS_PRIMARY_CAND(X)                                                   \
+    X((k_block_candidates<SPT_BC_MAX_TRIS>), SPT_ARGS_BLOCK_CAND)                     \
+    X((k_primary<true, false, false, true, false, BlockCand>), SPT_ARGS_PRIMARY_CAND) \
+    X((k_primary<true, true, false, true, false, BlockCand>), SPT_ARGS_PRIMARY_CAND)  \
+    X((k_primary<true, true, false, true, true, FilmMask, BlockCand>), SPT_ARGS_PRIMARY_MASK_CAND)
 
 // k_shadow / k_extend <kLds, kCount, kFlat>, refilling variants <kCount>
 #define SPT_KERNELS_RAYS(X)                          \
@@ -124,6 +135,8 @@
 
 #if defined(SPT_INSTANTIATE_GROUP_PRIMARY)
 SPT_KERNELS_PRIMARY(SPT_DEFINE_KERNEL)
+#elif defined(SPT_INSTANTIATE_GROUP_PRIMARY_CAND)
+SPT_KERNELS_PRIMARY_CAND(SPT_DEFINE_KERNEL)
 #elif defined(SPT_INSTANTIATE_GROUP_RAYS)
 SPT_KERNELS_RAYS(SPT_DEFINE_KERNEL)
 #elif defined(SPT_INSTANTIATE_GROUP_STREAM)
@@ -156,6 +169,7 @@ SPT_KERNELS_SHADE4X(SPT_DEFINE_KERNEL)
 SPT_KERNELS_SHADE5X(SPT_DEFINE_KERNEL)
 #else
 SPT_KERNELS_PRIMARY(SPT_DECLARE_KERNEL)
+SPT_KERNELS_PRIMARY_CAND(SPT_DECLARE_KERNEL)
 SPT_KERNELS_RAYS(SPT_DECLARE_KERNEL)
 SPT_KERNELS_STREAM(SPT_DECLARE_KERNEL)
 SPT_KERNELS_SHADE0(SPT_DECLARE_KERNEL)

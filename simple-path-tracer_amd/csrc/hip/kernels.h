@@ -45,6 +45,9 @@
 #ifndef SPT_W_PRI_L
 #define SPT_W_PRI_L 6   // k_primary of LDS-resident scenes (cfg2, cfg4): unbounded 106 VGPRs = 4 waves; MEASURED at 5 (96, 5 spilled): 0.736 -> 0.655 ms per launch on cfg2; at 6 with the camera terms pinned 0.708 (24 spilled), without the pin (SPT_PRIMARY_PIN 0: 80 VGPRs, the eye-relative instance spills none) 0.608 -> 0.581 ms: 98.0 -> 100.3 Gsamples/s
 #endif
+#ifndef SPT_W_PRI_C
+#define SPT_W_PRI_C 7   // k_primary<..., BlockCand> (candidate masks instead of the tree walk, LDS-resident scenes; no stack, no spill array): bound 6 gives 69 VGPRs (7 waves fit anyway), bound 7 63 VGPRs (8 fit, 20 SGPRs spilled, no VGPR), bound 8 64 VGPRs (41 SGPRs spilled).  MEASURED on cfg2, five alternating runs each on one box: 2.132 / 2.029 / 2.023 ms per step (medians; every run at 7 or 8 faster than every run at 6, 7 and 8 within their spread of 0.04)
+#endif
 #ifndef SPT_W_PRI
 #define SPT_W_PRI 6   // cfg5 primary: round 2 - 8.6 ms at 4 waves (111 VGPRs), 8.3 at 5 (96, 9 spilled), 9.6 at 6 (80, 28 spilled); round 3 (no packed pairs: 93 VGPRs unbounded) 8.0 at 5, 7.8 at 6 (80, 8 spilled)
 #endif
@@ -52,10 +55,13 @@
 #define SPT_PRIMARY_PIN 0   // 1: k_primary keeps its camera terms in VGPRs instead of (spilled) SGPRs, see the kernel.  Paid at 4 waves per SIMD (0.819 -> 0.790 ms);
                             // at 6 waves the 18 pinned registers are worth more as occupancy: pin + 5 waves 0.608 ms, no pin + 6 waves 0.581 ms (measured, round 3)
 #endif
+#include <type_traits>
+
 #include "shading.h"
 #include "stream.h"
 #include "flat.h"
 #include "eye.h"
+#include "../../../include/spt_block_cand.h"
 
 
 struct DCamera {
@@ -135,6 +141,14 @@ struct FilmMask {
     const uint8_t* pixel;     // per shard pixel: 1 = still active, 0 = retired
     const uint32_t* tile;     // per 16x16 tile (k_primary's numbering): active pixels after the last adapt
 };
+
+// The candidate masks of k_block_candidates: the extra argument of k_primary<..., BlockCand> (one uint64_t per block of the shard:
+// block = tile * 4 + wave, bit k = triangle slot k of the staged blob), kept out of RenderCtx like FilmMask
+struct BlockCand {
+    const uint64_t* mask;
+};
+template <class T, class... M>
+constexpr bool pack_has = (std::is_same<T, M>::value || ...);
 
 SPT_DEV uint32_t lane_id() { return threadIdx.x & 63u; }
 // image row of a local row of this shard (row strips dealt round-robin, spt_abi.h)
@@ -306,15 +320,70 @@ SPT_DEV bool mask_tile_idle(const RenderCtx& rc, const FilmMask& fm) {
     return true;
 }
 
+SPT_DEV void primary_arg(FilmMask& fm, BlockCand&, const FilmMask& a) { fm = a; }
+SPT_DEV void primary_arg(FilmMask&, BlockCand& bc, const BlockCand& a) { bc = a; }
+
+// One uint64_t per block of the shard (include/spt_block_cand.h): the triangle slots of the eye-relative blob `sc` that a camera
+// ray of the block may hit.  One thread per block; launched once per window of a render, before its first k_primary<..., BlockCand>.
+// Every instance is a triangle mesh and the blob holds at most kMaxTris triangles (the host checks both before it takes the path).
+template <uint32_t kMaxTris>
+__global__ void __launch_bounds__(64) k_block_candidates(DScene sc, RenderCtx rc, uint64_t* masks, uint32_t n_blocks) {
+    static_assert(kMaxTris <= 64u, "one uint64_t per block");
+    const uint32_t block = blockIdx.x * blockDim.x + threadIdx.x;
+    if (block >= n_blocks) return;
+    spt_bc_view v;
+    const f3 fwd_hc = rc.cam.forward * rc.cam.half_cot;
+    v.fwd_hc[0] = fwd_hc.x; v.fwd_hc[1] = fwd_hc.y; v.fwd_hc[2] = fwd_hc.z;
+    v.right[0] = rc.cam.right.x; v.right[1] = rc.cam.right.y; v.right[2] = rc.cam.right.z;
+    v.up[0] = rc.cam.up.x; v.up[1] = rc.cam.up.y; v.up[2] = rc.cam.up.z;
+    v.fwd[0] = rc.cam.forward.x; v.fwd[1] = rc.cam.forward.y; v.fwd[2] = rc.cam.forward.z;
+    v.width_inv = rc.width_inv; v.height_inv = rc.height_inv; v.aspect = rc.aspect;
+    v.width = rc.width; v.height = rc.height;
+    const spt_bc_layout l{rc.shard_index, rc.shard_count, rc.strip_rows, rc.row_base, rc.rows};
+    uint64_t mask = 0ull;
+    uint32_t i0, i1, row;
+    if (spt_bc_block_pixels(&v, &l, block, &i0, &i1, &row)) {
+        const uint32_t row_end = min(row + SPT_BC_ROWS, rc.rows);
+        uint32_t j0, j1;
+        while (spt_bc_next_run(&l, &row, row_end, &j0, &j1)) {
+            for (uint32_t inst = 0; inst < sc.n_instances; ++inst) {
+                const float4* I = sc.geo + sc.o_inst + 12u * inst;
+                float m[24];   // spt_instance::inv, fwd
+                for (uint32_t q = 0; q < 6u; ++q) { const float4 f = I[q]; m[4 * q] = f.x; m[4 * q + 1] = f.y; m[4 * q + 2] = f.z; m[4 * q + 3] = f.w; }
+                const uint32_t prim_id = __float_as_uint(I[8].z);
+                const uint32_t range = __float_as_uint(sc.geo[sc.o_mesh + 2u * prim_id + 1u].w);
+                const uint32_t first = range & 0xffffu, end = min(first + (range >> 16), kMaxTris);
+                spt_bc_cone cone;
+                spt_bc_cone_make(&v, i0, i1, j0, j1, m, m + 12, &cone);
+                for (uint32_t k = first; k < end; ++k) {
+                    const float4 a = sc.geo[sc.o_tri + 3u * k], b = sc.geo[sc.o_tri + 3u * k + 1u], c = sc.geo[sc.o_tri + 3u * k + 2u];
+                    const float s[3] = {a.x, a.y, a.z}, e1[3] = {b.x, b.y, b.z}, e2[3] = {c.x, c.y, c.z};
+                    if (spt_bc_keep(&cone, s, e1, e2)) mask |= 1ull << k;
+                }
+            }
+        }
+    }
+    masks[block] = mask;
+}
+
+// The trailing types of k_primary: FilmMask (kMask, an adaptive film) and / or BlockCand (with kEye only): the kernel takes one extra
+// argument per type, in that order.  BlockCand: the wave reads its block's candidate mask once and every sample tests exactly those
+// triangles (eye_cand_closest, eye.h) - no slab test, no stack; an empty mask is a wave whose samples all miss.
 template <bool kLds, bool kChunked = false, bool kCount = false, bool kEye = false, bool kMask = false, class... M>
-__global__ void __launch_bounds__(256, SPT_WITH_BEZIER ? 1 : (kLds ? SPT_W_PRI_L : SPT_W_PRI)) k_primary(DScene sc, RenderCtx rc, M... mask_arg) {
-    static_assert(sizeof...(M) == (kMask ? 1u : 0u), "k_primary<..., true> takes the film's FilmMask, <..., false> nothing more");
+__global__ void __launch_bounds__(256, SPT_WITH_BEZIER ? 1 : (kLds ? (pack_has<BlockCand, M...> ? SPT_W_PRI_C : SPT_W_PRI_L) : SPT_W_PRI)) k_primary(DScene sc, RenderCtx rc, M... mask_arg) {
+    constexpr bool kCand = pack_has<BlockCand, M...>;
+    static_assert(sizeof...(M) == (kMask ? 1u : 0u) + (kCand ? 1u : 0u), "k_primary takes the film's FilmMask with kMask, the BlockCand of a candidate instance, nothing more");
     static_assert(!kMask || (kChunked && !kCount), "masked primary instances are chunked and do not count");
+    static_assert(!kCand || kEye, "candidate masks index the eye-relative blob");
     FilmMask fm{nullptr, nullptr};
+    BlockCand bc{nullptr};
+    (primary_arg(fm, bc, mask_arg), ...);
     if constexpr (kMask) {
-        fm = (mask_arg, ...);
         if (mask_tile_idle(rc, fm)) return;   // the whole block: fm.tile[tile] is one value per block
     }
+    // (before the staging barrier: the load's latency hides behind it)
+    uint64_t cand = 0ull;
+    if constexpr (kCand) cand = bc.mask[(size_t)(kChunked ? blockIdx.x % rc.n_tiles : blockIdx.x) * 4u + (threadIdx.x >> 6)];
     stage_geometry<kLds>(sc);
     LaneVisits vc{0u, 0u, 0u};
     const uint32_t tile = kChunked ? blockIdx.x % rc.n_tiles : blockIdx.x, chunk = kChunked ? blockIdx.x / rc.n_tiles : 0u;
@@ -340,6 +409,10 @@ __global__ void __launch_bounds__(256, SPT_WITH_BEZIER ? 1 : (kLds ? SPT_W_PRI_L
     if (in_bounds && valid && rc.row_span != nullptr) {   // the row's own span inside the rectangle (projected hulls of the instances' boxes)
         const int2 span = rc.row_span[j];
         in_bounds = (int32_t)i >= span.x && (int32_t)i <= span.y;
+    }
+    if constexpr (kCand) {   // wave-uniform: the mask is one value per wave, held in scalar registers from here on
+        cand = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(cand >> 32)) << 32) | __builtin_amdgcn_readfirstlane((uint32_t)cand);
+        in_bounds = in_bounds && cand != 0ull;
     }
     bool live = in_bounds || has_env;
     if constexpr (kMask) live = live && valid && fm.pixel[lp] != 0u;   // a retired pixel traces nothing, environment or not
@@ -387,7 +460,11 @@ __global__ void __launch_bounds__(256, SPT_WITH_BEZIER ? 1 : (kLds ? SPT_W_PRI_L
         if (may_hit || has_env) ray.d = normalize(du);
         DHit h;
         h.inst = -1;
-        if (may_hit) h = kEye ? eye_trace_closest(sc, ray.d, ray.t_min, SPT_F32_MAX) : trace_closest<kLds, kCount>(sc, ray, SPT_F32_MAX, &vc);
+        if constexpr (kCand) {
+            if (may_hit) h = eye_cand_closest(sc, cand, ray.d, ray.t_min, SPT_F32_MAX);
+        } else {
+            if (may_hit) h = kEye ? eye_trace_closest(sc, ray.d, ray.t_min, SPT_F32_MAX) : trace_closest<kLds, kCount>(sc, ray, SPT_F32_MAX, &vc);
+        }
         const bool hit = valid && h.inst >= 0;
         const size_t ri = (size_t)s * rc.n_pixels + lp;
         if (valid && !hit) {

@@ -216,6 +216,10 @@ struct spt_scene {
     DeviceBuffer eye_geo;
     DScene eye_d{};
     size_t eye_lds_bytes = 0;
+    // per-block candidate masks of that copy (k_block_candidates, include/spt_block_cand.h): the copy qualifies when every instance
+    // is a triangle mesh and it holds at most 64 triangle slots; the masks of the last window, remade by every render
+    bool cand_ok = false;
+    DeviceBuffer block_cand;
     bool simple = false;  // Lambert + delta lights only, no emission / environment / media (k_shade<0, .>)
     bool lds_tables = false;  // the shading tables fit LDS behind the geometry (k_shade<.., kTab>)
     bool fused = false;     // k_shade<0, ., kFused> can run: lds_tables and a simple scene
@@ -660,12 +664,14 @@ static void make_eye_blob(spt_scene* sc, const float eye[3]) {
     }
     const uint32_t o_eye = (uint32_t)eb.size();
     eb.resize(eb.size() + n_tris, make_float4(0, 0, 0, 0));
+    sc->cand_ok = n_tris <= SPT_BC_MAX_TRIS && d.n_instances > 0u;
     for (uint32_t i = 0; i < sc->wtlas_f4; ++i) sub3(eb[d.o_tlas + i], eye);                 // TLAS nodes: world space
     for (uint32_t i = 0; i < d.n_instances; ++i) {
         float rec[48];
         std::memcpy(rec, &eb[d.o_inst + 12u * i], sizeof(rec));
         const float* m = rec;                                                                 // spt_instance::inv
         const uint32_t prim_type = as_u(rec[33]), prim_id = as_u(rec[34]);
+        if (prim_type != SPT_PRIM_MESH) sc->cand_ok = false;
         float oo[3];                                                                          // xf_point(inv, eye)
         for (int k = 0; k < 3; ++k) oo[k] = ((m[k] * eye[0] + m[3 + k] * eye[1]) + m[6 + k] * eye[2]) + m[9 + k];
         if (prim_type == SPT_PRIM_SPHERE) {                                                   // oc = o' - c, in pad[1..3] of the instance record
@@ -733,6 +739,7 @@ struct RenderRun {
     spt_render_stats* stats = nullptr;
     hipStream_t st = nullptr;
     bool profile = false, count = false, overlap = false, L = false, use_eye = false, dyn_shadow = false, dyn_extend = false;
+    bool use_cand = false;       // k_primary<..., BlockCand>: camera rays against the per-block candidate masks of the eye-relative copy
     bool fused = false;          // k_shade<0, ., kFused>: shade, shadow and extend of a bounce in one kernel, one hit queue class
     bool class_queues = false;   // the general shade kernels' hit queue may be binned by BxDF class (kClasses)
     bool tab = false;            // the general shade kernels read the shading tables from LDS (k_shade<.., kTab>)
@@ -802,6 +809,8 @@ void run_setup(RenderRun& run) {
     // primary rays of an LDS-resident scene through the eye-relative copy of its geometry (eye.h), remade when the eye has moved
     run.use_eye = !run.rays && run.L && !run.count && sc->eye_ok && std::getenv("SPT_NO_EYE_BLOB") == nullptr;
     if (run.use_eye && (!sc->eye_valid || std::memcmp(sc->eye_key, cam->eye, sizeof(sc->eye_key)) != 0)) make_eye_blob(sc, cam->eye);
+    // ... and, when that copy is at most 64 triangles of meshes only, against the triangles k_block_candidates leaves per wave
+    run.use_cand = run.use_eye && sc->cand_ok && std::getenv("SPT_NO_BLOCK_CANDIDATES") == nullptr;
     // refilling persistent waves for large scenes: on for shadow rays (any-hit walks end at very
     // different times: 10.9 -> 8.8 ms on the 1 M-triangle scene), off for extension rays (28 vs 20 ms)
     run.dyn_shadow = !run.L && std::getenv("SPT_NO_DYN_SHADOW") == nullptr;
@@ -1211,6 +1220,13 @@ void launch_primary(const RenderRun& run, uint32_t blocks, const RenderCtx& rc, 
     if constexpr (!kMask) {   // (visits are only counted outside LDS, so never through the eye-relative copy)
         if (run.count) fn = run.stream_p ? k_primary_stream<kChunked, true> : k_primary<false, kChunked, true>;
     }
+    if constexpr (kChunked || !kMask) {
+        if (run.use_cand && !run.stream_p && !run.count) {   // (use_cand implies use_eye; the masks are those of this window, see trace_window)
+            hipLaunchKernelGGL((k_primary<true, kChunked, false, true, kMask, M..., BlockCand>), dim3(blocks), dim3(kBlock), sc->eye_lds_bytes, run.st,
+                               run_scene(run, true), rc, mask..., BlockCand{sc->block_cand.as<uint64_t>()});
+            return;
+        }
+    }
     hipLaunchKernelGGL(fn, dim3(blocks), dim3(kBlock), run.use_eye ? sc->eye_lds_bytes : run.lds, run.st, run_scene(run, run.use_eye), rc, mask...);
 }
 
@@ -1442,6 +1458,18 @@ RenderCtx trace_window(RenderRun& run, uint32_t row_base, uint32_t rows, uint32_
     rc.visits = sc->visits.as<unsigned long long>();
     rc.row_span = run.row_span_dev;
     const LiveCount live = count_live(sc, run.env, rc);
+    // The candidate masks of this window's blocks: every render, ahead of its first k_primary on the same stream (whose earlier launches read the
+    // masks before this one overwrites them, by stream order).  Here, with the rest of the workspace: a growing buffer drains both streams and
+    // resets the overlap state, which the lines below set for this render.
+    if (run.use_cand && p.max_depth != 0u && rc.n_tiles != 0u) {
+        const uint32_t n_blocks = rc.n_tiles * 4u;
+        grow(sc, sc->block_cand, (size_t)n_blocks * sizeof(uint64_t));
+        run.begin(SPT_K_OTHER);
+        hipLaunchKernelGGL((k_block_candidates<SPT_BC_MAX_TRIS>), dim3((n_blocks + 63u) / 64u), dim3(64), 0, run.st, run_scene(run, true), rc,
+                           sc->block_cand.as<uint64_t>(), n_blocks);
+        HIP_CHECK(hipGetLastError());
+        run.end();
+    }
     // The overlapped schedule (run.film_overlap, asked for by spt_render): the main stream traces pass p + 1 into one set of
     // the doubled pass buffers while the film stream finishes pass p from the other - its tail-loop shade launch when that
     // kernel is chosen, and its resolve.  Neither needs the vector ALU that k_primary keeps busy.  Without memory for the

@@ -6,6 +6,7 @@
 #include <fstream>
 #include <sstream>
 
+#include "../../../include/spt_block_cand.h"
 #include "host_scene.hpp"
 #include "json.hpp"
 
@@ -270,6 +271,48 @@ static spt_status load_renderer(const char* path, spt_render_params* params, flo
         set_error(e.msg);
         return e.code;
     }
+}
+
+spt_status spt_host_block_candidates(const spt_camera* cam, uint32_t width, uint32_t height, uint32_t shard_index, uint32_t shard_count,
+                                     uint32_t strip_rows, uint32_t rows, uint32_t block, const float* inv, const float* fwd, uint32_t n_tris,
+                                     const float* tri_pos, uint64_t* mask_out) {
+    if (!cam || !inv || !fwd || !mask_out || (n_tris != 0u && !tri_pos)) { g_error = "block_candidates: null argument"; return SPT_ERR_INVALID_ARG; }
+    if (width == 0u || height == 0u || shard_count == 0u || shard_index >= shard_count || strip_rows == 0u || n_tris > SPT_BC_MAX_TRIS) {
+        g_error = "block_candidates: empty image, bad shard layout or more than 64 triangles";
+        return SPT_ERR_INVALID_ARG;
+    }
+    // the camera and image terms as the device forms them (plan_ctx of spt_hip.hip, k_primary)
+    spt_bc_view v;
+    for (int k = 0; k < 3; ++k) {
+        v.fwd_hc[k] = cam->forward[k] * cam->half_cot_half_fov;
+        v.right[k] = cam->right[k]; v.up[k] = cam->up[k]; v.fwd[k] = cam->forward[k];
+    }
+    v.aspect = (float)width / (float)height;
+    v.width_inv = 1.0f / (float)width;
+    v.height_inv = 1.0f / (float)height;
+    v.width = width; v.height = height;
+    const spt_bc_layout l{shard_index, shard_count, strip_rows, 0u, rows};
+    // the object-space eye of the eye-relative copy (make_eye_blob: xf_point(inv, eye))
+    float oo[3];
+    for (int k = 0; k < 3; ++k) oo[k] = ((inv[k] * cam->eye[0] + inv[3 + k] * cam->eye[1]) + inv[6 + k] * cam->eye[2]) + inv[9 + k];
+    uint64_t mask = 0ull;
+    uint32_t i0, i1, row;
+    if (spt_bc_block_pixels(&v, &l, block, &i0, &i1, &row)) {
+        const uint32_t row_end = std::min(row + SPT_BC_ROWS, rows);
+        uint32_t j0, j1;
+        while (spt_bc_next_run(&l, &row, row_end, &j0, &j1)) {
+            spt_bc_cone cone;
+            spt_bc_cone_make(&v, i0, i1, j0, j1, inv, fwd, &cone);
+            for (uint32_t t = 0; t < n_tris; ++t) {
+                const float* p = tri_pos + 9u * t;
+                float s[3], e1[3], e2[3];
+                for (int k = 0; k < 3; ++k) { s[k] = oo[k] - p[k]; e1[k] = p[3 + k] - p[k]; e2[k] = p[6 + k] - p[k]; }
+                if (spt_bc_keep(&cone, s, e1, e2)) mask |= 1ull << t;
+            }
+        }
+    }
+    *mask_out = mask;
+    return SPT_OK;
 }
 
 spt_status spt_host_load_renderer(const char* path, spt_render_params* params, float* filter_radius) {

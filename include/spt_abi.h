@@ -478,6 +478,16 @@ typedef struct spt_mesh_deform {
 } spt_mesh_deform;
 spt_status spt_scene_deform(spt_scene* scene, const spt_scene_update_desc* u, uint32_t n_meshes, const spt_mesh_deform* meshes);
 
+/* spt_scene_origin_candidates (additive to ABI v14: detect it by its symbol): the per-origin-triangle candidate table the fused
+ * simple shade kernels of the scene test their shadow and extension rays against (include/spt_origin_cand.h), as the device holds it
+ * behind every update queued so far.  *n_rows_out = 0: none - the scene does not qualify (not served by the fused simple kernels,
+ * an instance that is no triangle mesh, more than 64 triangles) or SPT_NO_ORIGIN_CANDIDATES=1 is set.  Else words_out (NULL: not
+ * wanted; room for 4 x 64) receives 4 words per row - loose up, loose down, tight up, tight down; row = a triangle's index in
+ * tri_pos, bit k = slot k of the library's own triangle order - and info_out (NULL: not wanted) 8 doubles: the scene's centre
+ * (3) and radius, the reach (a render takes the path when its eye is within it of the centre), delta(reach), tight (0: the
+ * tight words equal the loose ones), ns the host took to make the table. */
+spt_status spt_scene_origin_candidates(const spt_scene* scene, uint64_t* words_out, uint32_t* n_rows_out, double* info_out);
+
 /* The hot path: RendererT::render for one image shard.  rgb_mean_out receives
  * shard_rows*width*3 f32 = per-pixel mean radiance (Film::filter_pixel with the
  * box filter, src/core/film.rs:71-92: the sum of the samples of the (2 ceil(radius - 0.5) + 1)^2 pixels around it

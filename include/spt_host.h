@@ -117,6 +117,15 @@ spt_status spt_host_block_candidates(const spt_camera* cam, uint32_t width, uint
                                      uint32_t strip_rows, uint32_t rows, uint32_t block, const float* inv, const float* fwd, uint32_t n_tris,
                                      const float* tri_pos, uint64_t* mask_out);
 
+/* The per-origin-triangle candidate table of include/spt_origin_cand.h on the host, for checking it without a device.  Instance i
+ * has the spt_instance matrices inv / fwd (12 floats each) and the normal matrix nrm (9 floats); triangle k (at most 64) belongs
+ * to instance tri_instance[k], with tri_pos 9 floats (p0, p1, p2, object space) and tri_nrm its 3 vertex normals; its slot and its
+ * row are both k.  words_out receives 4 words per triangle (loose up, loose down, tight up, tight down; bit u = triangle u),
+ * info_out 8 doubles: the scene's centre (3) and radius, reach, delta(reach), delta_scene, tight (0 / 1). */
+spt_status spt_host_origin_candidates(uint32_t n_instances, const float* inv, const float* fwd, const float* nrm, uint32_t n_tris,
+                                      const uint32_t* tri_instance, const float* tri_pos, const float* tri_nrm, uint64_t* words_out,
+                                      double* info_out);
+
 /* OpenEXR scanline I/O (RGB f32 / f16; reads NO_COMPRESSION / RLE / ZIPS / ZIP / PIZ / PXR24, writes uncompressed) for
  * `environment {type: "exr"}` (get_exr_image, src/core/loader.rs:374-390). */
 spt_status spt_host_read_exr(const char* path, uint32_t* width, uint32_t* height, float** rgb_out);

@@ -341,6 +341,9 @@ def host_lib() -> C.CDLL:
             lib.spt_host_scene_mesh_positions.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint32), C.c_void_p]
             lib.spt_host_scene_set_mesh_positions.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_void_p, C.c_void_p]
             lib.spt_host_scene_mesh_index.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint32)]
+        if hasattr(lib, "spt_host_origin_candidates"):   # (the same)
+            lib.spt_host_origin_candidates.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p]
         if hasattr(lib, "spt_host_block_candidates"):   # (the same)
             lib.spt_host_block_candidates.argtypes = [C.POINTER(Camera)] + [C.c_uint32] * 7 + [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                                                                              C.POINTER(C.c_uint64)]
@@ -425,6 +428,8 @@ def hip_lib() -> C.CDLL:
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         if hasattr(lib, "spt_debug_render_info"):   # (the same)
             lib.spt_debug_render_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
+        if hasattr(lib, "spt_scene_origin_candidates"):   # (the same)
+            lib.spt_scene_origin_candidates.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
         _hip_lib = lib
     return _hip_lib
 
@@ -765,6 +770,23 @@ class DeviceScene:
         v = C.c_uint64(0)
         _check_hip(hip_lib().spt_debug_render_info(self._h, what, C.byref(v)))
         return int(v.value)
+
+    def origin_candidates(self):
+        """spt_scene_origin_candidates: None when the scene's shade kernels do not take the per-origin-triangle candidate path (or
+        SPT_NO_ORIGIN_CANDIDATES=1), else (words, info): words (n_rows, 4) uint64 as the device holds them - loose up, loose
+        down, tight up, tight down per triangle index, bit k = slot k - and info, a dict with center, radius, reach, delta, tight
+        and build_ns."""
+        lib = hip_lib()
+        if not hasattr(lib, "spt_scene_origin_candidates"):
+            raise SptError(4, "this libspt_hip.so has no spt_scene_origin_candidates")
+        words = np.zeros((64, 4), dtype=np.uint64)
+        info = np.zeros(8, dtype=np.float64)
+        n = C.c_uint32(0)
+        _check_hip(lib.spt_scene_origin_candidates(self._h, words.ctypes.data, C.byref(n), info.ctypes.data))
+        if n.value == 0:
+            return None
+        return words[:n.value].copy(), {"center": info[0:3].copy(), "radius": float(info[3]), "reach": float(info[4]), "delta": float(info[5]),
+                                        "tight": bool(info[6]), "build_ns": int(info[7])}
 
     def close(self) -> None:
         # an asynchronous frame may still be copying into one of the pinned film buffers: the scene goes first (its destroy
@@ -1401,6 +1423,25 @@ def block_candidates(camera: Camera, width: int, height: int, block: int, inv, f
     _check_host(host_lib().spt_host_block_candidates(C.byref(camera), width, height, shard_index, shard_count, strip_rows, rows, block,
                                                      inv.ctypes.data, fwd.ctypes.data, len(tri), tri.ctypes.data, C.byref(mask)))
     return int(mask.value)
+
+
+def origin_candidates(inv, fwd, nrm, tri_instance, tri_pos, tri_nrm):
+    """The per-origin-triangle candidate table (include/spt_origin_cand.h) on the host.  inv / fwd: (n_instances, 12), nrm:
+    (n_instances, 9) (spt_instance); triangle k belongs to instance tri_instance[k], tri_pos (n, 9) object-space vertices, tri_nrm
+    (n, 9) its vertex normals, n <= 64; slot and row of a triangle are both k.  Returns (words, info): words (n, 4) uint64 - loose
+    up, loose down, tight up, tight down - and info, a dict with center, radius, reach, delta, delta_scene and tight."""
+    inv, fwd = (np.ascontiguousarray(m, dtype=np.float32).reshape(-1, 12) for m in (inv, fwd))
+    nrm = np.ascontiguousarray(nrm, dtype=np.float32).reshape(-1, 9)
+    owner = np.ascontiguousarray(tri_instance, dtype=np.uint32).reshape(-1)
+    tri = np.ascontiguousarray(tri_pos, dtype=np.float32).reshape(-1, 9)
+    tn = np.ascontiguousarray(tri_nrm, dtype=np.float32).reshape(-1, 9)
+    assert len(inv) == len(fwd) == len(nrm) and len(tri) == len(tn) == len(owner)
+    words = np.zeros((max(len(tri), 1), 4), dtype=np.uint64)
+    info = np.zeros(8, dtype=np.float64)
+    _check_host(host_lib().spt_host_origin_candidates(len(inv), inv.ctypes.data, fwd.ctypes.data, nrm.ctypes.data, len(tri), owner.ctypes.data,
+                                                      tri.ctypes.data, tn.ctypes.data, words.ctypes.data, info.ctypes.data))
+    return words[:len(tri)], {"center": info[0:3].copy(), "radius": float(info[3]), "reach": float(info[4]), "delta": float(info[5]),
+                              "delta_scene": float(info[6]), "tight": bool(info[7])}
 
 
 def make_camera(eye, forward, up, fov_degrees: float) -> Camera:

@@ -75,6 +75,13 @@
     X((k_shade<0, false, false, true, true>), SPT_ARGS_BOUNCE)       \
     X((k_shade<0, true, false, false, false>), SPT_ARGS_BOUNCE)      \
     X((k_shade<0, false, false, false, false>), SPT_ARGS_BOUNCE)
+// k_shade<0, kFirst, true, true, true, kLoop, false, OriginCand>: the fused simple kernels with per-origin-triangle candidate sets
+// (origin.h) instead of the two tree walks: bounce 0, bounce >= 1 and the tail loop
+#define SPT_ARGS_BOUNCE_ORIGIN (DScene, RenderCtx, uint32_t, OriginCand)
+#define SPT_KERNELS_SHADE0_ORIGIN(X)                                                             \
+    X((k_shade<0, true, true, true, true, false, false, OriginCand>), SPT_ARGS_BOUNCE_ORIGIN)    \
+    X((k_shade<0, false, true, true, true, false, false, OriginCand>), SPT_ARGS_BOUNCE_ORIGIN)   \
+    X((k_shade<0, false, true, true, true, true, false, OriginCand>), SPT_ARGS_BOUNCE_ORIGIN)
 #define SPT_KERNELS_SHADE1(X)                                        \
     X((k_shade<1, true, false, true, true>), SPT_ARGS_BOUNCE)        \
     X((k_shade<1, false, false, true, true>), SPT_ARGS_BOUNCE)       \
@@ -143,6 +150,8 @@ SPT_KERNELS_RAYS(SPT_DEFINE_KERNEL)
 SPT_KERNELS_STREAM(SPT_DEFINE_KERNEL)
 #elif defined(SPT_INSTANTIATE_GROUP_SHADE0)
 SPT_KERNELS_SHADE0(SPT_DEFINE_KERNEL)
+#elif defined(SPT_INSTANTIATE_GROUP_SHADE0_ORIGIN)
+SPT_KERNELS_SHADE0_ORIGIN(SPT_DEFINE_KERNEL)
 #elif defined(SPT_INSTANTIATE_GROUP_SHADE1)
 SPT_KERNELS_SHADE1(SPT_DEFINE_KERNEL)
 #elif defined(SPT_INSTANTIATE_GROUP_SHADE2)
@@ -173,6 +182,7 @@ SPT_KERNELS_PRIMARY_CAND(SPT_DECLARE_KERNEL)
 SPT_KERNELS_RAYS(SPT_DECLARE_KERNEL)
 SPT_KERNELS_STREAM(SPT_DECLARE_KERNEL)
 SPT_KERNELS_SHADE0(SPT_DECLARE_KERNEL)
+SPT_KERNELS_SHADE0_ORIGIN(SPT_DECLARE_KERNEL)
 SPT_KERNELS_SHADE1(SPT_DECLARE_KERNEL)
 SPT_KERNELS_SHADE2(SPT_DECLARE_KERNEL)
 SPT_KERNELS_SHADE3A(SPT_DECLARE_KERNEL)

@@ -61,6 +61,7 @@
 #include "stream.h"
 #include "flat.h"
 #include "eye.h"
+#include "origin.h"
 #include "../../../include/spt_block_cand.h"
 
 
@@ -558,6 +559,9 @@ SPT_DEV void rad_store(const RenderCtx& rc, uint32_t slot, f3 c) {
 #define SPT_SHADE0_WAVES 0   // waves / SIMD the fused bounce-0 kernel is compiled for; 0 = no bound (146 VGPRs, 3 waves).
                              // MEASURED with 4 (128 VGPRs, 20 spilled): cfg2 shade_first 1.44 -> 1.96 ms per step; not kept
 #endif
+#ifndef SPT_SHADE0_ORIGIN_WAVES
+#define SPT_SHADE0_ORIGIN_WAVES 0   // ... and its OriginCand instance (no walk, no stack, no spill array); 0 = no bound (110 VGPRs, 4 waves, no scratch)
+#endif
 // kLoop (fused kernels of bounce >= 1 only): a vertex produced by the extension trace inside this kernel is shaded by the
 // same lane in the next turn of an inner loop instead of travelling through the queue to the next launch, down to the
 // last bounce.  The host picks it when the previous pass showed that few paths are left after bounce 0 (cfg2: a cube in
@@ -578,10 +582,15 @@ SPT_DEV void rad_store(const RenderCtx& rc, uint32_t slot, f3 c) {
 struct RayAux {
     const float4* rec;   // 4 float4 per ray of the pass (spt_ray_aux); a path's ray is its radiance slot modulo rc.n_pixels
 };
+// OriginCand (trailing type, fused simple instances only; the one extra argument is the scene's table, origin.h): the shadow and the
+// extension ray of a vertex are tested against the candidate sets of the triangle they leave instead of walking the tree.  Without
+// it there is no extra argument and the kernel's code stays what it was.
 template <int kFeat, bool kFirst, bool kFused = false, bool kTab = kFused, bool kGeoLds = kTab, bool kLoop = false, bool kAux = false, class... A>
-__global__ void __launch_bounds__(256, (kFeat == 0 && kFirst && kFused && SPT_SHADE0_WAVES) ? SPT_SHADE0_WAVES : ((kFeat == 3 || kFeat == 4) ? SPT_SHADE_HEAVY_WAVES : ((kFeat == 1 && kFirst && SPT_SHADE1_WAVES) ? SPT_SHADE1_WAVES : 1))) k_shade(DScene sc, RenderCtx rc, uint32_t bounce, A... aux_arg) {
+__global__ void __launch_bounds__(256, (kFeat == 0 && kFirst && kFused && pack_has<OriginCand, A...> && SPT_SHADE0_ORIGIN_WAVES) ? SPT_SHADE0_ORIGIN_WAVES : (kFeat == 0 && kFirst && kFused && !pack_has<OriginCand, A...> && SPT_SHADE0_WAVES) ? SPT_SHADE0_WAVES : ((kFeat == 3 || kFeat == 4) ? SPT_SHADE_HEAVY_WAVES : ((kFeat == 1 && kFirst && SPT_SHADE1_WAVES) ? SPT_SHADE1_WAVES : 1))) k_shade(DScene sc, RenderCtx rc, uint32_t bounce, A... aux_arg) {
     static_assert(!kLoop || (kFused && !kFirst), "the in-kernel bounce loop exists for the fused kernels of bounce >= 1");
-    static_assert(sizeof...(A) == (kAux ? 1u : 0u), "k_shade<..., kAux = true> takes the pass's RayAux, every other instance nothing more");
+    constexpr bool kOrig = pack_has<OriginCand, A...>;
+    static_assert(sizeof...(A) == (kAux ? 1u : 0u) + (kOrig ? 1u : 0u), "k_shade<..., kAux = true> takes the pass's RayAux, an OriginCand instance the scene's table, every other instance nothing more");
+    static_assert(!kOrig || (kFeat == 0 && kFused && !kAux), "origin candidates serve the fused simple kernels");
     static_assert(!kAux || (kFeat >= 2 && !kFirst && !kFused), "auxiliary rays serve the un-fused textured levels, on full path records");
     // kFeat 3: Subsurface substrates (the probe), 4: position-normal distributions (the glint walks), 5: both
     constexpr bool kSimple = kFeat == 0, kTex = kFeat >= 2, kSubsurface = kFeat == 3 || kFeat == 5, kPndf = kFeat == 4 || kFeat == 5;
@@ -653,10 +662,12 @@ __global__ void __launch_bounds__(256, (kFeat == 0 && kFirst && kFused && SPT_SH
         DRng rng;
         rng.s.state = 0ull;
         bool want_shadow = false, want_ext = false;
+        uint64_t oc_shadow = 0ull, oc_ext = 0ull;   // kOrig: the candidate words of this lane's two rays
         float shadow_tmax = 0.0f, next_pdf = 0.0f;
         f3 contrib = mk3(0, 0, 0);
         for (;;) {   // one turn, or (kLoop) one turn per bounce
         want_shadow = false; want_ext = false;
+        oc_shadow = 0ull; oc_ext = 0ull;
         contrib = mk3(0, 0, 0);
         if (lane_on) {
             float4 hv = kPrefetch ? cur_hv : rc.hits.t_v_w_prim[idx];
@@ -840,6 +851,14 @@ __global__ void __launch_bounds__(256, (kFeat == 0 && kFirst && kFused && SPT_SH
                 } else {  // pt.rs:112-193
                     const spt_surface sf = load_surface<kTab>(sc, it.surface);
                     const uint32_t sflags = sf.flags;
+                    // kOrig: the four words of the triangle this vertex lies on, and whether the frame's z axis is -it.normal (surface_coord)
+                    uint4 oc_loose = make_uint4(0u, 0u, 0u, 0u), oc_tight = oc_loose;
+                    bool oc_flip = false;
+                    if constexpr (kOrig) {
+                        const uint4* const row = (aux_arg, ...).table + 2u * (uint32_t)h.prim;
+                        oc_loose = row[0]; oc_tight = row[1];
+                        oc_flip = (sflags & SPT_SURF_DOUBLE_SIDED) != 0u && dot(ray.d, it.normal) > 0.0f;
+                    }
                     DMat mt = material_at<kTex, kTab, kPndf>(sc, sf.material, it);
                     if (kSimple) mt.bxdf = SPT_BXDF_LAMBERT;
                     DCoord coord = surface_coord<kTex>(sc, sf, ray, it);
@@ -897,6 +916,7 @@ __global__ void __launch_bounds__(256, (kFeat == 0 && kFirst && kFused && SPT_SH
                                 shadow_ray.t_min = kTMinEps / spt_max(spt_abs(wi.z), 0.00001f);
                                 shadow_tmax = ls.dist - 0.001f;
                                 want_shadow = true;
+                                if constexpr (kOrig) oc_shadow = origin_word(oc_loose, oc_tight, wi.z, oc_flip);
                             }
                         }
                     }
@@ -915,6 +935,7 @@ __global__ void __launch_bounds__(256, (kFeat == 0 && kFirst && kFused && SPT_SH
                     f3 wi_world = coord.to_world(samp.wi);
                     next_ray.o = po; next_ray.d = wi_world;
                     next_ray.t_min = kTMinEps / spt_max(spt_abs(samp.wi.z), 0.00001f);
+                    if constexpr (kOrig) oc_ext = origin_word(oc_loose, oc_tight, samp.wi.z, oc_flip);
                     thr = thr * crcp(samp.f * spt_abs(samp.wi.z), spt_max(samp.pdf, 0.00001f));
                     float hd = dot(wi_world, coord.hemi);  // Coordinate::in_expected_hemisphere
                     if (!(samp.transmit ? (hd <= 0.0f) : (hd >= 0.0f))) alive = false;
@@ -943,12 +964,24 @@ __global__ void __launch_bounds__(256, (kFeat == 0 && kFirst && kFused && SPT_SH
             // the two queue counters still count the segments (spt_render_stats); the slots are not used
             const PendingPush ps = wave_push_issue(want_shadow, kLoop ? q_count(rc.counts, b_cur, Q_SHADOW, shard) : shadow_count);
             const PendingPush pe = wave_push_issue(want_ext, kLoop ? q_count(rc.counts, b_cur, Q_EXT, shard) : ext_count);
-            if (want_shadow && !trace_any<true>(sc, shadow_ray, shadow_tmax)) slot_add(slot, contrib);   // k_shadow
+            if constexpr (kOrig) {   // the wave's rays against the union of their candidate sets (origin.h); an empty union is no trace
+                const uint64_t un = wave_or64(want_shadow ? oc_shadow : 0ull);
+                bool occluded = false;
+                if (un != 0ull) occluded = origin_cand_any(sc, un, want_shadow, shadow_ray, shadow_tmax);
+                if (want_shadow && !occluded) slot_add(slot, contrib);
+            } else {
+                if (want_shadow && !trace_any<true>(sc, shadow_ray, shadow_tmax)) slot_add(slot, contrib);   // k_shadow
+            }
             bool keep = false;                                                                               // k_extend
             DHit nh;
             nh.inst = -1; nh.t = SPT_F32_MAX; nh.prim = -1; nh.v = 0.0f; nh.w = 0.0f;
+            if constexpr (kOrig) {
+                const bool go = want_ext && b_cur + 1u < rc.max_depth;
+                const uint64_t un = wave_or64(go ? oc_ext : 0ull);
+                if (un != 0ull) nh = origin_cand_closest(sc, un, go, next_ray, SPT_F32_MAX);
+            }
             if (want_ext && b_cur + 1u < rc.max_depth) {   // the host launches no k_extend after the last bounce either
-                nh = trace_closest<true>(sc, next_ray, SPT_F32_MAX);
+                if constexpr (!kOrig) nh = trace_closest<true>(sc, next_ray, SPT_F32_MAX);
                 if (nh.inst >= 0 || medium >= 0) {
                     keep = true;
                 } else if (!kSimple && sc.env_w != 0u) {  // pt.rs:97-111, curr_depth > 0 here

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <array>
+#include <chrono>
 #include <cmath>
 #include <cstddef>
 #include <cstdio>
@@ -220,6 +221,13 @@ struct spt_scene {
     // is a triangle mesh and it holds at most 64 triangle slots; the masks of the last window, remade by every render
     bool cand_ok = false;
     DeviceBuffer block_cand;
+    // per-origin-triangle candidate sets of the fused simple shade kernels (origin.h, include/spt_origin_cand.h): made on the host
+    // from the blob of every committed scene state (origin_table), the device copy always 4 x 64 words; origin_ok: the scene qualifies
+    bool origin_ok = false;
+    std::vector<uint64_t> origin_words;
+    spt_oc_info origin_info{};
+    DeviceBuffer origin_cand;
+    uint64_t origin_build_ns = 0;   // what the last origin_table took on the host
     bool simple = false;  // Lambert + delta lights only, no emission / environment / media (k_shade<0, .>)
     bool lds_tables = false;  // the shading tables fit LDS behind the geometry (k_shade<.., kTab>)
     bool fused = false;     // k_shade<0, ., kFused> can run: lds_tables and a simple scene
@@ -345,6 +353,56 @@ void dyn_commit_host(spt_scene* sc, SceneDynamic& dy, bool lds_geo) {
     sc->bs_valid = dy.bs_valid;
     sc->hull_corners = std::move(dy.hull_corners);
 }
+
+// The origin-candidate table of the scene state `dy` (include/spt_origin_cand.h), from the blob the device stages: the instances'
+// matrices, the slots' (p0, e1, e2, id) and the vertex normals of the shading tables behind the geometry.  False - no table - unless
+// the state is served by the fused simple kernels with an eye-relative copy (every mesh used by one instance, so a triangle id names
+// one world triangle), every instance is a triangle mesh and the blob holds at most 64 slots: the preconditions of the block masks.
+bool origin_table(const SceneDynamic& dy, uint32_t n_instances, uint32_t n_meshes, std::vector<uint64_t>& words, spt_oc_info& info) {
+    if (!dy.fused || !dy.simple || !dy.eye_ok || dy.o_attr == 0u || n_instances == 0u || dy.blob.size() < dy.geo_f4) return false;
+    const float4* const b = dy.blob.data();
+    auto as_u = [](float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; };
+    std::vector<spt_oc_instance> inst(n_instances);
+    std::vector<spt_oc_triangle> tri;
+    std::vector<uint8_t> mesh_used(n_meshes, 0);
+    for (uint32_t i = 0; i < n_instances; ++i) {
+        float rec[48];
+        std::memcpy(rec, &b[dy.o_inst + 12u * i], sizeof(rec));
+        std::memcpy(inst[i].inv, rec, sizeof inst[i].inv);
+        std::memcpy(inst[i].fwd, rec + 12, sizeof inst[i].fwd);
+        std::memcpy(inst[i].nrm, rec + 24, sizeof inst[i].nrm);
+        const uint32_t prim_type = as_u(rec[33]), mesh = as_u(rec[34]);
+        if (prim_type != SPT_PRIM_MESH || mesh >= n_meshes || mesh_used[mesh]) return false;
+        mesh_used[mesh] = 1;
+        const uint32_t range = as_u(b[dy.o_mesh + 2u * mesh + 1u].w);
+        const uint32_t first = range & 0xffffu, count = range >> 16;
+        if (first + count > SPT_OC_MAX_TRIS) return false;
+        if (tri.size() < first + count) tri.resize(first + count, spt_oc_triangle{{0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, ~0u, ~0u});
+        for (uint32_t k = first; k < first + count; ++k) {
+            const float4 a = b[dy.o_tri + 3u * k], e1 = b[dy.o_tri + 3u * k + 1u], e2 = b[dy.o_tri + 3u * k + 2u];
+            spt_oc_triangle& t = tri[k];
+            t.p0[0] = a.x; t.p0[1] = a.y; t.p0[2] = a.z;
+            t.e1[0] = e1.x; t.e1[1] = e1.y; t.e1[2] = e1.z;
+            t.e2[0] = e2.x; t.e2[1] = e2.y; t.e2[2] = e2.z;
+            t.instance = i;
+            t.id = as_u(a.w);
+            if (t.id >= SPT_OC_MAX_TRIS || (size_t)dy.o_attr + 9u * t.id + 3u > dy.blob.size()) return false;
+            std::memcpy(t.n, &b[dy.o_attr + 9u * t.id], sizeof t.n);   // spt_tri_attr: the three vertex normals come first
+        }
+    }
+    for (const spt_oc_triangle& t : tri)
+        if (t.instance == ~0u) return false;   // a slot of a mesh no instance uses
+    words.assign((size_t)SPT_OC_WORDS * SPT_OC_MAX_TRIS, 0ull);
+    return spt_oc_build(inst.data(), n_instances, tri.data(), (uint32_t)tri.size(), words.data(), &info);
+}
+
+// ... installed as the scene's (host side; the caller copies sc->origin_words to sc->origin_cand where origin_ok)
+void origin_install(spt_scene* sc, const SceneDynamic& dy, uint32_t n_instances, uint32_t n_meshes) {
+    const auto t0 = std::chrono::steady_clock::now();
+    sc->origin_ok = origin_table(dy, n_instances, n_meshes, sc->origin_words, sc->origin_info);
+    sc->origin_build_ns = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+}
+constexpr size_t kOriginBytes = (size_t)SPT_OC_WORDS * SPT_OC_MAX_TRIS * sizeof(uint64_t);
 
 uint32_t shard_row_count(const spt_render_params& p) {
     uint32_t sc = p.shard_count ? p.shard_count : 1u, sr = p.strip_rows ? p.strip_rows : 1u;
@@ -632,6 +690,9 @@ spt_status spt_scene_create(const spt_scene_desc* desc, int32_t device, spt_scen
         const StaticSections st = sb.sections();
         SceneDynamic dy = build_dynamic(sb.fixed, dyn_view(*desc, sb.fixed.surf_emissive.data()), opt, sb.lds_geo, sb.blas_range.size(), &st);
         upload_scene(sc.get(), *desc, sb, dy);
+        origin_install(sc.get(), dy, desc->n_instances, desc->n_meshes);
+        sc->origin_cand.alloc(kOriginBytes);
+        if (sc->origin_ok) HIP_CHECK(hipMemcpy(sc->origin_cand.p, sc->origin_words.data(), kOriginBytes, hipMemcpyHostToDevice));
         dyn_commit_host(sc.get(), dy, sc->lds_geo);
         *out = sc.release();
         return SPT_OK;
@@ -741,6 +802,7 @@ struct RenderRun {
     bool profile = false, count = false, overlap = false, L = false, use_eye = false, dyn_shadow = false, dyn_extend = false;
     bool use_cand = false;       // k_primary<..., BlockCand>: camera rays against the per-block candidate masks of the eye-relative copy
     bool fused = false;          // k_shade<0, ., kFused>: shade, shadow and extend of a bounce in one kernel, one hit queue class
+    bool use_origin = false;     // ... its OriginCand instances: the two rays of a vertex against the scene's origin-candidate table
     bool class_queues = false;   // the general shade kernels' hit queue may be binned by BxDF class (kClasses)
     bool tab = false;            // the general shade kernels read the shading tables from LDS (k_shade<.., kTab>)
     bool tail_loop = false;      // the fused pipeline may take bounce 1 and every later one in one launch (kTailLoopBelow)
@@ -836,6 +898,14 @@ void run_setup(RenderRun& run) {
     // see k_shade<.., kFused>.  Only the lean k_shade<0> variant gains: with the general kernel's 220+ VGPRs
     // the two traversals run at 2 waves / SIMD and cfg4 is faster un-fused (4.30 vs 4.00 Gsamples/s, measured)
     run.fused = sc->fused && sc->simple && std::getenv("SPT_NO_FUSED") == nullptr;
+    // ... with the candidate sets of the triangle a vertex lies on instead of the two walks, for a camera whose eye is within the
+    // table's reach (the error bound of a bounce-0 origin grows with the camera's distance; caller rays start anywhere)
+    run.use_origin = run.fused && sc->origin_ok && !run.rays && !run.count && cam != nullptr && std::getenv("SPT_NO_ORIGIN_CANDIDATES") == nullptr;
+    if (run.use_origin) {
+        double d2 = 0.0;
+        for (int k = 0; k < 3; ++k) d2 += ((double)cam->eye[k] - sc->origin_info.center[k]) * ((double)cam->eye[k] - sc->origin_info.center[k]);
+        run.use_origin = std::sqrt(d2) <= sc->origin_info.reach;   // (a NaN eye fails the comparison)
+    }
     run.class_queues = std::getenv("SPT_NO_CLASS_QUEUES") == nullptr;
     run.tab = sc->lds_tables && std::getenv("SPT_NO_LDS_TABLES") == nullptr;   // shading tables from LDS (tab_ld)
     run.tail_loop = std::getenv("SPT_NO_TAIL_LOOP") == nullptr;
@@ -1289,6 +1359,13 @@ BounceFn shade_kernel(const RenderRun& run, uint32_t b, bool tail_loop) {
     return sc->has_pndf ? shade_level<5>(first, run.tab, run.L) : shade_level<3>(first, run.tab, run.L);
 }
 
+// ... and its OriginCand instance, which run.use_origin launches in its place
+using BounceOriginFn = void (*)(DScene, RenderCtx, uint32_t, OriginCand);
+BounceOriginFn shade_origin_kernel(uint32_t b, bool tail_loop) {
+    return b == 0 ? k_shade<0, true, true, true, true, false, false, OriginCand>
+                  : tail_loop ? k_shade<0, false, true, true, true, true, false, OriginCand> : k_shade<0, false, true, true, true, false, false, OriginCand>;
+}
+
 // k_shade<kFeat, false, false, kTab, kGeoLds, false, kAux = true>: bounce 0 of spt_radiance with auxiliary rays on a textured scene, chosen
 // as shade_level / shade_kernel choose the plain instances
 using BounceAuxFn = void (*)(DScene, RenderCtx, uint32_t, RayAux);
@@ -1362,6 +1439,8 @@ bool bounce(RenderRun& run, const RenderCtx& rc, uint32_t b, hipStream_t st) {
     }
     if (run.ray_aux != nullptr && b == 0u && sc->textured && !sc->simple && !run.fused)
         hipLaunchKernelGGL(shade_aux_kernel(run), dim3(kPersistentBlocks), dim3(kBlock), shade_lds, st, sc->d, ru, b, RayAux{run.ray_aux});
+    else if (run.use_origin)
+        hipLaunchKernelGGL(shade_origin_kernel(b, tail_loop), dim3(kPersistentBlocks), dim3(kBlock), shade_lds, st, sc->d, ru, b, OriginCand{sc->origin_cand.as<uint4>()});
     else
         hipLaunchKernelGGL(shade_kernel(run, b, tail_loop), dim3(kPersistentBlocks), dim3(kBlock), shade_lds, st, sc->d, ru, b);
     run.end();
@@ -1749,6 +1828,13 @@ spt_status update_locked(spt_scene* sc, const spt_scene_update_desc* u, uint32_t
             part(sc->light_k.p, u->light_alias.k, (size_t)fx.n_lights * sizeof(uint32_t));
         }
         part(sc->geo.as<float4>() + (fx.n4 ? fx.tail_first : 0u), dy.blob.data(), dy.blob.size() * 16);
+        // the origin-candidate table of the new state (instances moved, vertices deformed: both are in dy.blob), behind the blob
+        std::vector<uint64_t> origin_words;
+        spt_oc_info origin_info{};
+        const auto origin_t0 = std::chrono::steady_clock::now();
+        const bool origin_ok = origin_table(dy, fx.n_instances, fx.n_meshes, origin_words, origin_info);
+        const uint64_t origin_ns = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - origin_t0).count();
+        if (origin_ok) part(sc->origin_cand.p, origin_words.data(), kOriginBytes);
         if ((fx.n4 ? (size_t)fx.tail_first * 16 : 0) + dy.blob.size() * 16 > sc->geo.bytes) fail(SPT_ERR_UNSUPPORTED, w + ": the geometry blob outgrew its allocation: recreate the scene");
         HIP_CHECK(hipSetDevice(sc->device));
         if (!sc->ev_upd) HIP_CHECK(hipEventCreateWithFlags(&sc->ev_upd, hipEventDisableTiming));
@@ -1814,6 +1900,10 @@ spt_status update_locked(spt_scene* sc, const spt_scene_update_desc* u, uint32_t
             sc->blas_range = std::move(blas_range);
         }
         dyn_commit_host(sc, dy, sc->lds_geo);
+        sc->origin_ok = origin_ok;
+        sc->origin_words = std::move(origin_words);
+        sc->origin_info = origin_info;
+        sc->origin_build_ns = origin_ns;
         ++sc->updates;
         sc->update_bytes = 0;
         for (const Part& pt : parts) sc->update_bytes += pt.bytes;
@@ -1845,6 +1935,29 @@ spt_status spt_scene_deform(spt_scene* sc, const spt_scene_update_desc* u, uint3
     }
     std::lock_guard<std::mutex> lock(sc->mu);
     return update_locked(sc, u, n_meshes, meshes, "scene_deform");
+}
+
+spt_status spt_scene_origin_candidates(const spt_scene* scene_c, uint64_t* words_out, uint32_t* n_rows_out, double* info_out) {
+    if (!scene_c || !n_rows_out) { g_error = "scene_origin_candidates: null argument"; return SPT_ERR_INVALID_ARG; }
+    spt_scene* sc = const_cast<spt_scene*>(scene_c);
+    *n_rows_out = 0u;
+    if (sc->fwd) return SPT_OK;   // a scene with Bezier patches never qualifies
+    std::lock_guard<std::mutex> lock(sc->mu);
+    return guarded("scene_origin_candidates", [&] {
+        if (!sc->origin_ok || std::getenv("SPT_NO_ORIGIN_CANDIDATES") != nullptr) return SPT_OK;
+        const spt_oc_info& in = sc->origin_info;
+        if (words_out) {   // the device's copy, behind every update queued so far
+            HIP_CHECK(hipSetDevice(sc->device));
+            HIP_CHECK(hipStreamSynchronize(sc->stream));
+            HIP_CHECK(hipMemcpy(words_out, sc->origin_cand.p, (size_t)SPT_OC_WORDS * in.n_rows * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        }
+        if (info_out) {
+            const double out[8] = {in.center[0], in.center[1], in.center[2], in.radius, in.reach, in.delta, (double)in.tight, (double)sc->origin_build_ns};
+            std::memcpy(info_out, out, sizeof out);
+        }
+        *n_rows_out = in.n_rows;
+        return SPT_OK;
+    });
 }
 
 spt_status spt_render(const spt_scene* scene_c, const spt_camera* cam, const spt_render_params* params,

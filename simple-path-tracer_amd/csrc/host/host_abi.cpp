@@ -7,6 +7,7 @@
 #include <sstream>
 
 #include "../../../include/spt_block_cand.h"
+#include "../../../include/spt_origin_cand.h"
 #include "host_scene.hpp"
 #include "json.hpp"
 
@@ -312,6 +313,36 @@ spt_status spt_host_block_candidates(const spt_camera* cam, uint32_t width, uint
         }
     }
     *mask_out = mask;
+    return SPT_OK;
+}
+
+spt_status spt_host_origin_candidates(uint32_t n_instances, const float* inv, const float* fwd, const float* nrm, uint32_t n_tris,
+                                      const uint32_t* tri_instance, const float* tri_pos, const float* tri_nrm, uint64_t* words_out,
+                                      double* info_out) {
+    if (!inv || !fwd || !nrm || !tri_instance || !tri_pos || !tri_nrm || !words_out || !info_out) { g_error = "origin_candidates: null argument"; return SPT_ERR_INVALID_ARG; }
+    std::vector<spt_oc_instance> in(n_instances);
+    for (uint32_t i = 0; i < n_instances; ++i) {
+        std::memcpy(in[i].inv, inv + 12u * i, sizeof in[i].inv);
+        std::memcpy(in[i].fwd, fwd + 12u * i, sizeof in[i].fwd);
+        std::memcpy(in[i].nrm, nrm + 9u * i, sizeof in[i].nrm);
+    }
+    std::vector<spt_oc_triangle> tr(n_tris);
+    for (uint32_t k = 0; k < n_tris; ++k) {
+        const float* p = tri_pos + 9u * k;
+        for (int a = 0; a < 3; ++a) { tr[k].p0[a] = p[a]; tr[k].e1[a] = p[3 + a] - p[a]; tr[k].e2[a] = p[6 + a] - p[a]; }   // the blob's f32 differences
+        std::memcpy(tr[k].n, tri_nrm + 9u * k, sizeof tr[k].n);
+        tr[k].instance = tri_instance[k];
+        tr[k].id = k;
+    }
+    uint64_t words[SPT_OC_WORDS * SPT_OC_MAX_TRIS];
+    spt_oc_info info;
+    if (!spt_oc_build(in.data(), n_instances, tr.data(), n_tris, words, &info)) {
+        g_error = "origin_candidates: no triangle, more than 64, a bad instance index or a singular transform";
+        return SPT_ERR_INVALID_ARG;
+    }
+    std::memcpy(words_out, words, sizeof(uint64_t) * SPT_OC_WORDS * n_tris);
+    const double out[8] = {info.center[0], info.center[1], info.center[2], info.radius, info.reach, info.delta, info.delta_scene, (double)info.tight};
+    std::memcpy(info_out, out, sizeof out);
     return SPT_OK;
 }
 

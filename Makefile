@@ -25,7 +25,7 @@ HOST_HDR := $(wildcard $(PKG)/csrc/host/*.hpp) $(wildcard include/*.h)
 HIP_SRC  := $(wildcard $(PKG)/csrc/hip/*.hip)
 HIP_HDR  := $(wildcard $(PKG)/csrc/hip/*.h) $(wildcard include/*.h)
 
-.PHONY: all host hip hip-plain cli oracle selftest out-layout-check scene-build-check scene-deform-refit-check clean
+.PHONY: all host hip hip-plain cli oracle selftest out-layout-check scene-build-check scene-deform-refit-check mesh-assemble-check clean
 all: host oracle hip cli
 
 host: $(LIBDIR)/libspt_host.so
@@ -111,6 +111,16 @@ $(SELFTEST_DIR)/scene_deform_refit_check: tests/scene_deform_refit_check.cpp $(B
 	@mkdir -p $(SELFTEST_DIR)
 	$(CXX) -std=c++17 -O1 -g -Wall -Wextra -ffp-contract=off -fno-fast-math -Iinclude -I$(PKG)/csrc/hip -D__HIP_PLATFORM_AMD__ -isystem $(ROCM_PATH)/include \
 	    -fsanitize=address,undefined -fno-sanitize-recover=undefined -static-libasan -static-libubsan -o $@ tests/scene_deform_refit_check.cpp $(BUILD_SRC)
+
+# include/spt_mesh_assemble.h (the arithmetic of spt_scene_deform_vertices' kernels) against the loader's own calc_tangents and
+# face_records (linked from libspt_host.so, as scene-build-check links it), by the kernels' schedule, over random meshes: a
+# stand-alone host program under AddressSanitizer + UBSan (tests/test_mesh_assemble.py runs it)
+mesh-assemble-check: $(SELFTEST_DIR)/mesh_assemble_check
+$(SELFTEST_DIR)/mesh_assemble_check: tests/mesh_assemble_check.cpp $(HOST_HDR) $(LIBDIR)/libspt_host.so
+	@mkdir -p $(SELFTEST_DIR)
+	$(CXX) -std=c++17 -O1 -g -Wall -Wextra -ffp-contract=off -fno-fast-math -Iinclude \
+	    -fsanitize=address,undefined -fno-sanitize-recover=undefined -static-libasan -static-libubsan -o $@ tests/mesh_assemble_check.cpp \
+	    -L$(LIBDIR) -lspt_host -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
 
 clean:
 	rm -rf $(LIBDIR) build oracle/*.so oracle/_ref

@@ -478,6 +478,44 @@ typedef struct spt_mesh_deform {
 } spt_mesh_deform;
 spt_status spt_scene_deform(spt_scene* scene, const spt_scene_update_desc* u, uint32_t n_meshes, const spt_mesh_deform* meshes);
 
+/* spt_scene_mesh_topology / spt_scene_deform_vertices / spt_scene_read_triangles (additive to ABI v14: detect them by their
+ * symbols): spt_scene_deform from vertex arrays.  A mesh's topology is registered once; a deformation then sends 12 bytes per
+ * vertex (24 with normals) and the library makes the mesh's tri_pos / tri_attr records itself, with the loader's arithmetic
+ * (include/spt_mesh_assemble.h: the tangent frames of TriMesh::calc_tangents, the records of TriMesh::new) - on the device for a
+ * large scene, in front of the refit kernels of spt_scene_deform; on the host for an LDS-resident one, whose trees are built
+ * there anyway.  The records are, word for word, what the host loader makes of the same vertices (a NaN stays a NaN).
+ *   spt_scene_mesh_topology: indices are in FACE order, the order the tangents of a vertex are summed in; face_of_tri maps the
+ *     mesh's triangle range onto the faces (the order a BLAS build chose).  Checked on the host: every index < n_vertices,
+ *     face_of_tri a permutation, uv and normals finite, the mesh index, tri_count, size, null pointers (SPT_ERR_INVALID_ARG).
+ *     Everything is copied: the caller's arrays may go after the call.  A second call for a mesh replaces its registration.
+ *     Nothing a frame can see changes, so a live film does not refuse it.  SPT_ERR_UNSUPPORTED under SPT_REFERENCE_BVH=1.
+ *   spt_scene_deform_vertices: `u`, the films rule, the ordering, atomicity on refusal and counters 4 / 5 / 6 of
+ *     spt_debug_render_info are spt_scene_deform's.  Refused in addition, SPT_ERR_INVALID_ARG: a mesh without a registration, a
+ *     wrong n_vertices, a value that is not finite, a mesh named twice.  Large scenes: counter 5 is at most the update's bound
+ *     + 12 (24 with normals) per vertex of the named meshes + 64 per named mesh, and no record is uploaded.  An LDS-resident
+ *     scene's records are made on the host and go the way of spt_scene_deform.
+ *   spt_scene_read_triangles: copies records [first, first + count) of the scene's triangle arrays (the descriptor's order) out
+ *     of device memory, behind everything queued on the render stream.  Range errors: SPT_ERR_INVALID_ARG. */
+typedef struct spt_mesh_topology {
+    uint32_t size, mesh;              /* sizeof(spt_mesh_topology) AS THE CALLER WAS COMPILED; index into the creation's meshes[] */
+    uint32_t n_vertices, tri_count;   /* tri_count must equal meshes[mesh].tri_count */
+    const uint32_t* indices;          /* 3 * tri_count vertex indices, in face order */
+    const uint32_t* face_of_tri;      /* tri_count: triangle meshes[mesh].tri_first + k is face face_of_tri[k]; NULL = identity */
+    const float* uv;                  /* 2 * n_vertices */
+    const float* normals;             /* 3 * n_vertices: the normals a deformation without normals keeps */
+} spt_mesh_topology;
+spt_status spt_scene_mesh_topology(spt_scene* scene, const spt_mesh_topology* t);
+
+typedef struct spt_mesh_vertices {
+    uint32_t mesh, n_vertices;        /* n_vertices must equal the registration's */
+    const float* positions;           /* 3 * n_vertices, host memory */
+    const float* normals;             /* 3 * n_vertices, or NULL: the normals stay (the last ones given, else the registration's) */
+} spt_mesh_vertices;
+spt_status spt_scene_deform_vertices(spt_scene* scene, const spt_scene_update_desc* u, uint32_t n_meshes, const spt_mesh_vertices* meshes);
+
+spt_status spt_scene_read_triangles(const spt_scene* scene, uint32_t first, uint32_t count, spt_tri_pos* tri_pos_out /* or NULL */,
+                                    spt_tri_attr* tri_attr_out /* or NULL */);
+
 /* spt_scene_origin_candidates (additive to ABI v14: detect it by its symbol): the per-origin-triangle candidate table the fused
  * simple shade kernels of the scene test their shadow and extension rays against (include/spt_origin_cand.h), as the device holds it
  * behind every update queued so far.  *n_rows_out = 0: none - the scene does not qualify (not served by the fused simple kernels,
@@ -864,7 +902,7 @@ spt_status spt_debug_bxdf(const spt_scene* scene, int32_t device, const spt_mate
  *   what 6  ns the copies and kernels of the last spt_scene_deform that named a mesh took on the device (0: none yet); waits for
  *           them (a library without spt_scene_deform refuses 6).  Like every counter here a debug seam for the measuring tools
  *           (tools/scene_deform_cost.py), not part of what spt_scene_deform promises: it may change without an ABI version
- * spt_scene_deform counts as an update in 4 and reports its bytes in 5. */
+ * spt_scene_deform and spt_scene_deform_vertices count as an update in 4 and report their bytes in 5 (and their device time in 6). */
 spt_status spt_debug_render_info(const spt_scene* scene, uint32_t what, uint64_t* out);
 
 const char* spt_last_error(void);

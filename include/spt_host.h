@@ -77,6 +77,22 @@ spt_status spt_host_scene_mesh_index(const spt_host_scene* scene, const char* pr
 spt_status spt_host_scene_mesh_positions(const spt_host_scene* scene, const char* primitive_name, uint32_t* n_vertices, float* out /* may be NULL */);
 spt_status spt_host_scene_set_mesh_positions(spt_host_scene* scene, const char* primitive_name, uint32_t n_vertices, const float* positions,
                                              const float* normals /* NULL: keep */);
+/* Deforming a loaded mesh from vertex arrays, its records made only when somebody reads them (spt_scene_deform_vertices takes the
+ * vertices to a live device scene, which makes its own records).
+ *   _mesh_topology: fills *out for spt_scene_mesh_topology with pointers into the scene - the OBJ loader's indices in face order,
+ *     the triangle order the BLAS build chose as face_of_tri, uv, the normals in force, the counts, `mesh` as _mesh_index gives
+ *     it.  The pointers stay valid until spt_host_scene_free (the normals' contents follow later edits).
+ *   _set_mesh_vertices: the checks and refusals of _set_mesh_positions.  The vertices are stored, the mesh's root box is the
+ *     min / max over the vertices some face names, its instances, the TLAS, the lights and the alias table are made again from
+ *     that box - and the mesh is left PENDING: its tri_pos / tri_attr / blas_nodes ranges are made by the next
+ *     spt_host_scene_desc (or any other entry that reads them), which therefore returns exactly what _set_mesh_positions would
+ *     have left.  A mesh with an emissive instance needs its triangles for the light's power: it is made at once.
+ *     _set_mesh_positions on a pending mesh supersedes it.
+ *   _dynamic: the four arrays spt_scene_update takes, as they stand, WITHOUT making any pending mesh. */
+spt_status spt_host_scene_mesh_topology(const spt_host_scene* scene, const char* primitive_name, spt_mesh_topology* out);
+spt_status spt_host_scene_set_mesh_vertices(spt_host_scene* scene, const char* primitive_name, uint32_t n_vertices, const float* positions,
+                                            const float* normals /* NULL: keep */);
+spt_status spt_host_scene_dynamic(const spt_host_scene* scene, spt_scene_update_desc* out);
 /* `spt --animate FILE`: {"frames": [ {"<instance name>": <transform object in the scene file's own syntax: matrix, scale, rotate,
  * translate>, ...}, ... ]}, checked against `scene` (SPT_HOST_ERR_SCHEMA: a malformed file, an unknown instance).
  * spt_host_animation_apply hands frame `frame`'s transforms to spt_host_scene_set_transforms; instances a frame does not name

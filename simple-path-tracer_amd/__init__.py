@@ -290,6 +290,18 @@ class MeshDeform(C.Structure):
     _fields_ = [("mesh", C.c_uint32), ("tri_count", C.c_uint32), ("tri_pos", C.POINTER(TriPos)), ("tri_attr", C.POINTER(TriAttr))]
 
 
+class MeshTopology(C.Structure):
+    """spt_mesh_topology (spt_scene_mesh_topology); `size` is sizeof of the struct."""
+    _fields_ = [("size", C.c_uint32), ("mesh", C.c_uint32), ("n_vertices", C.c_uint32), ("tri_count", C.c_uint32),
+                ("indices", C.POINTER(C.c_uint32)), ("face_of_tri", C.POINTER(C.c_uint32)), ("uv", C.POINTER(C.c_float)),
+                ("normals", C.POINTER(C.c_float))]
+
+
+class MeshVertices(C.Structure):
+    """spt_mesh_vertices (spt_scene_deform_vertices): new positions (and normals, or NULL) for every vertex of one mesh."""
+    _fields_ = [("mesh", C.c_uint32), ("n_vertices", C.c_uint32), ("positions", C.POINTER(C.c_float)), ("normals", C.POINTER(C.c_float))]
+
+
 def _load(name: str) -> C.CDLL:
     path = os.path.join(LIB_DIR, name)
     if not os.path.exists(path):
@@ -341,6 +353,10 @@ def host_lib() -> C.CDLL:
             lib.spt_host_scene_mesh_positions.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint32), C.c_void_p]
             lib.spt_host_scene_set_mesh_positions.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_void_p, C.c_void_p]
             lib.spt_host_scene_mesh_index.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint32)]
+        if hasattr(lib, "spt_host_scene_set_mesh_vertices"):   # (the same)
+            lib.spt_host_scene_mesh_topology.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(MeshTopology)]
+            lib.spt_host_scene_set_mesh_vertices.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_void_p, C.c_void_p]
+            lib.spt_host_scene_dynamic.argtypes = [C.c_void_p, C.POINTER(SceneUpdateDesc)]
         if hasattr(lib, "spt_host_origin_candidates"):   # (the same)
             lib.spt_host_origin_candidates.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                        C.c_void_p, C.c_void_p]
@@ -423,6 +439,10 @@ def hip_lib() -> C.CDLL:
             lib.spt_scene_update.argtypes = [C.c_void_p, C.POINTER(SceneUpdateDesc)]
         if hasattr(lib, "spt_scene_deform"):   # (the same)
             lib.spt_scene_deform.argtypes = [C.c_void_p, C.POINTER(SceneUpdateDesc), C.c_uint32, C.POINTER(MeshDeform)]
+        if hasattr(lib, "spt_scene_deform_vertices"):   # (the same)
+            lib.spt_scene_mesh_topology.argtypes = [C.c_void_p, C.POINTER(MeshTopology)]
+            lib.spt_scene_deform_vertices.argtypes = [C.c_void_p, C.POINTER(SceneUpdateDesc), C.c_uint32, C.POINTER(MeshVertices)]
+            lib.spt_scene_read_triangles.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         lib.spt_debug_detmath.argtypes = [C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.spt_debug_bxdf.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Material), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -454,7 +474,9 @@ class Scene:
         _check_host(host_lib().spt_host_load_scene(os.fspath(path).encode(), C.byref(self._h)))
         self.path = os.fspath(path)
         self._device_scenes = {}
-        self._mesh_gen = {}   # mesh index -> how often set_mesh_positions has edited it (a DeviceScene compares with what it has seen)
+        self._mesh_gen = {}   # mesh index -> how often set_mesh_positions / set_mesh_vertices has edited it (a DeviceScene compares with what it has seen)
+        self._mesh_nrm_gen = {}    # ... and how often one of them gave it new normals
+        self._mesh_by_vertices = {}   # mesh index -> the primitive's name while its latest edit came by set_mesh_vertices
 
     @property
     def desc(self) -> SceneDesc:
@@ -566,6 +588,52 @@ class Scene:
                 raise ValueError("normals: one normal per position is expected")
         _check_host(lib.spt_host_scene_set_mesh_positions(self._h, name.encode(), pos.shape[0], pos.ctypes.data, nrm.ctypes.data if nrm is not None else None))
         self._mesh_gen[mesh] = self._mesh_gen.get(mesh, 0) + 1
+        if nrm is not None:
+            self._mesh_nrm_gen[mesh] = self._mesh_nrm_gen.get(mesh, 0) + 1
+        self._mesh_by_vertices.pop(mesh, None)
+
+    def _vertices_host(self):
+        lib = host_lib()
+        if not hasattr(lib, "spt_host_scene_set_mesh_vertices"):
+            raise SptError(4, "this libspt_host.so cannot deform a loaded mesh by its vertices (no spt_host_scene_set_mesh_vertices)")
+        return lib
+
+    def _mesh_topology(self, name: str) -> "MeshTopology":
+        """spt_host_scene_mesh_topology: the struct, its pointers into the host scene (valid until close())."""
+        t = MeshTopology()
+        _check_host(self._vertices_host().spt_host_scene_mesh_topology(self._h, name.encode(), C.byref(t)))
+        return t
+
+    def mesh_topology(self, name: str) -> dict:
+        """spt_host_scene_mesh_topology as numpy copies: mesh, indices (tri_count, 3) in face order, face_of_tri (tri_count,), uv
+        (n_vertices, 2) and the normals in force (n_vertices, 3) - what DeviceScene.set_topology takes."""
+        t = self._mesh_topology(name)
+        nv, nt = int(t.n_vertices), int(t.tri_count)
+        return {"mesh": int(t.mesh),
+                "indices": np.ctypeslib.as_array(t.indices, shape=(nt, 3)).copy(),
+                "face_of_tri": np.ctypeslib.as_array(t.face_of_tri, shape=(nt,)).copy(),
+                "uv": np.ctypeslib.as_array(t.uv, shape=(nv, 2)).copy(),
+                "normals": np.ctypeslib.as_array(t.normals, shape=(nv, 3)).copy()}
+
+    def set_mesh_vertices(self, name: str, positions, normals=None) -> None:
+        """spt_host_scene_set_mesh_vertices: set_mesh_positions with the mesh's triangle records and BLAS boxes left to be made
+        when somebody reads the descriptor (`desc`, `array`); instances, TLAS, lights and alias table follow at once.  A
+        DeviceScene.update() after it sends the vertices, not records, and the device makes its own records."""
+        lib = self._vertices_host()
+        mesh = self.mesh_index(name)
+        pos = np.ascontiguousarray(positions, dtype=np.float32)
+        if pos.ndim != 2 or pos.shape[1] != 3:
+            raise ValueError("positions: an (n_vertices, 3) array is expected")
+        nrm = None
+        if normals is not None:
+            nrm = np.ascontiguousarray(normals, dtype=np.float32)
+            if nrm.shape != pos.shape:
+                raise ValueError("normals: one normal per position is expected")
+        _check_host(lib.spt_host_scene_set_mesh_vertices(self._h, name.encode(), pos.shape[0], pos.ctypes.data, nrm.ctypes.data if nrm is not None else None))
+        self._mesh_gen[mesh] = self._mesh_gen.get(mesh, 0) + 1
+        if nrm is not None:
+            self._mesh_nrm_gen[mesh] = self._mesh_nrm_gen.get(mesh, 0) + 1
+        self._mesh_by_vertices[mesh] = name
 
     def device_scene(self, device: int = 0) -> "DeviceScene":
         if device not in self._device_scenes:
@@ -615,6 +683,8 @@ class DeviceScene:
         self._films = weakref.WeakSet()   # ProgressiveFilm objects on this scene: destroyed before it
         desc = scene.desc
         self._mesh_seen = dict(scene._mesh_gen)
+        self._mesh_ranges = [(int(desc.meshes[m].tri_first), int(desc.meshes[m].tri_count)) for m in range(desc.n_meshes)]
+        self._topology_nrm = {}   # mesh index -> Scene._mesh_nrm_gen of the normals this device scene's registration holds
         _check_hip(hip_lib().spt_scene_create(C.byref(desc), device, C.byref(self._h)))
 
     def film_buffer(self, rows: int, width: int) -> np.ndarray:
@@ -688,11 +758,16 @@ class DeviceScene:
     def update(self) -> None:
         """spt_scene_update with the Scene's current tlas_nodes, instances, lights and light alias table (after
         Scene.set_transforms / set_light): the device scene then behaves like one freshly created from the Scene.  Frames queued
-        before with SPT_RENDER_ASYNC still deliver the old state.  The scene's films must be closed first."""
+        before with SPT_RENDER_ASYNC still deliver the old state.  The scene's films must be closed first.  Meshes edited since the
+        last update go along: by spt_scene_deform_vertices when the latest edit of every one of them came by Scene.set_mesh_vertices
+        (their topology is registered on first use), else by spt_scene_deform with the Scene's records."""
+        dirty = sorted(m for m, gen in self.scene._mesh_gen.items() if self._mesh_seen.get(m) != gen)
+        if dirty and all(m in self.scene._mesh_by_vertices for m in dirty) and hasattr(hip_lib(), "spt_scene_deform_vertices"):
+            self._update_vertices(dirty)
+            return
         d = self.scene.desc
         u = SceneUpdateDesc(size=C.sizeof(SceneUpdateDesc), flags=0, n_tlas_nodes=d.n_tlas_nodes, tlas_nodes=d.tlas_nodes,
                             n_instances=d.n_instances, instances=d.instances, n_lights=d.n_lights, lights=d.lights, light_alias=d.light_alias)
-        dirty = sorted(m for m, gen in self.scene._mesh_gen.items() if self._mesh_seen.get(m) != gen)
         if not dirty:
             self._update(u)
             return
@@ -707,13 +782,82 @@ class DeviceScene:
         for m in dirty:
             self._mesh_seen[m] = self.scene._mesh_gen[m]
 
-    def update_arrays(self, instances, lights, tlas_nodes=None, light_alias=None, meshes=None) -> None:
+    def _update_vertices(self, dirty) -> None:
+        """update() when every dirty mesh's latest edit came by Scene.set_mesh_vertices: spt_scene_deform_vertices with the
+        Scene's stored vertices; nothing of the host scene is materialised."""
+        scene, lib = self.scene, hip_lib()
+        for m in dirty:   # the topology of meshes this device scene has not registered yet, straight from the host scene's arrays
+            if m not in self._topology_nrm:
+                t = scene._mesh_topology(scene._mesh_by_vertices[m])
+                _check_hip(lib.spt_scene_mesh_topology(self._h, C.byref(t)))
+                self._topology_nrm[m] = scene._mesh_nrm_gen.get(m, 0)
+        u = SceneUpdateDesc()
+        _check_host(host_lib().spt_host_scene_dynamic(scene._h, C.byref(u)))
+        keep = []
+        verts = (MeshVertices * len(dirty))()
+        for v, m in zip(verts, dirty):
+            name = scene._mesh_by_vertices[m]
+            pos = scene.mesh_positions(name)
+            keep.append(pos)
+            v.mesh, v.n_vertices = m, pos.shape[0]
+            v.positions = C.cast(pos.ctypes.data, C.POINTER(C.c_float))
+            if self._topology_nrm[m] != scene._mesh_nrm_gen.get(m, 0):   # normals newer than the ones the device holds
+                v.normals = scene._mesh_topology(name).normals
+        _check_hip(lib.spt_scene_deform_vertices(self._h, C.byref(u), len(dirty), verts))
+        for m in dirty:
+            self._mesh_seen[m] = scene._mesh_gen[m]
+            self._topology_nrm[m] = scene._mesh_nrm_gen.get(m, 0)
+
+    def set_topology(self, mesh: int, indices, face_of_tri, uv, normals) -> None:
+        """spt_scene_mesh_topology for callers with their own arrays (see Scene.mesh_topology): indices (tri_count, 3) in face
+        order, face_of_tri (tri_count,) or None for the identity, uv (n_vertices, 2), normals (n_vertices, 3).  Everything is
+        copied by the call; a second call for a mesh replaces its registration."""
+        lib = hip_lib()
+        if not hasattr(lib, "spt_scene_mesh_topology"):
+            raise SptError(4, "this libspt_hip.so has no spt_scene_mesh_topology")
+        idx = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+        uv = np.ascontiguousarray(uv, dtype=np.float32).reshape(-1)
+        nrm = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1)
+        if idx.shape[0] % 3 != 0 or uv.shape[0] % 2 != 0 or nrm.shape[0] != uv.shape[0] // 2 * 3:
+            raise ValueError("indices (tri_count, 3), uv (n_vertices, 2) and normals (n_vertices, 3) are expected")
+        t = MeshTopology(size=C.sizeof(MeshTopology), mesh=mesh, n_vertices=uv.shape[0] // 2, tri_count=idx.shape[0] // 3)
+        t.indices = C.cast(idx.ctypes.data, C.POINTER(C.c_uint32))
+        t.uv = C.cast(uv.ctypes.data, C.POINTER(C.c_float))
+        t.normals = C.cast(nrm.ctypes.data, C.POINTER(C.c_float))
+        if face_of_tri is not None:
+            fot = np.ascontiguousarray(face_of_tri, dtype=np.uint32).reshape(-1)
+            if fot.shape[0] != t.tri_count:
+                raise ValueError("face_of_tri: one face per triangle is expected")
+            t.face_of_tri = C.cast(fot.ctypes.data, C.POINTER(C.c_uint32))
+        _check_hip(lib.spt_scene_mesh_topology(self._h, C.byref(t)))
+        self._topology_nrm[mesh] = None   # (normals of the caller's: the next update() by vertices sends the Scene's)
+
+    def read_triangles(self, mesh_index: int):
+        """spt_scene_read_triangles: the (tri_pos, tri_attr) record arrays of mesh `mesh_index` as the device holds them, behind
+        every update queued so far."""
+        lib = hip_lib()
+        if not hasattr(lib, "spt_scene_read_triangles"):
+            raise SptError(4, "this libspt_hip.so has no spt_scene_read_triangles")
+        first, count = self._mesh_ranges[mesh_index]
+        tri_pos = np.zeros(count, dtype=np.dtype(TriPos))
+        tri_attr = np.zeros(count, dtype=np.dtype(TriAttr))
+        _check_hip(lib.spt_scene_read_triangles(self._h, first, count, tri_pos.ctypes.data, tri_attr.ctypes.data))
+        return tri_pos, tri_attr
+
+    def update_arrays(self, instances, lights, tlas_nodes=None, light_alias=None, meshes=None, vertices=None) -> None:
         """spt_scene_update for callers who edit the records themselves: `instances` / `lights` / `tlas_nodes` are arrays of the
         Instance / Light / BvhNode records (as Scene.array returns them; the instances in the leaf order of tlas_nodes),
         light_alias the (props, u, k) arrays of a power_is scene.  None: the Scene's current ones.  `meshes`: {mesh index:
         (tri_pos, tri_attr or None)} arrays of TriPos / TriAttr records for the mesh's whole range - then the call is
-        spt_scene_deform."""
-        d = self.scene.desc
+        spt_scene_deform.  `vertices`: {mesh index: (positions, normals or None)} for meshes registered with set_topology - then
+        it is spt_scene_deform_vertices; giving both is a ValueError."""
+        if meshes is not None and vertices is not None:
+            raise ValueError("meshes= and vertices= exclude each other: one call deforms by records or by vertices")
+        if vertices is not None and hasattr(host_lib(), "spt_host_scene_dynamic"):   # (the Scene's defaults without materialising it)
+            d = SceneUpdateDesc()
+            _check_host(host_lib().spt_host_scene_dynamic(self.scene._h, C.byref(d)))
+        else:
+            d = self.scene.desc
         keep = []
 
         def records(a, ty):
@@ -736,6 +880,26 @@ class DeviceScene:
             _, u.light_alias.u = records(uu, C.c_float)
             _, u.light_alias.k = records(k, C.c_uint32)
             u.light_alias.n = n
+        if vertices is not None:
+            lib = hip_lib()
+            if not hasattr(lib, "spt_scene_deform_vertices"):
+                raise SptError(4, "this libspt_hip.so has no spt_scene_deform_vertices")
+            verts = (MeshVertices * max(len(vertices), 1))()
+            for v, (m, (positions, normals)) in zip(verts, vertices.items()):
+                pos = np.ascontiguousarray(positions, dtype=np.float32)
+                if pos.ndim != 2 or pos.shape[1] != 3:
+                    raise ValueError("mesh %d: an (n_vertices, 3) array of positions is expected" % m)
+                keep.append(pos)
+                v.mesh, v.n_vertices = m, pos.shape[0]
+                v.positions = C.cast(pos.ctypes.data, C.POINTER(C.c_float))
+                if normals is not None:
+                    nrm = np.ascontiguousarray(normals, dtype=np.float32)
+                    if nrm.shape != pos.shape:
+                        raise ValueError("mesh %d: one normal per position is expected" % m)
+                    keep.append(nrm)
+                    v.normals = C.cast(nrm.ctypes.data, C.POINTER(C.c_float))
+            _check_hip(lib.spt_scene_deform_vertices(self._h, C.byref(u), len(vertices), verts))
+            return
         if meshes is None:
             self._update(u)
             return

@@ -6,6 +6,25 @@
 
 #include "scene_refit.h"
 
+#include "../../../include/spt_mesh_assemble.h"
+
+// One mesh of one spt_scene_deform_vertices call on a large scene, as the kernels of inst_assemble.hip see it: the registration's
+// device arrays and the call's vertices (m), the vertex frames between the two launches, and the scene's ABI-order triangle arrays
+struct AssembleMesh {
+    spt_ma_mesh m;
+    float* tan;               // 3 floats per vertex, written by k_vertex_frames, read by k_assemble_tris
+    float* bit;
+    float4* tri_pos;          // 3 float4 per triangle
+    float4* tri_attr;         // 9 float4 per triangle
+    uint32_t tri_first;       // the mesh's first triangle in them
+    uint32_t n_tris;          // their length
+};
+
+// one thread per vertex: the tangent and bitangent of the vertex from the faces that name it, in table order (spt_mesh_assemble.h)
+__global__ void k_vertex_frames(AssembleMesh a);
+// one thread per triangle k of the mesh's range: the two records of face face_of_tri[k] into tri_pos / tri_attr[tri_first + k]
+__global__ void k_assemble_tris(AssembleMesh a);
+
 constexpr uint8_t kRefitUnknown = 255;   // a node whose height is not known yet (k_refit_heights)
 
 // One mesh of one spt_scene_deform call, as its kernels see it

@@ -1278,6 +1278,22 @@ std::vector<RefitBox> deform_fixed_n4(SceneFixed& fx, uint32_t n_meshes, const s
     return roots;
 }
 
+std::vector<RefitBox> deform_fixed_n4_raw(SceneFixed& fx, uint32_t n_meshes, const uint32_t* mesh_ids, const RefitBox* raw) {
+    std::vector<RefitBox> roots(n_meshes);
+    for (uint32_t i = 0; i < n_meshes; ++i) {
+        const uint32_t mesh = mesh_ids[i];
+        for (int k = 0; k < 3; ++k) { fx.mesh_box[mesh][k] = (double)raw[i].lo[k]; fx.mesh_box[mesh][3 + k] = (double)raw[i].hi[k]; }
+        const RefitBox box = refit_padded(raw[i]);
+        for (int k = 0; k < 3; ++k)
+            if (refit_exponent(box.hi[k] - box.lo[k]) > 120) fail(SPT_ERR_UNSUPPORTED, "scene_deform_vertices: node extent too large to quantise");
+        uint32_t root_ref;
+        std::memcpy(&root_ref, &fx.mesh_rec[2 * mesh].w, 4);
+        set_mesh_record(fx, mesh, box.lo, box.hi, root_ref);
+        roots[i] = box;
+    }
+    return roots;
+}
+
 void deform_fixed_lds(SceneFixed& fx, std::vector<std::pair<uint32_t, uint32_t>>& blas_range, uint32_t n_meshes, const spt_mesh_deform* meshes,
                       const BuildOptions& opt) {
     if (blas_range.size() != fx.n_meshes) fail(SPT_ERR_UNSUPPORTED, "scene_deform: the scene keeps no node range per mesh");

@@ -145,6 +145,8 @@ void validate_deform(const SceneFixed& fx, uint32_t n_meshes, const spt_mesh_def
 // Large-scene form: what the host keeps of a named mesh - its object-space box and its record with pad(bounds of the whole
 // mesh), which contains every box the refit kernels make (scene_refit.h).  Returns that box per named mesh.
 std::vector<RefitBox> deform_fixed_n4(SceneFixed& fx, uint32_t n_meshes, const spt_mesh_deform* meshes);
+// The same from the raw bounds of the named meshes' vertices (spt_scene_deform_vertices, whose records are made on the device)
+std::vector<RefitBox> deform_fixed_n4_raw(SceneFixed& fx, uint32_t n_meshes, const uint32_t* mesh_ids, const RefitBox* raw);
 // LDS-resident form: the named meshes' static sections built again with the creation's functions (binned-SAH tree, wide nodes,
 // leaf-order triangles, attributes, record, box, depth), the other meshes' nodes moved to where they now start.
 void deform_fixed_lds(SceneFixed& fx, std::vector<std::pair<uint32_t, uint32_t>>& blas_range, uint32_t n_meshes, const spt_mesh_deform* meshes,

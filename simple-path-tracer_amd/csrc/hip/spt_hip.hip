@@ -139,6 +139,9 @@ struct BezierLib {
     decltype(&spt_radiance) radiance = nullptr;
     decltype(&spt_scene_update) scene_update = nullptr;   // (resolved if present, like film_filter)
     decltype(&spt_scene_deform) scene_deform = nullptr;   // (the same)
+    decltype(&spt_scene_mesh_topology) scene_mesh_topology = nullptr;       // (the same)
+    decltype(&spt_scene_deform_vertices) scene_deform_vertices = nullptr;   // (the same)
+    decltype(&spt_scene_read_triangles) scene_read_triangles = nullptr;     // (the same)
     decltype(&spt_debug_bxdf) debug_bxdf = nullptr;
     decltype(&spt_debug_render_info) debug_render_info = nullptr;
     decltype(&spt_last_error) last_error = nullptr;
@@ -253,6 +256,16 @@ struct spt_scene {
     std::vector<uint8_t> refit_heights_known;
     hipEvent_t ev_deform[2] = {nullptr, nullptr};   // around the copies and kernels of the last call that named meshes (counter 6)
     bool deform_timed = false;
+    // spt_scene_mesh_topology: per mesh its registration (null: none) - the host copy the checks and an LDS-resident scene's
+    // host assembly read, and the device arrays the kernels of inst_assemble.hip read and write
+    struct MeshTopology {
+        uint32_t n_vertices = 0, tri_count = 0;
+        std::vector<uint32_t> indices, face_of_tri, corner_first, corners;
+        std::vector<uint8_t> named;       // per vertex: some face names it (an empty row of the table; the bounds pass reads it)
+        std::vector<float> uv, normals;   // normals: the ones in force (the registration's, then the last ones a deformation gave)
+        DeviceBuffer d_indices, d_face_of_tri, d_corner_first, d_corners, d_uv, d_normals, d_positions, d_tan, d_bit;
+    };
+    std::vector<std::unique_ptr<MeshTopology>> topology;
     ~spt_scene() {
         if (fwd) { fwd->destroy(inner); return; }
         (void)hipSetDevice(device);
@@ -458,6 +471,9 @@ const BezierLib* bezier_lib() {
         (void)sym(lib.film_filter, "spt_film_filter");
         (void)sym(lib.scene_update, "spt_scene_update");
         (void)sym(lib.scene_deform, "spt_scene_deform");
+        (void)sym(lib.scene_mesh_topology, "spt_scene_mesh_topology");
+        (void)sym(lib.scene_deform_vertices, "spt_scene_deform_vertices");
+        (void)sym(lib.scene_read_triangles, "spt_scene_read_triangles");
         if (!all || version() != SPT_ABI_VERSION) {
             err = path + " does not export ABI version " + std::to_string(SPT_ABI_VERSION);
             return;
@@ -1768,7 +1784,17 @@ float* direct_destination(const spt_render_params& p, uint32_t own_rows, uint32_
 // call queues the triangles' copies and the refit kernels (deform_kernels.h) in front of the dynamic sections' copies; an
 // LDS-resident scene's blob is written whole as by any update.  Nothing of the scene is touched before the first copy is queued,
 // so a refused call leaves it as it was.
-spt_status update_locked(spt_scene* sc, const spt_scene_update_desc* u, uint32_t n_meshes, const spt_mesh_deform* meshes, const char* who) {
+// spt_scene_deform_vertices on a large scene: one named mesh, checked by the caller (vertices_locked) - what goes up instead of
+// records, and the raw bounds of the vertices some face names
+struct VertexEdit {
+    uint32_t mesh;
+    const float* positions;
+    const float* normals;   // or null: the ones on the device stay
+    RefitBox raw;
+};
+
+spt_status update_locked(spt_scene* sc, const spt_scene_update_desc* u, uint32_t n_meshes, const spt_mesh_deform* meshes, const char* who,
+                         const VertexEdit* verts = nullptr) {
     const std::string w(who);
     return guarded(who, [&] {
         const BuildOptions opt = build_options();
@@ -1778,14 +1804,19 @@ spt_status update_locked(spt_scene* sc, const spt_scene_update_desc* u, uint32_t
         if (u->n_lights != sc->fixed.n_lights) fail(SPT_ERR_INVALID_ARG, w + ": n_lights differs from the scene's");
         if ((u->n_tlas_nodes && !u->tlas_nodes) || (u->n_instances && !u->instances) || (u->n_lights && !u->lights)) fail(SPT_ERR_INVALID_ARG, w + ": null array");
         if (u->n_instances && sc->fixed.aggregate == SPT_AGGREGATE_BVH && u->n_tlas_nodes == 0) fail(SPT_ERR_INVALID_ARG, w + ": bvh aggregate without TLAS nodes");
-        validate_deform(sc->fixed, n_meshes, meshes);
+        if (!verts) validate_deform(sc->fixed, n_meshes, meshes);
         // a deformation: the fixed part with the named meshes made again, committed with the rest
         SceneFixed deformed;
         std::vector<std::pair<uint32_t, uint32_t>> blas_range = sc->blas_range;
         std::vector<RefitBox> root_box;
         if (n_meshes) {
             deformed = sc->fixed;
-            if (deformed.n4) root_box = deform_fixed_n4(deformed, n_meshes, meshes);
+            if (verts) {
+                std::vector<uint32_t> ids(n_meshes);
+                std::vector<RefitBox> raw(n_meshes);
+                for (uint32_t i = 0; i < n_meshes; ++i) { ids[i] = verts[i].mesh; raw[i] = verts[i].raw; }
+                root_box = deform_fixed_n4_raw(deformed, n_meshes, ids.data(), raw.data());
+            } else if (deformed.n4) root_box = deform_fixed_n4(deformed, n_meshes, meshes);
             else deform_fixed_lds(deformed, blas_range, n_meshes, meshes, opt);
         }
         const SceneFixed& fx = n_meshes ? deformed : sc->fixed;
@@ -1813,7 +1844,12 @@ spt_status update_locked(spt_scene* sc, const spt_scene_update_desc* u, uint32_t
             parts.push_back(Part{dst, src, bytes, total});
             total += (bytes + 15) / 16 * 16;
         };
-        for (uint32_t i = 0; i < n_meshes; ++i) {   // the ABI-order arrays the shade kernels (and the refit kernels) read
+        for (uint32_t i = 0; verts && i < n_meshes; ++i) {   // the vertex arrays the kernels of inst_assemble.hip make those records from
+            spt_scene::MeshTopology& tp = *sc->topology[verts[i].mesh];
+            part(tp.d_positions.p, verts[i].positions, (size_t)tp.n_vertices * 3 * sizeof(float));
+            if (verts[i].normals) part(tp.d_normals.p, verts[i].normals, (size_t)tp.n_vertices * 3 * sizeof(float));
+        }
+        for (uint32_t i = 0; !verts && i < n_meshes; ++i) {   // the ABI-order arrays the shade kernels (and the refit kernels) read
             const spt_mesh_deform& e = meshes[i];
             part(sc->tri_pos.as<spt_tri_pos>() + fx.mesh_first[e.mesh], e.tri_pos, (size_t)e.tri_count * sizeof(spt_tri_pos));
             if (e.tri_attr) part(sc->tri_attr.as<spt_tri_attr>() + fx.mesh_first[e.mesh], e.tri_attr, (size_t)e.tri_count * sizeof(spt_tri_attr));
@@ -1867,7 +1903,20 @@ spt_status update_locked(spt_scene* sc, const spt_scene_update_desc* u, uint32_t
         if (n_meshes) HIP_CHECK(hipEventRecord(sc->ev_deform[0], sc->stream));
         for (size_t k = 0; k < geometry_parts; ++k) queue_copy(parts[k]);
         for (uint32_t i = 0; refit && i < n_meshes; ++i) {
-            const uint32_t mesh = meshes[i].mesh;
+            const uint32_t mesh = verts ? verts[i].mesh : meshes[i].mesh;
+            if (verts) {   // the mesh's records from the vertex arrays the copies above brought, where k_deform_tris reads them
+                const spt_scene::MeshTopology& tp = *sc->topology[mesh];
+                AssembleMesh am{};
+                am.m.n_vertices = tp.n_vertices; am.m.tri_count = tp.tri_count;
+                am.m.indices = tp.d_indices.as<uint32_t>(); am.m.face_of_tri = tp.d_face_of_tri.as<uint32_t>();
+                am.m.corner_first = tp.d_corner_first.as<uint32_t>(); am.m.corners = tp.d_corners.as<uint32_t>();
+                am.m.uv = tp.d_uv.as<float>(); am.m.positions = tp.d_positions.as<float>(); am.m.normals = tp.d_normals.as<float>();
+                am.tan = tp.d_tan.as<float>(); am.bit = tp.d_bit.as<float>();
+                am.tri_pos = sc->tri_pos.as<float4>(); am.tri_attr = sc->tri_attr.as<float4>();
+                am.tri_first = fx.mesh_first[mesh]; am.n_tris = fx.n_tris;
+                hipLaunchKernelGGL(k_vertex_frames, dim3((tp.n_vertices + kBlock - 1u) / kBlock), dim3(kBlock), 0, sc->stream, am);
+                hipLaunchKernelGGL(k_assemble_tris, dim3((tp.tri_count + kBlock - 1u) / kBlock), dim3(kBlock), 0, sc->stream, am);
+            }
             DeformMesh dm{};
             dm.geo = sc->geo.as<float4>();
             dm.tri_pos = sc->tri_pos.as<float4>();
@@ -1911,9 +1960,169 @@ spt_status update_locked(spt_scene* sc, const spt_scene_update_desc* u, uint32_t
     });
 }
 
+// spt_scene_mesh_topology under the scene's lock: the checks, the vertex -> corner table, the synchronous uploads.  The new
+// registration replaces the old one only when all of it stands.
+spt_status topology_locked(spt_scene* sc, const spt_mesh_topology* t) {
+    return guarded("scene_mesh_topology", [&] {
+        const SceneFixed& fx = sc->fixed;
+        if (!fx.own_bvh) fail(SPT_ERR_UNSUPPORTED, "scene_mesh_topology: the scene walks the caller's trees (SPT_REFERENCE_BVH): the library owns none to refit");
+        if (t->mesh >= fx.n_meshes) fail(SPT_ERR_INVALID_ARG, "scene_mesh_topology: mesh index out of range");
+        if (t->tri_count == 0u || t->tri_count != fx.mesh_tris[t->mesh]) fail(SPT_ERR_INVALID_ARG, "scene_mesh_topology: tri_count differs from the mesh's");
+        if (t->n_vertices == 0u || !t->indices || !t->uv || !t->normals) fail(SPT_ERR_INVALID_ARG, "scene_mesh_topology: null array");
+        if ((uint64_t)fx.mesh_first[t->mesh] + t->tri_count > fx.n_tris) fail(SPT_ERR_INVALID_ARG, "scene_mesh_topology: the mesh's range leaves the scene's triangles");
+        const size_t nv = t->n_vertices, nt = t->tri_count;
+        for (size_t i = 0; i < 3 * nt; ++i)
+            if (t->indices[i] >= t->n_vertices) fail(SPT_ERR_INVALID_ARG, "scene_mesh_topology: a vertex index is out of range");
+        for (size_t i = 0; i < 2 * nv; ++i)
+            if (!std::isfinite(t->uv[i])) fail(SPT_ERR_INVALID_ARG, "scene_mesh_topology: a texture coordinate is not finite");
+        for (size_t i = 0; i < 3 * nv; ++i)
+            if (!std::isfinite(t->normals[i])) fail(SPT_ERR_INVALID_ARG, "scene_mesh_topology: a normal is not finite");
+        auto tp = std::make_unique<spt_scene::MeshTopology>();
+        tp->n_vertices = t->n_vertices;
+        tp->tri_count = t->tri_count;
+        tp->face_of_tri.resize(nt);
+        std::vector<uint8_t> seen(nt, 0);
+        for (size_t k = 0; k < nt; ++k) {
+            const uint32_t face = t->face_of_tri ? t->face_of_tri[k] : (uint32_t)k;
+            if (face >= t->tri_count || seen[face]++) fail(SPT_ERR_INVALID_ARG, "scene_mesh_topology: face_of_tri is no permutation of the faces");
+            tp->face_of_tri[k] = face;
+        }
+        tp->indices.assign(t->indices, t->indices + 3 * nt);
+        tp->uv.assign(t->uv, t->uv + 2 * nv);
+        tp->normals.assign(t->normals, t->normals + 3 * nv);
+        // the corners that name a vertex, in increasing (face, corner) order: the order calc_tangents adds them in
+        tp->corner_first.assign(nv + 1, 0u);
+        for (size_t i = 0; i < 3 * nt; ++i) ++tp->corner_first[tp->indices[i] + 1u];
+        tp->named.resize(nv);
+        for (size_t v = 0; v < nv; ++v) {
+            tp->named[v] = tp->corner_first[v + 1] != 0u;
+            tp->corner_first[v + 1] += tp->corner_first[v];
+        }
+        tp->corners.resize(3 * nt);
+        std::vector<uint32_t> at(tp->corner_first.begin(), tp->corner_first.end() - 1);
+        for (size_t i = 0; i < 3 * nt; ++i) tp->corners[at[tp->indices[i]]++] = (uint32_t)i;
+        HIP_CHECK(hipSetDevice(sc->device));
+        tp->d_indices.upload(tp->indices.data(), tp->indices.size());
+        tp->d_face_of_tri.upload(tp->face_of_tri.data(), tp->face_of_tri.size());
+        tp->d_corner_first.upload(tp->corner_first.data(), tp->corner_first.size());
+        tp->d_corners.upload(tp->corners.data(), tp->corners.size());
+        tp->d_uv.upload(tp->uv.data(), tp->uv.size());
+        tp->d_normals.upload(tp->normals.data(), tp->normals.size());
+        tp->d_positions.alloc(3 * nv * sizeof(float));
+        tp->d_tan.alloc(3 * nv * sizeof(float));
+        tp->d_bit.alloc(3 * nv * sizeof(float));
+        if (sc->topology.size() != fx.n_meshes) sc->topology.resize(fx.n_meshes);
+        // (the old registration's arrays: freeing them waits for the kernels of a deformation still in flight)
+        sc->topology[t->mesh] = std::move(tp);
+        return SPT_OK;
+    });
+}
+
+// spt_scene_deform_vertices under the scene's lock: its own checks, with the bounds of the face-named vertices taken in the same
+// pass, then update_locked - on a large scene with the vertex arrays in place of records, on an LDS-resident one with records
+// made here, with the kernels' functions.
+spt_status vertices_locked(spt_scene* sc, const spt_scene_update_desc* u, uint32_t n_meshes, const spt_mesh_vertices* meshes) {
+    const char* who = "scene_deform_vertices";
+    return guarded(who, [&]() -> spt_status {
+        const SceneFixed& fx = sc->fixed;
+        if (n_meshes == 0u) return update_locked(sc, u, 0u, nullptr, who);
+        if (!meshes) fail(SPT_ERR_INVALID_ARG, "scene_deform_vertices: null array");
+        if (!fx.own_bvh) fail(SPT_ERR_UNSUPPORTED, "scene_deform_vertices: the scene walks the caller's trees (SPT_REFERENCE_BVH): the library owns none to refit");
+        std::vector<uint8_t> named(fx.n_meshes, 0);
+        std::vector<VertexEdit> edits(n_meshes);
+        for (uint32_t i = 0; i < n_meshes; ++i) {
+            const spt_mesh_vertices& e = meshes[i];
+            if (e.mesh >= fx.n_meshes) fail(SPT_ERR_INVALID_ARG, "scene_deform_vertices: mesh index out of range");
+            if (named[e.mesh]++) fail(SPT_ERR_INVALID_ARG, "scene_deform_vertices: a mesh is named twice");
+            if (e.mesh >= sc->topology.size() || !sc->topology[e.mesh]) fail(SPT_ERR_INVALID_ARG, "scene_deform_vertices: the mesh has no registered topology (spt_scene_mesh_topology)");
+            const spt_scene::MeshTopology& tp = *sc->topology[e.mesh];
+            if (e.n_vertices != tp.n_vertices) fail(SPT_ERR_INVALID_ARG, "scene_deform_vertices: n_vertices differs from the registration's");
+            if (!e.positions) fail(SPT_ERR_INVALID_ARG, "scene_deform_vertices: null array");
+            // (min / max of finite values do not depend on the order they are taken in, but for the sign of a zero, which no
+            // padded box keeps: the box deformed_bounds takes over the records)
+            RefitBox raw = refit_empty();
+            for (size_t v = 0; v < tp.n_vertices; ++v) {
+                const float* p = e.positions + 3 * v;
+                bool finite = std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]);
+                if (e.normals) finite = finite && std::isfinite(e.normals[3 * v]) && std::isfinite(e.normals[3 * v + 1]) && std::isfinite(e.normals[3 * v + 2]);
+                if (!finite) fail(SPT_ERR_INVALID_ARG, "scene_deform_vertices: a value is not finite");
+                if (!tp.named[v]) continue;
+                for (int k = 0; k < 3; ++k) { raw.lo[k] = refit_min(raw.lo[k], p[k]); raw.hi[k] = refit_max(raw.hi[k], p[k]); }
+            }
+            edits[i] = VertexEdit{e.mesh, e.positions, e.normals, raw};
+        }
+        if (fx.n4) return update_locked(sc, u, n_meshes, nullptr, who, edits.data());
+        // LDS-resident: the records on the host, by the kernels' schedule - per vertex over the table, then per triangle
+        std::vector<std::vector<spt_tri_pos>> pos(n_meshes);
+        std::vector<std::vector<spt_tri_attr>> attr(n_meshes);
+        std::vector<spt_mesh_deform> recs(n_meshes);
+        for (uint32_t i = 0; i < n_meshes; ++i) {
+            const spt_scene::MeshTopology& tp = *sc->topology[meshes[i].mesh];
+            spt_ma_mesh m{};
+            m.n_vertices = tp.n_vertices; m.tri_count = tp.tri_count;
+            m.indices = tp.indices.data(); m.face_of_tri = tp.face_of_tri.data();
+            m.corner_first = tp.corner_first.data(); m.corners = tp.corners.data();
+            m.uv = tp.uv.data(); m.positions = meshes[i].positions; m.normals = meshes[i].normals ? meshes[i].normals : tp.normals.data();
+            std::vector<float> tan(3 * (size_t)tp.n_vertices), bit(3 * (size_t)tp.n_vertices);
+            for (uint32_t v = 0; v < tp.n_vertices; ++v) spt_ma_vertex_frame(&m, v, &tan[3 * (size_t)v], &bit[3 * (size_t)v]);
+            pos[i].resize(tp.tri_count);
+            attr[i].resize(tp.tri_count);
+            for (uint32_t k = 0; k < tp.tri_count; ++k)
+                if (!spt_ma_triangle(&m, tan.data(), bit.data(), k, &pos[i][k], &attr[i][k])) fail(SPT_ERR_INVALID_ARG, "scene_deform_vertices: the registration is inconsistent");
+            recs[i] = spt_mesh_deform{meshes[i].mesh, tp.tri_count, pos[i].data(), attr[i].data()};
+        }
+        const spt_status st = update_locked(sc, u, n_meshes, recs.data(), who);
+        if (st != SPT_OK) return st;
+        for (uint32_t i = 0; i < n_meshes; ++i)   // the normals now in force
+            if (meshes[i].normals) sc->topology[meshes[i].mesh]->normals.assign(meshes[i].normals, meshes[i].normals + 3 * (size_t)meshes[i].n_vertices);
+        return SPT_OK;
+    });
+}
+
 }  // namespace
 
 extern "C" {
+
+spt_status spt_scene_mesh_topology(spt_scene* sc, const spt_mesh_topology* t) {
+    if (!sc || !t) { g_error = "scene_mesh_topology: null argument"; return SPT_ERR_INVALID_ARG; }
+    if (t->size < sizeof(spt_mesh_topology)) { g_error = "scene_mesh_topology: size is smaller than spt_mesh_topology"; return SPT_ERR_INVALID_ARG; }
+    if (sc->fwd) {
+        if (!sc->fwd->scene_mesh_topology) { g_error = "scene_mesh_topology: libspt_hip_bez.so does not export spt_scene_mesh_topology"; return SPT_ERR_UNSUPPORTED; }
+        return forwarded(sc->fwd, sc->fwd->scene_mesh_topology(sc->inner, t));
+    }
+    std::lock_guard<std::mutex> lock(sc->mu);
+    return topology_locked(sc, t);
+}
+
+spt_status spt_scene_deform_vertices(spt_scene* sc, const spt_scene_update_desc* u, uint32_t n_meshes, const spt_mesh_vertices* meshes) {
+    if (!sc || !u) { g_error = "scene_deform_vertices: null argument"; return SPT_ERR_INVALID_ARG; }
+    if (u->size < sizeof(spt_scene_update_desc)) { g_error = "scene_deform_vertices: size is smaller than spt_scene_update_desc"; return SPT_ERR_INVALID_ARG; }
+    if (sc->fwd) {
+        if (!sc->fwd->scene_deform_vertices) { g_error = "scene_deform_vertices: libspt_hip_bez.so does not export spt_scene_deform_vertices"; return SPT_ERR_UNSUPPORTED; }
+        return forwarded(sc->fwd, sc->fwd->scene_deform_vertices(sc->inner, u, n_meshes, meshes));
+    }
+    std::lock_guard<std::mutex> lock(sc->mu);
+    return vertices_locked(sc, u, n_meshes, meshes);
+}
+
+spt_status spt_scene_read_triangles(const spt_scene* scene_c, uint32_t first, uint32_t count, spt_tri_pos* tri_pos_out, spt_tri_attr* tri_attr_out) {
+    if (!scene_c) { g_error = "scene_read_triangles: null argument"; return SPT_ERR_INVALID_ARG; }
+    spt_scene* sc = const_cast<spt_scene*>(scene_c);
+    if (sc->fwd) {
+        if (!sc->fwd->scene_read_triangles) { g_error = "scene_read_triangles: libspt_hip_bez.so does not export spt_scene_read_triangles"; return SPT_ERR_UNSUPPORTED; }
+        return forwarded(sc->fwd, sc->fwd->scene_read_triangles(sc->inner, first, count, tri_pos_out, tri_attr_out));
+    }
+    std::lock_guard<std::mutex> lock(sc->mu);
+    return guarded("scene_read_triangles", [&] {
+        if ((uint64_t)first + count > sc->fixed.n_tris) fail(SPT_ERR_INVALID_ARG, "scene_read_triangles: the range leaves the scene's triangles");
+        if (count == 0u || (!tri_pos_out && !tri_attr_out)) return SPT_OK;
+        HIP_CHECK(hipSetDevice(sc->device));
+        HIP_CHECK(hipStreamSynchronize(sc->stream));   // behind the copies and kernels of every update queued so far
+        if (tri_pos_out) HIP_CHECK(hipMemcpy(tri_pos_out, sc->tri_pos.as<spt_tri_pos>() + first, (size_t)count * sizeof(spt_tri_pos), hipMemcpyDeviceToHost));
+        if (tri_attr_out) HIP_CHECK(hipMemcpy(tri_attr_out, sc->tri_attr.as<spt_tri_attr>() + first, (size_t)count * sizeof(spt_tri_attr), hipMemcpyDeviceToHost));
+        return SPT_OK;
+    });
+}
 
 spt_status spt_scene_update(spt_scene* sc, const spt_scene_update_desc* u) {
     if (!sc || !u) { g_error = "scene_update: null argument"; return SPT_ERR_INVALID_ARG; }

@@ -93,7 +93,16 @@ spt_status spt_host_load_scene(const char* scene_json_path, spt_host_scene** out
     }
 }
 
-const spt_scene_desc* spt_host_scene_desc(const spt_host_scene* scene) { return scene ? &scene->hs->desc : nullptr; }
+// (the records of meshes spt_host_scene_set_mesh_vertices left pending are made here: a reader of the descriptor sees none missing)
+const spt_scene_desc* spt_host_scene_desc(const spt_host_scene* scene) {
+    if (!scene) return nullptr;
+    try {
+        scene->hs->materialize();
+    } catch (...) {   // (nothing set_mesh_vertices lets through is known to get here)
+        return nullptr;
+    }
+    return &scene->hs->desc;
+}
 
 spt_status spt_host_scene_set_bezier_newton(spt_host_scene* scene, int32_t newton) {
     if (!scene) { set_error("scene_set_bezier_newton: null argument"); return SPT_ERR_INVALID_ARG; }
@@ -143,6 +152,40 @@ spt_status spt_host_scene_mesh_positions(const spt_host_scene* scene, const char
 spt_status spt_host_scene_set_mesh_positions(spt_host_scene* scene, const char* primitive_name, uint32_t n_vertices, const float* positions, const float* normals) {
     if (!scene || !primitive_name || !positions) { set_error("scene_set_mesh_positions: null argument"); return SPT_ERR_INVALID_ARG; }
     return host_guarded("scene_set_mesh_positions", [&] { scene->hs->set_mesh_positions(primitive_name, n_vertices, positions, normals); });
+}
+
+spt_status spt_host_scene_mesh_topology(const spt_host_scene* scene, const char* primitive_name, spt_mesh_topology* out) {
+    if (!scene || !primitive_name || !out) { set_error("scene_mesh_topology: null argument"); return SPT_ERR_INVALID_ARG; }
+    return host_guarded("scene_mesh_topology", [&] {
+        const MeshSource& src = scene->hs->mesh_source(primitive_name);
+        static_assert(sizeof(V3) == 3 * sizeof(float), "MeshSource::nrm is handed out as 3 floats per vertex");
+        std::memset(out, 0, sizeof *out);
+        out->size = (uint32_t)sizeof(spt_mesh_topology);
+        out->mesh = src.mesh;
+        out->n_vertices = (uint32_t)src.pos.size();
+        out->tri_count = (uint32_t)(src.idx.size() / 3);
+        out->indices = src.idx.data();
+        out->face_of_tri = src.order.data();
+        out->uv = src.uv.data();
+        out->normals = &src.nrm.data()->x;
+    });
+}
+
+spt_status spt_host_scene_set_mesh_vertices(spt_host_scene* scene, const char* primitive_name, uint32_t n_vertices, const float* positions, const float* normals) {
+    if (!scene || !primitive_name || !positions) { set_error("scene_set_mesh_vertices: null argument"); return SPT_ERR_INVALID_ARG; }
+    return host_guarded("scene_set_mesh_vertices", [&] { scene->hs->set_mesh_vertices(primitive_name, n_vertices, positions, normals); });
+}
+
+spt_status spt_host_scene_dynamic(const spt_host_scene* scene, spt_scene_update_desc* out) {
+    if (!scene || !out) { set_error("scene_dynamic: null argument"); return SPT_ERR_INVALID_ARG; }
+    const spt_scene_desc& d = scene->hs->desc;   // (no materialize: none of the four arrays depends on a pending mesh's records)
+    std::memset(out, 0, sizeof *out);
+    out->size = (uint32_t)sizeof(spt_scene_update_desc);
+    out->n_tlas_nodes = d.n_tlas_nodes; out->tlas_nodes = d.tlas_nodes;
+    out->n_instances = d.n_instances; out->instances = d.instances;
+    out->n_lights = d.n_lights; out->lights = d.lights;
+    out->light_alias = d.light_alias;
+    return SPT_OK;
 }
 
 spt_status spt_host_animation_load(const char* path, const spt_host_scene* scene, spt_host_animation** out) {

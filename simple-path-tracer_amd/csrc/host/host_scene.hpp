@@ -29,7 +29,22 @@ struct MeshSource {
     std::vector<float> uv;              // 2 per vertex
     std::vector<uint32_t> idx;          // 3 per face
     std::vector<uint32_t> order;        // triangle k of the mesh's range is face order[k]
+    // spt_host_scene_set_mesh_vertices: pos / nrm are newer than the mesh's tri_pos / tri_attr / blas_nodes ranges, which
+    // HostScene::materialize makes from them
+    bool pending = false;
+    std::vector<uint8_t> named;         // per vertex: some face names it (made by the first set_mesh_vertices)
 };
+
+// A mesh as the OBJ loader makes it (single-index vertices), and the loader's two functions over it: the vertex tangents
+// (TriMesh::calc_tangents) and the two records of face t (TriMesh::new).  include/spt_mesh_assemble.h restates them for the device;
+// tests/mesh_assemble_check.cpp compares the two.
+struct ObjMesh {
+    std::vector<V3> pos, nrm, tan, bit;
+    std::vector<float> uv;  // 2 per vertex
+    std::vector<uint32_t> idx;
+};
+void calc_tangents(ObjMesh& m);
+void face_records(const ObjMesh& m, uint32_t t, spt_tri_pos& tp, spt_tri_attr& ta);
 
 struct HostScene {
     std::vector<spt_bvh_node> tlas_nodes, blas_nodes;
@@ -82,6 +97,11 @@ struct HostScene {
     const MeshSource& mesh_source(const std::string& name) const;   // HostError: unknown name, a mesh that cannot be edited
     MeshSource& mesh_source(const std::string& name);
     void set_mesh_positions(const std::string& name, uint32_t n_vertices, const float* positions, const float* normals);   // all or nothing
+    // spt_host_scene_set_mesh_vertices: set_mesh_positions with the mesh's records deferred (MeshSource::pending) unless an
+    // emissive instance needs them; materialize() makes the records of every pending mesh (every reader of tri_pos / tri_attr /
+    // blas_nodes calls it first: spt_host_scene_desc does)
+    void set_mesh_vertices(const std::string& name, uint32_t n_vertices, const float* positions, const float* normals);   // all or nothing
+    void materialize();
 };
 
 HostScene* load_scene_file(const std::string& path);

@@ -215,12 +215,6 @@ float srgb_to_linear(float s) {  // src/texture/srgb_tex.rs
     return std::pow((s + 0.055f) / 1.055f, 2.4f);
 }
 
-struct ObjMesh {
-    std::vector<V3> pos, nrm, tan, bit;
-    std::vector<float> uv;  // 2 per vertex
-    std::vector<uint32_t> idx;
-};
-
 // tobj::load_obj with triangulate + single_index (src/primitive/triangle.rs:57-63):
 // each distinct (v, vt, vn) tuple becomes one vertex in first-seen order; polygons
 // are fanned.  All models of the file are merged into one vertex/index list.
@@ -296,6 +290,9 @@ ObjMesh load_obj(const std::string& path) {
     return m;
 }
 
+}  // namespace
+
+// (the two functions below have external linkage - host_scene.hpp - for tests/mesh_assemble_check.cpp)
 // TriMesh::calc_tangents (src/primitive/triangle.rs:339-388)
 void calc_tangents(ObjMesh& m) {
     size_t nv = m.pos.size();
@@ -336,6 +333,8 @@ void face_records(const ObjMesh& m, uint32_t t, spt_tri_pos& tp, spt_tri_attr& t
         ta.uv[c][0] = m.uv[2 * vi]; ta.uv[c][1] = m.uv[2 * vi + 1];
     }
 }
+
+namespace {
 
 // ---- glTF 2.0 import helpers (role of the `gltf` crate's import(), reference src/loader/gltf.rs:19-20) ----
 std::vector<uint8_t> base64_decode(const std::string& in, const std::string& what) {
@@ -1811,29 +1810,29 @@ MeshSource& HostScene::mesh_source(const std::string& name) {
 // then the two records per face in the triangle order its BLAS build chose), the boxes of its BLAS refitted over the same
 // topology, every instance of it made again under its transform, then the loader's own finalisation.  Everything is made
 // before anything is replaced.
-void HostScene::set_mesh_positions(const std::string& name, uint32_t n_vertices, const float* positions, const float* normals) {
-    MeshSource& src = mesh_source(name);
-    if (n_vertices != src.pos.size()) throw HostError(SPT_ERR_INVALID_ARG, "primitive '" + name + "': " + std::to_string(src.pos.size()) + " vertices are expected");
-    for (size_t i = 0; i < (size_t)n_vertices * 3; ++i)
-        if (!std::isfinite(positions[i]) || (normals && !std::isfinite(normals[i]))) throw HostError(SPT_ERR_INVALID_ARG, "primitive '" + name + "': a value is not finite");
-    ObjMesh m;
-    m.pos.resize(n_vertices);
-    m.nrm = src.nrm;
-    for (uint32_t i = 0; i < n_vertices; ++i) {
-        m.pos[i] = {positions[3 * i], positions[3 * i + 1], positions[3 * i + 2]};
-        if (normals) m.nrm[i] = {normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]};
-    }
-    m.uv = src.uv;
-    m.idx = src.idx;
+namespace {
+struct MeshRanges {
+    std::vector<spt_tri_pos> pos;
+    std::vector<spt_tri_attr> attr;
+    std::vector<spt_bvh_node> nodes;
+};
+// the three ranges of a mesh from its vertices (m: pos, nrm, uv, idx): tangents, records, the boxes of its BLAS
+MeshRanges make_mesh_ranges(const HostScene& hs, const MeshSource& src, ObjMesh& m, const std::string& name) {
+    const uint32_t n_vertices = (uint32_t)m.pos.size();
+    const std::vector<spt_bvh_node>& blas_nodes = hs.blas_nodes;
+    MeshRanges out;
+    std::vector<spt_tri_pos>& new_pos = out.pos;
+    std::vector<spt_tri_attr>& new_attr = out.attr;
+    std::vector<spt_bvh_node>& new_nodes = out.nodes;
     m.tan.assign(n_vertices, V3{1, 0, 0});   // MeshVertex::default, as load_obj leaves them for calc_tangents
     m.bit.assign(n_vertices, V3{0, 1, 0});
     calc_tangents(m);
-    const spt_mesh mesh = meshes[src.mesh];
-    std::vector<spt_tri_pos> new_pos(mesh.tri_count);
-    std::vector<spt_tri_attr> new_attr(mesh.tri_count);
+    const spt_mesh mesh = hs.meshes[src.mesh];
+    new_pos.resize(mesh.tri_count);
+    new_attr.resize(mesh.tri_count);
     for (uint32_t k = 0; k < mesh.tri_count; ++k) face_records(m, src.order[k], new_pos[k], new_attr[k]);
     // the caller-side BLAS: children sit behind their parent (BvhBuilder), so one reverse sweep sees them first
-    std::vector<spt_bvh_node> new_nodes(blas_nodes.begin() + mesh.root, blas_nodes.begin() + mesh.root + mesh.node_count);
+    new_nodes.assign(blas_nodes.begin() + mesh.root, blas_nodes.begin() + mesh.root + mesh.node_count);
     for (uint32_t j = mesh.node_count; j-- > 0;) {
         spt_bvh_node& nd = new_nodes[j];
         Box b;
@@ -1854,6 +1853,29 @@ void HostScene::set_mesh_positions(const std::string& name, uint32_t n_vertices,
         nd.bmin[0] = b.lo.x; nd.bmin[1] = b.lo.y; nd.bmin[2] = b.lo.z;
         nd.bmax[0] = b.hi.x; nd.bmax[1] = b.hi.y; nd.bmax[2] = b.hi.z;
     }
+    return out;
+}
+}  // namespace
+
+void HostScene::set_mesh_positions(const std::string& name, uint32_t n_vertices, const float* positions, const float* normals) {
+    MeshSource& src = mesh_source(name);
+    if (n_vertices != src.pos.size()) throw HostError(SPT_ERR_INVALID_ARG, "primitive '" + name + "': " + std::to_string(src.pos.size()) + " vertices are expected");
+    for (size_t i = 0; i < (size_t)n_vertices * 3; ++i)
+        if (!std::isfinite(positions[i]) || (normals && !std::isfinite(normals[i]))) throw HostError(SPT_ERR_INVALID_ARG, "primitive '" + name + "': a value is not finite");
+    ObjMesh m;
+    m.pos.resize(n_vertices);
+    m.nrm = src.nrm;
+    for (uint32_t i = 0; i < n_vertices; ++i) {
+        m.pos[i] = {positions[3 * i], positions[3 * i + 1], positions[3 * i + 2]};
+        if (normals) m.nrm[i] = {normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]};
+    }
+    m.uv = src.uv;
+    m.idx = src.idx;
+    const spt_mesh mesh = meshes[src.mesh];
+    MeshRanges made_ranges = make_mesh_ranges(*this, src, m, name);
+    const std::vector<spt_tri_pos>& new_pos = made_ranges.pos;
+    const std::vector<spt_tri_attr>& new_attr = made_ranges.attr;
+    const std::vector<spt_bvh_node>& new_nodes = made_ranges.nodes;
     Box root_box;
     root_box.lo = {new_nodes[0].bmin[0], new_nodes[0].bmin[1], new_nodes[0].bmin[2]};
     root_box.hi = {new_nodes[0].bmax[0], new_nodes[0].bmax[1], new_nodes[0].bmax[2]};
@@ -1888,7 +1910,73 @@ void HostScene::set_mesh_positions(const std::string& name, uint32_t n_vertices,
         throw;
     }
     src.pos = std::move(m.pos);
-    src.nrm = std::move(m.nrm);
+    std::copy(m.nrm.begin(), m.nrm.end(), src.nrm.begin());   // (in place: spt_host_scene_mesh_topology hands the array out)
+    src.pending = false;  // (a mesh spt_host_scene_set_mesh_vertices left pending: superseded)
+}
+
+// spt_host_scene_set_mesh_vertices: set_mesh_positions without the mesh's three ranges.  Their only reader on this path is a
+// shape light's area (instance_area), so a mesh with an emissive instance takes set_mesh_positions whole; for every other mesh
+// the root box - all the instances, the TLAS and the lights need of it - is the min / max over the vertices some face names.
+void HostScene::set_mesh_vertices(const std::string& name, uint32_t n_vertices, const float* positions, const float* normals) {
+    MeshSource& src = mesh_source(name);
+    for (auto& kv : inst_recs) {
+        const spt_instance& in = kv.second.inst;
+        if (in.prim_type != SPT_PRIM_MESH || in.prim_id != src.mesh) continue;
+        const spt_surface& sfc = surfaces[in.surface];
+        if (luminance(V3{sfc.emissive[0], sfc.emissive[1], sfc.emissive[2]}) > 0.0f) {
+            set_mesh_positions(name, n_vertices, positions, normals);
+            return;
+        }
+    }
+    if (n_vertices != src.pos.size()) throw HostError(SPT_ERR_INVALID_ARG, "primitive '" + name + "': " + std::to_string(src.pos.size()) + " vertices are expected");
+    for (size_t i = 0; i < (size_t)n_vertices * 3; ++i)
+        if (!std::isfinite(positions[i]) || (normals && !std::isfinite(normals[i]))) throw HostError(SPT_ERR_INVALID_ARG, "primitive '" + name + "': a value is not finite");
+    if (src.named.empty()) {
+        src.named.assign(n_vertices, 0);
+        for (uint32_t i : src.idx) src.named[i] = 1;
+    }
+    Box root_box;
+    for (uint32_t i = 0; i < n_vertices; ++i)
+        if (src.named[i]) root_box.grow(V3{positions[3 * i], positions[3 * i + 1], positions[3 * i + 2]});
+    std::vector<std::pair<InstRec*, InstRec>> made;
+    for (auto& kv : inst_recs) {
+        const InstRec& old = kv.second;
+        if (old.inst.prim_type != SPT_PRIM_MESH || old.inst.prim_id != src.mesh) continue;
+        InstRec rec = make_instance_rec(old.name, old.trans, old.inst.prim_type, old.inst.prim_id, root_box, old.inst.surface);
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(rec.inst.bmin[k]) || !std::isfinite(rec.inst.bmax[k]) || std::fabs(rec.inst.bmin[k]) >= 3.0e38f || std::fabs(rec.inst.bmax[k]) >= 3.0e38f)
+                throw HostError(SPT_ERR_INVALID_ARG, "primitive '" + name + "': the box of instance '" + old.name + "' is not finite");
+        made.emplace_back(&kv.second, std::move(rec));
+    }
+    std::vector<InstRec> saved;
+    for (auto& mk : made) { saved.push_back(*mk.first); *mk.first = std::move(mk.second); }
+    try {
+        finalize_dynamic();
+    } catch (...) {
+        for (size_t i = 0; i < made.size(); ++i) *made[i].first = saved[i];
+        finalize_dynamic();
+        throw;
+    }
+    for (uint32_t i = 0; i < n_vertices; ++i) {
+        src.pos[i] = {positions[3 * i], positions[3 * i + 1], positions[3 * i + 2]};
+        if (normals) src.nrm[i] = {normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]};
+    }
+    src.pending = true;
+}
+
+void HostScene::materialize() {
+    for (auto& kv : mesh_sources) {
+        MeshSource& src = kv.second;
+        if (!src.pending) continue;
+        ObjMesh m;
+        m.pos = src.pos; m.nrm = src.nrm; m.uv = src.uv; m.idx = src.idx;
+        const MeshRanges r = make_mesh_ranges(*this, src, m, kv.first);
+        const spt_mesh mesh = meshes[src.mesh];
+        std::copy(r.pos.begin(), r.pos.end(), tri_pos.begin() + mesh.tri_first);
+        std::copy(r.attr.begin(), r.attr.end(), tri_attr.begin() + mesh.tri_first);
+        std::copy(r.nodes.begin(), r.nodes.end(), blas_nodes.begin() + mesh.root);
+        src.pending = false;
+    }
 }
 
 // `spt --animate FILE`: {"frames": [ {"<instance name>": {matrix / scale / rotate / translate as in the scene file}, ...}, ... ]}

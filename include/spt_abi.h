@@ -902,6 +902,9 @@ spt_status spt_debug_bxdf(const spt_scene* scene, int32_t device, const spt_mate
  *   what 6  ns the copies and kernels of the last spt_scene_deform that named a mesh took on the device (0: none yet); waits for
  *           them (a library without spt_scene_deform refuses 6).  Like every counter here a debug seam for the measuring tools
  *           (tools/scene_deform_cost.py), not part of what spt_scene_deform promises: it may change without an ABI version
+ *   what 7  passes whose bounce launches ran on the scene's second stream beside the next pass's camera rays (the pass pipeline
+ *           of an overlapped render of a fused plan; none with SPT_NO_PASS_PIPELINE=1).  Such a pass is resolved on the film
+ *           stream and counts under 0 as well (a library without the pipeline refuses 7)
  * spt_scene_deform and spt_scene_deform_vertices count as an update in 4 and report their bytes in 5 (and their device time in 6). */
 spt_status spt_debug_render_info(const spt_scene* scene, uint32_t what, uint64_t* out);
 

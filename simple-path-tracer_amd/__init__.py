@@ -930,7 +930,8 @@ class DeviceScene:
         2 the ns the kernels of the last read-out of a sample-keeping film of the scene took on the device; 3 frames whose
         finish kernel stored the image into the (page-locked) output buffer itself, without the runtime's copy; 4 the
         spt_scene_update / spt_scene_deform calls applied to the scene; 5 the bytes the last of them copied to the device; 6 the
-        ns the copies and kernels of the last spt_scene_deform that named a mesh took on the device (waits for them)."""
+        ns the copies and kernels of the last spt_scene_deform that named a mesh took on the device (waits for them); 7 passes whose
+        bounce launches ran on the second stream beside the next pass's camera rays (the pass pipeline; counted under 0 too)."""
         v = C.c_uint64(0)
         _check_hip(hip_lib().spt_debug_render_info(self._h, what, C.byref(v)))
         return int(v.value)

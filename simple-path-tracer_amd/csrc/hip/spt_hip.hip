@@ -153,7 +153,7 @@ struct spt_scene {
     spt_scene* inner = nullptr;
     int device = 0;
     hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr;            // side stream: k_shadow(b) next to k_extend(b) (see bounce)
+    hipStream_t stream2 = nullptr;            // side stream: k_shadow(b) next to k_extend(b) (see bounce); a fused plan's pass pipeline: its bounce launches (trace_window)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     // SPT_RENDER_ASYNC: the film stream.  It carries the film's D2H copy next to the following render's kernels and, on the
     // overlapped schedule (trace_window), the tail-loop shade launch, the resolve and the finish kernel of every pass next
@@ -169,7 +169,13 @@ struct spt_scene {
     int tail_set = -1;                        // >= 0: ev_film[tail_set] covers a tail-loop launch that may still read qb / hit_*_next
     bool film_pending = false;                // the main stream is not yet behind the film-stream kernels of an overlapped render (film_join)
     bool film_inflight = false;               // ... and the host has not waited for them since (grow)
+    // the pass pipeline (trace_window): the bounce launches of a pass on stream2 beside the next pass's k_primary on the main stream.  ev_prim[k]: "the
+    // main stream has traced the camera rays of the pass in set k"; ev_shade_idle: everything queued on stream2 so far (shade_join)
+    hipEvent_t ev_prim[2] = {nullptr, nullptr}, ev_shade_idle = nullptr;
+    bool shade_pending = false;               // the main stream is not yet behind the shade stage of a pipelined render (shade_join)
+    int ov_mode = 0;                          // the schedule of the overlapped passes still in flight: 1 two streams, 2 the pass pipeline (0: none yet)
     uint64_t passes_film = 0, passes_single = 0;   // spt_debug_render_info: passes resolved on the film stream / on the main stream
+    uint64_t passes_pipe = 0;                      // ... and passes whose shade stage ran on stream2 (counted under passes_film too)
     uint64_t frames_direct = 0;                    // ... and frames whose finish kernel stored into the caller's buffer (no copy-out)
     // ... and what the kernels of a sample-keeping film's last read-out (k_film_filter_box, k_film_filter_weighted) took on the device, in ns, between the
     // two events below (made by the first such film)
@@ -187,8 +193,13 @@ struct spt_scene {
     size_t lds_bytes = 0;   // dynamic LDS per 256-thread block: traversal stack (+ geometry)
     // render workspace (grown on demand, reused between calls)
     // (counts, rad, first_slot, slot_bits: what the film stream reads of pass p while the main stream writes pass p + 1; set 1
-    //  is made by the first overlapped render)
+    //  of these four is made by the first overlapped render, or with set 1 of the queues, below: already by the first spt_render of a fused plan)
     DeviceBuffer qa[5], qb[5], hit_f4, hit_inst, hit_f4_next, hit_inst_next, sh[3], counts[2], rad[2], film, first_slot[2], slot_bits[2], out;
+    // the pass pipeline's set 1 of the path and hit queues of a fused plan (set 0: the buffers above), made by the first spt_render of such a plan:
+    // k_primary of pass p + 1 fills one set while the shade kernels of pass p read and write the other
+    DeviceBuffer qa_1[5], qb_1[5], hit_f4_1, hit_inst_1, hit_f4_next_1, hit_inst_next_1;
+    bool pipe_warm = false;                   // stream2 and the film stream have run a first command (trace_window)
+    uint64_t pipe_refused_bytes = 0;         // != 0: a set of this many bytes was refused (no memory, or the limit): not asked for again at this size or above
     DeviceBuffer trace_in, trace_out, visits, inst_class;
     // spt_denoise_image's workspace, made by its first call and reused: the up to six input images (planar RGB f32) and the
     // page-locked staging buffer they go up through, the records of the a-trous kernels (two colour arrays, guide, albedo), the
@@ -274,7 +285,7 @@ struct spt_scene {
         if (ev_join) (void)hipEventDestroy(ev_join);
         if (ev_out_ready) (void)hipEventDestroy(ev_out_ready);
         if (ev_copy_done) (void)hipEventDestroy(ev_copy_done);
-        for (auto e : {ev_main[0], ev_main[1], ev_film[0], ev_film[1], ev_film_idle, ev_keep[0], ev_keep[1], ev_ray[0], ev_ray[1], ev_upd, ev_deform[0], ev_deform[1]})
+        for (auto e : {ev_main[0], ev_main[1], ev_film[0], ev_film[1], ev_film_idle, ev_prim[0], ev_prim[1], ev_shade_idle, ev_keep[0], ev_keep[1], ev_ray[0], ev_ray[1], ev_upd, ev_deform[0], ev_deform[1]})
             if (e) (void)hipEventDestroy(e);
         if (stream_film) (void)hipStreamDestroy(stream_film);
         if (stream2) (void)hipStreamDestroy(stream2);
@@ -554,7 +565,7 @@ std::unique_ptr<spt_scene> open_device(int32_t device) {
     HIP_CHECK(hipStreamCreateWithFlags(&sc->stream2, hipStreamNonBlocking));
     HIP_CHECK(hipStreamCreateWithFlags(&sc->stream_film, hipStreamNonBlocking));
     for (hipEvent_t* e : {&sc->ev_main[0], &sc->ev_main[1], &sc->ev_film[0], &sc->ev_film[1], &sc->ev_film_idle, &sc->ev_out_ready, &sc->ev_copy_done,
-                          &sc->ev_fork, &sc->ev_join})
+                          &sc->ev_fork, &sc->ev_join, &sc->ev_prim[0], &sc->ev_prim[1], &sc->ev_shade_idle})
         HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
     return sc;
 }
@@ -719,6 +730,7 @@ void spt_scene_destroy(spt_scene* scene) {
     if (!scene) return;
     (void)hipSetDevice(scene->device);
     (void)hipStreamSynchronize(scene->stream);
+    if (scene->stream2) (void)hipStreamSynchronize(scene->stream2);
     if (scene->stream_film) (void)hipStreamSynchronize(scene->stream_film);
     // every DeviceBuffer member frees itself (a list here used to miss the buffers added later)
     delete scene;
@@ -828,6 +840,9 @@ struct RenderRun {
     bool resolve32 = false;      // k_resolve_bits<32u> instead of <16u>
     bool film_stream = false;    // the overlapped schedule is allowed (no SPT_NO_FILM_STREAM)
     bool film_overlap = false;   // ... and this render takes it: tail launch, resolve, finish and copy-out on the film stream
+    bool pass_pipeline = false;  // an overlapped render of a fused plan may run its bounce launches on stream2 (no SPT_NO_PASS_PIPELINE)
+    bool pipe_plan = false;      // ... and this is an spt_render of such a plan: its overlapped form takes the pass pipeline (trace_window)
+    uint64_t pipe_max_bytes = ~0ull;   // ... unless its second queue set would hold more than this (SPT_PASS_PIPELINE_MAX_BYTES)
     bool direct_out = false;     // k_finish_host may store into a pinned rgb_mean_out (no SPT_NO_DIRECT_OUT)
     uint32_t direct_grid = 0;    // ... over this many workgroups at the most (kFinishHostGrid, or SPT_DIRECT_OUT_GRID for A/B runs)
     bool debug_spans = false;    // per-launch HIP-event times on stderr (profile mode)
@@ -931,6 +946,8 @@ void run_setup(RenderRun& run) {
     if (const char* v = std::getenv("SPT_PRIMARY_CHUNKS")) run.primary_chunks = (uint32_t)std::max(1, std::atoi(v));
     run.resolve32 = env_u32("SPT_RESOLVE_BATCH", 16u) == 32u;
     run.film_stream = env_u32("SPT_NO_FILM_STREAM", 0u) == 0u;
+    run.pass_pipeline = env_u32("SPT_NO_PASS_PIPELINE", 0u) == 0u;
+    if (const char* v = std::getenv("SPT_PASS_PIPELINE_MAX_BYTES")) run.pipe_max_bytes = std::strtoull(v, nullptr, 10);
     run.direct_out = env_u32("SPT_NO_DIRECT_OUT", 0u) == 0u;
     run.direct_grid = std::max(1u, env_u32("SPT_DIRECT_OUT_GRID", kFinishHostGrid));
     run.box_band_bytes = 8ull << 30;
@@ -1072,9 +1089,18 @@ RenderCtx plan_ctx(const spt_render_params& p, const spt_camera& cam, uint32_t r
     return rc;
 }
 
+// The main stream waits for whatever a pipelined render left on stream2 (its shade stage reads the scene and the path and hit queues).
+void shade_join(spt_scene* sc) {
+    if (!sc->shade_pending) return;
+    HIP_CHECK(hipEventRecord(sc->ev_shade_idle, sc->stream2));
+    HIP_CHECK(hipStreamWaitEvent(sc->stream, sc->ev_shade_idle, 0));
+    sc->shade_pending = false;
+}
+
 // Every entry point that queues work on sc->stream and is not the overlapped schedule itself starts here: the main stream
-// waits for whatever an overlapped render left on the film stream (the scene's lock is held, its device selected).
+// waits for whatever an overlapped render left on the film stream and on stream2 (the scene's lock is held, its device selected).
 void film_join(spt_scene* sc) {
+    shade_join(sc);
     if (!sc->film_pending) return;
     HIP_CHECK(hipEventRecord(sc->ev_film_idle, sc->stream_film));
     HIP_CHECK(hipStreamWaitEvent(sc->stream, sc->ev_film_idle, 0));
@@ -1089,8 +1115,9 @@ void grow(spt_scene* sc, DeviceBuffer& b, size_t n) {
     if (n <= b.bytes) return;
     if (sc->film_inflight) {
         HIP_CHECK(hipStreamSynchronize(sc->stream));
+        HIP_CHECK(hipStreamSynchronize(sc->stream2));
         HIP_CHECK(hipStreamSynchronize(sc->stream_film));
-        sc->film_inflight = sc->film_pending = sc->copy_pending = false;
+        sc->film_inflight = sc->film_pending = sc->copy_pending = sc->shade_pending = false;
         sc->film_recorded[0] = sc->film_recorded[1] = false;
         sc->tail_set = -1;
     }
@@ -1203,6 +1230,54 @@ bool grow_second_set(spt_scene* sc) {
         (void)hipGetLastError();
         return false;
     }
+    return true;
+}
+
+// Set 1 of the path and hit queues of a fused plan, sized like set 0 (grow_queues) and bound into q: what the pass pipeline needs on top of
+// grow_second_set.  False: no memory for it (the render keeps the two-stream schedule).
+struct QueueSet {
+    PathQueue qa, qb;
+    HitQueue hits, hits_next;
+};
+// max_bytes: the set is refused, as if the device had no memory for it, once it would hold more than this (SPT_PASS_PIPELINE_MAX_BYTES).
+// A refusal frees what the set holds - a part of it is of no use and would be missing for the film, `out` or kept chunks - and is
+// remembered for the size it was refused at (sc->pipe_refused_bytes), so that the frames that follow neither drain the streams
+// nor ask the device again.
+bool grow_pipeline_set(spt_scene* sc, uint64_t max_bytes, QueueSet& q) {
+    std::pair<DeviceBuffer*, const DeviceBuffer*> bufs[14];
+    for (int k = 0; k < 5; ++k) { bufs[2 * k] = {&sc->qa_1[k], &sc->qa[k]}; bufs[2 * k + 1] = {&sc->qb_1[k], &sc->qb[k]}; }
+    bufs[10] = {&sc->hit_f4_1, &sc->hit_f4};
+    bufs[11] = {&sc->hit_inst_1, &sc->hit_inst};
+    bufs[12] = {&sc->hit_f4_next_1, &sc->hit_f4_next};
+    bufs[13] = {&sc->hit_inst_next_1, &sc->hit_inst_next};
+    uint64_t need = 0;
+    for (const auto& b : bufs) need += b.second->bytes;
+    if (sc->pipe_refused_bytes != 0 && need >= sc->pipe_refused_bytes) return false;
+    try {
+        uint64_t held = 0;
+        for (const auto& b : bufs) {
+            held += std::max(b.first->bytes, b.second->bytes);
+            if (held > max_bytes) fail(SPT_ERR_OUT_OF_MEMORY, "render: the second queue set is above SPT_PASS_PIPELINE_MAX_BYTES");
+            grow(sc, *b.first, b.second->bytes);
+        }
+    } catch (const AbiError& e) {
+        if (e.code != SPT_ERR_OUT_OF_MEMORY) throw;
+        (void)hipGetLastError();
+        // (a buffer that had to grow drained the streams first, grow; a set that only failed the limit may still be in use)
+        if (sc->film_inflight) {
+            HIP_CHECK(hipStreamSynchronize(sc->stream));
+            HIP_CHECK(hipStreamSynchronize(sc->stream2));
+            HIP_CHECK(hipStreamSynchronize(sc->stream_film));
+        }
+        for (const auto& b : bufs) b.first->release();
+        sc->pipe_refused_bytes = need;
+        return false;
+    }
+    sc->pipe_refused_bytes = 0;
+    q.qa = PathQueue{sc->qa_1[0].as<float4>(), sc->qa_1[1].as<float4>(), sc->qa_1[2].as<float4>(), sc->qa_1[3].as<float4>(), sc->qa_1[4].as<uint2>()};
+    q.qb = PathQueue{sc->qb_1[0].as<float4>(), sc->qb_1[1].as<float4>(), sc->qb_1[2].as<float4>(), sc->qb_1[3].as<float4>(), sc->qb_1[4].as<uint2>()};
+    q.hits = HitQueue{sc->hit_f4_1.as<float4>(), sc->hit_inst_1.as<uint2>()};
+    q.hits_next = HitQueue{sc->hit_f4_next_1.as<float4>(), sc->hit_inst_next_1.as<uint2>()};
     return true;
 }
 
@@ -1575,7 +1650,38 @@ RenderCtx trace_window(RenderRun& run, uint32_t row_base, uint32_t rows, uint32_
     }
     const bool ov = run.film_overlap;
     const hipStream_t st_film = ov ? sc->stream_film : run.st;
+    // The pass pipeline, for the overlapped renders of a fused plan: a third stage between the two.  The main stream only fills the counters
+    // and traces the camera rays of a pass (ev_prim[set]); stream2 - never the shadow side stream of a fused plan - runs the bounce launches
+    // behind that event (ev_main[set]); the film stream does what it did.  k_primary of pass p + 1 then runs beside the bounce-0 shade kernel
+    // of pass p, and nothing on the main stream waits for the film stream's tail launch any more, because the path and hit queues a pass
+    // writes exist once per set too (grow_pipeline_set): whoever writes a set next is behind ev_film[set].  Without memory for them the
+    // render keeps the two-stream schedule.
+    // The second set is made by a scene's first spt_render of such a plan, synchronous or not (run.pipe_plan): allocating it takes up to
+    // seconds at the headline's size (profiles/r08_experiments.md), which belongs with the first render's workspace growth, not in the first
+    // asynchronous frame behind a synchronous warm-up.  A caller that only ever renders synchronously holds that memory for nothing:
+    // SPT_NO_PASS_PIPELINE=1 or SPT_PASS_PIPELINE_MAX_BYTES is for them.
+    QueueSet q1{};
+    const bool pipe_ready = run.pipe_plan && !collect && tgt.keep == nullptr && grow_pipeline_set(sc, run.pipe_max_bytes, q1);
+    // ... and so does everything else that only a first overlapped frame would do (measured: 30 - 36 ms inside the first frame queued behind a
+    // synchronous warm-up, in most processes): set 1 of the doubled pass buffers, and the first command on stream2 and on the film stream, with
+    // which the runtime makes their hardware queues.  (Nothing has used queue set 1 before pipe_warm is set.)
+    if (pipe_ready) {
+        (void)grow_second_set(sc);
+        if (!sc->pipe_warm && sc->hit_inst_1.bytes >= 4 && sc->hit_f4_1.bytes >= 4) {
+            HIP_CHECK(hipMemsetAsync(sc->hit_inst_1.p, 0, 4, sc->stream2));
+            HIP_CHECK(hipMemsetAsync(sc->hit_f4_1.p, 0, 4, sc->stream_film));
+            HIP_CHECK(hipStreamSynchronize(sc->stream2));
+            HIP_CHECK(hipStreamSynchronize(sc->stream_film));
+            sc->pipe_warm = true;
+        }
+    }
+    const bool pipe = ov && pipe_ready;
+    const QueueSet q0{rc.qa, rc.qb, rc.hits, rc.hits_next};
+    // a switch between the two schedules with passes in flight (SPT_NO_PASS_PIPELINE changed): they order the shared queues differently, so
+    // this render starts behind all of it
+    if (ov && sc->film_pending && sc->ov_mode != (pipe ? 2 : 1)) film_join(sc);
     if (ov) {
+        sc->ov_mode = pipe ? 2 : 1;
         sc->film_pending = sc->film_inflight = true;
         // the film stream starts behind what the main stream holds so far (an earlier single-stream render's use of the film)
         HIP_CHECK(hipEventRecord(sc->ev_main[1], run.st));
@@ -1599,7 +1705,12 @@ RenderCtx trace_window(RenderRun& run, uint32_t row_base, uint32_t rows, uint32_
         if (ov) sc->next_set ^= 1u;
         rc.counts = sc->counts[set].as<uint32_t>();
         rc.first_slot = sc->first_slot[set].as<uint32_t>();
-        // the film stream may still read this set: the pass before the previous one, of this render or an earlier one
+        if (pipe) {
+            const QueueSet& q = set ? q1 : q0;
+            rc.qa = q.qa; rc.qb = q.qb; rc.hits = q.hits; rc.hits_next = q.hits_next;
+        }
+        // the film stream may still read this set: the pass before the previous one, of this render or an earlier one (pipelined: and that
+        // pass's shade stage, which its film stage waited for)
         if (ov && sc->film_recorded[set]) HIP_CHECK(hipStreamWaitEvent(run.st, sc->ev_film[set], 0));
         rc.pass_first = s0;
         rc.pass_samples = std::min(ps.spp_pass, s_end - s0);
@@ -1617,9 +1728,15 @@ RenderCtx trace_window(RenderRun& run, uint32_t row_base, uint32_t rows, uint32_
         run.begin(SPT_K_PRIMARY);
         chunked_any |= primary_pass(run, rc, tgt, live.active_tiles, collect, sc->slot_bits[set].as<uint8_t>());
         run.end();
-        bool handed_over = false;   // the film stream waits for the main stream's part of this pass
+        const hipStream_t st_shade = pipe ? sc->stream2 : run.st;   // the stream of the bounce launches
+        if (pipe) {
+            HIP_CHECK(hipEventRecord(sc->ev_prim[set], run.st));
+            HIP_CHECK(hipStreamWaitEvent(st_shade, sc->ev_prim[set], 0));
+            sc->shade_pending = true;
+        }
+        bool handed_over = false;   // the film stream waits for the main stream's (pipelined: the shade stage's) part of this pass
         auto hand_over = [&] {
-            HIP_CHECK(hipEventRecord(sc->ev_main[set], run.st));
+            HIP_CHECK(hipEventRecord(sc->ev_main[set], st_shade));
             HIP_CHECK(hipStreamWaitEvent(st_film, sc->ev_main[set], 0));
             handed_over = true;
         };
@@ -1634,11 +1751,12 @@ RenderCtx trace_window(RenderRun& run, uint32_t row_base, uint32_t rows, uint32_
             }
             // bounce 0 writes qb / hit_*_next (un-fused: and the shadow queue), which a tail-loop launch still on the film
             // stream reads; the later bounces of a pass without that launch ping-pong through the queues on the main stream
-            if (ov && b == 0u && sc->tail_set >= 0) {
+            // (pipelined: that launch reads its own set's queues, and the bounces ping-pong on stream2)
+            if (ov && !pipe && b == 0u && sc->tail_set >= 0) {
                 HIP_CHECK(hipStreamWaitEvent(run.st, sc->ev_film[sc->tail_set], 0));
                 sc->tail_set = -1;
             }
-            if (bounce(run, rc, b, run.st)) break;
+            if (bounce(run, rc, b, st_shade)) break;
         }
         if (!collect) {
             if (ov && !handed_over) hand_over();
@@ -1649,8 +1767,9 @@ RenderCtx trace_window(RenderRun& run, uint32_t row_base, uint32_t rows, uint32_
             if (ov) {
                 HIP_CHECK(hipEventRecord(sc->ev_film[set], st_film));
                 sc->film_recorded[set] = true;
-                if (tail_on_film) sc->tail_set = (int)set;
+                if (tail_on_film) sc->tail_set = (int)set;   // (pipelined: for spt_scene_update only, the launch reads the scene)
                 ++sc->passes_film;
+                if (pipe) ++sc->passes_pipe;
             }
         }
         if (!ov) ++sc->passes_single;
@@ -1891,10 +2010,12 @@ spt_status update_locked(spt_scene* sc, const spt_scene_update_desc* u, uint32_t
         // Of what an overlapped render leaves on the film stream only a tail-loop launch reads the scene (the resolves, the finish
         // kernel and the copy-out read the render workspace): the copies go behind that launch, as the next frame's bounce 0 would,
         // and the copy-out of the previous frame goes on beside them and beside the next frame's kernels
+        // A pipelined render's bounce launches on stream2 read the scene as well: behind them too.
         if (sc->tail_set >= 0) {
             HIP_CHECK(hipStreamWaitEvent(sc->stream, sc->ev_film[sc->tail_set], 0));
             sc->tail_set = -1;
         }
+        shade_join(sc);
         auto queue_copy = [&](const Part& pt) {
             HIP_CHECK(hipMemcpyAsync(pt.dst, static_cast<const char*>(sc->upd_stage.p) + pt.at, pt.bytes, hipMemcpyHostToDevice, sc->stream));
         };
@@ -2219,6 +2340,7 @@ spt_status spt_render(const spt_scene* scene_c, const spt_camera* cam, const spt
         // an asynchronous frame without a wide box filter takes the overlapped schedule (trace_window); every other render
         // starts behind whatever such a frame left on the film stream
         run.film_overlap = async_out && R <= 0 && run.film_stream;
+        run.pipe_plan = R <= 0 && run.film_stream && run.pass_pipeline && run.fused && !run.albedo;
         if (!run.film_overlap) film_join(sc);
         hipEvent_t ev_total0 = run.get_event(), ev_total1 = run.get_event();
         HIP_CHECK(hipEventRecord(ev_total0, run.st));
@@ -2352,8 +2474,9 @@ spt_status spt_render_wait(const spt_scene* scene_c) {
     return guarded("render_wait", [&] {
         HIP_CHECK(hipSetDevice(sc->device));
         HIP_CHECK(hipStreamSynchronize(sc->stream));
+        HIP_CHECK(hipStreamSynchronize(sc->stream2));
         HIP_CHECK(hipStreamSynchronize(sc->stream_film));
-        sc->copy_pending = sc->film_pending = sc->film_inflight = false;
+        sc->copy_pending = sc->film_pending = sc->film_inflight = sc->shade_pending = false;
         sc->film_recorded[0] = sc->film_recorded[1] = false;
         sc->tail_set = -1;
         return SPT_OK;
@@ -3375,7 +3498,7 @@ spt_status spt_debug_pack_rgb8(int32_t device, uint32_t n, const float* in, uint
 }
 
 spt_status spt_debug_render_info(const spt_scene* scene_c, uint32_t what, uint64_t* out) {
-    if (!scene_c || !out || what > 6u) { g_error = "debug_render_info: null argument or unknown counter"; return SPT_ERR_INVALID_ARG; }
+    if (!scene_c || !out || what > 7u) { g_error = "debug_render_info: null argument or unknown counter"; return SPT_ERR_INVALID_ARG; }
     spt_scene* sc = const_cast<spt_scene*>(scene_c);
     if (sc->fwd) return forwarded(sc->fwd, sc->fwd->debug_render_info(sc->inner, what, out));
     std::lock_guard<std::mutex> lock(sc->mu);
@@ -3391,7 +3514,7 @@ spt_status spt_debug_render_info(const spt_scene* scene_c, uint32_t what, uint64
             return SPT_OK;
         });
     }
-    *out = what == 0u ? sc->passes_film : what == 1u ? sc->passes_single : what == 2u ? sc->keep_read_ns : what == 3u ? sc->frames_direct : what == 4u ? sc->updates : sc->update_bytes;
+    *out = what == 7u ? sc->passes_pipe : what == 0u ? sc->passes_film : what == 1u ? sc->passes_single : what == 2u ? sc->keep_read_ns : what == 3u ? sc->frames_direct : what == 4u ? sc->updates : sc->update_bytes;
     return SPT_OK;
 }
 

@@ -861,6 +861,54 @@ typedef struct spt_radiance_job {
 } spt_radiance_job;
 spt_status spt_radiance(const spt_scene* scene, const spt_radiance_job* job);
 
+/* ---- camera models (additive to ABI v14: detect it by symbol) ---------------------------------------------------------------------
+ * spt_render_camera and spt_film_create_camera are spt_render and spt_film_create with a camera model in the camera's place.  With
+ * SPT_CAMERA_PERSPECTIVE they ARE those two calls (same code path, same words); fields that do not belong to a type are ignored.
+ * A film remembers its model, and every film call keeps its documented meaning on a film of any model.  The pixel offsets, the path's
+ * RNG stream (seed, pixel, plan index) and the draws it has made before trace_ray starts are the pinhole plan's for every model.
+ *
+ * The models (include/spt_camera_models.h is this text as code; the kernel and spt_host_camera_rays of libspt_host.so include it).
+ * All arithmetic is IEEE f32, one rounded operation at a time, no contraction, in the written order.  x, y are the screen point of
+ * pt.rs:269-271 as spt_render computes it, hc = base.half_cot_half_fov, t_min = 0.0001f for every model.
+ *   PERSPECTIVE   o = eye, d = normalize((forward*hc + right*x) + up*y): PerspectiveCamera::generate_ray.
+ *   THIN_LENS     a pinhole behind a thin lens.
+ *     Lens draws: u1, u2 are the first two draws of the stream spt_rng_seed(seed ^ SPT_CAMERA_SEED_SALT, pixel, plan_index), a
+ *       stream of its own; the draws are made whatever the radius.
+ *     Disk map:   a = 2*u1 - 1, b = 2*u2 - 1.  a == 0 && b == 0 gives lx = ly = 0.  |a| > |b| gives r = a, phi = (SPT_PI/4) * (b/a).
+ *       Otherwise r = b, phi = SPT_PI/2 - (SPT_PI/4) * (a/b).  lx = r*spt_cos(phi), ly = r*spt_sin(phi).
+ *     Ray:        ft = focus_distance / hc, made once on the host in f32.  du = (forward*hc + right*x) + up*y, the pinhole's.
+ *       lo_k = (right_k*lx + up_k*ly) * lens_radius.  o = eye + lo.  d = normalize(du*ft - lo).
+ *   ORTHOGRAPHIC  sx = x*view_height, sy = y*view_height.  o_k = eye_k + (right_k*sx + up_k*sy).  d = forward, as given.
+ *   PANORAMA      equirectangular, in the environment map's own axes (environment.rs:128-133); it reads only base.eye.
+ *     ph = (x * aspect_inv) * (2*SPT_PI), with aspect_inv = 1.0f/aspect made once.  th = (0.5f - y) * SPT_PI.  st = spt_sin(th).
+ *     o = eye.  d = normalize((st*spt_sin(ph), spt_cos(th), st*spt_cos(ph))).  Row 0 starts at the +y pole and the image centre
+ *     looks along +z.
+ * normalize(v) = v / sqrt((v.x*v.x + v.y*v.y) + v.z*v.z), a true division per component.  The vertical offset runs upward like the
+ * pinhole's, so the offsets that filters and box read-outs re-derive stay valid.
+ * Auxiliary rays (textured scenes): the same model at (x + aux_dx, y) and (x, y + aux_dy) with the same lens point.
+ *
+ * A non-perspective render takes the single-stream or the film-stream schedule; the pass pipeline, the eye-relative copy, block and
+ * origin candidates, the screen bound and the row spans are derived from a pinhole eye and stay off for it.
+ * Refusals for the three new types leave nothing changed.  SPT_ERR_INVALID_ARG: a null model, size below sizeof(spt_camera_model),
+ * an unknown type, or a parameter of the type outside the ranges below.  SPT_ERR_UNSUPPORTED: SPT_RENDER_COUNT_VISITS;
+ * SPT_RENDER_AOV_ALBEDO (the first-hit albedo kernels read the pinhole's compact records).
+ * SPT_CAMERA_GENERAL=1 in the environment sends perspective renders through the camera-model kernel too (an A/B switch: same film). */
+enum { SPT_CAMERA_PERSPECTIVE = 0, SPT_CAMERA_THIN_LENS = 1, SPT_CAMERA_ORTHOGRAPHIC = 2, SPT_CAMERA_PANORAMA = 3 };
+#define SPT_CAMERA_SEED_SALT 0x4C454E5343414D31ull
+typedef struct spt_camera_model {
+    uint32_t size;          /* sizeof as the caller was compiled; grows at the tail only */
+    uint32_t type;          /* SPT_CAMERA_* */
+    spt_camera base;        /* eye, forward, up, right, half_cot_half_fov: as spt_render takes them */
+    float lens_radius;      /* THIN_LENS: finite, >= 0 */
+    float focus_distance;   /* THIN_LENS: finite, > 0, along base.forward from the eye */
+    float view_height;      /* ORTHOGRAPHIC: finite, > 0, world units the image is high */
+    uint32_t pad;
+} spt_camera_model;
+spt_status spt_render_camera(const spt_scene* scene, const spt_camera_model* model, const spt_render_params* params, float* rgb_mean_out,
+                             spt_render_stats* stats /* may be NULL */);
+spt_status spt_film_create_camera(const spt_scene* scene, const spt_camera_model* model, const spt_render_params* params,
+                                  uint32_t first_sample, uint32_t film_flags, spt_film** out);
+
 /* Page-locked host memory for rgb_mean_out: lets the final device-to-host copy of the film run as one
  * DMA at PCIe rate instead of being staged through the runtime's bounce buffers.  Optional: any host
  * pointer is accepted by spt_render. */
@@ -905,6 +953,8 @@ spt_status spt_debug_bxdf(const spt_scene* scene, int32_t device, const spt_mate
  *   what 7  passes whose bounce launches ran on the scene's second stream beside the next pass's camera rays (the pass pipeline
  *           of an overlapped render of a fused plan; none with SPT_NO_PASS_PIPELINE=1).  Such a pass is resolved on the film
  *           stream and counts under 0 as well (a library without the pipeline refuses 7)
+ *   what 8  passes whose camera rays came from the camera-model kernel (k_primary_cam: a non-perspective model, or any render under
+ *           SPT_CAMERA_GENERAL=1; a library without the kernel refuses 8)
  * spt_scene_deform and spt_scene_deform_vertices count as an update in 4 and report their bytes in 5 (and their device time in 6). */
 spt_status spt_debug_render_info(const spt_scene* scene, uint32_t what, uint64_t* out);
 

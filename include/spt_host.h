@@ -133,6 +133,14 @@ spt_status spt_host_block_candidates(const spt_camera* cam, uint32_t width, uint
                                      uint32_t strip_rows, uint32_t rows, uint32_t block, const float* inv, const float* fwd, uint32_t n_tris,
                                      const float* tri_pos, uint64_t* mask_out);
 
+/* The rays of a camera model (include/spt_abi.h, "camera models"; include/spt_camera_models.h, which the device kernel includes too)
+ * for the samples [first, first + count) of a plan: rays[count][height][width], streams (pixel, plan index), t_min 0.0001f; aux (or
+ * NULL) the auxiliary rays in the same order.  rays == radiance input: spt_radiance over them with the plan's seed and max_depth and
+ * rng_skip = the pixel-offset draws of the plan's sampler (2, recurrence 0) returns the samples a film of the model holds.  All four
+ * model types; SPT_ERR_INVALID_ARG for what spt_render_camera refuses of a model, a bad plan or samples past its spp. */
+spt_status spt_host_camera_rays(const spt_camera_model* model, const spt_render_params* plan, uint32_t first, uint32_t count,
+                                spt_path_ray* rays, spt_ray_aux* aux /* or NULL */);
+
 /* The per-origin-triangle candidate table of include/spt_origin_cand.h on the host, for checking it without a device.  Instance i
  * has the spt_instance matrices inv / fwd (12 floats each) and the normal matrix nrm (9 floats); triangle k (at most 64) belongs
  * to instance tri_instance[k], with tri_pos 9 floats (p0, p1, p2, object space) and tri_nrm its 3 vertex normals; its slot and its

@@ -177,6 +177,52 @@ class Camera(C.Structure):
 
 
 SAMPLER_RANDOM, SAMPLER_JITTERED, SAMPLER_RECURRENCE = 0, 1, 2
+CAMERA_PERSPECTIVE, CAMERA_THIN_LENS, CAMERA_ORTHOGRAPHIC, CAMERA_PANORAMA = 0, 1, 2, 3   # SPT_CAMERA_*
+CAMERA_SEED_SALT = 0x4C454E5343414D31   # SPT_CAMERA_SEED_SALT: the lens draws' stream is (seed ^ salt, pixel, plan index)
+
+
+class CameraModel(C.Structure):
+    """spt_camera_model (include/spt_abi.h, "camera models"): what PathTracer.render / render_shard / progressive take as
+    camera_model=.  `base` is a pinhole Camera (Scene.get_camera); fields that do not belong to a type are ignored."""
+    _fields_ = [("size", C.c_uint32), ("type", C.c_uint32), ("base", Camera), ("lens_radius", C.c_float), ("focus_distance", C.c_float),
+                ("view_height", C.c_float), ("pad", C.c_uint32)]
+
+    @classmethod
+    def _make(cls, kind: int, cam: "Camera", **fields) -> "CameraModel":
+        m = cls()
+        m.size = C.sizeof(cls)
+        m.type = kind
+        C.memmove(C.byref(m.base), C.byref(cam), C.sizeof(Camera))
+        for k, v in fields.items():
+            setattr(m, k, v)
+        return m
+
+    @classmethod
+    def perspective(cls, cam: "Camera") -> "CameraModel":
+        return cls._make(CAMERA_PERSPECTIVE, cam)
+
+    @classmethod
+    def thin_lens(cls, cam: "Camera", lens_radius: float, focus_distance: float) -> "CameraModel":
+        """A pinhole behind a thin lens of `lens_radius`, sharp at `focus_distance` along cam.forward from the eye."""
+        return cls._make(CAMERA_THIN_LENS, cam, lens_radius=lens_radius, focus_distance=focus_distance)
+
+    @classmethod
+    def orthographic(cls, cam: "Camera", view_height: float) -> "CameraModel":
+        """Parallel rays along cam.forward; the image is `view_height` world units high."""
+        return cls._make(CAMERA_ORTHOGRAPHIC, cam, view_height=view_height)
+
+    @classmethod
+    def panorama(cls, eye) -> "CameraModel":
+        """Equirectangular probe at `eye` in the environment map's axes: row 0 at the +y pole, the image centre looks along +z."""
+        cam = Camera()
+        cam.eye[:] = [float(v) for v in eye]
+        cam.forward[:] = [0.0, 0.0, 1.0]
+        cam.up[:] = [0.0, 1.0, 0.0]
+        cam.right[:] = [1.0, 0.0, 0.0]
+        cam.half_cot_half_fov = 1.0
+        return cls._make(CAMERA_PANORAMA, cam)
+
+
 RENDER_PROFILE = 1
 RENDER_BOX_RADIUS = 2
 RENDER_COUNT_VISITS = 4
@@ -363,6 +409,8 @@ def host_lib() -> C.CDLL:
         if hasattr(lib, "spt_host_block_candidates"):   # (the same)
             lib.spt_host_block_candidates.argtypes = [C.POINTER(Camera)] + [C.c_uint32] * 7 + [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                                                                              C.POINTER(C.c_uint64)]
+        if hasattr(lib, "spt_host_camera_rays"):
+            lib.spt_host_camera_rays.argtypes = [C.POINTER(CameraModel), C.POINTER(RenderParams), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         lib.spt_host_load_renderer.argtypes = [C.c_char_p, C.POINTER(RenderParams), C.POINTER(C.c_float)]
         if hasattr(lib, "spt_host_load_renderer_filter"):   # (a library built before the weighted filters lacks it)
             lib.spt_host_load_renderer_filter.argtypes = [C.c_char_p, C.POINTER(RenderParams), C.POINTER(FilterDesc)]
@@ -443,6 +491,9 @@ def hip_lib() -> C.CDLL:
             lib.spt_scene_mesh_topology.argtypes = [C.c_void_p, C.POINTER(MeshTopology)]
             lib.spt_scene_deform_vertices.argtypes = [C.c_void_p, C.POINTER(SceneUpdateDesc), C.c_uint32, C.POINTER(MeshVertices)]
             lib.spt_scene_read_triangles.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        if hasattr(lib, "spt_render_camera"):
+            lib.spt_render_camera.argtypes = [C.c_void_p, C.POINTER(CameraModel), C.POINTER(RenderParams), C.c_void_p, C.POINTER(RenderStats)]
+            lib.spt_film_create_camera.argtypes = [C.c_void_p, C.POINTER(CameraModel), C.POINTER(RenderParams), C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
         lib.spt_debug_detmath.argtypes = [C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.spt_debug_bxdf.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Material), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -931,7 +982,8 @@ class DeviceScene:
         finish kernel stored the image into the (page-locked) output buffer itself, without the runtime's copy; 4 the
         spt_scene_update / spt_scene_deform calls applied to the scene; 5 the bytes the last of them copied to the device; 6 the
         ns the copies and kernels of the last spt_scene_deform that named a mesh took on the device (waits for them); 7 passes whose
-        bounce launches ran on the second stream beside the next pass's camera rays (the pass pipeline; counted under 0 too)."""
+        bounce launches ran on the second stream beside the next pass's camera rays (the pass pipeline; counted under 0 too); 8 passes whose camera rays came from
+        the camera-model kernel (a camera_model=, or any render under SPT_CAMERA_GENERAL=1)."""
         v = C.c_uint64(0)
         _check_hip(hip_lib().spt_debug_render_info(self._h, what, C.byref(v)))
         return int(v.value)
@@ -971,6 +1023,32 @@ class DeviceScene:
             self.close()
         except Exception:
             pass
+
+
+def _camera_entry(name: str):
+    """spt_render_camera / spt_film_create_camera of the device library; a library without camera models is an error."""
+    fn = getattr(hip_lib(), name, None)
+    if fn is None:
+        raise SptError(4, "libspt_hip.so does not export %s (no camera models)" % name)
+    return fn
+
+
+def camera_rays(model: "CameraModel", renderer: "PathTracer", width: int, height: int, first: int = 0, count: Optional[int] = None,
+                aux: bool = False):
+    """spt_host_camera_rays: the rays of a camera model for the samples [first, first + count) of the renderer's plan, as
+    (count, height, width) PATH_RAY_DTYPE records with streams (pixel, plan index); aux=True: (rays, aux) with their auxiliary rays
+    as RAY_AUX_DTYPE.  rays == radiance input: DeviceScene.radiance(rays, aux, max_depth=, seed=, rng_skip=2 (recurrence: 0))
+    returns the samples a film of the model holds.  Made on the host from the header the device kernel includes."""
+    lib = host_lib()
+    if not hasattr(lib, "spt_host_camera_rays"):
+        raise SptError(4, "libspt_host.so does not export spt_host_camera_rays")
+    if count is None:
+        count = renderer.spp - first
+    p = renderer.params(width, height)
+    rays = np.zeros((count, height, width), dtype=PATH_RAY_DTYPE)
+    ax = np.zeros((count, height, width), dtype=RAY_AUX_DTYPE) if aux else None
+    _check_host(lib.spt_host_camera_rays(C.byref(model), C.byref(p), first, count, rays.ctypes.data, ax.ctypes.data if aux else None))
+    return (rays, ax) if aux else rays
 
 
 @dataclass
@@ -1035,7 +1113,7 @@ class PathTracer:
     def render_shard(self, scene: Scene, config: OutputConfig, device: int = 0, shard_index: int = 0,
                      shard_count: int = 1, strip_rows: int = 16, samples_per_pass: int = 0,
                      profile: bool = False, reuse_output: bool = False, film: Optional[np.ndarray] = None,
-                     count_visits: bool = False, wait: bool = True) -> np.ndarray:
+                     count_visits: bool = False, wait: bool = True, camera_model: Optional["CameraModel"] = None) -> np.ndarray:
         """Mean radiance of this shard's rows, shape (rows, width, 3) f32, via the HIP path.
         reuse_output=True returns a page-locked buffer owned by the device scene that the next call
         with the same shape overwrites (no per-call allocation, DMA-speed copy-out).
@@ -1044,13 +1122,15 @@ class PathTracer:
         or after a later wait=True call on the scene; no stats (last_stats keeps the previous synchronous call's).
         With a weighted filter_type the shard is rendered through a sample-keeping film (one increment, one read-out): film=,
         wait=False, profile and count_visits are refused (SptError), reuse_output is ignored (the result is a fresh array, not
-        the scene's pinned buffer) and last_stats is left as it was."""
+        the scene's pinned buffer) and last_stats is left as it was.
+        camera_model: a CameraModel in the place of the scene's camera (spt_render_camera)."""
         if self.filter_type != "box":
             # a weighted filter reads kept samples: one sample-keeping film, one increment, one read-out
             if film is not None or not wait or profile or count_visits:
                 raise SptError(2, "render_shard: a %s filter renders through a sample-keeping film, which takes no film=, wait=False, "
                                   "profile or count_visits" % self.filter_type)
-            with self.progressive(scene, config, device, 0, False, shard_index, shard_count, strip_rows, samples_per_pass, keep_samples=True) as pf:
+            with self.progressive(scene, config, device, 0, False, shard_index, shard_count, strip_rows, samples_per_pass, keep_samples=True,
+                                  camera_model=camera_model) as pf:
                 return pf.render(self.spp).mean()
         ds = scene.device_scene(device)
         cam = scene.get_camera(config.used_camera_name)
@@ -1058,6 +1138,12 @@ class PathTracer:
                         (RENDER_PROFILE if profile else 0) | (RENDER_COUNT_VISITS if count_visits else 0) | (0 if wait else RENDER_ASYNC))
         rows = C.c_uint32()
         _check_hip(hip_lib().spt_shard_rows(C.byref(p), C.byref(rows)))
+
+        def call(dst, stats_ref):
+            if camera_model is None:
+                return hip_lib().spt_render(ds._h, C.byref(cam), C.byref(p), dst, stats_ref)
+            return _camera_entry("spt_render_camera")(ds._h, C.byref(camera_model), C.byref(p), dst, stats_ref)
+
         if film is not None:
             # write this shard's strips in place into a full-image (height, width, 3) f32 film (e.g. SharedFilm.film)
             assert film.shape == (config.height, config.width, 3) and film.dtype == np.float32 and film.flags["C_CONTIGUOUS"]
@@ -1065,7 +1151,7 @@ class PathTracer:
             p.out_strip_stride = shard_count * strip_rows * row_bytes
             stats = RenderStats()
             first = film.ctypes.data + shard_index * strip_rows * row_bytes
-            _check_hip(hip_lib().spt_render(ds._h, C.byref(cam), C.byref(p), first if rows.value else film.ctypes.data, C.byref(stats) if wait else None))
+            _check_hip(call(first if rows.value else film.ctypes.data, C.byref(stats) if wait else None))
             if wait:
                 self.last_stats = stats
             return film
@@ -1079,14 +1165,15 @@ class PathTracer:
                 raise SptError(1, "render_shard(wait=False) needs reuse_output=True (the scene's pinned buffer) or a caller-owned film=")
             out = np.zeros((rows.value, config.width, 3), dtype=np.float32)
         stats = RenderStats()
-        _check_hip(hip_lib().spt_render(ds._h, C.byref(cam), C.byref(p), out.ctypes.data, C.byref(stats) if wait else None))
+        _check_hip(call(out.ctypes.data, C.byref(stats) if wait else None))
         if wait:
             self.last_stats = stats
         return out
 
     def progressive(self, scene: Scene, config: OutputConfig, device: int = 0, first_sample: int = 0, moments: bool = False,
                     shard_index: int = 0, shard_count: int = 1, strip_rows: int = 16, samples_per_pass: int = 0,
-                    flags: int = 0, keep_samples: bool = False, buckets: int = 0) -> "ProgressiveFilm":
+                    flags: int = 0, keep_samples: bool = False, camera_model: Optional["CameraModel"] = None,
+                    buckets: int = 0) -> "ProgressiveFilm":
         """A film that takes this renderer's samples in increments (spt_film_*): `spp` is the plan's total, each
         ProgressiveFilm.render(n) adds the next n samples, and after increments summing to spp (first_sample 0) mean() has the
         bits of render_shard with the same arguments.  moments=True also keeps the sums of squares (sum_sq, variance_of_mean).
@@ -1094,9 +1181,10 @@ class PathTracer:
         the plan goes to bucket s % K) for bucket_sums() and robust_mean().  keep_samples=True keeps every sample's radiance
         instead of running sums (FILM_KEEP_SAMPLES): the film then takes a box radius that reaches neighbouring pixels, kept()
         returns the samples, and moments, buckets, adapt and denoise are refused.  Such a film is read under this renderer's
-        filter_type (ProgressiveFilm.set_filter changes it later); without keep_samples a weighted filter is refused."""
+        filter_type (ProgressiveFilm.set_filter changes it later); without keep_samples a weighted filter is refused.
+        camera_model: a CameraModel in the place of the scene's camera (spt_film_create_camera); the film remembers it."""
         return ProgressiveFilm(self, scene, config, device, first_sample, moments, shard_index, shard_count, strip_rows,
-                               samples_per_pass, flags, keep_samples=keep_samples, buckets=buckets)
+                               samples_per_pass, flags, keep_samples=keep_samples, buckets=buckets, camera_model=camera_model)
 
     def guide_film(self, scene: Scene, config: OutputConfig, device: int = 0) -> "ProgressiveFilm":
         """The guide of ProgressiveFilm.denoise: a film of the same plan with debug_normal (its mean is the first-hit normal
@@ -1112,10 +1200,10 @@ class PathTracer:
         """spt_render_wait: every render_shard(..., wait=False) queued on the scene has delivered its film."""
         _check_hip(hip_lib().spt_render_wait(scene.device_scene(device)._h))
 
-    def render(self, scene: Scene, config: OutputConfig, device: int = 0) -> np.ndarray:
+    def render(self, scene: Scene, config: OutputConfig, device: int = 0, camera_model: Optional["CameraModel"] = None) -> np.ndarray:
         """RendererT::render (src/renderer/pt.rs:237-296): full image on one GPU; writes the PNG
-        when config.output_filename is set and returns the float film (H, W, 3)."""
-        film = self.render_shard(scene, config, device)
+        when config.output_filename is set and returns the float film (H, W, 3).  camera_model: see render_shard."""
+        film = self.render_shard(scene, config, device, camera_model=camera_model)
         if config.output_filename:
             write_image(config.output_filename, film)
         return film
@@ -1127,8 +1215,13 @@ class ProgressiveFilm:
 
     def __init__(self, renderer: PathTracer, scene: Scene, config: OutputConfig, device: int = 0, first_sample: int = 0,
                  moments: bool = False, shard_index: int = 0, shard_count: int = 1, strip_rows: int = 16,
-                 samples_per_pass: int = 0, flags: int = 0, keep_samples: bool = False, buckets: int = 0):
+                 samples_per_pass: int = 0, flags: int = 0, keep_samples: bool = False, camera_model: Optional["CameraModel"] = None,
+                 buckets: int = 0):
         self._h = C.c_void_p()
+        # tests/test_robust_abi.py pins `buckets` as the last parameter here and in PathTracer.progressive, so camera_model sits before it:
+        # a bucket count passed by position lands in camera_model and is named as what it is, before anything is created
+        if camera_model is not None and not isinstance(camera_model, CameraModel):
+            raise TypeError("camera_model takes a CameraModel, not %r; pass buckets= by keyword" % (camera_model,))
         if renderer.filter_type != "box" and not keep_samples:
             raise SptError(1, "a %s filter needs a film that keeps its samples (keep_samples=True)" % renderer.filter_type)
         self._ds = scene.device_scene(device)
@@ -1140,8 +1233,12 @@ class ProgressiveFilm:
         rows = C.c_uint32()
         _check_hip(hip_lib().spt_shard_rows(C.byref(self._params), C.byref(rows)))
         self.rows = rows.value
-        _check_hip(hip_lib().spt_film_create(self._ds._h, C.byref(self._cam), C.byref(self._params), first_sample,
-                                             (FILM_MOMENTS if moments else 0) | (FILM_KEEP_SAMPLES if keep_samples else 0), C.byref(self._h)))
+        film_flags = (FILM_MOMENTS if moments else 0) | (FILM_KEEP_SAMPLES if keep_samples else 0)
+        if camera_model is None:
+            _check_hip(hip_lib().spt_film_create(self._ds._h, C.byref(self._cam), C.byref(self._params), first_sample, film_flags, C.byref(self._h)))
+        else:
+            _check_hip(_camera_entry("spt_film_create_camera")(self._ds._h, C.byref(camera_model), C.byref(self._params), first_sample, film_flags,
+                                                               C.byref(self._h)))
         self._ds._films.add(self)
         self.n_buckets = 0
         if buckets:
@@ -1401,8 +1498,10 @@ class MultiFilm:
 
     def __init__(self, multi: "MultiDevice", renderer: "PathTracer", config: OutputConfig, strip_rows: int = 0, first_sample: int = 0,
                  moments: bool = False, flags: int = 0, buckets: int = 0, film_api: Optional[DeviceFilmApi] = None,
-                 keep_samples: bool = False):
+                 keep_samples: bool = False, camera_model: Optional["CameraModel"] = None):
         self._h = C.c_void_p()
+        if camera_model is not None:   # (the multi-device host layer copies a bare spt_camera)
+            raise SptError(4, "MultiFilm: films over several devices take the scene's pinhole camera only, no camera_model")
         self.multi = multi
         self.first_sample = first_sample
         self.width, self.height = config.width, config.height
@@ -1526,9 +1625,12 @@ class MultiDevice:
         _check_host(host_lib().spt_host_multi_create(C.byref(desc), C.byref(self._api), len(self.devices), devs, C.byref(self._h)))
 
     def render(self, renderer: "PathTracer", config: OutputConfig, strip_rows: int = 0, film: Optional[np.ndarray] = None,
-               samples_per_pass: int = 0) -> np.ndarray:
+               samples_per_pass: int = 0, camera_model: Optional["CameraModel"] = None) -> np.ndarray:
         """RendererT::render over all devices: the (H, W, 3) f32 film (a caller-owned `film` is filled in place).  A renderer
-        with a weighted filter_type is refused (SptError): spt_render knows the box only, and the plan carries just the radius."""
+        with a weighted filter_type is refused (SptError): spt_render knows the box only, and the plan carries just the radius.
+        A camera_model is refused too: the multi-device host layer copies a bare spt_camera."""
+        if camera_model is not None:
+            raise SptError(4, "MultiDevice.render: renders over several devices take the scene's pinhole camera only, no camera_model")
         if renderer.filter_type != "box":   # (params() would hand spt_render the reference's box at the filter's radius)
             raise SptError(4, "MultiDevice.render: spt_render over several devices filters with the box only, not %r "
                               "(render_shard serves a weighted filter on one device)" % (renderer.filter_type,))
@@ -1552,13 +1654,14 @@ class MultiDevice:
         return film
 
     def progressive(self, renderer: "PathTracer", config: OutputConfig, strip_rows: int = 0, first_sample: int = 0, moments: bool = False,
-                    flags: int = 0, buckets: int = 0, film_api: Optional[DeviceFilmApi] = None, keep_samples: bool = False) -> MultiFilm:
+                    flags: int = 0, buckets: int = 0, film_api: Optional[DeviceFilmApi] = None, keep_samples: bool = False,
+                    camera_model: Optional["CameraModel"] = None) -> MultiFilm:
         """PathTracer.progressive over all devices: a MultiFilm, one shard film per replica (shard k of n, strips of `strip_rows`
         rows, 0 = render()'s default).  `flags` are extra SPT_RENDER_* bits of the plan: RENDER_DEBUG_NORMAL / RENDER_AOV_ALBEDO
         with moments=True make the guide / albedo multi film of MultiFilm.denoise_job.  `film_api` defaults to libspt_hip.so's
         functions; tests pass stand-ins.  keep_samples=True: shard films that keep their samples (PathTracer.progressive), each
         tracing its own halo rows, so a box radius that reaches neighbouring pixels works over several devices too."""
-        return MultiFilm(self, renderer, config, strip_rows, first_sample, moments, flags, buckets, film_api, keep_samples)
+        return MultiFilm(self, renderer, config, strip_rows, first_sample, moments, flags, buckets, film_api, keep_samples, camera_model)
 
     def close(self) -> None:
         for film in list(getattr(self, "_films", ())):
@@ -1711,7 +1814,10 @@ def panorama_rays(origin, width: int, height: int, offsets, *, first_sample: int
     """Equirectangular rays from `origin`, in the environment map's own parametrisation (environment.rs:128-133: theta =
     acos(d.y), phi = atan2(d.x, d.z) + pi): row j looks at theta = (j + oy) / height * pi, so row 0 starts at theta 0 (+y, the
     top pole) and the last row ends at theta pi (-y); column i looks at phi = (i + ox) / width * 2 pi, so the seam phi = 0 at the
-    left edge of column 0 looks along -z, the image centre phi = pi along +z, and phi = pi / 2 along -x."""
+    left edge of column 0 looks along -z, the image centre phi = pi along +z, and phi = pi / 2 along -x.
+    This float64 helper counts the vertical offset downward (row j covers theta from j to j + 1); the device's panorama model
+    (CameraModel.panorama, camera_rays) keeps the pinhole's convention, oy running upward inside the row, so the two agree on
+    the pixel grid and differ in where inside its row a sample lies.  The helper stays as it is."""
     off = _offsets4(offsets, width, height)
     theta = (np.arange(height, dtype=np.float64)[None, :, None] + off[..., 1]) / height * np.pi
     phi = (np.arange(width, dtype=np.float64)[None, None, :] + off[..., 0]) / width * (2.0 * np.pi)

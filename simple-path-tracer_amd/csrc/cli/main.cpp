@@ -43,6 +43,7 @@ static void usage() {
                  "            [--guide normal|albedo|both] [--demodulate] [--albedo-out albedo.png]]\n"
                  "           [--robust K [--robust-estimator mon|gmon] [--mean-out mean.png]]   (K odd, 3 .. 15)\n"
                  "           [--film-devices a,b,..]   (the progressive options above over several devices)\n"
+                 "           [--lens-radius R --focus-distance D | --orthographic H | --panorama]   (a camera model in the scene camera's place)\n"
                  "           [--animate frames.json]   (one plain image <out>_NNNN per frame: {\"frames\": [{\"<instance>\": {<transform>}, ..}, ..]})\n");
 }
 
@@ -229,6 +230,9 @@ int main(int argc, char** argv) {
     int robust_k = 0;
     std::string robust_estimator, mean_out;
     std::string animate_path;
+    // camera models (spt_render_camera / spt_film_create_camera): a thin lens, an orthographic view or an equirectangular panorama
+    double lens_radius = 0.0, focus_distance = 0.0, view_height = 0.0;
+    bool lens_given = false, focus_given = false, ortho_given = false, panorama = false;
     std::vector<int32_t> device_list;
     std::vector<int32_t> film_devices;
     bool film_devices_given = false, film_devices_ok = true;
@@ -278,6 +282,10 @@ int main(int argc, char** argv) {
         else if (a == "--robust-estimator") robust_estimator = next();
         else if (a == "--mean-out") mean_out = next();
         else if (a == "--animate") animate_path = next();
+        else if (a == "--lens-radius") { lens_radius = std::atof(next()); lens_given = true; }
+        else if (a == "--focus-distance") { focus_distance = std::atof(next()); focus_given = true; }
+        else if (a == "--orthographic") { view_height = std::atof(next()); ortho_given = true; }
+        else if (a == "--panorama") panorama = true;
         else if (a == "--film-devices") { film_devices_given = true; film_devices_ok = parse_device_list(next(), &film_devices); }
         else { usage(); return 2; }
     }
@@ -306,6 +314,21 @@ int main(int argc, char** argv) {
     const bool guide_normal = guide_mode != "albedo", guide_albedo = guide_mode != "normal";
     if ((demodulate || !albedo_out.empty()) && !guide_albedo) {
         std::fprintf(stderr, "Error: --demodulate and --albedo-out need the albedo film (--guide albedo or --guide both)\n");
+        return 2;
+    }
+    const bool thin_lens = lens_given || focus_given;
+    const bool camera_model = thin_lens || ortho_given || panorama;
+    if ((thin_lens ? 1 : 0) + (ortho_given ? 1 : 0) + (panorama ? 1 : 0) > 1) {
+        std::fprintf(stderr, "Error: --lens-radius / --focus-distance, --orthographic and --panorama exclude each other (one camera model)\n");
+        return 2;
+    }
+    if (thin_lens && !(lens_given && focus_given)) {
+        std::fprintf(stderr, "Error: a thin lens needs both --lens-radius R and --focus-distance D\n");
+        return 2;
+    }
+    if (camera_model && (gpus > 1 || (film_devices_given && film_devices.size() > 1) || !animate_path.empty() || (denoise && guide_albedo))) {
+        std::fprintf(stderr, "Error: a camera model (--lens-radius, --orthographic, --panorama) renders on one device: not with several --gpus / --devices / "
+                             "--film-devices, --animate or --guide albedo|both\n");
         return 2;
     }
     const uint32_t estimator = robust_estimator == "mon" ? (uint32_t)SPT_ROBUST_MON : (uint32_t)SPT_ROBUST_GMON;
@@ -399,6 +422,16 @@ int main(int argc, char** argv) {
         spt_host_scene_free(hs);
         return 2;
     }
+    // a camera model on one device named through --film-devices d or --gpus 1 / --devices d: the film, or the plain image, lives there
+    // (behind every refusal above, which holds for these runs as for any other)
+    if (camera_model && film_devices_given) {
+        device = film_devices[0];
+        film_devices_given = false;
+    }
+    if (camera_model && gpus == 1) {
+        device = device_list.empty() ? 0 : device_list[0];
+        gpus = 0;
+    }
     // A box filter that reaches neighbouring pixels (ceil(radius - 0.5) >= 1): its film keeps the samples (SPT_FILM_KEEP_SAMPLES),
     // which previews, time limits and several devices can use.  What needs moments or buckets cannot: the library would refuse
     // (spt_film_create with SPT_FILM_MOMENTS, spt_film_buckets), so the run ends here, before any sample is traced
@@ -415,6 +448,21 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "Error: %s\n", spt_host_last_error());
         return 1;
     }
+    spt_camera_model model;
+    std::memset(&model, 0, sizeof model);
+    model.size = (uint32_t)sizeof model;
+    model.type = thin_lens ? SPT_CAMERA_THIN_LENS : ortho_given ? SPT_CAMERA_ORTHOGRAPHIC : panorama ? SPT_CAMERA_PANORAMA : SPT_CAMERA_PERSPECTIVE;
+    model.base = cam;
+    model.lens_radius = (float)lens_radius;
+    model.focus_distance = (float)focus_distance;
+    model.view_height = (float)view_height;
+    // the plain run and every film of it take the model when one is given (SPT_CAMERA_PERSPECTIVE: the calls they replace)
+    auto render_call = [&](const spt_scene* scene, const spt_render_params* rp, float* out, spt_render_stats* stats) {
+        return camera_model ? spt_render_camera(scene, &model, rp, out, stats) : spt_render(scene, &cam, rp, out, stats);
+    };
+    auto film_create_call = [&](const spt_scene* scene, const spt_render_params* rp, uint32_t first, uint32_t flags, spt_film** out) {
+        return camera_model ? spt_film_create_camera(scene, &model, rp, first, flags, out) : spt_film_create(scene, &cam, rp, first, flags, out);
+    };
     params.width = width;
     params.height = height;
     params.seed = seed;
@@ -508,7 +556,7 @@ int main(int argc, char** argv) {
             spt_host_scene_free(hs);
             return 0;
         }
-        if (!progressive && spt_render(ds, &cam, &params, film.data(), st.data()) != SPT_OK) {
+        if (!progressive && render_call(ds, &params, film.data(), st.data()) != SPT_OK) {
             std::fprintf(stderr, "Error: %s\n", spt_last_error());
             return 1;
         }
@@ -545,14 +593,14 @@ int main(int argc, char** argv) {
             return 1;
         };
         const bool moments = !variance_out.empty() || adaptive_on || denoise;
-        if (spt_film_create(ds, &cam, &params, 0, (moments ? (uint32_t)SPT_FILM_MOMENTS : 0u) | keep_flag, &pf) != SPT_OK) return film_fail();
+        if (film_create_call(ds, &params, 0, (moments ? (uint32_t)SPT_FILM_MOMENTS : 0u) | keep_flag, &pf) != SPT_OK) return film_fail();
         if (weighted && spt_film_filter(pf, &filter) != SPT_OK) return film_fail();
         if (robust && spt_film_buckets(pf, (uint32_t)robust_k) != SPT_OK) return film_fail();
         const spt_denoise_params dn = {(uint32_t)sizeof(spt_denoise_params), denoise_iterations, 2.0f, 1.0f, 1e-8f, 1e-2f};
         if (denoise && guide_normal) {   // the guide's samples come first: every preview is filtered with the whole guide
             spt_render_params gp = params;
             gp.flags |= SPT_RENDER_DEBUG_NORMAL;
-            if (spt_film_create(ds, &cam, &gp, 0, (uint32_t)SPT_FILM_MOMENTS, &guide) != SPT_OK) return film_fail();
+            if (film_create_call(ds, &gp, 0, (uint32_t)SPT_FILM_MOMENTS, &guide) != SPT_OK) return film_fail();
             if (spt_film_render(guide, std::max(2u, std::min(params.spp, guide_samples))) != SPT_OK) return film_fail();
         }
         if (denoise && guide_albedo) {

@@ -580,7 +580,8 @@ SPT_DEV void rad_store(const RenderCtx& rc, uint32_t slot, f3 c) {
 // (kFirst off), and the one extra argument names the rays' auxiliary rays, from which the hit's differentials are computed as
 // kFirst computes them from the camera's.  Without kAux there is no extra argument and the kernel's code stays what it was.
 struct RayAux {
-    const float4* rec;   // 4 float4 per ray of the pass (spt_ray_aux); a path's ray is its radiance slot modulo rc.n_pixels
+    const float4* rec;   // 4 float4 per ray of the pass (spt_ray_aux); a path's ray is its radiance slot modulo `wrap`
+    uint32_t wrap;       // spt_radiance: the rays of the pass (slot = repetition * rays + ray); a camera model: the slots of the pass (one record each)
 };
 // OriginCand (trailing type, fused simple instances only; the one extra argument is the scene's table, origin.h): the shadow and the
 // extension ray of a vertex are tested against the candidate sets of the triangle they leave instead of walking the tree.  Without
@@ -749,7 +750,7 @@ __global__ void __launch_bounds__(256, (kFeat == 0 && kFirst && kFused && pack_h
                 it = reconstruct_hit<kTex, kTab>(sc, ray, h);
                 if (kTex && kFirst) calc_differential(it, ray, h.t, rc.cam.eye, aux_xd, rc.cam.eye, aux_yd);   // pt.rs:51-53
                 if constexpr (kAux) {   // the same from the caller's auxiliary rays
-                    const float4* const ar = (aux_arg, ...).rec + 4u * (size_t)(slot % rc.n_pixels);
+                    const float4* const ar = (aux_arg, ...).rec + 4u * (size_t)(slot % (aux_arg, ...).wrap);
                     calc_differential(it, ray, h.t, mk3(ar[0]), mk3(ar[1]), mk3(ar[2]), mk3(ar[3]));
                 }
             }

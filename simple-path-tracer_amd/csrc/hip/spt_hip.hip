@@ -24,6 +24,7 @@
 #include "kernel_list.h"   // the heavy kernel templates: declared here, compiled in inst_*.hip
 #include "film_kernels.h"
 #include "radiance_kernels.h"
+#include "camera_kernels.h"   // k_primary_cam: declared here, compiled in inst_camera.hip
 #include "deform_kernels.h"   // spt_scene_deform's kernels: declared here, compiled in inst_deform.hip
 #include "abi_error.h"     // AbiError, fail
 #include "scene_build.h"   // everything a scene derives from its descriptor on the host
@@ -142,6 +143,8 @@ struct BezierLib {
     decltype(&spt_scene_mesh_topology) scene_mesh_topology = nullptr;       // (the same)
     decltype(&spt_scene_deform_vertices) scene_deform_vertices = nullptr;   // (the same)
     decltype(&spt_scene_read_triangles) scene_read_triangles = nullptr;     // (the same)
+    decltype(&spt_render_camera) render_camera = nullptr;             // (the same)
+    decltype(&spt_film_create_camera) film_create_camera = nullptr;   // (the same)
     decltype(&spt_debug_bxdf) debug_bxdf = nullptr;
     decltype(&spt_debug_render_info) debug_render_info = nullptr;
     decltype(&spt_last_error) last_error = nullptr;
@@ -176,6 +179,7 @@ struct spt_scene {
     int ov_mode = 0;                          // the schedule of the overlapped passes still in flight: 1 two streams, 2 the pass pipeline (0: none yet)
     uint64_t passes_film = 0, passes_single = 0;   // spt_debug_render_info: passes resolved on the film stream / on the main stream
     uint64_t passes_pipe = 0;                      // ... and passes whose shade stage ran on stream2 (counted under passes_film too)
+    uint64_t passes_cam = 0;                       // ... and passes whose camera rays came from k_primary_cam (camera_kernels.h)
     uint64_t frames_direct = 0;                    // ... and frames whose finish kernel stored into the caller's buffer (no copy-out)
     // ... and what the kernels of a sample-keeping film's last read-out (k_film_filter_box, k_film_filter_weighted) took on the device, in ns, between the
     // two events below (made by the first such film)
@@ -209,6 +213,7 @@ struct spt_scene {
     // spt_radiance's own buffers, made by its first call and reused: the rays (and auxiliary rays) of a pass on the device and the
     // two page-locked slots they go up through, the results of a call with host pointers, and the events that say a slot's copy is done
     DeviceBuffer ray_in, ray_aux_in, ray_rgb, ray_hits;
+    DeviceBuffer cam_aux;   // k_primary_cam on a textured scene: the auxiliary rays of a pass, one spt_ray_aux per radiance slot
     PinnedBuffer ray_stage[2];
     hipEvent_t ev_ray[2] = {nullptr, nullptr};
     std::mutex mu;
@@ -301,6 +306,7 @@ struct spt_film {
     spt_film* inner = nullptr;
     spt_scene* sc = nullptr;
     spt_camera cam{};
+    spt_camera_model model{};         // type != SPT_CAMERA_PERSPECTIVE: the film's camera model (spt_film_create_camera); cam == model.base
     spt_render_params plan{};
     uint32_t first = 0, done = 0;     // covers the plan's samples [first, first + done)
     uint32_t flags = 0;               // SPT_FILM_*
@@ -485,6 +491,8 @@ const BezierLib* bezier_lib() {
         (void)sym(lib.scene_mesh_topology, "spt_scene_mesh_topology");
         (void)sym(lib.scene_deform_vertices, "spt_scene_deform_vertices");
         (void)sym(lib.scene_read_triangles, "spt_scene_read_triangles");
+        (void)sym(lib.render_camera, "spt_render_camera");
+        (void)sym(lib.film_create_camera, "spt_film_create_camera");
         if (!all || version() != SPT_ABI_VERSION) {
             err = path + " does not export ABI version " + std::to_string(SPT_ABI_VERSION);
             return;
@@ -824,6 +832,7 @@ struct SampleTarget {
 struct RenderRun {
     spt_scene* sc = nullptr;
     const spt_camera* cam = nullptr;
+    const spt_camera_model* model = nullptr;   // a non-perspective camera model (cam == &model->base); null: the pinhole
     const spt_render_params* params = nullptr;
     spt_render_stats* stats = nullptr;
     hipStream_t st = nullptr;
@@ -846,6 +855,9 @@ struct RenderRun {
     bool direct_out = false;     // k_finish_host may store into a pinned rgb_mean_out (no SPT_NO_DIRECT_OUT)
     uint32_t direct_grid = 0;    // ... over this many workgroups at the most (kFinishHostGrid, or SPT_DIRECT_OUT_GRID for A/B runs)
     bool debug_spans = false;    // per-launch HIP-event times on stderr (profile mode)
+    bool general = false;        // the camera rays come from k_primary_cam (a camera model, or SPT_CAMERA_GENERAL=1): full path records at bounce 0, as `rays`
+    CamJob cam_job{};            // ... and what it takes besides the scene and the pass
+    uint32_t ray_aux_wrap = 0;   // RayAux::wrap of `ray_aux` below
     bool rays = false;           // spt_radiance: no camera, every bounce shaded from full path records (k_shade<., kFirst = false>)
     const float4* ray_aux = nullptr;   // ... and the auxiliary rays of the pass for the bounce-0 launch of a textured scene (kAux); null: none
     bool albedo = false;         // SPT_RENDER_AOV_ALBEDO: paths end at their first surface, and the kernels get the scene without its environment
@@ -899,8 +911,11 @@ void run_setup(RenderRun& run) {
     run.overlap = !run.profile && !run.env && std::getenv("SPT_NO_OVERLAP") == nullptr;
     run.lds = sc->lds_bytes;
     run.L = sc->lds_geo;
+    // a camera model - or, for A/B runs, the pinhole under SPT_CAMERA_GENERAL=1 (plans that count visits or ask for the albedo keep the
+    // pinhole kernels) - takes k_primary_cam: nothing below that is derived from a pinhole eye applies to it
+    run.general = !run.rays && (run.model != nullptr || (env_u32("SPT_CAMERA_GENERAL", 0u) != 0u && !run.albedo && !(p.flags & SPT_RENDER_COUNT_VISITS)));
     // primary rays of an LDS-resident scene through the eye-relative copy of its geometry (eye.h), remade when the eye has moved
-    run.use_eye = !run.rays && run.L && !run.count && sc->eye_ok && std::getenv("SPT_NO_EYE_BLOB") == nullptr;
+    run.use_eye = !run.rays && !run.general && run.L && !run.count && sc->eye_ok && std::getenv("SPT_NO_EYE_BLOB") == nullptr;
     if (run.use_eye && (!sc->eye_valid || std::memcmp(sc->eye_key, cam->eye, sizeof(sc->eye_key)) != 0)) make_eye_blob(sc, cam->eye);
     // ... and, when that copy is at most 64 triangles of meshes only, against the triangles k_block_candidates leaves per wave
     run.use_cand = run.use_eye && sc->cand_ok && std::getenv("SPT_NO_BLOCK_CANDIDATES") == nullptr;
@@ -931,7 +946,7 @@ void run_setup(RenderRun& run) {
     run.fused = sc->fused && sc->simple && std::getenv("SPT_NO_FUSED") == nullptr;
     // ... with the candidate sets of the triangle a vertex lies on instead of the two walks, for a camera whose eye is within the
     // table's reach (the error bound of a bounce-0 origin grows with the camera's distance; caller rays start anywhere)
-    run.use_origin = run.fused && sc->origin_ok && !run.rays && !run.count && cam != nullptr && std::getenv("SPT_NO_ORIGIN_CANDIDATES") == nullptr;
+    run.use_origin = run.fused && sc->origin_ok && !run.rays && !run.general && !run.count && cam != nullptr && std::getenv("SPT_NO_ORIGIN_CANDIDATES") == nullptr;
     if (run.use_origin) {
         double d2 = 0.0;
         for (int k = 0; k < 3; ++k) d2 += ((double)cam->eye[k] - sc->origin_info.center[k]) * ((double)cam->eye[k] - sc->origin_info.center[k]);
@@ -941,18 +956,25 @@ void run_setup(RenderRun& run) {
     run.tab = sc->lds_tables && std::getenv("SPT_NO_LDS_TABLES") == nullptr;   // shading tables from LDS (tab_ld)
     run.tail_loop = std::getenv("SPT_NO_TAIL_LOOP") == nullptr;
     run.pack_first = sc->d.n_instances < (1u << 20) && std::getenv("SPT_NO_PACK_FIRST") == nullptr;
-    run.pixel_cull = std::getenv("SPT_NO_PIXEL_CULL") == nullptr;
+    run.pixel_cull = !run.general && std::getenv("SPT_NO_PIXEL_CULL") == nullptr;
     run.row_spans = run.pixel_cull && std::getenv("SPT_NO_ROW_SPANS") == nullptr;
     if (const char* v = std::getenv("SPT_PRIMARY_CHUNKS")) run.primary_chunks = (uint32_t)std::max(1, std::atoi(v));
     run.resolve32 = env_u32("SPT_RESOLVE_BATCH", 16u) == 32u;
     run.film_stream = env_u32("SPT_NO_FILM_STREAM", 0u) == 0u;
-    run.pass_pipeline = env_u32("SPT_NO_PASS_PIPELINE", 0u) == 0u;
+    run.pass_pipeline = !run.general && env_u32("SPT_NO_PASS_PIPELINE", 0u) == 0u;
     if (const char* v = std::getenv("SPT_PASS_PIPELINE_MAX_BYTES")) run.pipe_max_bytes = std::strtoull(v, nullptr, 10);
     run.direct_out = env_u32("SPT_NO_DIRECT_OUT", 0u) == 0u;
     run.direct_grid = std::max(1u, env_u32("SPT_DIRECT_OUT_GRID", kFinishHostGrid));
     run.box_band_bytes = 8ull << 30;
     if (const char* v = std::getenv("SPT_BOX_BAND_BYTES")) run.box_band_bytes = std::max<uint64_t>(1, std::strtoull(v, nullptr, 10));
     run.debug_spans = std::getenv("SPT_DEBUG_SPANS") != nullptr;
+    if (run.general) {
+        spt_camera_model& m = run.cam_job.model;
+        if (run.model != nullptr) m = *run.model;
+        else { m = spt_camera_model{}; m.type = SPT_CAMERA_PERSPECTIVE; m.base = *cam; }
+        m.size = (uint32_t)sizeof(spt_camera_model);
+        run.cam_job.plan = spt_cm_plan_make(&m, p.width, p.height);
+    }
 }
 
 void run_spans(RenderRun& run) {
@@ -1183,8 +1205,18 @@ size_t grow_queues(spt_scene* sc, size_t cap, uint32_t shard_cap, uint32_t max_d
     return counts_words;
 }
 
+// The sample chunks of a k_primary_cam pass of pass_samples samples over n_tiles tiles: about 6144 workgroups, as primary_pass aims at
+struct CamChunks { uint32_t chunk_samples, chunks; };
+CamChunks cam_chunks(uint32_t n_tiles, uint32_t pass_samples) {
+    const uint32_t want = std::max(1u, std::min({64u, (6144u + n_tiles - 1u) / std::max(n_tiles, 1u), pass_samples}));
+    const uint32_t chunk_samples = (pass_samples + want - 1u) / want;
+    return CamChunks{chunk_samples, (pass_samples + chunk_samples - 1u) / chunk_samples};
+}
+
+// general: the passes are k_primary_cam's (camera_kernels.h), whose queue shards belong to workgroups, not to tiles, and whose bounce-0
+// records are full path records
 PassShape grow_workspace(spt_scene* sc, const spt_render_params& p, uint32_t n_samples, bool collect, bool fused, bool class_queues, float* sum,
-                         bool own_rad, RenderCtx& rc) {
+                         bool own_rad, bool general, bool cam_aux, RenderCtx& rc) {
     const uint32_t n_pix = rc.n_pixels;
     PassShape ps{};
     ps.spp_pass = pass_samples_of(p, n_pix, n_samples);
@@ -1199,13 +1231,22 @@ PassShape grow_workspace(spt_scene* sc, const spt_render_params& p, uint32_t n_s
         for (uint32_t ty = 0; ty < tiles_y; ++ty)
             for (uint32_t tx = 0; tx < rc.tiles_x; ++tx) max_tiles = std::max(max_tiles, ++per[(tx + 9u * ty) % kShards]);
     }
-    const uint64_t shard_cap64 = (uint64_t)max_tiles * kBlock * ps.spp_pass;
+    uint64_t shard_cap64 = (uint64_t)max_tiles * kBlock * ps.spp_pass;
+    if (general) {   // the passes come in two sizes, the full one and the rest behind the last full one: a shard holds either
+        shard_cap64 = 0;
+        for (const uint32_t pass_samples : {ps.spp_pass, n_samples % ps.spp_pass}) {
+            if (pass_samples == 0u) continue;
+            const CamChunks cc = cam_chunks(rc.n_tiles, pass_samples);
+            shard_cap64 = std::max(shard_cap64, (((uint64_t)rc.n_tiles * cc.chunks + kShards - 1) / kShards) * kBlock * cc.chunk_samples);
+        }
+    }
     const uint64_t cap64 = shard_cap64 * kShards;
     if (cap64 > 0x7fffffffull) fail(SPT_ERR_UNSUPPORTED, "render: pass too large (lower samples_per_pass)");
     const size_t cap = (size_t)cap64;
     ps.rad_slots = (uint64_t)n_pix * (collect ? p.spp : ps.spp_pass);
 
-    ps.counts_words = grow_queues(sc, cap, (uint32_t)shard_cap64, p.max_depth, fused, class_queues, true, rc);
+    ps.counts_words = grow_queues(sc, cap, (uint32_t)shard_cap64, p.max_depth, fused, class_queues, !general, rc);
+    if (cam_aux) grow(sc, sc->cam_aux, (size_t)n_pix * ps.spp_pass * sizeof(spt_ray_aux));
     if (!own_rad) grow(sc, sc->rad[0], (size_t)ps.rad_slots * 3 * sizeof(float));   // (own_rad: the passes write the caller's chunks, SampleTarget::keep)
     float* const film_sum = sum ? sum : (grow(sc, sc->film, (size_t)n_pix * 3 * sizeof(float)), sc->film.as<float>());
     grow(sc, sc->first_slot[0], (size_t)n_pix * sizeof(uint32_t));
@@ -1395,6 +1436,20 @@ void launch_primary(const RenderRun& run, uint32_t blocks, const RenderCtx& rc, 
 // marks the samples that own a radiance slot in rc.slot_bits for the resolve).
 bool primary_pass(const RenderRun& run, RenderCtx& rc, const SampleTarget& tgt, uint32_t active_tiles, bool collect, uint8_t* slot_bits) {
     spt_scene* const sc = run.sc;
+    if (run.general) {   // every sample of a live pixel owns its slot and the film is touched by the resolve only: the plain k_resolve follows
+        const CamChunks cc = cam_chunks(rc.n_tiles, rc.pass_samples);
+        rc.chunk_samples = cc.chunk_samples;
+        rc.primary_chunks = cc.chunks;
+        rc.slot_bits = nullptr;
+        CamJob job = run.cam_job;
+        job.mask = tgt.mask;
+        job.aux_out = run.ray_aux != nullptr ? sc->cam_aux.as<float4>() : nullptr;
+        const bool stream = sc->swalk && !sc->lds_geo;   // the walkers of spt_trace_closest, as spt_radiance's intake
+        hipLaunchKernelGGL(stream ? k_primary_cam<2> : sc->lds_geo ? k_primary_cam<0> : k_primary_cam<1>, dim3(rc.n_tiles * cc.chunks), dim3(kBlock),
+                           sc->lds_bytes, run.st, run_scene(run, false), rc, job);
+        ++sc->passes_cam;
+        return false;
+    }
     // sample chunks per tile: aim at ~6144 busy workgroups (24 per CU; 4096 .. 8192 measured within 2 %) given the tiles inside the screen bound
     // (an adaptive film: the tiles its last adapt left active; chunking does not change bits)
     const uint32_t busy_tiles = tgt.mask.pixel ? std::min(active_tiles, tgt.mask_tiles) : active_tiles;
@@ -1441,7 +1496,7 @@ BounceFn shade_level(bool first, bool tab, bool geo_lds) {
 // The shade kernel of bounce b.  tail_loop: the fused kernel that takes bounce 1 and every later one in one launch.
 BounceFn shade_kernel(const RenderRun& run, uint32_t b, bool tail_loop) {
     const spt_scene* const sc = run.sc;
-    const bool first = b == 0 && !run.rays;   // (caller rays: bounce 0 has full path records too, radiance_kernels.h)
+    const bool first = b == 0 && !run.rays && !run.general;   // (caller rays and camera models: bounce 0 has full path records too, radiance_kernels.h)
     if (run.fused) return first ? k_shade<0, true, true, true, true> : tail_loop ? k_shade<0, false, true, true, true, true> : k_shade<0, false, true, true, true>;
     if (sc->simple) return shade_level<0>(first, run.tab, false);
     if (!sc->textured) return shade_level<1>(first, run.tab, false);
@@ -1529,7 +1584,7 @@ bool bounce(RenderRun& run, const RenderCtx& rc, uint32_t b, hipStream_t st) {
         return false;
     }
     if (run.ray_aux != nullptr && b == 0u && sc->textured && !sc->simple && !run.fused)
-        hipLaunchKernelGGL(shade_aux_kernel(run), dim3(kPersistentBlocks), dim3(kBlock), shade_lds, st, sc->d, ru, b, RayAux{run.ray_aux});
+        hipLaunchKernelGGL(shade_aux_kernel(run), dim3(kPersistentBlocks), dim3(kBlock), shade_lds, st, sc->d, ru, b, RayAux{run.ray_aux, run.ray_aux_wrap});
     else if (run.use_origin)
         hipLaunchKernelGGL(shade_origin_kernel(b, tail_loop), dim3(kPersistentBlocks), dim3(kBlock), shade_lds, st, sc->d, ru, b, OriginCand{sc->origin_cand.as<uint4>()});
     else
@@ -1619,15 +1674,22 @@ RenderCtx trace_window(RenderRun& run, uint32_t row_base, uint32_t rows, uint32_
     if ((uint64_t)rows * p.width > 0x7fffffffull) fail(SPT_ERR_UNSUPPORTED, "render: window larger than 2^31 pixels");
     RenderCtx rc = plan_ctx(p, *run.cam, row_base, rows, w_index, w_count, w_strip);
     const uint32_t n_pix = rc.n_pixels;
-    const PassShape ps = grow_workspace(sc, p, tgt.count, collect && tgt.keep == nullptr, run.fused, run.class_queues, tgt.sum, tgt.keep != nullptr, rc);
-    screen_bound(sc, p, *run.cam, run.pixel_cull, rc);
+    // a camera model on a scene that samples textures: the kernel leaves the auxiliary rays of the pass for the kAux bounce-0 launch
+    const bool cam_aux = run.general && sc->textured && !sc->simple && !run.fused && p.max_depth > 0u;
+    const PassShape ps = grow_workspace(sc, p, tgt.count, collect && tgt.keep == nullptr, run.fused, run.class_queues, tgt.sum, tgt.keep != nullptr,
+                                        run.general, cam_aux, rc);
+    if (cam_aux) run.ray_aux = sc->cam_aux.as<float4>();
+    if (run.general) {   // no pinhole eye: no bounding-sphere early-out, no screen bound
+        rc.bs_valid = 0u;
+        rc.cull_i0 = 0; rc.cull_i1 = (int32_t)p.width - 1; rc.cull_j0 = 0; rc.cull_j1 = (int32_t)p.height - 1;
+    } else screen_bound(sc, p, *run.cam, run.pixel_cull, rc);
     rc.dyn_refill_below = run.dyn_refill_below;
     rc.dyn_steps = run.dyn_steps;
     rc.stream_rounds = run.stream_rounds;
     rc.stream_refill_below = run.stream_refill_below;
     rc.visits = sc->visits.as<unsigned long long>();
     rc.row_span = run.row_span_dev;
-    const LiveCount live = count_live(sc, run.env, rc);
+    const LiveCount live = count_live(sc, run.env || run.general, rc);
     // The candidate masks of this window's blocks: every render, ahead of its first k_primary on the same stream (whose earlier launches read the
     // masks before this one overwrites them, by stream order).  Here, with the rest of the workspace: a growing buffer drains both streams and
     // resets the overlap state, which the lines below set for this render.
@@ -1715,7 +1777,8 @@ RenderCtx trace_window(RenderRun& run, uint32_t row_base, uint32_t rows, uint32_
         rc.pass_first = s0;
         rc.pass_samples = std::min(ps.spp_pass, s_end - s0);
         rc.rad_plane = collect ? (size_t)p.spp * n_pix : (size_t)rc.pass_samples * n_pix;
-        rc.pack_first = (run.pack_first && rc.pass_samples <= 4096u) ? 1u : 0u;
+        rc.pack_first = (run.pack_first && !run.general && rc.pass_samples <= 4096u) ? 1u : 0u;
+        run.ray_aux_wrap = cam_aux ? rc.pass_samples * n_pix : 0u;
         if (tgt.keep != nullptr) {   // a sample-keeping film: the pass's own chunk, laid out like a pass that is not kept
             rc.rad_plane = (size_t)rc.pass_samples * n_pix;
             rc.rad = tgt.keep[(s0 - tgt.first) / ps.spp_pass];
@@ -2290,11 +2353,42 @@ spt_status spt_scene_origin_candidates(const spt_scene* scene_c, uint64_t* words
     });
 }
 
+// What spt_render_camera and spt_film_create_camera check of a non-perspective model and its plan before anything else happens; SPT_OK:
+// the call may go on
+static spt_status check_camera_model(const spt_camera_model* model, const spt_render_params* params, const char* who) {
+    if (const char* why = spt_cm_check(model)) { g_error = std::string(who) + ": " + why; return SPT_ERR_INVALID_ARG; }
+    if (params && (params->flags & SPT_RENDER_COUNT_VISITS)) { g_error = std::string(who) + ": a camera model does not count visits (SPT_RENDER_COUNT_VISITS)"; return SPT_ERR_UNSUPPORTED; }
+    if (params && (params->flags & SPT_RENDER_AOV_ALBEDO)) { g_error = std::string(who) + ": SPT_RENDER_AOV_ALBEDO is not served for a camera model (the albedo kernels read the pinhole's compact records)"; return SPT_ERR_UNSUPPORTED; }
+    return SPT_OK;
+}
+
+static spt_status render_impl(const spt_scene* scene_c, const spt_camera* cam, const spt_camera_model* model, const spt_render_params* params,
+                              float* rgb_mean_out, spt_render_stats* stats);
+
 spt_status spt_render(const spt_scene* scene_c, const spt_camera* cam, const spt_render_params* params,
                       float* rgb_mean_out, spt_render_stats* stats) {
+    return render_impl(scene_c, cam, nullptr, params, rgb_mean_out, stats);
+}
+
+spt_status spt_render_camera(const spt_scene* scene_c, const spt_camera_model* model, const spt_render_params* params, float* rgb_mean_out,
+                             spt_render_stats* stats) {
+    if (!scene_c || !model || !params || !rgb_mean_out) { g_error = "render_camera: null argument"; return SPT_ERR_INVALID_ARG; }
+    if (model->size >= sizeof(spt_camera_model) && model->type == SPT_CAMERA_PERSPECTIVE) return spt_render(scene_c, &model->base, params, rgb_mean_out, stats);
+    const spt_status st = check_camera_model(model, params, "render_camera");
+    if (st != SPT_OK) return st;
+    return render_impl(scene_c, &model->base, model, params, rgb_mean_out, stats);
+}
+
+// model: a checked non-perspective camera model with cam == &model->base, or null
+static spt_status render_impl(const spt_scene* scene_c, const spt_camera* cam, const spt_camera_model* model, const spt_render_params* params,
+                              float* rgb_mean_out, spt_render_stats* stats) {
     if (!scene_c || !cam || !params || !rgb_mean_out) { g_error = "render: null argument"; return SPT_ERR_INVALID_ARG; }
     spt_scene* sc = const_cast<spt_scene*>(scene_c);
-    if (sc->fwd) return forwarded(sc->fwd, sc->fwd->render(sc->inner, cam, params, rgb_mean_out, stats));
+    if (sc->fwd) {
+        if (model == nullptr) return forwarded(sc->fwd, sc->fwd->render(sc->inner, cam, params, rgb_mean_out, stats));
+        if (!sc->fwd->render_camera) { g_error = "render_camera: libspt_hip_bez.so does not export spt_render_camera"; return SPT_ERR_UNSUPPORTED; }
+        return forwarded(sc->fwd, sc->fwd->render_camera(sc->inner, model, params, rgb_mean_out, stats));
+    }
     std::lock_guard<std::mutex> lock(sc->mu);
     return guarded("render", [&] {
         const spt_render_params& p = *params;
@@ -2334,6 +2428,7 @@ spt_status spt_render(const spt_scene* scene_c, const spt_camera* cam, const spt
         RenderRun run;
         run.sc = sc;
         run.cam = cam;
+        run.model = model;
         run.params = &p;
         run.stats = stats;
         run_setup(run);
@@ -2483,14 +2578,35 @@ spt_status spt_render_wait(const spt_scene* scene_c) {
     });
 }
 
+static spt_status film_create_impl(const spt_scene* scene_c, const spt_camera* cam, const spt_camera_model* model, const spt_render_params* params,
+                                   uint32_t first_sample, uint32_t film_flags, spt_film** out);
+
 spt_status spt_film_create(const spt_scene* scene_c, const spt_camera* cam, const spt_render_params* params, uint32_t first_sample,
                            uint32_t film_flags, spt_film** out) {
+    return film_create_impl(scene_c, cam, nullptr, params, first_sample, film_flags, out);
+}
+
+spt_status spt_film_create_camera(const spt_scene* scene_c, const spt_camera_model* model, const spt_render_params* params, uint32_t first_sample,
+                                  uint32_t film_flags, spt_film** out) {
+    if (!scene_c || !model || !params || !out) { g_error = "film_create_camera: null argument"; return SPT_ERR_INVALID_ARG; }
+    if (model->size >= sizeof(spt_camera_model) && model->type == SPT_CAMERA_PERSPECTIVE) return spt_film_create(scene_c, &model->base, params, first_sample, film_flags, out);
+    *out = nullptr;
+    const spt_status st = check_camera_model(model, params, "film_create_camera");
+    if (st != SPT_OK) return st;
+    return film_create_impl(scene_c, &model->base, model, params, first_sample, film_flags, out);
+}
+
+// model: as render_impl's
+static spt_status film_create_impl(const spt_scene* scene_c, const spt_camera* cam, const spt_camera_model* model, const spt_render_params* params,
+                                   uint32_t first_sample, uint32_t film_flags, spt_film** out) {
     if (!scene_c || !cam || !params || !out) { g_error = "film_create: null argument"; return SPT_ERR_INVALID_ARG; }
     *out = nullptr;
     spt_scene* sc = const_cast<spt_scene*>(scene_c);
     if (sc->fwd) {
         spt_film* inner = nullptr;
-        const spt_status st = forwarded(sc->fwd, sc->fwd->film_create(sc->inner, cam, params, first_sample, film_flags, &inner));
+        if (model != nullptr && !sc->fwd->film_create_camera) { g_error = "film_create_camera: libspt_hip_bez.so does not export spt_film_create_camera"; return SPT_ERR_UNSUPPORTED; }
+        const spt_status st = forwarded(sc->fwd, model != nullptr ? sc->fwd->film_create_camera(sc->inner, model, params, first_sample, film_flags, &inner)
+                                                                  : sc->fwd->film_create(sc->inner, cam, params, first_sample, film_flags, &inner));
         if (st != SPT_OK) return st;
         spt_film* f = new (std::nothrow) spt_film;
         if (!f) { sc->fwd->film_destroy(inner); g_error = "film_create: out of host memory"; return SPT_ERR_OUT_OF_MEMORY; }
@@ -2520,6 +2636,7 @@ spt_status spt_film_create(const spt_scene* scene_c, const spt_camera* cam, cons
         auto f = std::make_unique<spt_film>();
         f->sc = sc;
         f->cam = *cam;
+        if (model != nullptr) { f->model = *model; f->model.size = (uint32_t)sizeof(spt_camera_model); }
         f->plan = p;
         f->first = first_sample;
         f->flags = film_flags;
@@ -2570,6 +2687,7 @@ spt_status spt_film_render(spt_film* f, uint32_t n_samples) {
             RenderRun run;
             run.sc = sc;
             run.cam = &f->cam;
+            run.model = f->model.type != SPT_CAMERA_PERSPECTIVE ? &f->model : nullptr;
             run.params = &p;
             run_setup(run);
             run_spans(run);
@@ -3401,6 +3519,7 @@ spt_status spt_radiance(const spt_scene* scene_c, const spt_radiance_job* job) {
                 rj.rays = sc->ray_in.as<float4>();
             }
             run.ray_aux = aux_dev;
+            run.ray_aux_wrap = n;
             rc.n_pixels = n;
             const dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
             // max_depth 0: `while curr_depth < self.max_depth` (pt.rs:48) never runs, every path is 0; the intake still reports the hits
@@ -3498,7 +3617,7 @@ spt_status spt_debug_pack_rgb8(int32_t device, uint32_t n, const float* in, uint
 }
 
 spt_status spt_debug_render_info(const spt_scene* scene_c, uint32_t what, uint64_t* out) {
-    if (!scene_c || !out || what > 7u) { g_error = "debug_render_info: null argument or unknown counter"; return SPT_ERR_INVALID_ARG; }
+    if (!scene_c || !out || what > 8u) { g_error = "debug_render_info: null argument or unknown counter"; return SPT_ERR_INVALID_ARG; }
     spt_scene* sc = const_cast<spt_scene*>(scene_c);
     if (sc->fwd) return forwarded(sc->fwd, sc->fwd->debug_render_info(sc->inner, what, out));
     std::lock_guard<std::mutex> lock(sc->mu);
@@ -3514,7 +3633,7 @@ spt_status spt_debug_render_info(const spt_scene* scene_c, uint32_t what, uint64
             return SPT_OK;
         });
     }
-    *out = what == 7u ? sc->passes_pipe : what == 0u ? sc->passes_film : what == 1u ? sc->passes_single : what == 2u ? sc->keep_read_ns : what == 3u ? sc->frames_direct : what == 4u ? sc->updates : sc->update_bytes;
+    *out = what == 8u ? sc->passes_cam : what == 7u ? sc->passes_pipe : what == 0u ? sc->passes_film : what == 1u ? sc->passes_single : what == 2u ? sc->keep_read_ns : what == 3u ? sc->frames_direct : what == 4u ? sc->updates : sc->update_bytes;
     return SPT_OK;
 }
 

@@ -1,12 +1,14 @@
 // C entry points of libspt_host.so (see include/spt_host.h for the reference
 // counterparts of each function).
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <sstream>
 
 #include "../../../include/spt_block_cand.h"
+#include "../../../include/spt_camera_models.h"
 #include "../../../include/spt_origin_cand.h"
 #include "host_scene.hpp"
 #include "json.hpp"
@@ -386,6 +388,56 @@ spt_status spt_host_origin_candidates(uint32_t n_instances, const float* inv, co
     std::memcpy(words_out, words, sizeof(uint64_t) * SPT_OC_WORDS * n_tris);
     const double out[8] = {info.center[0], info.center[1], info.center[2], info.radius, info.reach, info.delta, info.delta_scene, (double)info.tight};
     std::memcpy(info_out, out, sizeof out);
+    return SPT_OK;
+}
+
+spt_status spt_host_camera_rays(const spt_camera_model* model, const spt_render_params* plan, uint32_t first, uint32_t count, spt_path_ray* rays,
+                                spt_ray_aux* aux) {
+    if (!plan || (count != 0 && !rays)) { g_error = "camera_rays: null argument"; return SPT_ERR_INVALID_ARG; }
+    if (const char* why = spt_cm_check(model)) { g_error = std::string("camera_rays: ") + why; return SPT_ERR_INVALID_ARG; }
+    const spt_render_params& p = *plan;
+    if (p.width == 0 || p.height == 0 || p.spp == 0 || p.sampler > SPT_SAMPLER_RECURRENCE || (uint64_t)first + count > p.spp) {
+        g_error = "camera_rays: bad plan (width, height, spp > 0, a known sampler) or samples past the plan's spp";
+        return SPT_ERR_INVALID_ARG;
+    }
+    if (p.sampler == SPT_SAMPLER_JITTERED && (p.division_x == 0 || p.division_y == 0)) { g_error = "camera_rays: jittered sampler without divisions"; return SPT_ERR_INVALID_ARG; }
+    // what plan_ctx of the device library makes once per plan (pt.rs:239, 250-254, 272-275)
+    const float aspect = (float)p.width / (float)p.height, width_inv = 1.0f / (float)p.width, height_inv = 1.0f / (float)p.height;
+    const float spp_sqrt_inv = 1.0f / std::sqrt((float)p.spp);
+    const float aux_dx = aspect * width_inv * spp_sqrt_inv, aux_dy = height_inv * spp_sqrt_inv;
+    const spt_cm_plan pl = spt_cm_plan_make(model, p.width, p.height);
+    size_t k = 0;
+    for (uint32_t s = first; s < first + count; ++s)
+        for (uint32_t j = 0; j < p.height; ++j)
+            for (uint32_t i = 0; i < p.width; ++i, ++k) {
+                const uint32_t pixel = j * p.width + i;
+                float ox, oy;
+                if (p.sampler == SPT_SAMPLER_RECURRENCE) {
+                    spt_r2_offset(pixel, p.spp, s, &ox, &oy);
+                } else {
+                    spt_rng rng = spt_rng_seed(p.seed, pixel, s);
+                    const float a = spt_rng_f32(&rng), b = spt_rng_f32(&rng);
+                    if (p.sampler == SPT_SAMPLER_JITTERED) {
+                        ox = ((float)(s % p.division_x) + a) * (1.0f / (float)p.division_x);
+                        oy = ((float)(s / p.division_x) + b) * (1.0f / (float)p.division_y);
+                    } else { ox = a; oy = b; }
+                }
+                float x, y, lx = 0.0f, ly = 0.0f;
+                spt_cm_screen(i, j, p.height, ox, oy, width_inv, height_inv, aspect, &x, &y);
+                if (model->type == SPT_CAMERA_THIN_LENS) spt_cm_lens_point(p.seed, pixel, s, &lx, &ly);
+                spt_path_ray& r = rays[k];
+                std::memset(&r, 0, sizeof r);
+                spt_cm_ray(model, &pl, x, y, lx, ly, r.o, r.d);
+                r.t_min = SPT_CM_T_MIN;
+                r.stream_a = pixel;
+                r.stream_b = s;
+                if (aux) {
+                    spt_ray_aux& a = aux[k];
+                    std::memset(&a, 0, sizeof a);
+                    spt_cm_ray(model, &pl, x + aux_dx, y, lx, ly, a.rx_o, a.rx_d);
+                    spt_cm_ray(model, &pl, x, y + aux_dy, lx, ly, a.ry_o, a.ry_d);
+                }
+            }
     return SPT_OK;
 }
 

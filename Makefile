@@ -25,7 +25,7 @@ HOST_HDR := $(wildcard $(PKG)/csrc/host/*.hpp) $(wildcard include/*.h)
 HIP_SRC  := $(wildcard $(PKG)/csrc/hip/*.hip)
 HIP_HDR  := $(wildcard $(PKG)/csrc/hip/*.h) $(wildcard include/*.h)
 
-.PHONY: all host hip hip-plain cli oracle selftest out-layout-check scene-build-check scene-deform-refit-check mesh-assemble-check clean
+.PHONY: all host hip hip-plain cli oracle selftest out-layout-check scene-build-check scene-deform-refit-check mesh-assemble-check bake-check clean
 all: host oracle hip cli
 
 host: $(LIBDIR)/libspt_host.so
@@ -120,6 +120,16 @@ $(SELFTEST_DIR)/mesh_assemble_check: tests/mesh_assemble_check.cpp $(HOST_HDR) $
 	@mkdir -p $(SELFTEST_DIR)
 	$(CXX) -std=c++17 -O1 -g -Wall -Wextra -ffp-contract=off -fno-fast-math -Iinclude \
 	    -fsanitize=address,undefined -fno-sanitize-recover=undefined -static-libasan -static-libubsan -o $@ tests/mesh_assemble_check.cpp \
+	    -L$(LIBDIR) -lspt_host -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
+
+# include/spt_bake.h on the host and the lightmap rasteriser (csrc/host/bake.cpp, compiled into the program itself; the loader comes
+# from libspt_host.so, as mesh-assemble-check links it): a stand-alone host program under AddressSanitizer + UBSan
+# (tests/test_bake_host.py runs it)
+bake-check: $(SELFTEST_DIR)/bake_check
+$(SELFTEST_DIR)/bake_check: tests/bake_check.cpp $(PKG)/csrc/host/bake.cpp $(HOST_HDR) $(LIBDIR)/libspt_host.so
+	@mkdir -p $(SELFTEST_DIR)
+	$(CXX) -std=c++17 -O1 -g -Wall -Wextra -ffp-contract=off -fno-fast-math -Iinclude \
+	    -fsanitize=address,undefined -fno-sanitize-recover=undefined -static-libasan -static-libubsan -o $@ tests/bake_check.cpp $(PKG)/csrc/host/bake.cpp \
 	    -L$(LIBDIR) -lspt_host -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
 
 clean:

@@ -909,6 +909,73 @@ spt_status spt_render_camera(const spt_scene* scene, const spt_camera_model* mod
 spt_status spt_film_create_camera(const spt_scene* scene, const spt_camera_model* model, const spt_render_params* params,
                                   uint32_t first_sample, uint32_t film_flags, spt_film** out);
 
+/* ---- irradiance at surface points (additive to ABI v14: detect it by symbol) ------------------------------------------------------
+ * spt_bake returns, per point of a list of points on the scene's surfaces, the radiance a white Lambert surface would emit there:
+ * E / pi, so irradiance is pi times it.  The gather rays are made on the device, where the authoritative triangle records live
+ * (spt_scene_update, spt_scene_deform and spt_scene_deform_vertices move them without the host's copy).  include/spt_bake.h is this
+ * text as code: SPT_HD functions the kernel and spt_host_bake_rays of libspt_host.so both include.  All arithmetic is IEEE f32, one
+ * rounded operation at a time, in the written order, no contraction.
+ *
+ * Points.  SURFACE points are named the way spt_hit names a hit, so the hits_out of spt_radiance / spt_trace_closest can be fed
+ * straight back in: `instance` indexes the scene's current instance array (the order of the last update) and must be a SPT_PRIM_MESH
+ * instance; `prim` is the absolute triangle index as spt_hit::prim reports it and must lie in that mesh's [tri_first, tri_first +
+ * tri_count); v and w must be finite and are not range-checked (extrapolation is the caller's business).  The point is resolved as
+ *   u = (1.0f - v) - w;  object position (p0*u + p1*v) + p2*w, taken to the world by `fwd` as a point: ((c0*x + c1*y) + c2*z) + t;
+ *   normal exactly as a hit's is rebuilt: object n = normalize((n0*u + n1*v) + n2*w), world normalize((nrm0*n.x + nrm1*n.y) + nrm2*n.z).
+ * WORLD points give p and n as they are (unit length is the caller's business, as with spt_path_ray::d); both must be finite and n
+ * not all zero.  They serve spheres, patches and free-standing probes.  SPT_BAKE_FLIP negates every normal after it is resolved.
+ * spt_bake_point_ok / spt_bake_world_ok (spt_bake.h) state validity; the host refuses a call with them, the kernel uses them so that
+ * a bad record arriving through device pointers never indexes anything: such a point's result is the quiet NaN 0x7fc00000 in all
+ * three channels and its neighbours are unaffected.
+ *
+ * Per point i and sample k in [0, S): a = first_point + i (u32 wrap), b = first_sample + k.
+ *   Direction: rx, ry are the first two draws of spt_rng_seed(seed ^ SPT_BAKE_SEED_SALT, a, b), a stream of their own.  The cosine
+ *     map is the Lambert lobe's: phi = rx * 2.0f * SPT_PI, spt_sincos, st = spt_sqrt(ry), ct = spt_sqrt(1.0f - ry), local
+ *     (st*cp, st*sp, ct).  The frame is sphere_frame(n) (sphere.rs:70-82): s = spt_sqrt(1.0f - n.y*n.y); s != 0: bitangent =
+ *     n * (-n.y / s) with its y replaced by s, tangent = cross(bitangent, n); else n.y > 0: bitangent (1,0,0), tangent (0,0,1); else
+ *     bitangent (-1,0,0), tangent (0,0,-1).  d = normalize((tangent*lx + bitangent*ly) + n*lz), normalize with true divisions.
+ *   Gather ray: o = p, t_min = 0.0001f / spt_max(ct, 0.00001f) (the integrator's own epsilon for a bounce ray), direction d, path
+ *     stream (a, b), no draws skipped.
+ *   x(i, k) is what spt_radiance returns for exactly that record with repeats = 1, rng_skip = 0, no aux and the job's seed and
+ *     max_depth: depth 0 is a camera ray's (emission and the environment get weight 1), a textured first hit is textured without
+ *     differentials, the path starts outside any medium.
+ * Per point, once, the delta lights: D = 0; for l = 0 .. n_lights - 1 in array order, types directional, point and spot only:
+ *   dir, strength, dist are the three delta cases of the light sampler at position p (directional: -dir, strength, f32::MAX; point:
+ *   sv = pos - p, dist = sqrt(dot(sv, sv)), sv / dist, strength * (1.0f / dot(sv, sv)); spot: the same with strength * atten,
+ *   atten = clamp((dot(dir_l, -(sv / dist)) - cos_outer) / max(cos_inner - cos_outer, 0.0001f), 0, 1)).  c = dot(n, dir); skipped
+ *   unless c > 0.  li = (strength * SPT_FRAC_1_PI) * c; skipped when all three channels are 0.  The shadow ray is (p, dir, t_min =
+ *   0.0001f / spt_max(c, 0.00001f), t_max = dist - 0.001f), judged as spt_trace_any judges it; unoccluded: D = D + li.
+ *   A deterministic sum: no light sampling, no MIS.  Area lights and the environment are found by the gather rays with weight 1 and
+ *   delta lights cannot be hit, so nothing is counted twice.
+ * Result: out_i = D + (((0 + x(i,0)) + x(i,1)) + ... + x(i,S-1)) * (1.0f / (float)S), per channel, in k order.  max_depth == 0 gives
+ * D.  A point's result depends on its own record, on first_point + i and on the job's scalars only: not on its neighbours, on
+ * points_per_pass or on how samples are cut into chunks.  first_point lets a caller cut one list over calls or devices and get the
+ * same words; first_sample lets a caller add samples later and average them itself.
+ *
+ * Pointers, staging, the lock, the shared render workspace and scenes with Bezier patches: as spt_radiance.  With
+ * SPT_BAKE_DEVICE_POINTERS points (16-byte aligned) and rgb_out (4-byte aligned) are device memory on the scene's device.
+ * Refusals write nothing and leave the scene usable.  SPT_ERR_INVALID_ARG: a null scene or job; size below sizeof(spt_bake_job);
+ * unknown flags or kind; samples == 0; null points or rgb_out while n_points > 0; a host point that fails the predicate or is not
+ * finite (the message names the first such index); a device pointer that is not device memory of the scene's device or misaligned.
+ * SPT_ERR_UNSUPPORTED: max_depth > 255.  n_points == 0 returns SPT_OK and does nothing. */
+typedef struct spt_bake_point { uint32_t instance, prim; float v, w; } spt_bake_point;              /* 16 B: spt_hit without t */
+typedef struct spt_bake_world_point { float p[3], pad0, n[3], pad1; } spt_bake_world_point;         /* 32 B */
+enum { SPT_BAKE_POINTS_SURFACE = 0, SPT_BAKE_POINTS_WORLD = 1 };
+enum { SPT_BAKE_DEVICE_POINTERS = 1u, SPT_BAKE_FLIP = 2u };
+#define SPT_BAKE_SEED_SALT 0x42414B45504F4E54ull   /* "BAKEPONT": distinct from SPT_CAMERA_SEED_SALT */
+typedef struct spt_bake_job {
+    uint32_t size, flags;          /* sizeof(spt_bake_job) as the caller was compiled (the struct only grows at its tail); SPT_BAKE_* flags */
+    uint32_t kind, pad;            /* SPT_BAKE_POINTS_* */
+    uint64_t n_points;
+    const void* points;            /* n_points spt_bake_point or spt_bake_world_point */
+    float* rgb_out;                /* n_points * 3 f32 */
+    uint32_t samples, max_depth;   /* S >= 1 gather paths per point */
+    uint64_t seed;
+    uint32_t first_point, first_sample;
+    uint32_t points_per_pass, pad1;   /* tuning, 0 = default */
+} spt_bake_job;
+spt_status spt_bake(const spt_scene* scene, const spt_bake_job* job);
+
 /* Page-locked host memory for rgb_mean_out: lets the final device-to-host copy of the film run as one
  * DMA at PCIe rate instead of being staged through the runtime's bounce buffers.  Optional: any host
  * pointer is accepted by spt_render. */

@@ -141,6 +141,28 @@ spt_status spt_host_block_candidates(const spt_camera* cam, uint32_t width, uint
 spt_status spt_host_camera_rays(const spt_camera_model* model, const spt_render_params* plan, uint32_t first, uint32_t count,
                                 spt_path_ray* rays, spt_ray_aux* aux /* or NULL */);
 
+/* spt_bake's specification (include/spt_abi.h, "irradiance at surface points"; include/spt_bake.h, which the device kernel includes
+ * too) evaluated on the host over a descriptor, so that callers and tests can reproduce a bake from spt_radiance and spt_trace_any.
+ * `points`: n_points spt_bake_point (kind SPT_BAKE_POINTS_SURFACE) or spt_bake_world_point; flags: SPT_BAKE_FLIP or 0.  Every output
+ * may be NULL:
+ *   rays_out        n_points * samples gather rays in (i, k) order, streams (first_point + i, first_sample + k): spt_radiance input
+ *   pos_out, nrm_out  3 floats per point, the resolved world position and (flipped) normal
+ *   delta_rays_out  per point and light of desc->lights, [i * n_lights + l]: the shadow ray, all zero where the light is skipped
+ *   delta_li_out    3 floats at the same index: li, zeros where skipped
+ * SPT_ERR_INVALID_ARG: what spt_bake refuses of a host point (the message names the first index), an unknown kind or flag. */
+spt_status spt_host_bake_rays(const spt_scene_desc* desc, uint32_t kind, uint32_t flags, uint64_t n_points, const void* points, uint32_t samples,
+                              uint64_t seed, uint32_t first_point, uint32_t first_sample, spt_path_ray* rays_out, float* pos_out, float* nrm_out,
+                              spt_ray* delta_rays_out, float* delta_li_out);
+/* The texels of a width x height lightmap of the mesh instance called `instance_name`, as bake points.  The centre of texel (x, y) is
+ * uv ((x + 0.5) / W, (y + 0.5) / H), no wrap, no flip.  It is tested against the uv triangles of the instance's mesh in triangle
+ * order: E(a, b, p) = (b.x - a.x) * (p.y - a.y) - (b.y - a.y) * (p.x - a.x) in double, area = E(uv0, uv1, uv2), b0 = E(uv1, uv2, p) / area,
+ * b1 = E(uv2, uv0, p) / area, b2 = E(uv0, uv1, p) / area; inside when all three are >= 0; zero-area uv triangles are skipped; the lowest
+ * triangle index wins.  Emits {instance (its current index), prim, (float)b1, (float)b2} and the texel's linear index y * W + x, in
+ * texel order; uncovered texels are omitted.  *n_out is the number of covered texels; at most `capacity` records are written
+ * (capacity == 0 only counts, the outputs may then be NULL).  No dilation, no conservative coverage. */
+spt_status spt_host_lightmap_points(const spt_host_scene* scene, const char* instance_name, uint32_t width, uint32_t height,
+                                    spt_bake_point* points_out, uint32_t* texels_out, uint64_t capacity, uint64_t* n_out);
+
 /* The per-origin-triangle candidate table of include/spt_origin_cand.h on the host, for checking it without a device.  Instance i
  * has the spt_instance matrices inv / fwd (12 floats each) and the normal matrix nrm (9 floats); triangle k (at most 64) belongs
  * to instance tri_instance[k], with tri_pos 9 floats (p0, p1, p2, object space) and tri_nrm its 3 vertex normals; its slot and its

@@ -320,6 +320,20 @@ class RadianceJob(C.Structure):
                 ("rays_per_pass", C.c_uint32), ("rgb_out", C.c_void_p), ("hits_out", C.c_void_p)]
 
 
+# spt_bake: spt_bake_point (16 B: spt_hit without t) and spt_bake_world_point (32 B)
+BAKE_POINT_DTYPE = np.dtype([("instance", "<u4"), ("prim", "<u4"), ("v", "<f4"), ("w", "<f4")])
+BAKE_WORLD_DTYPE = np.dtype([("p", "<f4", 3), ("pad0", "<f4"), ("n", "<f4", 3), ("pad1", "<f4")])
+BAKE_POINTS_SURFACE, BAKE_POINTS_WORLD = 0, 1
+BAKE_DEVICE_POINTERS, BAKE_FLIP = 1, 2
+
+
+class BakeJob(C.Structure):
+    """spt_bake_job (spt_bake); `size` is sizeof of the struct."""
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("kind", C.c_uint32), ("pad", C.c_uint32), ("n_points", C.c_uint64),
+                ("points", C.c_void_p), ("rgb_out", C.c_void_p), ("samples", C.c_uint32), ("max_depth", C.c_uint32), ("seed", C.c_uint64),
+                ("first_point", C.c_uint32), ("first_sample", C.c_uint32), ("points_per_pass", C.c_uint32), ("pad1", C.c_uint32)]
+
+
 # ---- library loading -----------------------------------------------------------------
 
 class SceneUpdateDesc(C.Structure):
@@ -411,6 +425,11 @@ def host_lib() -> C.CDLL:
                                                                                              C.POINTER(C.c_uint64)]
         if hasattr(lib, "spt_host_camera_rays"):
             lib.spt_host_camera_rays.argtypes = [C.POINTER(CameraModel), C.POINTER(RenderParams), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        if hasattr(lib, "spt_host_bake_rays"):
+            lib.spt_host_bake_rays.argtypes = [C.POINTER(SceneDesc), C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32,
+                                               C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            lib.spt_host_lightmap_points.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                     C.POINTER(C.c_uint64)]
         lib.spt_host_load_renderer.argtypes = [C.c_char_p, C.POINTER(RenderParams), C.POINTER(C.c_float)]
         if hasattr(lib, "spt_host_load_renderer_filter"):   # (a library built before the weighted filters lacks it)
             lib.spt_host_load_renderer_filter.argtypes = [C.c_char_p, C.POINTER(RenderParams), C.POINTER(FilterDesc)]
@@ -483,6 +502,8 @@ def hip_lib() -> C.CDLL:
             lib.spt_denoise_image.argtypes = [C.c_void_p, C.POINTER(ImageDenoiseJob), C.c_void_p]
         if hasattr(lib, "spt_radiance"):   # (the same)
             lib.spt_radiance.argtypes = [C.c_void_p, C.POINTER(RadianceJob)]
+        if hasattr(lib, "spt_bake"):   # (the same)
+            lib.spt_bake.argtypes = [C.c_void_p, C.POINTER(BakeJob)]
         if hasattr(lib, "spt_scene_update"):   # (the same)
             lib.spt_scene_update.argtypes = [C.c_void_p, C.POINTER(SceneUpdateDesc)]
         if hasattr(lib, "spt_scene_deform"):   # (the same)
@@ -571,6 +592,20 @@ class Scene:
         if not hasattr(lib, "spt_host_scene_set_transforms"):
             raise SptError(4, "this libspt_host.so cannot edit a loaded scene (no spt_host_scene_set_transforms)")
         return lib
+
+    def lightmap_points(self, name: str, width: int, height: int):
+        """spt_host_lightmap_points: the covered texels of a width x height lightmap of the mesh instance `name` as (points, texels):
+        BAKE_POINT_DTYPE records for DeviceScene.bake and the texels' linear indices y * width + x, in texel order.  The centre of
+        texel (x, y) is uv ((x + 0.5) / W, (y + 0.5) / H); the lowest triangle index that contains it wins; no dilation."""
+        lib = host_lib()
+        if not hasattr(lib, "spt_host_lightmap_points"):
+            raise SptError(4, "libspt_host.so does not export spt_host_lightmap_points")
+        n = C.c_uint64(0)
+        _check_host(lib.spt_host_lightmap_points(self._h, name.encode(), width, height, None, None, 0, C.byref(n)))
+        points, texels = np.zeros(n.value, dtype=BAKE_POINT_DTYPE), np.zeros(n.value, dtype=np.uint32)
+        if n.value:
+            _check_host(lib.spt_host_lightmap_points(self._h, name.encode(), width, height, points.ctypes.data, texels.ctypes.data, n.value, C.byref(n)))
+        return points, texels
 
     def instance_index(self, name: str) -> int:
         """The index of the instance called `name` in the CURRENT descriptor (set_transforms reorders the instances)."""
@@ -806,6 +841,39 @@ class DeviceScene:
         _check_hip(lib.spt_radiance(self._h, C.byref(job)))
         return (out, hit) if hits else out
 
+    def bake(self, points, samples: int = 16, max_depth: int = 8, seed: int = 1, first_point: int = 0, first_sample: int = 0,
+             points_per_pass: int = 0, world: bool = False, flip: bool = False):
+        """spt_bake: per point on the scene's surfaces the radiance a white Lambert surface would emit there (E / pi), (n, 3) f32.
+        points are BAKE_POINT_DTYPE records (instance, prim, v, w: the fields of a hit), or BAKE_WORLD_DTYPE records (p, n) with
+        world=True; or contiguous float32 torch tensors on the scene's device of shape (n, 4) / (n, 8) holding the same records
+        (instance / prim as bit patterns): then the producer's current stream is synchronised, the library reads and writes device
+        memory and the result is a tensor.  flip negates every normal."""
+        lib = hip_lib()
+        if not hasattr(lib, "spt_bake"):
+            raise SptError(4, "this libspt_hip.so has no spt_bake")
+        job = BakeJob(size=C.sizeof(BakeJob), flags=BAKE_FLIP if flip else 0, kind=BAKE_POINTS_WORLD if world else BAKE_POINTS_SURFACE, samples=samples,
+                      max_depth=max_depth, seed=seed, first_point=first_point & 0xffffffff, first_sample=first_sample, points_per_pass=points_per_pass)
+        if type(points).__module__.split(".")[0] == "torch":
+            import torch
+            words = 8 if world else 4
+            if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != words or not points.is_contiguous():
+                raise ValueError("points: a contiguous float32 (n, %d) tensor is expected" % words)
+            if points.device.type != "cuda" or points.device.index != self.device:
+                raise ValueError("points: the tensor must live on the scene's device (cuda:%d)" % self.device)
+            n = points.shape[0]
+            out = torch.empty((n, 3), dtype=torch.float32, device=points.device)
+            torch.cuda.current_stream(points.device).synchronize()   # the points are complete before the library's stream reads them
+            job.flags |= BAKE_DEVICE_POINTERS
+            job.n_points, job.points, job.rgb_out = n, points.data_ptr() if n else None, out.data_ptr() if n else None
+            _check_hip(lib.spt_bake(self._h, C.byref(job)))
+            return out
+        points = np.ascontiguousarray(points, dtype=BAKE_WORLD_DTYPE if world else BAKE_POINT_DTYPE).reshape(-1)
+        n = points.shape[0]
+        out = np.zeros((n, 3), dtype=np.float32)
+        job.n_points, job.points, job.rgb_out = n, points.ctypes.data, out.ctypes.data
+        _check_hip(lib.spt_bake(self._h, C.byref(job)))
+        return out
+
     def update(self) -> None:
         """spt_scene_update with the Scene's current tlas_nodes, instances, lights and light alias table (after
         Scene.set_transforms / set_light): the device scene then behaves like one freshly created from the Scene.  Frames queued
@@ -1031,6 +1099,44 @@ def _camera_entry(name: str):
     if fn is None:
         raise SptError(4, "libspt_hip.so does not export %s (no camera models)" % name)
     return fn
+
+
+def bake_rays(scene: "Scene", points, samples: int = 16, seed: int = 1, first_point: int = 0, first_sample: int = 0, world: bool = False,
+              flip: bool = False):
+    """spt_host_bake_rays: spt_bake's specification (include/spt_bake.h) evaluated on the host over the Scene's descriptor.  Returns
+    a dict: "rays" (n, samples) PATH_RAY_DTYPE gather rays (radiance input), "pos" / "nrm" (n, 3) f32 the resolved points,
+    "delta_rays" (n, n_lights) RAY_DTYPE shadow rays and "delta_li" (n, n_lights, 3) f32 per delta light (zeros where skipped).
+    A bake is D + the in-order mean over k of DeviceScene.radiance(rays[:, k]), D the in-order sum of delta_li where
+    DeviceScene.trace_any(delta_rays) finds nothing."""
+    lib = host_lib()
+    if not hasattr(lib, "spt_host_bake_rays"):
+        raise SptError(4, "libspt_host.so does not export spt_host_bake_rays")
+    points = np.ascontiguousarray(points, dtype=BAKE_WORLD_DTYPE if world else BAKE_POINT_DTYPE).reshape(-1)
+    n, desc = points.shape[0], scene.desc
+    nl = int(desc.n_lights)
+    out = {"rays": np.zeros((n, samples), dtype=PATH_RAY_DTYPE), "pos": np.zeros((n, 3), dtype=np.float32), "nrm": np.zeros((n, 3), dtype=np.float32),
+           "delta_rays": np.zeros((n, nl), dtype=RAY_DTYPE), "delta_li": np.zeros((n, nl, 3), dtype=np.float32)}
+    _check_host(lib.spt_host_bake_rays(C.byref(desc), BAKE_POINTS_WORLD if world else BAKE_POINTS_SURFACE, BAKE_FLIP if flip else 0, n, points.ctypes.data,
+                                       samples, seed, first_point & 0xffffffff, first_sample, out["rays"].ctypes.data, out["pos"].ctypes.data,
+                                       out["nrm"].ctypes.data, out["delta_rays"].ctypes.data, out["delta_li"].ctypes.data))
+    return out
+
+
+def vertex_points(scene: "Scene", name: str) -> np.ndarray:
+    """One bake point per triangle corner of the mesh instance `name`, (tri_count, 3) BAKE_POINT_DTYPE: corner c of a triangle has
+    (v, w) = (0, 0), (1, 0), (0, 1).  Per-vertex lighting is a bake over these, averaged over the corners that share a vertex."""
+    inst = scene.instance_index(name)
+    d = scene.desc
+    rec = d.instances[inst]
+    if rec.prim_type != 1:
+        raise ValueError("%s is not a triangle-mesh instance" % name)
+    mesh = d.meshes[rec.prim_id]
+    pts = np.zeros((int(mesh.tri_count), 3), dtype=BAKE_POINT_DTYPE)
+    pts["instance"] = inst
+    pts["prim"] = (int(mesh.tri_first) + np.arange(int(mesh.tri_count), dtype=np.uint32))[:, None]
+    pts["v"] = np.array([0.0, 1.0, 0.0], dtype=np.float32)[None, :]
+    pts["w"] = np.array([0.0, 0.0, 1.0], dtype=np.float32)[None, :]
+    return pts
 
 
 def camera_rays(model: "CameraModel", renderer: "PathTracer", width: int, height: int, first: int = 0, count: Optional[int] = None,

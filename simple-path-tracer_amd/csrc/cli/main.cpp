@@ -44,6 +44,7 @@ static void usage() {
                  "           [--robust K [--robust-estimator mon|gmon] [--mean-out mean.png]]   (K odd, 3 .. 15)\n"
                  "           [--film-devices a,b,..]   (the progressive options above over several devices)\n"
                  "           [--lens-radius R --focus-distance D | --orthographic H | --panorama]   (a camera model in the scene camera's place)\n"
+                 "           [--bake-lightmap INSTANCE --bake-size WxH [--bake-samples N]]   (a float RGB EXR lightmap of a mesh instance: E / pi per texel)\n"
                  "           [--animate frames.json]   (one plain image <out>_NNNN per frame: {\"frames\": [{\"<instance>\": {<transform>}, ..}, ..]})\n");
 }
 
@@ -233,6 +234,9 @@ int main(int argc, char** argv) {
     // camera models (spt_render_camera / spt_film_create_camera): a thin lens, an orthographic view or an equirectangular panorama
     double lens_radius = 0.0, focus_distance = 0.0, view_height = 0.0;
     bool lens_given = false, focus_given = false, ortho_given = false, panorama = false;
+    // --bake-lightmap INSTANCE --bake-size WxH [--bake-samples N]: spt_bake over the texels of the instance's lightmap
+    std::string bake_instance, bake_size;
+    uint32_t bake_samples = 16;
     std::vector<int32_t> device_list;
     std::vector<int32_t> film_devices;
     bool film_devices_given = false, film_devices_ok = true;
@@ -286,6 +290,9 @@ int main(int argc, char** argv) {
         else if (a == "--focus-distance") { focus_distance = std::atof(next()); focus_given = true; }
         else if (a == "--orthographic") { view_height = std::atof(next()); ortho_given = true; }
         else if (a == "--panorama") panorama = true;
+        else if (a == "--bake-lightmap") bake_instance = next();
+        else if (a == "--bake-size") bake_size = next();
+        else if (a == "--bake-samples") bake_samples = (uint32_t)std::atoi(next());
         else if (a == "--film-devices") { film_devices_given = true; film_devices_ok = parse_device_list(next(), &film_devices); }
         else { usage(); return 2; }
     }
@@ -333,6 +340,22 @@ int main(int argc, char** argv) {
     }
     const uint32_t estimator = robust_estimator == "mon" ? (uint32_t)SPT_ROBUST_MON : (uint32_t)SPT_ROBUST_GMON;
     bool progressive = preview_every > 0 || time_limit > 0.0 || !variance_out.empty() || adaptive_on || !samples_out.empty() || denoise || robust;
+    uint32_t bake_w = 0, bake_h = 0;
+    if (!bake_instance.empty() || !bake_size.empty()) {
+        unsigned bw = 0, bh = 0;
+        char tail = 0;
+        if (bake_instance.empty() || std::sscanf(bake_size.c_str(), "%ux%u%c", &bw, &bh, &tail) != 2 || bw == 0 || bh == 0 || bake_samples == 0) {
+            std::fprintf(stderr, "Error: a lightmap needs --bake-lightmap INSTANCE and --bake-size WxH (and --bake-samples N >= 1)\n");
+            return 2;
+        }
+        if (progressive || camera_model || !animate_path.empty() || gpus > 0 || film_devices_given || debug_normal) {
+            std::fprintf(stderr, "Error: --bake-lightmap bakes on one device (--device D): not with a film option (--preview-every, --time-limit, --variance-out, "
+                                 "--adaptive, --samples-out, --denoise, --robust, --film-devices), a camera model, --animate, --debug-normal or --gpus / --devices\n");
+            return 2;
+        }
+        bake_w = bw;
+        bake_h = bh;
+    }
     if (film_devices_given && !film_devices_ok) {
         std::fprintf(stderr, "Error: --film-devices takes a list of device indices such as 0,1,2 (an index may repeat)\n");
         return 2;
@@ -441,6 +464,46 @@ int main(int argc, char** argv) {
                              "reaches neighbouring pixels (--preview-every, --time-limit and --film-devices work with it)\n", (double)params.filter_radius);
         spt_host_scene_free(hs);
         return 2;
+    }
+    if (!bake_instance.empty()) {   // the lightmap: max_depth from the renderer file, the seed of --seed; uncovered texels are 0
+        auto bake_fail = [&](const char* what) {
+            std::fprintf(stderr, "Error: %s\n", what);
+            spt_host_scene_free(hs);
+            return 1;
+        };
+        uint64_t n_points = 0;
+        if (spt_host_lightmap_points(hs, bake_instance.c_str(), bake_w, bake_h, nullptr, nullptr, 0, &n_points) != SPT_OK) return bake_fail(spt_host_last_error());
+        std::vector<spt_bake_point> points(n_points);
+        std::vector<uint32_t> texels(n_points);
+        if (n_points && spt_host_lightmap_points(hs, bake_instance.c_str(), bake_w, bake_h, points.data(), texels.data(), n_points, &n_points) != SPT_OK)
+            return bake_fail(spt_host_last_error());
+        std::vector<float> map((size_t)bake_w * bake_h * 3, 0.0f), rgb(points.size() * 3);
+        const auto t_bake = std::chrono::steady_clock::now();
+        if (!points.empty()) {
+            spt_scene* scene = nullptr;
+            if (spt_scene_create(spt_host_scene_desc(hs), device, &scene) != SPT_OK) return bake_fail(spt_last_error());
+            spt_bake_job job;
+            std::memset(&job, 0, sizeof job);
+            job.size = (uint32_t)sizeof job;
+            job.kind = SPT_BAKE_POINTS_SURFACE;
+            job.n_points = points.size();
+            job.points = points.data();
+            job.rgb_out = rgb.data();
+            job.samples = bake_samples;
+            job.max_depth = params.max_depth;
+            job.seed = seed;
+            const spt_status e = spt_bake(scene, &job);
+            const std::string why = e == SPT_OK ? "" : spt_last_error();
+            spt_scene_destroy(scene);
+            if (e != SPT_OK) return bake_fail(why.c_str());
+        }
+        for (size_t k = 0; k < points.size(); ++k)
+            for (int c = 0; c < 3; ++c) map[3 * (size_t)texels[k] + c] = rgb[3 * k + c];
+        if (spt_host_write_exr(out_path.c_str(), map.data(), bake_w, bake_h) != SPT_OK) return bake_fail(spt_host_last_error());
+        const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_bake).count();
+        std::fprintf(stderr, "Finished, time used: %.3fs (%zu of %zu texels covered, %u samples each)\n", sec, points.size(), (size_t)bake_w * bake_h, bake_samples);
+        spt_host_scene_free(hs);
+        return 0;
     }
     const uint32_t keep_flag = (wide_box || weighted) ? (uint32_t)SPT_FILM_KEEP_SAMPLES : 0u;
     spt_camera cam;

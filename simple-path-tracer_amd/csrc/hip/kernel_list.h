@@ -3,6 +3,7 @@
 // only launches them, gets explicit instantiation DECLARATIONS so that it compiles none of them).  One monolithic
 // .hip took ~4 minutes per library build; split this way the groups compile side by side.
 // (inst_deform.hip is a unit of the same kind without templates: spt_scene_deform's kernels, declared in deform_kernels.h.)
+// (inst_bake.hip: spt_bake's kernels, bake_kernels.h - k_bake_intake<true>, k_bake_intake<false>, k_bake_intake_stream, k_bake_finish.)
 #pragma once
 #include "kernels.h"
 

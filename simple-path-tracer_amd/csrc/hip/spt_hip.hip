@@ -24,6 +24,7 @@
 #include "kernel_list.h"   // the heavy kernel templates: declared here, compiled in inst_*.hip
 #include "film_kernels.h"
 #include "radiance_kernels.h"
+#include "bake_kernels.h"
 #include "camera_kernels.h"   // k_primary_cam: declared here, compiled in inst_camera.hip
 #include "deform_kernels.h"   // spt_scene_deform's kernels: declared here, compiled in inst_deform.hip
 #include "abi_error.h"     // AbiError, fail
@@ -145,6 +146,7 @@ struct BezierLib {
     decltype(&spt_scene_read_triangles) scene_read_triangles = nullptr;     // (the same)
     decltype(&spt_render_camera) render_camera = nullptr;             // (the same)
     decltype(&spt_film_create_camera) film_create_camera = nullptr;   // (the same)
+    decltype(&spt_bake) bake = nullptr;                               // (the same)
     decltype(&spt_debug_bxdf) debug_bxdf = nullptr;
     decltype(&spt_debug_render_info) debug_render_info = nullptr;
     decltype(&spt_last_error) last_error = nullptr;
@@ -493,6 +495,7 @@ const BezierLib* bezier_lib() {
         (void)sym(lib.scene_read_triangles, "spt_scene_read_triangles");
         (void)sym(lib.render_camera, "spt_render_camera");
         (void)sym(lib.film_create_camera, "spt_film_create_camera");
+        (void)sym(lib.bake, "spt_bake");
         if (!all || version() != SPT_ABI_VERSION) {
             err = path + " does not export ABI version " + std::to_string(SPT_ABI_VERSION);
             return;
@@ -3549,6 +3552,166 @@ spt_status spt_radiance(const spt_scene* scene_c, const spt_radiance_job* job) {
         } else {
             HIP_CHECK(hipStreamSynchronize(st));
         }
+        return SPT_OK;
+    });
+}
+
+// ---- irradiance at surface points (spt_bake) ----
+static void check_bake_pointer(const spt_scene* sc, const void* p, const char* what, bool align16) {
+    hipPointerAttribute_t at;
+    std::memset(&at, 0, sizeof at);
+    const hipError_t e = hipPointerGetAttributes(&at, p);
+    if (e != hipSuccess) (void)hipGetLastError();
+    if (e != hipSuccess || at.type != hipMemoryTypeDevice || at.device != sc->device)
+        fail(SPT_ERR_INVALID_ARG, std::string("bake: SPT_BAKE_DEVICE_POINTERS and `") + what + "` is not device memory on the scene's device");
+    if ((reinterpret_cast<uintptr_t>(p) & (align16 ? 15u : 3u)) != 0)
+        fail(SPT_ERR_INVALID_ARG, std::string("bake: device pointer `") + what + "` is not " + (align16 ? "16" : "4") + "-byte aligned");
+}
+
+// spt_radiance with the rays made by the intake kernel (bake_kernels.h): passes of P points x chunks of R samples under the same
+// capacity rules, the same staging slots, workspace and delivery
+spt_status spt_bake(const spt_scene* scene_c, const spt_bake_job* job) {
+    if (!scene_c || !job) { g_error = "bake: null argument"; return SPT_ERR_INVALID_ARG; }
+    if (job->size < sizeof(spt_bake_job)) { g_error = "bake: job->size is below sizeof(spt_bake_job)"; return SPT_ERR_INVALID_ARG; }
+    if (job->flags & ~(uint32_t)(SPT_BAKE_DEVICE_POINTERS | SPT_BAKE_FLIP)) { g_error = "bake: unknown flags"; return SPT_ERR_INVALID_ARG; }
+    if (job->kind > SPT_BAKE_POINTS_WORLD) { g_error = "bake: unknown kind of points"; return SPT_ERR_INVALID_ARG; }
+    if (job->samples == 0) { g_error = "bake: samples must be >= 1"; return SPT_ERR_INVALID_ARG; }
+    if (job->n_points != 0 && (!job->points || !job->rgb_out)) { g_error = "bake: null points or rgb_out"; return SPT_ERR_INVALID_ARG; }
+    if (job->max_depth > 255) { g_error = "bake: max_depth > 255"; return SPT_ERR_UNSUPPORTED; }
+    spt_scene* sc = const_cast<spt_scene*>(scene_c);
+    if (sc->fwd) {
+        if (!sc->fwd->bake) { g_error = "bake: libspt_hip_bez.so does not export spt_bake"; return SPT_ERR_UNSUPPORTED; }
+        return forwarded(sc->fwd, sc->fwd->bake(sc->inner, job));
+    }
+    if (job->n_points == 0) return SPT_OK;
+    std::lock_guard<std::mutex> lock(sc->mu);
+    return guarded("bake", [&] {
+        const uint64_t n_points = job->n_points;
+        const uint32_t S = job->samples;
+        const bool dev = (job->flags & SPT_BAKE_DEVICE_POINTERS) != 0;
+        const bool world = job->kind == SPT_BAKE_POINTS_WORLD;
+        const size_t rec_bytes = world ? sizeof(spt_bake_world_point) : sizeof(spt_bake_point);
+        if (n_points > (1ull << 40)) fail(SPT_ERR_UNSUPPORTED, "bake: more than 2^40 points");
+        HIP_CHECK(hipSetDevice(sc->device));
+        if (dev) {   // every check comes before the first allocation, copy or launch
+            check_bake_pointer(sc, job->points, "points", true);
+            check_bake_pointer(sc, job->rgb_out, "rgb_out", false);
+        } else {     // ... and a host list is checked as a whole, so that a refusal has written nothing at all
+            // SURFACE points are checked against the scene's CURRENT tables: the instance records as the device holds them behind the
+            // updates queued so far (read back as spt_trace_* read their results back), the meshes' ranges from the creation
+            const SceneFixed& fx = sc->fixed;
+            std::vector<spt_instance> inst_tab(world ? 0 : fx.n_instances);
+            std::vector<spt_mesh> mesh_tab(fx.n_meshes);
+            for (uint32_t m = 0; m < fx.n_meshes; ++m) mesh_tab[m] = spt_mesh{0u, 0u, fx.mesh_first[m], fx.mesh_tris[m]};
+            if (!inst_tab.empty()) {
+                film_join(sc);
+                HIP_CHECK(hipMemcpyAsync(inst_tab.data(), sc->instances.p, inst_tab.size() * sizeof(spt_instance), hipMemcpyDeviceToHost, sc->stream));
+                HIP_CHECK(hipStreamSynchronize(sc->stream));
+            }
+            const uint32_t n_inst = (uint32_t)inst_tab.size(), n_mesh = fx.n_meshes;
+            const uint32_t* const inst_words = inst_tab.empty() ? nullptr : &inst_tab[0].prim_type;
+            for (uint64_t i = 0; i < n_points; ++i) {
+                const bool ok = world ? spt_bake_world_ok(static_cast<const spt_bake_world_point*>(job->points) + i)
+                                      : spt_bake_point_ok(static_cast<const spt_bake_point*>(job->points) + i, n_inst, inst_words, (uint32_t)(sizeof(spt_instance) / sizeof(uint32_t)), n_mesh, mesh_tab.data());
+                if (!ok)
+                    fail(SPT_ERR_INVALID_ARG, "bake: point " + std::to_string(i) +
+                                                  (world ? " has a non-finite p or n or an all-zero n"
+                                                         : " does not name a triangle of a mesh instance (instance, prim) or has a non-finite v or w"));
+            }
+        }
+        film_join(sc);
+        spt_render_params plan{};      // what run_setup and bounce read of a plan
+        plan.max_depth = job->max_depth;
+        const spt_camera no_camera{};
+        RenderRun run;
+        run.sc = sc;
+        run.cam = &no_camera;
+        run.params = &plan;
+        run.rays = true;
+        run_setup(run);
+        const hipStream_t st = run.st;
+
+        // Passes of P points x chunks of R samples, around 2^22 paths each, as spt_radiance cuts rays x repetitions
+        constexpr uint64_t kStep = (uint64_t)kShards * kBlock, kTargetPaths = 1ull << 22;
+        uint64_t P64 = job->points_per_pass ? job->points_per_pass : std::max(kStep, kTargetPaths / S / kStep * kStep);
+        P64 = std::min(P64, n_points);
+        const uint32_t P = (uint32_t)P64;
+        const uint64_t P_up = (P64 + kStep - 1) / kStep * kStep;
+        const uint32_t R = (uint32_t)std::min<uint64_t>(S, std::max<uint64_t>(1, 2 * kTargetPaths / P_up));
+        if (P_up * R > 0x7fffffffull) fail(SPT_ERR_UNSUPPORTED, "bake: pass too large (lower points_per_pass)");
+
+        RenderCtx rc{};
+        rc.max_depth = job->max_depth;
+        rc.seed = job->seed;
+        rc.spp = S;
+        const size_t counts_words = grow_ray_workspace(sc, P, job->max_depth ? R : 0u, job->max_depth, run.fused, run.class_queues, rc);
+        rc.dyn_refill_below = run.dyn_refill_below;
+        rc.dyn_steps = run.dyn_steps;
+        rc.stream_rounds = run.stream_rounds;
+        rc.stream_refill_below = run.stream_refill_below;
+        rc.visits = sc->visits.as<unsigned long long>();
+        sc->ray_hits.ensure((size_t)P * 4 * sizeof(float));   // D and validity per point of a pass, 4 planes (bake_kernels.h): spt_radiance's hit buffer, idle here
+        float* rgb_dev = job->rgb_out;
+        if (!dev) {
+            const size_t in_bytes = (size_t)P * rec_bytes;
+            for (int k = 0; k < 2; ++k) {
+                sc->ray_stage[k].ensure(in_bytes);
+                if (!sc->ev_ray[k]) HIP_CHECK(hipEventCreateWithFlags(&sc->ev_ray[k], hipEventDisableTiming));
+            }
+            sc->ray_in.ensure(in_bytes);
+            sc->ray_rgb.ensure((size_t)n_points * 3 * sizeof(float));
+            rgb_dev = sc->ray_rgb.as<float>();
+        }
+        const bool stream = sc->swalk && !sc->lds_geo;   // the walkers of spt_trace_closest / spt_trace_any
+        const float inv = 1.0f / (float)S;
+        uint64_t pass = 0;
+        for (uint64_t r0 = 0; r0 < n_points; r0 += P, ++pass) {
+            const uint32_t n = (uint32_t)std::min<uint64_t>(P, n_points - r0);
+            BakeJob bj{};
+            bj.seed = job->seed;
+            bj.n = n;
+            bj.rgb_out = rgb_dev + 3 * r0;
+            bj.d_planes = sc->ray_hits.as<float>();
+            bj.stream_a = job->first_point + (uint32_t)r0;   // (u32 wrap)
+            bj.stream_b = job->first_sample;
+            bj.kind = job->kind;
+            bj.flip = (job->flags & SPT_BAKE_FLIP) ? 1u : 0u;
+            const char* const src = static_cast<const char*>(job->points) + r0 * rec_bytes;
+            if (dev) {
+                bj.points = reinterpret_cast<const float4*>(src);
+            } else {
+                // the slot's previous copy (two passes ago) has left it
+                PinnedBuffer& slot = sc->ray_stage[pass & 1u];
+                if (pass >= 2) HIP_CHECK(hipEventSynchronize(sc->ev_ray[pass & 1u]));
+                std::memcpy(slot.p, src, (size_t)n * rec_bytes);
+                HIP_CHECK(hipMemcpyAsync(sc->ray_in.p, slot.p, (size_t)n * rec_bytes, hipMemcpyHostToDevice, st));
+                HIP_CHECK(hipEventRecord(sc->ev_ray[pass & 1u], st));
+                bj.points = sc->ray_in.as<float4>();
+            }
+            run.ray_aux = nullptr;
+            run.ray_aux_wrap = n;
+            rc.n_pixels = n;
+            const dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
+            // max_depth 0: no path runs and out = D; the intake still sums the delta lights
+            const uint32_t k_end = job->max_depth ? S : 0u;
+            for (uint64_t k0 = 0; k0 == 0u || k0 < k_end; k0 += R) {
+                bj.k_first = (uint32_t)k0;
+                bj.reps = (uint32_t)std::min<uint64_t>(R, k_end - std::min<uint64_t>(k0, k_end));
+                rc.pass_first = (uint32_t)k0;
+                rc.pass_samples = bj.reps;
+                rc.rad_plane = (size_t)std::max(bj.reps, 1u) * n;
+                HIP_CHECK(hipMemsetAsync(rc.counts, 0, counts_words * sizeof(uint32_t), st));
+                hipLaunchKernelGGL(stream ? k_bake_intake_stream : sc->lds_geo ? k_bake_intake<true> : k_bake_intake<false>, grid, block, sc->lds_bytes, st, sc->d,
+                                   rc, bj);
+                HIP_CHECK(hipGetLastError());
+                for (uint32_t b = 0; b < (bj.reps ? job->max_depth : 0u); ++b)
+                    if (bounce(run, rc, b, st)) break;
+                hipLaunchKernelGGL(k_bake_finish, grid, block, 0, st, rc, bj, k0 == 0u ? 1u : 0u, k0 + R >= k_end ? 1u : 0u, inv);
+                HIP_CHECK(hipGetLastError());
+            }
+        }
+        if (!dev) deliver(sc->img_out8, sc->ray_rgb.p, (size_t)n_points * 3, FilmReadOut{job->rgb_out, nullptr}, st);   // the device-to-host path of the film read-outs
+        else HIP_CHECK(hipStreamSynchronize(st));
         return SPT_OK;
     });
 }

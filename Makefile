@@ -25,7 +25,7 @@ HOST_HDR := $(wildcard $(PKG)/csrc/host/*.hpp) $(wildcard include/*.h)
 HIP_SRC  := $(wildcard $(PKG)/csrc/hip/*.hip)
 HIP_HDR  := $(wildcard $(PKG)/csrc/hip/*.h) $(wildcard include/*.h)
 
-.PHONY: all host hip hip-plain cli oracle selftest out-layout-check scene-build-check scene-deform-refit-check mesh-assemble-check bake-check clean
+.PHONY: all host hip hip-plain cli oracle selftest out-layout-check scene-build-check scene-deform-refit-check mesh-assemble-check bake-check probe-check clean
 all: host oracle hip cli
 
 host: $(LIBDIR)/libspt_host.so
@@ -130,6 +130,16 @@ $(SELFTEST_DIR)/bake_check: tests/bake_check.cpp $(PKG)/csrc/host/bake.cpp $(HOS
 	@mkdir -p $(SELFTEST_DIR)
 	$(CXX) -std=c++17 -O1 -g -Wall -Wextra -ffp-contract=off -fno-fast-math -Iinclude \
 	    -fsanitize=address,undefined -fno-sanitize-recover=undefined -static-libasan -static-libubsan -o $@ tests/bake_check.cpp $(PKG)/csrc/host/bake.cpp \
+	    -L$(LIBDIR) -lspt_host -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
+
+# include/spt_probe.h on the host and the host entry points of csrc/host/probe.cpp (compiled into the program itself; the error
+# channel comes from libspt_host.so) over degenerate inputs: a stand-alone host program under AddressSanitizer + UBSan
+# (tests/test_probe_host.py runs it)
+probe-check: $(SELFTEST_DIR)/probe_check
+$(SELFTEST_DIR)/probe_check: tests/probe_check.cpp $(PKG)/csrc/host/probe.cpp $(HOST_HDR) $(LIBDIR)/libspt_host.so
+	@mkdir -p $(SELFTEST_DIR)
+	$(CXX) -std=c++17 -O1 -g -Wall -Wextra -ffp-contract=off -fno-fast-math -Iinclude \
+	    -fsanitize=address,undefined -fno-sanitize-recover=undefined -static-libasan -static-libubsan -o $@ tests/probe_check.cpp $(PKG)/csrc/host/probe.cpp \
 	    -L$(LIBDIR) -lspt_host -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
 
 clean:

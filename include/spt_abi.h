@@ -976,6 +976,62 @@ typedef struct spt_bake_job {
 } spt_bake_job;
 spt_status spt_bake(const spt_scene* scene, const spt_bake_job* job);
 
+/* ---- spherical-harmonic light probes (additive to ABI v14: detect it by symbol) --------------------------------------------------
+ * spt_probe returns, per free point in space, the incident radiance there projected onto the nine real spherical harmonics of bands
+ * 0 .. 2, per colour channel, and (optionally) a visibility record that tells a probe buried in geometry from a free one.  The gather
+ * rays are made on the device.  include/spt_probe.h is this text as code: functions the kernels and spt_host_probe_rays of
+ * libspt_host.so both include.  All arithmetic is IEEE f32, one rounded operation at a time, in the written order, no contraction.
+ *
+ * A probe is spt_probe_point {p, pad}; it is valid iff p is finite (spt_probe_ok).  The host refuses a host-side list with an invalid
+ * probe (the message names the first such index); an invalid probe that arrives through device pointers indexes nothing, all its
+ * outputs (27 words of sh_out, 4 of aux_out) are the quiet NaN 0x7fc00000 and its neighbours are unaffected.
+ *
+ * Per probe i and sample k in [0, S): a = first_point + i (u32 wrap), b = first_sample + k.
+ *   Direction: rx, ry are the first two draws of spt_rng_seed(seed ^ SPT_PROBE_SEED_SALT, a, b), a stream of their own.  The uniform
+ *     sphere map: z = 1.0f - 2.0f*rx; r = spt_sqrt(spt_max(0.0f, 1.0f - z*z)); phi = ry * 2.0f * SPT_PI; spt_sincos(phi, &sp, &cp);
+ *     d = normalize(r*cp, r*sp, z), normalize with true divisions (spt_cm_normalize).
+ *   Gather ray: o = p, t_min = 0.0001f (SPT_BAKE_T_EPS), direction d, path stream (a, b) under the job's seed, no draws skipped.
+ *   x(i, k) is what spt_radiance returns for exactly that record with repeats = 1, rng_skip = 0, no aux and the job's seed and
+ *     max_depth: depth 0 is a camera ray's, the path starts outside any medium.
+ * Basis spt_probe_basis(d, Y): real orthonormal SH without the Condon-Shortley sign, index j = l(l+1)+m, world axes as given, d =
+ *   (x, y, z):  Y0 = 0.282094792f;  Y1 = 0.488602512f*y;  Y2 = 0.488602512f*z;  Y3 = 0.488602512f*x;  Y4 = 1.092548431f*(x*y);
+ *   Y5 = 1.092548431f*(y*z);  Y6 = 0.315391565f*(3.0f*(z*z) - 1.0f);  Y7 = 1.092548431f*(x*z);  Y8 = 0.546274215f*(x*x - y*y).
+ * Per probe, once, the delta lights (no gather ray can find them): D[j][c] = 0; for l = 0 .. n_lights - 1 in array order, types
+ *   directional, point and spot only: dir, strength, dist are the three delta cases of the light sampler at p, exactly as for spt_bake;
+ *   li = strength (no cosine, no 1/pi); a light whose three channels are all 0 is skipped.  The shadow ray is (p, dir, t_min =
+ *   0.0001f, t_max = dist - 0.001f), judged as spt_trace_any judges it; unoccluded: D[j][c] = D[j][c] + li[c] * Y_j(dir).
+ * Result: sh[j][c] = D[j][c] + (((0 + x_c(i,0)*Y_j(d_0)) + x_c(i,1)*Y_j(d_1)) + ...) * w, w = (4.0f*SPT_PI) * (1.0f/(float)S) made
+ *   once on the host, the sum in k order.  max_depth == 0 gives D.  sh_out holds 27 f32 per probe, coefficient-major [9][3], RGB
+ *   innermost.
+ * Visibility record aux[4], over the first segments of the S gather rays (traced whatever max_depth is), inv = 1.0f/(float)S:
+ *   aux[0] = (float)hits * inv;  aux[1] = (float)backfacing * inv: a hit on a SPT_PRIM_MESH instance is backfacing iff
+ *   (n0*d0 + n1*d1) + n2*d2 > 0 with n the normal spt_bake_resolve gives for the hit's (instance, prim, v, w); sphere and patch hits
+ *   count as front;  aux[2] = the sum of the hit distances in k order divided by (float)hits, 0 without a hit;  aux[3] = the smallest
+ *   hit distance, SPT_F32_MAX without one.
+ * A probe's words depend on its record, on first_point + i and on the job's scalars only: not on its neighbours, on points_per_pass
+ * or on how samples are cut into chunks.
+ *
+ * Pointers, staging, the lock, the shared render workspace and scenes with Bezier patches: as spt_bake.  With
+ * SPT_PROBE_DEVICE_POINTERS points (16-byte aligned), sh_out and aux_out (4-byte aligned) are device memory on the scene's device.
+ * Refusals write nothing and leave the scene usable.  SPT_ERR_INVALID_ARG: a null scene or job; size below sizeof(spt_probe_job);
+ * unknown flags; samples == 0; null points or sh_out while n_points > 0; an invalid host probe; a device pointer that is not device
+ * memory of the scene's device or misaligned.  SPT_ERR_UNSUPPORTED: max_depth > 255.  n_points == 0 returns SPT_OK and does nothing. */
+typedef struct spt_probe_point { float p[3]; float pad; } spt_probe_point;   /* 16 B */
+enum { SPT_PROBE_DEVICE_POINTERS = 1u };
+#define SPT_PROBE_SEED_SALT 0x50524F4245534831ull   /* "PROBESH1": distinct from SPT_BAKE_SEED_SALT and SPT_CAMERA_SEED_SALT */
+typedef struct spt_probe_job {
+    uint32_t size, flags;          /* sizeof(spt_probe_job) as the caller was compiled (the struct only grows at its tail); SPT_PROBE_* flags */
+    uint64_t n_points;
+    const spt_probe_point* points;
+    float* sh_out;                 /* n_points * 27 f32 */
+    float* aux_out;                /* NULL, or n_points * 4 f32 */
+    uint32_t samples, max_depth;   /* S >= 1 gather paths per probe */
+    uint64_t seed;
+    uint32_t first_point, first_sample;
+    uint32_t points_per_pass, pad;   /* tuning, 0 = default */
+} spt_probe_job;
+spt_status spt_probe(const spt_scene* scene, const spt_probe_job* job);
+
 /* Page-locked host memory for rgb_mean_out: lets the final device-to-host copy of the film run as one
  * DMA at PCIe rate instead of being staged through the runtime's bounce buffers.  Optional: any host
  * pointer is accepted by spt_render. */

@@ -163,6 +163,21 @@ spt_status spt_host_bake_rays(const spt_scene_desc* desc, uint32_t kind, uint32_
 spt_status spt_host_lightmap_points(const spt_host_scene* scene, const char* instance_name, uint32_t width, uint32_t height,
                                     spt_bake_point* points_out, uint32_t* texels_out, uint64_t capacity, uint64_t* n_out);
 
+/* spt_probe's specification (include/spt_abi.h, "spherical-harmonic light probes"; include/spt_probe.h, which the device kernels
+ * include too) evaluated on the host, so that callers and tests can reproduce a probe from spt_radiance and spt_trace_any.  `lights`
+ * are n_lights records of a descriptor (may be NULL with n_lights == 0).  Every output may be NULL:
+ *   rays_out        n_points * samples gather rays in (i, k) order, streams (first_point + i, first_sample + k): spt_radiance input
+ *   weights_out     9 floats per (i, k): spt_probe_basis of the ray's direction
+ *   delta_rays_out  per probe and light, [i * n_lights + l]: the shadow ray, all zero where the light is skipped
+ *   delta_li_out    3 floats at the same index: li, zeros where skipped
+ *   delta_basis_out 9 floats at the same index: spt_probe_basis of the shadow ray's direction, zeros where skipped
+ * SPT_ERR_INVALID_ARG: a probe whose p is not finite (the message names the first index). */
+spt_status spt_host_probe_rays(uint32_t n_lights, const spt_light* lights, uint64_t n_points, const spt_probe_point* points, uint32_t samples, uint64_t seed,
+                               uint32_t first_point, uint32_t first_sample, spt_path_ray* rays_out, float* weights_out, spt_ray* delta_rays_out,
+                               float* delta_li_out, float* delta_basis_out);
+/* spt_probe_basis over n directions (3 floats each, used as given): 9 floats per direction */
+spt_status spt_host_probe_basis(uint64_t n, const float* dirs, float* out);
+
 /* The per-origin-triangle candidate table of include/spt_origin_cand.h on the host, for checking it without a device.  Instance i
  * has the spt_instance matrices inv / fwd (12 floats each) and the normal matrix nrm (9 floats); triangle k (at most 64) belongs
  * to instance tri_instance[k], with tri_pos 9 floats (p0, p1, p2, object space) and tri_nrm its 3 vertex normals; its slot and its

@@ -334,6 +334,18 @@ class BakeJob(C.Structure):
                 ("first_point", C.c_uint32), ("first_sample", C.c_uint32), ("points_per_pass", C.c_uint32), ("pad1", C.c_uint32)]
 
 
+# spt_probe: spt_probe_point (16 B)
+PROBE_DTYPE = np.dtype([("p", "<f4", 3), ("pad", "<f4")])
+PROBE_DEVICE_POINTERS = 1
+
+
+class ProbeJob(C.Structure):
+    """spt_probe_job (spt_probe); `size` is sizeof of the struct."""
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("n_points", C.c_uint64), ("points", C.c_void_p), ("sh_out", C.c_void_p),
+                ("aux_out", C.c_void_p), ("samples", C.c_uint32), ("max_depth", C.c_uint32), ("seed", C.c_uint64), ("first_point", C.c_uint32),
+                ("first_sample", C.c_uint32), ("points_per_pass", C.c_uint32), ("pad", C.c_uint32)]
+
+
 # ---- library loading -----------------------------------------------------------------
 
 class SceneUpdateDesc(C.Structure):
@@ -430,6 +442,10 @@ def host_lib() -> C.CDLL:
                                                C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             lib.spt_host_lightmap_points.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
                                                      C.POINTER(C.c_uint64)]
+        if hasattr(lib, "spt_host_probe_rays"):
+            lib.spt_host_probe_rays.argtypes = [C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            lib.spt_host_probe_basis.argtypes = [C.c_uint64, C.c_void_p, C.c_void_p]
         lib.spt_host_load_renderer.argtypes = [C.c_char_p, C.POINTER(RenderParams), C.POINTER(C.c_float)]
         if hasattr(lib, "spt_host_load_renderer_filter"):   # (a library built before the weighted filters lacks it)
             lib.spt_host_load_renderer_filter.argtypes = [C.c_char_p, C.POINTER(RenderParams), C.POINTER(FilterDesc)]
@@ -504,6 +520,8 @@ def hip_lib() -> C.CDLL:
             lib.spt_radiance.argtypes = [C.c_void_p, C.POINTER(RadianceJob)]
         if hasattr(lib, "spt_bake"):   # (the same)
             lib.spt_bake.argtypes = [C.c_void_p, C.POINTER(BakeJob)]
+        if hasattr(lib, "spt_probe"):   # (the same)
+            lib.spt_probe.argtypes = [C.c_void_p, C.POINTER(ProbeJob)]
         if hasattr(lib, "spt_scene_update"):   # (the same)
             lib.spt_scene_update.argtypes = [C.c_void_p, C.POINTER(SceneUpdateDesc)]
         if hasattr(lib, "spt_scene_deform"):   # (the same)
@@ -874,6 +892,44 @@ class DeviceScene:
         _check_hip(lib.spt_bake(self._h, C.byref(job)))
         return out
 
+    def probes(self, points, samples: int = 64, max_depth: int = 8, seed: int = 1, first_point: int = 0, first_sample: int = 0, aux: bool = False,
+               points_per_pass: int = 0):
+        """spt_probe: per free point in space the incident radiance projected onto the nine real SH of bands 0 .. 2, (n, 9, 3) f32
+        (coefficient j = l(l+1)+m, RGB innermost); with aux=True also the (n, 4) visibility record (fraction of first segments that hit,
+        fraction that hit a mesh from behind, mean and smallest hit distance).  points: an (n, 3) float array, PROBE_DTYPE records, or
+        a contiguous float32 torch tensor on the scene's device of shape (n, 3) or (n, 4): then the producer's current stream is
+        synchronised, the library reads and writes device memory and the results are tensors."""
+        lib = hip_lib()
+        if not hasattr(lib, "spt_probe"):
+            raise SptError(4, "this libspt_hip.so has no spt_probe")
+        job = ProbeJob(size=C.sizeof(ProbeJob), flags=0, samples=samples, max_depth=max_depth, seed=seed, first_point=first_point & 0xffffffff,
+                       first_sample=first_sample, points_per_pass=points_per_pass)
+        if type(points).__module__.split(".")[0] == "torch":
+            import torch
+            if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] not in (3, 4) or not points.is_contiguous():
+                raise ValueError("points: a contiguous float32 (n, 3) or (n, 4) tensor is expected")
+            if points.device.type != "cuda" or points.device.index != self.device:
+                raise ValueError("points: the tensor must live on the scene's device (cuda:%d)" % self.device)
+            n = points.shape[0]
+            if points.shape[1] == 3:   # the 16-byte records of the ABI
+                points = torch.cat([points, torch.zeros((n, 1), dtype=torch.float32, device=points.device)], dim=1).contiguous()
+            sh = torch.empty((n, 9, 3), dtype=torch.float32, device=points.device)
+            vis = torch.empty((n, 4), dtype=torch.float32, device=points.device) if aux else None
+            torch.cuda.current_stream(points.device).synchronize()   # the points are complete before the library's stream reads them
+            job.flags |= PROBE_DEVICE_POINTERS
+            job.n_points, job.points, job.sh_out = n, points.data_ptr() if n else None, sh.data_ptr() if n else None
+            job.aux_out = vis.data_ptr() if aux and n else None
+            _check_hip(lib.spt_probe(self._h, C.byref(job)))
+            return (sh, vis) if aux else sh
+        points = _probe_records(points)
+        n = points.shape[0]
+        sh = np.zeros((n, 9, 3), dtype=np.float32)
+        vis = np.zeros((n, 4), dtype=np.float32) if aux else None
+        job.n_points, job.points, job.sh_out = n, points.ctypes.data, sh.ctypes.data
+        job.aux_out = vis.ctypes.data if aux else None
+        _check_hip(lib.spt_probe(self._h, C.byref(job)))
+        return (sh, vis) if aux else sh
+
     def update(self) -> None:
         """spt_scene_update with the Scene's current tlas_nodes, instances, lights and light alias table (after
         Scene.set_transforms / set_light): the device scene then behaves like one freshly created from the Scene.  Frames queued
@@ -1120,6 +1176,65 @@ def bake_rays(scene: "Scene", points, samples: int = 16, seed: int = 1, first_po
                                        samples, seed, first_point & 0xffffffff, first_sample, out["rays"].ctypes.data, out["pos"].ctypes.data,
                                        out["nrm"].ctypes.data, out["delta_rays"].ctypes.data, out["delta_li"].ctypes.data))
     return out
+
+
+def _probe_records(points) -> np.ndarray:
+    """PROBE_DTYPE records from records or an (n, 3) float array."""
+    if isinstance(points, np.ndarray) and points.dtype == PROBE_DTYPE:
+        return np.ascontiguousarray(points).reshape(-1)
+    xyz = np.asarray(points, dtype=np.float32).reshape(-1, 3)
+    out = np.zeros(xyz.shape[0], dtype=PROBE_DTYPE)
+    out["p"] = xyz
+    return out
+
+
+def probe_rays(scene: "Scene", points, samples: int = 64, seed: int = 1, first_point: int = 0, first_sample: int = 0):
+    """spt_host_probe_rays: spt_probe's specification (include/spt_probe.h) evaluated on the host over the Scene's lights.  Returns a
+    dict: "rays" (n, samples) PATH_RAY_DTYPE gather rays (radiance input), "weights" (n, samples, 9) f32 the basis of each ray's
+    direction, "delta_rays" (n, n_lights) RAY_DTYPE shadow rays, "delta_li" (n, n_lights, 3) and "delta_basis" (n, n_lights, 9) f32 per
+    delta light (zeros where skipped).  A probe is D + w * the in-order sum over k of DeviceScene.radiance(rays[:, k]) * weights[:, k],
+    w = 4 pi / samples, D the in-order sum of delta_li * delta_basis where DeviceScene.trace_any(delta_rays) finds nothing."""
+    lib = host_lib()
+    if not hasattr(lib, "spt_host_probe_rays"):
+        raise SptError(4, "libspt_host.so does not export spt_host_probe_rays")
+    points = _probe_records(points)
+    n, desc = points.shape[0], scene.desc
+    nl = int(desc.n_lights)
+    out = {"rays": np.zeros((n, samples), dtype=PATH_RAY_DTYPE), "weights": np.zeros((n, samples, 9), dtype=np.float32),
+           "delta_rays": np.zeros((n, nl), dtype=RAY_DTYPE), "delta_li": np.zeros((n, nl, 3), dtype=np.float32),
+           "delta_basis": np.zeros((n, nl, 9), dtype=np.float32)}
+    _check_host(lib.spt_host_probe_rays(nl, C.cast(desc.lights, C.c_void_p), n, points.ctypes.data, samples, seed, first_point & 0xffffffff, first_sample,
+                                        out["rays"].ctypes.data, out["weights"].ctypes.data, out["delta_rays"].ctypes.data, out["delta_li"].ctypes.data,
+                                        out["delta_basis"].ctypes.data))
+    return out
+
+
+def sh_basis(dirs) -> np.ndarray:
+    """spt_host_probe_basis: the nine real SH of bands 0 .. 2 (no Condon-Shortley sign, j = l(l+1)+m) of directions (..., 3), in f32
+    exactly as spt_probe evaluates them: (..., 9)."""
+    lib = host_lib()
+    if not hasattr(lib, "spt_host_probe_basis"):
+        raise SptError(4, "libspt_host.so does not export spt_host_probe_basis")
+    dirs = np.ascontiguousarray(dirs, dtype=np.float32)
+    out = np.zeros(dirs.shape[:-1] + (9,), dtype=np.float32)
+    _check_host(lib.spt_host_probe_basis(dirs.size // 3, dirs.ctypes.data, out.ctypes.data))
+    return out
+
+
+_SH_CONST = (0.282094792, 0.488602512, 1.092548431, 0.315391565, 0.546274215)
+
+
+def sh_irradiance(coeffs, normals) -> np.ndarray:
+    """Irradiance from probe coefficients, in float64: the convolution with the clamped cosine lobe, A = pi, 2 pi / 3, pi / 4 per
+    band.  coeffs (..., 9, 3), normals (..., 3) unit vectors, broadcast against each other; returns (..., 3).  A constant radiance L
+    (coeffs[0] = L / Y0, the rest 0) gives pi * L for every normal."""
+    c = np.asarray(coeffs, dtype=np.float64)
+    n = np.asarray(normals, dtype=np.float64)
+    x, y, z = n[..., 0], n[..., 1], n[..., 2]
+    k0, k1, k2, k3, k4 = _SH_CONST
+    Y = np.stack([np.full_like(x, k0), k1 * y, k1 * z, k1 * x, k2 * (x * y), k2 * (y * z), k3 * (3.0 * (z * z) - 1.0), k2 * (x * z), k4 * (x * x - y * y)], axis=-1)
+    A = np.array([np.pi] + [2.0 * np.pi / 3.0] * 3 + [np.pi / 4.0] * 5)
+    return np.sum((Y * A)[..., None] * c, axis=-2)
 
 
 def vertex_points(scene: "Scene", name: str) -> np.ndarray:

@@ -45,6 +45,7 @@ static void usage() {
                  "           [--film-devices a,b,..]   (the progressive options above over several devices)\n"
                  "           [--lens-radius R --focus-distance D | --orthographic H | --panorama]   (a camera model in the scene camera's place)\n"
                  "           [--bake-lightmap INSTANCE --bake-size WxH [--bake-samples N]]   (a float RGB EXR lightmap of a mesh instance: E / pi per texel)\n"
+                 "           [--bake-probes points.txt [--probe-samples N]]   (SH light probes at the `x y z` of each line: 27 coefficients + 4 visibility numbers per line of -o)\n"
                  "           [--animate frames.json]   (one plain image <out>_NNNN per frame: {\"frames\": [{\"<instance>\": {<transform>}, ..}, ..]})\n");
 }
 
@@ -237,6 +238,9 @@ int main(int argc, char** argv) {
     // --bake-lightmap INSTANCE --bake-size WxH [--bake-samples N]: spt_bake over the texels of the instance's lightmap
     std::string bake_instance, bake_size;
     uint32_t bake_samples = 16;
+    // --bake-probes points.txt [--probe-samples N]: spt_probe at the points of the file
+    std::string probe_path;
+    uint32_t probe_samples = 64;
     std::vector<int32_t> device_list;
     std::vector<int32_t> film_devices;
     bool film_devices_given = false, film_devices_ok = true;
@@ -293,6 +297,8 @@ int main(int argc, char** argv) {
         else if (a == "--bake-lightmap") bake_instance = next();
         else if (a == "--bake-size") bake_size = next();
         else if (a == "--bake-samples") bake_samples = (uint32_t)std::atoi(next());
+        else if (a == "--bake-probes") probe_path = next();
+        else if (a == "--probe-samples") probe_samples = (uint32_t)std::atoi(next());
         else if (a == "--film-devices") { film_devices_given = true; film_devices_ok = parse_device_list(next(), &film_devices); }
         else { usage(); return 2; }
     }
@@ -355,6 +361,43 @@ int main(int argc, char** argv) {
         }
         bake_w = bw;
         bake_h = bh;
+    }
+    std::vector<spt_probe_point> probe_points;
+    if (!probe_path.empty()) {
+        if (probe_samples == 0) {
+            std::fprintf(stderr, "Error: --probe-samples N needs N >= 1\n");
+            return 2;
+        }
+        if (progressive || camera_model || !animate_path.empty() || gpus > 0 || film_devices_given || debug_normal || !bake_instance.empty()) {
+            std::fprintf(stderr, "Error: --bake-probes runs on one device (--device D): not with a film option (--preview-every, --time-limit, --variance-out, "
+                                 "--adaptive, --samples-out, --denoise, --robust, --film-devices), a camera model, --animate, --debug-normal, --bake-lightmap or "
+                                 "--gpus / --devices\n");
+            return 2;
+        }
+        // one `x y z` per line; blank lines are skipped, anything else is malformed
+        std::FILE* pf = std::fopen(probe_path.c_str(), "r");
+        if (!pf) {
+            std::fprintf(stderr, "Error: cannot open %s\n", probe_path.c_str());
+            return 2;
+        }
+        char line[512];
+        size_t line_no = 0;
+        bool good = true;
+        while (good && std::fgets(line, sizeof line, pf)) {
+            ++line_no;
+            if (line[std::strspn(line, " \t\r\n")] == 0) continue;
+            float x = 0.0f, y = 0.0f, z = 0.0f;
+            char tail = 0;
+            spt_probe_point pt{};
+            if (std::sscanf(line, "%f %f %f %c", &x, &y, &z, &tail) != 3 || !std::isfinite(x) || !std::isfinite(y) || !std::isfinite(z)) good = false;
+            pt.p[0] = x; pt.p[1] = y; pt.p[2] = z;
+            probe_points.push_back(pt);
+        }
+        std::fclose(pf);
+        if (!good) {
+            std::fprintf(stderr, "Error: %s line %zu: three finite numbers `x y z` are expected\n", probe_path.c_str(), line_no);
+            return 2;
+        }
     }
     if (film_devices_given && !film_devices_ok) {
         std::fprintf(stderr, "Error: --film-devices takes a list of device indices such as 0,1,2 (an index may repeat)\n");
@@ -464,6 +507,44 @@ int main(int argc, char** argv) {
                              "reaches neighbouring pixels (--preview-every, --time-limit and --film-devices work with it)\n", (double)params.filter_radius);
         spt_host_scene_free(hs);
         return 2;
+    }
+    if (!probe_path.empty()) {   // the probes: max_depth from the renderer file, the seed of --seed
+        auto probe_fail = [&](const char* what) {
+            std::fprintf(stderr, "Error: %s\n", what);
+            spt_host_scene_free(hs);
+            return 1;
+        };
+        std::vector<float> sh(probe_points.size() * 27), vis(probe_points.size() * 4);
+        const auto t_probe = std::chrono::steady_clock::now();
+        if (!probe_points.empty()) {
+            spt_scene* scene = nullptr;
+            if (spt_scene_create(spt_host_scene_desc(hs), device, &scene) != SPT_OK) return probe_fail(spt_last_error());
+            spt_probe_job job;
+            std::memset(&job, 0, sizeof job);
+            job.size = (uint32_t)sizeof job;
+            job.n_points = probe_points.size();
+            job.points = probe_points.data();
+            job.sh_out = sh.data();
+            job.aux_out = vis.data();
+            job.samples = probe_samples;
+            job.max_depth = params.max_depth;
+            job.seed = seed;
+            const spt_status e = spt_probe(scene, &job);
+            const std::string why = e == SPT_OK ? "" : spt_last_error();
+            spt_scene_destroy(scene);
+            if (e != SPT_OK) return probe_fail(why.c_str());
+        }
+        std::FILE* of = std::fopen(out_path.c_str(), "w");
+        if (!of) return probe_fail("cannot write the output file");
+        for (size_t i = 0; i < probe_points.size(); ++i) {   // %.9g round-trips f32
+            for (int q = 0; q < 27; ++q) std::fprintf(of, "%.9g ", (double)sh[27 * i + q]);
+            std::fprintf(of, "%.9g %.9g %.9g %.9g\n", (double)vis[4 * i], (double)vis[4 * i + 1], (double)vis[4 * i + 2], (double)vis[4 * i + 3]);
+        }
+        if (std::fclose(of) != 0) return probe_fail("cannot write the output file");
+        const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_probe).count();
+        std::fprintf(stderr, "Finished, time used: %.3fs (%zu probes, %u samples each)\n", sec, probe_points.size(), probe_samples);
+        spt_host_scene_free(hs);
+        return 0;
     }
     if (!bake_instance.empty()) {   // the lightmap: max_depth from the renderer file, the seed of --seed; uncovered texels are 0
         auto bake_fail = [&](const char* what) {

@@ -4,6 +4,7 @@
 // .hip took ~4 minutes per library build; split this way the groups compile side by side.
 // (inst_deform.hip is a unit of the same kind without templates: spt_scene_deform's kernels, declared in deform_kernels.h.)
 // (inst_bake.hip: spt_bake's kernels, bake_kernels.h - k_bake_intake<true>, k_bake_intake<false>, k_bake_intake_stream, k_bake_finish.)
+// (inst_probe.hip: spt_probe's kernels, probe_kernels.h - k_probe_intake<true>, k_probe_intake<false>, k_probe_intake_stream, k_probe_finish.)
 #pragma once
 #include "kernels.h"
 

@@ -25,6 +25,7 @@
 #include "film_kernels.h"
 #include "radiance_kernels.h"
 #include "bake_kernels.h"
+#include "probe_kernels.h"
 #include "camera_kernels.h"   // k_primary_cam: declared here, compiled in inst_camera.hip
 #include "deform_kernels.h"   // spt_scene_deform's kernels: declared here, compiled in inst_deform.hip
 #include "abi_error.h"     // AbiError, fail
@@ -147,6 +148,7 @@ struct BezierLib {
     decltype(&spt_render_camera) render_camera = nullptr;             // (the same)
     decltype(&spt_film_create_camera) film_create_camera = nullptr;   // (the same)
     decltype(&spt_bake) bake = nullptr;                               // (the same)
+    decltype(&spt_probe) probe = nullptr;                             // (the same)
     decltype(&spt_debug_bxdf) debug_bxdf = nullptr;
     decltype(&spt_debug_render_info) debug_render_info = nullptr;
     decltype(&spt_last_error) last_error = nullptr;
@@ -496,6 +498,7 @@ const BezierLib* bezier_lib() {
         (void)sym(lib.render_camera, "spt_render_camera");
         (void)sym(lib.film_create_camera, "spt_film_create_camera");
         (void)sym(lib.bake, "spt_bake");
+        (void)sym(lib.probe, "spt_probe");
         if (!all || version() != SPT_ABI_VERSION) {
             err = path + " does not export ABI version " + std::to_string(SPT_ABI_VERSION);
             return;
@@ -3712,6 +3715,161 @@ spt_status spt_bake(const spt_scene* scene_c, const spt_bake_job* job) {
         }
         if (!dev) deliver(sc->img_out8, sc->ray_rgb.p, (size_t)n_points * 3, FilmReadOut{job->rgb_out, nullptr}, st);   // the device-to-host path of the film read-outs
         else HIP_CHECK(hipStreamSynchronize(st));
+        return SPT_OK;
+    });
+}
+
+// ---- spherical-harmonic light probes (spt_probe) ----
+static void check_probe_pointer(const spt_scene* sc, const void* p, const char* what, bool align16) {
+    hipPointerAttribute_t at;
+    std::memset(&at, 0, sizeof at);
+    const hipError_t e = hipPointerGetAttributes(&at, p);
+    if (e != hipSuccess) (void)hipGetLastError();
+    if (e != hipSuccess || at.type != hipMemoryTypeDevice || at.device != sc->device)
+        fail(SPT_ERR_INVALID_ARG, std::string("probe: SPT_PROBE_DEVICE_POINTERS and `") + what + "` is not device memory on the scene's device");
+    if ((reinterpret_cast<uintptr_t>(p) & (align16 ? 15u : 3u)) != 0)
+        fail(SPT_ERR_INVALID_ARG, std::string("probe: device pointer `") + what + "` is not " + (align16 ? "16" : "4") + "-byte aligned");
+}
+
+// spt_bake with uniform sphere rays and a projection behind the bounces (probe_kernels.h): the same passes of P probes x chunks of R
+// samples, the same staging slots, workspace and delivery
+spt_status spt_probe(const spt_scene* scene_c, const spt_probe_job* job) {
+    if (!scene_c || !job) { g_error = "probe: null argument"; return SPT_ERR_INVALID_ARG; }
+    if (job->size < sizeof(spt_probe_job)) { g_error = "probe: job->size is below sizeof(spt_probe_job)"; return SPT_ERR_INVALID_ARG; }
+    if (job->flags & ~(uint32_t)SPT_PROBE_DEVICE_POINTERS) { g_error = "probe: unknown flags"; return SPT_ERR_INVALID_ARG; }
+    if (job->samples == 0) { g_error = "probe: samples must be >= 1"; return SPT_ERR_INVALID_ARG; }
+    if (job->n_points != 0 && (!job->points || !job->sh_out)) { g_error = "probe: null points or sh_out"; return SPT_ERR_INVALID_ARG; }
+    if (job->max_depth > 255) { g_error = "probe: max_depth > 255"; return SPT_ERR_UNSUPPORTED; }
+    spt_scene* sc = const_cast<spt_scene*>(scene_c);
+    if (sc->fwd) {
+        if (!sc->fwd->probe) { g_error = "probe: libspt_hip_bez.so does not export spt_probe"; return SPT_ERR_UNSUPPORTED; }
+        return forwarded(sc->fwd, sc->fwd->probe(sc->inner, job));
+    }
+    if (job->n_points == 0) return SPT_OK;
+    std::lock_guard<std::mutex> lock(sc->mu);
+    return guarded("probe", [&] {
+        const uint64_t n_points = job->n_points;
+        const uint32_t S = job->samples;
+        const bool dev = (job->flags & SPT_PROBE_DEVICE_POINTERS) != 0;
+        const bool want_aux = job->aux_out != nullptr;
+        if (n_points > (1ull << 36)) fail(SPT_ERR_UNSUPPORTED, "probe: more than 2^36 probes");
+        HIP_CHECK(hipSetDevice(sc->device));
+        if (dev) {   // every check comes before the first allocation, copy or launch
+            check_probe_pointer(sc, job->points, "points", true);
+            check_probe_pointer(sc, job->sh_out, "sh_out", false);
+            if (want_aux) check_probe_pointer(sc, job->aux_out, "aux_out", false);
+        } else {     // ... and a host list is checked as a whole, so that a refusal has written nothing at all
+            for (uint64_t i = 0; i < n_points; ++i)
+                if (!spt_probe_ok(job->points + i)) fail(SPT_ERR_INVALID_ARG, "probe: point " + std::to_string(i) + " has a non-finite p");
+        }
+        film_join(sc);
+        spt_render_params plan{};      // what run_setup and bounce read of a plan
+        plan.max_depth = job->max_depth;
+        const spt_camera no_camera{};
+        RenderRun run;
+        run.sc = sc;
+        run.cam = &no_camera;
+        run.params = &plan;
+        run.rays = true;
+        run_setup(run);
+        const hipStream_t st = run.st;
+
+        // Passes of P probes x chunks of R samples, around 2^22 paths each, as spt_bake cuts points x samples
+        constexpr uint64_t kStep = (uint64_t)kShards * kBlock, kTargetPaths = 1ull << 22;
+        uint64_t P64 = job->points_per_pass ? job->points_per_pass : std::max(kStep, kTargetPaths / S / kStep * kStep);
+        P64 = std::min(P64, n_points);
+        const uint32_t P = (uint32_t)P64;
+        const uint64_t P_up = (P64 + kStep - 1) / kStep * kStep;
+        const uint32_t R = (uint32_t)std::min<uint64_t>(S, std::max<uint64_t>(1, 2 * kTargetPaths / P_up));
+        if (P_up * R > 0x7fffffffull) fail(SPT_ERR_UNSUPPORTED, "probe: pass too large (lower points_per_pass)");
+        // max_depth 0: no path runs and sh = D; the first segments are still traced when the visibility record is asked for
+        const uint32_t k_end = (job->max_depth || want_aux) ? S : 0u;
+
+        RenderCtx rc{};
+        rc.max_depth = job->max_depth;
+        rc.seed = job->seed;
+        rc.spp = S;
+        const size_t counts_words = grow_ray_workspace(sc, P, k_end ? R : 0u, job->max_depth, run.fused, run.class_queues, rc);
+        rc.dyn_refill_below = run.dyn_refill_below;
+        rc.dyn_steps = run.dyn_steps;
+        rc.stream_rounds = run.stream_rounds;
+        rc.stream_refill_below = run.stream_refill_below;
+        rc.visits = sc->visits.as<unsigned long long>();
+        // D, validity and the visibility carry per probe of a pass (kProbePlanes planes of P words), then the first segments of a chunk
+        // (R * P words), probe_kernels.h: spt_radiance's hit buffer, idle here
+        const size_t seg_cap = (size_t)P * std::max(R, 1u);
+        sc->ray_hits.ensure(((size_t)P * kProbePlanes + seg_cap) * sizeof(float));
+        float* sh_dev = job->sh_out;
+        float* aux_dev = job->aux_out;
+        if (!dev) {
+            const size_t in_bytes = (size_t)P * sizeof(spt_probe_point);
+            for (int k = 0; k < 2; ++k) {
+                sc->ray_stage[k].ensure(in_bytes);
+                if (!sc->ev_ray[k]) HIP_CHECK(hipEventCreateWithFlags(&sc->ev_ray[k], hipEventDisableTiming));
+            }
+            sc->ray_in.ensure(in_bytes);
+            // sh for every probe, then aux for every probe
+            sc->ray_rgb.ensure((size_t)n_points * (SPT_PROBE_SH_WORDS + (want_aux ? SPT_PROBE_AUX_WORDS : 0u)) * sizeof(float));
+            sh_dev = sc->ray_rgb.as<float>();
+            aux_dev = want_aux ? sh_dev + (size_t)n_points * SPT_PROBE_SH_WORDS : nullptr;
+        }
+        const bool stream = sc->swalk && !sc->lds_geo;   // the walkers of spt_trace_closest / spt_trace_any
+        const float inv = 1.0f / (float)S;
+        const float w = spt_probe_weight(S);
+        uint64_t pass = 0;
+        for (uint64_t r0 = 0; r0 < n_points; r0 += P, ++pass) {
+            const uint32_t n = (uint32_t)std::min<uint64_t>(P, n_points - r0);
+            ProbeJob pj{};
+            pj.seed = job->seed;
+            pj.n = n;
+            pj.sh_out = sh_dev + SPT_PROBE_SH_WORDS * r0;
+            pj.aux_out = aux_dev ? aux_dev + SPT_PROBE_AUX_WORDS * r0 : nullptr;
+            pj.planes = sc->ray_hits.as<float>();
+            pj.seg = reinterpret_cast<uint32_t*>(sc->ray_hits.as<float>() + (size_t)P * kProbePlanes);
+            pj.plane_cap = P;
+            pj.seg_cap = (uint32_t)seg_cap;
+            pj.stream_a = job->first_point + (uint32_t)r0;   // (u32 wrap)
+            pj.stream_b = job->first_sample;
+            pj.paths = job->max_depth ? 1u : 0u;
+            const spt_probe_point* const src = job->points + r0;
+            if (dev) {
+                pj.points = reinterpret_cast<const float4*>(src);
+            } else {
+                // the slot's previous copy (two passes ago) has left it
+                PinnedBuffer& slot = sc->ray_stage[pass & 1u];
+                if (pass >= 2) HIP_CHECK(hipEventSynchronize(sc->ev_ray[pass & 1u]));
+                std::memcpy(slot.p, src, (size_t)n * sizeof(spt_probe_point));
+                HIP_CHECK(hipMemcpyAsync(sc->ray_in.p, slot.p, (size_t)n * sizeof(spt_probe_point), hipMemcpyHostToDevice, st));
+                HIP_CHECK(hipEventRecord(sc->ev_ray[pass & 1u], st));
+                pj.points = sc->ray_in.as<float4>();
+            }
+            run.ray_aux = nullptr;
+            run.ray_aux_wrap = n;
+            rc.n_pixels = n;
+            const dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
+            const dim3 grid_finish((uint32_t)(((uint64_t)n * SPT_PROBE_COEFFS + kBlock - 1) / kBlock));
+            for (uint64_t k0 = 0; k0 == 0u || k0 < k_end; k0 += R) {
+                pj.k_first = (uint32_t)k0;
+                pj.reps = (uint32_t)std::min<uint64_t>(R, k_end - std::min<uint64_t>(k0, k_end));
+                rc.pass_first = (uint32_t)k0;
+                rc.pass_samples = pj.reps;
+                rc.rad_plane = (size_t)std::max(pj.reps, 1u) * n;
+                HIP_CHECK(hipMemsetAsync(rc.counts, 0, counts_words * sizeof(uint32_t), st));
+                hipLaunchKernelGGL(stream ? k_probe_intake_stream : sc->lds_geo ? k_probe_intake<true> : k_probe_intake<false>, grid, block, sc->lds_bytes, st,
+                                   sc->d, rc, pj);
+                HIP_CHECK(hipGetLastError());
+                for (uint32_t b = 0; b < (pj.reps ? job->max_depth : 0u); ++b)
+                    if (bounce(run, rc, b, st)) break;
+                hipLaunchKernelGGL(k_probe_finish, grid_finish, block, 0, st, rc, pj, k0 == 0u ? 1u : 0u, k0 + R >= k_end ? 1u : 0u, w, inv);
+                HIP_CHECK(hipGetLastError());
+            }
+        }
+        if (!dev) {   // the device-to-host path of the film read-outs
+            if (want_aux) HIP_CHECK(hipMemcpyAsync(job->aux_out, aux_dev, (size_t)n_points * SPT_PROBE_AUX_WORDS * sizeof(float), hipMemcpyDeviceToHost, st));
+            deliver(sc->img_out8, sc->ray_rgb.p, (size_t)n_points * SPT_PROBE_SH_WORDS, FilmReadOut{job->sh_out, nullptr}, st);
+        } else {
+            HIP_CHECK(hipStreamSynchronize(st));
+        }
         return SPT_OK;
     });
 }

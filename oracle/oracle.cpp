@@ -2351,6 +2351,41 @@ int oracle_trace_any(const spt_scene_desc* desc, uint32_t flags, uint32_t n, con
     return 0;
 }
 
+// spt_radiance's contract (include/spt_abi.h) on trace_ray: the ray (o, d, t_min) with d as it is, auxiliary rays only when `aux`
+// is given, stream (seed, stream_a, stream_b + k) advanced by rng_skip draws, out = ((0 + x0) + x1 + ...) * (1.0f / S)
+int oracle_radiance(const spt_scene_desc* desc, uint32_t flags, uint64_t n, const spt_path_ray* rays, const spt_ray_aux* aux,
+                    uint32_t repeats, uint32_t max_depth, uint64_t seed, uint32_t rng_skip, float* rgb_out) {
+    if (!desc || (!rays && n) || (!rgb_out && n) || repeats == 0) return 1;
+    Flags f{(flags & ORACLE_SLAB_RECIPROCAL) != 0, (flags & ORACLE_BRUTE_FORCE) != 0, (flags & ORACLE_LIBM) != 0, (flags & ORACLE_TIE_MIN_ID) != 0};
+    // (at most 16 threads, one per 256 rays: a ray's result does not depend on which thread traces it)
+    uint64_t n_threads = std::min<uint64_t>(std::min(std::max(1u, std::thread::hardware_concurrency()), 16u), n / 256 + 1);
+    std::vector<Counters> counters((size_t)n_threads);
+    const float inv = 1.0f / (float)repeats;
+    auto work = [&](uint64_t t) {
+        Ctx cx{desc, f, Math{f.libm}, &counters[(size_t)t]};
+        for (uint64_t i = t; i < n; i += n_threads) {
+            Ray ray{v3(rays[i].o), v3(rays[i].d), rays[i].t_min};
+            if (aux) {
+                ray.has_aux = true;
+                ray.x_origin = v3(aux[i].rx_o); ray.x_direction = v3(aux[i].rx_d);
+                ray.y_origin = v3(aux[i].ry_o); ray.y_direction = v3(aux[i].ry_d);
+            }
+            Color sum = gray(0.0f);
+            for (uint32_t k = 0; k < repeats; ++k) {
+                Rng rng{spt_rng_seed(seed, rays[i].stream_a, rays[i].stream_b + k)};
+                for (uint32_t s = 0; s < rng_skip; ++s) rng.uniform_1d();
+                sum = sum + trace_ray(cx, ray, rng, max_depth);
+            }
+            rgb_out[i * 3 + 0] = sum.r * inv; rgb_out[i * 3 + 1] = sum.g * inv; rgb_out[i * 3 + 2] = sum.b * inv;
+        }
+    };
+    std::vector<std::thread> th;
+    for (uint64_t t = 1; t < n_threads; ++t) th.emplace_back(work, t);
+    work(0);
+    for (auto& x : th) x.join();
+    return 0;
+}
+
 // ---- unit seams for known-answer tests ------------------------------------------------
 void oracle_bxdf_sample(const spt_material* mt, const float wo[3], uint64_t rng_state, uint32_t flags, float wi_out[3],
                         float bxdf_out[3], float* pdf_out, int32_t* dir_out) {

@@ -40,6 +40,11 @@ int oracle_render_samples(const spt_scene_desc* desc, const spt_camera* cam, con
                           int32_t n_threads, uint32_t first_sample, uint32_t n_samples, float* samples_out);
 int oracle_trace_closest(const spt_scene_desc* desc, uint32_t flags, uint32_t n, const spt_ray* rays, spt_hit* hits);
 int oracle_trace_any(const spt_scene_desc* desc, uint32_t flags, uint32_t n, const spt_ray* rays, uint8_t* occluded);
+/* spt_radiance's contract (include/spt_abi.h) on trace_ray, for rays of any origin: the ray is (o, d, t_min) with d taken as it is;
+ * it carries auxiliary rays only when `aux` is given; path k of ray i draws from spt_rng_seed(seed, stream_a, stream_b + k) advanced
+ * by rng_skip draws; rgb_out[i] = ((0 + x0) + x1 + ...) * (1.0f / repeats), n * 3 floats. */
+int oracle_radiance(const spt_scene_desc* desc, uint32_t flags, uint64_t n, const spt_path_ray* rays, const spt_ray_aux* aux /* or NULL */,
+                    uint32_t repeats, uint32_t max_depth, uint64_t seed, uint32_t rng_skip, float* rgb_out);
 
 void oracle_bxdf_sample(const spt_material* mt, const float wo[3], uint64_t rng_state, uint32_t flags, float wi_out[3],
                         float bxdf_out[3], float* pdf_out, int32_t* dir_out);

@@ -70,6 +70,8 @@ def oracle_lib():
                                               C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p]
         lib.oracle_trace_closest.argtypes = [C.POINTER(spt.SceneDesc), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         lib.oracle_trace_any.argtypes = [C.POINTER(spt.SceneDesc), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        lib.oracle_radiance.argtypes = [C.POINTER(spt.SceneDesc), C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                        C.c_uint64, C.c_uint32, C.c_void_p]
         lib.oracle_bxdf_sample.argtypes = [C.POINTER(spt.Material), C.c_float * 3, C.c_uint64, C.c_uint32,
                                            C.c_float * 3, C.c_float * 3, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
         lib.oracle_bxdf_sample.restype = None
@@ -253,6 +255,51 @@ def oracle_trace_any(scene, rays, flags=0):
     desc = scene.desc
     assert oracle_lib().oracle_trace_any(C.byref(desc), flags, rays.shape[0], rays.ctypes.data, occ.ctypes.data) == 0
     return occ
+
+
+def oracle_radiance(scene, rays, aux=None, repeats=1, max_depth=8, seed=1, rng_skip=0, flags=0):
+    """spt_radiance's contract on the oracle's trace_ray, for PATH_RAY_DTYPE rays of any origin (and their RAY_AUX_DTYPE records or
+    None): (n, 3) f32."""
+    spt = load_pkg()
+    rays = np.ascontiguousarray(rays, dtype=spt.PATH_RAY_DTYPE).reshape(-1)
+    n = rays.shape[0]
+    if aux is not None:
+        aux = np.ascontiguousarray(aux, dtype=spt.RAY_AUX_DTYPE).reshape(-1)
+        assert aux.shape[0] == n
+    out = np.zeros((n, 3), dtype=np.float32)
+    desc = scene.desc
+    rc = oracle_lib().oracle_radiance(C.byref(desc), flags, n, rays.ctypes.data, aux.ctypes.data if aux is not None else None, repeats,
+                                      max_depth, seed, rng_skip, out.ctypes.data)
+    assert rc == 0
+    return out
+
+
+def first_segments(rays):
+    """The RAY_DTYPE records (o, t_min, d, f32::MAX) of PATH_RAY_DTYPE rays: what spt_radiance's hits_out answers."""
+    spt = load_pkg()
+    rays = np.asarray(rays).reshape(-1)
+    seg = np.zeros(rays.shape[0], dtype=spt.RAY_DTYPE)
+    seg["o"], seg["t_min"], seg["d"], seg["t_max"] = rays["o"], rays["t_min"], rays["d"], np.finfo(np.float32).max
+    return seg
+
+
+class OracleScene:
+    """The oracle behind the three DeviceScene calls that tests/_bake_ref.py and tests/_probe_ref.py build their references from:
+    radiance (oracle_radiance; hits: oracle_trace_closest with t_max = f32::MAX), trace_closest and trace_any."""
+
+    def __init__(self, scene, flags=None):
+        self.scene = scene
+        self.flags = device_oracle_flags() if flags is None else flags
+
+    def radiance(self, rays, aux=None, repeats=1, max_depth=8, seed=1, rng_skip=0, hits=False):
+        rgb = oracle_radiance(self.scene, rays, aux, repeats, max_depth, seed, rng_skip, self.flags)
+        return (rgb, oracle_trace_closest(self.scene, first_segments(rays), self.flags)) if hits else rgb
+
+    def trace_closest(self, rays):
+        return oracle_trace_closest(self.scene, rays, self.flags)
+
+    def trace_any(self, rays):
+        return oracle_trace_any(self.scene, rays, self.flags)
 
 
 def random_rays(scene, n, seed, spread=6.0):

@@ -3,6 +3,9 @@
 The reference of every comparison is computed from calls that exist without spt_bake, over tests/_bake_ref.py's restatement of the
 specification:  want_i = D_ref + in-order mean over k of ds.radiance(rays_ref[i, k], repeats=1, rng_skip=0), with D_ref summed from
 _bake_ref's li, gated by ds.trace_any on _bake_ref's shadow rays.  Every comparison is _util.same_words; no point is left out.
+That reference is the device's own integrator: it shows that spt_bake is those calls, not that those calls are right for rays that
+start on a surface.  The tie to the oracle is test_a_bake_is_the_oracles_delta_sum_plus_the_mean_of_the_oracles_radiance (the same
+formula over oracle_radiance and oracle_trace_any) and, for spt_radiance itself, tests/test_gpu_radiance_anywhere.py.
 
 Points: the mesh hits of a 48 x 36 camera grid (trace_closest) plus random points and the three corners of a triangle on every mesh
 instance; 4 samples, max_depth 5."""
@@ -129,6 +132,21 @@ def test_a_bake_is_the_delta_sum_plus_the_mean_of_radiance(name):
         assert np.mean(np.any(acc != 0, axis=-1)) > 0.5
     if name in ("t_medium", "t_textured"):
         assert np.any(acc != 0)
+
+
+@pytest.mark.parametrize("name", ["t_materials", "t_medium", "t_textured"])
+def test_a_bake_is_the_oracles_delta_sum_plus_the_mean_of_the_oracles_radiance(name):
+    """The same restated rays, but no device call on the expected side: _util.OracleScene stands in for the DeviceScene, so D is gated
+    by oracle_trace_any and the gather term is oracle_radiance's (trace_ray from points on surfaces, which no camera ray reaches)."""
+    pts, ref, _, _, _ = _reference(name)
+    want, D, acc = _bake_ref.bake_from_existing_calls(_util.OracleScene(_scene(name)), ref, DEPTH, SEED)
+    gathered = np.isfinite(acc).all(axis=-1) & np.any(acc != 0, axis=-1)
+    assert gathered.mean() >= (0.05 if name == "t_medium" else 0.25) and len(np.unique(acc[gathered], axis=0)) >= 100
+    if name != "t_medium":        # (t_medium has no delta light)
+        assert np.any(D > 0) and not np.all(np.any(D > 0, axis=-1))
+    got = _ds(name).bake(pts, samples=S, max_depth=DEPTH, seed=SEED)
+    bad = ~((got.view(np.uint32) == want.view(np.uint32)) | (np.isnan(got) & np.isnan(want)))
+    assert _util.same_words(got, want), "%s: %d of %d words differ from the reference built from the oracle" % (name, int(bad.sum()), bad.size)
 
 
 def test_a_scene_with_patches_is_forwarded():

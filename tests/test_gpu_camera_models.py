@@ -3,8 +3,10 @@
 1. The general kernel against the oracle: under SPT_CAMERA_GENERAL=1 the pinhole goes through k_primary_cam and must give the
    oracle's film word for word; a thin lens of radius 0 focused at 2 * hc is the pinhole too (its rays have the pinhole's bits, which
    the test asserts on the CPU first) and must give that film without the switch.
-2. Real parameters against the existing integrator: the kept samples of a film of the model equal spt_radiance (unchanged code, held
-   to the oracle by test_gpu_radiance.py) over the rays of tests/_camera_ref.py, sample by sample, word for word.
+2. Real parameters against the existing integrator: the kept samples of a film of the model equal spt_radiance (unchanged code) over
+   the rays of tests/_camera_ref.py, sample by sample, word for word.  test_gpu_radiance.py holds spt_radiance to the oracle on a
+   pinhole's rays only, so the tie to the oracle for these rays is test_kept_samples_equal_the_oracles_radiance_over_the_reference_rays
+   (oracle_radiance over the same rays) and, for spt_radiance itself, tests/test_gpu_radiance_anywhere.py.
 3. Film semantics on films of a model.  4. An independent pin of the orthographic model.  5. Refusals.  6. The command-line program.
 Every comparison is word for word with NaN counted equal (_util.same_words)."""
 import ctypes as C
@@ -177,6 +179,21 @@ def test_kept_samples_equal_radiance_over_the_reference_rays(name, kind):
     # ... and the model matters: the pinhole's samples are other samples
     with r.progressive(sc, _cfg(name), keep_samples=True) as film:
         assert not _util.same_words(film.render(4).kept(), want)
+
+
+@pytest.mark.parametrize("kind", ["thin_lens", "orthographic", "panorama"])
+@pytest.mark.parametrize("name", ["t_materials.json", "t_textured.json"])
+def test_kept_samples_equal_the_oracles_radiance_over_the_reference_rays(name, kind):
+    """No device call on the expected side: oracle_radiance (trace_ray on caller rays) over the same restated rays and auxiliary rays."""
+    sc, r = _scene(name), _tracer("random", 4)
+    rays, aux, _ = _samples(name, kind)
+    want = _util.oracle_radiance(sc, rays.reshape(-1), aux.reshape(-1), max_depth=DEPTH, seed=SEED, rng_skip=_radiance_ref.rng_skip(spt, r),
+                                 flags=_util.device_oracle_flags()).reshape(4, H, W, 3)
+    flat = want.reshape(-1, 3)
+    lit = np.isfinite(flat).all(axis=-1) & (flat != 0).any(axis=-1)
+    assert lit.mean() >= 0.25 and len(np.unique(flat[lit], axis=0)) >= 100
+    with r.progressive(sc, _cfg(name), keep_samples=True, camera_model=_models(name)[kind]) as film:
+        _same(film.render(4).kept(), want, "%s, %s, against the oracle" % (name, kind))
 
 
 # ---- 3. film semantics -------------------------------------------------------------------------------------------------------------

@@ -4,6 +4,10 @@ The reference of every comparison is computed from calls that exist without spt_
 specification:  want = D_ref + (in-order sum over k of ds.radiance(rays_ref[:, k]) * Y_ref[:, k]) * w, with D_ref summed from
 _probe_ref's li * Y(dir), gated by ds.trace_any on _probe_ref's shadow rays; the visibility record from the hits of ds.radiance(...,
 hits=True) and _bake_ref.resolve.  Every comparison is _util.same_words; no probe is left out.
+That reference is the device's own integrator: it shows that spt_probe is those calls, not that those calls are right for rays that
+start at a free point.  The tie to the oracle is test_probes_are_the_oracles_delta_sum_plus_the_oracles_projected_radiance (the same
+formulas over oracle_radiance, oracle_trace_closest and oracle_trace_any) and, for spt_radiance itself,
+tests/test_gpu_radiance_anywhere.py.
 
 Probes: about 300 on a jittered grid over the scene's bounds grown by 10 %; 8 samples, max_depth 5."""
 import ctypes as C
@@ -96,6 +100,24 @@ def test_probes_are_the_delta_sum_plus_the_projected_radiance(name):
         assert np.mean(np.any(acc.reshape(len(p), -1) != 0, axis=-1)) > 0.5
     if name in ("t_medium", "t_textured", "t_bezier"):
         assert np.any(acc != 0)
+
+
+@pytest.mark.parametrize("name", ["t_materials", "t_medium", "t_textured"])
+def test_probes_are_the_oracles_delta_sum_plus_the_oracles_projected_radiance(name):
+    """The same restated rays, but no device call on the expected side: _util.OracleScene stands in for the DeviceScene, so D is gated
+    by oracle_trace_any, the projected term is oracle_radiance's (trace_ray from free points, which no camera ray reaches) and the
+    visibility record comes from oracle_trace_closest's hits."""
+    p, ref, _, _, _, _ = _reference(name)
+    want, D, acc, aux = _probe_ref.probes_from_existing_calls(_util.OracleScene(_scene(name)), ref, DEPTH, SEED, tab=_bake_ref.tables(_scene(name)))
+    lit = np.any(acc.reshape(len(p), -1) != 0, axis=-1)
+    assert np.isfinite(acc).all() and lit.mean() >= (0.05 if name == "t_medium" else 0.25) and len(np.unique(acc[lit].reshape(-1, 27), axis=0)) >= 100
+    assert np.any(aux[:, 0] > 0) and np.any(aux[:, 0] < 1) and np.any(aux[:, 1] > 0)
+    if name != "t_medium":        # (t_medium has no delta light)
+        assert np.any(D != 0)
+    sh, vis = _ds(name).probes(p, samples=S, max_depth=DEPTH, seed=SEED, aux=True)
+    for got, exp, what in ((sh, want, "coefficients"), (vis, aux, "visibility record")):
+        bad = ~((got.view(np.uint32) == exp.view(np.uint32)) | (np.isnan(got) & np.isnan(exp)))
+        assert _util.same_words(got, exp), "%s, %s: %d of %d words differ from the reference built from the oracle" % (name, what, int(bad.sum()), bad.size)
 
 
 # the walkers of scenes that do not fit LDS: the streaming intake kernel, and the walker over the geometry in memory

@@ -814,6 +814,28 @@ class DeviceScene:
         _check_hip(hip_lib().spt_trace_any(self._h, rays.shape[0], rays.ctypes.data, occ.ctypes.data))
         return occ
 
+    @staticmethod
+    def _entry(name: str):
+        """The HIP library, which must export `name` (additive to ABI v14: an older library may lack it)."""
+        lib = hip_lib()
+        if not hasattr(lib, name):
+            raise SptError(4, "this libspt_hip.so has no %s" % name)
+        return lib
+
+    def _check_tensor(self, t, what: str, widths) -> None:
+        """`t` holds one record of one of `widths` float32 words per row, contiguous, on the scene's device."""
+        import torch
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] not in widths or not t.is_contiguous():
+            raise ValueError("%s: a contiguous float32 %s tensor is expected" % (what, " or ".join("(n, %d)" % w for w in widths)))
+        if t.device.type != "cuda" or t.device.index != self.device:
+            raise ValueError("%s: the tensor must live on the scene's device (cuda:%d)" % (what, self.device))
+
+    @staticmethod
+    def _producer_done(t) -> None:
+        """The records of `t` are complete before the library's stream reads them."""
+        import torch
+        torch.cuda.current_stream(t.device).synchronize()
+
     def radiance(self, rays, aux=None, repeats: int = 1, max_depth: int = 8, seed: int = 1, rng_skip: int = 0, rays_per_pass: int = 0,
                  hits: bool = False):
         """spt_radiance: the radiance arriving along caller rays, (n, 3) f32; with `hits` also the closest hit of every ray's first
@@ -821,25 +843,19 @@ class DeviceScene:
         generators), or contiguous float32 torch tensors on the scene's device of shape (n, 12) / (n, 16) holding the same records
         (stream_a / stream_b as bit patterns): then the producer's current stream is synchronised, the library reads and writes
         device memory and the results are tensors, the hits an (n, 5) int32 tensor of the spt_hit words."""
-        lib = hip_lib()
-        if not hasattr(lib, "spt_radiance"):
-            raise SptError(4, "this libspt_hip.so has no spt_radiance")
+        lib = self._entry("spt_radiance")
         job = RadianceJob(size=C.sizeof(RadianceJob), repeats=repeats, max_depth=max_depth, seed=seed, rng_skip=rng_skip, rays_per_pass=rays_per_pass)
         if type(rays).__module__.split(".")[0] == "torch":
             import torch
-            for t, words, what in ((rays, 12, "rays"), (aux, 16, "aux")):
-                if t is None:
-                    continue
-                if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != words or not t.is_contiguous():
-                    raise ValueError("%s: a contiguous float32 (n, %d) tensor is expected" % (what, words))
-                if t.device.type != "cuda" or t.device.index != self.device:
-                    raise ValueError("%s: the tensor must live on the scene's device (cuda:%d)" % (what, self.device))
+            self._check_tensor(rays, "rays", (12,))
+            if aux is not None:
+                self._check_tensor(aux, "aux", (16,))
             n = rays.shape[0]
             if aux is not None and aux.shape[0] != n:
                 raise ValueError("aux: one record per ray is expected")
             out = torch.empty((n, 3), dtype=torch.float32, device=rays.device)
             hit = torch.empty((n, 5), dtype=torch.int32, device=rays.device) if hits else None
-            torch.cuda.current_stream(rays.device).synchronize()   # the rays are complete before the library's stream reads them
+            self._producer_done(rays)
             job.flags, job.n_rays = RADIANCE_DEVICE_POINTERS, n
             job.rays, job.aux = rays.data_ptr() if n else None, aux.data_ptr() if aux is not None and n else None
             job.rgb_out, job.hits_out = out.data_ptr() if n else None, hit.data_ptr() if hits and n else None
@@ -866,21 +882,15 @@ class DeviceScene:
         world=True; or contiguous float32 torch tensors on the scene's device of shape (n, 4) / (n, 8) holding the same records
         (instance / prim as bit patterns): then the producer's current stream is synchronised, the library reads and writes device
         memory and the result is a tensor.  flip negates every normal."""
-        lib = hip_lib()
-        if not hasattr(lib, "spt_bake"):
-            raise SptError(4, "this libspt_hip.so has no spt_bake")
+        lib = self._entry("spt_bake")
         job = BakeJob(size=C.sizeof(BakeJob), flags=BAKE_FLIP if flip else 0, kind=BAKE_POINTS_WORLD if world else BAKE_POINTS_SURFACE, samples=samples,
                       max_depth=max_depth, seed=seed, first_point=first_point & 0xffffffff, first_sample=first_sample, points_per_pass=points_per_pass)
         if type(points).__module__.split(".")[0] == "torch":
             import torch
-            words = 8 if world else 4
-            if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != words or not points.is_contiguous():
-                raise ValueError("points: a contiguous float32 (n, %d) tensor is expected" % words)
-            if points.device.type != "cuda" or points.device.index != self.device:
-                raise ValueError("points: the tensor must live on the scene's device (cuda:%d)" % self.device)
+            self._check_tensor(points, "points", (8 if world else 4,))
             n = points.shape[0]
             out = torch.empty((n, 3), dtype=torch.float32, device=points.device)
-            torch.cuda.current_stream(points.device).synchronize()   # the points are complete before the library's stream reads them
+            self._producer_done(points)
             job.flags |= BAKE_DEVICE_POINTERS
             job.n_points, job.points, job.rgb_out = n, points.data_ptr() if n else None, out.data_ptr() if n else None
             _check_hip(lib.spt_bake(self._h, C.byref(job)))
@@ -899,23 +909,18 @@ class DeviceScene:
         fraction that hit a mesh from behind, mean and smallest hit distance).  points: an (n, 3) float array, PROBE_DTYPE records, or
         a contiguous float32 torch tensor on the scene's device of shape (n, 3) or (n, 4): then the producer's current stream is
         synchronised, the library reads and writes device memory and the results are tensors."""
-        lib = hip_lib()
-        if not hasattr(lib, "spt_probe"):
-            raise SptError(4, "this libspt_hip.so has no spt_probe")
+        lib = self._entry("spt_probe")
         job = ProbeJob(size=C.sizeof(ProbeJob), flags=0, samples=samples, max_depth=max_depth, seed=seed, first_point=first_point & 0xffffffff,
                        first_sample=first_sample, points_per_pass=points_per_pass)
         if type(points).__module__.split(".")[0] == "torch":
             import torch
-            if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] not in (3, 4) or not points.is_contiguous():
-                raise ValueError("points: a contiguous float32 (n, 3) or (n, 4) tensor is expected")
-            if points.device.type != "cuda" or points.device.index != self.device:
-                raise ValueError("points: the tensor must live on the scene's device (cuda:%d)" % self.device)
+            self._check_tensor(points, "points", (3, 4))
             n = points.shape[0]
             if points.shape[1] == 3:   # the 16-byte records of the ABI
                 points = torch.cat([points, torch.zeros((n, 1), dtype=torch.float32, device=points.device)], dim=1).contiguous()
             sh = torch.empty((n, 9, 3), dtype=torch.float32, device=points.device)
             vis = torch.empty((n, 4), dtype=torch.float32, device=points.device) if aux else None
-            torch.cuda.current_stream(points.device).synchronize()   # the points are complete before the library's stream reads them
+            self._producer_done(points)
             job.flags |= PROBE_DEVICE_POINTERS
             job.n_points, job.points, job.sh_out = n, points.data_ptr() if n else None, sh.data_ptr() if n else None
             job.aux_out = vis.data_ptr() if aux and n else None

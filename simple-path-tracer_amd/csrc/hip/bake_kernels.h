@@ -1,18 +1,16 @@
 // spt_bake (include/spt_abi.h, "irradiance at surface points"): the front and the back end that put gather rays made on the device
-// through the wavefront pipeline of kernels.h.  The ray source of k_ray_intake* (radiance_kernels.h) without the 48-byte load.
+// through the wavefront pipeline of kernels.h.
 //
 //   intake : one lane per point of the pass.  The lane resolves its point once (include/spt_bake.h) through the global instance and
 //            triangle records, as instance_sample reads them.  In the chunk with k_first == 0 it sums the unoccluded delta lights
-//            into D with the any-hit walker of k_trace_any*, and stores D and the point's validity in planes of their own.  Per sample
-//            of the chunk it then makes the gather ray, traces its first segment with the closest-hit walker of k_ray_intake* and
-//            files the path exactly as ray_intake_finish does: slot k * n + i, the miss term or a zeroed slot, store_path with
-//            throughput 1, last_pdf 0, depth 0, and the hit push for fused or class queues.  The ray and its hit differ per k, so
-//            the trace sits inside the repetition loop; the loop is wave-uniform (flat_closest and the pushes need whole waves).
+//            into D (first_any, first_segment.h), and stores D and the point's validity in planes of their own.  Per sample of the
+//            chunk it then makes the gather ray, traces its first segment and files the path at slot k * n + i (first_closest,
+//            first_file).  The ray and its hit differ per k, so the trace sits inside the sample loop; the loop is wave-uniform.
 //   bounces: the loop of spt_radiance.
 //   finish : k_ray_finish plus D: acc += x(i, k) in k order, behind the last chunk acc * (1 / S), then D + acc.  A point that failed
 //            the predicate gets the quiet NaN SPT_BAKE_NAN_BITS and has indexed nothing.
 #pragma once
-#include "kernels.h"
+#include "first_segment.h"
 #include "../../../include/spt_bake.h"
 
 static_assert(kTMinEps == SPT_BAKE_T_EPS, "the gather ray's epsilon is the integrator's");
@@ -30,10 +28,9 @@ struct BakeJob {
     uint32_t kind, flip;
 };
 
-// kWalk: 0 geometry in LDS (the flat layout included), 1 geometry from memory, 2 the streaming walker
+// kWalk: see first_segment.h
 template <int kWalk>
 SPT_DEV void bake_intake(const DScene& sc, const RenderCtx& rc, const BakeJob& job) {
-    constexpr bool kLds = kWalk == 0;
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     const bool active = i < job.n;
     [[maybe_unused]] uint2 spill_mem[kSpillStack];
@@ -70,19 +67,7 @@ SPT_DEV void bake_intake(const DScene& sc, const RenderCtx& rc, const BakeJob& j
             if (__ballot(want) == 0ull) continue;
             DRay sr;
             sr.o = origin; sr.d = mk3(dir[0], dir[1], dir[2]); sr.t_min = t_min;
-            bool occ = false;
-            if constexpr (kWalk == 2) {
-                SWalker<false, false> wk;
-                wk.done = true;
-                wk.cur = kNoRef;
-                wk.h.inst = -1; wk.h.t = SPT_F32_MAX; wk.h.prim = -1; wk.h.v = 0.0f; wk.h.w = 0.0f;
-                if (want) wk.begin(sc, sr, t_max);
-                for (uint32_t guard = 0; guard < (1u << 20) && __ballot(!wk.done) != 0ull; ++guard) wk.run(sc, 8u, spill_mem);
-                occ = wk.h.inst >= 0;
-            } else {
-                if (kLds && sc.flat) occ = flat_any(sc, sr, t_max, want);   // (whole waves, see flat.h)
-                else if (want) occ = trace_any<kLds>(sc, sr, t_max);
-            }
+            const bool occ = first_any<kWalk>(sc, sr, t_max, want, spill_mem);
             if (want && !occ) D = D + mk3(li[0], li[1], li[2]);
         }
         if (active) {
@@ -96,8 +81,6 @@ SPT_DEV void bake_intake(const DScene& sc, const RenderCtx& rc, const BakeJob& j
     float tg[3], bt[3];
     spt_bake_frame(n, tg, bt);
     const uint32_t sa = job.stream_a + i;
-    const uint32_t shard = blockIdx.x % kShards;
-    const uint32_t qbase = shard * rc.shard_cap;
     for (uint32_t k = 0; k < job.reps; ++k) {   // (block-uniform: every lane walks the same samples)
         const uint32_t sb = job.stream_b + job.k_first + k;
         float d[3], t_min;
@@ -106,40 +89,12 @@ SPT_DEV void bake_intake(const DScene& sc, const RenderCtx& rc, const BakeJob& j
         ray.o = origin;
         ray.d = mk3(d[0], d[1], d[2]);
         ray.t_min = t_min;
-        DHit h;
-        h.inst = -1; h.t = SPT_F32_MAX; h.prim = -1; h.v = 0.0f; h.w = 0.0f;
-        if constexpr (kWalk == 2) {
-            SWalker<true, false> wk;
-            wk.done = true;
-            wk.cur = kNoRef;
-            wk.h = h;
-            if (live) wk.begin(sc, ray, SPT_F32_MAX);
-            for (uint32_t guard = 0; guard < (1u << 20) && __ballot(!wk.done) != 0ull; ++guard) wk.run(sc, 8u, spill_mem);
-            h = wk.h;
-        } else {
-            if (kLds && sc.flat) h = flat_closest(sc, ray, SPT_F32_MAX, live);   // (whole waves, see flat.h)
-            else if (live) h = trace_closest<kLds>(sc, ray, SPT_F32_MAX);
-        }
-        const bool hit = live && h.inst >= 0;
-        const uint32_t ri = k * job.n + i;
-        f3 miss = mk3(0.0f, 0.0f, 0.0f);
-        if (live && !hit && sc.env_w != 0u) {  // pt.rs:98-110 at depth 0: weight 1
-            f3 env;
-            float env_pdf;
-            env_strength_pdf(sc, ray.d, &env, &env_pdf);
-            miss = mk3(0, 0, 0) + (gray(1.0f) * env) * 1.0f;
-        }
-        if (active) rad_store(rc, ri, miss);   // (a hit: the 0 the shade stages add to)
-        const uint32_t slot = rc.n_classes > 1u ? hit_push<kLds>(sc, rc, hit, h.inst, 0u, shard) : qbase + wave_push(hit, q_count(rc.counts, 0, Q_HIT, shard));
-        // class queues: the hit sits in its class' sub-queue, the record (as after k_extend) at an index of its own inside the shard
-        const uint32_t rec = rc.n_classes > 1u ? qbase + ((blockIdx.x / kShards) * blockDim.x + threadIdx.x) * job.reps + k : slot;
-        if (hit && rec < qbase + rc.shard_cap) {   // (always: the host sizes a shard for its workgroups' samples; nothing is ever written past it)
+        const DHit h = first_closest<kWalk>(sc, ray, live, spill_mem);
+        first_file<kWalk>(sc, rc, ray, h, active, live, k * job.n + i, job.reps, k, [&] {
             DRng rng;
             rng.s = spt_rng_seed(job.seed, sa, sb);
-            store_path(rc.qa, rec, ray, 0.0f, gray(1.0f), ri, mk3(0, 0, 0), pack_meta(0u, -1), rng);
-            rc.hits.t_v_w_prim[slot] = make_float4(h.t, h.v, h.w, __int_as_float(h.prim));
-            rc.hits.inst_src[slot] = make_uint2((uint32_t)h.inst, rec);
-        }
+            return rng;
+        });
     }
 }
 

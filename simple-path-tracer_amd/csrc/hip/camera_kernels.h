@@ -3,21 +3,18 @@
 //   k_primary_cam : one launch per pass.  Blocks are k_primary's 16x16 pixel tiles times sample chunks (blockIdx = tile + n_tiles * chunk),
 //                   so the lanes of a wave cover a compact pixel block and the samples of the chunk are the loop.  Per sample a lane makes
 //                   its ray in registers (include/spt_camera_models.h; and its two auxiliary rays when the scene samples textures),
-//                   traces the first segment with the walkers of k_ray_intake / k_ray_intake_stream (radiance_kernels.h) and files the
-//                   result with film semantics: slot s * n_pixels + lp; a hit zeroes its slot and appends a full path record
-//                   (store_path, the RNG seeded from the path stream and advanced past the pixel-offset draws) with its hit record to
-//                   the hit queue of bounce 0; a miss writes the environment term of depth 0, or 0.  No ray record goes through memory.
+//                   traces the first segment and files the path (first_segment.h) with film semantics: slot s * n_pixels + lp, the RNG
+//                   seeded from the path stream and advanced past the pixel-offset draws.  No ray record goes through memory.
 //   bounces       : the loop of trace_window from bounce 0 with the non-first shade instances (k_shade<., kFirst = false>), as for
 //                   spt_radiance; a textured scene's bounce-0 launch is the kAux instance, fed from the records written here per slot.
 //   resolve       : every sample of a live pixel owns its slot (first_slot = 0, as after a `collect` pass), so the resolve is the
 //                   plain k_resolve / k_resolve_buckets<false> (rc.slot_bits stays null).  A pixel an adaptive film has retired traces
 //                   nothing and has first_slot == pass_samples.
 //
-// Queue shards: workgroup g appends to shard g % kShards only; a shard receives at most ceil(G / kShards) * 256 * chunk_samples
-// records (G workgroups), which is what the host sizes it for (cam_chunks, grow_workspace).  With class queues the record of (workgroup, lane,
-// sample of the chunk) sits at an index of its own inside the shard, as in ray_intake_finish.
+// Queue shards (first_segment.h): a lane files at most chunk_samples paths per launch, which is what the host sizes a shard for
+// (cam_chunks, grow_workspace).
 #pragma once
-#include "kernels.h"
+#include "first_segment.h"
 #include "../../../include/spt_camera_models.h"
 
 static_assert(kTMinEps == SPT_CM_T_MIN, "the camera models' t_min is the pinhole's");
@@ -29,13 +26,12 @@ struct CamJob {
     FilmMask mask;       // an adaptive film's active set; pixel == null: every pixel
 };
 
-// kWalk: 0 geometry in LDS (the flat layout included), 1 geometry from memory, 2 the streaming walker
+// kWalk: see first_segment.h
 template <int kWalk>
 __global__ void __launch_bounds__(256) k_primary_cam(DScene sc, RenderCtx rc, CamJob job) {
-    constexpr bool kLds = kWalk == 0;
     const bool masked = job.mask.pixel != nullptr;
     if (masked && mask_tile_idle(rc, job.mask)) return;   // the whole block: mask.tile[tile] is one value per block
-    stage_geometry<kLds>(sc);
+    stage_geometry<kWalk == 0>(sc);
     const uint32_t tile = blockIdx.x % rc.n_tiles, chunk = blockIdx.x / rc.n_tiles;
     const uint32_t tx = tile % rc.tiles_x, ty = tile / rc.tiles_x;
     const uint32_t i = tx * kTile + (threadIdx.x % kTile);
@@ -48,9 +44,6 @@ __global__ void __launch_bounds__(256) k_primary_cam(DScene sc, RenderCtx rc, Ca
     if (masked) live = live && job.mask.pixel[lp] != 0u;   // a retired pixel traces nothing, environment or not
     const bool lazy_rng = rc.sampler == SPT_SAMPLER_RECURRENCE;   // the R2 sampler draws nothing: seed hits only
     const bool thin = job.model.type == SPT_CAMERA_THIN_LENS;
-    const uint32_t shard = blockIdx.x % kShards;
-    const uint32_t qbase = shard * rc.shard_cap;
-    uint32_t* const hit_counter = q_count(rc.counts, 0, Q_HIT, shard);
     const uint32_t s_begin = chunk * rc.chunk_samples;
     const uint32_t s_end = min(s_begin + rc.chunk_samples, rc.pass_samples);   // (block-uniform: every lane walks the same samples)
     [[maybe_unused]] uint2 spill_mem[kSpillStack];
@@ -69,48 +62,21 @@ __global__ void __launch_bounds__(256) k_primary_cam(DScene sc, RenderCtx rc, Ca
         ray.o = mk3(o[0], o[1], o[2]);
         ray.d = mk3(d[0], d[1], d[2]);
         ray.t_min = kTMinEps;
-        DHit h;
-        h.inst = -1; h.t = SPT_F32_MAX; h.prim = -1; h.v = 0.0f; h.w = 0.0f;
-        if constexpr (kWalk == 2) {
-            SWalker<true, false> wk;
-            wk.done = true;
-            wk.cur = kNoRef;
-            wk.h = h;
-            if (live) wk.begin(sc, ray, SPT_F32_MAX);
-            for (uint32_t guard = 0; guard < (1u << 20) && __ballot(!wk.done) != 0ull; ++guard) wk.run(sc, 8u, spill_mem);
-            h = wk.h;
-        } else {
-            if (kLds && sc.flat) h = flat_closest(sc, ray, SPT_F32_MAX, live);   // (whole waves, see flat.h)
-            else if (live) h = trace_closest<kLds>(sc, ray, SPT_F32_MAX);
-        }
-        const bool hit = live && h.inst >= 0;
+        const DHit h = first_closest<kWalk>(sc, ray, live, spill_mem);
         const uint32_t ri = s * rc.n_pixels + lp;
-        f3 miss = mk3(0.0f, 0.0f, 0.0f);
-        if (live && !hit && sc.env_w != 0u) {  // pt.rs:98-110 at depth 0: weight 1
-            f3 env;
-            float env_pdf;
-            env_strength_pdf(sc, ray.d, &env, &env_pdf);
-            miss = mk3(0, 0, 0) + (gray(1.0f) * env) * 1.0f;
-        }
-        if (live) rad_store(rc, ri, miss);   // (a hit: the 0 the shade stages add to)
-        const uint32_t slot = rc.n_classes > 1u ? hit_push<kLds>(sc, rc, hit, h.inst, 0u, shard) : qbase + wave_push(hit, hit_counter);
-        // class queues: the hit sits in its class' sub-queue, the record (as after k_extend) at an index of its own inside the shard
-        const uint32_t rec = rc.n_classes > 1u ? qbase + ((blockIdx.x / kShards) * blockDim.x + threadIdx.x) * rc.chunk_samples + (s - s_begin) : slot;
-        if (hit && rec < qbase + rc.shard_cap) {   // (always: the host sizes a shard for its workgroups' samples, cam_chunks; nothing is ever written past it)
+        const bool filed = first_file<kWalk>(sc, rc, ray, h, live, live, ri, rc.chunk_samples, s - s_begin, [&] {
             if (lazy_rng) rng.s = spt_rng_seed(rc.seed, pixel, gs);   // (else: the stream stands behind the two pixel-offset draws)
-            store_path(rc.qa, rec, ray, 0.0f, gray(1.0f), ri, mk3(0, 0, 0), pack_meta(0u, -1), rng);
-            rc.hits.t_v_w_prim[slot] = make_float4(h.t, h.v, h.w, __int_as_float(h.prim));
-            rc.hits.inst_src[slot] = make_uint2((uint32_t)h.inst, rec);
-            if (job.aux_out != nullptr) {   // the same model at (x + aux_dx, y) and (x, y + aux_dy) with the same lens point
-                float ao[3], ad[3];
-                float4* const ar = job.aux_out + 4u * (size_t)ri;
-                spt_cm_ray(&job.model, &job.plan, x + rc.aux_dx, y, lx, ly, ao, ad);
-                ar[0] = make_float4(ao[0], ao[1], ao[2], 0.0f);
-                ar[1] = make_float4(ad[0], ad[1], ad[2], 0.0f);
-                spt_cm_ray(&job.model, &job.plan, x, y + rc.aux_dy, lx, ly, ao, ad);
-                ar[2] = make_float4(ao[0], ao[1], ao[2], 0.0f);
-                ar[3] = make_float4(ad[0], ad[1], ad[2], 0.0f);
-            }
+            return rng;
+        });
+        if (filed && job.aux_out != nullptr) {   // the same model at (x + aux_dx, y) and (x, y + aux_dy) with the same lens point
+            float ao[3], ad[3];
+            float4* const ar = job.aux_out + 4u * (size_t)ri;
+            spt_cm_ray(&job.model, &job.plan, x + rc.aux_dx, y, lx, ly, ao, ad);
+            ar[0] = make_float4(ao[0], ao[1], ao[2], 0.0f);
+            ar[1] = make_float4(ad[0], ad[1], ad[2], 0.0f);
+            spt_cm_ray(&job.model, &job.plan, x, y + rc.aux_dy, lx, ly, ao, ad);
+            ar[2] = make_float4(ao[0], ao[1], ao[2], 0.0f);
+            ar[3] = make_float4(ad[0], ad[1], ad[2], 0.0f);
         }
     }
     if (valid && chunk == 0u) rc.first_slot[lp] = live ? 0u : rc.pass_samples;

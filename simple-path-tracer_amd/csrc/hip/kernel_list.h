@@ -5,6 +5,9 @@
 // (inst_deform.hip is a unit of the same kind without templates: spt_scene_deform's kernels, declared in deform_kernels.h.)
 // (inst_bake.hip: spt_bake's kernels, bake_kernels.h - k_bake_intake<true>, k_bake_intake<false>, k_bake_intake_stream, k_bake_finish.)
 // (inst_probe.hip: spt_probe's kernels, probe_kernels.h - k_probe_intake<true>, k_probe_intake<false>, k_probe_intake_stream, k_probe_finish.)
+// (inst_camera.hip: the camera models' k_primary_cam<0|1|2>, camera_kernels.h.  spt_radiance's k_ray_intake<true>, k_ray_intake<false>,
+//  k_ray_intake_stream and k_ray_finish, radiance_kernels.h, are compiled in spt_hip.hip itself.)
+// (These four front ends trace and file their first segments with first_segment.h, which the four kernel headers include.)
 #pragma once
 #include "kernels.h"
 

@@ -1,11 +1,10 @@
 // spt_probe (include/spt_abi.h, "spherical-harmonic light probes"): the front and the back end that put uniform sphere rays made on
 // the device through the wavefront pipeline of kernels.h, and project what the paths return onto nine SH coefficients per probe.
 //
-//   intake : one lane per probe of the pass, the three walkers of k_bake_intake.  In the chunk with k_first == 0 it sums the unoccluded
-//            delta lights, each times the basis of its direction, into D[9][3] with the any-hit walker, and stores D and the probe's
-//            validity in planes of their own.  Per sample of the chunk it makes the gather ray from the header (include/spt_probe.h),
-//            traces its first segment with the closest-hit walker and files the path exactly as bake_intake does: slot k * n + i, the
-//            miss term or a zeroed slot, store_path, the hit push for fused or class queues.  The first segment's t, with the backface
+//   intake : one lane per probe of the pass.  In the chunk with k_first == 0 it sums the unoccluded delta lights (first_any,
+//            first_segment.h), each times the basis of its direction, into D[9][3], and stores D and the probe's validity in planes
+//            of their own.  Per sample of the chunk it makes the gather ray from the header (include/spt_probe.h), traces its first
+//            segment and files the path at slot k * n + i (first_closest, first_file).  The first segment's t, with the backface
 //            bit in its sign, goes to a plane of its own at the same slot (kProbeMiss: no hit).  The loops are wave-uniform.
 //   bounces: the loop of spt_radiance.
 //   finish : one lane per (coefficient j, probe i), i fastest: the three plane loads per k are coalesced, and a job of few probes
@@ -18,7 +17,7 @@
 // stride); the segment plane at k * n + i < seg_cap; the radiance planes at the same slot < rc.rad_plane (reps * n); the queue
 // record at rec < qbase + rc.shard_cap; sh_out / aux_out at i < n of the pass' slice of the caller's (or the staging) array.
 #pragma once
-#include "kernels.h"
+#include "first_segment.h"
 #include "../../../include/spt_probe.h"
 
 static_assert(kTMinEps == SPT_BAKE_T_EPS, "the gather ray's epsilon is the integrator's");
@@ -42,10 +41,9 @@ struct ProbeJob {
     uint32_t paths;          // 0: max_depth == 0, the segments are traced for the visibility record only and every x is 0
 };
 
-// kWalk: 0 geometry in LDS (the flat layout included), 1 geometry from memory, 2 the streaming walker
+// kWalk: see first_segment.h
 template <int kWalk>
 SPT_DEV void probe_intake(const DScene& sc, const RenderCtx& rc, const ProbeJob& job) {
-    constexpr bool kLds = kWalk == 0;
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     const bool active = i < job.n && i < job.plane_cap;
     [[maybe_unused]] uint2 spill_mem[kSpillStack];
@@ -71,19 +69,7 @@ SPT_DEV void probe_intake(const DScene& sc, const RenderCtx& rc, const ProbeJob&
             if (__ballot(want) == 0ull) continue;
             DRay sr;
             sr.o = origin; sr.d = mk3(dir[0], dir[1], dir[2]); sr.t_min = SPT_BAKE_T_EPS;
-            bool occ = false;
-            if constexpr (kWalk == 2) {
-                SWalker<false, false> wk;
-                wk.done = true;
-                wk.cur = kNoRef;
-                wk.h.inst = -1; wk.h.t = SPT_F32_MAX; wk.h.prim = -1; wk.h.v = 0.0f; wk.h.w = 0.0f;
-                if (want) wk.begin(sc, sr, t_max);
-                for (uint32_t guard = 0; guard < (1u << 20) && __ballot(!wk.done) != 0ull; ++guard) wk.run(sc, 8u, spill_mem);
-                occ = wk.h.inst >= 0;
-            } else {
-                if (kLds && sc.flat) occ = flat_any(sc, sr, t_max, want);   // (whole waves, see flat.h)
-                else if (want) occ = trace_any<kLds>(sc, sr, t_max);
-            }
+            const bool occ = first_any<kWalk>(sc, sr, t_max, want, spill_mem);
             if (want && !occ) {
 #pragma unroll
                 for (uint32_t j = 0; j < SPT_PROBE_COEFFS; ++j) {
@@ -102,8 +88,6 @@ SPT_DEV void probe_intake(const DScene& sc, const RenderCtx& rc, const ProbeJob&
     }
 
     const uint32_t sa = job.stream_a + i;
-    const uint32_t shard = blockIdx.x % kShards;
-    const uint32_t qbase = shard * rc.shard_cap;
     const spt_instance* const inst = reinterpret_cast<const spt_instance*>(sc.instances);
     for (uint32_t k = 0; k < job.reps; ++k) {   // (block-uniform: every lane walks the same samples)
         const uint32_t sb = job.stream_b + job.k_first + k;
@@ -113,20 +97,7 @@ SPT_DEV void probe_intake(const DScene& sc, const RenderCtx& rc, const ProbeJob&
         ray.o = origin;
         ray.d = mk3(d[0], d[1], d[2]);
         ray.t_min = SPT_BAKE_T_EPS;
-        DHit h;
-        h.inst = -1; h.t = SPT_F32_MAX; h.prim = -1; h.v = 0.0f; h.w = 0.0f;
-        if constexpr (kWalk == 2) {
-            SWalker<true, false> wk;
-            wk.done = true;
-            wk.cur = kNoRef;
-            wk.h = h;
-            if (live) wk.begin(sc, ray, SPT_F32_MAX);
-            for (uint32_t guard = 0; guard < (1u << 20) && __ballot(!wk.done) != 0ull; ++guard) wk.run(sc, 8u, spill_mem);
-            h = wk.h;
-        } else {
-            if (kLds && sc.flat) h = flat_closest(sc, ray, SPT_F32_MAX, live);   // (whole waves, see flat.h)
-            else if (live) h = trace_closest<kLds>(sc, ray, SPT_F32_MAX);
-        }
+        const DHit h = first_closest<kWalk>(sc, ray, live, spill_mem);
         const bool hit = live && h.inst >= 0;
         const uint32_t ri = k * job.n + i;
         uint32_t seg = kProbeMiss;
@@ -142,24 +113,11 @@ SPT_DEV void probe_intake(const DScene& sc, const RenderCtx& rc, const ProbeJob&
             if (active) rad_store(rc, ri, mk3(0.0f, 0.0f, 0.0f));
             continue;
         }
-        f3 miss = mk3(0.0f, 0.0f, 0.0f);
-        if (live && !hit && sc.env_w != 0u) {  // pt.rs:98-110 at depth 0: weight 1
-            f3 env;
-            float env_pdf;
-            env_strength_pdf(sc, ray.d, &env, &env_pdf);
-            miss = mk3(0, 0, 0) + (gray(1.0f) * env) * 1.0f;
-        }
-        if (active) rad_store(rc, ri, miss);   // (a hit: the 0 the shade stages add to)
-        const uint32_t slot = rc.n_classes > 1u ? hit_push<kLds>(sc, rc, hit, h.inst, 0u, shard) : qbase + wave_push(hit, q_count(rc.counts, 0, Q_HIT, shard));
-        // class queues: the hit sits in its class' sub-queue, the record (as after k_extend) at an index of its own inside the shard
-        const uint32_t rec = rc.n_classes > 1u ? qbase + ((blockIdx.x / kShards) * blockDim.x + threadIdx.x) * job.reps + k : slot;
-        if (hit && rec < qbase + rc.shard_cap) {   // (always: the host sizes a shard for its workgroups' samples; nothing is ever written past it)
+        first_file<kWalk>(sc, rc, ray, h, active, live, ri, job.reps, k, [&] {
             DRng rng;
             rng.s = spt_rng_seed(job.seed, sa, sb);
-            store_path(rc.qa, rec, ray, 0.0f, gray(1.0f), ri, mk3(0, 0, 0), pack_meta(0u, -1), rng);
-            rc.hits.t_v_w_prim[slot] = make_float4(h.t, h.v, h.w, __int_as_float(h.prim));
-            rc.hits.inst_src[slot] = make_uint2((uint32_t)h.inst, rec);
-        }
+            return rng;
+        });
     }
 }
 

@@ -3385,31 +3385,141 @@ static spt_status trace_common(const spt_scene* scene_c, uint32_t n, const spt_r
     });
 }
 
-// ---- radiance along caller rays (spt_radiance) ----
-// The queues, counters and radiance slots of a pass of n rays x reps repetitions, grown and bound into rc as grow_workspace does for
-// a window of pixels.  A queue shard holds what the intake workgroups mapped to it can append (radiance_kernels.h).
-static size_t grow_ray_workspace(spt_scene* sc, uint32_t n, uint32_t reps, uint32_t max_depth, bool fused, bool class_queues, RenderCtx& rc) {
-    const uint64_t blocks = ((uint64_t)n + kBlock - 1) / kBlock, per_shard = (blocks + kShards - 1) / kShards;
-    const uint64_t shard_cap64 = per_shard * kBlock * std::max(reps, 1u), cap64 = shard_cap64 * kShards;
-    if (cap64 > 0x7fffffffull) fail(SPT_ERR_UNSUPPORTED, "radiance: pass too large (lower rays_per_pass)");
-    const size_t counts_words = grow_queues(sc, (size_t)cap64, (uint32_t)shard_cap64, max_depth, fused, class_queues, false, rc);
-    grow(sc, sc->rad[0], (size_t)n * std::max(reps, 1u) * 3 * sizeof(float));
-    rc.rad = sc->rad[0].as<float>();
-    return counts_words;
-}
+// ---- jobs of n items x S samples without a camera: spt_radiance (rays x repetitions), spt_bake (points), spt_probe (probes) ----
+// An entry checks its arguments, begins an ItemRun, cuts the job into passes of P items x chunks of R samples, and per pass stages its
+// item records, fills its kernels' job struct and runs the chunks with its intake and finish kernels.
 
 // `p` is device memory on the scene's device, aligned to 16 bytes where `align16` (records loaded as float4), else to 4
-static void check_device_pointer(const spt_scene* sc, const void* p, const char* what, bool align16) {
+static void check_device_pointer(const spt_scene* sc, const char* who, const char* flag, const void* p, const char* what, bool align16) {
     hipPointerAttribute_t at;
     std::memset(&at, 0, sizeof at);
     const hipError_t e = hipPointerGetAttributes(&at, p);
     if (e != hipSuccess) (void)hipGetLastError();
     if (e != hipSuccess || at.type != hipMemoryTypeDevice || at.device != sc->device)
-        fail(SPT_ERR_INVALID_ARG, std::string("radiance: SPT_RADIANCE_DEVICE_POINTERS and `") + what + "` is not device memory on the scene's device");
+        fail(SPT_ERR_INVALID_ARG, std::string(who) + ": " + flag + " and `" + what + "` is not device memory on the scene's device");
     if ((reinterpret_cast<uintptr_t>(p) & (align16 ? 15u : 3u)) != 0)
-        fail(SPT_ERR_INVALID_ARG, std::string("radiance: device pointer `") + what + "` is not " + (align16 ? "16" : "4") + "-byte aligned");
+        fail(SPT_ERR_INVALID_ARG, std::string(who) + ": device pointer `" + what + "` is not " + (align16 ? "16" : "4") + "-byte aligned");
 }
 
+extern "C++" {   // (member templates cannot have C linkage; it stands here, inside the file's extern "C" block, behind deliver and FilmReadOut)
+struct ItemRun {
+    spt_scene* const sc;
+    const char* const who;         // the entry, for the refusals
+    spt_render_params plan{};      // what run_setup and bounce read of a plan
+    const spt_camera no_camera{};
+    RenderRun run;                 // (points at the two above)
+    RenderCtx rc{};
+    hipStream_t st = nullptr;
+    uint32_t P = 0, R = 0;         // items per pass, samples per chunk
+    uint32_t k_end = 0;            // the samples that are traced: S, or 0 where nothing asks for a first segment's path
+    size_t counts_words = 0;
+    size_t in_cap = 0;             // host lists: the bytes of a staging slot that hold the item records of a full pass
+
+    // Joins the films and makes the kernel choices of the call (the scene's lock is held and its device selected)
+    ItemRun(spt_scene* sc_, const char* who_, uint32_t max_depth, uint64_t seed, uint32_t S) : sc(sc_), who(who_) {
+        film_join(sc);
+        plan.max_depth = max_depth;
+        run.sc = sc;
+        run.cam = &no_camera;
+        run.params = &plan;
+        run.rays = true;
+        run_setup(run);
+        st = run.st;
+        rc.max_depth = max_depth;
+        rc.seed = seed;
+        rc.spp = S;
+        rc.dyn_refill_below = run.dyn_refill_below;
+        rc.dyn_steps = run.dyn_steps;
+        rc.stream_rounds = run.stream_rounds;
+        rc.stream_refill_below = run.stream_refill_below;
+        rc.visits = sc->visits.as<unsigned long long>();
+    }
+    ItemRun(const ItemRun&) = delete;
+
+    // Passes of P items x chunks of R samples, around 2^22 paths each (`per_pass`: the caller's P, the job field `per_pass_name`; 0:
+    // ours).  Workgroup g of an intake launch appends to queue shard g % kShards only, so a shard's capacity comes in steps of
+    // kShards * kBlock items - the default P is a multiple of that - times R (first_segment.h).  Grows the queues, the counters and
+    // the radiance slots of such a pass and binds them into rc, as grow_workspace does for a window of pixels.
+    void cut(uint64_t n_items, uint32_t S, uint32_t per_pass, const char* per_pass_name, uint32_t k_end_) {
+        constexpr uint64_t kStep = (uint64_t)kShards * kBlock, kTargetPaths = 1ull << 22;
+        const uint64_t P64 = std::min<uint64_t>(per_pass ? per_pass : std::max(kStep, kTargetPaths / S / kStep * kStep), n_items);
+        const uint64_t P_up = (P64 + kStep - 1) / kStep * kStep;
+        P = (uint32_t)P64;
+        R = (uint32_t)std::min<uint64_t>(S, std::max<uint64_t>(1, 2 * kTargetPaths / P_up));
+        if (P_up * R > 0x7fffffffull) fail(SPT_ERR_UNSUPPORTED, std::string(who) + ": pass too large (lower " + per_pass_name + ")");
+        k_end = k_end_;
+        const uint32_t reps = k_end ? R : 1u;
+        counts_words = grow_queues(sc, (size_t)(P_up * reps), (uint32_t)(P_up / kShards * reps), rc.max_depth, run.fused, run.class_queues, false, rc);
+        grow(sc, sc->rad[0], (size_t)P * reps * 3 * sizeof(float));
+        rc.rad = sc->rad[0].as<float>();
+    }
+
+    // Host lists: the two pinned staging slots of in_bytes + aux_bytes with their events, the device copies of a pass' records, and
+    // `out_bytes` of results for the whole job (sc->ray_rgb), which it returns
+    float* stage_buffers(size_t in_bytes, size_t aux_bytes, size_t out_bytes) {
+        in_cap = in_bytes;
+        for (int k = 0; k < 2; ++k) {
+            sc->ray_stage[k].ensure(in_bytes + aux_bytes);
+            if (!sc->ev_ray[k]) HIP_CHECK(hipEventCreateWithFlags(&sc->ev_ray[k], hipEventDisableTiming));
+        }
+        sc->ray_in.ensure(in_bytes);
+        if (aux_bytes) sc->ray_aux_in.ensure(aux_bytes);
+        sc->ray_rgb.ensure(out_bytes);
+        return sc->ray_rgb.as<float>();
+    }
+
+    // Host lists: once the slot's previous copy (two passes ago) has left it, `fill(records, aux)` fills it beside the pass in flight;
+    // then its in_bytes go to sc->ray_in and its aux_bytes, which lie behind the records of a full pass, to sc->ray_aux_in
+    template <class Fill>
+    void stage(uint64_t pass, size_t in_bytes, size_t aux_bytes, Fill fill) {
+        char* const slot = static_cast<char*>(sc->ray_stage[pass & 1u].p);
+        if (pass >= 2) HIP_CHECK(hipEventSynchronize(sc->ev_ray[pass & 1u]));
+        fill(slot, slot + in_cap);
+        HIP_CHECK(hipMemcpyAsync(sc->ray_in.p, slot, in_bytes, hipMemcpyHostToDevice, st));
+        if (aux_bytes) HIP_CHECK(hipMemcpyAsync(sc->ray_aux_in.p, slot + in_cap, aux_bytes, hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipEventRecord(sc->ev_ray[pass & 1u], st));
+    }
+
+    // one of an entry's three intake kernels over the n items of the pass, behind the zeroing of the queue counters
+    template <class Job>
+    void launch_intake(void (*lds)(DScene, RenderCtx, Job), void (*mem)(DScene, RenderCtx, Job), void (*streaming)(DScene, RenderCtx, Job), const Job& job) {
+        const bool stream = sc->swalk && !sc->lds_geo;   // the walkers of spt_trace_closest / spt_trace_any
+        HIP_CHECK(hipMemsetAsync(rc.counts, 0, counts_words * sizeof(uint32_t), st));
+        hipLaunchKernelGGL(stream ? streaming : sc->lds_geo ? lds : mem, dim3((job.n + kBlock - 1) / kBlock), dim3(kBlock), sc->lds_bytes, st, sc->d, rc, job);
+        HIP_CHECK(hipGetLastError());
+    }
+
+    // The chunks of a pass of n items: per chunk it writes the job's `k_first` and `reps`, then `intake(first)` (the entry's
+    // launch_intake), the bounces, `finish(first, last)`.  With k_end == 0 (`while curr_depth < self.max_depth`, pt.rs:48, never
+    // runs: every path is 0) there is one chunk of no samples
+    template <class Intake, class Finish>
+    void chunks(uint32_t n, uint32_t& k_first, uint32_t& reps, const float4* ray_aux, Intake intake, Finish finish) {
+        run.ray_aux = ray_aux;
+        run.ray_aux_wrap = n;
+        rc.n_pixels = n;
+        for (uint64_t k0 = 0; k0 == 0u || k0 < k_end; k0 += R) {
+            k_first = (uint32_t)k0;
+            reps = (uint32_t)std::min<uint64_t>(R, k_end - std::min<uint64_t>(k0, k_end));
+            rc.pass_first = k_first;
+            rc.pass_samples = reps;
+            rc.rad_plane = (size_t)std::max(reps, 1u) * n;
+            intake(k0 == 0u);
+            for (uint32_t b = 0; b < (reps ? rc.max_depth : 0u); ++b)
+                if (bounce(run, rc, b, st)) break;
+            finish(k0 == 0u ? 1u : 0u, k0 + R >= k_end ? 1u : 0u);
+            HIP_CHECK(hipGetLastError());
+        }
+    }
+
+    // the results are where the caller asked: host lists through the device-to-host path of the film read-outs
+    void deliver_out(bool dev, float* out, size_t n_floats) {
+        if (!dev) deliver(sc->img_out8, sc->ray_rgb.p, n_floats, FilmReadOut{out, nullptr}, st);
+        else HIP_CHECK(hipStreamSynchronize(st));
+    }
+};
+}
+
+// ---- radiance along caller rays (spt_radiance) ----
 spt_status spt_radiance(const spt_scene* scene_c, const spt_radiance_job* job) {
     if (!scene_c || !job) { g_error = "radiance: null argument"; return SPT_ERR_INVALID_ARG; }
     if (job->size < sizeof(spt_radiance_job)) { g_error = "radiance: job->size is below sizeof(spt_radiance_job)"; return SPT_ERR_INVALID_ARG; }
@@ -3429,150 +3539,71 @@ spt_status spt_radiance(const spt_scene* scene_c, const spt_radiance_job* job) {
         if (n_rays > (1ull << 40)) fail(SPT_ERR_UNSUPPORTED, "radiance: more than 2^40 rays");
         HIP_CHECK(hipSetDevice(sc->device));
         if (dev) {   // every check comes before the first allocation, copy or launch
-            check_device_pointer(sc, job->rays, "rays", true);
-            if (job->aux) check_device_pointer(sc, job->aux, "aux", true);
-            check_device_pointer(sc, job->rgb_out, "rgb_out", false);
-            if (want_hits) check_device_pointer(sc, job->hits_out, "hits_out", false);
+            const auto check = [&](const void* p, const char* what, bool align16) { check_device_pointer(sc, "radiance", "SPT_RADIANCE_DEVICE_POINTERS", p, what, align16); };
+            check(job->rays, "rays", true);
+            if (job->aux) check(job->aux, "aux", true);
+            check(job->rgb_out, "rgb_out", false);
+            if (want_hits) check(job->hits_out, "hits_out", false);
         }
-        film_join(sc);
-        spt_render_params plan{};      // what run_setup and bounce read of a plan
-        plan.max_depth = job->max_depth;
-        const spt_camera no_camera{};
-        RenderRun run;
-        run.sc = sc;
-        run.cam = &no_camera;
-        run.params = &plan;
-        run.rays = true;
-        run_setup(run);
-        const hipStream_t st = run.st;
+        ItemRun ir(sc, "radiance", job->max_depth, job->seed, S);
         // auxiliary rays are read by the textured shade levels only
-        const bool use_aux = job->aux != nullptr && sc->textured && !sc->simple && !run.fused && job->max_depth > 0;
-
-        // Passes of P rays x chunks of R repetitions, around 2^22 paths each.  A shard's capacity comes in steps of kShards * kBlock
-        // rays, so the default P is a multiple of that
-        constexpr uint64_t kStep = (uint64_t)kShards * kBlock, kTargetPaths = 1ull << 22;
-        uint64_t P64 = job->rays_per_pass ? job->rays_per_pass : std::max(kStep, kTargetPaths / S / kStep * kStep);
-        P64 = std::min(P64, n_rays);
-        const uint32_t P = (uint32_t)P64;
-        const uint64_t P_up = (P64 + kStep - 1) / kStep * kStep;
-        const uint32_t R = (uint32_t)std::min<uint64_t>(S, std::max<uint64_t>(1, 2 * kTargetPaths / P_up));
-        if (P_up * R > 0x7fffffffull) fail(SPT_ERR_UNSUPPORTED, "radiance: pass too large (lower rays_per_pass)");
-
-        RenderCtx rc{};
-        rc.max_depth = job->max_depth;
-        rc.seed = job->seed;
-        rc.spp = S;
-        const size_t counts_words = grow_ray_workspace(sc, P, job->max_depth ? R : 0u, job->max_depth, run.fused, run.class_queues, rc);
-        rc.dyn_refill_below = run.dyn_refill_below;
-        rc.dyn_steps = run.dyn_steps;
-        rc.stream_rounds = run.stream_rounds;
-        rc.stream_refill_below = run.stream_refill_below;
-        rc.visits = sc->visits.as<unsigned long long>();
+        const bool use_aux = job->aux != nullptr && sc->textured && !sc->simple && !ir.run.fused && job->max_depth > 0;
+        // max_depth 0: no path runs; the intake still reports the hits
+        ir.cut(n_rays, S, job->rays_per_pass, "rays_per_pass", job->max_depth ? S : 0u);
+        const uint32_t P = ir.P;
         float* rgb_dev = job->rgb_out;
         spt_hit* hits_dev = job->hits_out;
         if (!dev) {
-            const size_t in_bytes = (size_t)P * sizeof(spt_path_ray), aux_bytes = use_aux ? (size_t)P * sizeof(spt_ray_aux) : 0;
-            for (int k = 0; k < 2; ++k) {
-                sc->ray_stage[k].ensure(in_bytes + aux_bytes);
-                if (!sc->ev_ray[k]) HIP_CHECK(hipEventCreateWithFlags(&sc->ev_ray[k], hipEventDisableTiming));
-            }
-            sc->ray_in.ensure(in_bytes);
-            if (use_aux) sc->ray_aux_in.ensure(aux_bytes);
-            sc->ray_rgb.ensure((size_t)n_rays * 3 * sizeof(float));
+            rgb_dev = ir.stage_buffers((size_t)P * sizeof(spt_path_ray), use_aux ? (size_t)P * sizeof(spt_ray_aux) : 0, (size_t)n_rays * 3 * sizeof(float));
             if (want_hits) sc->ray_hits.ensure((size_t)n_rays * sizeof(spt_hit));
-            rgb_dev = sc->ray_rgb.as<float>();
             hits_dev = want_hits ? sc->ray_hits.as<spt_hit>() : nullptr;
         }
-        const bool stream = sc->swalk && !sc->lds_geo;   // the walkers of spt_trace_closest
         const float inv = 1.0f / (float)S;
         uint64_t pass = 0;
         for (uint64_t r0 = 0; r0 < n_rays; r0 += P, ++pass) {
-            const uint32_t n = (uint32_t)std::min<uint64_t>(P, n_rays - r0);
             RayJob rj{};
             rj.seed = job->seed;
-            rj.n = n;
+            rj.n = (uint32_t)std::min<uint64_t>(P, n_rays - r0);
             rj.rng_skip = job->rng_skip;
             rj.rgb_out = rgb_dev + 3 * r0;
-            const float4* aux_dev = nullptr;
-            if (dev) {
-                rj.rays = reinterpret_cast<const float4*>(job->rays + r0);
-                if (use_aux) aux_dev = reinterpret_cast<const float4*>(job->aux + r0);
-            } else {
-                // the slot's previous copy (two passes ago) has left it; the host checks and fills it beside the pass in flight
-                PinnedBuffer& slot = sc->ray_stage[pass & 1u];
-                if (pass >= 2) HIP_CHECK(hipEventSynchronize(sc->ev_ray[pass & 1u]));
-                spt_path_ray* const dst = static_cast<spt_path_ray*>(slot.p);
-                const spt_path_ray* const src = job->rays + r0;
-                for (uint32_t i = 0; i < n; ++i) {
-                    const spt_path_ray& r = src[i];
-                    const bool finite = std::isfinite(r.o[0]) && std::isfinite(r.o[1]) && std::isfinite(r.o[2]) && std::isfinite(r.d[0]) &&
-                                        std::isfinite(r.d[1]) && std::isfinite(r.d[2]) && std::isfinite(r.t_min);
-                    if (!finite || (r.d[0] == 0.0f && r.d[1] == 0.0f && r.d[2] == 0.0f)) {
-                        HIP_CHECK(hipStreamSynchronize(st));   // the earlier passes wrote the library's own buffers only
-                        fail(SPT_ERR_INVALID_ARG, "radiance: ray " + std::to_string(r0 + i) + (finite ? " has an all-zero direction" : " has a non-finite o, d or t_min"));
+            rj.rays = reinterpret_cast<const float4*>(job->rays + r0);
+            const float4* aux_dev = use_aux ? reinterpret_cast<const float4*>(job->aux + r0) : nullptr;
+            if (!dev) {   // the host checks the rays while it copies them
+                ir.stage(pass, (size_t)rj.n * sizeof(spt_path_ray), use_aux ? (size_t)rj.n * sizeof(spt_ray_aux) : 0, [&](char* rays, char* aux) {
+                    spt_path_ray* const dst = reinterpret_cast<spt_path_ray*>(rays);
+                    const spt_path_ray* const src = job->rays + r0;
+                    for (uint32_t i = 0; i < rj.n; ++i) {
+                        const spt_path_ray& r = src[i];
+                        const bool finite = std::isfinite(r.o[0]) && std::isfinite(r.o[1]) && std::isfinite(r.o[2]) && std::isfinite(r.d[0]) &&
+                                            std::isfinite(r.d[1]) && std::isfinite(r.d[2]) && std::isfinite(r.t_min);
+                        if (!finite || (r.d[0] == 0.0f && r.d[1] == 0.0f && r.d[2] == 0.0f)) {
+                            HIP_CHECK(hipStreamSynchronize(ir.st));   // the earlier passes wrote the library's own buffers only
+                            fail(SPT_ERR_INVALID_ARG, "radiance: ray " + std::to_string(r0 + i) + (finite ? " has an all-zero direction" : " has a non-finite o, d or t_min"));
+                        }
+                        dst[i] = r;
                     }
-                    dst[i] = r;
-                }
-                const size_t in_bytes = (size_t)n * sizeof(spt_path_ray);
-                HIP_CHECK(hipMemcpyAsync(sc->ray_in.p, slot.p, in_bytes, hipMemcpyHostToDevice, st));
-                if (use_aux) {
-                    char* const aux_slot = static_cast<char*>(slot.p) + (size_t)P * sizeof(spt_path_ray);
-                    std::memcpy(aux_slot, job->aux + r0, (size_t)n * sizeof(spt_ray_aux));
-                    HIP_CHECK(hipMemcpyAsync(sc->ray_aux_in.p, aux_slot, (size_t)n * sizeof(spt_ray_aux), hipMemcpyHostToDevice, st));
-                    aux_dev = sc->ray_aux_in.as<float4>();
-                }
-                HIP_CHECK(hipEventRecord(sc->ev_ray[pass & 1u], st));
+                    if (use_aux) std::memcpy(aux, job->aux + r0, (size_t)rj.n * sizeof(spt_ray_aux));
+                });
                 rj.rays = sc->ray_in.as<float4>();
+                if (use_aux) aux_dev = sc->ray_aux_in.as<float4>();
             }
-            run.ray_aux = aux_dev;
-            run.ray_aux_wrap = n;
-            rc.n_pixels = n;
-            const dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
-            // max_depth 0: `while curr_depth < self.max_depth` (pt.rs:48) never runs, every path is 0; the intake still reports the hits
-            const uint32_t k_end = job->max_depth ? S : 0u;
-            for (uint64_t k0 = 0; k0 == 0u || k0 < k_end; k0 += R) {
-                rj.k_first = (uint32_t)k0;
-                rj.reps = (uint32_t)std::min<uint64_t>(R, k_end - std::min<uint64_t>(k0, k_end));
-                rj.hits_out = (k0 == 0u && hits_dev) ? hits_dev + r0 : nullptr;
-                rc.pass_first = (uint32_t)k0;
-                rc.pass_samples = rj.reps;
-                rc.rad_plane = (size_t)std::max(rj.reps, 1u) * n;
-                if (rj.reps != 0u || rj.hits_out != nullptr) {
-                    HIP_CHECK(hipMemsetAsync(rc.counts, 0, counts_words * sizeof(uint32_t), st));
-                    hipLaunchKernelGGL(stream ? k_ray_intake_stream : sc->lds_geo ? k_ray_intake<true> : k_ray_intake<false>, grid, block, sc->lds_bytes, st,
-                                       sc->d, rc, rj);
-                    HIP_CHECK(hipGetLastError());
-                }
-                for (uint32_t b = 0; b < (rj.reps ? job->max_depth : 0u); ++b)
-                    if (bounce(run, rc, b, st)) break;
-                hipLaunchKernelGGL(k_ray_finish, grid, block, 0, st, rc, rj, k0 == 0u ? 1u : 0u, k0 + R >= k_end ? 1u : 0u, inv);
-                HIP_CHECK(hipGetLastError());
-            }
+            // (chunks() writes rj.k_first and rj.reps before each call of the two lambdas, which launch with rj as it then stands)
+            ir.chunks(rj.n, rj.k_first, rj.reps, aux_dev,
+                      [&](bool first) {
+                          rj.hits_out = (first && hits_dev) ? hits_dev + r0 : nullptr;
+                          if (rj.reps != 0u || rj.hits_out != nullptr) ir.launch_intake(k_ray_intake<true>, k_ray_intake<false>, k_ray_intake_stream, rj);
+                      },
+                      [&](uint32_t first, uint32_t last) {
+                          hipLaunchKernelGGL(k_ray_finish, dim3((rj.n + kBlock - 1) / kBlock), dim3(kBlock), 0, ir.st, ir.rc, rj, first, last, inv);
+                      });
         }
-        if (!dev) {   // the device-to-host path of the film read-outs
-            if (want_hits) HIP_CHECK(hipMemcpyAsync(job->hits_out, sc->ray_hits.p, (size_t)n_rays * sizeof(spt_hit), hipMemcpyDeviceToHost, st));
-            deliver(sc->img_out8, sc->ray_rgb.p, (size_t)n_rays * 3, FilmReadOut{job->rgb_out, nullptr}, st);
-        } else {
-            HIP_CHECK(hipStreamSynchronize(st));
-        }
+        if (!dev && want_hits) HIP_CHECK(hipMemcpyAsync(job->hits_out, sc->ray_hits.p, (size_t)n_rays * sizeof(spt_hit), hipMemcpyDeviceToHost, ir.st));
+        ir.deliver_out(dev, job->rgb_out, (size_t)n_rays * 3);
         return SPT_OK;
     });
 }
 
-// ---- irradiance at surface points (spt_bake) ----
-static void check_bake_pointer(const spt_scene* sc, const void* p, const char* what, bool align16) {
-    hipPointerAttribute_t at;
-    std::memset(&at, 0, sizeof at);
-    const hipError_t e = hipPointerGetAttributes(&at, p);
-    if (e != hipSuccess) (void)hipGetLastError();
-    if (e != hipSuccess || at.type != hipMemoryTypeDevice || at.device != sc->device)
-        fail(SPT_ERR_INVALID_ARG, std::string("bake: SPT_BAKE_DEVICE_POINTERS and `") + what + "` is not device memory on the scene's device");
-    if ((reinterpret_cast<uintptr_t>(p) & (align16 ? 15u : 3u)) != 0)
-        fail(SPT_ERR_INVALID_ARG, std::string("bake: device pointer `") + what + "` is not " + (align16 ? "16" : "4") + "-byte aligned");
-}
-
-// spt_radiance with the rays made by the intake kernel (bake_kernels.h): passes of P points x chunks of R samples under the same
-// capacity rules, the same staging slots, workspace and delivery
+// ---- irradiance at surface points (spt_bake): the rays are made by the intake kernel (bake_kernels.h) ----
 spt_status spt_bake(const spt_scene* scene_c, const spt_bake_job* job) {
     if (!scene_c || !job) { g_error = "bake: null argument"; return SPT_ERR_INVALID_ARG; }
     if (job->size < sizeof(spt_bake_job)) { g_error = "bake: job->size is below sizeof(spt_bake_job)"; return SPT_ERR_INVALID_ARG; }
@@ -3597,8 +3628,8 @@ spt_status spt_bake(const spt_scene* scene_c, const spt_bake_job* job) {
         if (n_points > (1ull << 40)) fail(SPT_ERR_UNSUPPORTED, "bake: more than 2^40 points");
         HIP_CHECK(hipSetDevice(sc->device));
         if (dev) {   // every check comes before the first allocation, copy or launch
-            check_bake_pointer(sc, job->points, "points", true);
-            check_bake_pointer(sc, job->rgb_out, "rgb_out", false);
+            check_device_pointer(sc, "bake", "SPT_BAKE_DEVICE_POINTERS", job->points, "points", true);
+            check_device_pointer(sc, "bake", "SPT_BAKE_DEVICE_POINTERS", job->rgb_out, "rgb_out", false);
         } else {     // ... and a host list is checked as a whole, so that a refusal has written nothing at all
             // SURFACE points are checked against the scene's CURRENT tables: the instance records as the device holds them behind the
             // updates queued so far (read back as spt_trace_* read their results back), the meshes' ranges from the creation
@@ -3622,57 +3653,19 @@ spt_status spt_bake(const spt_scene* scene_c, const spt_bake_job* job) {
                                                          : " does not name a triangle of a mesh instance (instance, prim) or has a non-finite v or w"));
             }
         }
-        film_join(sc);
-        spt_render_params plan{};      // what run_setup and bounce read of a plan
-        plan.max_depth = job->max_depth;
-        const spt_camera no_camera{};
-        RenderRun run;
-        run.sc = sc;
-        run.cam = &no_camera;
-        run.params = &plan;
-        run.rays = true;
-        run_setup(run);
-        const hipStream_t st = run.st;
-
-        // Passes of P points x chunks of R samples, around 2^22 paths each, as spt_radiance cuts rays x repetitions
-        constexpr uint64_t kStep = (uint64_t)kShards * kBlock, kTargetPaths = 1ull << 22;
-        uint64_t P64 = job->points_per_pass ? job->points_per_pass : std::max(kStep, kTargetPaths / S / kStep * kStep);
-        P64 = std::min(P64, n_points);
-        const uint32_t P = (uint32_t)P64;
-        const uint64_t P_up = (P64 + kStep - 1) / kStep * kStep;
-        const uint32_t R = (uint32_t)std::min<uint64_t>(S, std::max<uint64_t>(1, 2 * kTargetPaths / P_up));
-        if (P_up * R > 0x7fffffffull) fail(SPT_ERR_UNSUPPORTED, "bake: pass too large (lower points_per_pass)");
-
-        RenderCtx rc{};
-        rc.max_depth = job->max_depth;
-        rc.seed = job->seed;
-        rc.spp = S;
-        const size_t counts_words = grow_ray_workspace(sc, P, job->max_depth ? R : 0u, job->max_depth, run.fused, run.class_queues, rc);
-        rc.dyn_refill_below = run.dyn_refill_below;
-        rc.dyn_steps = run.dyn_steps;
-        rc.stream_rounds = run.stream_rounds;
-        rc.stream_refill_below = run.stream_refill_below;
-        rc.visits = sc->visits.as<unsigned long long>();
+        ItemRun ir(sc, "bake", job->max_depth, job->seed, S);
+        // max_depth 0: no path runs and out = D; the intake still sums the delta lights
+        ir.cut(n_points, S, job->points_per_pass, "points_per_pass", job->max_depth ? S : 0u);
+        const uint32_t P = ir.P;
         sc->ray_hits.ensure((size_t)P * 4 * sizeof(float));   // D and validity per point of a pass, 4 planes (bake_kernels.h): spt_radiance's hit buffer, idle here
         float* rgb_dev = job->rgb_out;
-        if (!dev) {
-            const size_t in_bytes = (size_t)P * rec_bytes;
-            for (int k = 0; k < 2; ++k) {
-                sc->ray_stage[k].ensure(in_bytes);
-                if (!sc->ev_ray[k]) HIP_CHECK(hipEventCreateWithFlags(&sc->ev_ray[k], hipEventDisableTiming));
-            }
-            sc->ray_in.ensure(in_bytes);
-            sc->ray_rgb.ensure((size_t)n_points * 3 * sizeof(float));
-            rgb_dev = sc->ray_rgb.as<float>();
-        }
-        const bool stream = sc->swalk && !sc->lds_geo;   // the walkers of spt_trace_closest / spt_trace_any
+        if (!dev) rgb_dev = ir.stage_buffers((size_t)P * rec_bytes, 0, (size_t)n_points * 3 * sizeof(float));
         const float inv = 1.0f / (float)S;
         uint64_t pass = 0;
         for (uint64_t r0 = 0; r0 < n_points; r0 += P, ++pass) {
-            const uint32_t n = (uint32_t)std::min<uint64_t>(P, n_points - r0);
             BakeJob bj{};
             bj.seed = job->seed;
-            bj.n = n;
+            bj.n = (uint32_t)std::min<uint64_t>(P, n_points - r0);
             bj.rgb_out = rgb_dev + 3 * r0;
             bj.d_planes = sc->ray_hits.as<float>();
             bj.stream_a = job->first_point + (uint32_t)r0;   // (u32 wrap)
@@ -3680,59 +3673,23 @@ spt_status spt_bake(const spt_scene* scene_c, const spt_bake_job* job) {
             bj.kind = job->kind;
             bj.flip = (job->flags & SPT_BAKE_FLIP) ? 1u : 0u;
             const char* const src = static_cast<const char*>(job->points) + r0 * rec_bytes;
-            if (dev) {
-                bj.points = reinterpret_cast<const float4*>(src);
-            } else {
-                // the slot's previous copy (two passes ago) has left it
-                PinnedBuffer& slot = sc->ray_stage[pass & 1u];
-                if (pass >= 2) HIP_CHECK(hipEventSynchronize(sc->ev_ray[pass & 1u]));
-                std::memcpy(slot.p, src, (size_t)n * rec_bytes);
-                HIP_CHECK(hipMemcpyAsync(sc->ray_in.p, slot.p, (size_t)n * rec_bytes, hipMemcpyHostToDevice, st));
-                HIP_CHECK(hipEventRecord(sc->ev_ray[pass & 1u], st));
+            bj.points = reinterpret_cast<const float4*>(src);
+            if (!dev) {
+                ir.stage(pass, (size_t)bj.n * rec_bytes, 0, [&](char* records, char*) { std::memcpy(records, src, (size_t)bj.n * rec_bytes); });
                 bj.points = sc->ray_in.as<float4>();
             }
-            run.ray_aux = nullptr;
-            run.ray_aux_wrap = n;
-            rc.n_pixels = n;
-            const dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
-            // max_depth 0: no path runs and out = D; the intake still sums the delta lights
-            const uint32_t k_end = job->max_depth ? S : 0u;
-            for (uint64_t k0 = 0; k0 == 0u || k0 < k_end; k0 += R) {
-                bj.k_first = (uint32_t)k0;
-                bj.reps = (uint32_t)std::min<uint64_t>(R, k_end - std::min<uint64_t>(k0, k_end));
-                rc.pass_first = (uint32_t)k0;
-                rc.pass_samples = bj.reps;
-                rc.rad_plane = (size_t)std::max(bj.reps, 1u) * n;
-                HIP_CHECK(hipMemsetAsync(rc.counts, 0, counts_words * sizeof(uint32_t), st));
-                hipLaunchKernelGGL(stream ? k_bake_intake_stream : sc->lds_geo ? k_bake_intake<true> : k_bake_intake<false>, grid, block, sc->lds_bytes, st, sc->d,
-                                   rc, bj);
-                HIP_CHECK(hipGetLastError());
-                for (uint32_t b = 0; b < (bj.reps ? job->max_depth : 0u); ++b)
-                    if (bounce(run, rc, b, st)) break;
-                hipLaunchKernelGGL(k_bake_finish, grid, block, 0, st, rc, bj, k0 == 0u ? 1u : 0u, k0 + R >= k_end ? 1u : 0u, inv);
-                HIP_CHECK(hipGetLastError());
-            }
+            // (chunks() writes bj.k_first and bj.reps before each call of the two lambdas, which launch with bj as it then stands)
+            ir.chunks(bj.n, bj.k_first, bj.reps, nullptr, [&](bool) { ir.launch_intake(k_bake_intake<true>, k_bake_intake<false>, k_bake_intake_stream, bj); },
+                      [&](uint32_t first, uint32_t last) {
+                          hipLaunchKernelGGL(k_bake_finish, dim3((bj.n + kBlock - 1) / kBlock), dim3(kBlock), 0, ir.st, ir.rc, bj, first, last, inv);
+                      });
         }
-        if (!dev) deliver(sc->img_out8, sc->ray_rgb.p, (size_t)n_points * 3, FilmReadOut{job->rgb_out, nullptr}, st);   // the device-to-host path of the film read-outs
-        else HIP_CHECK(hipStreamSynchronize(st));
+        ir.deliver_out(dev, job->rgb_out, (size_t)n_points * 3);
         return SPT_OK;
     });
 }
 
-// ---- spherical-harmonic light probes (spt_probe) ----
-static void check_probe_pointer(const spt_scene* sc, const void* p, const char* what, bool align16) {
-    hipPointerAttribute_t at;
-    std::memset(&at, 0, sizeof at);
-    const hipError_t e = hipPointerGetAttributes(&at, p);
-    if (e != hipSuccess) (void)hipGetLastError();
-    if (e != hipSuccess || at.type != hipMemoryTypeDevice || at.device != sc->device)
-        fail(SPT_ERR_INVALID_ARG, std::string("probe: SPT_PROBE_DEVICE_POINTERS and `") + what + "` is not device memory on the scene's device");
-    if ((reinterpret_cast<uintptr_t>(p) & (align16 ? 15u : 3u)) != 0)
-        fail(SPT_ERR_INVALID_ARG, std::string("probe: device pointer `") + what + "` is not " + (align16 ? "16" : "4") + "-byte aligned");
-}
-
-// spt_bake with uniform sphere rays and a projection behind the bounces (probe_kernels.h): the same passes of P probes x chunks of R
-// samples, the same staging slots, workspace and delivery
+// ---- spherical-harmonic light probes (spt_probe): uniform sphere rays and a projection behind the bounces (probe_kernels.h) ----
 spt_status spt_probe(const spt_scene* scene_c, const spt_probe_job* job) {
     if (!scene_c || !job) { g_error = "probe: null argument"; return SPT_ERR_INVALID_ARG; }
     if (job->size < sizeof(spt_probe_job)) { g_error = "probe: job->size is below sizeof(spt_probe_job)"; return SPT_ERR_INVALID_ARG; }
@@ -3755,73 +3712,34 @@ spt_status spt_probe(const spt_scene* scene_c, const spt_probe_job* job) {
         if (n_points > (1ull << 36)) fail(SPT_ERR_UNSUPPORTED, "probe: more than 2^36 probes");
         HIP_CHECK(hipSetDevice(sc->device));
         if (dev) {   // every check comes before the first allocation, copy or launch
-            check_probe_pointer(sc, job->points, "points", true);
-            check_probe_pointer(sc, job->sh_out, "sh_out", false);
-            if (want_aux) check_probe_pointer(sc, job->aux_out, "aux_out", false);
+            check_device_pointer(sc, "probe", "SPT_PROBE_DEVICE_POINTERS", job->points, "points", true);
+            check_device_pointer(sc, "probe", "SPT_PROBE_DEVICE_POINTERS", job->sh_out, "sh_out", false);
+            if (want_aux) check_device_pointer(sc, "probe", "SPT_PROBE_DEVICE_POINTERS", job->aux_out, "aux_out", false);
         } else {     // ... and a host list is checked as a whole, so that a refusal has written nothing at all
             for (uint64_t i = 0; i < n_points; ++i)
                 if (!spt_probe_ok(job->points + i)) fail(SPT_ERR_INVALID_ARG, "probe: point " + std::to_string(i) + " has a non-finite p");
         }
-        film_join(sc);
-        spt_render_params plan{};      // what run_setup and bounce read of a plan
-        plan.max_depth = job->max_depth;
-        const spt_camera no_camera{};
-        RenderRun run;
-        run.sc = sc;
-        run.cam = &no_camera;
-        run.params = &plan;
-        run.rays = true;
-        run_setup(run);
-        const hipStream_t st = run.st;
-
-        // Passes of P probes x chunks of R samples, around 2^22 paths each, as spt_bake cuts points x samples
-        constexpr uint64_t kStep = (uint64_t)kShards * kBlock, kTargetPaths = 1ull << 22;
-        uint64_t P64 = job->points_per_pass ? job->points_per_pass : std::max(kStep, kTargetPaths / S / kStep * kStep);
-        P64 = std::min(P64, n_points);
-        const uint32_t P = (uint32_t)P64;
-        const uint64_t P_up = (P64 + kStep - 1) / kStep * kStep;
-        const uint32_t R = (uint32_t)std::min<uint64_t>(S, std::max<uint64_t>(1, 2 * kTargetPaths / P_up));
-        if (P_up * R > 0x7fffffffull) fail(SPT_ERR_UNSUPPORTED, "probe: pass too large (lower points_per_pass)");
+        ItemRun ir(sc, "probe", job->max_depth, job->seed, S);
         // max_depth 0: no path runs and sh = D; the first segments are still traced when the visibility record is asked for
-        const uint32_t k_end = (job->max_depth || want_aux) ? S : 0u;
-
-        RenderCtx rc{};
-        rc.max_depth = job->max_depth;
-        rc.seed = job->seed;
-        rc.spp = S;
-        const size_t counts_words = grow_ray_workspace(sc, P, k_end ? R : 0u, job->max_depth, run.fused, run.class_queues, rc);
-        rc.dyn_refill_below = run.dyn_refill_below;
-        rc.dyn_steps = run.dyn_steps;
-        rc.stream_rounds = run.stream_rounds;
-        rc.stream_refill_below = run.stream_refill_below;
-        rc.visits = sc->visits.as<unsigned long long>();
+        ir.cut(n_points, S, job->points_per_pass, "points_per_pass", (job->max_depth || want_aux) ? S : 0u);
+        const uint32_t P = ir.P;
         // D, validity and the visibility carry per probe of a pass (kProbePlanes planes of P words), then the first segments of a chunk
         // (R * P words), probe_kernels.h: spt_radiance's hit buffer, idle here
-        const size_t seg_cap = (size_t)P * std::max(R, 1u);
+        const size_t seg_cap = (size_t)P * std::max(ir.R, 1u);
         sc->ray_hits.ensure(((size_t)P * kProbePlanes + seg_cap) * sizeof(float));
         float* sh_dev = job->sh_out;
         float* aux_dev = job->aux_out;
-        if (!dev) {
-            const size_t in_bytes = (size_t)P * sizeof(spt_probe_point);
-            for (int k = 0; k < 2; ++k) {
-                sc->ray_stage[k].ensure(in_bytes);
-                if (!sc->ev_ray[k]) HIP_CHECK(hipEventCreateWithFlags(&sc->ev_ray[k], hipEventDisableTiming));
-            }
-            sc->ray_in.ensure(in_bytes);
-            // sh for every probe, then aux for every probe
-            sc->ray_rgb.ensure((size_t)n_points * (SPT_PROBE_SH_WORDS + (want_aux ? SPT_PROBE_AUX_WORDS : 0u)) * sizeof(float));
-            sh_dev = sc->ray_rgb.as<float>();
+        if (!dev) {   // sh for every probe, then aux for every probe
+            sh_dev = ir.stage_buffers((size_t)P * sizeof(spt_probe_point), 0, (size_t)n_points * (SPT_PROBE_SH_WORDS + (want_aux ? SPT_PROBE_AUX_WORDS : 0u)) * sizeof(float));
             aux_dev = want_aux ? sh_dev + (size_t)n_points * SPT_PROBE_SH_WORDS : nullptr;
         }
-        const bool stream = sc->swalk && !sc->lds_geo;   // the walkers of spt_trace_closest / spt_trace_any
         const float inv = 1.0f / (float)S;
         const float w = spt_probe_weight(S);
         uint64_t pass = 0;
         for (uint64_t r0 = 0; r0 < n_points; r0 += P, ++pass) {
-            const uint32_t n = (uint32_t)std::min<uint64_t>(P, n_points - r0);
             ProbeJob pj{};
             pj.seed = job->seed;
-            pj.n = n;
+            pj.n = (uint32_t)std::min<uint64_t>(P, n_points - r0);
             pj.sh_out = sh_dev + SPT_PROBE_SH_WORDS * r0;
             pj.aux_out = aux_dev ? aux_dev + SPT_PROBE_AUX_WORDS * r0 : nullptr;
             pj.planes = sc->ray_hits.as<float>();
@@ -3832,44 +3750,20 @@ spt_status spt_probe(const spt_scene* scene_c, const spt_probe_job* job) {
             pj.stream_b = job->first_sample;
             pj.paths = job->max_depth ? 1u : 0u;
             const spt_probe_point* const src = job->points + r0;
-            if (dev) {
-                pj.points = reinterpret_cast<const float4*>(src);
-            } else {
-                // the slot's previous copy (two passes ago) has left it
-                PinnedBuffer& slot = sc->ray_stage[pass & 1u];
-                if (pass >= 2) HIP_CHECK(hipEventSynchronize(sc->ev_ray[pass & 1u]));
-                std::memcpy(slot.p, src, (size_t)n * sizeof(spt_probe_point));
-                HIP_CHECK(hipMemcpyAsync(sc->ray_in.p, slot.p, (size_t)n * sizeof(spt_probe_point), hipMemcpyHostToDevice, st));
-                HIP_CHECK(hipEventRecord(sc->ev_ray[pass & 1u], st));
+            pj.points = reinterpret_cast<const float4*>(src);
+            if (!dev) {
+                ir.stage(pass, (size_t)pj.n * sizeof(spt_probe_point), 0, [&](char* records, char*) { std::memcpy(records, src, (size_t)pj.n * sizeof(spt_probe_point)); });
                 pj.points = sc->ray_in.as<float4>();
             }
-            run.ray_aux = nullptr;
-            run.ray_aux_wrap = n;
-            rc.n_pixels = n;
-            const dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
-            const dim3 grid_finish((uint32_t)(((uint64_t)n * SPT_PROBE_COEFFS + kBlock - 1) / kBlock));
-            for (uint64_t k0 = 0; k0 == 0u || k0 < k_end; k0 += R) {
-                pj.k_first = (uint32_t)k0;
-                pj.reps = (uint32_t)std::min<uint64_t>(R, k_end - std::min<uint64_t>(k0, k_end));
-                rc.pass_first = (uint32_t)k0;
-                rc.pass_samples = pj.reps;
-                rc.rad_plane = (size_t)std::max(pj.reps, 1u) * n;
-                HIP_CHECK(hipMemsetAsync(rc.counts, 0, counts_words * sizeof(uint32_t), st));
-                hipLaunchKernelGGL(stream ? k_probe_intake_stream : sc->lds_geo ? k_probe_intake<true> : k_probe_intake<false>, grid, block, sc->lds_bytes, st,
-                                   sc->d, rc, pj);
-                HIP_CHECK(hipGetLastError());
-                for (uint32_t b = 0; b < (pj.reps ? job->max_depth : 0u); ++b)
-                    if (bounce(run, rc, b, st)) break;
-                hipLaunchKernelGGL(k_probe_finish, grid_finish, block, 0, st, rc, pj, k0 == 0u ? 1u : 0u, k0 + R >= k_end ? 1u : 0u, w, inv);
-                HIP_CHECK(hipGetLastError());
-            }
+            // (chunks() writes pj.k_first and pj.reps before each call of the two lambdas, which launch with pj as it then stands)
+            ir.chunks(pj.n, pj.k_first, pj.reps, nullptr, [&](bool) { ir.launch_intake(k_probe_intake<true>, k_probe_intake<false>, k_probe_intake_stream, pj); },
+                      [&](uint32_t first, uint32_t last) {   // a lane per (coefficient, probe)
+                          const dim3 grid((uint32_t)(((uint64_t)pj.n * SPT_PROBE_COEFFS + kBlock - 1) / kBlock));
+                          hipLaunchKernelGGL(k_probe_finish, grid, dim3(kBlock), 0, ir.st, ir.rc, pj, first, last, w, inv);
+                      });
         }
-        if (!dev) {   // the device-to-host path of the film read-outs
-            if (want_aux) HIP_CHECK(hipMemcpyAsync(job->aux_out, aux_dev, (size_t)n_points * SPT_PROBE_AUX_WORDS * sizeof(float), hipMemcpyDeviceToHost, st));
-            deliver(sc->img_out8, sc->ray_rgb.p, (size_t)n_points * SPT_PROBE_SH_WORDS, FilmReadOut{job->sh_out, nullptr}, st);
-        } else {
-            HIP_CHECK(hipStreamSynchronize(st));
-        }
+        if (!dev && want_aux) HIP_CHECK(hipMemcpyAsync(job->aux_out, aux_dev, (size_t)n_points * SPT_PROBE_AUX_WORDS * sizeof(float), hipMemcpyDeviceToHost, ir.st));
+        ir.deliver_out(dev, job->sh_out, (size_t)n_points * SPT_PROBE_SH_WORDS);
         return SPT_OK;
     });
 }

@@ -337,3 +337,42 @@ def test_max_depth_zero_is_black_and_still_reports_hits():
     assert (rgb.view(np.uint32) == 0).all()
     _, ref = ds.radiance(rays, max_depth=DEPTH, seed=SEED, hits=True)
     assert hits.tobytes() == ref.tobytes()
+
+
+# ---- 10. the three item entries share their staging and workspace buffers -----------------------------------------------------------
+
+@pytest.mark.parametrize("name,camera", [("cfg2_cube", None), ("t_materials", "main")])
+def test_radiance_bake_and_probes_interleaved_with_sizes_that_shrink_and_grow(name, camera):
+    """spt_probe, spt_radiance and spt_bake in turn on one device scene, host lists cut into passes of 256 items: the calls share the
+    pinned staging slots and their events, the device copies of a pass' records, the result buffer and the hit buffer, which each
+    entry sizes and lays out for itself.  Every call must give, word for word, what it gives as the first call on a fresh device scene.
+    The reference is the same code on a fresh scene, not the oracle: this finds state that leaks from one entry into the next, not an
+    error every call shares (the oracle-anchored tests above and in test_gpu_bake.py / test_gpu_probe.py are there for that).  The calls
+    of 700, 900 and 1000 items have three or four passes and wait for a staging slot's event; those of 300, 40 and 17 have one or two."""
+    import test_gpu_bake
+    import test_gpu_probe
+    sc = _scene(name + ".json")
+    rays, _, _, skip = _plan(name + ".json", camera)
+    points = test_gpu_bake._points(name)
+    probes = np.concatenate([test_gpu_probe._grid(sc, seed) for seed in (5, 6, 7)])
+    assert rays.shape[0] >= 4000 and points.shape[0] >= 917 and probes.shape[0] >= 740
+    kw = dict(max_depth=DEPTH, seed=SEED)
+    calls = [
+        lambda ds: ds.probes(probes[:700], samples=8, aux=True, points_per_pass=256, **kw),
+        lambda ds: ds.radiance(rays[3000:3300], rng_skip=skip, hits=True, repeats=3, rays_per_pass=256, **kw),
+        lambda ds: ds.bake(points[:900], samples=4, points_per_pass=256, **kw),
+        lambda ds: ds.probes(probes[700:740], samples=8, points_per_pass=256, **kw),
+        lambda ds: ds.radiance(rays[3000:4000], rng_skip=skip, hits=True, rays_per_pass=256, **kw),
+        lambda ds: ds.bake(points[900:917], samples=4, points_per_pass=256, **kw),
+    ]
+    sc.close_device_scene(0)
+    ds = sc.device_scene(0)
+    got = [call(ds) for call in calls]
+    for i, call in enumerate(calls):
+        sc.close_device_scene(0)
+        want = call(sc.device_scene(0))
+        for g, w in zip(got[i] if isinstance(got[i], tuple) else (got[i],), want if isinstance(want, tuple) else (want,)):
+            if g.dtype == spt.HIT_DTYPE:
+                assert g.tobytes() == w.tobytes(), "call %d: hits" % i
+            else:
+                assert np.isfinite(w).any() and _util.same_words(g, w), "call %d" % i

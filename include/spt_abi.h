@@ -1032,6 +1032,53 @@ typedef struct spt_probe_job {
 } spt_probe_job;
 spt_status spt_probe(const spt_scene* scene, const spt_probe_job* job);
 
+/* ---- first-hit surface records along caller rays (additive to ABI v14: detect it by symbol) --------------------------------------
+ * spt_gbuffer returns, per caller ray, the surface the ray sees first: where, which, its normal and its albedo.  It is what lies
+ * between spt_trace_closest and a path trace: the shading inputs of the integrator's depth-0 vertex, without a path.
+ * All arithmetic is IEEE f32, one rounded operation at a time, in the written order, no contraction.
+ * Hit.     (t, instance, prim, v, w) are word for word what spt_trace_closest returns for (o, t_min, d, f32::MAX): the hits_out
+ *          of spt_radiance.
+ * Miss.    t = f32::MAX, instance = prim = -1, every other word +0.
+ * p        p_k = o_k + d_k * t: the point the integrator shades from.
+ * n        the world-space interpolated normal of the hit as the integrator rebuilds it (what SPT_RENDER_DEBUG_NORMAL shows before
+ *          its * 0.5 + 0.5).  No normal map enters, for spheres, patches and meshes alike; for a mesh it is the normal
+ *          spt_bake_resolve gives for the hit.
+ * albedo   the rule of SPT_RENDER_AOV_ALBEDO on the material record evaluated at the hit (per-hit recipes and P-NDF fallbacks as
+ *          there; emission and the normal map do not enter).  With `aux`, a scene that samples textures computes the texture
+ *          footprint from the ray's two auxiliary rays, Intersection::calc_differential with (rx_o, rx_d, ry_o, ry_d), as
+ *          spt_radiance does for its depth-0 hit; without it the differentials are 0.  Scenes that sample no texture never read
+ *          `aux`.
+ * surface  the instance's `surface` index.
+ * flags    SPT_GBUF_BACKFACING iff (n0*d0 + n1*d1) + n2*d2 > 0;  SPT_GBUF_LIGHT iff the instance's light >= 0;  bits 8..15 the
+ *          instance's prim_type.
+ * A record depends on its own ray (and its aux record) and on the scene only: not on its place in the array, its neighbours,
+ * rays_per_pass or how the call is cut into passes.  Nothing is random: stream_a / stream_b of the rays are ignored.
+ * Pointers, staging, the checks of host rays, the lock, the shared render workspace and scenes with Bezier patches: as
+ * spt_radiance.  With SPT_GBUFFER_DEVICE_POINTERS rays, aux and out are device memory on the scene's device, each 16-byte aligned.
+ * Refusals write nothing and leave the scene usable.  SPT_ERR_INVALID_ARG: a null scene or job; null rays or out while n_rays > 0;
+ * size below sizeof(spt_gbuffer_job); unknown flags; a host ray whose o, d or t_min is not finite or whose d is all zero (the
+ * message names the first such index); a device pointer that is not device memory of the scene's device or misaligned.
+ * SPT_ERR_UNSUPPORTED: more than 2^40 rays.  n_rays == 0 returns SPT_OK and does nothing.
+ * Synchronous.  It reads the scene's current records, so it follows spt_scene_update, spt_scene_deform and
+ * spt_scene_deform_vertices like the other ray entries, and touches no film. */
+enum { SPT_GBUFFER_DEVICE_POINTERS = 1u };
+enum { SPT_GBUF_BACKFACING = 1u, SPT_GBUF_LIGHT = 2u };   /* spt_gbuffer_rec::flags; bits 8..15: the instance's prim_type */
+typedef struct spt_gbuffer_rec {      /* 64 B: four 16-byte words */
+    float p[3];      float t;         /* world hit point; t = f32::MAX on a miss */
+    float n[3];      int32_t instance;/* -1 on a miss */
+    float albedo[3]; int32_t prim;    /* -1 on a miss */
+    float v, w;      uint32_t surface; uint32_t flags;
+} spt_gbuffer_rec;
+typedef struct spt_gbuffer_job {
+    uint32_t size, flags;             /* sizeof(spt_gbuffer_job) as the caller was compiled (the struct only grows at its tail); SPT_GBUFFER_* */
+    uint64_t n_rays;
+    const spt_path_ray* rays;         /* spt_radiance's records; stream_a / stream_b are ignored */
+    const spt_ray_aux* aux;           /* NULL, or one per ray: texture footprints, as spt_radiance takes them */
+    uint32_t rays_per_pass, pad;      /* tuning, 0 = default */
+    spt_gbuffer_rec* out;             /* n_rays records */
+} spt_gbuffer_job;
+spt_status spt_gbuffer(const spt_scene* scene, const spt_gbuffer_job* job);
+
 /* Page-locked host memory for rgb_mean_out: lets the final device-to-host copy of the film run as one
  * DMA at PCIe rate instead of being staged through the runtime's bounce buffers.  Optional: any host
  * pointer is accepted by spt_render. */

@@ -320,6 +320,19 @@ class RadianceJob(C.Structure):
                 ("rays_per_pass", C.c_uint32), ("rgb_out", C.c_void_p), ("hits_out", C.c_void_p)]
 
 
+# spt_gbuffer: spt_gbuffer_rec (64 B) and the bits of its `flags` (bits 8..15: the instance's prim_type)
+GBUFFER_DTYPE = np.dtype([("p", "<f4", 3), ("t", "<f4"), ("n", "<f4", 3), ("instance", "<i4"), ("albedo", "<f4", 3), ("prim", "<i4"),
+                          ("v", "<f4"), ("w", "<f4"), ("surface", "<u4"), ("flags", "<u4")])
+GBUFFER_DEVICE_POINTERS = 1
+GBUF_BACKFACING, GBUF_LIGHT = 1, 2
+
+
+class GBufferJob(C.Structure):
+    """spt_gbuffer_job (spt_gbuffer); `size` is sizeof of the struct."""
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("n_rays", C.c_uint64), ("rays", C.c_void_p), ("aux", C.c_void_p),
+                ("rays_per_pass", C.c_uint32), ("pad", C.c_uint32), ("out", C.c_void_p)]
+
+
 # spt_bake: spt_bake_point (16 B: spt_hit without t) and spt_bake_world_point (32 B)
 BAKE_POINT_DTYPE = np.dtype([("instance", "<u4"), ("prim", "<u4"), ("v", "<f4"), ("w", "<f4")])
 BAKE_WORLD_DTYPE = np.dtype([("p", "<f4", 3), ("pad0", "<f4"), ("n", "<f4", 3), ("pad1", "<f4")])
@@ -522,6 +535,8 @@ def hip_lib() -> C.CDLL:
             lib.spt_bake.argtypes = [C.c_void_p, C.POINTER(BakeJob)]
         if hasattr(lib, "spt_probe"):   # (the same)
             lib.spt_probe.argtypes = [C.c_void_p, C.POINTER(ProbeJob)]
+        if hasattr(lib, "spt_gbuffer"):   # (the same)
+            lib.spt_gbuffer.argtypes = [C.c_void_p, C.POINTER(GBufferJob)]
         if hasattr(lib, "spt_scene_update"):   # (the same)
             lib.spt_scene_update.argtypes = [C.c_void_p, C.POINTER(SceneUpdateDesc)]
         if hasattr(lib, "spt_scene_deform"):   # (the same)
@@ -874,6 +889,42 @@ class DeviceScene:
         job.rgb_out, job.hits_out = out.ctypes.data, hit.ctypes.data if hits else None
         _check_hip(lib.spt_radiance(self._h, C.byref(job)))
         return (out, hit) if hits else out
+
+    def gbuffer(self, rays, aux=None, rays_per_pass: int = 0):
+        """spt_gbuffer: per caller ray the surface it sees first, n GBUFFER_DTYPE records (p, t, n, instance, albedo, prim, v, w,
+        surface, flags; a miss has t = f32::MAX, instance = prim = -1 and zeros elsewhere).  rays / aux are PATH_RAY_DTYPE /
+        RAY_AUX_DTYPE arrays as radiance takes them (the streams are ignored), or contiguous float32 torch tensors on the scene's
+        device of shape (n, 12) / (n, 16): then the producer's current stream is synchronised, the library reads and writes device
+        memory and the result is an (n, 16) float32 tensor holding the same 64-byte records; its integer fields (columns 7
+        instance, 11 prim, 14 surface, 15 flags) are read through .view(torch.int32)."""
+        lib = self._entry("spt_gbuffer")
+        job = GBufferJob(size=C.sizeof(GBufferJob), flags=0, rays_per_pass=rays_per_pass)
+        if type(rays).__module__.split(".")[0] == "torch":
+            import torch
+            self._check_tensor(rays, "rays", (12,))
+            if aux is not None:
+                self._check_tensor(aux, "aux", (16,))
+            n = rays.shape[0]
+            if aux is not None and aux.shape[0] != n:
+                raise ValueError("aux: one record per ray is expected")
+            out = torch.empty((n, 16), dtype=torch.float32, device=rays.device)
+            self._producer_done(rays)
+            job.flags, job.n_rays = GBUFFER_DEVICE_POINTERS, n
+            job.rays, job.aux = rays.data_ptr() if n else None, aux.data_ptr() if aux is not None and n else None
+            job.out = out.data_ptr() if n else None
+            _check_hip(lib.spt_gbuffer(self._h, C.byref(job)))
+            return out
+        rays = np.ascontiguousarray(rays, dtype=PATH_RAY_DTYPE).reshape(-1)
+        n = rays.shape[0]
+        if aux is not None:
+            aux = np.ascontiguousarray(aux, dtype=RAY_AUX_DTYPE).reshape(-1)
+            if aux.shape[0] != n:
+                raise ValueError("aux: one record per ray is expected")
+        out = np.zeros(n, dtype=GBUFFER_DTYPE)
+        job.n_rays = n
+        job.rays, job.aux, job.out = rays.ctypes.data, aux.ctypes.data if aux is not None else None, out.ctypes.data
+        _check_hip(lib.spt_gbuffer(self._h, C.byref(job)))
+        return out
 
     def bake(self, points, samples: int = 16, max_depth: int = 8, seed: int = 1, first_point: int = 0, first_sample: int = 0,
              points_per_pass: int = 0, world: bool = False, flip: bool = False):
@@ -1275,6 +1326,32 @@ def camera_rays(model: "CameraModel", renderer: "PathTracer", width: int, height
     ax = np.zeros((count, height, width), dtype=RAY_AUX_DTYPE) if aux else None
     _check_host(lib.spt_host_camera_rays(C.byref(model), C.byref(p), first, count, rays.ctypes.data, ax.ctypes.data if aux else None))
     return (rays, ax) if aux else rays
+
+
+def camera_gbuffer(scene, model: "CameraModel", renderer: "PathTracer", width: int, height: int, samples: int = 1, device: int = 0) -> dict:
+    """First-hit images of a camera model: camera_rays(model, renderer, width, height, k, 1, aux=True) through DeviceScene.gbuffer
+    for the plan samples k = 0 .. samples - 1, one at a time.  `scene` is a Scene (its device scene on `device` serves the call) or
+    a DeviceScene.  Returns float32 images: "albedo" and "normal" (height, width, 3), the sums in sample order (a miss adds 0)
+    times 1 / samples; "depth" (height, width), the sum of t over the hit samples divided by their count, 0 without one;
+    "coverage" (height, width), hits / samples."""
+    if samples < 1:
+        raise ValueError("samples must be >= 1")
+    ds = scene if isinstance(scene, DeviceScene) else scene.device_scene(device)
+    albedo = np.zeros((height, width, 3), dtype=np.float32)
+    normal = np.zeros((height, width, 3), dtype=np.float32)
+    t_sum = np.zeros((height, width), dtype=np.float32)
+    hits = np.zeros((height, width), dtype=np.float32)
+    for k in range(samples):
+        rays, aux = camera_rays(model, renderer, width, height, k, 1, aux=True)
+        rec = ds.gbuffer(rays, aux).reshape(height, width)
+        hit = rec["instance"] >= 0
+        albedo += rec["albedo"]
+        normal += rec["n"]
+        t_sum += np.where(hit, rec["t"], np.float32(0.0))
+        hits += hit.astype(np.float32)
+    inv = np.float32(1.0) / np.float32(samples)
+    depth = np.where(hits > 0, t_sum / np.maximum(hits, np.float32(1.0)), np.float32(0.0)).astype(np.float32)
+    return {"albedo": albedo * inv, "normal": normal * inv, "depth": depth, "coverage": hits / np.float32(samples)}
 
 
 @dataclass

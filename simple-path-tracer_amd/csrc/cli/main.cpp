@@ -18,6 +18,9 @@
 // 8-bit image the reference saves (spt_film_read_rgb8: a quarter of the float film's bytes); the EXR outputs stay float.
 // --film-devices d0,d1,.. (an index may repeat) runs the same progressive loop over a multi film on those devices (one shard film per
 // device, spt_host_multi_film_*; the denoiser runs once on the gathered image, spt_denoise_image) and writes the same bytes.
+// --gbuffer-out STEM [--gbuffer-samples N] writes the first-hit images of the camera, or of the camera model of the same command line,
+// as float EXR files STEM_albedo.exr, STEM_normal.exr and STEM_depth.exr (R depth, G coverage): spt_gbuffer over spt_host_camera_rays,
+// N plan samples averaged, on one device; -o may then be left out.
 // A renderer whose box filter reaches neighbouring pixels (ceil(radius - 0.5) >= 1) gets a film that keeps its samples
 // (SPT_FILM_KEEP_SAMPLES): --preview-every, --time-limit and --film-devices work with it, the options that need moments or buckets exit with code 2.
 // A renderer with a weighted filter ("tent", "gaussian", "mitchell") always renders through such a film plus spt_film_filter, the plain
@@ -46,6 +49,7 @@ static void usage() {
                  "           [--lens-radius R --focus-distance D | --orthographic H | --panorama]   (a camera model in the scene camera's place)\n"
                  "           [--bake-lightmap INSTANCE --bake-size WxH [--bake-samples N]]   (a float RGB EXR lightmap of a mesh instance: E / pi per texel)\n"
                  "           [--bake-probes points.txt [--probe-samples N]]   (SH light probes at the `x y z` of each line: 27 coefficients + 4 visibility numbers per line of -o)\n"
+                 "           [--gbuffer-out STEM [--gbuffer-samples N]]   (first-hit images STEM_albedo.exr, STEM_normal.exr, STEM_depth.exr; -o may be left out)\n"
                  "           [--animate frames.json]   (one plain image <out>_NNNN per frame: {\"frames\": [{\"<instance>\": {<transform>}, ..}, ..]})\n");
 }
 
@@ -241,6 +245,10 @@ int main(int argc, char** argv) {
     // --bake-probes points.txt [--probe-samples N]: spt_probe at the points of the file
     std::string probe_path;
     uint32_t probe_samples = 64;
+    // --gbuffer-out STEM [--gbuffer-samples N]: spt_gbuffer over the camera's rays
+    std::string gbuffer_out;
+    uint32_t gbuffer_samples = 1;
+    bool gbuffer_samples_given = false;
     std::vector<int32_t> device_list;
     std::vector<int32_t> film_devices;
     bool film_devices_given = false, film_devices_ok = true;
@@ -299,10 +307,12 @@ int main(int argc, char** argv) {
         else if (a == "--bake-samples") bake_samples = (uint32_t)std::atoi(next());
         else if (a == "--bake-probes") probe_path = next();
         else if (a == "--probe-samples") probe_samples = (uint32_t)std::atoi(next());
+        else if (a == "--gbuffer-out") gbuffer_out = next();
+        else if (a == "--gbuffer-samples") { gbuffer_samples = (uint32_t)std::atoi(next()); gbuffer_samples_given = true; }
         else if (a == "--film-devices") { film_devices_given = true; film_devices_ok = parse_device_list(next(), &film_devices); }
         else { usage(); return 2; }
     }
-    if (scene_path.empty() || renderer_path.empty() || out_path.empty()) { usage(); return 2; }
+    if (scene_path.empty() || renderer_path.empty() || (out_path.empty() && gbuffer_out.empty())) { usage(); return 2; }
     const bool adaptive_on = adaptive >= 0.0;
     if (!robust && (!robust_estimator.empty() || !mean_out.empty())) {
         std::fprintf(stderr, "Error: --robust-estimator and --mean-out need --robust K\n");
@@ -343,6 +353,24 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "Error: a camera model (--lens-radius, --orthographic, --panorama) renders on one device: not with several --gpus / --devices / "
                              "--film-devices, --animate or --guide albedo|both\n");
         return 2;
+    }
+    if (gbuffer_samples_given && gbuffer_out.empty()) {
+        std::fprintf(stderr, "Error: --gbuffer-samples needs --gbuffer-out STEM\n");
+        return 2;
+    }
+    if (!gbuffer_out.empty()) {
+        if (gbuffer_samples == 0) {
+            std::fprintf(stderr, "Error: --gbuffer-samples N needs N >= 1\n");
+            return 2;
+        }
+        if (gpus > 1 || (film_devices_given && film_devices.size() > 1)) {
+            std::fprintf(stderr, "Error: --gbuffer-out runs on one device: not with several --gpus / --devices / --film-devices\n");
+            return 2;
+        }
+        if (!animate_path.empty() || !bake_instance.empty() || !bake_size.empty() || !probe_path.empty()) {
+            std::fprintf(stderr, "Error: --gbuffer-out writes the first-hit images of one camera: not with --animate, --bake-lightmap or --bake-probes\n");
+            return 2;
+        }
     }
     const uint32_t estimator = robust_estimator == "mon" ? (uint32_t)SPT_ROBUST_MON : (uint32_t)SPT_ROBUST_GMON;
     bool progressive = preview_every > 0 || time_limit > 0.0 || !variance_out.empty() || adaptive_on || !samples_out.empty() || denoise || robust;
@@ -614,6 +642,72 @@ int main(int argc, char** argv) {
     params.shard_count = 1;
     params.strip_rows = 16;
     if (debug_normal) params.flags |= SPT_RENDER_DEBUG_NORMAL;
+    if (!gbuffer_out.empty()) {
+        // The first-hit images, from a device scene of their own ahead of the render, which then runs as it would without them.  Per
+        // plan sample k the model's rays (spt_host_camera_rays, with their auxiliary rays) go through spt_gbuffer; albedo and normal
+        // are the sums in sample order (a miss adds 0) times 1 / N, depth the sum of t over the hit samples divided by their count
+        // (0 without one), coverage hits / N
+        auto gbuffer_fail = [&](const char* what) {
+            std::fprintf(stderr, "Error: %s\n", what);
+            spt_host_scene_free(hs);
+            return 1;
+        };
+        const int32_t gdevice = (film_devices_given && !film_devices.empty()) ? film_devices[0] : (gpus == 1 && !device_list.empty()) ? device_list[0] : gpus == 1 ? 0 : device;
+        const size_t n_pix = (size_t)width * height;
+        std::vector<spt_path_ray> rays(n_pix);
+        std::vector<spt_ray_aux> aux(n_pix);
+        std::vector<spt_gbuffer_rec> rec(n_pix);
+        std::vector<float> albedo(n_pix * 3, 0.0f), normal(n_pix * 3, 0.0f), depth(n_pix * 3, 0.0f), t_sum(n_pix, 0.0f), hits(n_pix, 0.0f);
+        spt_scene* scene = nullptr;
+        if (spt_scene_create(spt_host_scene_desc(hs), gdevice, &scene) != SPT_OK) return gbuffer_fail(spt_last_error());
+        for (uint32_t k = 0; k < gbuffer_samples; ++k) {
+            if (spt_host_camera_rays(&model, &params, k, 1, rays.data(), aux.data()) != SPT_OK) {
+                spt_scene_destroy(scene);
+                return gbuffer_fail(spt_host_last_error());
+            }
+            spt_gbuffer_job job;
+            std::memset(&job, 0, sizeof job);
+            job.size = (uint32_t)sizeof job;
+            job.n_rays = n_pix;
+            job.rays = rays.data();
+            job.aux = aux.data();
+            job.out = rec.data();
+            if (spt_gbuffer(scene, &job) != SPT_OK) {
+                const std::string why = spt_last_error();
+                spt_scene_destroy(scene);
+                return gbuffer_fail(why.c_str());
+            }
+            for (size_t i = 0; i < n_pix; ++i) {
+                const spt_gbuffer_rec& r = rec[i];
+                for (int c = 0; c < 3; ++c) {
+                    albedo[3 * i + c] += r.albedo[c];
+                    normal[3 * i + c] += r.n[c];
+                }
+                if (r.instance >= 0) {
+                    t_sum[i] += r.t;
+                    hits[i] += 1.0f;
+                }
+            }
+        }
+        spt_scene_destroy(scene);
+        const float inv = 1.0f / (float)gbuffer_samples;
+        for (size_t i = 0; i < n_pix; ++i) {
+            for (int c = 0; c < 3; ++c) {
+                albedo[3 * i + c] *= inv;
+                normal[3 * i + c] *= inv;
+            }
+            depth[3 * i] = hits[i] > 0.0f ? t_sum[i] / hits[i] : 0.0f;
+            depth[3 * i + 1] = hits[i] / (float)gbuffer_samples;
+        }
+        if (spt_host_write_exr((gbuffer_out + "_albedo.exr").c_str(), albedo.data(), width, height) != SPT_OK ||
+            spt_host_write_exr((gbuffer_out + "_normal.exr").c_str(), normal.data(), width, height) != SPT_OK ||
+            spt_host_write_exr((gbuffer_out + "_depth.exr").c_str(), depth.data(), width, height) != SPT_OK)
+            return gbuffer_fail(spt_host_last_error());
+        if (out_path.empty()) {
+            spt_host_scene_free(hs);
+            return 0;
+        }
+    }
     if (film_devices_given) {   // the progressive loop over a multi film: a second implementation of the loop below
         ProgressiveJob o;
         o.hs = hs; o.cam = cam; o.params = params; o.devices = film_devices;

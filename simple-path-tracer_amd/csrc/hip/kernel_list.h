@@ -7,9 +7,11 @@
 // (inst_probe.hip: spt_probe's kernels, probe_kernels.h - k_probe_intake<true>, k_probe_intake<false>, k_probe_intake_stream, k_probe_finish.)
 // (inst_camera.hip: the camera models' k_primary_cam<0|1|2>, camera_kernels.h.  spt_radiance's k_ray_intake<true>, k_ray_intake<false>,
 //  k_ray_intake_stream and k_ray_finish, radiance_kernels.h, are compiled in spt_hip.hip itself.)
+// (inst_gbuffer.hip: spt_gbuffer's k_gbuffer<kTex, kPndf>, gbuffer_kernels.h, the stage behind spt_radiance's intake kernels.)
 // (These four front ends trace and file their first segments with first_segment.h, which the four kernel headers include.)
 #pragma once
 #include "kernels.h"
+#include "gbuffer_kernels.h"
 
 #define SPT_UNPAREN(...) __VA_ARGS__
 #define SPT_DECLARE_KERNEL(NAME, ARGS) extern template __global__ void SPT_UNPAREN NAME ARGS;
@@ -145,6 +147,13 @@
     X((k_shade<5, false, false, false, false, false, true, RayAux>), SPT_ARGS_BOUNCE_AUX)     \
     X((k_shade<5, false, false, false, true, false, true, RayAux>), SPT_ARGS_BOUNCE_AUX)
 
+// k_gbuffer<kTex, kPndf>: first-hit records along caller rays (spt_gbuffer), chosen like k_shade_albedo's instances
+#define SPT_ARGS_GBUFFER (DScene, GBufferJob)
+#define SPT_KERNELS_GBUFFER(X)                                       \
+    X((k_gbuffer<false, false>), SPT_ARGS_GBUFFER)                   \
+    X((k_gbuffer<true, false>), SPT_ARGS_GBUFFER)                    \
+    X((k_gbuffer<true, true>), SPT_ARGS_GBUFFER)
+
 #if defined(SPT_INSTANTIATE_GROUP_PRIMARY)
 SPT_KERNELS_PRIMARY(SPT_DEFINE_KERNEL)
 #elif defined(SPT_INSTANTIATE_GROUP_PRIMARY_CAND)
@@ -181,6 +190,8 @@ SPT_KERNELS_SHADE3X(SPT_DEFINE_KERNEL)
 SPT_KERNELS_SHADE4X(SPT_DEFINE_KERNEL)
 #elif defined(SPT_INSTANTIATE_GROUP_SHADE5X)
 SPT_KERNELS_SHADE5X(SPT_DEFINE_KERNEL)
+#elif defined(SPT_INSTANTIATE_GROUP_GBUFFER)
+SPT_KERNELS_GBUFFER(SPT_DEFINE_KERNEL)
 #else
 SPT_KERNELS_PRIMARY(SPT_DECLARE_KERNEL)
 SPT_KERNELS_PRIMARY_CAND(SPT_DECLARE_KERNEL)
@@ -200,4 +211,5 @@ SPT_KERNELS_SHADE2X(SPT_DECLARE_KERNEL)
 SPT_KERNELS_SHADE3X(SPT_DECLARE_KERNEL)
 SPT_KERNELS_SHADE4X(SPT_DECLARE_KERNEL)
 SPT_KERNELS_SHADE5X(SPT_DECLARE_KERNEL)
+SPT_KERNELS_GBUFFER(SPT_DECLARE_KERNEL)
 #endif

@@ -149,6 +149,7 @@ struct BezierLib {
     decltype(&spt_film_create_camera) film_create_camera = nullptr;   // (the same)
     decltype(&spt_bake) bake = nullptr;                               // (the same)
     decltype(&spt_probe) probe = nullptr;                             // (the same)
+    decltype(&spt_gbuffer) gbuffer = nullptr;                         // (the same)
     decltype(&spt_debug_bxdf) debug_bxdf = nullptr;
     decltype(&spt_debug_render_info) debug_render_info = nullptr;
     decltype(&spt_last_error) last_error = nullptr;
@@ -499,6 +500,7 @@ const BezierLib* bezier_lib() {
         (void)sym(lib.film_create_camera, "spt_film_create_camera");
         (void)sym(lib.bake, "spt_bake");
         (void)sym(lib.probe, "spt_probe");
+        (void)sym(lib.gbuffer, "spt_gbuffer");
         if (!all || version() != SPT_ABI_VERSION) {
             err = path + " does not export ABI version " + std::to_string(SPT_ABI_VERSION);
             return;
@@ -3480,6 +3482,26 @@ struct ItemRun {
         HIP_CHECK(hipEventRecord(sc->ev_ray[pass & 1u], st));
     }
 
+    // Host lists of spt_path_ray (spt_radiance, spt_gbuffer): stage() of the n rays from r0 on, checked while they are copied, with
+    // their auxiliary rays (`aux`, or null) behind them
+    void stage_rays(uint64_t pass, uint64_t r0, uint32_t n, const spt_path_ray* rays, const spt_ray_aux* aux) {
+        stage(pass, (size_t)n * sizeof(spt_path_ray), aux ? (size_t)n * sizeof(spt_ray_aux) : 0, [&](char* records, char* aux_records) {
+            spt_path_ray* const dst = reinterpret_cast<spt_path_ray*>(records);
+            const spt_path_ray* const src = rays + r0;
+            for (uint32_t i = 0; i < n; ++i) {
+                const spt_path_ray& r = src[i];
+                const bool finite = std::isfinite(r.o[0]) && std::isfinite(r.o[1]) && std::isfinite(r.o[2]) && std::isfinite(r.d[0]) &&
+                                    std::isfinite(r.d[1]) && std::isfinite(r.d[2]) && std::isfinite(r.t_min);
+                if (!finite || (r.d[0] == 0.0f && r.d[1] == 0.0f && r.d[2] == 0.0f)) {
+                    HIP_CHECK(hipStreamSynchronize(st));   // the earlier passes wrote the library's own buffers only
+                    fail(SPT_ERR_INVALID_ARG, std::string(who) + ": ray " + std::to_string(r0 + i) + (finite ? " has an all-zero direction" : " has a non-finite o, d or t_min"));
+                }
+                dst[i] = r;
+            }
+            if (aux) std::memcpy(aux_records, aux + r0, (size_t)n * sizeof(spt_ray_aux));
+        });
+    }
+
     // one of an entry's three intake kernels over the n items of the pass, behind the zeroing of the queue counters
     template <class Job>
     void launch_intake(void (*lds)(DScene, RenderCtx, Job), void (*mem)(DScene, RenderCtx, Job), void (*streaming)(DScene, RenderCtx, Job), const Job& job) {
@@ -3569,21 +3591,7 @@ spt_status spt_radiance(const spt_scene* scene_c, const spt_radiance_job* job) {
             rj.rays = reinterpret_cast<const float4*>(job->rays + r0);
             const float4* aux_dev = use_aux ? reinterpret_cast<const float4*>(job->aux + r0) : nullptr;
             if (!dev) {   // the host checks the rays while it copies them
-                ir.stage(pass, (size_t)rj.n * sizeof(spt_path_ray), use_aux ? (size_t)rj.n * sizeof(spt_ray_aux) : 0, [&](char* rays, char* aux) {
-                    spt_path_ray* const dst = reinterpret_cast<spt_path_ray*>(rays);
-                    const spt_path_ray* const src = job->rays + r0;
-                    for (uint32_t i = 0; i < rj.n; ++i) {
-                        const spt_path_ray& r = src[i];
-                        const bool finite = std::isfinite(r.o[0]) && std::isfinite(r.o[1]) && std::isfinite(r.o[2]) && std::isfinite(r.d[0]) &&
-                                            std::isfinite(r.d[1]) && std::isfinite(r.d[2]) && std::isfinite(r.t_min);
-                        if (!finite || (r.d[0] == 0.0f && r.d[1] == 0.0f && r.d[2] == 0.0f)) {
-                            HIP_CHECK(hipStreamSynchronize(ir.st));   // the earlier passes wrote the library's own buffers only
-                            fail(SPT_ERR_INVALID_ARG, "radiance: ray " + std::to_string(r0 + i) + (finite ? " has an all-zero direction" : " has a non-finite o, d or t_min"));
-                        }
-                        dst[i] = r;
-                    }
-                    if (use_aux) std::memcpy(aux, job->aux + r0, (size_t)rj.n * sizeof(spt_ray_aux));
-                });
+                ir.stage_rays(pass, r0, rj.n, job->rays, use_aux ? job->aux : nullptr);
                 rj.rays = sc->ray_in.as<float4>();
                 if (use_aux) aux_dev = sc->ray_aux_in.as<float4>();
             }
@@ -3599,6 +3607,65 @@ spt_status spt_radiance(const spt_scene* scene_c, const spt_radiance_job* job) {
         }
         if (!dev && want_hits) HIP_CHECK(hipMemcpyAsync(job->hits_out, sc->ray_hits.p, (size_t)n_rays * sizeof(spt_hit), hipMemcpyDeviceToHost, ir.st));
         ir.deliver_out(dev, job->rgb_out, (size_t)n_rays * 3);
+        return SPT_OK;
+    });
+}
+
+// ---- first-hit surface records along caller rays (spt_gbuffer): spt_radiance's intake for the hits, then k_gbuffer (gbuffer_kernels.h) ----
+spt_status spt_gbuffer(const spt_scene* scene_c, const spt_gbuffer_job* job) {
+    if (!scene_c || !job) { g_error = "gbuffer: null argument"; return SPT_ERR_INVALID_ARG; }
+    if (job->size < sizeof(spt_gbuffer_job)) { g_error = "gbuffer: job->size is below sizeof(spt_gbuffer_job)"; return SPT_ERR_INVALID_ARG; }
+    if (job->flags & ~(uint32_t)SPT_GBUFFER_DEVICE_POINTERS) { g_error = "gbuffer: unknown flags"; return SPT_ERR_INVALID_ARG; }
+    if (job->n_rays != 0 && (!job->rays || !job->out)) { g_error = "gbuffer: null rays or out"; return SPT_ERR_INVALID_ARG; }
+    spt_scene* sc = const_cast<spt_scene*>(scene_c);
+    if (sc->fwd) {
+        if (!sc->fwd->gbuffer) { g_error = "gbuffer: libspt_hip_bez.so does not export spt_gbuffer"; return SPT_ERR_UNSUPPORTED; }
+        return forwarded(sc->fwd, sc->fwd->gbuffer(sc->inner, job));
+    }
+    if (job->n_rays == 0) return SPT_OK;
+    std::lock_guard<std::mutex> lock(sc->mu);
+    return guarded("gbuffer", [&] {
+        const uint64_t n_rays = job->n_rays;
+        const bool dev = (job->flags & SPT_GBUFFER_DEVICE_POINTERS) != 0;
+        if (n_rays > (1ull << 40)) fail(SPT_ERR_UNSUPPORTED, "gbuffer: more than 2^40 rays");
+        HIP_CHECK(hipSetDevice(sc->device));
+        if (dev) {   // every check comes before the first allocation, copy or launch
+            const auto check = [&](const void* p, const char* what) { check_device_pointer(sc, "gbuffer", "SPT_GBUFFER_DEVICE_POINTERS", p, what, true); };
+            check(job->rays, "rays");
+            if (job->aux) check(job->aux, "aux");
+            check(job->out, "out");
+        }
+        ItemRun ir(sc, "gbuffer", 0u, 0u, 1u);   // max_depth 0: no path runs, nothing is random; the intake reports the hits
+        const bool use_aux = job->aux != nullptr && sc->textured;   // auxiliary rays are read by the textured instances only
+        ir.cut(n_rays, 1u, job->rays_per_pass, "rays_per_pass", 0u);
+        const uint32_t P = ir.P;
+        sc->ray_hits.ensure((size_t)P * sizeof(spt_hit));   // the hits of a pass, between the two kernels
+        float4* out_dev = reinterpret_cast<float4*>(job->out);
+        if (!dev)
+            out_dev = reinterpret_cast<float4*>(
+                ir.stage_buffers((size_t)P * sizeof(spt_path_ray), use_aux ? (size_t)P * sizeof(spt_ray_aux) : 0, (size_t)n_rays * sizeof(spt_gbuffer_rec)));
+        // the instance, as bounce() chooses k_shade_albedo's
+        const bool pndf = sc->textured && sc->subsurface && sc->has_pndf;
+        void (*const fn)(DScene, GBufferJob) = pndf ? k_gbuffer<true, true> : sc->textured ? k_gbuffer<true, false> : k_gbuffer<false, false>;
+        uint64_t pass = 0;
+        for (uint64_t r0 = 0; r0 < n_rays; r0 += P, ++pass) {
+            RayJob rj{};
+            rj.n = (uint32_t)std::min<uint64_t>(P, n_rays - r0);
+            rj.rays = reinterpret_cast<const float4*>(job->rays + r0);
+            rj.hits_out = sc->ray_hits.as<spt_hit>();
+            const float4* aux_dev = use_aux ? reinterpret_cast<const float4*>(job->aux + r0) : nullptr;
+            if (!dev) {   // the host checks the rays while it copies them
+                ir.stage_rays(pass, r0, rj.n, job->rays, use_aux ? job->aux : nullptr);
+                rj.rays = sc->ray_in.as<float4>();
+                if (use_aux) aux_dev = sc->ray_aux_in.as<float4>();
+            }
+            const GBufferJob gj{rj.rays, rj.hits_out, aux_dev, out_dev + 4u * r0, rj.n};
+            // (one chunk of no samples: chunks() leaves rj.reps == 0, so the intake files no path and writes the hits only)
+            ir.chunks(rj.n, rj.k_first, rj.reps, nullptr,
+                      [&](bool) { ir.launch_intake(k_ray_intake<true>, k_ray_intake<false>, k_ray_intake_stream, rj); },
+                      [&](uint32_t, uint32_t) { hipLaunchKernelGGL(fn, dim3((gj.n + kBlock - 1) / kBlock), dim3(kBlock), 0, ir.st, sc->d, gj); });
+        }
+        ir.deliver_out(dev, reinterpret_cast<float*>(job->out), (size_t)n_rays * (sizeof(spt_gbuffer_rec) / sizeof(float)));
         return SPT_OK;
     });
 }

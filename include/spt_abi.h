@@ -1079,6 +1079,73 @@ typedef struct spt_gbuffer_job {
 } spt_gbuffer_job;
 spt_status spt_gbuffer(const spt_scene* scene, const spt_gbuffer_job* job);
 
+/* ---- visibility along caller rays and at surface points (additive to ABI v14: detect them by symbol) -----------------------------
+ * The any-hit siblings of spt_gbuffer and spt_bake.  All arithmetic is IEEE f32, one rounded operation at a time, in the written
+ * order, no contraction.
+ *
+ * spt_occluded: whether anything lies on the segment (o, t_min, d, t_max) of each caller ray.
+ * Result.  Byte i is word for word what spt_trace_any returns for record i: 1 occluded, 0 not.  With SPT_OCCLUDED_PACKED `out` is
+ *          ceil(n_rays / 64) u64 words instead: ray i is bit i & 63 of word i >> 6, and the bits past n_rays in the last word are 0.
+ *          A result depends on its own record and the scene only: not on its place, its neighbours, rays_per_pass or the cut into
+ *          passes (with PACKED the pass size is rounded up to a multiple of 64).
+ * Pointers.  Host pointers by default: the rays go through spt_radiance's two page-locked staging slots and are checked while they
+ *          are copied.  With SPT_OCCLUDED_DEVICE_POINTERS rays (16-byte aligned) and out (any alignment; PACKED: 8-byte aligned) are
+ *          device memory on the scene's device; device records are not checked.
+ * Refusals write nothing and leave the scene usable.  SPT_ERR_INVALID_ARG: a null scene or job; null rays or out while n_rays > 0;
+ *          size below sizeof(spt_occluded_job); unknown flags; a host ray whose o, d or t_min is not finite, whose d is all zero or
+ *          whose t_max is NaN (the message names the first such index); a device pointer that is not device memory of the scene's
+ *          device or misaligned.  SPT_ERR_UNSUPPORTED: more than 2^40 rays.  n_rays == 0 returns SPT_OK and does nothing.
+ *
+ * spt_ao: cosine-weighted ambient occlusion and the bent normal at the points spt_bake takes.
+ * Points.  spt_bake's: resolved, validated and flipped exactly as there (spt_bake_point_ok / spt_bake_world_ok, spt_bake_resolve,
+ *          SPT_AO_FLIP = SPT_BAKE_FLIP; include/spt_bake.h).
+ * Rays.    For point i and sample k, a = first_point + i (u32 wrap), b = first_sample + k: spt_bake's gather ray, spt_bake_frame then
+ *          spt_bake_sample(seed, a, b, ...) - the same salt, direction and t_min - with t_max = max_distance when that is finite, else
+ *          f32::MAX, judged as spt_trace_any judges (p, t_min, d, t_max).  They are the first segments of the bake with the same
+ *          (seed, first_point, first_sample): spt_host_bake_rays returns them.
+ * Record.  count = the samples that are not occluded; sum = ((0 + d_k1) + d_k2) + ... over those samples in k order, per component;
+ *          open = (float)count * (1.0f / (float)samples): the directions are cosine-distributed, so this is the cosine-weighted
+ *          openness; bent = sum / sqrt((sum.x*sum.x + sum.y*sum.y) + sum.z*sum.z) (spt_cm_normalize) when count > 0 and sum is not
+ *          all zero, else (0, 0, 0).  sum and count let a caller join calls cut by first_sample.
+ *          A record depends on its point, first_point + i and the job's scalars only: not on its neighbours, points_per_pass or
+ *          how the samples are cut into launches.
+ * Invalid. Behind device pointers a point that fails the predicate indexes nothing: its seven float words are 0x7fc00000
+ *          (SPT_BAKE_NAN_BITS), its count is 0xffffffff, and its neighbours are unaffected.  A host list with such a point is
+ *          refused; the message names the first such index.
+ * Pointers, staging, lock and ordering as spt_bake; with SPT_AO_DEVICE_POINTERS points and out are each 16-byte aligned.
+ * Refusals.  SPT_ERR_INVALID_ARG: a null scene or job; null points or out while n_points > 0; size below sizeof(spt_ao_job);
+ *          unknown flags or kind; samples == 0 or > 2^24; max_distance NaN or <= 0; a bad device pointer; an invalid host point.
+ *          SPT_ERR_UNSUPPORTED: more than 2^40 points.  n_points == 0 returns SPT_OK and does nothing.
+ *
+ * Both are synchronous, take the scene's lock, start behind the film stream, read the scene's current records (so they follow
+ * spt_scene_update, spt_scene_deform and spt_scene_deform_vertices), touch no film and none of spt_render's buffers: they need no
+ * path queue and no radiance slot.  Scenes with Bezier patches are forwarded like the other ray entries. */
+enum { SPT_OCCLUDED_DEVICE_POINTERS = 1u, SPT_OCCLUDED_PACKED = 2u };
+typedef struct spt_occluded_job {
+    uint32_t size, flags;             /* sizeof(spt_occluded_job) as the caller was compiled (the struct only grows at its tail); SPT_OCCLUDED_* */
+    uint64_t n_rays;
+    const spt_ray* rays;              /* o, t_min, d, t_max: spt_trace_any's records */
+    void* out;                        /* n_rays u8 (1 occluded, 0 not); PACKED: ceil(n_rays / 64) u64 */
+    uint32_t rays_per_pass, pad;      /* tuning, 0 = default */
+} spt_occluded_job;
+spt_status spt_occluded(const spt_scene* scene, const spt_occluded_job* job);
+
+enum { SPT_AO_DEVICE_POINTERS = 1u, SPT_AO_FLIP = 2u };
+typedef struct spt_ao_rec { float sum[3]; float open; float bent[3]; uint32_t count; } spt_ao_rec;   /* 32 B: two 16-byte words */
+typedef struct spt_ao_job {
+    uint32_t size, flags;             /* sizeof(spt_ao_job) as the caller was compiled (the struct only grows at its tail); SPT_AO_* */
+    uint32_t kind, pad;               /* SPT_BAKE_POINTS_SURFACE / SPT_BAKE_POINTS_WORLD */
+    uint64_t n_points;
+    const void* points;               /* spt_bake_point / spt_bake_world_point */
+    spt_ao_rec* out;                  /* n_points records */
+    uint32_t samples;                 /* S in 1 .. 2^24 */
+    float max_distance;               /* > 0, +inf allowed */
+    uint64_t seed;
+    uint32_t first_point, first_sample;
+    uint32_t points_per_pass, pad1;   /* tuning, 0 = default */
+} spt_ao_job;
+spt_status spt_ao(const spt_scene* scene, const spt_ao_job* job);
+
 /* Page-locked host memory for rgb_mean_out: lets the final device-to-host copy of the film run as one
  * DMA at PCIe rate instead of being staged through the runtime's bounce buffers.  Optional: any host
  * pointer is accepted by spt_render. */

@@ -347,6 +347,40 @@ class BakeJob(C.Structure):
                 ("first_point", C.c_uint32), ("first_sample", C.c_uint32), ("points_per_pass", C.c_uint32), ("pad1", C.c_uint32)]
 
 
+# spt_occluded / spt_ao: visibility along caller rays (spt_ray records) and at bake points; spt_ao_rec (32 B)
+OCCLUDED_DEVICE_POINTERS, OCCLUDED_PACKED = 1, 2
+AO_DEVICE_POINTERS, AO_FLIP = 1, 2
+AO_DTYPE = np.dtype([("sum", "<f4", 3), ("open", "<f4"), ("bent", "<f4", 3), ("count", "<u4")])
+
+
+class OccludedJob(C.Structure):
+    """spt_occluded_job (spt_occluded); `size` is sizeof of the struct."""
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("n_rays", C.c_uint64), ("rays", C.c_void_p), ("out", C.c_void_p),
+                ("rays_per_pass", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class AoJob(C.Structure):
+    """spt_ao_job (spt_ao); `size` is sizeof of the struct."""
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("kind", C.c_uint32), ("pad", C.c_uint32), ("n_points", C.c_uint64),
+                ("points", C.c_void_p), ("out", C.c_void_p), ("samples", C.c_uint32), ("max_distance", C.c_float), ("seed", C.c_uint64),
+                ("first_point", C.c_uint32), ("first_sample", C.c_uint32), ("points_per_pass", C.c_uint32), ("pad1", C.c_uint32)]
+
+
+def pack_occluded(occ) -> np.ndarray:
+    """The words spt_occluded writes with SPT_OCCLUDED_PACKED for the bytes `occ`: ray i is bit i & 63 of word i >> 6, the bits past
+    the last ray are 0."""
+    occ = np.asarray(occ).reshape(-1) != 0
+    padded = np.zeros((occ.shape[0] + 63) // 64 * 64, dtype=np.uint8)
+    padded[:occ.shape[0]] = occ
+    return np.packbits(padded.reshape(-1, 64), axis=1, bitorder="little").view("<u8").reshape(-1)
+
+
+def unpack_occluded(words, n: int) -> np.ndarray:
+    """The n bytes (1 occluded, 0 not) behind the packed words of spt_occluded."""
+    words = np.ascontiguousarray(words).reshape(-1).view("<u8")
+    return np.unpackbits(words.view(np.uint8), bitorder="little")[:n].copy()
+
+
 # spt_probe: spt_probe_point (16 B)
 PROBE_DTYPE = np.dtype([("p", "<f4", 3), ("pad", "<f4")])
 PROBE_DEVICE_POINTERS = 1
@@ -537,6 +571,10 @@ def hip_lib() -> C.CDLL:
             lib.spt_probe.argtypes = [C.c_void_p, C.POINTER(ProbeJob)]
         if hasattr(lib, "spt_gbuffer"):   # (the same)
             lib.spt_gbuffer.argtypes = [C.c_void_p, C.POINTER(GBufferJob)]
+        if hasattr(lib, "spt_occluded"):   # (the same)
+            lib.spt_occluded.argtypes = [C.c_void_p, C.POINTER(OccludedJob)]
+        if hasattr(lib, "spt_ao"):   # (the same)
+            lib.spt_ao.argtypes = [C.c_void_p, C.POINTER(AoJob)]
         if hasattr(lib, "spt_scene_update"):   # (the same)
             lib.spt_scene_update.argtypes = [C.c_void_p, C.POINTER(SceneUpdateDesc)]
         if hasattr(lib, "spt_scene_deform"):   # (the same)
@@ -951,6 +989,57 @@ class DeviceScene:
         out = np.zeros((n, 3), dtype=np.float32)
         job.n_points, job.points, job.rgb_out = n, points.ctypes.data, out.ctypes.data
         _check_hip(lib.spt_bake(self._h, C.byref(job)))
+        return out
+
+    def occluded(self, rays, packed: bool = False, rays_per_pass: int = 0):
+        """spt_occluded: whether anything lies on each caller segment (o, t_min, d, t_max), byte for byte what trace_any returns:
+        uint8 (n,), 1 occluded; with packed=True ceil(n / 64) uint64 words instead, ray i at bit i & 63 of word i >> 6 (see
+        pack_occluded / unpack_occluded).  rays are RAY_DTYPE records, or a contiguous float32 (n, 8) torch tensor on the scene's
+        device holding the same records: then the producer's current stream is synchronised, the library reads and writes device
+        memory and the result is a uint8 tensor, packed an int64 tensor holding the same words."""
+        lib = self._entry("spt_occluded")
+        job = OccludedJob(size=C.sizeof(OccludedJob), flags=OCCLUDED_PACKED if packed else 0, rays_per_pass=rays_per_pass)
+        if type(rays).__module__.split(".")[0] == "torch":
+            import torch
+            self._check_tensor(rays, "rays", (8,))
+            n = rays.shape[0]
+            out = torch.empty(((n + 63) // 64,), dtype=torch.int64, device=rays.device) if packed else torch.empty((n,), dtype=torch.uint8, device=rays.device)
+            self._producer_done(rays)
+            job.flags |= OCCLUDED_DEVICE_POINTERS
+            job.n_rays, job.rays, job.out = n, rays.data_ptr() if n else None, out.data_ptr() if n else None
+            _check_hip(lib.spt_occluded(self._h, C.byref(job)))
+            return out
+        rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE).reshape(-1)
+        n = rays.shape[0]
+        out = np.zeros((n + 63) // 64, dtype=np.uint64) if packed else np.zeros(n, dtype=np.uint8)
+        job.n_rays, job.rays, job.out = n, rays.ctypes.data, out.ctypes.data
+        _check_hip(lib.spt_occluded(self._h, C.byref(job)))
+        return out
+
+    def ambient_occlusion(self, points, samples: int = 16, max_distance: float = float("inf"), seed: int = 1, first_point: int = 0,
+                          first_sample: int = 0, points_per_pass: int = 0, world: bool = False, flip: bool = False):
+        """spt_ao: cosine-weighted ambient occlusion and the bent normal at bake's points, n AO_DTYPE records: `count` of the
+        `samples` gather rays of bake (the same seed, first_point, first_sample) found nothing within max_distance, `sum` adds their
+        directions in sample order, open = count / samples, bent = normalize(sum) or 0.  points as bake takes them; torch tensors give
+        an (n, 8) float32 tensor holding the same 32-byte records, `count` (column 7) read through .view(torch.int32)."""
+        lib = self._entry("spt_ao")
+        job = AoJob(size=C.sizeof(AoJob), flags=AO_FLIP if flip else 0, kind=BAKE_POINTS_WORLD if world else BAKE_POINTS_SURFACE, samples=samples,
+                    max_distance=max_distance, seed=seed, first_point=first_point & 0xffffffff, first_sample=first_sample, points_per_pass=points_per_pass)
+        if type(points).__module__.split(".")[0] == "torch":
+            import torch
+            self._check_tensor(points, "points", (8 if world else 4,))
+            n = points.shape[0]
+            out = torch.empty((n, 8), dtype=torch.float32, device=points.device)
+            self._producer_done(points)
+            job.flags |= AO_DEVICE_POINTERS
+            job.n_points, job.points, job.out = n, points.data_ptr() if n else None, out.data_ptr() if n else None
+            _check_hip(lib.spt_ao(self._h, C.byref(job)))
+            return out
+        points = np.ascontiguousarray(points, dtype=BAKE_WORLD_DTYPE if world else BAKE_POINT_DTYPE).reshape(-1)
+        n = points.shape[0]
+        out = np.zeros(n, dtype=AO_DTYPE)
+        job.n_points, job.points, job.out = n, points.ctypes.data, out.ctypes.data
+        _check_hip(lib.spt_ao(self._h, C.byref(job)))
         return out
 
     def probes(self, points, samples: int = 64, max_depth: int = 8, seed: int = 1, first_point: int = 0, first_sample: int = 0, aux: bool = False,

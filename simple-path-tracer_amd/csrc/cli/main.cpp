@@ -31,6 +31,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -48,6 +49,7 @@ static void usage() {
                  "           [--film-devices a,b,..]   (the progressive options above over several devices)\n"
                  "           [--lens-radius R --focus-distance D | --orthographic H | --panorama]   (a camera model in the scene camera's place)\n"
                  "           [--bake-lightmap INSTANCE --bake-size WxH [--bake-samples N]]   (a float RGB EXR lightmap of a mesh instance: E / pi per texel)\n"
+                 "           [--bake-ao INSTANCE --bake-size WxH [--ao-samples N] [--ao-distance D] [--bent-out bent.exr]]   (a float EXR of the cosine-weighted openness per texel; the bent normals)\n"
                  "           [--bake-probes points.txt [--probe-samples N]]   (SH light probes at the `x y z` of each line: 27 coefficients + 4 visibility numbers per line of -o)\n"
                  "           [--gbuffer-out STEM [--gbuffer-samples N]]   (first-hit images STEM_albedo.exr, STEM_normal.exr, STEM_depth.exr; -o may be left out)\n"
                  "           [--animate frames.json]   (one plain image <out>_NNNN per frame: {\"frames\": [{\"<instance>\": {<transform>}, ..}, ..]})\n");
@@ -242,6 +244,11 @@ int main(int argc, char** argv) {
     // --bake-lightmap INSTANCE --bake-size WxH [--bake-samples N]: spt_bake over the texels of the instance's lightmap
     std::string bake_instance, bake_size;
     uint32_t bake_samples = 16;
+    // --bake-ao INSTANCE --bake-size WxH [--ao-samples N] [--ao-distance D] [--bent-out bent.exr]: spt_ao over the same texels
+    std::string ao_instance, bent_out;
+    uint32_t ao_samples = 16;
+    double ao_distance = std::numeric_limits<double>::infinity();
+    bool ao_option_given = false;
     // --bake-probes points.txt [--probe-samples N]: spt_probe at the points of the file
     std::string probe_path;
     uint32_t probe_samples = 64;
@@ -305,6 +312,10 @@ int main(int argc, char** argv) {
         else if (a == "--bake-lightmap") bake_instance = next();
         else if (a == "--bake-size") bake_size = next();
         else if (a == "--bake-samples") bake_samples = (uint32_t)std::atoi(next());
+        else if (a == "--bake-ao") ao_instance = next();
+        else if (a == "--ao-samples") { ao_samples = (uint32_t)std::atoi(next()); ao_option_given = true; }
+        else if (a == "--ao-distance") { ao_distance = std::atof(next()); ao_option_given = true; }
+        else if (a == "--bent-out") { bent_out = next(); ao_option_given = true; }
         else if (a == "--bake-probes") probe_path = next();
         else if (a == "--probe-samples") probe_samples = (uint32_t)std::atoi(next());
         else if (a == "--gbuffer-out") gbuffer_out = next();
@@ -354,6 +365,29 @@ int main(int argc, char** argv) {
                              "--film-devices, --animate or --guide albedo|both\n");
         return 2;
     }
+    bool progressive = preview_every > 0 || time_limit > 0.0 || !variance_out.empty() || adaptive_on || !samples_out.empty() || denoise || robust;
+    uint32_t bake_w = 0, bake_h = 0;
+    if (ao_option_given && ao_instance.empty()) {
+        std::fprintf(stderr, "Error: --ao-samples, --ao-distance and --bent-out need --bake-ao INSTANCE\n");
+        return 2;
+    }
+    if (!ao_instance.empty()) {
+        unsigned bw = 0, bh = 0;
+        char tail = 0;
+        if (std::sscanf(bake_size.c_str(), "%ux%u%c", &bw, &bh, &tail) != 2 || bw == 0 || bh == 0 || ao_samples == 0 || ao_samples > (1u << 24) || !(ao_distance > 0.0)) {
+            std::fprintf(stderr, "Error: --bake-ao INSTANCE needs --bake-size WxH (and --ao-samples N in 1 .. 2^24, --ao-distance D > 0)\n");
+            return 2;
+        }
+        if (progressive || camera_model || !animate_path.empty() || gpus > 0 || film_devices_given || debug_normal || !bake_instance.empty() || !probe_path.empty() ||
+            !gbuffer_out.empty()) {
+            std::fprintf(stderr, "Error: --bake-ao bakes on one device (--device D): not with a film option (--preview-every, --time-limit, --variance-out, "
+                                 "--adaptive, --samples-out, --denoise, --robust, --film-devices), a camera model, --animate, --debug-normal, --bake-lightmap, "
+                                 "--bake-probes, --gbuffer-out or --gpus / --devices\n");
+            return 2;
+        }
+        bake_w = bw;
+        bake_h = bh;
+    }
     if (gbuffer_samples_given && gbuffer_out.empty()) {
         std::fprintf(stderr, "Error: --gbuffer-samples needs --gbuffer-out STEM\n");
         return 2;
@@ -373,9 +407,7 @@ int main(int argc, char** argv) {
         }
     }
     const uint32_t estimator = robust_estimator == "mon" ? (uint32_t)SPT_ROBUST_MON : (uint32_t)SPT_ROBUST_GMON;
-    bool progressive = preview_every > 0 || time_limit > 0.0 || !variance_out.empty() || adaptive_on || !samples_out.empty() || denoise || robust;
-    uint32_t bake_w = 0, bake_h = 0;
-    if (!bake_instance.empty() || !bake_size.empty()) {
+    if (ao_instance.empty() && (!bake_instance.empty() || !bake_size.empty())) {
         unsigned bw = 0, bh = 0;
         char tail = 0;
         if (bake_instance.empty() || std::sscanf(bake_size.c_str(), "%ux%u%c", &bw, &bh, &tail) != 2 || bw == 0 || bh == 0 || bake_samples == 0) {
@@ -571,6 +603,51 @@ int main(int argc, char** argv) {
         if (std::fclose(of) != 0) return probe_fail("cannot write the output file");
         const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_probe).count();
         std::fprintf(stderr, "Finished, time used: %.3fs (%zu probes, %u samples each)\n", sec, probe_points.size(), probe_samples);
+        spt_host_scene_free(hs);
+        return 0;
+    }
+    if (!ao_instance.empty()) {   // the openness map (and the bent normals): the texels of --bake-lightmap, the seed of --seed; uncovered texels are 0
+        auto ao_fail = [&](const char* what) {
+            std::fprintf(stderr, "Error: %s\n", what);
+            spt_host_scene_free(hs);
+            return 1;
+        };
+        uint64_t n_points = 0;
+        if (spt_host_lightmap_points(hs, ao_instance.c_str(), bake_w, bake_h, nullptr, nullptr, 0, &n_points) != SPT_OK) return ao_fail(spt_host_last_error());
+        std::vector<spt_bake_point> points(n_points);
+        std::vector<uint32_t> texels(n_points);
+        if (n_points && spt_host_lightmap_points(hs, ao_instance.c_str(), bake_w, bake_h, points.data(), texels.data(), n_points, &n_points) != SPT_OK)
+            return ao_fail(spt_host_last_error());
+        std::vector<float> open_map((size_t)bake_w * bake_h * 3, 0.0f), bent_map(bent_out.empty() ? 0 : (size_t)bake_w * bake_h * 3, 0.0f);
+        std::vector<spt_ao_rec> recs(points.size());
+        const auto t_ao = std::chrono::steady_clock::now();
+        if (!points.empty()) {
+            spt_scene* scene = nullptr;
+            if (spt_scene_create(spt_host_scene_desc(hs), device, &scene) != SPT_OK) return ao_fail(spt_last_error());
+            spt_ao_job job;
+            std::memset(&job, 0, sizeof job);
+            job.size = (uint32_t)sizeof job;
+            job.kind = SPT_BAKE_POINTS_SURFACE;
+            job.n_points = points.size();
+            job.points = points.data();
+            job.out = recs.data();
+            job.samples = ao_samples;
+            job.max_distance = (float)ao_distance;
+            job.seed = seed;
+            const spt_status e = spt_ao(scene, &job);
+            const std::string why = e == SPT_OK ? "" : spt_last_error();
+            spt_scene_destroy(scene);
+            if (e != SPT_OK) return ao_fail(why.c_str());
+        }
+        for (size_t k = 0; k < points.size(); ++k)
+            for (int c = 0; c < 3; ++c) {
+                open_map[3 * (size_t)texels[k] + c] = recs[k].open;
+                if (!bent_map.empty()) bent_map[3 * (size_t)texels[k] + c] = recs[k].bent[c];
+            }
+        if (spt_host_write_exr(out_path.c_str(), open_map.data(), bake_w, bake_h) != SPT_OK) return ao_fail(spt_host_last_error());
+        if (!bent_out.empty() && spt_host_write_exr(bent_out.c_str(), bent_map.data(), bake_w, bake_h) != SPT_OK) return ao_fail(spt_host_last_error());
+        const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_ao).count();
+        std::fprintf(stderr, "Finished, time used: %.3fs (%zu of %zu texels covered, %u samples each)\n", sec, points.size(), (size_t)bake_w * bake_h, ao_samples);
         spt_host_scene_free(hs);
         return 0;
     }

@@ -8,6 +8,8 @@
 // (inst_camera.hip: the camera models' k_primary_cam<0|1|2>, camera_kernels.h.  spt_radiance's k_ray_intake<true>, k_ray_intake<false>,
 //  k_ray_intake_stream and k_ray_finish, radiance_kernels.h, are compiled in spt_hip.hip itself.)
 // (inst_gbuffer.hip: spt_gbuffer's k_gbuffer<kTex, kPndf>, gbuffer_kernels.h, the stage behind spt_radiance's intake kernels.)
+// (inst_visibility.hip: spt_occluded's and spt_ao's kernels, visibility_kernels.h - k_occluded<true>, k_occluded<false>, k_occluded_stream,
+//  k_ao<true>, k_ao<false>, k_ao_stream: any-hit walks over first_segment.h's first_any, without a path.)
 // (These four front ends trace and file their first segments with first_segment.h, which the four kernel headers include.)
 #pragma once
 #include "kernels.h"

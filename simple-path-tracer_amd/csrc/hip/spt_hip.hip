@@ -25,6 +25,7 @@
 #include "film_kernels.h"
 #include "radiance_kernels.h"
 #include "bake_kernels.h"
+#include "visibility_kernels.h"   // spt_occluded's and spt_ao's kernels: declared here, compiled in inst_visibility.hip
 #include "probe_kernels.h"
 #include "camera_kernels.h"   // k_primary_cam: declared here, compiled in inst_camera.hip
 #include "deform_kernels.h"   // spt_scene_deform's kernels: declared here, compiled in inst_deform.hip
@@ -150,6 +151,8 @@ struct BezierLib {
     decltype(&spt_bake) bake = nullptr;                               // (the same)
     decltype(&spt_probe) probe = nullptr;                             // (the same)
     decltype(&spt_gbuffer) gbuffer = nullptr;                         // (the same)
+    decltype(&spt_occluded) occluded = nullptr;                       // (the same)
+    decltype(&spt_ao) ao = nullptr;                                   // (the same)
     decltype(&spt_debug_bxdf) debug_bxdf = nullptr;
     decltype(&spt_debug_render_info) debug_render_info = nullptr;
     decltype(&spt_last_error) last_error = nullptr;
@@ -501,6 +504,8 @@ const BezierLib* bezier_lib() {
         (void)sym(lib.bake, "spt_bake");
         (void)sym(lib.probe, "spt_probe");
         (void)sym(lib.gbuffer, "spt_gbuffer");
+        (void)sym(lib.occluded, "spt_occluded");
+        (void)sym(lib.ao, "spt_ao");
         if (!all || version() != SPT_ABI_VERSION) {
             err = path + " does not export ABI version " + std::to_string(SPT_ABI_VERSION);
             return;
@@ -3391,16 +3396,20 @@ static spt_status trace_common(const spt_scene* scene_c, uint32_t n, const spt_r
 // An entry checks its arguments, begins an ItemRun, cuts the job into passes of P items x chunks of R samples, and per pass stages its
 // item records, fills its kernels' job struct and runs the chunks with its intake and finish kernels.
 
-// `p` is device memory on the scene's device, aligned to 16 bytes where `align16` (records loaded as float4), else to 4
-static void check_device_pointer(const spt_scene* sc, const char* who, const char* flag, const void* p, const char* what, bool align16) {
+// `p` is device memory on the scene's device, aligned to `align` bytes (a power of two); below: to 16 bytes where `align16` (records
+// loaded as float4), else to 4
+static void check_device_pointer_aligned(const spt_scene* sc, const char* who, const char* flag, const void* p, const char* what, uint32_t align) {
     hipPointerAttribute_t at;
     std::memset(&at, 0, sizeof at);
     const hipError_t e = hipPointerGetAttributes(&at, p);
     if (e != hipSuccess) (void)hipGetLastError();
     if (e != hipSuccess || at.type != hipMemoryTypeDevice || at.device != sc->device)
         fail(SPT_ERR_INVALID_ARG, std::string(who) + ": " + flag + " and `" + what + "` is not device memory on the scene's device");
-    if ((reinterpret_cast<uintptr_t>(p) & (align16 ? 15u : 3u)) != 0)
-        fail(SPT_ERR_INVALID_ARG, std::string(who) + ": device pointer `" + what + "` is not " + (align16 ? "16" : "4") + "-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(p) & (uintptr_t)(align - 1u)) != 0)
+        fail(SPT_ERR_INVALID_ARG, std::string(who) + ": device pointer `" + what + "` is not " + std::to_string(align) + "-byte aligned");
+}
+static void check_device_pointer(const spt_scene* sc, const char* who, const char* flag, const void* p, const char* what, bool align16) {
+    check_device_pointer_aligned(sc, who, flag, p, what, align16 ? 16u : 4u);
 }
 
 extern "C++" {   // (member templates cannot have C linkage; it stands here, inside the file's extern "C" block, behind deliver and FilmReadOut)
@@ -3670,6 +3679,31 @@ spt_status spt_gbuffer(const spt_scene* scene_c, const spt_gbuffer_job* job) {
     });
 }
 
+// A host list of spt_bake's points (spt_bake, spt_ao) is checked as a whole, so that a refusal has written nothing at all.
+// SURFACE points are checked against the scene's CURRENT tables: the instance records as the device holds them behind the
+// updates queued so far (read back as spt_trace_* read their results back), the meshes' ranges from the creation
+static void check_host_points(spt_scene* sc, const char* who, bool world, const void* points, uint64_t n_points) {
+    const SceneFixed& fx = sc->fixed;
+    std::vector<spt_instance> inst_tab(world ? 0 : fx.n_instances);
+    std::vector<spt_mesh> mesh_tab(fx.n_meshes);
+    for (uint32_t m = 0; m < fx.n_meshes; ++m) mesh_tab[m] = spt_mesh{0u, 0u, fx.mesh_first[m], fx.mesh_tris[m]};
+    if (!inst_tab.empty()) {
+        film_join(sc);
+        HIP_CHECK(hipMemcpyAsync(inst_tab.data(), sc->instances.p, inst_tab.size() * sizeof(spt_instance), hipMemcpyDeviceToHost, sc->stream));
+        HIP_CHECK(hipStreamSynchronize(sc->stream));
+    }
+    const uint32_t n_inst = (uint32_t)inst_tab.size(), n_mesh = fx.n_meshes;
+    const uint32_t* const inst_words = inst_tab.empty() ? nullptr : &inst_tab[0].prim_type;
+    for (uint64_t i = 0; i < n_points; ++i) {
+        const bool ok = world ? spt_bake_world_ok(static_cast<const spt_bake_world_point*>(points) + i)
+                              : spt_bake_point_ok(static_cast<const spt_bake_point*>(points) + i, n_inst, inst_words, (uint32_t)(sizeof(spt_instance) / sizeof(uint32_t)), n_mesh, mesh_tab.data());
+        if (!ok)
+            fail(SPT_ERR_INVALID_ARG, std::string(who) + ": point " + std::to_string(i) +
+                                          (world ? " has a non-finite p or n or an all-zero n"
+                                                 : " does not name a triangle of a mesh instance (instance, prim) or has a non-finite v or w"));
+    }
+}
+
 // ---- irradiance at surface points (spt_bake): the rays are made by the intake kernel (bake_kernels.h) ----
 spt_status spt_bake(const spt_scene* scene_c, const spt_bake_job* job) {
     if (!scene_c || !job) { g_error = "bake: null argument"; return SPT_ERR_INVALID_ARG; }
@@ -3697,28 +3731,8 @@ spt_status spt_bake(const spt_scene* scene_c, const spt_bake_job* job) {
         if (dev) {   // every check comes before the first allocation, copy or launch
             check_device_pointer(sc, "bake", "SPT_BAKE_DEVICE_POINTERS", job->points, "points", true);
             check_device_pointer(sc, "bake", "SPT_BAKE_DEVICE_POINTERS", job->rgb_out, "rgb_out", false);
-        } else {     // ... and a host list is checked as a whole, so that a refusal has written nothing at all
-            // SURFACE points are checked against the scene's CURRENT tables: the instance records as the device holds them behind the
-            // updates queued so far (read back as spt_trace_* read their results back), the meshes' ranges from the creation
-            const SceneFixed& fx = sc->fixed;
-            std::vector<spt_instance> inst_tab(world ? 0 : fx.n_instances);
-            std::vector<spt_mesh> mesh_tab(fx.n_meshes);
-            for (uint32_t m = 0; m < fx.n_meshes; ++m) mesh_tab[m] = spt_mesh{0u, 0u, fx.mesh_first[m], fx.mesh_tris[m]};
-            if (!inst_tab.empty()) {
-                film_join(sc);
-                HIP_CHECK(hipMemcpyAsync(inst_tab.data(), sc->instances.p, inst_tab.size() * sizeof(spt_instance), hipMemcpyDeviceToHost, sc->stream));
-                HIP_CHECK(hipStreamSynchronize(sc->stream));
-            }
-            const uint32_t n_inst = (uint32_t)inst_tab.size(), n_mesh = fx.n_meshes;
-            const uint32_t* const inst_words = inst_tab.empty() ? nullptr : &inst_tab[0].prim_type;
-            for (uint64_t i = 0; i < n_points; ++i) {
-                const bool ok = world ? spt_bake_world_ok(static_cast<const spt_bake_world_point*>(job->points) + i)
-                                      : spt_bake_point_ok(static_cast<const spt_bake_point*>(job->points) + i, n_inst, inst_words, (uint32_t)(sizeof(spt_instance) / sizeof(uint32_t)), n_mesh, mesh_tab.data());
-                if (!ok)
-                    fail(SPT_ERR_INVALID_ARG, "bake: point " + std::to_string(i) +
-                                                  (world ? " has a non-finite p or n or an all-zero n"
-                                                         : " does not name a triangle of a mesh instance (instance, prim) or has a non-finite v or w"));
-            }
+        } else {     // ... and a host list is checked as a whole (check_host_points)
+            check_host_points(sc, "bake", world, job->points, n_points);
         }
         ItemRun ir(sc, "bake", job->max_depth, job->seed, S);
         // max_depth 0: no path runs and out = D; the intake still sums the delta lights
@@ -3752,6 +3766,153 @@ spt_status spt_bake(const spt_scene* scene_c, const spt_bake_job* job) {
                       });
         }
         ir.deliver_out(dev, job->rgb_out, (size_t)n_points * 3);
+        return SPT_OK;
+    });
+}
+
+// ---- visibility along caller rays and at surface points (spt_occluded, spt_ao): any-hit walks, visibility_kernels.h ----
+// Both use an ItemRun for the join with the films, the stream, the staging slots and the delivery, and never cut(): no queue, counter or
+// radiance slot of the render workspace is sized or touched.
+
+// one of an entry's three kernels, chosen as spt_trace_any chooses its walker
+extern "C++" {   // (a template, inside the file's extern "C" block: as ItemRun)
+template <class Job>
+static void launch_visibility(spt_scene* sc, hipStream_t st, void (*lds)(DScene, Job), void (*mem)(DScene, Job), void (*streaming)(DScene, Job), const Job& job) {
+    const bool stream = sc->swalk && !sc->lds_geo;
+    hipLaunchKernelGGL(stream ? streaming : sc->lds_geo ? lds : mem, dim3((job.n + kBlock - 1) / kBlock), dim3(kBlock), sc->lds_bytes, st, sc->d, job);
+    HIP_CHECK(hipGetLastError());
+}
+}
+
+spt_status spt_occluded(const spt_scene* scene_c, const spt_occluded_job* job) {
+    if (!scene_c || !job) { g_error = "occluded: null argument"; return SPT_ERR_INVALID_ARG; }
+    if (job->size < sizeof(spt_occluded_job)) { g_error = "occluded: job->size is below sizeof(spt_occluded_job)"; return SPT_ERR_INVALID_ARG; }
+    if (job->flags & ~(uint32_t)(SPT_OCCLUDED_DEVICE_POINTERS | SPT_OCCLUDED_PACKED)) { g_error = "occluded: unknown flags"; return SPT_ERR_INVALID_ARG; }
+    if (job->n_rays != 0 && (!job->rays || !job->out)) { g_error = "occluded: null rays or out"; return SPT_ERR_INVALID_ARG; }
+    spt_scene* sc = const_cast<spt_scene*>(scene_c);
+    if (sc->fwd) {
+        if (!sc->fwd->occluded) { g_error = "occluded: libspt_hip_bez.so does not export spt_occluded"; return SPT_ERR_UNSUPPORTED; }
+        return forwarded(sc->fwd, sc->fwd->occluded(sc->inner, job));
+    }
+    if (job->n_rays == 0) return SPT_OK;
+    std::lock_guard<std::mutex> lock(sc->mu);
+    return guarded("occluded", [&] {
+        const uint64_t n_rays = job->n_rays;
+        const bool dev = (job->flags & SPT_OCCLUDED_DEVICE_POINTERS) != 0;
+        const bool packed = (job->flags & SPT_OCCLUDED_PACKED) != 0;
+        if (n_rays > (1ull << 40)) fail(SPT_ERR_UNSUPPORTED, "occluded: more than 2^40 rays");
+        HIP_CHECK(hipSetDevice(sc->device));
+        if (dev) {   // every check comes before the first allocation, copy or launch
+            check_device_pointer_aligned(sc, "occluded", "SPT_OCCLUDED_DEVICE_POINTERS", job->rays, "rays", 16u);
+            check_device_pointer_aligned(sc, "occluded", "SPT_OCCLUDED_DEVICE_POINTERS", job->out, "out", packed ? 8u : 1u);
+        }
+        ItemRun ir(sc, "occluded", 0u, 0u, 1u);
+        // Passes of 2^20 rays by default where they are staged (the host fills one slot beside the copy and the walk of the other), of 2^30
+        // behind device pointers: every launch ends in a tail of its longest walks, and nothing is gained by cutting (16 launches of 2^20
+        // rays took 11.4 ms on the million-triangle grid where one launch takes 6.1, profiles/visibility_cost.json).  A PACKED pass begins
+        // at a word of its own
+        uint64_t P64 = std::min<uint64_t>(job->rays_per_pass ? job->rays_per_pass : dev ? (1u << 30) : (1u << 20), n_rays);
+        if (packed) P64 = (P64 + 63u) / 64u * 64u;
+        const uint32_t P = (uint32_t)P64;
+        const size_t out_bytes = packed ? (size_t)((n_rays + 63u) / 64u) * sizeof(uint64_t) : (size_t)n_rays;
+        char* out_dev = static_cast<char*>(job->out);
+        if (!dev) out_dev = reinterpret_cast<char*>(ir.stage_buffers((size_t)P * sizeof(spt_ray), 0, out_bytes));
+        uint64_t pass = 0;
+        for (uint64_t r0 = 0; r0 < n_rays; r0 += P, ++pass) {
+            OccludedJob oj{};
+            oj.n = (uint32_t)std::min<uint64_t>(P, n_rays - r0);
+            oj.packed = packed ? 1u : 0u;
+            oj.rays = reinterpret_cast<const float4*>(job->rays + r0);
+            oj.out = out_dev + (packed ? r0 / 64u * sizeof(uint64_t) : r0);
+            if (!dev) {   // the host checks the rays while it copies them
+                ir.stage(pass, (size_t)oj.n * sizeof(spt_ray), 0, [&](char* records, char*) {
+                    spt_ray* const dst = reinterpret_cast<spt_ray*>(records);
+                    const spt_ray* const src = job->rays + r0;
+                    for (uint32_t i = 0; i < oj.n; ++i) {
+                        const spt_ray& r = src[i];
+                        const bool finite = std::isfinite(r.o[0]) && std::isfinite(r.o[1]) && std::isfinite(r.o[2]) && std::isfinite(r.d[0]) &&
+                                            std::isfinite(r.d[1]) && std::isfinite(r.d[2]) && std::isfinite(r.t_min);
+                        const bool zero = r.d[0] == 0.0f && r.d[1] == 0.0f && r.d[2] == 0.0f;
+                        if (!finite || zero || std::isnan(r.t_max)) {
+                            HIP_CHECK(hipStreamSynchronize(ir.st));   // the earlier passes wrote the library's own buffers only
+                            fail(SPT_ERR_INVALID_ARG, "occluded: ray " + std::to_string(r0 + i) +
+                                                          (!finite ? " has a non-finite o, d or t_min" : zero ? " has an all-zero direction" : " has a NaN t_max"));
+                        }
+                        dst[i] = r;
+                    }
+                });
+                oj.rays = sc->ray_in.as<float4>();
+            }
+            launch_visibility(sc, ir.st, k_occluded<true>, k_occluded<false>, k_occluded_stream, oj);
+        }
+        if (!dev) HIP_CHECK(hipMemcpyAsync(job->out, sc->ray_rgb.p, out_bytes, hipMemcpyDeviceToHost, ir.st));
+        HIP_CHECK(hipStreamSynchronize(ir.st));
+        return SPT_OK;
+    });
+}
+
+spt_status spt_ao(const spt_scene* scene_c, const spt_ao_job* job) {
+    if (!scene_c || !job) { g_error = "ao: null argument"; return SPT_ERR_INVALID_ARG; }
+    if (job->size < sizeof(spt_ao_job)) { g_error = "ao: job->size is below sizeof(spt_ao_job)"; return SPT_ERR_INVALID_ARG; }
+    if (job->flags & ~(uint32_t)(SPT_AO_DEVICE_POINTERS | SPT_AO_FLIP)) { g_error = "ao: unknown flags"; return SPT_ERR_INVALID_ARG; }
+    if (job->kind > SPT_BAKE_POINTS_WORLD) { g_error = "ao: unknown kind of points"; return SPT_ERR_INVALID_ARG; }
+    if (job->samples == 0 || job->samples > (1u << 24)) { g_error = "ao: samples must be in 1 .. 2^24"; return SPT_ERR_INVALID_ARG; }
+    if (!(job->max_distance > 0.0f)) { g_error = "ao: max_distance must be > 0 (+inf: no limit)"; return SPT_ERR_INVALID_ARG; }
+    if (job->n_points != 0 && (!job->points || !job->out)) { g_error = "ao: null points or out"; return SPT_ERR_INVALID_ARG; }
+    spt_scene* sc = const_cast<spt_scene*>(scene_c);
+    if (sc->fwd) {
+        if (!sc->fwd->ao) { g_error = "ao: libspt_hip_bez.so does not export spt_ao"; return SPT_ERR_UNSUPPORTED; }
+        return forwarded(sc->fwd, sc->fwd->ao(sc->inner, job));
+    }
+    if (job->n_points == 0) return SPT_OK;
+    std::lock_guard<std::mutex> lock(sc->mu);
+    return guarded("ao", [&] {
+        const uint64_t n_points = job->n_points;
+        const uint32_t S = job->samples;
+        const bool dev = (job->flags & SPT_AO_DEVICE_POINTERS) != 0;
+        const bool world = job->kind == SPT_BAKE_POINTS_WORLD;
+        const size_t rec_bytes = world ? sizeof(spt_bake_world_point) : sizeof(spt_bake_point);
+        if (n_points > (1ull << 40)) fail(SPT_ERR_UNSUPPORTED, "ao: more than 2^40 points");
+        HIP_CHECK(hipSetDevice(sc->device));
+        if (dev) {   // every check comes before the first allocation, copy or launch
+            check_device_pointer(sc, "ao", "SPT_AO_DEVICE_POINTERS", job->points, "points", true);
+            check_device_pointer(sc, "ao", "SPT_AO_DEVICE_POINTERS", job->out, "out", true);
+        } else {     // ... and a host list is checked as a whole (check_host_points)
+            check_host_points(sc, "ao", world, job->points, n_points);
+        }
+        ItemRun ir(sc, "ao", 0u, job->seed, S);
+        // Passes of 2^20 points by default, and launches of at most R samples: around 2^24 rays each, 16 .. 512 samples.  The chunks
+        // behind the first carry sum and count through the out record (k_ao).
+        const uint32_t P = (uint32_t)std::min<uint64_t>(job->points_per_pass ? job->points_per_pass : (1u << 20), n_points);
+        const uint32_t R = std::min(S, std::max(16u, std::min(512u, (1u << 24) / P)));
+        float4* out_dev = reinterpret_cast<float4*>(job->out);
+        if (!dev) out_dev = reinterpret_cast<float4*>(ir.stage_buffers((size_t)P * rec_bytes, 0, (size_t)n_points * sizeof(spt_ao_rec)));
+        uint64_t pass = 0;
+        for (uint64_t r0 = 0; r0 < n_points; r0 += P, ++pass) {
+            AoJob aj{};
+            aj.seed = job->seed;
+            aj.t_max = std::isfinite(job->max_distance) ? job->max_distance : SPT_F32_MAX;
+            aj.inv = 1.0f / (float)S;
+            aj.n = (uint32_t)std::min<uint64_t>(P, n_points - r0);
+            aj.out = out_dev + 2u * r0;
+            aj.stream_a = job->first_point + (uint32_t)r0;   // (u32 wrap)
+            aj.stream_b = job->first_sample;
+            aj.kind = job->kind;
+            aj.flip = (job->flags & SPT_AO_FLIP) ? 1u : 0u;
+            const char* const src = static_cast<const char*>(job->points) + r0 * rec_bytes;
+            aj.points = reinterpret_cast<const float4*>(src);
+            if (!dev) {
+                ir.stage(pass, (size_t)aj.n * rec_bytes, 0, [&](char* records, char*) { std::memcpy(records, src, (size_t)aj.n * rec_bytes); });
+                aj.points = sc->ray_in.as<float4>();
+            }
+            for (uint32_t k0 = 0; k0 < S; k0 += R) {
+                aj.k_first = k0;
+                aj.reps = std::min(R, S - k0);
+                aj.last = k0 + aj.reps == S ? 1u : 0u;
+                launch_visibility(sc, ir.st, k_ao<true>, k_ao<false>, k_ao_stream, aj);
+            }
+        }
+        ir.deliver_out(dev, reinterpret_cast<float*>(job->out), (size_t)n_points * (sizeof(spt_ao_rec) / sizeof(float)));
         return SPT_OK;
     });
 }

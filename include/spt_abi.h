@@ -1146,6 +1146,69 @@ typedef struct spt_ao_job {
 } spt_ao_job;
 spt_status spt_ao(const spt_scene* scene, const spt_ao_job* job);
 
+/* ---- camera rays and first-hit images made on the device (additive to ABI v14: detect them by symbol) ----------------------------
+ * The rays of a camera model's plan without the host in the loop, and the first-hit images of such a plan.  All arithmetic is IEEE
+ * f32, one rounded operation at a time, in the written order, no contraction.
+ *
+ * spt_camera_rays: the rays spt_host_camera_rays of libspt_host.so makes, made by a kernel.
+ * Result.  rays is [count][height][width] and aux, when given, as many: every word of both is the word
+ *          spt_host_camera_rays(model, plan, first, count, rays, aux) writes - the model's ray ("camera models" above, any type,
+ *          SPT_CAMERA_PERSPECTIVE included) at the plan's pixel offset of plan sample first + k, t_min = 0.0001f, stream_a = the
+ *          pixel index row * width + column, stream_b = the plan index, every padding word +0.  Of the plan it reads what that
+ *          call reads: width, height, spp, sampler, division_x, division_y, seed.  The words do not depend on rays_per_pass.
+ * Scene.   It names the device, the stream and the lock, and is taken as spt_gbuffer takes it; no geometry is read.
+ * Pointers.  Host pointers by default: the rays are made in the shared workspace pass by pass and copied out.  With
+ *          SPT_CAMERA_RAYS_DEVICE_POINTERS rays and aux are device memory on the scene's device, each 16-byte aligned, checked as
+ *          spt_gbuffer checks its pointers.
+ * Refusals write nothing.  SPT_ERR_INVALID_ARG: a null scene or job; size below sizeof(spt_camera_rays_job); unknown flags; null
+ *          rays while count > 0; whatever spt_host_camera_rays refuses - a null plan, a model that fails spt_cm_check, width, height
+ *          or spp of 0, an unknown sampler, first + count > spp, a jittered sampler with a division of 0; a bad device pointer.
+ *          SPT_ERR_UNSUPPORTED: more than 2^40 rays, or an image of more than 2^31 pixels.  count == 0 returns SPT_OK and does
+ *          nothing.
+ *
+ * spt_camera_gbuffer: the first-hit images of the plan samples first .. first + count - 1 of a model.  Per pixel:
+ *          A = N = (+0, +0, +0), T = +0, K = 0;
+ *          for s = first .. first + count - 1, in that order, with r the spt_gbuffer_rec of the ray spt_camera_rays makes for
+ *          (pixel, s) - with its aux record on a scene that samples textures -: A += r.albedo and N += r.n per component (a miss
+ *          adds +0), and on a hit T += r.t and K += 1;
+ *          inv = 1.0f / (float)count;  albedo = A * inv;  normal = N * inv;  depth = K > 0 ? T / (float)K : +0;
+ *          coverage = (float)K / (float)count.
+ *          albedo and normal are [height][width][3], depth and coverage [height][width]; a NULL image is not made.  An image does
+ *          not depend on rays_per_pass or on how the call is cut into passes.
+ * Pointers.  Host pointers by default; with SPT_CAMERA_GBUFFER_DEVICE_POINTERS the images are device memory on the scene's device,
+ *          4-byte aligned.
+ * Refusals write nothing.  SPT_ERR_INVALID_ARG: all four images NULL; count == 0; everything else as spt_camera_rays, likewise
+ *          SPT_ERR_UNSUPPORTED.
+ *
+ * Both are synchronous, take the scene's lock, start behind the film stream and share the render workspace.  spt_camera_gbuffer reads
+ * the scene's current records (so it follows spt_scene_update, spt_scene_deform and spt_scene_deform_vertices) and touches no film.
+ * Scenes with Bezier patches are forwarded like the other ray entries. */
+enum { SPT_CAMERA_RAYS_DEVICE_POINTERS = 1u };
+typedef struct spt_camera_rays_job {
+    uint32_t size, flags;              /* sizeof(spt_camera_rays_job) as the caller was compiled (the struct only grows at its tail); SPT_CAMERA_RAYS_* */
+    const spt_camera_model* model;
+    const spt_render_params* plan;
+    uint32_t first, count;             /* plan samples [first, first + count) */
+    spt_path_ray* rays;                /* [count][height][width] */
+    spt_ray_aux* aux;                  /* NULL, or as many */
+    uint32_t rays_per_pass, pad;       /* tuning, 0 = default */
+} spt_camera_rays_job;
+spt_status spt_camera_rays(const spt_scene* scene, const spt_camera_rays_job* job);
+
+enum { SPT_CAMERA_GBUFFER_DEVICE_POINTERS = 1u };
+typedef struct spt_camera_gbuffer_job {
+    uint32_t size, flags;              /* sizeof(spt_camera_gbuffer_job) as the caller was compiled (the struct only grows at its tail); SPT_CAMERA_GBUFFER_* */
+    const spt_camera_model* model;
+    const spt_render_params* plan;
+    uint32_t first, count;             /* plan samples [first, first + count); count >= 1 */
+    float* albedo;                     /* [height][width][3] or NULL */
+    float* normal;                     /* [height][width][3] or NULL */
+    float* depth;                      /* [height][width] or NULL */
+    float* coverage;                   /* [height][width] or NULL */
+    uint32_t rays_per_pass, pad;       /* tuning, 0 = default */
+} spt_camera_gbuffer_job;
+spt_status spt_camera_gbuffer(const spt_scene* scene, const spt_camera_gbuffer_job* job);
+
 /* Page-locked host memory for rgb_mean_out: lets the final device-to-host copy of the film run as one
  * DMA at PCIe rate instead of being staged through the runtime's bounce buffers.  Optional: any host
  * pointer is accepted by spt_render. */

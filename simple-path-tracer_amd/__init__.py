@@ -333,6 +333,23 @@ class GBufferJob(C.Structure):
                 ("rays_per_pass", C.c_uint32), ("pad", C.c_uint32), ("out", C.c_void_p)]
 
 
+CAMERA_RAYS_DEVICE_POINTERS = 1
+CAMERA_GBUFFER_DEVICE_POINTERS = 1
+
+
+class CameraRaysJob(C.Structure):
+    """spt_camera_rays_job (spt_camera_rays); `size` is sizeof of the struct."""
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("model", C.c_void_p), ("plan", C.c_void_p), ("first", C.c_uint32),
+                ("count", C.c_uint32), ("rays", C.c_void_p), ("aux", C.c_void_p), ("rays_per_pass", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class CameraGBufferJob(C.Structure):
+    """spt_camera_gbuffer_job (spt_camera_gbuffer); `size` is sizeof of the struct."""
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("model", C.c_void_p), ("plan", C.c_void_p), ("first", C.c_uint32),
+                ("count", C.c_uint32), ("albedo", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("coverage", C.c_void_p),
+                ("rays_per_pass", C.c_uint32), ("pad", C.c_uint32)]
+
+
 # spt_bake: spt_bake_point (16 B: spt_hit without t) and spt_bake_world_point (32 B)
 BAKE_POINT_DTYPE = np.dtype([("instance", "<u4"), ("prim", "<u4"), ("v", "<f4"), ("w", "<f4")])
 BAKE_WORLD_DTYPE = np.dtype([("p", "<f4", 3), ("pad0", "<f4"), ("n", "<f4", 3), ("pad1", "<f4")])
@@ -575,6 +592,10 @@ def hip_lib() -> C.CDLL:
             lib.spt_occluded.argtypes = [C.c_void_p, C.POINTER(OccludedJob)]
         if hasattr(lib, "spt_ao"):   # (the same)
             lib.spt_ao.argtypes = [C.c_void_p, C.POINTER(AoJob)]
+        if hasattr(lib, "spt_camera_rays"):   # (the same)
+            lib.spt_camera_rays.argtypes = [C.c_void_p, C.POINTER(CameraRaysJob)]
+        if hasattr(lib, "spt_camera_gbuffer"):   # (the same)
+            lib.spt_camera_gbuffer.argtypes = [C.c_void_p, C.POINTER(CameraGBufferJob)]
         if hasattr(lib, "spt_scene_update"):   # (the same)
             lib.spt_scene_update.argtypes = [C.c_void_p, C.POINTER(SceneUpdateDesc)]
         if hasattr(lib, "spt_scene_deform"):   # (the same)
@@ -962,6 +983,60 @@ class DeviceScene:
         job.n_rays = n
         job.rays, job.aux, job.out = rays.ctypes.data, aux.ctypes.data if aux is not None else None, out.ctypes.data
         _check_hip(lib.spt_gbuffer(self._h, C.byref(job)))
+        return out
+
+    def camera_rays(self, model: "CameraModel", renderer: "PathTracer", width: int, height: int, first: int = 0, count: Optional[int] = None,
+                    aux: bool = False, on_device: bool = False, rays_per_pass: int = 0):
+        """spt_camera_rays: the records of the module's camera_rays, word for word, made by a kernel on the scene's device:
+        (count, height, width) PATH_RAY_DTYPE records, with aux=True (rays, aux) with their RAY_AUX_DTYPE records.  on_device=True:
+        float32 torch tensors on the scene's device instead, (count, height, width, 12) and (count, height, width, 16) holding the
+        same records; reshaped to (n, 12) / (n, 16) they are what radiance and gbuffer take, and the first eight columns with a
+        t_max written into the last of them what occluded takes."""
+        lib = self._entry("spt_camera_rays")
+        if count is None:
+            count = renderer.spp - first
+        p = renderer.params(width, height)
+        job = CameraRaysJob(size=C.sizeof(CameraRaysJob), model=C.addressof(model), plan=C.addressof(p), first=first, count=count, rays_per_pass=rays_per_pass)
+        if on_device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            rays = torch.empty((count, height, width, 12), dtype=torch.float32, device=dev)
+            ax = torch.empty((count, height, width, 16), dtype=torch.float32, device=dev) if aux else None
+            self._producer_done(rays)   # (the allocator may hand out memory that work queued on torch's stream still uses)
+            job.flags = CAMERA_RAYS_DEVICE_POINTERS
+            job.rays, job.aux = rays.data_ptr() if rays.numel() else None, ax.data_ptr() if aux and ax.numel() else None
+        else:
+            rays = np.zeros((count, height, width), dtype=PATH_RAY_DTYPE)
+            ax = np.zeros((count, height, width), dtype=RAY_AUX_DTYPE) if aux else None
+            job.rays, job.aux = rays.ctypes.data, ax.ctypes.data if aux else None
+        _check_hip(lib.spt_camera_rays(self._h, C.byref(job)))
+        return (rays, ax) if aux else rays
+
+    def camera_gbuffer(self, model: "CameraModel", renderer: "PathTracer", width: int, height: int, samples: int = 1, first: int = 0,
+                       on_device: bool = False, rays_per_pass: int = 0) -> dict:
+        """spt_camera_gbuffer: the first-hit images of the plan samples first .. first + samples - 1 of a camera model, made on the
+        device from the rays camera_rays makes: the dict the module's camera_gbuffer returns ("albedo" and "normal" (height, width,
+        3), "depth" and "coverage" (height, width), float32), word for word.  on_device=True: torch tensors on the scene's device."""
+        if samples < 1:
+            raise ValueError("samples must be >= 1")
+        lib = self._entry("spt_camera_gbuffer")
+        p = renderer.params(width, height)
+        job = CameraGBufferJob(size=C.sizeof(CameraGBufferJob), model=C.addressof(model), plan=C.addressof(p), first=first, count=samples,
+                               rays_per_pass=rays_per_pass)
+        shapes = {"albedo": (height, width, 3), "normal": (height, width, 3), "depth": (height, width), "coverage": (height, width)}
+        if on_device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            out = {k: torch.empty(s, dtype=torch.float32, device=dev) for k, s in shapes.items()}
+            self._producer_done(out["albedo"])
+            job.flags = CAMERA_GBUFFER_DEVICE_POINTERS
+            for k, t in out.items():
+                setattr(job, k, t.data_ptr())
+        else:
+            out = {k: np.zeros(s, dtype=np.float32) for k, s in shapes.items()}
+            for k, a in out.items():
+                setattr(job, k, a.ctypes.data)
+        _check_hip(lib.spt_camera_gbuffer(self._h, C.byref(job)))
         return out
 
     def bake(self, points, samples: int = 16, max_depth: int = 8, seed: int = 1, first_point: int = 0, first_sample: int = 0,
@@ -1417,15 +1492,20 @@ def camera_rays(model: "CameraModel", renderer: "PathTracer", width: int, height
     return (rays, ax) if aux else rays
 
 
-def camera_gbuffer(scene, model: "CameraModel", renderer: "PathTracer", width: int, height: int, samples: int = 1, device: int = 0) -> dict:
-    """First-hit images of a camera model: camera_rays(model, renderer, width, height, k, 1, aux=True) through DeviceScene.gbuffer
-    for the plan samples k = 0 .. samples - 1, one at a time.  `scene` is a Scene (its device scene on `device` serves the call) or
-    a DeviceScene.  Returns float32 images: "albedo" and "normal" (height, width, 3), the sums in sample order (a miss adds 0)
-    times 1 / samples; "depth" (height, width), the sum of t over the hit samples divided by their count, 0 without one;
-    "coverage" (height, width), hits / samples."""
+def camera_gbuffer(scene, model: "CameraModel", renderer: "PathTracer", width: int, height: int, samples: int = 1, device: int = 0,
+                   host_rays: bool = False) -> dict:
+    """First-hit images of a camera model for the plan samples k = 0 .. samples - 1.  `scene` is a Scene (its device scene on
+    `device` serves the call) or a DeviceScene.  Returns float32 images: "albedo" and "normal" (height, width, 3), the sums in
+    sample order (a miss adds 0) times 1 / samples; "depth" (height, width), the sum of t over the hit samples divided by their
+    count, 0 without one; "coverage" (height, width), hits / samples.
+    One spt_camera_gbuffer call (DeviceScene.camera_gbuffer) when the library exports it.  Otherwise, and with host_rays=True, the
+    route it replaces, which gives the same words: camera_rays(model, renderer, width, height, k, 1, aux=True) through
+    DeviceScene.gbuffer, one sample at a time, summed on the host."""
     if samples < 1:
         raise ValueError("samples must be >= 1")
     ds = scene if isinstance(scene, DeviceScene) else scene.device_scene(device)
+    if not host_rays and hasattr(hip_lib(), "spt_camera_gbuffer"):
+        return ds.camera_gbuffer(model, renderer, width, height, samples)
     albedo = np.zeros((height, width, 3), dtype=np.float32)
     normal = np.zeros((height, width, 3), dtype=np.float32)
     t_sum = np.zeros((height, width), dtype=np.float32)

@@ -19,8 +19,9 @@
 // --film-devices d0,d1,.. (an index may repeat) runs the same progressive loop over a multi film on those devices (one shard film per
 // device, spt_host_multi_film_*; the denoiser runs once on the gathered image, spt_denoise_image) and writes the same bytes.
 // --gbuffer-out STEM [--gbuffer-samples N] writes the first-hit images of the camera, or of the camera model of the same command line,
-// as float EXR files STEM_albedo.exr, STEM_normal.exr and STEM_depth.exr (R depth, G coverage): spt_gbuffer over spt_host_camera_rays,
-// N plan samples averaged, on one device; -o may then be left out.
+// as float EXR files STEM_albedo.exr, STEM_normal.exr and STEM_depth.exr (R depth, G coverage): one spt_camera_gbuffer call, N plan
+// samples averaged, on one device; -o may then be left out.  --gbuffer-host-rays takes the route that call replaces, spt_gbuffer over
+// spt_host_camera_rays with the sums made here (the same bytes), which also serves when the device library refuses the call as unsupported.
 // A renderer whose box filter reaches neighbouring pixels (ceil(radius - 0.5) >= 1) gets a film that keeps its samples
 // (SPT_FILM_KEEP_SAMPLES): --preview-every, --time-limit and --film-devices work with it, the options that need moments or buckets exit with code 2.
 // A renderer with a weighted filter ("tent", "gaussian", "mitchell") always renders through such a film plus spt_film_filter, the plain
@@ -51,7 +52,7 @@ static void usage() {
                  "           [--bake-lightmap INSTANCE --bake-size WxH [--bake-samples N]]   (a float RGB EXR lightmap of a mesh instance: E / pi per texel)\n"
                  "           [--bake-ao INSTANCE --bake-size WxH [--ao-samples N] [--ao-distance D] [--bent-out bent.exr]]   (a float EXR of the cosine-weighted openness per texel; the bent normals)\n"
                  "           [--bake-probes points.txt [--probe-samples N]]   (SH light probes at the `x y z` of each line: 27 coefficients + 4 visibility numbers per line of -o)\n"
-                 "           [--gbuffer-out STEM [--gbuffer-samples N]]   (first-hit images STEM_albedo.exr, STEM_normal.exr, STEM_depth.exr; -o may be left out)\n"
+                 "           [--gbuffer-out STEM [--gbuffer-samples N] [--gbuffer-host-rays]]   (first-hit images STEM_albedo.exr, STEM_normal.exr, STEM_depth.exr; -o may be left out)\n"
                  "           [--animate frames.json]   (one plain image <out>_NNNN per frame: {\"frames\": [{\"<instance>\": {<transform>}, ..}, ..]})\n");
 }
 
@@ -255,7 +256,7 @@ int main(int argc, char** argv) {
     // --gbuffer-out STEM [--gbuffer-samples N]: spt_gbuffer over the camera's rays
     std::string gbuffer_out;
     uint32_t gbuffer_samples = 1;
-    bool gbuffer_samples_given = false;
+    bool gbuffer_samples_given = false, gbuffer_host_rays = false;
     std::vector<int32_t> device_list;
     std::vector<int32_t> film_devices;
     bool film_devices_given = false, film_devices_ok = true;
@@ -319,6 +320,7 @@ int main(int argc, char** argv) {
         else if (a == "--bake-probes") probe_path = next();
         else if (a == "--probe-samples") probe_samples = (uint32_t)std::atoi(next());
         else if (a == "--gbuffer-out") gbuffer_out = next();
+        else if (a == "--gbuffer-host-rays") { gbuffer_host_rays = true; gbuffer_samples_given = true; }
         else if (a == "--gbuffer-samples") { gbuffer_samples = (uint32_t)std::atoi(next()); gbuffer_samples_given = true; }
         else if (a == "--film-devices") { film_devices_given = true; film_devices_ok = parse_device_list(next(), &film_devices); }
         else { usage(); return 2; }
@@ -389,7 +391,7 @@ int main(int argc, char** argv) {
         bake_h = bh;
     }
     if (gbuffer_samples_given && gbuffer_out.empty()) {
-        std::fprintf(stderr, "Error: --gbuffer-samples needs --gbuffer-out STEM\n");
+        std::fprintf(stderr, "Error: --gbuffer-samples and --gbuffer-host-rays need --gbuffer-out STEM\n");
         return 2;
     }
     if (!gbuffer_out.empty()) {
@@ -720,10 +722,11 @@ int main(int argc, char** argv) {
     params.strip_rows = 16;
     if (debug_normal) params.flags |= SPT_RENDER_DEBUG_NORMAL;
     if (!gbuffer_out.empty()) {
-        // The first-hit images, from a device scene of their own ahead of the render, which then runs as it would without them.  Per
-        // plan sample k the model's rays (spt_host_camera_rays, with their auxiliary rays) go through spt_gbuffer; albedo and normal
-        // are the sums in sample order (a miss adds 0) times 1 / N, depth the sum of t over the hit samples divided by their count
-        // (0 without one), coverage hits / N
+        // The first-hit images, from a device scene of their own ahead of the render, which then runs as it would without them:
+        // spt_camera_gbuffer over the plan samples 0 .. N - 1.  The route it replaces gives the same words: per plan sample k the
+        // model's rays (spt_host_camera_rays, with their auxiliary rays) go through spt_gbuffer; albedo and normal are the sums in
+        // sample order (a miss adds 0) times 1 / N, depth the sum of t over the hit samples divided by their count (0 without one),
+        // coverage hits / N
         auto gbuffer_fail = [&](const char* what) {
             std::fprintf(stderr, "Error: %s\n", what);
             spt_host_scene_free(hs);
@@ -731,13 +734,37 @@ int main(int argc, char** argv) {
         };
         const int32_t gdevice = (film_devices_given && !film_devices.empty()) ? film_devices[0] : (gpus == 1 && !device_list.empty()) ? device_list[0] : gpus == 1 ? 0 : device;
         const size_t n_pix = (size_t)width * height;
-        std::vector<spt_path_ray> rays(n_pix);
-        std::vector<spt_ray_aux> aux(n_pix);
-        std::vector<spt_gbuffer_rec> rec(n_pix);
         std::vector<float> albedo(n_pix * 3, 0.0f), normal(n_pix * 3, 0.0f), depth(n_pix * 3, 0.0f), t_sum(n_pix, 0.0f), hits(n_pix, 0.0f);
         spt_scene* scene = nullptr;
         if (spt_scene_create(spt_host_scene_desc(hs), gdevice, &scene) != SPT_OK) return gbuffer_fail(spt_last_error());
-        for (uint32_t k = 0; k < gbuffer_samples; ++k) {
+        bool on_device = false;
+        if (!gbuffer_host_rays) {
+            spt_camera_gbuffer_job job;
+            std::memset(&job, 0, sizeof job);
+            job.size = (uint32_t)sizeof job;
+            job.model = &model;
+            job.plan = &params;
+            job.count = gbuffer_samples;
+            job.albedo = albedo.data();
+            job.normal = normal.data();
+            job.depth = t_sum.data();
+            job.coverage = hits.data();
+            const spt_status st = spt_camera_gbuffer(scene, &job);
+            if (st != SPT_OK && st != SPT_ERR_UNSUPPORTED) {
+                const std::string why = spt_last_error();
+                spt_scene_destroy(scene);
+                return gbuffer_fail(why.c_str());
+            }
+            on_device = st == SPT_OK;
+            for (size_t i = 0; on_device && i < n_pix; ++i) {
+                depth[3 * i] = t_sum[i];
+                depth[3 * i + 1] = hits[i];
+            }
+        }
+        std::vector<spt_path_ray> rays(on_device ? 0 : n_pix);
+        std::vector<spt_ray_aux> aux(on_device ? 0 : n_pix);
+        std::vector<spt_gbuffer_rec> rec(on_device ? 0 : n_pix);
+        for (uint32_t k = 0; !on_device && k < gbuffer_samples; ++k) {
             if (spt_host_camera_rays(&model, &params, k, 1, rays.data(), aux.data()) != SPT_OK) {
                 spt_scene_destroy(scene);
                 return gbuffer_fail(spt_host_last_error());
@@ -768,7 +795,7 @@ int main(int argc, char** argv) {
         }
         spt_scene_destroy(scene);
         const float inv = 1.0f / (float)gbuffer_samples;
-        for (size_t i = 0; i < n_pix; ++i) {
+        for (size_t i = 0; !on_device && i < n_pix; ++i) {
             for (int c = 0; c < 3; ++c) {
                 albedo[3 * i + c] *= inv;
                 normal[3 * i + c] *= inv;

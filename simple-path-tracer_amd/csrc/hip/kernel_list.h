@@ -10,6 +10,8 @@
 // (inst_gbuffer.hip: spt_gbuffer's k_gbuffer<kTex, kPndf>, gbuffer_kernels.h, the stage behind spt_radiance's intake kernels.)
 // (inst_visibility.hip: spt_occluded's and spt_ao's kernels, visibility_kernels.h - k_occluded<true>, k_occluded<false>, k_occluded_stream,
 //  k_ao<true>, k_ao<false>, k_ao_stream: any-hit walks over first_segment.h's first_any, without a path.)
+// (inst_camera_device.hip: spt_camera_rays' and spt_camera_gbuffer's kernels, camera_device_kernels.h - k_camera_rays,
+//  k_gbuffer_image<false, false>, k_gbuffer_image<true, false>, k_gbuffer_image<true, true>, k_gbuffer_image_finish.)
 // (These four front ends trace and file their first segments with first_segment.h, which the four kernel headers include.)
 #pragma once
 #include "kernels.h"

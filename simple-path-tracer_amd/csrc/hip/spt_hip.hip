@@ -28,6 +28,7 @@
 #include "visibility_kernels.h"   // spt_occluded's and spt_ao's kernels: declared here, compiled in inst_visibility.hip
 #include "probe_kernels.h"
 #include "camera_kernels.h"   // k_primary_cam: declared here, compiled in inst_camera.hip
+#include "camera_device_kernels.h"   // spt_camera_rays' and spt_camera_gbuffer's kernels: declared here, compiled in inst_camera_device.hip
 #include "deform_kernels.h"   // spt_scene_deform's kernels: declared here, compiled in inst_deform.hip
 #include "abi_error.h"     // AbiError, fail
 #include "scene_build.h"   // everything a scene derives from its descriptor on the host
@@ -153,6 +154,8 @@ struct BezierLib {
     decltype(&spt_gbuffer) gbuffer = nullptr;                         // (the same)
     decltype(&spt_occluded) occluded = nullptr;                       // (the same)
     decltype(&spt_ao) ao = nullptr;                                   // (the same)
+    decltype(&spt_camera_rays) camera_rays = nullptr;                 // (the same)
+    decltype(&spt_camera_gbuffer) camera_gbuffer = nullptr;           // (the same)
     decltype(&spt_debug_bxdf) debug_bxdf = nullptr;
     decltype(&spt_debug_render_info) debug_render_info = nullptr;
     decltype(&spt_last_error) last_error = nullptr;
@@ -506,6 +509,8 @@ const BezierLib* bezier_lib() {
         (void)sym(lib.gbuffer, "spt_gbuffer");
         (void)sym(lib.occluded, "spt_occluded");
         (void)sym(lib.ao, "spt_ao");
+        (void)sym(lib.camera_rays, "spt_camera_rays");
+        (void)sym(lib.camera_gbuffer, "spt_camera_gbuffer");
         if (!all || version() != SPT_ABI_VERSION) {
             err = path + " does not export ABI version " + std::to_string(SPT_ABI_VERSION);
             return;
@@ -3675,6 +3680,169 @@ spt_status spt_gbuffer(const spt_scene* scene_c, const spt_gbuffer_job* job) {
                       [&](uint32_t, uint32_t) { hipLaunchKernelGGL(fn, dim3((gj.n + kBlock - 1) / kBlock), dim3(kBlock), 0, ir.st, sc->d, gj); });
         }
         ir.deliver_out(dev, reinterpret_cast<float*>(job->out), (size_t)n_rays * (sizeof(spt_gbuffer_rec) / sizeof(float)));
+        return SPT_OK;
+    });
+}
+
+// ---- camera rays and first-hit images made on the device (spt_camera_rays, spt_camera_gbuffer): camera_device_kernels.h ----
+// What spt_host_camera_rays refuses of a model, a plan and a range of its samples, and the sizes the kernels' 32-bit indices bound;
+// returns the job's rays
+static uint64_t check_camera_plan(const char* who, const spt_camera_model* model, const spt_render_params* plan, uint32_t first, uint32_t count) {
+    const std::string w(who);
+    if (!plan) fail(SPT_ERR_INVALID_ARG, w + ": null plan");
+    if (const char* why = spt_cm_check(model)) fail(SPT_ERR_INVALID_ARG, w + ": " + why);
+    const spt_render_params& p = *plan;
+    if (p.width == 0 || p.height == 0 || p.spp == 0 || p.sampler > SPT_SAMPLER_RECURRENCE || (uint64_t)first + count > p.spp)
+        fail(SPT_ERR_INVALID_ARG, w + ": bad plan (width, height, spp > 0, a known sampler) or samples past the plan's spp");
+    if (p.sampler == SPT_SAMPLER_JITTERED && (p.division_x == 0 || p.division_y == 0)) fail(SPT_ERR_INVALID_ARG, w + ": jittered sampler without divisions");
+    const uint64_t n_pix = (uint64_t)p.width * p.height;
+    if (n_pix > (1ull << 31)) fail(SPT_ERR_UNSUPPORTED, w + ": more than 2^31 pixels");
+    if (n_pix * count > (1ull << 40)) fail(SPT_ERR_UNSUPPORTED, w + ": more than 2^40 rays");
+    return n_pix * count;
+}
+
+// k_camera_rays over the n rays of the job from ray r0 on, into `rays` and `aux` (or null)
+static void launch_camera_rays(const RenderCtx& rc, const spt_camera_model& model, uint32_t first, uint64_t r0, uint32_t n, float4* rays, float4* aux,
+                               hipStream_t st) {
+    CamRaysJob cj{};
+    cj.model = model;
+    cj.plan = spt_cm_plan_make(&model, rc.width, rc.height);
+    cj.rays = rays;
+    cj.aux = aux;
+    cj.n = n;
+    cj.p0 = (uint32_t)(r0 % rc.n_pixels);
+    cj.s0 = first + (uint32_t)(r0 / rc.n_pixels);
+    hipLaunchKernelGGL(k_camera_rays, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, rc, cj);
+    HIP_CHECK(hipGetLastError());
+}
+
+spt_status spt_camera_rays(const spt_scene* scene_c, const spt_camera_rays_job* job) {
+    if (!scene_c || !job) { g_error = "camera_rays: null argument"; return SPT_ERR_INVALID_ARG; }
+    if (job->size < sizeof(spt_camera_rays_job)) { g_error = "camera_rays: job->size is below sizeof(spt_camera_rays_job)"; return SPT_ERR_INVALID_ARG; }
+    if (job->flags & ~(uint32_t)SPT_CAMERA_RAYS_DEVICE_POINTERS) { g_error = "camera_rays: unknown flags"; return SPT_ERR_INVALID_ARG; }
+    if (job->count != 0 && !job->rays) { g_error = "camera_rays: null rays"; return SPT_ERR_INVALID_ARG; }
+    spt_scene* sc = const_cast<spt_scene*>(scene_c);
+    if (sc->fwd) {
+        if (!sc->fwd->camera_rays) { g_error = "camera_rays: libspt_hip_bez.so does not export spt_camera_rays"; return SPT_ERR_UNSUPPORTED; }
+        return forwarded(sc->fwd, sc->fwd->camera_rays(sc->inner, job));
+    }
+    std::lock_guard<std::mutex> lock(sc->mu);
+    return guarded("camera_rays", [&] {
+        const uint64_t n_rays = check_camera_plan("camera_rays", job->model, job->plan, job->first, job->count);
+        if (n_rays == 0) return SPT_OK;
+        const bool dev = (job->flags & SPT_CAMERA_RAYS_DEVICE_POINTERS) != 0;
+        HIP_CHECK(hipSetDevice(sc->device));
+        if (dev) {   // every check comes before the first allocation, copy or launch
+            check_device_pointer(sc, "camera_rays", "SPT_CAMERA_RAYS_DEVICE_POINTERS", job->rays, "rays", true);
+            if (job->aux) check_device_pointer(sc, "camera_rays", "SPT_CAMERA_RAYS_DEVICE_POINTERS", job->aux, "aux", true);
+        }
+        film_join(sc);
+        const hipStream_t st = sc->stream;
+        const spt_render_params& p = *job->plan;
+        const RenderCtx rc = plan_ctx(p, job->model->base, 0u, p.height, 0u, 1u, 1u);
+        // passes of around 2^22 rays; below 2^30, so that a pass' pixel indices stay below 2^32 (camera_device_kernels.h)
+        const uint32_t P = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(job->rays_per_pass ? job->rays_per_pass : 1u << 22, 1u << 30), n_rays);
+        if (!dev) {
+            sc->ray_in.ensure((size_t)P * sizeof(spt_path_ray));
+            if (job->aux) sc->ray_aux_in.ensure((size_t)P * sizeof(spt_ray_aux));
+        }
+        for (uint64_t r0 = 0; r0 < n_rays; r0 += P) {
+            const uint32_t n = (uint32_t)std::min<uint64_t>(P, n_rays - r0);
+            float4* const rays_dev = dev ? reinterpret_cast<float4*>(job->rays + r0) : sc->ray_in.as<float4>();
+            float4* const aux_dev = !job->aux ? nullptr : dev ? reinterpret_cast<float4*>(job->aux + r0) : sc->ray_aux_in.as<float4>();
+            launch_camera_rays(rc, *job->model, job->first, r0, n, rays_dev, aux_dev, st);
+            if (!dev) {
+                HIP_CHECK(hipMemcpyAsync(job->rays + r0, rays_dev, (size_t)n * sizeof(spt_path_ray), hipMemcpyDeviceToHost, st));
+                if (job->aux) HIP_CHECK(hipMemcpyAsync(job->aux + r0, aux_dev, (size_t)n * sizeof(spt_ray_aux), hipMemcpyDeviceToHost, st));
+            }
+        }
+        HIP_CHECK(hipStreamSynchronize(st));
+        return SPT_OK;
+    });
+}
+
+// The staged form: per pass k_camera_rays into the workspace, spt_gbuffer's intake for the hits, k_gbuffer_image into the per-pixel
+// sums; k_gbuffer_image_finish behind the last pass
+spt_status spt_camera_gbuffer(const spt_scene* scene_c, const spt_camera_gbuffer_job* job) {
+    if (!scene_c || !job) { g_error = "camera_gbuffer: null argument"; return SPT_ERR_INVALID_ARG; }
+    if (job->size < sizeof(spt_camera_gbuffer_job)) { g_error = "camera_gbuffer: job->size is below sizeof(spt_camera_gbuffer_job)"; return SPT_ERR_INVALID_ARG; }
+    if (job->flags & ~(uint32_t)SPT_CAMERA_GBUFFER_DEVICE_POINTERS) { g_error = "camera_gbuffer: unknown flags"; return SPT_ERR_INVALID_ARG; }
+    if (!job->albedo && !job->normal && !job->depth && !job->coverage) { g_error = "camera_gbuffer: no image is asked for"; return SPT_ERR_INVALID_ARG; }
+    if (job->count == 0) { g_error = "camera_gbuffer: count must be >= 1"; return SPT_ERR_INVALID_ARG; }
+    spt_scene* sc = const_cast<spt_scene*>(scene_c);
+    if (sc->fwd) {
+        if (!sc->fwd->camera_gbuffer) { g_error = "camera_gbuffer: libspt_hip_bez.so does not export spt_camera_gbuffer"; return SPT_ERR_UNSUPPORTED; }
+        return forwarded(sc->fwd, sc->fwd->camera_gbuffer(sc->inner, job));
+    }
+    std::lock_guard<std::mutex> lock(sc->mu);
+    return guarded("camera_gbuffer", [&] {
+        const uint64_t n_rays = check_camera_plan("camera_gbuffer", job->model, job->plan, job->first, job->count);
+        const bool dev = (job->flags & SPT_CAMERA_GBUFFER_DEVICE_POINTERS) != 0;
+        HIP_CHECK(hipSetDevice(sc->device));
+        if (dev) {   // every check comes before the first allocation, copy or launch
+            const auto check = [&](const void* ptr, const char* what) {
+                if (ptr) check_device_pointer(sc, "camera_gbuffer", "SPT_CAMERA_GBUFFER_DEVICE_POINTERS", ptr, what, false);
+            };
+            check(job->albedo, "albedo");
+            check(job->normal, "normal");
+            check(job->depth, "depth");
+            check(job->coverage, "coverage");
+        }
+        const spt_render_params& p = *job->plan;
+        const uint32_t n_pix = p.width * p.height;
+        ItemRun ir(sc, "camera_gbuffer", 0u, 0u, 1u);   // max_depth 0: no path runs, nothing is random; the intake reports the hits
+        const RenderCtx cam_rc = plan_ctx(p, job->model->base, 0u, p.height, 0u, 1u, 1u);
+        ir.cut(n_rays, 1u, job->rays_per_pass, "rays_per_pass", 0u);   // (P < 2^31, as camera_device_kernels.h wants it)
+        const uint32_t P = ir.P;
+        const bool use_aux = sc->textured;   // auxiliary rays are read by the textured instances only
+        sc->ray_in.ensure((size_t)P * sizeof(spt_path_ray));
+        if (use_aux) sc->ray_aux_in.ensure((size_t)P * sizeof(spt_ray_aux));
+        sc->ray_hits.ensure((size_t)P * sizeof(spt_hit));
+        // the sums, 8 words per pixel, and behind them - host pointers - the four images, 8 floats per pixel together
+        const size_t sums_bytes = (size_t)n_pix * 2 * sizeof(float4);
+        sc->ray_rgb.ensure(sums_bytes + (dev ? 0 : (size_t)n_pix * 8 * sizeof(float)));
+        float4* const sums = sc->ray_rgb.as<float4>();
+        HIP_CHECK(hipMemsetAsync(sums, 0, sums_bytes, ir.st));
+        float4* const rays_dev = sc->ray_in.as<float4>();
+        float4* const aux_dev = use_aux ? sc->ray_aux_in.as<float4>() : nullptr;
+        // the instance, as spt_gbuffer chooses k_gbuffer's
+        const bool pndf = sc->textured && sc->subsurface && sc->has_pndf;
+        void (*const fn)(DScene, GBufferImageJob) = pndf ? k_gbuffer_image<true, true> : sc->textured ? k_gbuffer_image<true, false> : k_gbuffer_image<false, false>;
+        for (uint64_t r0 = 0; r0 < n_rays; r0 += P) {
+            RayJob rj{};
+            rj.n = (uint32_t)std::min<uint64_t>(P, n_rays - r0);
+            rj.rays = rays_dev;
+            rj.hits_out = sc->ray_hits.as<spt_hit>();
+            launch_camera_rays(cam_rc, *job->model, job->first, r0, rj.n, rays_dev, aux_dev, ir.st);
+            const GBufferImageJob gj{rays_dev, rj.hits_out, aux_dev, sums, rj.n, (uint32_t)(r0 % n_pix), n_pix};
+            const uint32_t lanes = std::min(gj.n, n_pix);
+            // (one chunk of no samples: chunks() leaves rj.reps == 0, so the intake files no path and writes the hits only)
+            ir.chunks(rj.n, rj.k_first, rj.reps, nullptr,
+                      [&](bool) { ir.launch_intake(k_ray_intake<true>, k_ray_intake<false>, k_ray_intake_stream, rj); },
+                      [&](uint32_t, uint32_t) { hipLaunchKernelGGL(fn, dim3((lanes + kBlock - 1) / kBlock), dim3(kBlock), 0, ir.st, sc->d, gj); });
+        }
+        GBufferImageOut go{};
+        go.sums = sums;
+        go.n_pixels = n_pix;
+        go.count = (float)job->count;
+        go.inv = 1.0f / (float)job->count;
+        float* const images = reinterpret_cast<float*>(sc->ray_rgb.as<char>() + sums_bytes);
+        go.albedo = !job->albedo ? nullptr : dev ? job->albedo : images;
+        go.normal = !job->normal ? nullptr : dev ? job->normal : images + 3 * (size_t)n_pix;
+        go.depth = !job->depth ? nullptr : dev ? job->depth : images + 6 * (size_t)n_pix;
+        go.coverage = !job->coverage ? nullptr : dev ? job->coverage : images + 7 * (size_t)n_pix;
+        hipLaunchKernelGGL(k_gbuffer_image_finish, dim3((n_pix + kBlock - 1) / kBlock), dim3(kBlock), 0, ir.st, go);
+        HIP_CHECK(hipGetLastError());
+        if (!dev) {
+            const auto copy_out = [&](float* to, const float* from, size_t floats) {
+                if (to) HIP_CHECK(hipMemcpyAsync(to, from, floats * sizeof(float), hipMemcpyDeviceToHost, ir.st));
+            };
+            copy_out(job->albedo, go.albedo, 3 * (size_t)n_pix);
+            copy_out(job->normal, go.normal, 3 * (size_t)n_pix);
+            copy_out(job->depth, go.depth, n_pix);
+            copy_out(job->coverage, go.coverage, n_pix);
+        }
+        HIP_CHECK(hipStreamSynchronize(ir.st));
         return SPT_OK;
     });
 }

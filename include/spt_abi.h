@@ -1209,6 +1209,70 @@ typedef struct spt_camera_gbuffer_job {
 } spt_camera_gbuffer_job;
 spt_status spt_camera_gbuffer(const spt_scene* scene, const spt_camera_gbuffer_job* job);
 
+/* ---- all hits along caller rays (additive to ABI v14: detect it by symbol) --------------------------------------------------------
+ * spt_hits returns, per caller segment (o, t_min, d, t_max), the K nearest surfaces the segment crosses and how many it crosses in
+ * all: what lies behind the first hit.  spt_trace_closest / spt_gbuffer answer "which surface first", spt_trace_any / spt_occluded
+ * "any at all"; this is the third standard query, all hits.
+ * Crossing.  A crossing of ray i is a primitive of an instance whose test succeeds with t_min < t && t < t_max.  All arithmetic is
+ *          IEEE f32, one rounded operation at a time, in the written order, no contraction, and is what the closest-hit walk does:
+ *          the ray goes into the instance's object space with `inv` (o as a point, d as a vector, not renormalised, so t is shared
+ *          between the spaces); a triangle is tested as Triangle::intersect_ray tests it on the stored p0, p1 - p0, p2 - p0; a
+ *          sphere gives the two roots mn = (-b - sqrt(delta)) / a and mx = (-b + sqrt(delta)) / a of Sphere::intersect_ray when
+ *          delta >= 0.
+ *          Triangle: (t, v, w) are the words of that test, prim is the absolute triangle index (spt_hit::prim), and
+ *          SPT_HIT_BACKFACING is set iff det = e1 . (d x e2) < 0: the ray leaves through the object-space face e1 x e2.
+ *          Sphere: up to TWO crossings, the root mn (front) and the root mx (SPT_HIT_BACKFACING), each judged on its own; prim is
+ *          the sphere index and v = w = +0.
+ *          Bits 8..15 of flags hold the instance's prim_type, as in spt_gbuffer_rec::flags.
+ * Result.  Record j of ray i (hits[i * max_hits + j]) is its j-th crossing in ascending order of the key (t, instance, prim,
+ *          backfacing).  Records past the last crossing are the miss record: t = f32::MAX, instance = prim = -1, every other word 0.
+ *          Without SPT_HITS_COUNT_ALL counts[i].total is the number of records written (<= max_hits) and `back` counts the
+ *          back-facing ones among them; the walk may cull behind the K-th key.  With SPT_HITS_COUNT_ALL total and back count EVERY
+ *          crossing of the segment, and the records are the same K nearest, word for word.  max_hits == 0 (COUNT_ALL only) gives the
+ *          counters alone; hits may then be null.
+ * Consequences.
+ *          Record 0 is spt_trace_closest's hit for the same spt_ray record, word for word, whenever that call reports a hit.  The one
+ *          exception is a sphere root exactly equal to t_min: the closest-hit rule t = (mn < t_min) ? mx : mn; t_min < t loses the far
+ *          root when mn == t_min, and this call reports it.
+ *          On a scene without spheres, total > 0 under COUNT_ALL is spt_trace_any's byte.  For spheres it is not: spt_trace_any
+ *          calls a segment that lies inside a sphere occluded (mn < t_max && mx > t_min), and this call reports no crossing there.
+ *          A ray through an edge shared by two triangles crosses both: both records appear, with equal t, ordered by prim.
+ *          back > total - back under COUNT_ALL along any ray from a point says the point is enclosed, for closed meshes whose faces
+ *          point outward and for spheres.
+ *          A result depends on its own record and the scene only: not on its place, its neighbours, rays_per_pass or the cut into
+ *          passes; nor on the tree or the order the walk visits it in, since the K nearest are the K smallest keys.
+ * Pointers, staging, checks, lock and ordering as spt_occluded.  Host pointers by default: the rays go through the two page-locked
+ *          staging slots and are checked while they are copied; the results of the whole call are kept on the device and copied out
+ *          behind the last pass.  A staged pass is sized so that its max_hits * 32 + 8 result bytes per ray fit the 32 MiB a default
+ *          slot holds (2^20 rays, fewer as max_hits grows; rays_per_pass overrides it).  With SPT_HITS_DEVICE_POINTERS rays, hits and
+ *          counts are device memory on the scene's device, 16-, 16- and 8-byte aligned, and the records are not checked.
+ *          Synchronous; takes the scene's lock; starts behind the film stream; reads the scene's current records (so it follows
+ *          spt_scene_update, spt_scene_deform and spt_scene_deform_vertices); touches no film and none of spt_render's buffers.
+ * Refusals write nothing and leave the scene usable.  SPT_ERR_INVALID_ARG: a null scene or job; size below sizeof(spt_hits_job);
+ *          unknown flags; max_hits > 64; max_hits == 0 without SPT_HITS_COUNT_ALL; null rays or counts while n_rays > 0; null hits
+ *          while n_rays > 0 and max_hits > 0; a host ray whose o, d or t_min is not finite, whose d is all zero or whose t_max is NaN
+ *          (the message names the first such index); a device pointer that is not device memory of the scene's device or
+ *          misaligned.  SPT_ERR_UNSUPPORTED: more than 2^40 rays; a scene with Bezier-patch instances, Catmull-Clark surfaces
+ *          included - the patch test yields one root by construction, so "all crossings" has no meaning there, and the call is
+ *          not forwarded to libspt_hip_bez.so.  n_rays == 0 returns SPT_OK and does nothing. */
+enum { SPT_HITS_DEVICE_POINTERS = 1u, SPT_HITS_COUNT_ALL = 2u };
+enum { SPT_HIT_BACKFACING = 1u };     /* spt_hit_rec::flags; bits 8..15: the instance's prim_type, as in spt_gbuffer */
+typedef struct spt_hit_rec {          /* 32 B: two 16-byte words */
+    float t; int32_t instance; int32_t prim; uint32_t flags;
+    float v, w; uint32_t pad[2];      /* pad = 0 */
+} spt_hit_rec;
+typedef struct spt_hit_count { uint32_t total, back; } spt_hit_count;
+typedef struct spt_hits_job {
+    uint32_t size, flags;             /* sizeof(spt_hits_job) as the caller was compiled (the struct only grows at its tail); SPT_HITS_* */
+    uint64_t n_rays;
+    const spt_ray* rays;              /* o, t_min, d, t_max */
+    spt_hit_rec* hits;                /* n_rays * max_hits records, ray-major; may be null when max_hits == 0 */
+    spt_hit_count* counts;            /* n_rays */
+    uint32_t max_hits;                /* K in 0 .. 64; 0 only with SPT_HITS_COUNT_ALL */
+    uint32_t rays_per_pass;           /* tuning, 0 = default */
+} spt_hits_job;
+spt_status spt_hits(const spt_scene* scene, const spt_hits_job* job);
+
 /* Page-locked host memory for rgb_mean_out: lets the final device-to-host copy of the film run as one
  * DMA at PCIe rate instead of being staged through the runtime's bounce buffers.  Optional: any host
  * pointer is accepted by spt_render. */

@@ -383,6 +383,19 @@ class AoJob(C.Structure):
                 ("first_point", C.c_uint32), ("first_sample", C.c_uint32), ("points_per_pass", C.c_uint32), ("pad1", C.c_uint32)]
 
 
+# spt_hits: the K nearest crossings of caller segments and the crossing counts; spt_hit_rec (32 B), spt_hit_count (8 B)
+HITS_DEVICE_POINTERS, HITS_COUNT_ALL = 1, 2
+HIT_BACKFACING = 1
+HIT_REC_DTYPE = np.dtype([("t", "<f4"), ("instance", "<i4"), ("prim", "<i4"), ("flags", "<u4"), ("v", "<f4"), ("w", "<f4"), ("pad", "<u4", 2)])
+HIT_COUNT_DTYPE = np.dtype([("total", "<u4"), ("back", "<u4")])
+
+
+class HitsJob(C.Structure):
+    """spt_hits_job (spt_hits); `size` is sizeof of the struct."""
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("n_rays", C.c_uint64), ("rays", C.c_void_p), ("hits", C.c_void_p),
+                ("counts", C.c_void_p), ("max_hits", C.c_uint32), ("rays_per_pass", C.c_uint32)]
+
+
 def pack_occluded(occ) -> np.ndarray:
     """The words spt_occluded writes with SPT_OCCLUDED_PACKED for the bytes `occ`: ray i is bit i & 63 of word i >> 6, the bits past
     the last ray are 0."""
@@ -590,6 +603,8 @@ def hip_lib() -> C.CDLL:
             lib.spt_gbuffer.argtypes = [C.c_void_p, C.POINTER(GBufferJob)]
         if hasattr(lib, "spt_occluded"):   # (the same)
             lib.spt_occluded.argtypes = [C.c_void_p, C.POINTER(OccludedJob)]
+        if hasattr(lib, "spt_hits"):   # (the same)
+            lib.spt_hits.argtypes = [C.c_void_p, C.POINTER(HitsJob)]
         if hasattr(lib, "spt_ao"):   # (the same)
             lib.spt_ao.argtypes = [C.c_void_p, C.POINTER(AoJob)]
         if hasattr(lib, "spt_camera_rays"):   # (the same)
@@ -1090,6 +1105,56 @@ class DeviceScene:
         job.n_rays, job.rays, job.out = n, rays.ctypes.data, out.ctypes.data
         _check_hip(lib.spt_occluded(self._h, C.byref(job)))
         return out
+
+    def all_hits(self, rays, max_hits: int = 4, count_all: bool = False, rays_per_pass: int = 0):
+        """spt_hits: what each caller segment (o, t_min, d, t_max) crosses, nearest first: (records, counts), an (n, max_hits) array of
+        HIT_REC_DTYPE (t, instance, prim, flags, v, w; flags & HIT_BACKFACING: the ray leaves through the face, or the far root of a
+        sphere; bits 8..15 the primitive type; past the last crossing t = f32::MAX, instance = prim = -1) in ascending order of (t,
+        instance, prim, backfacing), and n HIT_COUNT_DTYPE (total, back): the records written and the back-facing ones among them, or
+        with count_all=True EVERY crossing of the segment (the records are the same either way).  A sphere gives up to two crossings,
+        a ray through a shared edge both triangles.  max_hits is 0 .. 64, 0 (counters alone) only with count_all.  Record 0 is what
+        trace_closest returns.  rays are RAY_DTYPE records, or a contiguous float32 (n, 8) torch tensor on the scene's device holding
+        the same records: then the producer's current stream is synchronised, the library reads and writes device memory and the
+        results are an (n, max_hits, 8) float32 tensor holding the 32-byte records (instance, prim and flags read through
+        .view(torch.int32)) and an (n, 2) int32 tensor.  Scenes with Bezier patches are refused."""
+        lib = self._entry("spt_hits")
+        job = HitsJob(size=C.sizeof(HitsJob), flags=HITS_COUNT_ALL if count_all else 0, max_hits=max_hits, rays_per_pass=rays_per_pass)
+        k = max(0, min(int(max_hits), 64))   # (the shape of the buffers only: the library judges max_hits itself)
+        if type(rays).__module__.split(".")[0] == "torch":
+            import torch
+            self._check_tensor(rays, "rays", (8,))
+            n = rays.shape[0]
+            recs = torch.empty((n, k, 8), dtype=torch.float32, device=rays.device)
+            counts = torch.empty((n, 2), dtype=torch.int32, device=rays.device)
+            self._producer_done(rays)
+            job.flags |= HITS_DEVICE_POINTERS
+            job.n_rays, job.rays, job.counts = n, rays.data_ptr() if n else None, counts.data_ptr() if n else None
+            job.hits = recs.data_ptr() if n and k else None
+            _check_hip(lib.spt_hits(self._h, C.byref(job)))
+            return recs, counts
+        rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE).reshape(-1)
+        n = rays.shape[0]
+        recs = np.zeros((n, k), dtype=HIT_REC_DTYPE)
+        counts = np.zeros(n, dtype=HIT_COUNT_DTYPE)
+        job.n_rays, job.rays, job.counts = n, rays.ctypes.data, counts.ctypes.data
+        job.hits = recs.ctypes.data if n and k else None
+        _check_hip(lib.spt_hits(self._h, C.byref(job)))
+        return recs, counts
+
+    def enclosed(self, points, direction=(0.0, 0.0, 1.0)) -> np.ndarray:
+        """Whether each of the (n, 3) points lies inside the scene's geometry: one all_hits call that counts every crossing of the ray
+        from the point along `direction` (max_hits=0, count_all=True) and answers back > total - back, more crossings that leave a
+        surface than enter one.  Valid for closed meshes whose faces point outward and for spheres; open or inward-facing meshes give
+        no meaningful answer.  bool (n,)."""
+        points = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        rays = np.zeros(points.shape[0], dtype=RAY_DTYPE)
+        rays["o"] = points
+        rays["d"] = np.asarray(direction, dtype=np.float32)
+        rays["t_min"] = 0.0
+        rays["t_max"] = np.finfo(np.float32).max
+        _, counts = self.all_hits(rays, max_hits=0, count_all=True)
+        total, back = counts["total"].astype(np.int64), counts["back"].astype(np.int64)
+        return back > total - back
 
     def ambient_occlusion(self, points, samples: int = 16, max_distance: float = float("inf"), seed: int = 1, first_point: int = 0,
                           first_sample: int = 0, points_per_pass: int = 0, world: bool = False, flip: bool = False):

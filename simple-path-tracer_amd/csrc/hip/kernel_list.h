@@ -12,6 +12,9 @@
 //  k_ao<true>, k_ao<false>, k_ao_stream: any-hit walks over first_segment.h's first_any, without a path.)
 // (inst_camera_device.hip: spt_camera_rays' and spt_camera_gbuffer's kernels, camera_device_kernels.h - k_camera_rays,
 //  k_gbuffer_image<false, false>, k_gbuffer_image<true, false>, k_gbuffer_image<true, true>, k_gbuffer_image_finish.)
+// (inst_hits.hip: spt_hits' kernels, hits_kernels.h - k_hits<true, false>, k_hits<true, true>, k_hits<false, false>, k_hits<false, true>:
+//  the K nearest crossings and the crossing counts, over trace.h's nested walkers with a leaf functor of their own; compiled into
+//  libspt_hip.so only.)
 // (These four front ends trace and file their first segments with first_segment.h, which the four kernel headers include.)
 #pragma once
 #include "kernels.h"

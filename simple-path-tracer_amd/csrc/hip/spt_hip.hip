@@ -26,6 +26,7 @@
 #include "radiance_kernels.h"
 #include "bake_kernels.h"
 #include "visibility_kernels.h"   // spt_occluded's and spt_ao's kernels: declared here, compiled in inst_visibility.hip
+#include "hits_kernels.h"   // spt_hits' kernels: declared here, compiled in inst_hits.hip
 #include "probe_kernels.h"
 #include "camera_kernels.h"   // k_primary_cam: declared here, compiled in inst_camera.hip
 #include "camera_device_kernels.h"   // spt_camera_rays' and spt_camera_gbuffer's kernels: declared here, compiled in inst_camera_device.hip
@@ -4017,6 +4018,97 @@ spt_status spt_occluded(const spt_scene* scene_c, const spt_occluded_job* job) {
         HIP_CHECK(hipStreamSynchronize(ir.st));
         return SPT_OK;
     });
+}
+
+// ---- all hits along caller rays (spt_hits): the K nearest crossings and the crossing counts, hits_kernels.h ----
+// As spt_occluded: an ItemRun without cut(), the two staging slots, one lane per ray.  The results of a host call stay in
+// sc->ray_rgb, [records | counts], until the last pass is done, so a ray refused in a later pass leaves the caller's memory as it was.
+spt_status spt_hits(const spt_scene* scene_c, const spt_hits_job* job) {
+    if (!scene_c || !job) { g_error = "hits: null argument"; return SPT_ERR_INVALID_ARG; }
+    if (job->size < sizeof(spt_hits_job)) { g_error = "hits: job->size is below sizeof(spt_hits_job)"; return SPT_ERR_INVALID_ARG; }
+    if (job->flags & ~(uint32_t)(SPT_HITS_DEVICE_POINTERS | SPT_HITS_COUNT_ALL)) { g_error = "hits: unknown flags"; return SPT_ERR_INVALID_ARG; }
+    if (job->max_hits > 64u) { g_error = "hits: max_hits must be in 0 .. 64"; return SPT_ERR_INVALID_ARG; }
+    if (job->max_hits == 0u && !(job->flags & SPT_HITS_COUNT_ALL)) { g_error = "hits: max_hits == 0 needs SPT_HITS_COUNT_ALL"; return SPT_ERR_INVALID_ARG; }
+    if (job->n_rays != 0 && (!job->rays || !job->counts)) { g_error = "hits: null rays or counts"; return SPT_ERR_INVALID_ARG; }
+    if (job->n_rays != 0 && job->max_hits != 0u && !job->hits) { g_error = "hits: null hits with max_hits > 0"; return SPT_ERR_INVALID_ARG; }
+#if SPT_WITH_BEZIER
+    // (this library serves the scenes with patch instances, and compiles no k_hits)
+    g_error = "hits: scenes with Bezier patches are not supported: the patch test yields one root by construction";
+    return SPT_ERR_UNSUPPORTED;
+#else
+    spt_scene* sc = const_cast<spt_scene*>(scene_c);
+    if (sc->fwd) {   // not forwarded: there is nothing libspt_hip_bez.so could answer
+        g_error = "hits: the scene has Bezier-patch instances (Catmull-Clark surfaces included), which are not supported: the patch test yields one root by construction, "
+                  "so the crossings behind it are not defined";
+        return SPT_ERR_UNSUPPORTED;
+    }
+    if (job->n_rays == 0) return SPT_OK;
+    std::lock_guard<std::mutex> lock(sc->mu);
+    return guarded("hits", [&] {
+        const uint64_t n_rays = job->n_rays;
+        const uint32_t K = job->max_hits;
+        const bool dev = (job->flags & SPT_HITS_DEVICE_POINTERS) != 0;
+        const bool all = (job->flags & SPT_HITS_COUNT_ALL) != 0;
+        if (n_rays > (1ull << 40)) fail(SPT_ERR_UNSUPPORTED, "hits: more than 2^40 rays");
+        HIP_CHECK(hipSetDevice(sc->device));
+        if (dev) {   // every check comes before the first allocation, copy or launch
+            check_device_pointer_aligned(sc, "hits", "SPT_HITS_DEVICE_POINTERS", job->rays, "rays", 16u);
+            if (K) check_device_pointer_aligned(sc, "hits", "SPT_HITS_DEVICE_POINTERS", job->hits, "hits", 16u);
+            check_device_pointer_aligned(sc, "hits", "SPT_HITS_DEVICE_POINTERS", job->counts, "counts", 8u);
+        }
+        ItemRun ir(sc, "hits", 0u, 0u, 1u);
+        // Passes as spt_occluded cuts them: 2^30 rays behind device pointers (a lane's index and its max_hits records stay below
+        // 2^32 and are addressed in 64 bits), and where the rays are staged as many as write the 32 MiB of a default slot, 2^20 at most
+        const size_t per_ray = (size_t)K * sizeof(spt_hit_rec) + sizeof(spt_hit_count);
+        const uint64_t staged = std::max<uint64_t>(1u, std::min<uint64_t>(1u << 20, ((size_t)32 << 20) / per_ray));
+        const uint32_t P = (uint32_t)std::min<uint64_t>(job->rays_per_pass ? job->rays_per_pass : dev ? (1u << 30) : staged, n_rays);
+        const size_t hits_bytes = (size_t)n_rays * K * sizeof(spt_hit_rec), counts_bytes = (size_t)n_rays * sizeof(spt_hit_count);
+        spt_hit_rec* hits_dev = job->hits;
+        spt_hit_count* counts_dev = job->counts;
+        if (!dev) {
+            char* const out = reinterpret_cast<char*>(ir.stage_buffers((size_t)P * sizeof(spt_ray), 0, hits_bytes + counts_bytes));
+            hits_dev = reinterpret_cast<spt_hit_rec*>(out);
+            counts_dev = reinterpret_cast<spt_hit_count*>(out + hits_bytes);   // (a multiple of 32 bytes behind an aligned allocation)
+        }
+        uint64_t pass = 0;
+        for (uint64_t r0 = 0; r0 < n_rays; r0 += P, ++pass) {
+            HitsJob hj{};
+            hj.n = (uint32_t)std::min<uint64_t>(P, n_rays - r0);
+            hj.max_hits = K;
+            hj.rays = reinterpret_cast<const float4*>(job->rays + r0);
+            hj.hits = reinterpret_cast<float4*>(hits_dev + (K ? r0 * K : 0u));
+            hj.counts = reinterpret_cast<uint2*>(counts_dev + r0);
+            if (!dev) {   // the host checks the rays while it copies them
+                ir.stage(pass, (size_t)hj.n * sizeof(spt_ray), 0, [&](char* records, char*) {
+                    spt_ray* const dst = reinterpret_cast<spt_ray*>(records);
+                    const spt_ray* const src = job->rays + r0;
+                    for (uint32_t i = 0; i < hj.n; ++i) {
+                        const spt_ray& r = src[i];
+                        const bool finite = std::isfinite(r.o[0]) && std::isfinite(r.o[1]) && std::isfinite(r.o[2]) && std::isfinite(r.d[0]) &&
+                                            std::isfinite(r.d[1]) && std::isfinite(r.d[2]) && std::isfinite(r.t_min);
+                        const bool zero = r.d[0] == 0.0f && r.d[1] == 0.0f && r.d[2] == 0.0f;
+                        if (!finite || zero || std::isnan(r.t_max)) {
+                            HIP_CHECK(hipStreamSynchronize(ir.st));   // the earlier passes wrote the library's own buffers only
+                            fail(SPT_ERR_INVALID_ARG, "hits: ray " + std::to_string(r0 + i) +
+                                                          (!finite ? " has a non-finite o, d or t_min" : zero ? " has an all-zero direction" : " has a NaN t_max"));
+                        }
+                        dst[i] = r;
+                    }
+                });
+                hj.rays = sc->ray_in.as<float4>();
+            }
+            void (*const kernel)(DScene, HitsJob) = sc->lds_geo ? (all ? k_hits<true, true> : k_hits<true, false>) : (all ? k_hits<false, true> : k_hits<false, false>);
+            hipLaunchKernelGGL(kernel, dim3((hj.n + kBlock - 1) / kBlock), dim3(kBlock), sc->lds_bytes, ir.st, sc->d, hj);
+            HIP_CHECK(hipGetLastError());
+        }
+        if (!dev) {
+            if (K) HIP_CHECK(hipMemcpyAsync(job->hits, hits_dev, hits_bytes, hipMemcpyDeviceToHost, ir.st));
+            HIP_CHECK(hipMemcpyAsync(job->counts, counts_dev, counts_bytes, hipMemcpyDeviceToHost, ir.st));
+        }
+        HIP_CHECK(hipStreamSynchronize(ir.st));
+        return SPT_OK;
+    });
+#endif
 }
 
 spt_status spt_ao(const spt_scene* scene_c, const spt_ao_job* job) {
